@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- BASELINE.json's metric on BASELINE.json's config, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2] [--mode align|train]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2] [--mode align|train] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times exactly K steps and prints one JSON line (`ms_per_step` = the timed region / K);
+`--dump-outputs DIR` writes what the last timed step handed its caller (dump_outputs). Every secondary record below
+(cpu_baseline, kernel_resident_Msamp_s, plain_arithmetic, cfg2_polya, scale_ref, short_reads, train, cfg3, e2e_cli) runs
+only with `--full`.
 
 A "step" is one pass of the hot path over one batch of synthetic reads THROUGH THE DROP-IN BOUNDARY:
 the batch starts in host arrays the caller owns, goes through dyn_batch_align_async (validateInput +
@@ -33,7 +38,7 @@ rank 0 copies them to page-locked host memory: "gather_lands_in": "rank0_pinned_
 reduces the ranks' clocks. RCCL's kernels do not fit beside resident waves: --reserve-cus (8) compute units stay free of
 the resident read queue (`exchange` in the line reports what was observed).
 
-N = 1 also carries: `plain_arithmetic` (strict mode off), `cfg2_polya` (cfg2 with a polyA tail behind the pad: EVERY read runs
+With --full, N = 1 also carries: `plain_arithmetic` (strict mode off), `cfg2_polya` (cfg2 with a polyA tail behind the pad: EVERY read runs
 the certified sweeps, as on real direct-RNA data), `scale_ref` (configs[3]'s per-GPU share on this one GPU: the N = 1 point of
 the scaling curve, the workload every rank runs at N > 1) -- each with its own warm-up, timed region and roofline fraction --
 and `e2e_cli`: the dynamont-resquiggle counterpart itself on a synthetic .pod5 + BAM dataset of 32 768 reads (configs[3]'s
@@ -121,6 +126,13 @@ def parse():
                     help="N > 1: compute units kept free of the resident read queue for RCCL's kernels (dyn_aligner_set_session_mode)")
     ap.add_argument("--mode", default="align", choices=["align", "train"],
                     help="align = the headline metric; train = Baum-Welch statistics pass (config 5 shape, secondary)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary record (cpu_baseline, kernel_resident, plain_arithmetic, cfg2_polya, scale_ref, "
+                         "short_reads, train, cfg3, e2e_cli and its cold legs; the --no-* flags skip single ones). Without it the run "
+                         "sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to the caller as DIR/<name>.npy "
+                         "(float64; a fixed sample of the reads where the whole batch would exceed 64 MB)")
     return ap.parse_args()
 
 
@@ -269,17 +281,22 @@ class Workload:
             model_cache[self.k] = synth.write_model(os.path.join(workdir, f"syn{self.k}.model"), self.k, seed=7, stdev=0.25 if self.k == 5 else 0.15)
         self.model_path = model_cache[self.k]
         _, mean, sd = synth.read_model_file(self.model_path)
-        self.batches = []
-        for j in range(self.n_batches):
+
+        def make(j):
             reads = synth.make_reads(cfg["seed"] + 1000 * rank + 100003 * j, cfg["n_reads"], self.pore, mean, sd, cfg["n_bases"], polya=cfg.get("polya"))
-            sig, sig_off, seqs, seq_off = synth.pack_reads(reads)
-            if args.pinned_inputs:
-                from dynamont_amd._dynamont import pinned_empty
+            return synth.pack_reads(reads) + (len(reads),)
+
+        # every batch has a seed of its own: side by side they come out the same, in half the time (NumPy's sampling and
+        # gathers release the GIL), which a plain run's set-up would otherwise spend
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=min(8, self.n_batches)) as ex:
+            self.batches = list(ex.map(make, range(self.n_batches)))
+        if args.pinned_inputs:
+            from dynamont_amd._dynamont import pinned_empty
+            for j, (sig, *rest) in enumerate(self.batches):
                 ps = pinned_empty(sig.size, np.float64)
                 ps[:] = sig
-                sig = ps
-            self.batches.append((sig, sig_off, seqs, seq_off, len(reads)))
-            del reads
+                self.batches[j] = (ps, *rest)
         self.samples_of = [int(b[1][-1]) for b in self.batches]
 
     @classmethod
@@ -484,6 +501,38 @@ class Exchange:
         self.comm.close()
 
 
+DUMP_BYTES = 60 << 20   # --dump-outputs: at most 64 MB in all
+
+
+def dump_outputs(out_dir: str, res, seq_off, budget: int = DUMP_BYTES) -> dict:
+    """--dump-outputs: the result object of the last timed step, as its caller received it, one float64 DIR/<name>.npy per
+    array. align: per read Z, status, bad_char, n_segments; per segment sequence_positions, signal_positions, probabilities,
+    states of the reads listed in sampled_reads, one after the other -- every read when the batch fits `budget`, otherwise the
+    longest prefix that fits of a permutation seeded with 0, sized by the sequence lengths (inputs: two builds dump the same
+    reads). train: Z, status, bad_char, transitions, trans_counts. Returns {name: bytes}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"Z": res.Z, "status": res.status, "bad_char": res.bad_char}
+    if hasattr(res, "transitions"):
+        arrays.update(transitions=res.transitions, trans_counts=res.trans_counts)
+    else:
+        n, seg_cols = res.n, ("sequence_positions", "signal_positions", "probabilities", "states")
+        bound = np.diff(np.asarray(seq_off, dtype=np.int64))   # a read has at most len(seq) - k + 1 segments
+        order = np.random.default_rng(0).permutation(n)
+        room = budget - 8 * 5 * n
+        take = np.sort(order[:int(np.searchsorted(np.cumsum(bound[order]) * 8 * len(seg_cols), room, side="right"))])
+        first, count = res.seg_offsets[take].astype(np.int64), res.n_segments[take].astype(np.int64)
+        rows = np.repeat(first - (np.cumsum(count) - count), count) + np.arange(int(count.sum()))
+        arrays.update(n_segments=res.n_segments, sampled_reads=take, **{c: getattr(res, c)[rows] for c in seg_cols})
+    sizes = {}
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        sizes[name] = a.nbytes
+    assert sum(sizes.values()) <= budget, sizes
+    return sizes
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -500,7 +549,7 @@ def main():
     wl = Workload.get(workload, rank, args, model_cache, workdir)
 
     cpu_proc = cpu_out = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_cpu_baseline:
         cpu_proc, cpu_out = start_cpu_baseline(args, workload, wl.model_path, workdir)
         # the CPU sample uses every host core: let it finish before timing the GPU
         _, err = cpu_proc.communicate()
@@ -510,7 +559,7 @@ def main():
     # e2e_cli.cold, first leg: the CLI in a fresh child process BEFORE this process touches the GPU -- the device as the bench
     # found it (whatever ran before has long exited: its memory is scrubbed)
     cold_first = None
-    want_e2e = rank == 0 and n_gpus == 1 and args.mode == "align" and not args.no_e2e and "WORLD_SIZE" not in os.environ \
+    want_e2e = rank == 0 and n_gpus == 1 and args.full and args.mode == "align" and not args.no_e2e and "WORLD_SIZE" not in os.environ \
         and not os.environ.get("DYN_BENCH_FORCE_DIST")
     if want_e2e and not args.no_cold:
         try:
@@ -622,6 +671,8 @@ def main():
             al.set_session_mode(False)
             resident_with_exchange = False
     m = measure(al, wl, args, args.steps, args.warmup, 0, args.mode, exch, sync)
+    if args.dump_outputs and rank == 0 and m["last"] is not None:
+        dump_outputs(args.dump_outputs, m["last"], wl.batches[(args.warmup + args.steps - 1) % wl.n_batches][3])
     elapsed = m["elapsed"]
     per_rank_ms = [elapsed * 1e3]
     if use_dist:
@@ -640,7 +691,7 @@ def main():
 
     # ---- secondary: kernels only, inputs resident in HBM, ONE batch in one launch (the round-1 headline) -----------------
     resident = None
-    if (rank == 0 or use_dist) and not args.no_resident:
+    if (rank == 0 or use_dist) and args.full and not args.no_resident:
         sig, sig_off, seqs, seq_off, _n = wl.batches[0]
         with al.batch_packed(sig, sig_off, seqs, seq_off) as b0:
             best = None
@@ -674,7 +725,7 @@ def main():
 
     # ---- what bit-exactness costs: the same steps on the plain arithmetic (strict mode off), outside the headline region
     plain = None
-    if args.mode == "align" and args.strict != "off" and not args.no_plain:
+    if args.mode == "align" and args.full and args.strict != "off" and not args.no_plain:
         plain = side_record(al, wl, min(args.steps, max(6, args.steps // 2)), "off",
                             "the table softplus alone: equal to the reference on every read without a structural tie, and on "
                             "3 397 of the 3 400 tie-bearing reads of tests/golden/g10_ties.npz")
@@ -736,14 +787,14 @@ def main():
             line["per_rank_ms"] = [round(x, 2) for x in per_rank_ms]
         if cpu_out and os.path.exists(cpu_out):
             line["cpu_baseline"] = json.load(open(cpu_out))
-        elif n_gpus == 1 and not args.no_cpu_baseline:
+        elif n_gpus == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = None
         if plain is not None:
             line["plain_arithmetic"] = plain
         assert line["n_gpus"] == args.gpus
 
     # ---- N = 1: the workloads the headline does not show (same clock discipline, each with its own roofline) -------------
-    if n_gpus == 1 and not use_dist and args.mode == "align" and workload == "cfg2" and not args.reads:
+    if n_gpus == 1 and not use_dist and args.full and args.mode == "align" and workload == "cfg2" and not args.reads:
         if not args.no_polya:
             # real direct-RNA reads start with their polyA tail: EVERY read then carries a structural tie and runs the certified
             # sweeps (segment.py:155-158 pads every RNA read; the tail follows the pad) -- the headline's synthetic reads: 26 %
@@ -774,7 +825,7 @@ def main():
     al.close()  # (parks the lattice pool: the next handle takes it over instead of allocating its own)
     if exch is not None:
         exch.close()
-    if rank == 0 and n_gpus == 1 and args.mode == "align" and not args.no_e2e and not use_dist:
+    if rank == 0 and n_gpus == 1 and args.full and args.mode == "align" and not args.no_e2e and not use_dist:
         try:
             strict = {"start": "ties"}.get(args.strict, args.strict)
             big = None
@@ -786,7 +837,7 @@ def main():
                 line["e2e_cli"]["large"] = {k_: big[k_] for k_ in ("value", "unit", "wall_s", "reads", "reads_per_s", "samples", "input", "output", "error_lines")}
         except Exception as e:  # the headline stands on its own
             line.setdefault("e2e_cli", {})["error"] = f"{type(e).__name__}: {e}"
-    if rank == 0 and n_gpus == 1 and not use_dist and args.mode == "align" and workload == "cfg2" and not args.reads and not args.no_cfg3:
+    if rank == 0 and n_gpus == 1 and not use_dist and args.full and args.mode == "align" and workload == "cfg2" and not args.reads and not args.no_cfg3:
         # BASELINE configs[2]: another pore, hence another handle. 4 096 DNA reads of 10 k-100 k samples per batch do not get an
         # arena each (1 024 arenas of the longest read: 550 GB): a PAGED session, posteriors in place (24.125 B per cell)
         try:
@@ -800,7 +851,7 @@ def main():
             Workload.drop("cfg3", rank)
         except Exception as e:  # the headline stands on its own
             line["cfg3"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and n_gpus == 1 and args.mode == "align" and not args.no_e2e and not use_dist and not args.no_cold and line.get("e2e_cli", {}).get("wall_s"):
+    if rank == 0 and n_gpus == 1 and args.full and args.mode == "align" and not args.no_e2e and not use_dist and not args.no_cold and line.get("e2e_cli", {}).get("wall_s"):
         try:
             strict = {"start": "ties"}.get(args.strict, args.strict)
             if True:  # (second leg of e2e_cli.cold)

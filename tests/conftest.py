@@ -1,4 +1,6 @@
+import functools
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -9,6 +11,16 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+@functools.lru_cache(maxsize=None)
+def torch_sees_a_gpu() -> bool:
+    """torch.cuda.is_available(), asked in a CHILD process: PyTorch's wheel bundles its own HIP runtime, and bringing it up
+    in a process that has loaded libdynamont_mi.so (the system one) leaves the library without a device for every later
+    test of the session ("no ROCm-capable device is detected")."""
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"],
+                       capture_output=True, text=True, timeout=300, check=True)
+    return r.stdout.split()[-1] == "True"
 
 
 def pytest_configure(config):

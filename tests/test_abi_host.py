@@ -8,7 +8,7 @@ import re
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN, ROOT, torch_sees_a_gpu
 from dynamont_amd import Aligner, PoreType, pore_type, synth
 from dynamont_amd import _native as N
 from oracle.pyoracle import Oracle
@@ -122,8 +122,7 @@ def test_compute_without_gpu_fails_loudly(models):
         al.align(np.zeros(100), "ACGTACGTAC", True)
     with pytest.raises(RuntimeError, match="no CPU compute path"):
         al.train(np.zeros(100), "ACGTACGTAC")
-    import torch
-    if not torch.cuda.is_available():
+    if not torch_sees_a_gpu():
         with pytest.raises(RuntimeError, match="no CPU compute path"):
             Aligner(models["syn5"], "rna002")
 

@@ -11,7 +11,7 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import golden, model_for
+from conftest import golden, model_for, torch_sees_a_gpu
 from dynamont_amd import synth, zstd_io
 from dynamont_amd.segmentation import segment as seg
 from dynamont_amd.segmentation import train as trn
@@ -462,12 +462,68 @@ def test_bench_contract_without_a_gpu():
     finally:
         sys.argv = old
     assert (a.gpus, a.steps, a.warmup, a.mode, a.strict) == (1, 20, 5, "align", "ties") and a.workload is None
+    assert not a.full and a.dump_outputs is None   # a plain run: the headline line only, nothing written
     for name, (cfgname, _per_batch, _n) in bench.WORKLOADS.items():
         assert cfgname in synth.CONFIGS, name
     assert synth.CONFIGS["cfg2"] == dict(pore="rna004", n_reads=1024, n_bases=2000, seed=2)
     assert bench.KBWD_BYTES_PER_CELL + bench.KFWD_BYTES_PER_CELL == 20.125 and bench.HBM_PEAK_GBPS == 8000.0
-    import torch
-    if not torch.cuda.is_available():
+    if not torch_sees_a_gpu():
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-e2e", "--reads", "4", "--batches", "1"],
                            capture_output=True, text=True, timeout=300)
         assert r.returncode != 0 and "needs a GPU" in (r.stderr + r.stdout) and not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_dump_outputs_sample_and_budget(tmp_path):
+    """bench.py --dump-outputs: the last step's result object as float64 .npy files. A batch that fits the budget is written
+    whole; a larger one as whole reads of a sample chosen from the sequence lengths alone (the same on every run), within
+    the budget. Train results: Z, status and the per-read transitions."""
+    import importlib.util
+
+    from conftest import ROOT
+    from dynamont_amd._dynamont import AlignBatchResult, TrainBatchResult
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    rng = np.random.default_rng(5)
+    n, k = 40, 9
+    lens = rng.integers(20, 200, n)
+    seq_off = np.concatenate(([0], np.cumsum(lens))).astype(np.uint64)
+    cap_of = lens - k + 1
+    res = AlignBatchResult(n, int(cap_of.sum()))
+    res.seg_offsets[:] = np.concatenate(([0], np.cumsum(cap_of)))
+    res.n_segments[:] = cap_of
+    res.n_segments[3], res.status[3], res.bad_char[3] = 0, 4, ord("X")
+    res.Z[:] = rng.standard_normal(n) * 1e4
+    res.sequence_positions[:] = np.arange(res.cap)
+    res.signal_positions[:] = 3 * np.arange(res.cap)
+    res.probabilities[:] = rng.random(res.cap)
+    res.states[:] = ord("M")
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+
+    def check(d, sizes, budget):
+        got = load(d)
+        assert set(got) == set(sizes) and all(a.dtype == np.float64 for a in got.values())
+        assert sum(a.nbytes for a in got.values()) <= budget
+        assert np.array_equal(got["Z"], res.Z) and np.array_equal(got["status"], res.status)
+        assert np.array_equal(got["n_segments"], res.n_segments.astype(np.float64))
+        rows = np.concatenate([np.arange(int(res.seg_offsets[i]), int(res.seg_offsets[i] + res.n_segments[i])) for i in got["sampled_reads"].astype(int)])
+        for c in ("sequence_positions", "signal_positions", "probabilities", "states"):
+            assert np.array_equal(got[c], getattr(res, c)[rows].astype(np.float64)), c
+        return got
+
+    whole = check(tmp_path / "whole", bench.dump_outputs(str(tmp_path / "whole"), res, seq_off), bench.DUMP_BYTES)
+    assert np.array_equal(whole["sampled_reads"], np.arange(n))
+    small = 8 * 5 * n + 8 * 4 * int(lens.sum()) // 3
+    part = check(tmp_path / "part", bench.dump_outputs(str(tmp_path / "part"), res, seq_off, small), small)
+    again = check(tmp_path / "again", bench.dump_outputs(str(tmp_path / "again"), res, seq_off, small), small)
+    assert 0 < len(part["sampled_reads"]) < n and np.array_equal(part["sampled_reads"], again["sampled_reads"])
+
+    tr = TrainBatchResult(n, 0, 4 ** k, False, emissions=False)
+    tr.Z[:], tr.transitions[:], tr.trans_counts[:] = res.Z, rng.random(3 * n), rng.random(2 * n)
+    bench.dump_outputs(str(tmp_path / "train"), tr, seq_off)
+    got = load(tmp_path / "train")
+    assert set(got) == {"Z", "status", "bad_char", "transitions", "trans_counts"}
+    assert np.array_equal(got["transitions"], tr.transitions) and np.array_equal(got["Z"], tr.Z)

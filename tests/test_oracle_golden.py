@@ -111,35 +111,53 @@ def test_g7_train(models):
         assert np.array_equal(res["stdev"][touched], g[p + "stdev"])
 
 
-def test_oracle_against_compiled_reference_when_present(models):
+def _reference_outputs(models, band=400, pore=3):
+    """The compiled reference's outputs: stored in G14 (tests/golden/make_golden_g14.py); where oracle/_ref is built,
+    the live reference as well, each compared with the oracle."""
     from oracle import pyoracle
-    if not pyoracle.reference_available():
-        pytest.skip("oracle/_ref not built here (needs /root/reference)")
+    g = golden("g14_reference_checks.npz")
+    return g, (pyoracle.Reference(models["syn9"], pore, band) if pyoracle.reference_available() else None)
+
+
+def test_oracle_against_compiled_reference_when_present(models):
+    g, ref = _reference_outputs(models)
     _, mean, sd = synth.read_model_file(models["syn9"])
     reads = synth.make_reads(991, 4, "dna_r10_260bps", mean, sd, (60, 500))
+    assert len(reads) == int(g["short_n"])
     orc = Oracle(models["syn9"], 3)
-    ref = pyoracle.Reference(models["syn9"], 3)
-    for rd in reads:
-        a, b = orc.align(rd.signal, rd.sequence, True), ref.align(rd.signal, rd.sequence, True)
-        assert a["Z"] == b["Z"] and np.array_equal(a["probabilities"], b["probabilities"])
-        assert np.array_equal(a["signal_positions"], b["signal_positions"])
-        ta, tb = orc.train(rd.signal, rd.sequence), ref.train(rd.signal, rd.sequence, orc.num_kmers)
-        assert ta["m1"] == tb["m1"] and ta["e2"] == tb["e2"]
-        assert np.array_equal(ta["mean"], tb["mean"]) and np.array_equal(ta["stdev"], tb["stdev"])
+    mean0, sd0 = orc.table()
+    for i, rd in enumerate(reads):
+        p = f"short_r{i}_"
+        assert hashlib.sha256(rd.signal.tobytes()).hexdigest() == str(g[p + "sha"])
+        want_mean, want_sd = mean0.copy(), sd0.copy()
+        want_mean[g[p + "codes"]], want_sd[g[p + "codes"]] = g[p + "mean"], g[p + "stdev"]
+        stored = {"Z": float(g[p + "Z"]), "probabilities": g[p + "prob"], "signal_positions": g[p + "sigpos"].astype(np.uint64)}
+        stored_train = {"m1": float(g[p + "m1"]), "e2": float(g[p + "e2"]), "mean": want_mean, "stdev": want_sd}
+        a, ta = orc.align(rd.signal, rd.sequence, True), orc.train(rd.signal, rd.sequence)
+        for b, tb in [(stored, stored_train)] + ([(ref.align(rd.signal, rd.sequence, True), ref.train(rd.signal, rd.sequence, orc.num_kmers))] if ref else []):
+            assert a["Z"] == b["Z"] and np.array_equal(a["probabilities"], b["probabilities"])
+            assert np.array_equal(a["signal_positions"], b["signal_positions"])
+            assert ta["m1"] == tb["m1"] and ta["e2"] == tb["e2"]
+            assert np.array_equal(ta["mean"], tb["mean"]) and np.array_equal(ta["stdev"], tb["stdev"])
 
 
 @pytest.mark.parametrize("band,dwell", [(400, 0.5), (100, 0.5), (446, 3.0)])
 def test_oracle_against_compiled_reference_dense_long_reads(models, band, dwell):
     """The regime of tests/test_gpu_parity.py::test_dense_reads_moving_window: reads longer than the
     band with 2-3 samples per base (the band window moves in almost every other row)."""
-    from oracle import pyoracle
-    if not pyoracle.reference_available():
-        pytest.skip("oracle/_ref not built here (needs /root/reference)")
+    g, ref = _reference_outputs(models, band, 1)
+    j = [(int(b), float(d)) for b, d in zip(g["dense_band"], g["dense_dwell"])].index((band, dwell))
     _, mean, sd = synth.read_model_file(models["syn9"])
     reads = synth.make_reads(99, 3, "rna004", mean, sd, (band + 30, band + 500), dwell=dwell)
-    orc, ref = Oracle(models["syn9"], 1, band), pyoracle.Reference(models["syn9"], 1, band)
-    for rd in reads:
-        a, b = orc.align(rd.signal, rd.sequence, True), ref.align(rd.signal, rd.sequence, True)
-        assert a["Z"] == b["Z"] and np.array_equal(a["probabilities"], b["probabilities"])
-        assert np.array_equal(a["signal_positions"], b["signal_positions"])
-        assert np.array_equal(a["sequence_positions"], b["sequence_positions"])
+    assert len(reads) == int(g[f"dense{j}_n"])
+    orc = Oracle(models["syn9"], 1, band)
+    for i, rd in enumerate(reads):
+        p = f"dense{j}_r{i}_"
+        assert hashlib.sha256(rd.signal.tobytes()).hexdigest() == str(g[p + "sha"])
+        stored = {"Z": float(g[p + "Z"]), "probabilities": g[p + "prob"], "signal_positions": g[p + "sigpos"].astype(np.uint64),
+                  "sequence_positions": g[p + "seqpos"].astype(np.uint64)}
+        a = orc.align(rd.signal, rd.sequence, True)
+        for b in [stored] + ([ref.align(rd.signal, rd.sequence, True)] if ref else []):
+            assert a["Z"] == b["Z"] and np.array_equal(a["probabilities"], b["probabilities"])
+            assert np.array_equal(a["signal_positions"], b["signal_positions"])
+            assert np.array_equal(a["sequence_positions"], b["sequence_positions"])

@@ -11,7 +11,7 @@ import sysconfig
 import numpy as np
 import pytest
 
-from conftest import ROOT, golden
+from conftest import ROOT, golden, torch_sees_a_gpu
 
 
 @pytest.fixture(scope="module")
@@ -100,8 +100,7 @@ def c_example(tmp_path_factory, native_lib):
 
 
 def test_c_example_builds_and_fails_loudly_without_a_gpu(c_example, models):
-    import torch
-    if torch.cuda.is_available():
+    if torch_sees_a_gpu():
         pytest.skip("GPU present: covered by the gpu test")
     r = subprocess.run([c_example, models["syn9"], "rna004", "0"], capture_output=True, text=True)
     assert r.returncode == 1 and "no CPU compute path" in r.stderr

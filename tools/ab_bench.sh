@@ -4,9 +4,11 @@
 #   bash tools/ab_bench.sh <outdir> [bench args...]
 OUT=$1; shift
 mkdir -p $OUT
+# (a bench.py from before --full runs every record without it)
+PREV_FULL=$(grep -q -- '"--full"' build/prev/bench.py && echo --full)
 for rep in 1 2; do
-  (cd build/prev && timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > ../../$OUT/prev_$rep.json 2> ../../$OUT/prev_$rep.err)
-  timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > $OUT/new_$rep.json 2> $OUT/new_$rep.err
+  (cd build/prev && timeout -k 10 300 python bench.py $PREV_FULL --no-cpu-baseline "$@" > ../../$OUT/prev_$rep.json 2> ../../$OUT/prev_$rep.err)
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > $OUT/new_$rep.json 2> $OUT/new_$rep.err
 done
 python - "$OUT" <<'PY'
 import json, glob, sys

@@ -18,7 +18,7 @@ def main(argv):
     for name, flags in pairs:
         env = dict(os.environ, DYN_HIPCC_EXTRA=flags)
         subprocess.run([sys.executable, "-c", "import dynamont_amd._native as n; n.build(force=True)"], cwd=ROOT, env=env, check=True)
-        r = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline"] + os.environ.get("DYN_VARIANT_BENCH_ARGS", "").split(),
+        r = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline"] + os.environ.get("DYN_VARIANT_BENCH_ARGS", "").split(),
                            cwd=ROOT, capture_output=True, text=True, timeout=600)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if r.returncode or not line:
