@@ -104,6 +104,21 @@ class AlignBatchResult:
                                 _ptr(self.n_segments, N.c_u64_p), _ptr(self.sequence_positions, N.c_u64_p),
                                 _ptr(self.signal_positions, N.c_u64_p), _ptr(self.probabilities, N.c_double_p),
                                 _ptr(self.states, N.c_u8_p), cap)
+        # per-segment signal levels (Aligner.set_event_stats): float64 [cap] like the segment columns, None when not requested
+        self.level_mean = self.level_stdv = self.level_median = None
+
+    def _fetch_levels(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
+        """dyn_batch_fetch_events into this object's level columns (allocated on first use), or drop them."""
+        if not wanted:
+            self.level_mean = self.level_stdv = self.level_median = None
+            return
+        if self.level_mean is None:
+            self.level_mean, self.level_stdv, self.level_median = (np.zeros(self.cap) for _ in range(3))
+        ev = N.DynEventOut(_ptr(self.level_mean, N.c_double_p), _ptr(self.level_stdv, N.c_double_p),
+                           _ptr(self.level_median, N.c_double_p), self.cap)
+        rc = L.dyn_batch_fetch_events(handle, C.byref(ev))
+        if rc != N.DYN_OK:
+            _raise(rc, aligner.last_error())
 
     def error(self, i: int) -> str | None:
         if self.status[i] == 0:
@@ -117,7 +132,7 @@ class AlignBatchResult:
             raise RuntimeError(self.error(i))
         a = int(self.seg_offsets[i])
         b = a + int(self.n_segments[i])
-        return {
+        d = {
             "Z": float(self.Z[i]),
             "sequence_positions": self.sequence_positions[a:b].copy(),
             "signal_positions": self.signal_positions[a:b].copy(),
@@ -125,6 +140,11 @@ class AlignBatchResult:
             "states": [chr(c) for c in self.states[a:b]],
             "polishes": [""] * (b - a),
         }
+        if self.level_mean is not None:  # only when requested: the reference's dict is unchanged by default
+            d["level_mean"] = self.level_mean[a:b].copy()
+            d["level_stdv"] = self.level_stdv[a:b].copy()
+            d["level_median"] = self.level_median[a:b].copy()
+        return d
 
 
 def format_csv(aligner: "Aligner", res: AlignBatchResult, sequences: Sequence[str], readids: Sequence[str],
@@ -148,13 +168,18 @@ def format_csv(aligner: "Aligner", res: AlignBatchResult, sequences: Sequence[st
     begin = np.zeros(n, dtype=np.uint64)
     end = np.zeros(n, dtype=np.uint64)
     L = N.lib()
-    cap = int(L.dyn_format_csv_bound(aligner._h, n, C.byref(res._c), rid, sid))
+    # the signal levels when the result carries them (Aligner.set_event_stats): three more columns per row
+    ev = None
+    if res.level_mean is not None:
+        ev = C.byref(N.DynEventOut(_ptr(res.level_mean, N.c_double_p), _ptr(res.level_stdv, N.c_double_p),
+                                   _ptr(res.level_median, N.c_double_p), res.cap))
+    cap = int(L.dyn_format_csv_bound_events(aligner._h, n, C.byref(res._c), ev, rid, sid))
     # one grow-only buffer per handle: first-touch page faults of a fresh 350 MB buffer cost ~100x
     # the formatting itself (15 ms per 1 024-read batch with warm pages)
     buf = getattr(aligner, "_csv_buf", None)
     if buf is None or buf.size < cap:
         buf = aligner._csv_buf = np.empty(max(cap, 1), dtype=np.uint8)
-    rc = L.dyn_format_csv(aligner._h, n, C.byref(res._c), seqs, _ptr(seq_off, N.c_u64_p), rid, sid,
+    rc = L.dyn_format_csv_events(aligner._h, n, C.byref(res._c), ev, seqs, _ptr(seq_off, N.c_u64_p), rid, sid,
                           so.ctypes.data_as(C.POINTER(C.c_int64)), li.ctypes.data_as(C.POINTER(C.c_int64)),
                           int(threads), buf.ctypes.data, cap, _ptr(begin, N.c_u64_p), _ptr(end, N.c_u64_p))
     if rc != N.DYN_OK:
@@ -271,6 +296,7 @@ class Batch:
         self.close()
 
     def align(self, calc_probabilities: bool = True) -> None:
+        self._levels = bool(calc_probabilities) and self._al._event_stats  # the switch at submission decides
         rc = self._L.dyn_batch_align(self._h, int(bool(calc_probabilities)))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
@@ -289,7 +315,14 @@ class Batch:
         rc = self._L.dyn_batch_fetch(self._h, C.byref(out._c))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
+        out._fetch_levels(self._L, self._h, self._al, getattr(self, "_levels", False))
         return out
+
+    def fetch_events(self, out: N.DynEventOut) -> None:
+        """dyn_batch_fetch_events into caller-owned columns (raises ValueError for a batch that did not ask)."""
+        rc = self._L.dyn_batch_fetch_events(self._h, C.byref(out))
+        if rc != N.DYN_OK:
+            _raise(rc, self._al.last_error())
 
     def fetch_train(self, pooled: bool = False) -> TrainBatchResult:
         out = TrainBatchResult(self.n, self.capacity, self._al.num_kmers, pooled)
@@ -336,13 +369,14 @@ class AsyncBatch:
     handle's pipeline; ``wait()`` returns the filled result object. The input arrays are kept alive here
     (the library reads them until the batch is complete)."""
 
-    def __init__(self, aligner: "Aligner", handle, result, keep):
+    def __init__(self, aligner: "Aligner", handle, result, keep, levels: bool = False):
         self._al = aligner
         self._L = N.lib()
         self._h = handle
         self.result = result
         self._keep = keep
         self._waited = False
+        self._levels = levels  # an align ticket submitted with the event-stats switch on (and calc_probabilities)
 
     def wait(self):
         if not self._waited:
@@ -350,7 +384,11 @@ class AsyncBatch:
             self._waited = True
             if rc != N.DYN_OK:
                 _raise(rc, self._al.last_error())
+            if isinstance(self.result, AlignBatchResult):
+                self.result._fetch_levels(self._L, self._h, self._al, self._levels)
         return self.result
+
+    fetch_events = Batch.fetch_events
 
     def timing(self) -> dict:
         self.wait()
@@ -418,6 +456,8 @@ class Aligner:
     ``device="host"`` creates a handle for the host-side contract only (model/validation), every
     compute call on it raises RuntimeError -- there is no CPU compute path.
     """
+
+    _event_stats = False  # set_event_stats
 
     def __init__(self, model_file: str, pore, mode: str = "basic", threads: int = 1, band: int = 400,
                  device=None):
@@ -508,6 +548,15 @@ class Aligner:
         d["wave_cycles_last_turn"], d["wave_cycles_longest_last_turn"] = int(sp[2]), int(sp[3])
         return d
 
+    def set_event_stats(self, on: bool) -> None:
+        """dyn_aligner_set_event_stats: align(calc_probabilities=True) jobs submitted while on also compute the per-segment
+        signal levels (level_mean / level_stdv / level_median of the aligned, normalised signal) on the GPU; results carry
+        them as ``AlignBatchResult.level_*`` and ``read(i)`` adds the three keys."""
+        rc = self._L.dyn_aligner_set_event_stats(self._h, 1 if on else 0)
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        self._event_stats = bool(on)
+
     def set_train_zcheck(self, on: bool) -> None:
         """dyn_aligner_set_train_zcheck: also refuse the reads the reference's |Zf - Zb| rule refuses (one more Z-only
         forward sweep per read)."""
@@ -593,7 +642,7 @@ class Aligner:
                                            C.byref(h))
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
-        return AsyncBatch(self, h, out, (sig, sig_off, seqs, seq_off))
+        return AsyncBatch(self, h, out, (sig, sig_off, seqs, seq_off), levels=self._event_stats and bool(calc_probabilities))
 
     def _raw_args(self, raw, shift, scale, calibration=None):
         scattered = isinstance(raw, (list, tuple))
@@ -642,7 +691,8 @@ class Aligner:
                                                int(bool(calc_probabilities)), C.byref(out._c), C.byref(h))
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
-        return AsyncBatch(self, h, out, (raw, raw_off, shift, scale, seqs, seq_off, cal))
+        return AsyncBatch(self, h, out, (raw, raw_off, shift, scale, seqs, seq_off, cal),
+                          levels=self._event_stats and bool(calc_probabilities))
 
     def align_vbz_async(self, chunks, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 3,
                         n_sigmas: float = 3.0, f32: bool = False, calc_probabilities: bool = True,
@@ -675,7 +725,8 @@ class Aligner:
                                                C.byref(out._c), C.byref(h))
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
-        return AsyncBatch(self, h, out, (ptrs, nbytes, samples, read_off, skip, raw_off, shift, scale, seqs, seq_off, cal))
+        return AsyncBatch(self, h, out, (ptrs, nbytes, samples, read_off, skip, raw_off, shift, scale, seqs, seq_off, cal),
+                          levels=self._event_stats and bool(calc_probabilities))
 
     def train_raw_async(self, raw, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 7,
                         n_sigmas: float = 5.0, f32: bool = True, pooled: bool = False,

@@ -14,10 +14,11 @@ CSRC = os.path.join(HERE, "csrc")
 # DYN_LIB_PATH: another build of the SAME sources (tools/sanitize: the host side under ASan / UBSan / TSan on the CPU)
 LIB_PATH = os.environ.get("DYN_LIB_PATH") or os.path.join(HERE, "libdynamont_mi.so")
 SOURCES = ["dynamont_mi.cpp", "buffers.cpp", "launch.cpp", "session.cpp", "async_engine.cpp", "pore_model.cpp", "csv_format.cpp", "csv_sink.cpp", "vbz_decode.cpp", "bam_reader.cpp", "rccl_comm.cpp", "model_format.cpp",
-           "nt_kernels.hip", "pool_stats.hip", "wide_band.hip"]
+           "nt_kernels.hip", "pool_stats.hip", "wide_band.hip", "event_stats.hip"]
 HEADERS = ["engine.hpp", "engine_internal.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
 
 DYN_DEVICE_HOST_ONLY = -2
+DYN_CSV_EVENT_STATS = 0x1  # dyn_csv_sink_open_ex flag
 DYN_OK, DYN_ERR_INVALID_ARGUMENT, DYN_ERR_RUNTIME, DYN_ERR_DEVICE, DYN_ERR_OUT_OF_MEMORY = range(5)
 
 c_double_p = C.POINTER(C.c_double)
@@ -38,6 +39,10 @@ class DynAlignOut(C.Structure):
     _fields_ = [("Z", c_double_p), ("status", c_i32_p), ("bad_char", C.c_void_p), ("seg_offsets", c_u64_p),
                 ("n_segments", c_u64_p), ("sequence_positions", c_u64_p), ("signal_positions", c_u64_p),
                 ("probabilities", c_double_p), ("states", c_u8_p), ("capacity", C.c_uint64)]
+
+
+class DynEventOut(C.Structure):
+    _fields_ = [("mean", c_double_p), ("stdev", c_double_p), ("median", c_double_p), ("capacity", C.c_uint64)]
 
 
 class DynTrainOut(C.Structure):
@@ -95,6 +100,7 @@ SIGNATURES = {
     "dyn_aligner_set_mem_budget": (C.c_int, [C.c_void_p, C.c_uint64]),
     "dyn_aligner_set_strict": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_aligner_set_train_zcheck": (C.c_int, [C.c_void_p, C.c_int]),
+    "dyn_aligner_set_event_stats": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_tie_rows": (C.c_uint32, [C.c_void_p, c_i32_p, C.c_uint64, C.c_uint64]),
     "dyn_aligner_last_error": (C.c_char_p, [C.c_void_p]),
     "dyn_read_strerror": (C.c_int, [C.c_int, C.c_char, C.c_char_p, C.c_uint64]),
@@ -110,9 +116,16 @@ SIGNATURES = {
     "dyn_format_csv": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(DynAlignOut), C.c_char_p, c_u64_p,
                                  C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_int64),
                                  C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_uint64, c_u64_p, c_u64_p]),
+    "dyn_format_csv_bound_events": (C.c_uint64, [C.c_void_p, C.c_uint64, C.POINTER(DynAlignOut), C.POINTER(DynEventOut),
+                                                 C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]),
+    "dyn_format_csv_events": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(DynAlignOut), C.POINTER(DynEventOut), C.c_char_p,
+                                        c_u64_p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_uint64, c_u64_p, c_u64_p]),
     "dyn_csv_compact": (C.c_uint64, [C.c_void_p, C.c_uint64, c_u64_p, c_u64_p]),
     "dyn_csv_sink_open": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_uint64]),
     "dyn_csv_sink_open_part": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_uint64]),
+    "dyn_csv_sink_open_ex": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32,
+                                       C.POINTER(C.c_void_p), C.c_char_p, C.c_uint64]),
     "dyn_csv_sink_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DynAlignOut), C.c_uint64, C.c_char_p, c_u64_p,
                                       C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_int64), c_u64_p]),
     "dyn_csv_sink_submit_bases": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DynAlignOut), C.c_uint64, C.c_char_p, c_u64_p,
@@ -136,6 +149,7 @@ SIGNATURES = {
     "dyn_batch_align": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_batch_train": (C.c_int, [C.c_void_p]),
     "dyn_batch_fetch": (C.c_int, [C.c_void_p, C.POINTER(DynAlignOut)]),
+    "dyn_batch_fetch_events": (C.c_int, [C.c_void_p, C.POINTER(DynEventOut)]),
     "dyn_batch_fetch_train": (C.c_int, [C.c_void_p, C.POINTER(DynTrainOut), c_double_p]),
     "dyn_batch_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_u64_p, C.POINTER(C.c_void_p)]),
     "dyn_batch_device_pooled": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_u64_p]),

@@ -6,6 +6,7 @@
 //   basepos = sequence_pos[i]   (RNA: len(read) - basepos - 1, AFTER base/motif were taken)
 //   base    = read[basepos]     motif = read[max(0,bp-k/2) : min(len,bp+k/2+1)]  (reversed for RNA)
 //   state   = 'M'               posterior = f"{p:.6f}"      polish = "NA"
+// dyn_format_csv_events appends ,level_mean,level_stdv,level_median (f"{x:.6f}" each) to every row.
 // The bytes must equal Python's: "%.6f" of a double is the correctly rounded decimal in both glibc
 // and CPython; the fast path (scaled integer) is used only when the value is provably not within
 // 1e-6 of a rounding boundary, otherwise snprintf decides.
@@ -54,8 +55,17 @@ inline char* put_int(char* p, int64_t v) {
   return put_uint(p, (uint64_t)v);
 }
 
+// kEvent (the signal levels, dyn_format_csv_events): any finite double, signed. The sign is written apart ("%.6f" rounds
+// symmetrically; -0.0 and tiny negatives give "-0.000000", as Python), the fast path is taken below 512 only, where the
+// product's rounding error (<= 2^-24) stays far below the 1e-6 margin, and the fallback writes "%.6f" whatever its length
+// (<= 316 characters + the sign: kEventValueBound).
+template <bool kEvent = false>
 inline char* put_prob6(char* p, double x) {
-  if (x >= 0.0 && x < 4.0e9) {
+  if (kEvent && std::signbit(x) && !std::isnan(x)) {
+    *p++ = '-';
+    x = -x;
+  }
+  if (x >= 0.0 && x < (kEvent ? 512.0 : 4.0e9)) {
     const double scaled = x * 1e6;
     const double fl = std::floor(scaled);
     const double frac = scaled - fl;
@@ -77,7 +87,8 @@ inline char* put_prob6(char* p, double x) {
   // (<= 24 characters, the value still exact): outside the reference's range of values there is no reference text to match.
   char buf[352];
   int n = std::snprintf(buf, sizeof buf, "%.6f", x);
-  if (n < 0 || n > 47) n = std::snprintf(buf, sizeof buf, "%.17g", x);
+  if (!kEvent && (n < 0 || n > 47)) n = std::snprintf(buf, sizeof buf, "%.17g", x);
+  if (n < 0) n = 0;
   std::memcpy(p, buf, (size_t)n);
   return p + n;
 }
@@ -85,6 +96,7 @@ inline char* put_prob6(char* p, double x) {
 struct Args {
   int k, rna;
   const dyn_align_out* res;
+  const dyn_event_out* ev;  // nullptr: no level columns
   const char* seqs;
   const uint64_t* seq_offsets;
   const char* const* readids;
@@ -97,9 +109,23 @@ struct Args {
 // state, "%.6f" (<= 48 by the snprintf bound above), "NA", 9 commas, newline
 constexpr uint64_t kRowBound = 3 * 20 + 1 + 32 + 1 + 48 + 2 + 9 + 1;
 
+// bytes of put_prob6<true>(x), at most: "-" + up to 16 integer digits + "." + 6 below 1e16, else the full "%.6f" of a
+// finite double (309 integer digits at most) -- a per-value bound keeps a batch's slots near its real size
+constexpr uint64_t kEventSmallBound = 1 + 16 + 1 + 6;
+constexpr uint64_t kEventValueBound = 1 + 309 + 1 + 6;
+inline uint64_t event_value_bound(double x) { return std::fabs(x) < 1e15 ? kEventSmallBound : kEventValueBound; }
+
 uint64_t read_bound(const Args& a, uint64_t i) {
   if (a.res->status[i] != DYN_READ_OK) return 0;
-  return a.res->n_segments[i] * (std::strlen(a.readids[i]) + std::strlen(a.signalids[i]) + kRowBound);
+  const uint64_t n = a.res->n_segments[i];
+  uint64_t b = n * (std::strlen(a.readids[i]) + std::strlen(a.signalids[i]) + kRowBound);
+  if (a.ev) {
+    const uint64_t o = a.res->seg_offsets[i];
+    b += 3 * n;  // the commas
+    for (uint64_t s = o; s < o + n; ++s)
+      b += event_value_bound(a.ev->mean[s]) + event_value_bound(a.ev->stdev[s]) + event_value_bound(a.ev->median[s]);
+  }
+  return b;
 }
 
 char* format_read(const Args& a, uint64_t i, char* p) {
@@ -134,7 +160,16 @@ char* format_read(const Args& a, uint64_t i, char* p) {
     *p++ = (char)(r.states ? r.states[o + s] : 'M');
     *p++ = ',';
     p = put_prob6(p, r.probabilities[o + s]);
-    *p++ = ','; *p++ = 'N'; *p++ = 'A'; *p++ = '\n';
+    *p++ = ','; *p++ = 'N'; *p++ = 'A';
+    if (a.ev) {
+      *p++ = ',';
+      p = put_prob6<true>(p, a.ev->mean[o + s]);
+      *p++ = ',';
+      p = put_prob6<true>(p, a.ev->stdev[o + s]);
+      *p++ = ',';
+      p = put_prob6<true>(p, a.ev->median[o + s]);
+    }
+    *p++ = '\n';
   }
   return p;
 }
@@ -143,8 +178,14 @@ char* format_read(const Args& a, uint64_t i, char* p) {
 
 extern "C" uint64_t dyn_format_csv_bound(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
                                          const char* const* readids, const char* const* signalids) {
-  if (!a || !res) return 0;
-  Args args{0, 0, res, nullptr, nullptr, readids, signalids, nullptr, nullptr};
+  return dyn_format_csv_bound_events(a, n_reads, res, nullptr, readids, signalids);
+}
+
+extern "C" uint64_t dyn_format_csv_bound_events(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
+                                                const dyn_event_out* ev, const char* const* readids,
+                                                const char* const* signalids) {
+  if (!a || !res || (ev && (!ev->mean || !ev->stdev || !ev->median))) return 0;
+  Args args{0, 0, res, ev, nullptr, nullptr, readids, signalids, nullptr, nullptr};
   uint64_t total = 0;
   for (uint64_t i = 0; i < n_reads; ++i) total += read_bound(args, i);
   return total;
@@ -155,13 +196,23 @@ extern "C" int dyn_format_csv(const dyn_aligner* a, uint64_t n_reads, const dyn_
                               const char* const* readids, const char* const* signalids,
                               const int64_t* sig_offsets, const int64_t* last_index, int threads,
                               char* out, uint64_t out_cap, uint64_t* row_begin, uint64_t* row_end) {
+  return dyn_format_csv_events(a, n_reads, res, nullptr, seqs, seq_offsets, readids, signalids, sig_offsets, last_index,
+                               threads, out, out_cap, row_begin, row_end);
+}
+
+extern "C" int dyn_format_csv_events(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
+                                     const dyn_event_out* ev, const char* seqs, const uint64_t* seq_offsets,
+                                     const char* const* readids, const char* const* signalids,
+                                     const int64_t* sig_offsets, const int64_t* last_index, int threads,
+                                     char* out, uint64_t out_cap, uint64_t* row_begin, uint64_t* row_end) {
   if (!a || !res || !res->status || !res->n_segments || !res->seg_offsets || !res->sequence_positions ||
-      !res->signal_positions || !res->probabilities || !out || !row_begin || !row_end)
+      !res->signal_positions || !res->probabilities || !out || !row_begin || !row_end ||
+      (ev && (!ev->mean || !ev->stdev || !ev->median)))
     return DYN_ERR_INVALID_ARGUMENT;
   dyn_info info;
   dyn_aligner_info(a, &info);
   if (info.kmer_size > 31) return DYN_ERR_INVALID_ARGUMENT;
-  Args args{info.kmer_size, info.rna, res, seqs, seq_offsets, readids, signalids, sig_offsets, last_index};
+  Args args{info.kmer_size, info.rna, res, ev, seqs, seq_offsets, readids, signalids, sig_offsets, last_index};
   // every read formats straight into its own worst-case slot of the caller's buffer: no allocation,
   // no shared cache lines between threads
   uint64_t pos = 0;

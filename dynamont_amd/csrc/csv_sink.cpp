@@ -39,6 +39,8 @@ namespace {
 
 constexpr size_t kJobBytes = 4u << 20;
 const char kHeader[] = "readid,signalid,start,end,basepos,base,motif,state,posterior_probability,polish\n";  // segment.py:80
+const char kHeaderEvents[] =
+    "readid,signalid,start,end,basepos,base,motif,state,posterior_probability,polish,level_mean,level_stdv,level_median\n";
 
 struct Blob {  // the formatted rows of one batch; freed when its last job has been compressed
   std::unique_ptr<char[]> data;
@@ -74,6 +76,11 @@ struct Item {
 
 }  // namespace
 
+namespace dyneng {
+// DYN_OK when the ticket was submitted with the handle's event-stats switch on (dynamont_mi.cpp); else the handle's message
+int batch_check_events(dyn_batch* b);
+}
+
 struct dyn_csv_sink {
   dynzstd::Zstd z;
   int level = 3, threads = 4;
@@ -91,6 +98,8 @@ struct dyn_csv_sink {
   std::atomic<uint64_t> error_lines{0};
   bool closing = false, items_done = false, jobs_closed = false, failed = false;
   bool first_part = true, last_part = true;  // dyn_csv_sink_open_part: a part of a frame that several processes write
+  bool events = false;                        // DYN_CSV_EVENT_STATS
+  std::vector<double> ev_cols;                // [3][capacity] the batch's levels (dyn_batch_fetch_events)
   std::thread t_sink, t_writer;
   std::vector<std::thread> t_comp;
   std::vector<std::shared_ptr<Blob>> spare;  // recycled row buffers (first-touch page faults cost more than formatting)
@@ -250,7 +259,19 @@ struct dyn_csv_sink {
     begin.resize(it.n);
     end.resize(it.n);
     for (uint64_t i = 0; i < it.n; ++i) last_index[i] = (int64_t)it.signal_lengths[i] + it.sig_offsets[i];
-    const uint64_t bound = dyn_format_csv_bound(it.a, it.n, it.res, it.readids, it.signalids);
+    dyn_event_out ev{};
+    if (events) {
+      const uint64_t cap = it.res->seg_offsets ? it.res->seg_offsets[it.n] : 0;
+      ev_cols.resize(std::max<uint64_t>(1, 3 * cap));
+      ev = dyn_event_out{ev_cols.data(), ev_cols.data() + cap, ev_cols.data() + 2 * cap, cap};
+      if (dyn_batch_fetch_events(it.ticket, &ev) != DYN_OK) {
+        std::lock_guard<std::mutex> lk(m);
+        fail(std::string("batch levels: ") + dyn_aligner_last_error(it.a));
+        return;
+      }
+    }
+    const dyn_event_out* evp = events ? &ev : nullptr;
+    const uint64_t bound = dyn_format_csv_bound_events(it.a, it.n, it.res, evp, it.readids, it.signalids);
     std::shared_ptr<Blob> blob;
     {
       std::lock_guard<std::mutex> lk(m);
@@ -268,8 +289,8 @@ struct dyn_csv_sink {
       if (spare.size() < 4) spare.push_back(blob);
     }
     const double c2 = now_ms();
-    const int frc = dyn_format_csv(it.a, it.n, it.res, it.seqs, it.seq_offsets, it.readids, it.signalids, it.sig_offsets,
-                                   last_index.data(), std::min(threads, 8), blob->data.get(), blob->cap, begin.data(), end.data());
+    const int frc = dyn_format_csv_events(it.a, it.n, it.res, evp, it.seqs, it.seq_offsets, it.readids, it.signalids, it.sig_offsets,
+                                          last_index.data(), std::min(threads, 8), blob->data.get(), blob->cap, begin.data(), end.data());
     if (frc != DYN_OK) {
       std::lock_guard<std::mutex> lk(m);
       fail("dyn_format_csv failed");
@@ -311,13 +332,15 @@ struct dyn_csv_sink {
   void sink_loop() {
     if (first_part) {
       auto hdr = std::make_shared<Blob>();
-      hdr->cap = sizeof kHeader;
+      const char* text = events ? kHeaderEvents : kHeader;
+      const size_t len = std::strlen(text);
+      hdr->cap = len + 1;
       hdr->data.reset(new char[hdr->cap]);
-      std::memcpy(hdr->data.get(), kHeader, sizeof kHeader - 1);
+      std::memcpy(hdr->data.get(), text, len);
       hdr->begin = {0};
-      hdr->end = {sizeof kHeader - 1};
-      hdr->prefix = {0, sizeof kHeader - 1};
-      append(hdr, sizeof kHeader - 1);
+      hdr->end = {len};
+      hdr->prefix = {0, len};
+      append(hdr, len);
     }
     for (;;) {
       Item it;
@@ -357,6 +380,11 @@ int dyn_csv_sink_open(const char* csv_zst_path, const char* errors_path, int lev
 
 int dyn_csv_sink_open_part(const char* csv_zst_path, const char* errors_path, int level, int threads, int first, int last,
                            dyn_csv_sink** out, char* err, uint64_t errcap) {
+  return dyn_csv_sink_open_ex(csv_zst_path, errors_path, level, threads, first, last, 0u, out, err, errcap);
+}
+
+int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int level, int threads, int first, int last,
+                         uint32_t flags, dyn_csv_sink** out, char* err, uint64_t errcap) {
   auto put = [&](const std::string& s) {
     if (err && errcap) {
       std::snprintf(err, (size_t)errcap, "%s", s.c_str());
@@ -364,6 +392,10 @@ int dyn_csv_sink_open_part(const char* csv_zst_path, const char* errors_path, in
   };
   if (!csv_zst_path || !errors_path || !out) return DYN_ERR_INVALID_ARGUMENT;
   *out = nullptr;
+  if (flags & ~DYN_CSV_EVENT_STATS) {
+    put("dyn_csv_sink_open_ex: unknown flags");
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
   std::unique_ptr<dyn_csv_sink> s(new dyn_csv_sink());
   std::string e;
   if (!s->z.load(e)) {
@@ -381,6 +413,7 @@ int dyn_csv_sink_open_part(const char* csv_zst_path, const char* errors_path, in
   s->threads = std::max(1, threads);
   s->first_part = first != 0;
   s->last_part = last != 0;
+  s->events = (flags & DYN_CSV_EVENT_STATS) != 0;
   dyn_csv_sink* p = s.release();
   for (int t = 0; t < p->threads; ++t) p->t_comp.emplace_back([p] { p->compress_loop(); });
   p->t_writer = std::thread([p] { p->writer_loop(); });
@@ -401,6 +434,8 @@ int dyn_csv_sink_submit_bases(dyn_csv_sink* s, dyn_aligner* a, dyn_batch* ticket
                               const uint32_t* stored_bases) {
   if (!s || !a || !ticket || !res || !seq_offsets || (n_reads && (!seqs || !readids || !signalids || !sig_offsets || !signal_lengths)))
     return DYN_ERR_INVALID_ARGUMENT;
+  if (s->events)
+    if (int rc = dyneng::batch_check_events(ticket)) return rc;  // the message is the handle's (dyn_aligner_last_error)
   {
     std::lock_guard<std::mutex> lk(s->m);
     if (s->closing) return DYN_ERR_INVALID_ARGUMENT;

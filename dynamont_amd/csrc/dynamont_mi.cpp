@@ -59,7 +59,7 @@ void attach_cache(dyn_batch* b) {
   dyneng::BufCache* c = &b->a->cache;
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_norm, &b->d_meta, &b->d_wide})
+                    &b->d_pathn, &b->d_ev, &b->d_norm, &b->d_meta, &b->d_wide})
     d->cache = c;
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->cache = c;
 }
@@ -522,6 +522,12 @@ int dyn_aligner_set_train_zcheck(dyn_aligner* a, int on) {
   return DYN_OK;
 }
 
+int dyn_aligner_set_event_stats(dyn_aligner* a, int on) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  a->event_stats = on != 0;
+  return DYN_OK;
+}
+
 }  // extern "C"
 
 namespace dyneng {
@@ -766,7 +772,7 @@ void dyn_batch_destroy(dyn_batch* b) {
   if (b->a && !b->a->host_only) (void)hipSetDevice(b->a->device);
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_norm, &b->d_meta, &b->d_tctl})
+                    &b->d_pathn, &b->d_ev, &b->d_norm, &b->d_meta, &b->d_tctl})
     d->release();
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->release();
   for (hipEvent_t e : b->events) (void)hipEventDestroy(e);
@@ -905,6 +911,7 @@ int run_job_sync(dyn_batch* b, DynJob job) {
     std::lock_guard<std::mutex> lk(a->mu);
     int rc = need_device(a);
     if (rc != DYN_OK) return rc;
+    b->ev_want = a->event_stats;
     rc = enqueue_job(b, job);
     if (rc != DYN_OK) {
       (void)hipStreamSynchronize(a->stream);
@@ -981,6 +988,46 @@ int dyn_batch_fetch(dyn_batch* b, dyn_align_out* out) {
     rows = static_cast<const SegRow*>(a->h_rows.p) - seg0;  // unpack_align indexes rows by the batch's own segment offsets
   }
   unpack_align(src, st.data(), rows, out, &pool, read0, b->n, seg0);
+  return DYN_OK;
+}
+
+}  // extern "C"
+
+namespace dyneng {
+int batch_check_events(dyn_batch* b) {
+  if (b->ev_want && b->job == DynJob::AlignFull) return DYN_OK;
+  std::lock_guard<std::mutex> lk(b->a->err_mu);
+  b->a->last_error = "dyn_csv_sink_submit: the sink writes the signal levels (DYN_CSV_EVENT_STATS) and this ticket was submitted "
+                     "without dyn_aligner_set_event_stats(a, 1) or with calc_probabilities = 0";
+  return DYN_ERR_INVALID_ARGUMENT;
+}
+}  // namespace dyneng
+
+extern "C" {
+
+int dyn_batch_fetch_events(dyn_batch* b, dyn_event_out* out) {
+  if (!b || !out || !out->mean || !out->stdev || !out->median) return DYN_ERR_INVALID_ARGUMENT;
+  dyn_aligner* a = b->a;
+  // a member of a merged launch: rows [g_seg0, g_seg0 + capacity) of the group's columns (dyn_batch_fetch)
+  const dyn_batch* src = (b->group && b->group->g) ? b->group->g : b;
+  const uint64_t seg0 = src == b ? 0 : b->g_seg0;
+  if (!b->aligned || !b->last_calc || !src->ev_ready) {
+    a->last_error = !b->aligned || !b->last_calc
+                        ? "dyn_batch_fetch_events: the batch was not aligned with calc_probabilities = 1"
+                        : "dyn_batch_fetch_events: the batch was submitted without dyn_aligner_set_event_stats(a, 1)";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  if (out->capacity < b->capacity) {
+    a->last_error = "dyn_event_out.capacity is smaller than dyn_segment_capacity()";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  int rc = need_device(a);
+  if (rc != DYN_OK) return rc;
+  if (!b->capacity) return DYN_OK;
+  const double* e = src->d_ev.as<double>() + seg0;
+  HIP_TRY(a, copy_out(a, out->mean, e, b->capacity * 8));
+  HIP_TRY(a, copy_out(a, out->stdev, e + src->capacity, b->capacity * 8));
+  HIP_TRY(a, copy_out(a, out->median, e + 2 * src->capacity, b->capacity * 8));
   return DYN_OK;
 }
 

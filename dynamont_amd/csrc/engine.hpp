@@ -146,6 +146,7 @@ struct dyn_aligner {
   uint64_t mem_budget = 0;
   int strict_mode = 1;  // dyn_aligner_set_strict: reads with a structural tie run bit for bit by default
   bool train_zcheck = false;  // dyn_aligner_set_train_zcheck
+  bool event_stats = false;   // dyn_aligner_set_event_stats: read by every batch / ticket at its submission
   bool ntk = false;     // created with mode "resquiggle" / "ntk"
   std::string last_error;
   // grow-only lattice workspace pool, reused across batches (only ever touched by work on `stream`,
@@ -234,6 +235,9 @@ struct dyn_batch {
   dyneng::DevBuf d_sig, d_kmers, d_par, d_state, d_rows, d_segrow, d_medhi, d_medlo, d_descs;
   dyneng::DevBuf d_colw, d_cols1, d_cols2, d_trans, d_pooled, d_poolwork, d_pooltemp;
   dyneng::DevBuf d_pp, d_pathn;                // per-row path arrays (traceback -> k_median / k_final)
+  dyneng::DevBuf d_ev;                         // [3][capacity] level mean / stdev / median (event_stats.hip), when asked for
+  bool ev_want = false;                        // the handle's event-stats switch when this batch / ticket was submitted
+  bool ev_ready = false;                       // the last job computed the event columns into d_ev
   dyneng::PinnedBuf h_descs, h_state, h_rows;  // h_state/h_rows: D2H targets of the asynchronous path
   dyneng::PinnedBuf h_stats;                   // wave-cycle statistics of the read-queue launch
   dyneng::PinnedBuf h_sig;                     // staging of pageable caller signals (asynchronous path)

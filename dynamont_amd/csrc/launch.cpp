@@ -574,7 +574,17 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     dynk::launch_wide_reads(job == DynJob::Train ? 2 : calc ? 1 : 0, wa, wide_groups, a->stream);
   }
   const int nr_all = (int)n_all;
-  if (calc) dynk::launch_segments(q.descs, nr_all, rows_total, max_N, q.st, q.tb, b->d_rows.as<SegRow>(), m.k, a->stream);
+  dynk::EventCols evc{};
+  b->ev_ready = false;
+  if (calc && b->ev_want) {
+    // [mean | stdev | median] x capacity; rows of reads that fail keep the zeros
+    HIP_TRY(a, b->d_ev.ensure(std::max<uint64_t>(24, b->capacity * 24)));
+    if (b->capacity) HIP_TRY(a, hipMemsetAsync(b->d_ev.p, 0, b->capacity * 24, a->stream));
+    double* e = b->d_ev.as<double>();
+    evc = dynk::EventCols{q.sig, e, e + b->capacity, e + 2 * b->capacity};
+    b->ev_ready = true;
+  }
+  if (calc) dynk::launch_segments(q.descs, nr_all, rows_total, max_N, q.st, q.tb, b->d_rows.as<SegRow>(), m.k, a->stream, evc);
   if (job == DynJob::Train) {
     b->pool_nr = nr_all;
     b->pool_max_N = max_N;

@@ -2188,7 +2188,7 @@ void launch_session_publish(SessionTicket* ring, uint32_t* ctl, const SessionTic
 void launch_session_close(uint32_t* ctl, hipStream_t s) { hipLaunchKernelGGL(k_session_close, dim3(1), dim3(64), 0, s, ctl); }
 
 void launch_segments(const ReadDesc* descs, int n_reads, uint64_t rows_total, uint32_t max_N, const ReadState* st,
-                     TraceBuffers tb, SegRow* rows, int kmer_size, hipStream_t s) {
+                     TraceBuffers tb, SegRow* rows, int kmer_size, hipStream_t s, const EventCols& ev) {
   if (n_reads > 0 && rows_total)
     hipLaunchKernelGGL(k_median, dim3((unsigned)((rows_total + 255) / 256)), dim3(256), 0, s, descs, n_reads, rows_total, st, tb);
   for (int r0 = 0; r0 < n_reads; r0 += MAX_GRID_Y) {
@@ -2196,6 +2196,7 @@ void launch_segments(const ReadDesc* descs, int n_reads, uint64_t rows_total, ui
     hipLaunchKernelGGL(k_median_long, dim3(nr), dim3(256), 0, s, descs + r0, st, tb);
     hipLaunchKernelGGL(k_final, dim3((max_N + 255) / 256, nr), dim3(256), 0, s, descs + r0, st, tb, rows, kmer_size);
   }
+  launch_event_stats(descs, n_reads, rows_total, st, tb, ev, s);
 }
 
 }  // namespace dynk

@@ -223,9 +223,19 @@ void launch_pool_init(const PagePool& pool, uint32_t first_free, int n_static, h
 // with_strict: the launch holds reads flagged READ_STRICT (JOB_ALIGN / JOB_ALIGN_INPLACE only): the kernel variant
 // that carries both arithmetic flavours and branches per read
 void launch_read_queue(QueueJob job, bool with_strict, const QueueArgs& q, int n_cus, hipStream_t s);
-// per-segment median posterior + output rows for all reads of descs (after launch_read_queue)
+// per-segment signal levels (event_stats.hip): columns indexed like the output rows; mean == nullptr: not asked for
+struct EventCols {
+  const double* sig;  // the signal the read queue aligned (ReadDesc::sig_off counts from here)
+  double* mean;
+  double* stdev;
+  double* median;
+};
+void launch_event_stats(const ReadDesc* descs, int n_reads, uint64_t rows_total, const ReadState* st, const TraceBuffers& tb,
+                        const EventCols& ev, hipStream_t s);
+// per-segment median posterior + output rows for all reads of descs (after launch_read_queue), then the signal levels when
+// `ev` asks for them
 void launch_segments(const ReadDesc* descs, int n_reads, uint64_t rows_total, uint32_t max_N, const ReadState* st,
-                     TraceBuffers tb, SegRow* rows, int kmer_size, hipStream_t s);
+                     TraceBuffers tb, SegRow* rows, int kmer_size, hipStream_t s, const EventCols& ev = EventCols{});
 // pooled[3*num_kmers] (zeroed by the caller) = per-k-mer (w, s1, s2) of the ok reads in descs, summed in a FIXED order:
 // per read over its columns ascending, then over the reads in input order -- bit for bit the host's sum (pool_stats.hip).
 // work: pool_stats_work_bytes(total_cols) device bytes; temp: pool_stats_temp_bytes(...) (rocprim's radix sort).

@@ -370,6 +370,8 @@ int session_publish(dyn_batch* b) {
   HIP_TRY(a, b->d_segrow.ensure(std::max<uint64_t>(4, b->capacity * 4)));
   HIP_TRY(a, b->d_medhi.ensure(std::max<uint64_t>(8, b->capacity * 8)));
   HIP_TRY(a, b->d_medlo.ensure(std::max<uint64_t>(8, b->capacity * 8)));
+  b->ev_ready = b->ev_want;  // the columns are filled by session_finish_enqueue, behind the per-segment kernels
+  if (b->ev_want) HIP_TRY(a, b->d_ev.ensure(std::max<uint64_t>(24, b->capacity * 24)));
   ReadState* st = b->h_state.as<ReadState>();
   for (uint64_t i = 0; i < b->n; ++i) {
     st[i].Zb = 0.0;
@@ -524,8 +526,14 @@ int session_finish_enqueue(dyn_batch* b, hipStream_t s) {
   HIP_TRY(a, hipEventRecord(ev[1], s));
   dynk::TraceBuffers tb{b->d_pp.as<double>(), b->d_pathn.as<uint32_t>(), b->d_segrow.as<uint32_t>(), b->d_medhi.as<double>(),
                         b->d_medlo.as<double>()};
+  dynk::EventCols evc{};
+  if (b->ev_ready) {
+    if (b->capacity) HIP_TRY(a, hipMemsetAsync(b->d_ev.p, 0, b->capacity * 24, s));
+    double* e = b->d_ev.as<double>();
+    evc = dynk::EventCols{b->d_sig.as<double>(), e, e + b->capacity, e + 2 * b->capacity};
+  }
   dynk::launch_segments(b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_rows_total, b->sess_max_N, b->d_state.as<ReadState>(), tb,
-                        b->d_rows.as<SegRow>(), a->model.k, s);
+                        b->d_rows.as<SegRow>(), a->model.k, s, evc);
   HIP_TRY(a, hipGetLastError());
   HIP_TRY(a, hipEventRecord(ev[2], s));
   HIP_TRY(a, hipMemcpyAsync(b->h_stats.p, b->d_tctl.p, dynk::SESSION_TCTL_WORDS * 4, hipMemcpyDeviceToHost, s));

@@ -42,6 +42,8 @@ import time as _time  # noqa: E402
 _IMPORTED_AT = _time.time()
 
 CSV_HEADER = b"readid,signalid,start,end,basepos,base,motif,state,posterior_probability,polish\n"
+# --event-stats: every row also carries the per-segment signal levels (Aligner.set_event_stats)
+CSV_HEADER_EVENTS = CSV_HEADER[:-1] + b",level_mean,level_stdv,level_median\n"
 POLYA = "AAAAAAAAA"
 
 MAX_SAMPLES_IN_FLIGHT = 512 << 20  # ~1 GB of pinned int16 staging + ~4 GB of float64 on the device, whatever --depth says
@@ -82,6 +84,9 @@ def parse(argv=None) -> Namespace:
                         "old name) for reads with a structural tie -- two neighbouring columns with the same emission "
                         "parameters, e.g. polyA pad + A --, 'all' for every read (1.3-1.4x), 'off' for none")
     p.add_argument("--host-preprocess", action="store_true", help="normalise + Hampel-filter with NumPy on the host instead of on the GPU (same bytes)")
+    p.add_argument("--event-stats", action="store_true",
+                   help="add level_mean,level_stdv,level_median to every row: mean, population standard deviation and median "
+                        "of the segment's samples of the normalised signal, in the model's units (computed on the GPU)")
     p.add_argument("--parallel-zstd-frames", action="store_true",
                    help="write the CSV as consecutive independent zstd frames (readers must read across frames: "
                         "python-zstandard's defaults stop after the first). Default: one frame, like the reference, "
@@ -89,14 +94,14 @@ def parse(argv=None) -> Namespace:
     return p.parse_args(argv)
 
 
-def listener(q, outfile: str) -> None:
+def listener(q, outfile: str, header: bytes = CSV_HEADER) -> None:
     """Writer (segment.py:69-107): header, then bytes -> CSV stream, str -> ``<out>.errors``,
     "kill" terminates."""
     errfile = splitext(splitext(outfile)[0])[0] + ".errors"
     num_err = 0
     with open(outfile, "wb") as raw:
         with open_writer(raw, level=3, threads=ZSTD_WORKERS, parallel_frames=ZSTD_PARALLEL_FRAMES) as output:
-            output.write(CSV_HEADER)
+            output.write(header)
             while True:
                 result = q.get()
                 if isinstance(result, str) and result == "kill":
@@ -499,8 +504,9 @@ class _NativePipeline:
         import os
         threads = int(os.environ.get("DYN_SINK_THREADS", threads))
         self.threads = threads
-        rc = self.L.dyn_csv_sink_open_part(outfile.encode(), errfile.encode(), int(os.environ.get("DYN_SINK_LEVEL", level)), int(threads),
-                                           int(first), int(last), C.byref(h), err, 1024)
+        flags = N.DYN_CSV_EVENT_STATS if aligner._event_stats else 0  # the rows carry the signal levels (--event-stats)
+        rc = self.L.dyn_csv_sink_open_ex(outfile.encode(), errfile.encode(), int(os.environ.get("DYN_SINK_LEVEL", level)), int(threads),
+                                         int(first), int(last), flags, C.byref(h), err, 1024)
         if rc != N.DYN_OK:
             raise OSError(err.value.decode())
         self.h = h
@@ -691,7 +697,7 @@ def _gather_parts(comm, parallel, outfile: str, part: str, part_err: str | None)
 def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_path: str, pore: str, mode: str,
             minq: float = 0, device: int = 0, batch_reads: int = 1024, mem_budget_gib: float = 0.0,
             host_preprocess: bool = False, depth: int = 12, strict_ties: str = "ties", host_threads: int = 0,
-            zstd_level: int = 3) -> None:
+            zstd_level: int = 3, event_stats: bool = False) -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
@@ -713,7 +719,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
     q = queue_mod.Queue() if (rank == 0 and not native) else None
     writer = None
     if q is not None:
-        writer = threading.Thread(target=listener, args=(q, outfile), daemon=True)
+        writer = threading.Thread(target=listener, args=(q, outfile, CSV_HEADER_EVENTS if event_stats else CSV_HEADER), daemon=True)
         writer.start()
     sink = None if native else (q if comm is None else _Collector())
     is_rna = "rna" in pore
@@ -741,6 +747,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             if mem_budget_gib:
                 aligner.set_mem_budget(int(mem_budget_gib * (1 << 30)))
             aligner.set_strict(strict_ties)
+            if event_stats:
+                aligner.set_event_stats(True)
             if native:
                 import os
                 import tempfile
@@ -885,7 +893,7 @@ def main(argv=None) -> None:
     segment(args.raw, args.basecalls, args.processes, outfile, model_path, args.pore, args.mode, args.qscore,
             device=args.device, batch_reads=args.batch_reads, mem_budget_gib=args.mem_budget,
             host_preprocess=args.host_preprocess, depth=args.depth, strict_ties=args.strict_ties, host_threads=args.host_threads,
-            zstd_level=args.zstd_level)
+            zstd_level=args.zstd_level, event_stats=args.event_stats)
     _stamp("segment() returned (aligner closed)")
     if argv is None and not int(__import__("os").environ.get("WORLD_SIZE", "1") or 1) > 1:
         # Invoked as the command (console script / python -m), single process, everything written and closed: leave without

@@ -138,10 +138,12 @@ def _state_char(state) -> str:
 
 
 def segmentation_to_string(result: dict, readid: str, signalid: str, sigOffset: int, lastIndex: int,
-                           read: str, kmerSize: int, rna: bool) -> bytes:
+                           read: str, kmerSize: int, rna: bool, levels=None) -> bytes:
     """CSV rows of one read (utils.py:193-232): ``readid,signalid,start,end,basepos,base,motif,
     state,posterior_probability,polish``. ``read`` is in aligner orientation; for RNA the motif is
-    reversed and basepos flipped AFTER ``base`` was taken."""
+    reversed and basepos flipped AFTER ``base`` was taken. ``levels`` = (level_mean, level_stdv, level_median) of
+    the read's segments (Aligner.set_event_stats): every row gets ``,{mean:.6f},{stdv:.6f},{median:.6f}`` after
+    ``polish`` -- the rows dyn_format_csv_events writes."""
     seq_pos = result["sequence_positions"]
     sig_pos = result["signal_positions"]
     probs = result["probabilities"]
@@ -161,8 +163,9 @@ def segmentation_to_string(result: dict, readid: str, signalid: str, sigOffset: 
         if rna:
             motif = motif[::-1]
             bp = L - bp - 1
+        ev = "" if levels is None else f",{float(levels[0][i]):.6f},{float(levels[1][i]):.6f},{float(levels[2][i]):.6f}"
         rows.append(f"{readid},{signalid},{start},{end},{bp},{base},{motif},{_state_char(states[i])},"
-                    f"{float(probs[i]):.6f},{polish}\n")
+                    f"{float(probs[i]):.6f},{polish}{ev}\n")
     return "".join(rows).encode("utf-8")
 
 

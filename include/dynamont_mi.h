@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DYN_ABI_VERSION 8 /* 8: dyn_aligner_session_idle_split (additive). 7: dyn_aligner_session_page_wait, dyn_comm_gather_bytes / _gathered_bytes / _allreduce_f64 (additive). 7: half bands 224 .. 2 046 are computed (wide_band.hip). 5: any band constructs (DYN_READ_BAND_TOO_WIDE per read); dyn_bam_*, dyn_csv_sink_wait / _open_part */
+#define DYN_ABI_VERSION 9 /* 9: per-segment signal levels: dyn_aligner_set_event_stats, dyn_batch_fetch_events, dyn_format_csv[_bound]_events, dyn_csv_sink_open_ex (additive). 8: dyn_aligner_session_idle_split (additive). 7: dyn_aligner_session_page_wait, dyn_comm_gather_bytes / _gathered_bytes / _allreduce_f64 (additive). 7: half bands 224 .. 2 046 are computed (wide_band.hip). 5: any band constructs (DYN_READ_BAND_TOO_WIDE per read); dyn_bam_*, dyn_csv_sink_wait / _open_part */
 
 /* device argument of dyn_aligner_create: bind no GPU. Such a handle serves the host-side
  * contract only (model loading, dyn_aligner_info/_model, dyn_validate_batch); every compute
@@ -133,6 +133,22 @@ typedef struct dyn_align_out {
   uint8_t* states;              /* [capacity]  'M'                               */
   uint64_t capacity;
 } dyn_align_out;
+
+/* (ABI 9) Per-segment signal levels of an align(calc_probabilities = 1) job whose handle had dyn_aligner_set_event_stats
+ * on when the batch was submitted: caller-allocated columns indexed like the segment arrays of dyn_align_out: read i's
+ * segments at seg_offsets[i], n_segments[i] of them; rows of failed reads are 0. Over segment s's samples of the ALIGNED
+ * signal x (after preprocessing, as dyn_batch_signals returns it), [signal_positions[s], signal_positions[s+1]) -- the
+ * last one up to the read's end -- in the model's normalised units (not pA), L >= 1 samples:
+ *   mean   = S / L, S = sum of x in chunks of 64 consecutive samples from the first (each chunk left to right from its
+ *            first element, the chunk sums left to right from the first), one IEEE fp64 operation each, no FMA
+ *   stdev  = sqrt(Q / L), Q = the same chunked sum of (x - mean)^2 (population standard deviation)
+ *   median = s[L/2] (odd L) or (s[L/2 - 1] + s[L/2]) / 2.0 (even L) of the sorted samples, then + 0.0 */
+typedef struct dyn_event_out {
+  double* mean;    /* [capacity] level_mean */
+  double* stdev;   /* [capacity] level_stdv */
+  double* median;  /* [capacity] level_median */
+  uint64_t capacity;
+} dyn_event_out;
 
 /* Per-read training results (replaces dynamont::TrainingResult, aligner.hpp:48-53, whose
  * pybind form is a list of num_kmers dicts per read, aligner_bindings.cpp:86-107). The emission
@@ -303,6 +319,10 @@ int dyn_aligner_set_strict(dyn_aligner* a, int mode);
  * from one more (Z-only, no lattice traffic) forward sweep per read: `.errors` then lists the pathological reads the
  * reference lists (a sample ~1e6 model standard deviations out), at ~25 % more time per train() launch. */
 int dyn_aligner_set_train_zcheck(dyn_aligner* a, int on);
+/* (ABI 9) align(calc_probabilities = 1) also computes the per-segment signal levels (dyn_event_out) on the device, behind
+ * the per-segment kernels, for every batch or ticket SUBMITTED while it is on (dyn_batch_align, dyn_batch_align*_async);
+ * 3 x 8 bytes of device memory per segment row for those batches only. Default off: nothing else changes. */
+int dyn_aligner_set_event_stats(dyn_aligner* a, int on);
 /* The rule of mode 1 for one read, given its k-mer codes (dyn_validate_batch) and signal length: 0 = no structural tie;
  * otherwise the number of forward rows that run in the strict arithmetic (UINT32_MAX: all of them). Host only. */
 uint32_t dyn_tie_rows(const dyn_aligner* a, const int32_t* kmers, uint64_t n_kmers, uint64_t signal_len);
@@ -353,6 +373,17 @@ int dyn_format_csv(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* 
                    const int64_t* last_index, int threads, char* out, uint64_t out_cap,
                    uint64_t* row_begin, uint64_t* row_end);
 
+/* (ABI 9) The same with the signal levels of dyn_batch_fetch_events (ev indexed like res' segment arrays): every row gets
+ * ",{mean:.6f},{stdev:.6f},{median:.6f}" after "NA", the bytes of Python's f"{x:.6f}" for any finite value (negatives and
+ * -0.000000 included). ev == NULL: the bytes of dyn_format_csv / dyn_format_csv_bound, which are these with ev = NULL. */
+uint64_t dyn_format_csv_bound_events(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                                     const char* const* readids, const char* const* signalids);
+int dyn_format_csv_events(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                          const char* seqs, const uint64_t* seq_offsets, const char* const* readids,
+                          const char* const* signalids, const int64_t* sig_offsets,
+                          const int64_t* last_index, int threads, char* out, uint64_t out_cap,
+                          uint64_t* row_begin, uint64_t* row_end);
+
 /* Closes the gaps between the per-read ranges dyn_format_csv produced: all rows become one contiguous run at the
  * front of `out`, in read order; row_begin/row_end are updated. Returns the total byte count. */
 uint64_t dyn_csv_compact(char* out, uint64_t n_reads, uint64_t* row_begin, uint64_t* row_end);
@@ -385,6 +416,13 @@ int dyn_csv_sink_open(const char* csv_zst_path, const char* errors_path, int lev
  * order][DYN_ZSTD_FRAME_END] is ONE valid frame. */
 int dyn_csv_sink_open_part(const char* csv_zst_path, const char* errors_path, int level, int threads, int first, int last,
                            dyn_csv_sink** out, char* err, uint64_t errcap);
+/* (ABI 9) dyn_csv_sink_open_part with flags. DYN_CSV_EVENT_STATS: the header gains ",level_mean,level_stdv,level_median",
+ * every row the three columns (dyn_format_csv_events); the sink fetches each ticket's levels after its wait, and a submit
+ * whose ticket was submitted without dyn_aligner_set_event_stats on fails with DYN_ERR_INVALID_ARGUMENT. `.errors` lines
+ * are unchanged. flags = 0 is dyn_csv_sink_open_part. */
+#define DYN_CSV_EVENT_STATS 0x1u
+int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int level, int threads, int first, int last,
+                         uint32_t flags, dyn_csv_sink** out, char* err, uint64_t errcap);
 #define DYN_ZSTD_FRAME_END "\x01\x00\x00" /* an empty last block (raw, size 0): 3 bytes; the frames carry no checksum */
 int dyn_csv_sink_submit(dyn_csv_sink* s, dyn_aligner* a, dyn_batch* ticket, const dyn_align_out* res, uint64_t n_reads,
                         const char* seqs, const uint64_t* seq_offsets, const char* const* readids,
@@ -494,6 +532,10 @@ int dyn_batch_train(dyn_batch* b);
 /* Copy results of the last dyn_batch_align to the host. */
 int dyn_batch_fetch(dyn_batch* b, dyn_align_out* out);
 int dyn_batch_fetch_train(dyn_batch* b, dyn_train_out* out, double* pooled3n);
+/* (ABI 9) Copy the signal levels of the last dyn_batch_align (or of a completed ticket, merged launch or not) into `out`
+ * (capacity >= dyn_segment_capacity()). DYN_ERR_INVALID_ARGUMENT + message for a batch submitted without
+ * dyn_aligner_set_event_stats on, or aligned with calc_probabilities = 0. */
+int dyn_batch_fetch_events(dyn_batch* b, dyn_event_out* out);
 /* Device-resident results of the last dyn_batch_align, for an RCCL gather without a host hop:
  * rows = dyn_segment_row[capacity] (read i at seg_offsets[i], as in dyn_align_out);
  * z_status = per read {double Z; int32 status; uint32 n_segments}. Pointers stay valid until the
