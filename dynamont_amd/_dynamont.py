@@ -106,6 +106,22 @@ class AlignBatchResult:
                                 _ptr(self.states, N.c_u8_p), cap)
         # per-segment signal levels (Aligner.set_event_stats): float64 [cap] like the segment columns, None when not requested
         self.level_mean = self.level_stdv = self.level_median = None
+        # per-read transforms (Aligner.set_rescale): shift / scale float64 [n], fits applied int32 [n], None when off
+        self.rescale_shift = self.rescale_scale = self.rescale_iters = None
+
+    def _fetch_rescale(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
+        """dyn_batch_fetch_rescale into this object's per-read columns (allocated on first use), or drop them."""
+        if not wanted:
+            self.rescale_shift = self.rescale_scale = self.rescale_iters = None
+            return
+        if self.rescale_shift is None:
+            self.rescale_shift, self.rescale_scale = np.zeros(self.n), np.ones(self.n)
+            self.rescale_iters = np.zeros(self.n, dtype=np.int32)
+        out = N.DynRescaleOut(_ptr(self.rescale_shift, N.c_double_p), _ptr(self.rescale_scale, N.c_double_p),
+                              _ptr(self.rescale_iters, N.c_i32_p), self.n)
+        rc = L.dyn_batch_fetch_rescale(handle, C.byref(out))
+        if rc != N.DYN_OK:
+            _raise(rc, aligner.last_error())
 
     def _fetch_levels(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
         """dyn_batch_fetch_events into this object's level columns (allocated on first use), or drop them."""
@@ -144,6 +160,10 @@ class AlignBatchResult:
             d["level_mean"] = self.level_mean[a:b].copy()
             d["level_stdv"] = self.level_stdv[a:b].copy()
             d["level_median"] = self.level_median[a:b].copy()
+        if self.rescale_shift is not None:  # only when requested (Aligner.set_rescale)
+            d["rescale_shift"] = float(self.rescale_shift[i])
+            d["rescale_scale"] = float(self.rescale_scale[i])
+            d["rescale_iters"] = int(self.rescale_iters[i])
         return d
 
 
@@ -297,6 +317,7 @@ class Batch:
 
     def align(self, calc_probabilities: bool = True) -> None:
         self._levels = bool(calc_probabilities) and self._al._event_stats  # the switch at submission decides
+        self._rescale = bool(calc_probabilities) and self._al._rescale > 0
         rc = self._L.dyn_batch_align(self._h, int(bool(calc_probabilities)))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
@@ -316,11 +337,18 @@ class Batch:
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
         out._fetch_levels(self._L, self._h, self._al, getattr(self, "_levels", False))
+        out._fetch_rescale(self._L, self._h, self._al, getattr(self, "_rescale", False))
         return out
 
     def fetch_events(self, out: N.DynEventOut) -> None:
         """dyn_batch_fetch_events into caller-owned columns (raises ValueError for a batch that did not ask)."""
         rc = self._L.dyn_batch_fetch_events(self._h, C.byref(out))
+        if rc != N.DYN_OK:
+            _raise(rc, self._al.last_error())
+
+    def fetch_rescale(self, out: N.DynRescaleOut) -> None:
+        """dyn_batch_fetch_rescale into caller-owned arrays (raises ValueError for a batch that did not ask)."""
+        rc = self._L.dyn_batch_fetch_rescale(self._h, C.byref(out))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
 
@@ -369,7 +397,7 @@ class AsyncBatch:
     handle's pipeline; ``wait()`` returns the filled result object. The input arrays are kept alive here
     (the library reads them until the batch is complete)."""
 
-    def __init__(self, aligner: "Aligner", handle, result, keep, levels: bool = False):
+    def __init__(self, aligner: "Aligner", handle, result, keep, levels: bool = False, rescale: bool = False):
         self._al = aligner
         self._L = N.lib()
         self._h = handle
@@ -377,6 +405,7 @@ class AsyncBatch:
         self._keep = keep
         self._waited = False
         self._levels = levels  # an align ticket submitted with the event-stats switch on (and calc_probabilities)
+        self._rescale = rescale  # ... with the rescale switch on
 
     def wait(self):
         if not self._waited:
@@ -386,9 +415,11 @@ class AsyncBatch:
                 _raise(rc, self._al.last_error())
             if isinstance(self.result, AlignBatchResult):
                 self.result._fetch_levels(self._L, self._h, self._al, self._levels)
+                self.result._fetch_rescale(self._L, self._h, self._al, self._rescale)
         return self.result
 
     fetch_events = Batch.fetch_events
+    fetch_rescale = Batch.fetch_rescale
 
     def timing(self) -> dict:
         self.wait()
@@ -458,6 +489,7 @@ class Aligner:
     """
 
     _event_stats = False  # set_event_stats
+    _rescale = 0  # set_rescale
 
     def __init__(self, model_file: str, pore, mode: str = "basic", threads: int = 1, band: int = 400,
                  device=None):
@@ -557,6 +589,15 @@ class Aligner:
             _raise(rc, self.last_error())
         self._event_stats = bool(on)
 
+    def set_rescale(self, iters: int) -> None:
+        """dyn_aligner_set_rescale: align(calc_probabilities=True) jobs submitted while ``iters`` (0 .. 8) > 0 align every
+        read 1 + iters times, refitting the read's signal shift and scale on the GPU between the passes (INTEGRATION.md
+        section 3); all results are those of the last pass, and results carry ``AlignBatchResult.rescale_*``."""
+        rc = self._L.dyn_aligner_set_rescale(self._h, int(iters))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        self._rescale = int(iters)
+
     def set_train_zcheck(self, on: bool) -> None:
         """dyn_aligner_set_train_zcheck: also refuse the reads the reference's |Zf - Zb| rule refuses (one more Z-only
         forward sweep per read)."""
@@ -642,7 +683,8 @@ class Aligner:
                                            C.byref(h))
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
-        return AsyncBatch(self, h, out, (sig, sig_off, seqs, seq_off), levels=self._event_stats and bool(calc_probabilities))
+        return AsyncBatch(self, h, out, (sig, sig_off, seqs, seq_off), levels=self._event_stats and bool(calc_probabilities),
+                          rescale=self._rescale > 0 and bool(calc_probabilities))
 
     def _raw_args(self, raw, shift, scale, calibration=None):
         scattered = isinstance(raw, (list, tuple))
@@ -692,7 +734,8 @@ class Aligner:
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
         return AsyncBatch(self, h, out, (raw, raw_off, shift, scale, seqs, seq_off, cal),
-                          levels=self._event_stats and bool(calc_probabilities))
+                          levels=self._event_stats and bool(calc_probabilities),
+                          rescale=self._rescale > 0 and bool(calc_probabilities))
 
     def align_vbz_async(self, chunks, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 3,
                         n_sigmas: float = 3.0, f32: bool = False, calc_probabilities: bool = True,
@@ -726,7 +769,8 @@ class Aligner:
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
         return AsyncBatch(self, h, out, (ptrs, nbytes, samples, read_off, skip, raw_off, shift, scale, seqs, seq_off, cal),
-                          levels=self._event_stats and bool(calc_probabilities))
+                          levels=self._event_stats and bool(calc_probabilities),
+                          rescale=self._rescale > 0 and bool(calc_probabilities))
 
     def train_raw_async(self, raw, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 7,
                         n_sigmas: float = 5.0, f32: bool = True, pooled: bool = False,

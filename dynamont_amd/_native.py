@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 # DYN_LIB_PATH: another build of the SAME sources (tools/sanitize: the host side under ASan / UBSan / TSan on the CPU)
 LIB_PATH = os.environ.get("DYN_LIB_PATH") or os.path.join(HERE, "libdynamont_mi.so")
 SOURCES = ["dynamont_mi.cpp", "buffers.cpp", "launch.cpp", "session.cpp", "async_engine.cpp", "pore_model.cpp", "csv_format.cpp", "csv_sink.cpp", "vbz_decode.cpp", "bam_reader.cpp", "rccl_comm.cpp", "model_format.cpp",
-           "nt_kernels.hip", "pool_stats.hip", "wide_band.hip", "event_stats.hip"]
+           "nt_kernels.hip", "pool_stats.hip", "wide_band.hip", "event_stats.hip", "rescale.hip"]
 HEADERS = ["engine.hpp", "engine_internal.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
 
 DYN_DEVICE_HOST_ONLY = -2
@@ -43,6 +43,10 @@ class DynAlignOut(C.Structure):
 
 class DynEventOut(C.Structure):
     _fields_ = [("mean", c_double_p), ("stdev", c_double_p), ("median", c_double_p), ("capacity", C.c_uint64)]
+
+
+class DynRescaleOut(C.Structure):
+    _fields_ = [("shift", c_double_p), ("scale", c_double_p), ("iters_applied", c_i32_p), ("n", C.c_uint64)]
 
 
 class DynTrainOut(C.Structure):
@@ -101,6 +105,7 @@ SIGNATURES = {
     "dyn_aligner_set_strict": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_aligner_set_train_zcheck": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_aligner_set_event_stats": (C.c_int, [C.c_void_p, C.c_int]),
+    "dyn_aligner_set_rescale": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_tie_rows": (C.c_uint32, [C.c_void_p, c_i32_p, C.c_uint64, C.c_uint64]),
     "dyn_aligner_last_error": (C.c_char_p, [C.c_void_p]),
     "dyn_read_strerror": (C.c_int, [C.c_int, C.c_char, C.c_char_p, C.c_uint64]),
@@ -150,6 +155,7 @@ SIGNATURES = {
     "dyn_batch_train": (C.c_int, [C.c_void_p]),
     "dyn_batch_fetch": (C.c_int, [C.c_void_p, C.POINTER(DynAlignOut)]),
     "dyn_batch_fetch_events": (C.c_int, [C.c_void_p, C.POINTER(DynEventOut)]),
+    "dyn_batch_fetch_rescale": (C.c_int, [C.c_void_p, C.POINTER(DynRescaleOut)]),
     "dyn_batch_fetch_train": (C.c_int, [C.c_void_p, C.POINTER(DynTrainOut), c_double_p]),
     "dyn_batch_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_u64_p, C.POINTER(C.c_void_p)]),
     "dyn_batch_device_pooled": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_u64_p]),

@@ -151,7 +151,7 @@ static bool mergeable(const dyn_batch* x) {
   return x->job != DynJob::Train && x->n > 0 && 2 * x->n <= 3 * (uint64_t)x->a->n_cus * dynk::WAVES_PER_CU;
 }
 static bool same_kind(const dyn_batch* x, const dyn_batch* y) {
-  if (x->job != y->job || x->has_raw != y->has_raw || x->ev_want != y->ev_want) return false;
+  if (x->job != y->job || x->has_raw != y->has_raw || x->ev_want != y->ev_want || x->rs_want != y->rs_want) return false;
   if (!x->has_raw) return true;
   const RawSource &p = x->raw_src, &q = y->raw_src;
   return p.vbz == q.vbz && p.dtype == q.dtype && p.window == q.window && p.n_sigmas == q.n_sigmas && p.compute_f32 == q.compute_f32;
@@ -211,6 +211,7 @@ std::shared_ptr<BatchGroup> Pipeline::merge(const std::vector<dyn_batch*>& ticke
   g->n = n;
   g->job = first->job;
   g->ev_want = first->ev_want;  // (same_kind: every member asked alike)
+  g->rs_want = first->rs_want;
   g->in_sig_offsets = grp->sig_offsets.data();
   g->in_seqs = grp->seqs.data();
   g->in_seq_offsets = grp->seq_offsets.data();
@@ -754,6 +755,7 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
   b->async = true;
   b->job = job;
   b->ev_want = a->event_stats;
+  b->rs_want = a->rescale_iters;
   b->in_signals = signals;
   if (rs) {
     b->has_raw = true;

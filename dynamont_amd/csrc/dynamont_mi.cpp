@@ -59,7 +59,7 @@ void attach_cache(dyn_batch* b) {
   dyneng::BufCache* c = &b->a->cache;
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_norm, &b->d_meta, &b->d_wide})
+                    &b->d_pathn, &b->d_ev, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_wide})
     d->cache = c;
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->cache = c;
 }
@@ -528,6 +528,17 @@ int dyn_aligner_set_event_stats(dyn_aligner* a, int on) {
   return DYN_OK;
 }
 
+int dyn_aligner_set_rescale(dyn_aligner* a, int iters) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  if (iters < 0 || iters > DYN_RESCALE_MAX_ITERS) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = "dyn_aligner_set_rescale: iters must be 0 .. 8, got " + std::to_string(iters);
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  a->rescale_iters = iters;
+  return DYN_OK;
+}
+
 }  // extern "C"
 
 namespace dyneng {
@@ -772,7 +783,7 @@ void dyn_batch_destroy(dyn_batch* b) {
   if (b->a && !b->a->host_only) (void)hipSetDevice(b->a->device);
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_norm, &b->d_meta, &b->d_tctl})
+                    &b->d_pathn, &b->d_ev, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl})
     d->release();
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->release();
   for (hipEvent_t e : b->events) (void)hipEventDestroy(e);
@@ -912,6 +923,7 @@ int run_job_sync(dyn_batch* b, DynJob job) {
     int rc = need_device(a);
     if (rc != DYN_OK) return rc;
     b->ev_want = a->event_stats;
+    b->rs_want = a->rescale_iters;
     rc = enqueue_job(b, job);
     if (rc != DYN_OK) {
       (void)hipStreamSynchronize(a->stream);
@@ -1028,6 +1040,35 @@ int dyn_batch_fetch_events(dyn_batch* b, dyn_event_out* out) {
   HIP_TRY(a, copy_out(a, out->mean, e, b->capacity * 8));
   HIP_TRY(a, copy_out(a, out->stdev, e + src->capacity, b->capacity * 8));
   HIP_TRY(a, copy_out(a, out->median, e + 2 * src->capacity, b->capacity * 8));
+  return DYN_OK;
+}
+
+int dyn_batch_fetch_rescale(dyn_batch* b, dyn_rescale_out* out) {
+  if (!b || !out || !out->shift || !out->scale || !out->iters_applied) return DYN_ERR_INVALID_ARGUMENT;
+  dyn_aligner* a = b->a;
+  // a member of a merged launch: reads [g_read0, g_read0 + n) of the group's transforms
+  const dyn_batch* src = (b->group && b->group->g) ? b->group->g : b;
+  const uint64_t read0 = src == b ? 0 : b->g_read0;
+  if (!b->aligned || !b->last_calc || !src->rs_ready) {
+    a->last_error = !b->aligned || !b->last_calc
+                        ? "dyn_batch_fetch_rescale: the batch was not aligned with calc_probabilities = 1"
+                        : "dyn_batch_fetch_rescale: the batch was submitted without dyn_aligner_set_rescale(a, iters > 0)";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  if (out->n < b->n) {
+    a->last_error = "dyn_rescale_out.n is smaller than the batch's read count";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  int rc = need_device(a);
+  if (rc != DYN_OK) return rc;
+  if (!b->n) return DYN_OK;
+  std::vector<dynk::RescaleState> h(b->n);
+  HIP_TRY(a, copy_out(a, h.data(), src->d_rs.as<dynk::RescaleState>() + read0, b->n * sizeof(dynk::RescaleState)));
+  for (uint64_t i = 0; i < b->n; ++i) {
+    out->shift[i] = h[i].A;
+    out->scale[i] = h[i].B;
+    out->iters_applied[i] = h[i].applied;
+  }
   return DYN_OK;
 }
 

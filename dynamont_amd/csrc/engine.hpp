@@ -147,6 +147,7 @@ struct dyn_aligner {
   int strict_mode = 1;  // dyn_aligner_set_strict: reads with a structural tie run bit for bit by default
   bool train_zcheck = false;  // dyn_aligner_set_train_zcheck
   bool event_stats = false;   // dyn_aligner_set_event_stats: read by every batch / ticket at its submission
+  int rescale_iters = 0;      // dyn_aligner_set_rescale (0 .. 8): read by every batch / ticket at its submission
   bool ntk = false;     // created with mode "resquiggle" / "ntk"
   std::string last_error;
   // grow-only lattice workspace pool, reused across batches (only ever touched by work on `stream`,
@@ -238,6 +239,14 @@ struct dyn_batch {
   dyneng::DevBuf d_ev;                         // [3][capacity] level mean / stdev / median (event_stats.hip), when asked for
   bool ev_want = false;                        // the handle's event-stats switch when this batch / ticket was submitted
   bool ev_ready = false;                       // the last job computed the event columns into d_ev
+  // per-read rescaling (rescale.hip, dyn_aligner_set_rescale)
+  dyneng::DevBuf d_sig0;                       // the preprocessed signal x0, kept while d_sig holds a rescaled one
+  dyneng::DevBuf d_rs;                         // [n] dynk::RescaleState | [capacity] row means of the fit (scratch)
+  int rs_want = 0;                             // the handle's rescale iterations when this batch / ticket was submitted
+  bool rs_ready = false;                       // the last job ran its passes: d_rs holds the per-read transforms
+  bool sig0_kept = false;                      // d_sig0 holds x0 (a synchronous batch aligned again starts from it)
+  uint64_t sig0_len = 0;                       // samples kept in d_sig0
+  int n_passes = 1;                            // alignment passes of the last job (h_stats holds one record each)
   dyneng::PinnedBuf h_descs, h_state, h_rows;  // h_state/h_rows: D2H targets of the asynchronous path
   dyneng::PinnedBuf h_stats;                   // wave-cycle statistics of the read-queue launch
   dyneng::PinnedBuf h_sig;                     // staging of pageable caller signals (asynchronous path)

@@ -508,8 +508,34 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   HIP_TRY(a, b->d_descs.ensure(std::max<size_t>(sizeof(ReadDesc), n_all * sizeof(ReadDesc))));
   if (n_all)
     HIP_TRY(a, hipMemcpyAsync(b->d_descs.p, descs, n_all * sizeof(ReadDesc), hipMemcpyHostToDevice, a->stream));
-  HIP_TRY(a, b->h_stats.ensure(dynk::QUEUE_CTL_WORDS * 4));
-  std::memset(b->h_stats.p, 0, dynk::QUEUE_CTL_WORDS * 4);
+  // per-read rescaling (dyn_aligner_set_rescale): align(calc = 1) runs 1 + iters passes of everything below, in stream order
+  const int iters = calc ? b->rs_want : 0;
+  const int n_pass = 1 + iters;
+  HIP_TRY(a, b->h_stats.ensure((size_t)n_pass * dynk::QUEUE_CTL_WORDS * 4));
+  std::memset(b->h_stats.p, 0, (size_t)n_pass * dynk::QUEUE_CTL_WORDS * 4);
+  // x0 is kept apart the first time a job of this batch rescales; every later job of the batch starts from it again
+  uint64_t sig_len = 0;
+  for (uint64_t i = 0; i < b->n; ++i) sig_len = std::max<uint64_t>(sig_len, b->reads[i].sig_off + b->reads[i].S);
+  sig_len = std::min<uint64_t>(sig_len, b->d_sig.bytes / 8);
+  if (b->sig0_kept) {
+    if (b->sig0_len) HIP_TRY(a, hipMemcpyAsync(b->d_sig.p, b->d_sig0.p, b->sig0_len * 8, hipMemcpyDeviceToDevice, a->stream));
+  } else if (iters) {
+    HIP_TRY(a, b->d_sig0.ensure(std::max<uint64_t>(8, sig_len * 8)));
+    if (sig_len) HIP_TRY(a, hipMemcpyAsync(b->d_sig0.p, b->d_sig.p, sig_len * 8, hipMemcpyDeviceToDevice, a->stream));
+    b->sig0_kept = true;
+    b->sig0_len = sig_len;
+  }
+  b->rs_ready = iters > 0;
+  dynk::RescaleState* rs = nullptr;
+  double* rs_y = nullptr;
+  if (iters) {
+    const uint64_t head = (b->n * sizeof(dynk::RescaleState) + 255) / 256 * 256;
+    HIP_TRY(a, b->d_rs.ensure(std::max<uint64_t>(256, head + b->capacity * 8)));
+    rs = b->d_rs.as<dynk::RescaleState>();
+    rs_y = reinterpret_cast<double*>(b->d_rs.as<char>() + head);
+    dynk::launch_rescale_init(rs, b->n, a->stream);
+  }
+  b->n_passes = n_pass;
 
   while (b->events.size() < 3) {
     hipEvent_t e = nullptr;
@@ -538,40 +564,50 @@ int enqueue_job(dyn_batch* b, DynJob job) {
                               : lpe_separate       ? dynk::JOB_ALIGN
                                                    : dynk::JOB_ALIGN_INPLACE;
   if (!b->ev_done) HIP_TRY(a, hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
-  dynk::launch_pool_init(pool, used_pages, (int)n_static, a->stream);
-  HIP_TRY(a, hipEventRecord(ev[0], a->stream));
-  dynk::launch_read_queue(qjob, n_strict != 0, q, a->n_cus, a->stream);
-  HIP_TRY(a, hipEventRecord(ev[1], a->stream));
-  // the statistics leave the control words before the next batch's k_pool_init resets them (same stream)
-  HIP_TRY(a, hipMemcpyAsync(b->h_stats.p, pool.ctl, dynk::QUEUE_CTL_WORDS * 4, hipMemcpyDeviceToHost, a->stream));
-  // (Running the per-segment kernels on a stream of their own, beside the next batch's read queue, was measured:
-  //  the 0.35 ms gap it closes comes back as a 0.4 ms slower start of that read queue -- same-box A/B, no gain.)
-  if (!wide.empty()) {
-    // one workgroup per wide read at a time, each with a lattice arena for the largest of them; behind the read queue on the
-    // compute stream (its results feed the same per-segment kernels / the same host finalisation)
-    {
-      const uint64_t want = 256 + (uint64_t)wide_groups * wide_arena;
-      size_t free_b = 0, total_b = 0;
-      HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
-      if (want > b->d_wide.bytes && want > (uint64_t)((double)free_b * 0.95)) free_parked(a->device);  // (counted as room above)
-      HIP_TRY(a, b->d_wide.ensure(want));
+  // The plan above (order, pages, strict rows) depends on T, N and the k-mers only: every pass reuses it. Each pass resets
+  // what a launch resets -- per-read state, queue head and page pool (k_pool_init), the wide-band head (launch_wide_reads).
+  for (int pass = 0; pass < n_pass; ++pass) {
+    if (pass > 0 && b->n) HIP_TRY(a, hipMemcpyAsync(b->d_state.p, st, b->n * sizeof(ReadState), hipMemcpyHostToDevice, a->stream));
+    dynk::launch_pool_init(pool, used_pages, (int)n_static, a->stream);
+    if (pass == 0) HIP_TRY(a, hipEventRecord(ev[0], a->stream));
+    dynk::launch_read_queue(qjob, n_strict != 0, q, a->n_cus, a->stream);
+    if (pass + 1 == n_pass) HIP_TRY(a, hipEventRecord(ev[1], a->stream));
+    // the statistics leave the control words before the next pass's or batch's k_pool_init resets them (same stream)
+    HIP_TRY(a, hipMemcpyAsync(b->h_stats.as<uint32_t>() + (size_t)pass * dynk::QUEUE_CTL_WORDS, pool.ctl, dynk::QUEUE_CTL_WORDS * 4,
+                              hipMemcpyDeviceToHost, a->stream));
+    // (Running the per-segment kernels on a stream of their own, beside the next batch's read queue, was measured:
+    //  the 0.35 ms gap it closes comes back as a 0.4 ms slower start of that read queue -- same-box A/B, no gain.)
+    if (!wide.empty()) {
+      // one workgroup per wide read at a time, each with a lattice arena for the largest of them; behind the read queue on the
+      // compute stream (its results feed the same per-segment kernels / the same host finalisation)
+      if (pass == 0) {
+        const uint64_t want = 256 + (uint64_t)wide_groups * wide_arena;
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
+        if (want > b->d_wide.bytes && want > (uint64_t)((double)free_b * 0.95)) free_parked(a->device);  // (counted as room above)
+        HIP_TRY(a, b->d_wide.ensure(want));
+      }
+      dynk::WideArgs wa{};
+      wa.descs = q.descs + n_ok;
+      wa.n_reads = (int)wide.size();
+      wa.sig = q.sig;
+      wa.par = q.par;
+      wa.st = q.st;
+      wa.tb = q.tb;
+      wa.tr = q.tr;
+      wa.head = b->d_wide.as<uint32_t>();
+      wa.arena = b->d_wide.as<char>() + 256;
+      wa.arena_bytes = wide_arena;
+      wa.exp_tab = reinterpret_cast<const uint64_t*>(a->d_sptab.as<dynmath::SoftplusNode>() + dynmath::SP_NODES + dynmath::EXP128_NODES);
+      wa.m1 = m.log_m1;
+      wa.e2 = m.log_e2;
+      wa.z_fail_status = z_fail;
+      dynk::launch_wide_reads(job == DynJob::Train ? 2 : calc ? 1 : 0, wa, wide_groups, a->stream);
     }
-    dynk::WideArgs wa{};
-    wa.descs = q.descs + n_ok;
-    wa.n_reads = (int)wide.size();
-    wa.sig = q.sig;
-    wa.par = q.par;
-    wa.st = q.st;
-    wa.tb = q.tb;
-    wa.tr = q.tr;
-    wa.head = b->d_wide.as<uint32_t>();
-    wa.arena = b->d_wide.as<char>() + 256;
-    wa.arena_bytes = wide_arena;
-    wa.exp_tab = reinterpret_cast<const uint64_t*>(a->d_sptab.as<dynmath::SoftplusNode>() + dynmath::SP_NODES + dynmath::EXP128_NODES);
-    wa.m1 = m.log_m1;
-    wa.e2 = m.log_e2;
-    wa.z_fail_status = z_fail;
-    dynk::launch_wide_reads(job == DynJob::Train ? 2 : calc ? 1 : 0, wa, wide_groups, a->stream);
+    // between two passes: the fit of every read and its signal recomputed from x0. (The per-segment kernels run once, after
+    // the last pass: the fit reads the borders the traceback wrote, segrow, and nothing of k_median / k_final.)
+    if (pass + 1 < n_pass)
+      dynk::launch_rescale_pass(q.descs, (int)n_all, max_T, q.st, q.tb, b->d_sig0.as<double>(), b->d_sig.as<double>(), q.par, rs_y, rs, a->stream);
   }
   const int nr_all = (int)n_all;
   dynk::EventCols evc{};
@@ -627,12 +663,18 @@ int collect_timing(dyn_batch* b) {
   HIP_TRY(a, hipEventElapsedTime(&ms12, ev[1], ev[2]));
   // wave-cycles per phase, summed over all waves of the launch: backward, forward, traceback (+ state
   // write-back and page release), waiting for a read / for pages, lifetime; [5] = longest lifetime
-  if (b->h_stats.as<uint32_t>()[3] != 0) {
-    std::lock_guard<std::mutex> elk(a->err_mu);
-    a->last_error = "the read queue aborted: a wave waited for the queue lock or for lattice pages for seconds";
-    return DYN_ERR_DEVICE;
+  // one record per pass (dyn_aligner_set_rescale): the cycle counts are summed, the longest lifetime is the longest of any
+  uint64_t s[10] = {};
+  for (int p = 0; p < b->n_passes; ++p) {
+    const uint32_t* rec = b->h_stats.as<uint32_t>() + (size_t)p * dynk::QUEUE_CTL_WORDS;
+    if (rec[3] != 0) {
+      std::lock_guard<std::mutex> elk(a->err_mu);
+      a->last_error = "the read queue aborted: a wave waited for the queue lock or for lattice pages for seconds";
+      return DYN_ERR_DEVICE;
+    }
+    const uint64_t* sp = reinterpret_cast<const uint64_t*>(rec + dynk::QUEUE_STATS);
+    for (int k = 0; k < 10; ++k) s[k] = k == 5 ? std::max(s[k], sp[k]) : s[k] + sp[k];
   }
-  const uint64_t* s = reinterpret_cast<const uint64_t*>(b->h_stats.as<uint32_t>() + dynk::QUEUE_STATS);
   const double life = (double)s[4];
   tm.ms_dp = ms01;
   tm.ms_total = ms01 + ms12;

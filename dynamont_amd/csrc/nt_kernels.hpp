@@ -236,6 +236,20 @@ void launch_event_stats(const ReadDesc* descs, int n_reads, uint64_t rows_total,
 // `ev` asks for them
 void launch_segments(const ReadDesc* descs, int n_reads, uint64_t rows_total, uint32_t max_N, const ReadState* st,
                      TraceBuffers tb, SegRow* rows, int kmer_size, hipStream_t s, const EventCols& ev = EventCols{});
+// per-read signal rescaling (rescale.hip, dyn_aligner_set_rescale): the transform x = (x0 - A) / B of read `read`
+struct RescaleState {
+  double A;         // shift: 0.0 until a fit is applied
+  double B;         // scale: 1.0 until a fit is applied
+  int32_t applied;  // fits applied so far
+  int32_t frozen;   // a fit was refused (or the read failed): no later fit
+  int32_t fitted;   // the last fit was applied: k_rescale_apply recomputes the read's signal
+  int32_t pad;
+};
+void launch_rescale_init(RescaleState* rs, uint64_t n_reads, hipStream_t s);
+// between two passes: the fit of every read of descs (after the read queue and the wide-band kernel of the pass), then
+// sig = (sig0 - A) / B for the reads whose fit was applied. y: scratch column indexed like the output rows.
+void launch_rescale_pass(const ReadDesc* descs, int n_reads, uint32_t max_T, const ReadState* st, const TraceBuffers& tb,
+                         const double* sig0, double* sig, const Emis* par, double* y, RescaleState* rs, hipStream_t s);
 // pooled[3*num_kmers] (zeroed by the caller) = per-k-mer (w, s1, s2) of the ok reads in descs, summed in a FIXED order:
 // per read over its columns ascending, then over the reads in input order -- bit for bit the host's sum (pool_stats.hip).
 // work: pool_stats_work_bytes(total_cols) device bytes; temp: pool_stats_temp_bytes(...) (rocprim's radix sort).

@@ -176,7 +176,10 @@ bool session_candidate(const dyn_batch* b) {
   // waves; those statistics are computed on demand since (dyn_batch_device_pooled). Then, with nothing following a training
   // ticket, sessions measured 805.6 / 810.5 against 810.7 / 813.9 Msamp/s for one launch per batch: 1 024 reads on 1 024
   // waves keep a launch's waves busy 0.98 of it already. Training stays one launch per batch.
-  return a->sess_enabled.load() && !a->host_only && !a->ntk && b->async && b->job == DynJob::AlignFull &&
+  // Tickets that rescale (dyn_aligner_set_rescale) stay on one launch per batch as well: their passes run back to back in
+  // stream order (launch.cpp, enqueue_job), which costs what a session gains over it (README: 476 against 533 Msamp/s) for
+  // every pass. Publishing such a ticket into the session once per pass is a follow-up.
+  return a->sess_enabled.load() && !a->host_only && !a->ntk && b->async && b->job == DynJob::AlignFull && b->rs_want == 0 &&
          (a->sess_open_hint.load() || b->n >= SESSION_MIN_READS);
 }
 

@@ -87,6 +87,11 @@ def parse(argv=None) -> Namespace:
     p.add_argument("--event-stats", action="store_true",
                    help="add level_mean,level_stdv,level_median to every row: mean, population standard deviation and median "
                         "of the segment's samples of the normalised signal, in the model's units (computed on the GPU)")
+    p.add_argument("--rescale-iters", type=int, default=0, choices=range(0, 9), metavar="N",
+                   help="align every read N + 1 times (0 .. 8, default 0 = off), refitting the read's signal shift and scale "
+                        "on the GPU between the passes: a least-squares fit of the segment levels on the model levels. "
+                        "The rows are those of the last pass (with --event-stats, its levels). The CSV columns are unchanged; "
+                        "the per-read shift and scale are not written anywhere")
     p.add_argument("--parallel-zstd-frames", action="store_true",
                    help="write the CSV as consecutive independent zstd frames (readers must read across frames: "
                         "python-zstandard's defaults stop after the first). Default: one frame, like the reference, "
@@ -697,7 +702,7 @@ def _gather_parts(comm, parallel, outfile: str, part: str, part_err: str | None)
 def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_path: str, pore: str, mode: str,
             minq: float = 0, device: int = 0, batch_reads: int = 1024, mem_budget_gib: float = 0.0,
             host_preprocess: bool = False, depth: int = 12, strict_ties: str = "ties", host_threads: int = 0,
-            zstd_level: int = 3, event_stats: bool = False) -> None:
+            zstd_level: int = 3, event_stats: bool = False, rescale_iters: int = 0) -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
@@ -749,6 +754,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             aligner.set_strict(strict_ties)
             if event_stats:
                 aligner.set_event_stats(True)
+            if rescale_iters:
+                aligner.set_rescale(rescale_iters)
             if native:
                 import os
                 import tempfile
@@ -893,7 +900,7 @@ def main(argv=None) -> None:
     segment(args.raw, args.basecalls, args.processes, outfile, model_path, args.pore, args.mode, args.qscore,
             device=args.device, batch_reads=args.batch_reads, mem_budget_gib=args.mem_budget,
             host_preprocess=args.host_preprocess, depth=args.depth, strict_ties=args.strict_ties, host_threads=args.host_threads,
-            zstd_level=args.zstd_level, event_stats=args.event_stats)
+            zstd_level=args.zstd_level, event_stats=args.event_stats, rescale_iters=args.rescale_iters)
     _stamp("segment() returned (aligner closed)")
     if argv is None and not int(__import__("os").environ.get("WORLD_SIZE", "1") or 1) > 1:
         # Invoked as the command (console script / python -m), single process, everything written and closed: leave without

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DYN_ABI_VERSION 9 /* 9: per-segment signal levels: dyn_aligner_set_event_stats, dyn_batch_fetch_events, dyn_format_csv[_bound]_events, dyn_csv_sink_open_ex (additive). 8: dyn_aligner_session_idle_split (additive). 7: dyn_aligner_session_page_wait, dyn_comm_gather_bytes / _gathered_bytes / _allreduce_f64 (additive). 7: half bands 224 .. 2 046 are computed (wide_band.hip). 5: any band constructs (DYN_READ_BAND_TOO_WIDE per read); dyn_bam_*, dyn_csv_sink_wait / _open_part */
+#define DYN_ABI_VERSION 10 /* 10: per-read signal rescaling: dyn_aligner_set_rescale, dyn_batch_fetch_rescale (additive). 9: per-segment signal levels: dyn_aligner_set_event_stats, dyn_batch_fetch_events, dyn_format_csv[_bound]_events, dyn_csv_sink_open_ex (additive). 8: dyn_aligner_session_idle_split (additive). 7: dyn_aligner_session_page_wait, dyn_comm_gather_bytes / _gathered_bytes / _allreduce_f64 (additive). 7: half bands 224 .. 2 046 are computed (wide_band.hip). 5: any band constructs (DYN_READ_BAND_TOO_WIDE per read); dyn_bam_*, dyn_csv_sink_wait / _open_part */
 
 /* device argument of dyn_aligner_create: bind no GPU. Such a handle serves the host-side
  * contract only (model loading, dyn_aligner_info/_model, dyn_validate_batch); every compute
@@ -149,6 +149,30 @@ typedef struct dyn_event_out {
   double* median;  /* [capacity] level_median */
   uint64_t capacity;
 } dyn_event_out;
+
+/* (ABI 10) Per-read signal rescaling of an align(calc_probabilities = 1) job whose handle had dyn_aligner_set_rescale(a, K)
+ * with K > 0 when the batch was submitted. Read r is aligned K + 1 times. x0 = its preprocessed signal (what
+ * dyn_batch_signals returns with the switch off); A_0 = 0.0, B_0 = 1.0; pass k = 0 .. K aligns x_k, x_0 = x0 and
+ * x_k[i] = (x0[i] - A_k) / B_k (one IEEE subtraction, one IEEE division per sample). After pass k < K, for a read whose
+ * status is OK, over its n output rows in the order of dyn_align_out:
+ *   y_j = the row's level_mean over x_k (dyn_event_out: chunks of 64 samples)
+ *   m_j = the model level_mean of the k-mer whose emission scored the segment (the row's motif: lattice column n = j + 1,
+ *         basepos = n - 1 + k/2), from the handle's table the alignment scores with (dyn_aligner_set_model included)
+ *   mbar = S(m) / n, ybar = S(y) / n, Sxx = S((m - mbar)^2), Sxy = S((m - mbar) * (y - ybar)), b = Sxy / Sxx,
+ *   a = ybar - b * mbar
+ * S is a sum over the rows in chunks of 64 consecutive rows, each chunk left to right, the chunk sums left to right; every
+ * operation one IEEE fp64 operation, no FMA. The fit is applied only if n >= 16, Sxx > 0, a and b are finite,
+ * 0.5 <= b <= 2.0 and |a| <= 2.0: A_{k+1} = A_k + B_k * a (multiply, then add), B_{k+1} = B_k * b. Otherwise the read keeps
+ * its transform and all its later fits are skipped too. A read that fails in a pass gets no fit; its status and message are
+ * those of its last pass. Every result of the batch (rows, Z, probabilities, dyn_event_out, dyn_batch_signals) is that of
+ * the last pass, over x_K. */
+#define DYN_RESCALE_MAX_ITERS 8
+typedef struct dyn_rescale_out {
+  double* shift;           /* [n] A_K (0.0 for reads that were never fitted) */
+  double* scale;           /* [n] B_K (1.0 for reads that were never fitted) */
+  int32_t* iters_applied;  /* [n] fits applied */
+  uint64_t n;              /* entries of each array: at least the batch's read count */
+} dyn_rescale_out;
 
 /* Per-read training results (replaces dynamont::TrainingResult, aligner.hpp:48-53, whose
  * pybind form is a list of num_kmers dicts per read, aligner_bindings.cpp:86-107). The emission
@@ -323,6 +347,13 @@ int dyn_aligner_set_train_zcheck(dyn_aligner* a, int on);
  * the per-segment kernels, for every batch or ticket SUBMITTED while it is on (dyn_batch_align, dyn_batch_align*_async);
  * 3 x 8 bytes of device memory per segment row for those batches only. Default off: nothing else changes. */
 int dyn_aligner_set_event_stats(dyn_aligner* a, int on);
+/* (ABI 10) align(calc_probabilities = 1) of every batch or ticket SUBMITTED while iters > 0 runs 1 + iters passes with a
+ * per-read refit of the signal's shift and scale between them (dyn_rescale_out), all on the device with no host round trip.
+ * iters = 0 .. DYN_RESCALE_MAX_ITERS, default 0 = off (nothing changes); DYN_ERR_INVALID_ARGUMENT + message outside that
+ * range. Z-only jobs and train() ignore it. Such tickets always take one launch per batch, never the resident session.
+ * Each pass costs about one alignment; device memory: a copy of the batch's signal, 32 bytes per read, 8 per segment row.
+ * dyn_multi_*: set it on each device's handle (dyn_multi_handle). */
+int dyn_aligner_set_rescale(dyn_aligner* a, int iters);
 /* The rule of mode 1 for one read, given its k-mer codes (dyn_validate_batch) and signal length: 0 = no structural tie;
  * otherwise the number of forward rows that run in the strict arithmetic (UINT32_MAX: all of them). Host only. */
 uint32_t dyn_tie_rows(const dyn_aligner* a, const int32_t* kmers, uint64_t n_kmers, uint64_t signal_len);
@@ -536,6 +567,10 @@ int dyn_batch_fetch_train(dyn_batch* b, dyn_train_out* out, double* pooled3n);
  * (capacity >= dyn_segment_capacity()). DYN_ERR_INVALID_ARGUMENT + message for a batch submitted without
  * dyn_aligner_set_event_stats on, or aligned with calc_probabilities = 0. */
 int dyn_batch_fetch_events(dyn_batch* b, dyn_event_out* out);
+/* (ABI 10) Copy the per-read transforms of the last dyn_batch_align (or of a completed ticket, merged launch or not) into
+ * `out` (n >= the batch's read count). DYN_ERR_INVALID_ARGUMENT + message for a batch submitted with
+ * dyn_aligner_set_rescale(a, 0), or aligned with calc_probabilities = 0. */
+int dyn_batch_fetch_rescale(dyn_batch* b, dyn_rescale_out* out);
 /* Device-resident results of the last dyn_batch_align, for an RCCL gather without a host hop:
  * rows = dyn_segment_row[capacity] (read i at seg_offsets[i], as in dyn_align_out);
  * z_status = per read {double Z; int32 status; uint32 n_segments}. Pointers stay valid until the
@@ -644,7 +679,7 @@ int dyn_multi_create(const char* model_path, int pore, const char* mode, int thr
                      const int* device_ids, int n_devices, dyn_multi** out, char* err, uint64_t errcap);
 void dyn_multi_destroy(dyn_multi* m);
 int dyn_multi_device_count(const dyn_multi* m);
-/* the per-device handle (dyn_aligner_info, dyn_aligner_model, dyn_aligner_set_mem_budget, ...) */
+/* the per-device handle (dyn_aligner_info, dyn_aligner_model, dyn_aligner_set_mem_budget, dyn_aligner_set_rescale, ...) */
 dyn_aligner* dyn_multi_handle(dyn_multi* m, int i);
 const char* dyn_multi_last_error(const dyn_multi* m);
 int dyn_multi_align_batch(dyn_multi* m, uint64_t n_reads, const double* signals, const uint64_t* sig_offsets,
