@@ -548,15 +548,23 @@ namespace dyneng {
 // followed by A, any homopolymer of k+1 bases -- or distinct k-mers whose table entries coincide). Moving the border
 // between their segments leaves the exact score unchanged, so the traceback's comparison vE == vM_prev + LPE
 // (NT_aligner_api.cpp:445-448) is a tie in exact arithmetic wherever the path crosses them, decided by the last bits of
-// the reference's sums. Columns are compared by their (mean, stdev) bits, not by k-mer code.
+// the reference's sums. Columns are compared by their (mean, stdev) VALUES, not by k-mer code, and NEAR-duplicates count:
+// entries within TIE_TAU of each other in mean and in stdev leave the comparison a margin of the order of their gap, and
+// the plain arithmetic's ~1e-13 then decides some of them differently from the reference (fixture G15: 8 of 5 040 reads
+// on tables with gaps of 1e-12 .. 1e-16, all with a gap <= 1.2e-14). TIE_TAU = 1e-9 is the smallest decade at which the
+// reads left unflagged keep an on-path margin >= 1e-9 in the compiled reference (profiles/imperfect/decision_margins.json,
+// tie_rule_sweep); tables whose k-mers lie further apart (every model shipped with the reference, the synthetic bench
+// tables) flag exactly the reads they flagged under bit-equality.
 // Returns 0 for a read without such a pair; otherwise the number of forward rows that must be exact: up to the row in
 // which the LAST tied pair has left the band for good (no decision is taken on a column outside the band), UINT32_MAX
 // when that is the whole read. Z enters every posterior, so a flagged read's backward sweep is exact in full.
+static constexpr double TIE_TAU = 1e-9;
+static inline bool tie_close(double x, double y) { return x == y || std::fabs(x - y) <= TIE_TAU; }
 uint32_t tie_rows(const dynhost::PoreModel& m, const int32_t* km, uint64_t kc, uint64_t S) {
   int64_t last = -1;
   for (uint64_t j = 0; j + 1 < kc; ++j) {
     const int32_t a = km[j], b = km[j + 1];
-    if (a == b || (m.mean[a] == m.mean[b] && m.stdev[a] == m.stdev[b])) last = (int64_t)j;
+    if (a == b || (tie_close(m.mean[a], m.mean[b]) && tie_close(m.stdev[a], m.stdev[b]))) last = (int64_t)j;
   }
   if (last < 0) return 0;
   const uint64_t T = S + 1, N = kc + 1;

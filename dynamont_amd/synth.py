@@ -259,3 +259,110 @@ def write_dataset(outdir: str, name: str, reads: list[SynthRead], pore: str, see
             w.write("query_name\tsequence\tqs\tpi\tns\tts\tsp\tfn\tsm\tsd\n")
             w.writelines(rows)
     return raw, bam, expected
+
+
+# ---- reads and tables that stress a banded DP (fixture G15, tests/test_imperfect_reads.py) -----------------------------
+def imperfect_read(rng: np.random.Generator, mean_code: np.ndarray, sd_code: np.ndarray, k: int, n_bases: int,
+                   heavy: bool, p_sub: float, p_indel: float, rna: bool) -> SynthRead:
+    """One read whose basecall disagrees with its signal: the signal follows the true bases, the sequence handed to the
+    aligner carries ``p_sub`` substitutions and ``p_indel`` insertions + deletions (half each). ``heavy``: gamma dwell
+    (mean 10, shape 1.2) and one k-mer in a hundred stalls 10-40 times as long, so that the path strays from the band's
+    diagonal; else max(2, Poisson(10)). RNA reads start with the polyA pad, which the basecall keeps; DNA reads have none
+    (their first 9 bases are never mis-called either, so both kinds consume the generator alike)."""
+    digits = rng.integers(0, 4, size=n_bases)
+    if rna:
+        digits[:9] = 0
+    codes = _seq_codes(digits, k)
+    if heavy:
+        dw = 2 + np.floor(rng.gamma(1.2, 8.0 / 1.2, size=len(codes))).astype(np.int64)
+        stall = rng.random(len(codes)) < 0.01
+        dw[stall] *= rng.integers(10, 40, size=int(stall.sum()))
+    else:
+        dw = np.maximum(2, rng.poisson(10.0, size=len(codes)))
+    c = rng.uniform(0.8, 2.0)
+    idx = np.repeat(codes, dw)
+    sig = mean_code[idx] + c * sd_code[idx] * rng.standard_normal(len(idx))
+    called = []
+    for i, d in enumerate(digits):
+        if i < 9:
+            called.append(d)
+            continue
+        u = rng.random()
+        if u < p_indel / 2:
+            continue                                  # deletion
+        if u < p_indel:
+            called.append(int(rng.integers(0, 4)))    # insertion before the base
+        called.append(int(rng.integers(0, 4)) if rng.random() < p_sub else int(d))
+    return SynthRead(np.ascontiguousarray(sig), "".join(BASES[d] for d in called))
+
+
+def stress_variants(base: list[SynthRead], rng: np.random.Generator, sd_typ: float) -> list[SynthRead]:
+    """Seven reads per read of ``base``, in this order: spiky, far-out, permuted, reversed, flat, squeezed, mis-called."""
+    out = []
+    for r in base:
+        s = r.signal
+        spiky = s.copy()
+        spiky[rng.integers(0, len(s), size=len(s) // 37)] += 60 * sd_typ      # every cell of those rows below e^-300
+        out.append(SynthRead(spiky, r.sequence))
+        far = s.copy()
+        far[len(s) // 3] = 300.0                                                # ~2 000 sd away
+        far[len(s) // 2] = -5e3                                                 # log density -5e8
+        out.append(SynthRead(far, r.sequence))
+        out.append(SynthRead(np.ascontiguousarray(s[rng.permutation(len(s))]), r.sequence))   # fits nothing
+        out.append(SynthRead(np.ascontiguousarray(s[::-1]), r.sequence))
+        flat = np.full(len(s), float(np.median(s)))                             # no information at all
+        out.append(SynthRead(flat, r.sequence))
+        # all the k-mers of the first half squeezed into a tenth of the samples: the path hugs the band edge
+        cut = len(s) // 2
+        squeezed = np.concatenate([s[:cut:5], np.repeat(s[cut:], 2)[: len(s) - len(s[:cut:5])]])
+        out.append(SynthRead(np.ascontiguousarray(squeezed), r.sequence))
+        # what a basecaller does: 5 % substitutions, 3 % insertions / deletions against the signal's true sequence
+        seq = list(r.sequence)
+        called = seq[:9]
+        for ch in seq[9:]:
+            u = rng.random()
+            if u < 0.015:
+                continue
+            if u < 0.03:
+                called.append("ACGT"[rng.integers(0, 4)])
+            called.append("ACGT"[rng.integers(0, 4)] if rng.random() < 0.05 else ch)
+        out.append(SynthRead(s.copy(), "".join(called)))
+    return out
+
+
+STRESS_VARIANTS = ("spiky", "far_out", "permuted", "reversed", "flat", "squeezed", "miscalled")
+
+
+def near_duplicate_table(k: int, gap_exponents, seed: int, flavour: str = "mean", stdev: float = 0.15):
+    """(mean, stdev) per k-mer in FILE order for a table of near-duplicate entries: every k-mer takes the level of its base
+    COMPOSITION (how many A, C, G it holds: 56 levels for 5-mers, 220 for 9-mers, N(0, 1) draws), moved by
+    +-10^-e (1 + u), e picked per k-mer from ``gap_exponents``, u in [0, 1) -- in its mean (``flavour`` "mean") or in its
+    stdev ("stdev"). Consecutive k-mers of a sequence, b0..b(k-1) and b1..bk, have the same composition whenever b0 == bk:
+    a quarter of all neighbouring lattice columns of a random read carry distinct k-mers whose parameters lie 10^-e apart
+    (a composition is the same read forwards and backwards, so this holds for RNA and DNA pores alike). Two entries of one
+    cluster are bit-equal only where the gap is below the level's last bit (e >= 16)."""
+    if flavour not in ("mean", "stdev"):
+        raise ValueError(flavour)
+    n = 4 ** k
+    code = np.arange(n, dtype=np.int64)
+    counts = np.zeros((3, n), dtype=np.int64)
+    c = code.copy()
+    for _ in range(k):
+        d = c % 4
+        for b in range(3):
+            counts[b] += d == b
+        c //= 4
+    comp = (counts[0] * (k + 1) + counts[1]) * (k + 1) + counts[2]
+    rng = np.random.default_rng(seed)
+    level = rng.standard_normal((k + 1) ** 3)
+    exps = np.asarray(list(gap_exponents), dtype=np.float64)
+    e = exps[rng.integers(0, len(exps), size=n)]
+    sign = np.where(rng.random(n) < 0.5, -1.0, 1.0)
+    jitter = sign * 10.0 ** -e * (1.0 + rng.random(n))
+    mean = level[comp]
+    sd = np.full(n, float(stdev))
+    if flavour == "mean":
+        mean = mean + jitter
+    else:
+        sd = sd + jitter
+    return mean, sd

@@ -322,7 +322,8 @@ int dyn_aligner_set_mem_budget(dyn_aligner* a, uint64_t bytes);
  * read that starts with the polyA pad + A, any homopolymer of k+1 bases, distinct k-mers with coinciding table entries)
  * moving the border between their segments leaves the exact score unchanged: such a comparison is a tie in exact
  * arithmetic and the reference's choice rests on the last bits of glibc's exp/log1p inside logPlus (aligner.cpp:
- * 276-285). The plain kernels use a table softplus that is <= 1 ulp away from those and reproduce 3 397 of the 3 400
+ * 276-285). Entries within 1e-9 of each other in mean and in stdev are treated alike: there the comparison is no
+ * exact tie, but its margin is of the order of the gap and can lie below what the plain arithmetic resolves. The plain kernels use a table softplus that is <= 1 ulp away from those and reproduce 3 397 of the 3 400
  * such reads of tests/golden/g10_ties.npz. The strict kernels reproduce the reference's sums bit for bit at 1.3-1.4x
  * the price of a row ("certified arithmetic", dynamont_amd/csrc/dp_math_strict.hpp): the emission's quotient formed
  * exactly from stdev and 1/stdev, each logPlus from the table softplus plus a certificate that its rounded sum cannot

@@ -49,6 +49,8 @@ int64_t nto_debug_fb(const nto_model* m, const double* sig, uint64_t S, const ch
 double nto_last_decision_margin(void);
 /* the same over decisions between columns with different k-mers only (see nt_oracle.c) */
 double nto_last_decision_margin_distinct(void);
+/* the same over decisions between columns whose (mean, stdev) differ: the decisions of reads dyn_tie_rows leaves unflagged */
+double nto_last_decision_margin_distinct_params(void);
 /* row / column of the smallest margin and the two values compared there */
 void nto_last_decision_margin_at(uint64_t* t, uint64_t* n, double* vm, double* ve);
 

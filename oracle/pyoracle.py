@@ -70,6 +70,7 @@ class Oracle(_Base):
         L.nto_log_plus.argtypes = [C.c_double] * 2
         L.nto_last_decision_margin.restype = C.c_double
         L.nto_last_decision_margin_distinct.restype = C.c_double
+        L.nto_last_decision_margin_distinct_params.restype = C.c_double
         L.nto_last_decision_margin_at.argtypes = [_u64p, _u64p, _dp, _dp]
         err = self._err()
         self.h = L.nto_model_load(model_path.encode(), pore, band, err, self.ERRCAP)
@@ -126,6 +127,10 @@ class Oracle(_Base):
     def last_decision_margin_distinct(self) -> float:
         """The same over decisions between columns with different k-mers (structural ties excluded)."""
         return float(self.lib.nto_last_decision_margin_distinct())
+
+    def last_decision_margin_distinct_params(self) -> float:
+        """The same over decisions between columns whose (mean, stdev) differ: what dyn_tie_rows leaves unflagged."""
+        return float(self.lib.nto_last_decision_margin_distinct_params())
 
     def last_decision_margin_at(self):
         """(row, column, vM, vE) of the smallest margin of the last align(calc=True)."""

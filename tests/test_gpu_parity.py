@@ -992,7 +992,11 @@ def test_g13_decision_margin_families_in_the_default_mode(models, tmp_path, fami
     real 5-mer level), and configs[2]'s long DNA reads. The strict mode "ties" certifies a read only on IDENTICAL neighbouring
     parameters; everything else rests on the traceback's on-path margin (NT_aligner_api.cpp:445-448), which the fixture
     records per read from the compiled reference: its floor over all four families is 6e-7, seven orders above what the table
-    softplus can move. Every read runs here in the DEFAULT mode and must come out on the reference's borders."""
+    softplus can move -- on THESE tables, whose closest distinct entries are 1e-7 apart. The margin is not a constant of the
+    method: on tables with near-duplicate k-mers it goes down to 0 (fixture G15, tests/test_imperfect_reads.py), which is why
+    dyn_tie_rows flags neighbouring columns within 1e-9 of each other and unflagged reads are trusted only above that gap
+    (measured floor there: 3.67e-9 over 77 reads; on imperfect reads over ordinary tables: 4.4e-6). Every read runs here in the DEFAULT mode
+    and must come out on the reference's borders."""
     import json
     g = golden("g13_margin_families.npz")
     spec = json.loads(str(g["families"]))[family]

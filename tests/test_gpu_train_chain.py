@@ -65,37 +65,7 @@ def _check(al, orc, reads, tag):
     return ok
 
 
-def _variants(base, rng, sd_typ):
-    out = []
-    for r in base:
-        s = r.signal
-        spiky = s.copy()
-        spiky[rng.integers(0, len(s), size=len(s) // 37)] += 60 * sd_typ      # every cell of those rows below e^-300
-        out.append(synth.SynthRead(spiky, r.sequence))
-        far = s.copy()
-        far[len(s) // 3] = 300.0                                                # ~2 000 sd away
-        far[len(s) // 2] = -5e3                                                 # log density -5e8
-        out.append(synth.SynthRead(far, r.sequence))
-        out.append(synth.SynthRead(np.ascontiguousarray(s[rng.permutation(len(s))]), r.sequence))   # fits nothing
-        out.append(synth.SynthRead(np.ascontiguousarray(s[::-1]), r.sequence))
-        flat = np.full(len(s), float(np.median(s)))                             # no information at all
-        out.append(synth.SynthRead(flat, r.sequence))
-        # all the k-mers of the first half squeezed into a tenth of the samples: the path hugs the band edge
-        cut = len(s) // 2
-        squeezed = np.concatenate([s[:cut:5], np.repeat(s[cut:], 2)[: len(s) - len(s[:cut:5])]])
-        out.append(synth.SynthRead(np.ascontiguousarray(squeezed), r.sequence))
-        # what a basecaller does: 5 % substitutions, 3 % insertions / deletions against the signal's true sequence
-        seq = list(r.sequence)
-        called = seq[:9]
-        for ch in seq[9:]:
-            u = rng.random()
-            if u < 0.015:
-                continue
-            if u < 0.03:
-                called.append("ACGT"[rng.integers(0, 4)])
-            called.append("ACGT"[rng.integers(0, 4)] if rng.random() < 0.05 else ch)
-        out.append(synth.SynthRead(s.copy(), "".join(called)))
-    return out
+_variants = synth.stress_variants
 
 
 @pytest.mark.parametrize("pore,nb", [("rna004", (250, 420)), ("dna_r9", (150, 400)), ("rna002", (100, 300))])

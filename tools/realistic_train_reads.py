@@ -17,31 +17,7 @@ from dynamont_amd import Aligner, synth  # noqa: E402
 
 
 def make(rng, mean_code, sd_code, k, n_bases, heavy, p_sub, p_indel):
-    digits = rng.integers(0, 4, size=n_bases)
-    digits[:9] = 0
-    codes = synth._seq_codes(digits, k)
-    if heavy:  # gamma dwell (mean 10, shape 1.2) and one k-mer in a hundred stalls 10-40 times as long
-        dw = 2 + np.floor(rng.gamma(1.2, 8.0 / 1.2, size=len(codes))).astype(np.int64)
-        stall = rng.random(len(codes)) < 0.01
-        dw[stall] *= rng.integers(10, 40, size=int(stall.sum()))
-    else:
-        dw = np.maximum(2, rng.poisson(10.0, size=len(codes)))
-    c = rng.uniform(0.8, 2.0)
-    idx = np.repeat(codes, dw)
-    sig = mean_code[idx] + c * sd_code[idx] * rng.standard_normal(len(idx))
-    # what the basecaller reports: the true bases with errors (the polyA pad stays)
-    called = []
-    for i, d in enumerate(digits):
-        if i < 9:
-            called.append(d)
-            continue
-        u = rng.random()
-        if u < p_indel / 2:
-            continue                                  # deletion
-        if u < p_indel:
-            called.append(int(rng.integers(0, 4)))    # insertion before the base
-        called.append(int(rng.integers(0, 4)) if rng.random() < p_sub else int(d))
-    return synth.SynthRead(np.ascontiguousarray(sig), "".join(synth.BASES[d] for d in called))
+    return synth.imperfect_read(rng, mean_code, sd_code, k, n_bases, heavy, p_sub, p_indel, rna=True)
 
 
 def main():
