@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("DYN_LIB_PATH") or os.path.join(HERE, "libdynamont_mi.so")
 SOURCES = ["dynamont_mi.cpp", "buffers.cpp", "launch.cpp", "session.cpp", "async_engine.cpp", "pore_model.cpp", "csv_format.cpp", "csv_sink.cpp", "vbz_decode.cpp", "bam_reader.cpp", "rccl_comm.cpp", "model_format.cpp",
            "nt_kernels.hip", "pool_stats.hip", "wide_band.hip", "event_stats.hip", "rescale.hip"]
-HEADERS = ["engine.hpp", "engine_internal.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
+HEADERS = ["engine.hpp", "engine_internal.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "dp_cell.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
 
 DYN_DEVICE_HOST_ONLY = -2
 DYN_CSV_EVENT_STATS = 0x1  # dyn_csv_sink_open_ex flag
@@ -210,6 +210,13 @@ def hipcc_path() -> str:
     return "hipcc"
 
 
+def hipcc_flags() -> list:
+    """The flags every translation unit of the product is compiled with (tests/test_gpu_cell_math.py compiles its
+    device-side test unit with exactly these, so that it runs the arithmetic as the library's kernels do)."""
+    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result", "-pthread"]
+    return flags + os.environ.get("DYN_HIPCC_EXTRA", "").split()  # kernel experiments: -DDYN_EXP_...
+
+
 def needs_build() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
@@ -226,8 +233,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         return LIB_PATH  # (a library named by DYN_LIB_PATH is built by whoever named it)
     import hashlib
     from concurrent.futures import ThreadPoolExecutor
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result", "-pthread"]
-    flags += os.environ.get("DYN_HIPCC_EXTRA", "").split()  # kernel experiments: -DDYN_EXP_...
+    flags = hipcc_flags()
     objdir = os.path.join(os.path.dirname(HERE), "build", "obj", hashlib.sha1(" ".join(flags).encode()).hexdigest()[:12])
     os.makedirs(objdir, exist_ok=True)
     newest_header = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS if os.path.exists(os.path.join(CSRC, h)))

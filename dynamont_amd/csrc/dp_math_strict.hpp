@@ -18,8 +18,8 @@
 //
 // tests/test_dp_math.py compiles this header with g++ and compares both functions with libm on > 1e7 arguments
 // (0 differing bits); tests/tie_parity.py mode 6 replays the oracle's control flow with them (0 differing reads).
-// Every operation is a single IEEE fp64 operation, so the device build (hipcc -ffp-contract=off, IEEE division)
-// produces the same bits.
+// Every operation is a single IEEE fp64 operation; that the device build (hipcc -ffp-contract=off, IEEE division) gives
+// the host build's bits is checked function by function on an MI355X by tests/test_gpu_cell_math.py.
 #pragma once
 
 #include <cstdint>

@@ -267,6 +267,93 @@ double softplus_gap(long n, uint64_t seed, double* absmax_below) {
   *absmax_below = below;
   return worst;
 }
+
+// ---- plain evaluations, 7 cells at a time: the host side of tests/test_gpu_cell_math.py, which runs the same headers on the
+// device (tests/device_math/cell_math.hip, same operations in the same order) and compares bit patterns ----
+#define SEVENS(i) for (long i = 0; i + 7 <= n; i += 7)
+#define LOAD7(v, src) for (int j = 0; j < 7; ++j) v[j] = src[i + j]
+#define STORE7(dst, v) for (int j = 0; j < 7; ++j) dst[i + j] = v[j]
+static const double* exp128() { static double T[EXP128_SIZE]; static bool init = false; if (!init) { exp128_build_table(T); init = true; } return T; }
+void ev_libm_exp(const double* x, double* o, long n) { for (long i = 0; i < n; ++i) o[i] = std::exp(x[i]); }
+void ev_ref_log_plus(const double* x, const double* y, double* o, long n) { for (long i = 0; i < n; ++i) o[i] = ref_log_plus(x[i], y[i]); }
+void ev_exp_strict(const double* x, double* o, long n) {
+  SEVENS(i) { double a[7], r[7]; LOAD7(a, x); exp_strict_vec<7>(a, r, strict_exp_table()); STORE7(o, r); } }
+void ev_log1p_strict(const double* x, double* o, long n) {
+  SEVENS(i) { double a[7], r[7]; LOAD7(a, x); log1p_strict_vec<7>(a, r); STORE7(o, r); } }
+void ev_log_plus_strict(const double* x, const double* y, double* o, double* o_from, long n) {
+  SEVENS(i) {
+    double a[7], b[7], r[7]; LOAD7(a, x); LOAD7(b, y);
+    log_plus_strict_vec<7>(a, b, r, strict_exp_table()); STORE7(o, r);
+    SoftplusLookup<7> L; log_plus_issue<7>(a, b, L, tab());
+    for (int j = 0; j < 7; ++j) o_from[i + j] = log_plus_strict_from(L.hi[j], L.diff[j], strict_exp_table());
+  } }
+// inv = RN(1 / sd) and nls = -log(sd) come from the caller, as the kernels get them from the model load
+void ev_pdf_strict(const double* x, const double* mean, const double* sd, const double* inv, const double* nls, double* o_strict,
+                   double* o_cert, double* o_cert4, double* o_q5, double* o_q4, double* o_q, long n) {
+  SEVENS(i) {
+    EmisV<7> p; double st[7], yl[7], o[7];
+    for (int j = 0; j < 7; ++j) {
+      const Emis e{mean[i + j], inv[i + j], nls[i + j], sd[i + j]};
+      p.set(j, e); st[j] = e.stdev; yl[j] = recip_lo(e.stdev, e.inv_stdev);
+      o_strict[i + j] = log_normal_pdf_strict(x[i + j], e);
+      const double d = x[i + j] - e.mean;
+      o_q5[i + j] = div_by_const(d, e.stdev, e.inv_stdev);
+      o_q4[i + j] = div_by_const4(d, e.stdev, e.inv_stdev, yl[j]);
+      o_q[i + j] = d / e.stdev;
+    }
+    for (int j = 0; j < 7; ++j) {
+      log_normal_pdf_cert_vec<7>(x[i + j], p, st, o); o_cert[i + j] = o[j];
+      log_normal_pdf_cert4_vec<7>(x[i + j], p, st, yl, o); o_cert4[i + j] = o[j];
+    }
+  } }
+void ev_log_plus_table(const double* x, const double* y, double* o5, double* o3, long n) {
+  SEVENS(i) {
+    double a[7], b[7], r[7]; LOAD7(a, x); LOAD7(b, y);
+    SoftplusLookup<7> L; log_plus_issue<7>(a, b, L, tab());
+    log_plus_finish<7>(L, r); STORE7(o5, r);
+    log_plus_finish3<7>(L, r); STORE7(o3, r);
+  } }
+void ev_softplus_table(const double* d, double* o5, double* o3, long n) {
+  SEVENS(i) {
+    double a[7], r[7]; LOAD7(a, d);
+    softplus_table_vec<7>(a, r, tab()); STORE7(o5, r);
+    softplus_table3_vec<7>(a, r, tab()); STORE7(o3, r);
+  } }
+void ev_pdf_vec(const double* x, const double* mean, const double* inv, const double* nls, double* o, long n) {
+  SEVENS(i) {
+    EmisV<7> p; double r[7];
+    for (int j = 0; j < 7; ++j) p.set(j, Emis{mean[i + j], inv[i + j], nls[i + j], 0.0});
+    for (int j = 0; j < 7; ++j) { log_normal_pdf_vec<7>(x[i + j], p, r); o[i + j] = r[j]; }
+  } }
+// the training sweep's exponential, and its value clipped to 1 as forward_train_chain clips it
+void ev_exp128(const double* x, double* o, double* o_min, long n) {
+  SEVENS(i) {
+    double a[7], r[7]; LOAD7(a, x);
+    exp_table128_vec<7>(a, r, exp128()); STORE7(o, r);
+    for (int j = 0; j < 7; ++j) o_min[i + j] = min_hw(r[j], 1.0);
+  } }
+// the training sweep's folded emission (dp_cell.hpp, set_emis<ARITH_FOLDED> + emission_vec<ARITH_FOLDED>: device code, so its
+// preparatory product and difference and its three operations are repeated here): ln P = ln K - u^2, u = (x - mean) c,
+// c = 1 / (stdev sqrt 2)
+void ev_emis_folded(const double* x, const double* mean, const double* inv, const double* nls, double* o, long n) {
+  for (long i = 0; i < n; ++i) {
+    const double c = inv[i] * 0x1.6a09e667f3bcdp-1, k = nls[i] - HALF_LOG_2PI;
+    double u = x[i] - mean[i];
+    u = u * c;
+    o[i] = fma_(-u, u, k);
+  } }
+// the certified logPlus cell by cell: o = its result (fallback included), o_lo = the lower end of the certificate (what a
+// kernel without the fallback would keep), amb = 1 where the certificate failed
+void ev_log_plus_cert(const double* x, const double* y, double* o, double* o_lo, unsigned char* amb, long n) {
+  for (long i = 0; i < n; ++i) {
+    double a[1] = {x[i]}, b[1] = {y[i]}, l[1], h[1];
+    SoftplusLookup<1> L;
+    log_plus_issue<1>(a, b, L, tab());
+    log_plus_finish_cert<1>(L, l, h);
+    o_lo[i] = l[0];
+    amb[i] = !(l[0] == h[0]);
+    o[i] = log_plus_cert(x[i], y[i], tab(), strict_exp_table(), nullptr);
+  } }
 }
 ''' % ROOT
 
