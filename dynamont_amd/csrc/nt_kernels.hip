@@ -47,6 +47,7 @@
 
 #include <algorithm>
 
+#include "band_runs.hpp"
 #include "dp_cell.hpp"
 #include "dp_math_strict.hpp"
 
@@ -151,10 +152,8 @@ constexpr bool SKIP_OOB = false;
 // sweep fetches those of [lo, lo + W + OOB_SLACK) -- always inside what was stored, always containing the fetched row's band.
 constexpr int OOB_SLACK = 5;
 
-// size_t(t * RATIO): one IEEE fp64 multiply, then truncation (NT_aligner_api.cpp:100).
-__device__ __forceinline__ int band_mid(int t, double ratio) {
-  return (int)__dmul_rn((double)t, ratio);
-}
+// size_t(t * RATIO): one IEEE fp64 multiply, then truncation (NT_aligner_api.cpp:100); band_runs.hpp
+using dynband::band_mid;
 
 __device__ __forceinline__ double readlane_f64(double v, int l) {
   int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
@@ -356,6 +355,7 @@ __device__ __forceinline__ double backward_sweep(const ReadDesc& rd, const WaveC
 
   bool bad_sample = false;
   int lo = band_mid(T - 1, ratio) - bw;
+  const double inv_ratio = 1.0 / ratio;  // seeds the run-length prediction only (band_runs.hpp)
   // DYN_SKIP_OOB: the lanes whose row stores count (align jobs: the forward sweep fetches exactly these or fewer)
   constexpr bool MASKED = SKIP_OOB && STORE && ARITH != ARITH_FOLDED;
   uint64_t store_mask = MASKED ? uniform_u64(lanes_of_window(lo - OOB_SLACK, W + 2 * OOB_SLACK)) : ~0ull;
@@ -402,8 +402,38 @@ __device__ __forceinline__ double backward_sweep(const ReadDesc& rd, const WaveC
     emission_vec<ARITH>(readlane_f64(xs, 63), p, p_stdev, p_ylo, e);  // e(thi+1, n) from sig[thi]
     // one lattice row: reads (bE_in, bM_in) = row t+1, writes (bE_out, bM_out) = row t; the loop is unrolled by two and
     // ping-pongs between the two pairs (see forward_sweep: no register moves at the loop's back edge)
-    auto row = [&](int i, const double (&bE_in)[CPL], const double (&bM_in)[CPL], double (&bE_out)[CPL], double (&bM_out)[CPL]) {
-      const int t = base + i;
+    // The window moves down by one column in front of row t (wave-uniform). Runs BETWEEN rows: the row reads n[] and p only
+    // in its look-ahead emission e(t, .), and e[] = e(t+1, .) is already computed with the parameters of row t+1's window.
+    auto hand_over = [&](int new_lo) {
+      const int leaving = lo + P - 1;
+      const int top = lo + W - 1;  // last band column of row t+1: above the band of row t
+      // uniform address, outside the per-lane branch: a scalar load (lgkmcnt). A vector load here
+      // makes hipcc guard every later read of p with s_waitcnt vmcnt(0) in EVERY row.
+      const Emis fresh = load_emis(pr, new_lo, N);
+      const Emis none = load_emis(pr, 0, 0);
+#pragma unroll
+      for (int j = 0; j < CPL; ++j) {
+        if (n[j] == leaving) {
+          n[j] = new_lo;
+          set_p(j, fresh);
+        }
+        // Upper band edge: bM(t, top) = bE(t+1, top) + e must not see the in-band cell (t+1, top), while Y keeps
+        // bM(t+1, top) + e for the diagonal into (t, top-1). bE(t+1, top) has no other reader left (row t+1 is stored):
+        // it becomes -inf here, and -inf + e = -inf (e is a log-density or -inf, never +inf). From row t on the slot
+        // carries the "no k-mer" parameters, so e = -inf and with it bM = Y = -inf for every column above the band
+        // without a per-row select -- including the slot of column lo+P-1, whose bE picks up a finite x1 from its
+        // ring neighbour, band column lo, in every row (the slot ring wraps) and is emptied by e = -inf before
+        // anything reads it.
+        if (n[j] == top) {
+          bE[j] = NEG_INF;
+          set_p(j, none);
+        }
+      }
+      lo = new_lo;
+      if constexpr (MASKED) store_mask = uniform_u64(lanes_of_window(lo - OOB_SLACK, W + 2 * OOB_SLACK));
+    };
+    auto row = [&](int t, const double (&bE_in)[CPL], const double (&bM_in)[CPL], double (&bE_out)[CPL], double (&bM_out)[CPL]) {
+      const int i = t - base;
       // e[] = e(t+1, n) was computed during the previous row's table lookups (software pipeline)
       double Y[CPL], Yr[CPL], x1[CPL], x2[CPL];
 #pragma unroll
@@ -411,34 +441,6 @@ __device__ __forceinline__ double backward_sweep(const ReadDesc& rd, const WaveC
 #pragma unroll
       for (int j = 0; j < CPL; ++j) bM_out[j] = bE_in[j] + e[j];  // bM(t, n) ("A" below)
       from_right(Y, Yr);
-      const int new_lo = band_mid(t, ratio) - bw;
-      if (__builtin_expect(new_lo != lo, 0)) {  // wave-uniform: the window moved down by one column
-        const int leaving = lo + P - 1;
-        const int top = lo + W - 1;  // last band column of row t+1: above the band of row t
-        // uniform address, outside the per-lane branch: a scalar load (lgkmcnt). A vector load here
-        // makes hipcc guard every later read of p with s_waitcnt vmcnt(0) in EVERY row.
-        const Emis fresh = load_emis(pr, new_lo, N);
-        const Emis none = load_emis(pr, 0, 0);
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) {
-          if (n[j] == leaving) {
-            n[j] = new_lo;
-            set_p(j, fresh);
-          }
-          // Upper band edge: bM(t, top) = A must not see the in-band cell (t+1, top); Y keeps it for
-          // the diagonal into (t, top-1). From row t on the slot carries the "no k-mer" parameters, so
-          // e = -inf and with it A = Y = -inf for every column above the band without a per-row
-          // select -- including the slot of column lo+P-1, whose bE picks up a finite x1 from its
-          // ring neighbour, band column lo, in every row (the slot ring wraps) and is emptied by
-          // e = -inf before anything reads it.
-          if (n[j] == top) {
-            bM_out[j] = NEG_INF;
-            set_p(j, none);
-          }
-        }
-        lo = new_lo;
-        if constexpr (MASKED) store_mask = uniform_u64(lanes_of_window(lo - OOB_SLACK, W + 2 * OOB_SLACK));
-      }
 #pragma unroll
       for (int j = 0; j < CPL; ++j) x1[j] = Yr[j] + m1;
 #pragma unroll
@@ -475,18 +477,29 @@ __device__ __forceinline__ double backward_sweep(const ReadDesc& rd, const WaveC
         }
       }
     };
-    int i = 63;
+    // The block's rows in RUNS, top-down: maximal spans of rows t with band_mid(t) - bw == lo, the hand-over in front of a
+    // run's first row and no window test inside a run (see forward_sweep).
+    int t = thi;
+    const int tlo = base + ilo;  // the block's lowest row
 #pragma unroll 1
-    for (; i - 1 >= ilo; i -= 2) {
-      row(i, bE, bM, bE2, bM2);
-      row(i - 1, bE2, bM2, bE, bM);
-    }
-    if (i >= ilo) {  // odd number of rows (first block of a read only)
-      row(i, bE, bM, bE2, bM2);
+    while (t >= tlo) {
+      const int new_lo = band_mid(t, ratio) - bw;
+      if (new_lo != lo) hand_over(new_lo);
+      // the run's lowest row (band_runs.hpp: predicted with one multiply, confirmed with band_mid itself)
+      const int tq = __builtin_amdgcn_readfirstlane(dynband::run_first_row(t, ratio, inv_ratio, tlo));
+#pragma unroll 1
+      for (; t - 1 >= tq; t -= 2) {
+        row(t, bE, bM, bE2, bM2);
+        row(t - 1, bE2, bM2, bE, bM);
+      }
+      if (t >= tq) {  // a run of odd length: one more row, then the roles are swapped back
+        row(t, bE, bM, bE2, bM2);
 #pragma unroll
-      for (int j = 0; j < CPL; ++j) {
-        bE[j] = bE2[j];
-        bM[j] = bM2[j];
+        for (int j = 0; j < CPL; ++j) {
+          bE[j] = bE2[j];
+          bM[j] = bM2[j];
+        }
+        --t;
       }
     }
   }
@@ -561,6 +574,7 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
   // (log_norm = -inf), hence e = -inf, hence fM = fE = LPM = LPE = vM = vE = -inf in that slot with
   // no select in the row loop. Both hand-overs happen in the rare block that looks one row ahead.
   int lo = band_mid(1, ratio) - bw;  // band of row 1 (column 0 of row 0 is inside: band_mid(1) <= 1 <= bw)
+  const double inv_ratio = 1.0 / ratio;  // seeds the run-length prediction only (band_runs.hpp)
   // DYN_SKIP_OOB: lanes whose part of a row is fetched (rows up to RING_D + 1 ahead) / whose posteriors of a row are stored
   // (the row's band, whichever side of the hand-over `lo` is on when the stores are issued)
   constexpr bool MASKED = SKIP_OOB && POST;
@@ -645,9 +659,29 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
     }
   }
 
+  // The window moves up by one column between rows t and t+1 (wave-uniform). Runs BETWEEN rows, in front of row t: nothing
+  // in a row reads n[] or p before the look-ahead emission e(t+1, .), and the row's own in.e, in.fE, in.vE are not touched.
+  auto hand_over = [&](auto strict_tag, int next_lo) {
+    // uniform addresses -> scalar loads (see backward_sweep)
+    const Emis none = load_emis(pr, 0, 0);
+    const Emis entering = load_emis(pr, lo + W, N);
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+      // Column lo is in the band for the last time in row t; its slot becomes column lo+P. n and p are only read by
+      // the emission of row t+1, which must already be -inf there; e(t, lo) and fE/vE(t-1, lo) stay where row t and
+      // the right neighbour (fEl/vEl) still read them.
+      const bool leaves = n[j] == lo;
+      n[j] = leaves ? lo + P : n[j];
+      if (leaves) set_p(j, none, strict_tag);
+      if (n[j] == lo + W) set_p(j, entering, strict_tag);  // first band row of this column is t+1
+    }
+    lo = next_lo;
+    set_masks();
+  };
+
   // one lattice row: reads the state `in` (row t-1), writes `out` (row t)
   // strict_tag: a row of a STRICT block (certified arithmetic, its look-ahead emission included)
-  auto row = [&](auto check_move, auto strict_tag, int t, double xn, const RowState& in, RowState& out) {
+  auto row = [&](auto strict_tag, int t, double xn, const RowState& in, RowState& out) {
     constexpr bool STRICT_ROW = STRICT && decltype(strict_tag)::value;
     double fEl[CPL], vEl[CPL];
     if (POST) {
@@ -663,26 +697,6 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
     }
     from_left(in.fE, fEl);
     if (POST) from_left(in.vE, vEl);
-    if constexpr (decltype(check_move)::value) {
-      const int next_lo = band_mid(t + 1, ratio) - bw;
-      if (__builtin_expect(next_lo != lo, 0)) {  // wave-uniform: the window moves up by one column between rows t and t+1
-        // uniform addresses -> scalar loads (see backward_sweep)
-        const Emis none = load_emis(pr, 0, 0);
-        const Emis entering = load_emis(pr, lo + W, N);
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) {
-          // Column lo is in the band for the last time in this row; its slot becomes column lo+P. n and
-          // p are only read by the emission of row t+1 below, which must already be -inf here; e(t, lo)
-          // and fE/vE(t-1, lo) stay where this row and the right neighbour (fEl/vEl) still read them.
-          const bool leaves = n[j] == lo;
-          n[j] = leaves ? lo + P : n[j];
-          if (leaves) set_p(j, none, strict_tag);
-          if (n[j] == lo + W) set_p(j, entering, strict_tag);  // first band row of this column is t+1
-        }
-        lo = next_lo;
-        set_masks();
-      }
-    }
     double a1[CPL], a2[CPL];
 #pragma unroll
     for (int j = 0; j < CPL; ++j) out.fM[j] = (fEl[j] + in.e[j]) + m1;
@@ -776,16 +790,27 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
     // s_waitcnt vmcnt(0) for this load in front of its first use INSIDE the loop, where it drains the
     // DMA ring in every row (+7 % on the sweep). A use here pins the wait to once per 64 rows.
     asm volatile("" ::"v"(xs));
-    const int iend = min(64, T - tb);
-    int i = 0;
+    const int tend = tb + min(64, T - tb);  // one past the block's last row
+    // The block's rows in RUNS: maximal spans of rows t with band_mid(t + 1) - bw == lo. The hand-over sits in front of a
+    // run's first row and the rows of a run are instantiated without a window test: with the test inside the pair loop
+    // hipcc copied all 21 emission parameters on its fall-through, in every row (21 of a row's 24 v_mov_b64).
+    int t = tb;
 #pragma unroll 1
-    for (; i + 1 < iend; i += 2) {
-      row(std::true_type{}, strict_tag, tb + i, readlane_f64(xs, i), sa, sb);
-      row(std::true_type{}, strict_tag, tb + i + 1, readlane_f64(xs, i + 1), sb, sa);
-    }
-    if (i < iend) {  // odd tail (last block of a read only): one more row, then the roles are swapped back
-      row(std::true_type{}, strict_tag, tb + i, readlane_f64(xs, i), sa, sb);
-      sa = sb;
+    while (t < tend) {
+      const int next_lo = band_mid(t + 1, ratio) - bw;
+      if (next_lo != lo) hand_over(strict_tag, next_lo);
+      // the next run's first row (band_runs.hpp: predicted with one multiply, confirmed with band_mid itself)
+      const int te = __builtin_amdgcn_readfirstlane(dynband::next_move_row(t + 1, ratio, inv_ratio, tend));
+#pragma unroll 1
+      for (; t + 1 < te; t += 2) {
+        row(strict_tag, t, readlane_f64(xs, t - tb), sa, sb);
+        row(strict_tag, t + 1, readlane_f64(xs, t + 1 - tb), sb, sa);
+      }
+      if (t < te) {  // a run of odd length: one more row, then the roles are swapped back
+        row(strict_tag, t, readlane_f64(xs, t - tb), sa, sb);
+        sa = sb;
+        ++t;
+      }
     }
   };
   // Whole 64-row blocks are strict or not (rows past strict_rows inside a strict block cost a little and harm nothing), and
