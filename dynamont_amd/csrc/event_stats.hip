@@ -15,7 +15,7 @@
 //   k_event_long   segments longer than EV_SHORT_MAX rows, one 256-thread block per read: lanes sum chunks in parallel,
 //                  one lane combines the chunk sums in order; the median by an 8-bit radix select over an order-preserving
 //                  key of the signed doubles. (k_median_long's select works on raw bits -- its posteriors are never
-//                  negative -- and is left as it is, so the posterior medians cannot move.)
+//                  negative -- and is left as it is; it is pinned bit for bit by tests/test_gpu_segment_median.py.)
 // No float atomics (the histograms are integer counts): results are identical run to run.
 #include "nt_kernels.hpp"
 
