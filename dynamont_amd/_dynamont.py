@@ -480,6 +480,26 @@ class _Scattered:
         self.ctypes = table.ctypes  # .ctypes.data -> the table
 
 
+KMER_SUMMARY_TOTALS = ("reads_ok", "segments", "samples", "skipped_segments")
+
+
+def int128_of_limbs(lo, hi) -> np.ndarray:
+    """object array of Python ints: the signed 128-bit two's complement values (hi << 64 | lo)"""
+    out = np.empty(len(lo), dtype=object)
+    for i, (l, h) in enumerate(zip(lo.tolist(), hi.tolist())):
+        v = (h << 64) | l
+        out[i] = v - (1 << 128) if h >> 63 else v
+    return out
+
+
+def kmer_summary_from_limbs(cols, totals) -> dict:
+    """the dict Aligner.kmer_summary() returns, from the six uint64 arrays and the four totals of the C interface"""
+    cols = [np.ascontiguousarray(c, dtype=np.uint64) for c in cols]
+    t = [int(x) for x in np.asarray(totals, dtype=np.uint64).tolist()]
+    return {"n_segments": cols[0], "n_samples": cols[1], "Q1": int128_of_limbs(cols[2], cols[3]),
+            "Q2": int128_of_limbs(cols[4], cols[5]), "limbs": cols, "totals": dict(zip(KMER_SUMMARY_TOTALS, t))}
+
+
 class Aligner:
     """Mirror of ``_dynamont.Aligner`` (aligner_bindings.cpp:191-216).
 
@@ -597,6 +617,32 @@ class Aligner:
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
         self._rescale = int(iters)
+
+    def set_kmer_summary(self, on: bool) -> None:
+        """dyn_aligner_set_kmer_summary: while on, every segment of every ok read of the align(calc_probabilities=True) jobs
+        submitted on this aligner is added to its k-mer's entry of a per-k-mer summary kept on the GPU as exact integers
+        (INTEGRATION.md section 3); ``kmer_summary()`` fetches it, ``reset_kmer_summary()`` zeroes it."""
+        rc = self._L.dyn_aligner_set_kmer_summary(self._h, 1 if on else 0)
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+
+    def reset_kmer_summary(self) -> None:
+        rc = self._L.dyn_aligner_kmer_summary_reset(self._h)
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+
+    def kmer_summary(self) -> dict:
+        """dyn_aligner_kmer_summary_fetch: the summary of every job that has completed, in k-mer-code order. ``n_segments``,
+        ``n_samples``: uint64 arrays; ``Q1``, ``Q2``: object arrays of Python ints (the signed 128-bit sums of
+        rint(S1 * 2**40) and rint(S2 * 2**40) per segment); ``limbs``: the six raw uint64 arrays as fetched; ``totals``:
+        reads_ok, segments, samples, skipped_segments. Fetch when the pipeline is dry."""
+        n = self.num_kmers
+        cols = [np.zeros(n, dtype=np.uint64) for _ in range(6)]
+        totals = np.zeros(4, dtype=np.uint64)
+        rc = self._L.dyn_aligner_kmer_summary_fetch(self._h, *[_ptr(c, N.c_u64_p) for c in cols], _ptr(totals, N.c_u64_p))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        return kmer_summary_from_limbs(cols, totals)
 
     def set_train_zcheck(self, on: bool) -> None:
         """dyn_aligner_set_train_zcheck: also refuse the reads the reference's |Zf - Zb| rule refuses (one more Z-only

@@ -14,8 +14,8 @@ CSRC = os.path.join(HERE, "csrc")
 # DYN_LIB_PATH: another build of the SAME sources (tools/sanitize: the host side under ASan / UBSan / TSan on the CPU)
 LIB_PATH = os.environ.get("DYN_LIB_PATH") or os.path.join(HERE, "libdynamont_mi.so")
 SOURCES = ["dynamont_mi.cpp", "buffers.cpp", "launch.cpp", "session.cpp", "async_engine.cpp", "pore_model.cpp", "csv_format.cpp", "csv_sink.cpp", "vbz_decode.cpp", "bam_reader.cpp", "rccl_comm.cpp", "model_format.cpp",
-           "nt_kernels.hip", "pool_stats.hip", "wide_band.hip", "event_stats.hip", "rescale.hip"]
-HEADERS = ["engine.hpp", "engine_internal.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "dp_cell.hpp", "segment_kernels.hpp", "band_runs.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
+           "nt_kernels.hip", "pool_stats.hip", "wide_band.hip", "event_stats.hip", "rescale.hip", "kmer_summary.hip"]
+HEADERS = ["engine.hpp", "engine_internal.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "dp_cell.hpp", "segment_kernels.hpp", "kmer_summary_kernels.hpp", "band_runs.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
 
 DYN_DEVICE_HOST_ONLY = -2
 DYN_CSV_EVENT_STATS = 0x1  # dyn_csv_sink_open_ex flag
@@ -106,6 +106,9 @@ SIGNATURES = {
     "dyn_aligner_set_train_zcheck": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_aligner_set_event_stats": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_aligner_set_rescale": (C.c_int, [C.c_void_p, C.c_int]),
+    "dyn_aligner_set_kmer_summary": (C.c_int, [C.c_void_p, C.c_int]),
+    "dyn_aligner_kmer_summary_fetch": (C.c_int, [C.c_void_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p]),
+    "dyn_aligner_kmer_summary_reset": (C.c_int, [C.c_void_p]),
     "dyn_tie_rows": (C.c_uint32, [C.c_void_p, c_i32_p, C.c_uint64, C.c_uint64]),
     "dyn_aligner_last_error": (C.c_char_p, [C.c_void_p]),
     "dyn_read_strerror": (C.c_int, [C.c_int, C.c_char, C.c_char_p, C.c_uint64]),

@@ -212,6 +212,14 @@ std::shared_ptr<BatchGroup> Pipeline::merge(const std::vector<dyn_batch*>& ticke
   g->job = first->job;
   g->ev_want = first->ev_want;  // (same_kind: every member asked alike)
   g->rs_want = first->rs_want;
+  // the per-k-mer summary is snapshot per ticket and same_kind does not look at it: the launch sums the members that asked
+  for (dyn_batch* t : tickets) {
+    if (!t->ks_want || !t->n) continue;
+    g->ks_want = true;
+    const uint32_t lo = (uint32_t)t->g_read0, hi = (uint32_t)(t->g_read0 + t->n);
+    if (!g->ks_ranges.empty() && g->ks_ranges.back().second == lo) g->ks_ranges.back().second = hi;
+    else g->ks_ranges.emplace_back(lo, hi);
+  }
   g->in_sig_offsets = grp->sig_offsets.data();
   g->in_seqs = grp->seqs.data();
   g->in_seq_offsets = grp->seq_offsets.data();
@@ -756,6 +764,7 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
   b->job = job;
   b->ev_want = a->event_stats;
   b->rs_want = a->rescale_iters;
+  b->ks_want = a->kmer_summary;
   b->in_signals = signals;
   if (rs) {
     b->has_raw = true;

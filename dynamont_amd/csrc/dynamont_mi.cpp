@@ -421,6 +421,7 @@ void dyn_aligner_destroy(dyn_aligner* a) {
     if (trace) std::fprintf(stderr, "[dyn] destroy %p: device idle; releasing buffers\n", (void*)a);
     a->d_model.release();
     a->d_sptab.release();
+    a->d_ksum.release();
     park_pool_buffer(a->device, 0, a->ws);
     park_pool_buffer(a->device, 1, a->lpe);
     park_pool_buffer(a->device, 2, a->bits);
@@ -536,6 +537,66 @@ int dyn_aligner_set_rescale(dyn_aligner* a, int iters) {
     return DYN_ERR_INVALID_ARGUMENT;
   }
   a->rescale_iters = iters;
+  return DYN_OK;
+}
+
+int dyn_aligner_set_kmer_summary(dyn_aligner* a, int on) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  if (a->ntk) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = "dyn_aligner_set_kmer_summary: modes ntk / resquiggle have no align(calc_probabilities = 1) job to summarise";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = need_device(a)) return rc;
+  if (on && !a->d_ksum.p) {
+    // the accumulator lives as long as the handle: 48 bytes per k-mer and the four totals, zeroed once
+    const size_t bytes = (6 * a->model.num_kmers + 4) * sizeof(uint64_t);
+    HIP_TRY(a, a->d_ksum.ensure(bytes));
+    HIP_TRY(a, hipMemsetAsync(a->d_ksum.p, 0, bytes, a->s_get));
+    HIP_TRY(a, hipStreamSynchronize(a->s_get));
+  }
+  a->kmer_summary = on != 0;
+  return DYN_OK;
+}
+
+namespace {
+// every kernel that adds to the accumulator runs on the compute stream (one launch per batch) or on the copy-out stream
+// (tickets of a resident session): the summary of the jobs that have completed is behind both
+int kmer_summary_quiet(dyn_aligner* a, const char* who) {
+  if (int rc = need_device(a)) return rc;
+  if (!a->d_ksum.p) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = std::string(who) + ": dyn_aligner_set_kmer_summary(a, 1) was never called on this handle";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  HIP_TRY(a, hipStreamSynchronize(a->stream));
+  HIP_TRY(a, hipStreamSynchronize(a->s_out));
+  return DYN_OK;
+}
+}  // namespace
+
+int dyn_aligner_kmer_summary_fetch(dyn_aligner* a, uint64_t* n_segments, uint64_t* n_samples, uint64_t* q1_lo, uint64_t* q1_hi,
+                                   uint64_t* q2_lo, uint64_t* q2_hi, uint64_t totals[4]) {
+  if (!a || !n_segments || !n_samples || !q1_lo || !q1_hi || !q2_lo || !q2_hi || !totals) return DYN_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = kmer_summary_quiet(a, "dyn_aligner_kmer_summary_fetch")) return rc;
+  const uint64_t nk = a->model.num_kmers;
+  std::vector<uint64_t> h(6 * nk + 4);
+  HIP_TRY(a, copy_out(a, h.data(), a->d_ksum.p, h.size() * sizeof(uint64_t)));
+  uint64_t* cols[6] = {n_segments, n_samples, q1_lo, q1_hi, q2_lo, q2_hi};
+  for (uint64_t c = 0; c < nk; ++c)
+    for (int f = 0; f < 6; ++f) cols[f][c] = h[6 * c + f];
+  for (int t = 0; t < 4; ++t) totals[t] = h[6 * nk + t];
+  return DYN_OK;
+}
+
+int dyn_aligner_kmer_summary_reset(dyn_aligner* a) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = kmer_summary_quiet(a, "dyn_aligner_kmer_summary_reset")) return rc;
+  HIP_TRY(a, hipMemsetAsync(a->d_ksum.p, 0, (6 * a->model.num_kmers + 4) * sizeof(uint64_t), a->s_get));
+  HIP_TRY(a, hipStreamSynchronize(a->s_get));
   return DYN_OK;
 }
 
@@ -932,6 +993,7 @@ int run_job_sync(dyn_batch* b, DynJob job) {
     if (rc != DYN_OK) return rc;
     b->ev_want = a->event_stats;
     b->rs_want = a->rescale_iters;
+    b->ks_want = a->kmer_summary;
     rc = enqueue_job(b, job);
     if (rc != DYN_OK) {
       (void)hipStreamSynchronize(a->stream);

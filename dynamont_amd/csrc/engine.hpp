@@ -148,6 +148,9 @@ struct dyn_aligner {
   bool train_zcheck = false;  // dyn_aligner_set_train_zcheck
   bool event_stats = false;   // dyn_aligner_set_event_stats: read by every batch / ticket at its submission
   int rescale_iters = 0;      // dyn_aligner_set_rescale (0 .. 8): read by every batch / ticket at its submission
+  bool kmer_summary = false;  // dyn_aligner_set_kmer_summary: read by every batch / ticket at its submission
+  dyneng::DevBuf d_ksum;      // [6 num_kmers + 4] u64: the per-k-mer accumulator and its totals (kmer_summary_kernels.hpp),
+                              // allocated and zeroed by the first dyn_aligner_set_kmer_summary(a, 1)
   bool ntk = false;     // created with mode "resquiggle" / "ntk"
   std::string last_error;
   // grow-only lattice workspace pool, reused across batches (only ever touched by work on `stream`,
@@ -247,6 +250,10 @@ struct dyn_batch {
   bool sig0_kept = false;                      // d_sig0 holds x0 (a synchronous batch aligned again starts from it)
   uint64_t sig0_len = 0;                       // samples kept in d_sig0
   int n_passes = 1;                            // alignment passes of the last job (h_stats holds one record each)
+  // per-k-mer summary (dyn_aligner_set_kmer_summary): the handle's switch when this batch / ticket was submitted. A merged
+  // launch's batch lists the read ranges of the members that asked (same_kind does not look at the switch)
+  bool ks_want = false;
+  std::vector<std::pair<uint32_t, uint32_t>> ks_ranges;
   dyneng::PinnedBuf h_descs, h_state, h_rows;  // h_state/h_rows: D2H targets of the asynchronous path
   dyneng::PinnedBuf h_stats;                   // wave-cycle statistics of the read-queue launch
   dyneng::PinnedBuf h_sig;                     // staging of pageable caller signals (asynchronous path)
@@ -351,6 +358,9 @@ int session_publish(dyn_batch* b);
 // All of its reads are redone (the results of those that had finished are the same). *republished = false: nothing was
 // missing after all (the waves that were still busy finished the ticket before they left). Caller holds a->mu.
 int session_recover(dyn_batch* b, bool* republished);
+// what launch_segments and launch_kmer_summary get for this batch's align(calc = 1) job: one entry per range of reads whose
+// ticket asked for the summary (empty: none did)
+std::vector<dynk::KmerSummary> kmer_summary_args(const dyn_batch* b);
 // the per-segment kernels and the statistics copy of a COMPLETED session ticket, on `s`
 int session_finish_enqueue(dyn_batch* b, hipStream_t s);
 int session_collect_timing(dyn_batch* b);

@@ -620,7 +620,13 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     evc = dynk::EventCols{q.sig, e, e + b->capacity, e + 2 * b->capacity};
     b->ev_ready = true;
   }
-  if (calc) dynk::launch_segments(q.descs, nr_all, rows_total, max_N, q.st, q.tb, b->d_rows.as<SegRow>(), m.k, a->stream, evc);
+  if (calc) {
+    // the per-k-mer summary (once per job, after the last pass: the signal of a rescaling job is its last pass's)
+    const std::vector<dynk::KmerSummary> ks = kmer_summary_args(b);
+    dynk::launch_segments(q.descs, nr_all, rows_total, max_N, q.st, q.tb, b->d_rows.as<SegRow>(), m.k, a->stream, evc,
+                          ks.empty() ? dynk::KmerSummary{} : ks[0]);
+    for (size_t k = 1; k < ks.size(); ++k) dynk::launch_kmer_summary(q.descs, nr_all, max_N, q.st, q.tb, ks[k], a->stream);
+  }
   if (job == DynJob::Train) {
     b->pool_nr = nr_all;
     b->pool_max_N = max_N;
@@ -646,6 +652,25 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   b->trained = job == DynJob::Train;
   b->last_calc = calc ? 1 : 0;
   return DYN_OK;
+}
+
+std::vector<dynk::KmerSummary> kmer_summary_args(const dyn_batch* b) {
+  std::vector<dynk::KmerSummary> out;
+  const dyn_aligner* a = b->a;
+  if (!b->ks_want || !a->d_ksum.p) return out;
+  unsigned long long* acc = a->d_ksum.as<unsigned long long>();
+  dynk::KmerSummary ks{b->d_sig.as<double>(), b->d_kmers.as<int32_t>(), acc, acc + 6 * a->model.num_kmers,
+                       (uint32_t)a->model.num_kmers, 0u, (uint32_t)b->n};
+  if (b->ks_ranges.empty()) {
+    out.push_back(ks);
+  } else {
+    for (const auto& r : b->ks_ranges) {
+      ks.read_lo = r.first;
+      ks.read_hi = r.second;
+      out.push_back(ks);
+    }
+  }
+  return out;
 }
 
 // After the compute stream has passed the batch (and the statistics copy behind it).

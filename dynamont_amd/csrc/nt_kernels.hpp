@@ -232,10 +232,23 @@ struct EventCols {
 };
 void launch_event_stats(const ReadDesc* descs, int n_reads, uint64_t rows_total, const ReadState* st, const TraceBuffers& tb,
                         const EventCols& ev, hipStream_t s);
+// per-k-mer level summary of a run (kmer_summary.hip, dyn_aligner_set_kmer_summary); acc == nullptr: not asked for
+struct KmerSummary {
+  const double* sig;          // the signal the read queue aligned (ReadDesc::sig_off counts from here)
+  const int32_t* kmers;       // k-mer code of every lattice column (ReadDesc::par_off counts from here): row j <-> entry j
+  unsigned long long* acc;    // the handle's accumulator: [num_kmers][6] n_segments, n_samples, q1 lo / hi, q2 lo / hi
+  unsigned long long* totals; // [4] reads_ok, segments, samples, skipped_segments
+  uint32_t num_kmers;
+  uint32_t read_lo, read_hi;  // the reads [read_lo, read_hi) (ReadDesc::read) contribute: the members of a merged launch
+                              // whose handle had the switch on when they were submitted
+};
+void launch_kmer_summary(const ReadDesc* descs, int n_reads, uint32_t max_N, const ReadState* st, const TraceBuffers& tb,
+                         const KmerSummary& ks, hipStream_t s);
 // per-segment median posterior + output rows for all reads of descs (after launch_read_queue), then the signal levels when
-// `ev` asks for them
+// `ev` asks for them and the per-k-mer summary when `ks` does
 void launch_segments(const ReadDesc* descs, int n_reads, uint64_t rows_total, uint32_t max_N, const ReadState* st,
-                     TraceBuffers tb, SegRow* rows, int kmer_size, hipStream_t s, const EventCols& ev = EventCols{});
+                     TraceBuffers tb, SegRow* rows, int kmer_size, hipStream_t s, const EventCols& ev = EventCols{},
+                     const KmerSummary& ks = KmerSummary{});
 // per-read signal rescaling (rescale.hip, dyn_aligner_set_rescale): the transform x = (x0 - A) / B of read `read`
 struct RescaleState {
   double A;         // shift: 0.0 until a fit is applied

@@ -535,8 +535,11 @@ int session_finish_enqueue(dyn_batch* b, hipStream_t s) {
     double* e = b->d_ev.as<double>();
     evc = dynk::EventCols{b->d_sig.as<double>(), e, e + b->capacity, e + 2 * b->capacity};
   }
+  const std::vector<dynk::KmerSummary> ks = kmer_summary_args(b);
   dynk::launch_segments(b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_rows_total, b->sess_max_N, b->d_state.as<ReadState>(), tb,
-                        b->d_rows.as<SegRow>(), a->model.k, s, evc);
+                        b->d_rows.as<SegRow>(), a->model.k, s, evc, ks.empty() ? dynk::KmerSummary{} : ks[0]);
+  for (size_t k = 1; k < ks.size(); ++k)
+    dynk::launch_kmer_summary(b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_max_N, b->d_state.as<ReadState>(), tb, ks[k], s);
   HIP_TRY(a, hipGetLastError());
   HIP_TRY(a, hipEventRecord(ev[2], s));
   HIP_TRY(a, hipMemcpyAsync(b->h_stats.p, b->d_tctl.p, dynk::SESSION_TCTL_WORDS * 4, hipMemcpyDeviceToHost, s));

@@ -92,6 +92,11 @@ def parse(argv=None) -> Namespace:
                         "on the GPU between the passes: a least-squares fit of the segment levels on the model levels. "
                         "The rows are those of the last pass (with --event-stats, its levels). The CSV columns are unchanged; "
                         "the per-read shift and scale are not written anywhere")
+    p.add_argument("--kmer-summary", default="", metavar="PATH",
+                   help="also write a per-k-mer summary of the run to PATH: a TSV in the model file's k-mer order with the "
+                        "level (mean, stdev of the normalised signal) and dwell the run's segments showed per k-mer beside the "
+                        "model's values, summed on the GPU as exact integers (the same bytes for any number of GPUs). Its "
+                        "first three columns load as a model file; k-mers the run never met keep the model's values")
     p.add_argument("--parallel-zstd-frames", action="store_true",
                    help="write the CSV as consecutive independent zstd frames (readers must read across frames: "
                         "python-zstandard's defaults stop after the first). Default: one frame, like the reference, "
@@ -702,7 +707,7 @@ def _gather_parts(comm, parallel, outfile: str, part: str, part_err: str | None)
 def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_path: str, pore: str, mode: str,
             minq: float = 0, device: int = 0, batch_reads: int = 1024, mem_budget_gib: float = 0.0,
             host_preprocess: bool = False, depth: int = 12, strict_ties: str = "ties", host_threads: int = 0,
-            zstd_level: int = 3, event_stats: bool = False, rescale_iters: int = 0) -> None:
+            zstd_level: int = 3, event_stats: bool = False, rescale_iters: int = 0, kmer_summary: str = "") -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
@@ -741,6 +746,29 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                 for line in blob.decode().split("\n") if blob else []:
                     q.put(line)
 
+    def write_summary(aligner):
+        # --kmer-summary, with the pipeline dry: every rank's raw integer arrays travel to rank 0 (one more gather), which adds
+        # them as Python ints and writes the file -- the same bytes for any number of ranks
+        if not kmer_summary:
+            return
+        from dynamont_amd._dynamont import kmer_summary_from_limbs
+        from dynamont_amd.segmentation.utils import merge_kmer_summaries, write_kmer_summary
+        mine = aligner.kmer_summary()
+        parts = [mine]
+        if comm is not None:
+            t = np.array([mine["totals"][k] for k in ("reads_ok", "segments", "samples", "skipped_segments")], dtype=np.uint64)
+            blobs = parallel.gather_bytes(comm, b"".join(c.tobytes() for c in mine["limbs"]) + t.tobytes())
+            if rank != 0:
+                return
+            parts = []
+            for blob in blobs:
+                words = np.frombuffer(blob, dtype=np.uint64)
+                n = aligner.num_kmers
+                parts.append(kmer_summary_from_limbs([words[f * n:(f + 1) * n] for f in range(6)], words[6 * n:6 * n + 4]))
+        mean, stdev = aligner.model_table()
+        write_kmer_summary(kmer_summary, merge_kmer_summaries(parts), model_path, mean, stdev, aligner.rna)
+        print(f"k-mer summary written: {kmer_summary}", file=sys.stderr, flush=True)
+
     # A failing rank ends the whole job (parallel.abort): a barrier in a `finally` would leave the other ranks in
     # their next collective until the process-group timeout.
     with parallel.abort_on_error(comm):
@@ -756,6 +784,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                 aligner.set_event_stats(True)
             if rescale_iters:
                 aligner.set_rescale(rescale_iters)
+            if kmer_summary:
+                aligner.set_kmer_summary(True)
             if native:
                 import os
                 import tempfile
@@ -818,6 +848,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                 _stamp("pipeline closed: output complete")
                 if comm is not None:
                     _gather_parts(comm, parallel, outfile, part, part_err)
+                write_summary(aligner)
                 parallel.remove_scratch()
                 print("Done with segmentation.", file=sys.stderr, flush=True)
                 return
@@ -860,6 +891,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                     break
             pipe.close()
             pipe = None
+            write_summary(aligner)
             print("Done with segmentation.", file=sys.stderr, flush=True)
         finally:
             if pipe is not None:  # an exception is on its way: release what is queued, keep the first error
@@ -900,7 +932,8 @@ def main(argv=None) -> None:
     segment(args.raw, args.basecalls, args.processes, outfile, model_path, args.pore, args.mode, args.qscore,
             device=args.device, batch_reads=args.batch_reads, mem_budget_gib=args.mem_budget,
             host_preprocess=args.host_preprocess, depth=args.depth, strict_ties=args.strict_ties, host_threads=args.host_threads,
-            zstd_level=args.zstd_level, event_stats=args.event_stats, rescale_iters=args.rescale_iters)
+            zstd_level=args.zstd_level, event_stats=args.event_stats, rescale_iters=args.rescale_iters,
+            kmer_summary=args.kmer_summary)
     _stamp("segment() returned (aligner closed)")
     if argv is None and not int(__import__("os").environ.get("WORLD_SIZE", "1") or 1) > 1:
         # Invoked as the command (console script / python -m), single process, everything written and closed: leave without

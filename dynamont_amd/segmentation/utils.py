@@ -211,3 +211,81 @@ def kmer_of_code(code: int, k: int, rna: bool) -> str:
         code //= 4
     kmer = "".join(reversed(s))
     return kmer[::-1] if rna else kmer
+
+
+def code_of_kmer(kmer: str, rna: bool) -> int:
+    """inverse of kmer_of_code"""
+    code = 0
+    for ch in (kmer[::-1] if rna else kmer):
+        code = code * 4 + "ACGT".index(ch)
+    return code
+
+
+def merge_kmer_summaries(parts: list) -> dict:
+    """The sum of several Aligner.kmer_summary() results (the ranks of a multi-GPU run), added as Python ints: integer
+    addition commutes, so the sum does not depend on how the reads were dealt out."""
+    from dynamont_amd._dynamont import KMER_SUMMARY_TOTALS
+    n = len(parts[0]["n_segments"])
+    out = {"n_segments": np.zeros(n, dtype=np.uint64), "n_samples": np.zeros(n, dtype=np.uint64),
+           "Q1": np.array([0] * n, dtype=object), "Q2": np.array([0] * n, dtype=object),
+           "totals": dict.fromkeys(KMER_SUMMARY_TOTALS, 0)}
+    for p in parts:
+        out["n_segments"] = out["n_segments"] + p["n_segments"]
+        out["n_samples"] = out["n_samples"] + p["n_samples"]
+        out["Q1"] = out["Q1"] + p["Q1"]
+        out["Q2"] = out["Q2"] + p["Q2"]
+        for k in KMER_SUMMARY_TOTALS:
+            out["totals"][k] += p["totals"][k]
+    return out
+
+
+def kmer_summary_table(summary: dict, model_mean, model_stdev) -> dict:
+    """The derived columns of a per-k-mer summary (Aligner.kmer_summary), in k-mer-code order, each formed from the exact
+    integers with one fp64 operation per step:
+        m1 = float(Q1) * 2**-40 (int -> float correctly rounded), level_mean = m1 / n_samples,
+        ex2 = float(Q2) * 2**-40 / n_samples, level_stdv = sqrt(max(0.0, ex2 - level_mean * level_mean)),
+        dwell_mean = n_samples / n_segments.
+    A k-mer the run never met (n_segments == 0) or met with zero variance carries the MODEL's mean and stdev in
+    ``level_mean`` / ``level_stdv`` (``fitted`` is False there), so the table is always a loadable model."""
+    import math
+    n = len(summary["n_segments"])
+    mm = np.asarray(model_mean, dtype=np.float64)
+    ms = np.asarray(model_stdev, dtype=np.float64)
+    assert len(mm) == n and len(ms) == n
+    mean, stdv, dwell = mm.copy(), ms.copy(), np.zeros(n)
+    fitted = np.zeros(n, dtype=bool)
+    nseg, nsamp = summary["n_segments"].tolist(), summary["n_samples"].tolist()
+    scale = 2.0 ** -40
+    for c in np.flatnonzero(summary["n_segments"]).tolist():
+        ns = float(nsamp[c])
+        lm = float(summary["Q1"][c]) * scale / ns
+        ex2 = float(summary["Q2"][c]) * scale / ns
+        sd = math.sqrt(max(0.0, ex2 - lm * lm))
+        dwell[c] = ns / float(nseg[c])
+        if sd > 0.0:
+            mean[c], stdv[c], fitted[c] = lm, sd, True
+    return {"level_mean": mean, "level_stdv": stdv, "n_segments": summary["n_segments"], "n_samples": summary["n_samples"],
+            "dwell_mean": dwell, "model_mean": mm, "model_stdv": ms, "fitted": fitted}
+
+
+KMER_SUMMARY_HEADER = "kmer\tlevel_mean\tlevel_stdv\tn_segments\tn_samples\tdwell_mean\tmodel_mean\tmodel_stdv\n"
+
+
+def write_kmer_summary(path: str, summary: dict, model_file: str, model_mean, model_stdev, rna: bool) -> dict:
+    """The per-k-mer summary as a TSV in ``model_file``'s own k-mer order and orientation (floats as ``repr``). Its first
+    three columns are a model file: ``read_kmer_model(path)`` and ``Aligner(path, pore)`` load it -- a hard-EM (Viterbi
+    path) re-estimate of the model, with the model's own values where the run has none. ``model_mean`` / ``model_stdev``:
+    the table the run aligned with, in k-mer-code order (Aligner.model_table()). Returns the table written."""
+    t = kmer_summary_table(summary, model_mean, model_stdev)
+    with open(model_file) as f:
+        header = f.readline().rstrip("\n").split("\t")
+        ik = header.index("kmer")
+        names = [line.split("\t")[ik].strip() for line in f if line.strip()]
+    nseg, nsamp = t["n_segments"].tolist(), t["n_samples"].tolist()
+    cols = [t[k].tolist() for k in ("level_mean", "level_stdv", "dwell_mean", "model_mean", "model_stdv")]
+    with open(path, "w") as w:
+        w.write(KMER_SUMMARY_HEADER)
+        for name in names:
+            c = code_of_kmer(name, rna)
+            w.write(f"{name}\t{cols[0][c]!r}\t{cols[1][c]!r}\t{nseg[c]}\t{nsamp[c]}\t{cols[2][c]!r}\t{cols[3][c]!r}\t{cols[4][c]!r}\n")
+    return t

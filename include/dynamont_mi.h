@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DYN_ABI_VERSION 10 /* 10: per-read signal rescaling: dyn_aligner_set_rescale, dyn_batch_fetch_rescale (additive). 9: per-segment signal levels: dyn_aligner_set_event_stats, dyn_batch_fetch_events, dyn_format_csv[_bound]_events, dyn_csv_sink_open_ex (additive). 8: dyn_aligner_session_idle_split (additive). 7: dyn_aligner_session_page_wait, dyn_comm_gather_bytes / _gathered_bytes / _allreduce_f64 (additive). 7: half bands 224 .. 2 046 are computed (wide_band.hip). 5: any band constructs (DYN_READ_BAND_TOO_WIDE per read); dyn_bam_*, dyn_csv_sink_wait / _open_part */
+#define DYN_ABI_VERSION 10 /* 10 (number kept; look the symbols up): per-k-mer level summary of a run: dyn_aligner_set_kmer_summary, dyn_aligner_kmer_summary_fetch / _reset (additive). 10: per-read signal rescaling: dyn_aligner_set_rescale, dyn_batch_fetch_rescale (additive). 9: per-segment signal levels: dyn_aligner_set_event_stats, dyn_batch_fetch_events, dyn_format_csv[_bound]_events, dyn_csv_sink_open_ex (additive). 8: dyn_aligner_session_idle_split (additive). 7: dyn_aligner_session_page_wait, dyn_comm_gather_bytes / _gathered_bytes / _allreduce_f64 (additive). 7: half bands 224 .. 2 046 are computed (wide_band.hip). 5: any band constructs (DYN_READ_BAND_TOO_WIDE per read); dyn_bam_*, dyn_csv_sink_wait / _open_part */
 
 /* device argument of dyn_aligner_create: bind no GPU. Such a handle serves the host-side
  * contract only (model loading, dyn_aligner_info/_model, dyn_validate_batch); every compute
@@ -355,6 +355,26 @@ int dyn_aligner_set_event_stats(dyn_aligner* a, int on);
  * Each pass costs about one alignment; device memory: a copy of the batch's signal, 32 bytes per read, 8 per segment row.
  * dyn_multi_*: set it on each device's handle (dyn_multi_handle). */
 int dyn_aligner_set_rescale(dyn_aligner* a, int iters);
+/* (added within ABI 10: a caller that must know looks the symbol up) Per-k-mer level summary of a run. While it is on, every output row (segment) of every read with status 0 of an
+ * align(calc_probabilities = 1) batch or ticket SUBMITTED on this handle is added, on the device behind the per-segment
+ * kernels, to its k-mer's entry of an accumulator that lives on the handle: six u64 per k-mer code (48 bytes x num_kmers of
+ * device memory, allocated and zeroed by the first call with on != 0), as EXACT INTEGERS --
+ *   n_segments, n_samples         segments and samples the k-mer's emission scored (the row's `motif`)
+ *   Q1 = sum q1, Q2 = sum q2      signed 128-bit two's complement, two u64 limbs each; per segment q1 = rint(S1 * 2^40) and
+ *                                 q2 = rint(S2 * 2^40) with S1 / S2 the chunked fp64 sums of x and x * x over the segment's
+ *                                 samples (the samples and the summation order of dyn_event_out)
+ * so the result is the same bits whatever the launch path, the merging of tickets or the order of the device's atomics. A
+ * segment with S2 >= 2^64 or a non-finite sum is skipped and counted. A job counts once per time it runs; a rescaling job
+ * (dyn_aligner_set_rescale) counts once, with its last pass's signal. Default off: nothing is allocated, launched or changed.
+ * DYN_ERR_INVALID_ARGUMENT for a handle of mode "ntk" / "resquiggle", DYN_ERR_DEVICE for one without a device. */
+int dyn_aligner_set_kmer_summary(dyn_aligner* a, int on);
+/* The accumulator as it stands after every job that has COMPLETED (dyn_batch_align returned, dyn_batch_wait returned); with
+ * jobs still in flight it is defined only up to those jobs. Arrays of num_kmers (dyn_info); totals: reads_ok, segments,
+ * samples (both of the segments added), skipped_segments. DYN_ERR_INVALID_ARGUMENT when the switch was never on. */
+int dyn_aligner_kmer_summary_fetch(dyn_aligner* a, uint64_t* n_segments, uint64_t* n_samples, uint64_t* q1_lo, uint64_t* q1_hi,
+                                   uint64_t* q2_lo, uint64_t* q2_hi, uint64_t totals[4]);
+/* Zeroes the accumulator and the totals (same conditions as the fetch). */
+int dyn_aligner_kmer_summary_reset(dyn_aligner* a);
 /* The rule of mode 1 for one read, given its k-mer codes (dyn_validate_batch) and signal length: 0 = no structural tie;
  * otherwise the number of forward rows that run in the strict arithmetic (UINT32_MAX: all of them). Host only. */
 uint32_t dyn_tie_rows(const dyn_aligner* a, const int32_t* kmers, uint64_t n_kmers, uint64_t signal_len);

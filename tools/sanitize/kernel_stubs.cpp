@@ -22,7 +22,13 @@ void launch_preprocess(const void*, int, int, const uint64_t*, const double*, co
 void launch_prep_params(const int32_t*, const Emis*, Emis*, uint64_t, uint32_t, hipStream_t) { no_device("launch_prep_params"); }
 void launch_pool_init(const PagePool&, uint32_t, int, hipStream_t) { no_device("launch_pool_init"); }
 void launch_read_queue(QueueJob, bool, const QueueArgs&, int, hipStream_t) { no_device("launch_read_queue"); }
-void launch_segments(const ReadDesc*, int, uint64_t, uint32_t, const ReadState*, TraceBuffers, SegRow*, int, hipStream_t) { no_device("launch_segments"); }
+void launch_segments(const ReadDesc*, int, uint64_t, uint32_t, const ReadState*, TraceBuffers, SegRow*, int, hipStream_t, const EventCols&,
+                     const KmerSummary&) {
+  no_device("launch_segments");
+}
+void launch_kmer_summary(const ReadDesc*, int, uint32_t, const ReadState*, const TraceBuffers&, const KmerSummary&, hipStream_t) {
+  no_device("launch_kmer_summary");
+}
 size_t pool_stats_temp_bytes(uint64_t, uint64_t) { return 8; }
 size_t pool_stats_work_bytes(uint64_t) { return 8; }
 hipError_t launch_pool_stats(const ReadDesc*, int, uint32_t, const ReadState*, const int32_t*, TrainBuffers, double*, uint64_t, uint64_t, void*, void*,
