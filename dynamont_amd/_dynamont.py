@@ -108,6 +108,21 @@ class AlignBatchResult:
         self.level_mean = self.level_stdv = self.level_median = None
         # per-read transforms (Aligner.set_rescale): shift / scale float64 [n], fits applied int32 [n], None when off
         self.rescale_shift = self.rescale_scale = self.rescale_iters = None
+        # per-border segment scores (Aligner.set_segment_scores): float64 [cap] like the segment columns, None when off
+        self.median_delta = self.mad_delta = self.homogeneity = None
+
+    def _fetch_scores(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
+        """dyn_batch_fetch_scores into this object's score columns (allocated on first use), or drop them."""
+        if not wanted:
+            self.median_delta = self.mad_delta = self.homogeneity = None
+            return
+        if self.median_delta is None:
+            self.median_delta, self.mad_delta, self.homogeneity = (np.zeros(self.cap) for _ in range(3))
+        sc = N.DynScoreOut(_ptr(self.median_delta, N.c_double_p), _ptr(self.mad_delta, N.c_double_p),
+                           _ptr(self.homogeneity, N.c_double_p), self.cap)
+        rc = L.dyn_batch_fetch_scores(handle, C.byref(sc))
+        if rc != N.DYN_OK:
+            _raise(rc, aligner.last_error())
 
     def _fetch_rescale(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
         """dyn_batch_fetch_rescale into this object's per-read columns (allocated on first use), or drop them."""
@@ -160,6 +175,10 @@ class AlignBatchResult:
             d["level_mean"] = self.level_mean[a:b].copy()
             d["level_stdv"] = self.level_stdv[a:b].copy()
             d["level_median"] = self.level_median[a:b].copy()
+        if self.median_delta is not None:  # only when requested (Aligner.set_segment_scores)
+            d["median_delta"] = self.median_delta[a:b].copy()
+            d["mad_delta"] = self.mad_delta[a:b].copy()
+            d["homogeneity"] = self.homogeneity[a:b].copy()
         if self.rescale_shift is not None:  # only when requested (Aligner.set_rescale)
             d["rescale_shift"] = float(self.rescale_shift[i])
             d["rescale_scale"] = float(self.rescale_scale[i])
@@ -193,13 +212,18 @@ def format_csv(aligner: "Aligner", res: AlignBatchResult, sequences: Sequence[st
     if res.level_mean is not None:
         ev = C.byref(N.DynEventOut(_ptr(res.level_mean, N.c_double_p), _ptr(res.level_stdv, N.c_double_p),
                                    _ptr(res.level_median, N.c_double_p), res.cap))
-    cap = int(L.dyn_format_csv_bound_events(aligner._h, n, C.byref(res._c), ev, rid, sid))
+    # ... and the segment scores (Aligner.set_segment_scores): three more after those
+    sc = None
+    if res.median_delta is not None:
+        sc = C.byref(N.DynScoreOut(_ptr(res.median_delta, N.c_double_p), _ptr(res.mad_delta, N.c_double_p),
+                                   _ptr(res.homogeneity, N.c_double_p), res.cap))
+    cap = int(L.dyn_format_csv_bound_scores(aligner._h, n, C.byref(res._c), ev, sc, rid, sid))
     # one grow-only buffer per handle: first-touch page faults of a fresh 350 MB buffer cost ~100x
     # the formatting itself (15 ms per 1 024-read batch with warm pages)
     buf = getattr(aligner, "_csv_buf", None)
     if buf is None or buf.size < cap:
         buf = aligner._csv_buf = np.empty(max(cap, 1), dtype=np.uint8)
-    rc = L.dyn_format_csv_events(aligner._h, n, C.byref(res._c), ev, seqs, _ptr(seq_off, N.c_u64_p), rid, sid,
+    rc = L.dyn_format_csv_scores(aligner._h, n, C.byref(res._c), ev, sc, seqs, _ptr(seq_off, N.c_u64_p), rid, sid,
                           so.ctypes.data_as(C.POINTER(C.c_int64)), li.ctypes.data_as(C.POINTER(C.c_int64)),
                           int(threads), buf.ctypes.data, cap, _ptr(begin, N.c_u64_p), _ptr(end, N.c_u64_p))
     if rc != N.DYN_OK:
@@ -318,6 +342,7 @@ class Batch:
     def align(self, calc_probabilities: bool = True) -> None:
         self._levels = bool(calc_probabilities) and self._al._event_stats  # the switch at submission decides
         self._rescale = bool(calc_probabilities) and self._al._rescale > 0
+        self._scores = bool(calc_probabilities) and self._al._segment_scores > 0
         rc = self._L.dyn_batch_align(self._h, int(bool(calc_probabilities)))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
@@ -338,11 +363,18 @@ class Batch:
             _raise(rc, self._al.last_error())
         out._fetch_levels(self._L, self._h, self._al, getattr(self, "_levels", False))
         out._fetch_rescale(self._L, self._h, self._al, getattr(self, "_rescale", False))
+        out._fetch_scores(self._L, self._h, self._al, getattr(self, "_scores", False))
         return out
 
     def fetch_events(self, out: N.DynEventOut) -> None:
         """dyn_batch_fetch_events into caller-owned columns (raises ValueError for a batch that did not ask)."""
         rc = self._L.dyn_batch_fetch_events(self._h, C.byref(out))
+        if rc != N.DYN_OK:
+            _raise(rc, self._al.last_error())
+
+    def fetch_scores(self, out: N.DynScoreOut) -> None:
+        """dyn_batch_fetch_scores into caller-owned columns (raises ValueError for a batch that did not ask)."""
+        rc = self._L.dyn_batch_fetch_scores(self._h, C.byref(out))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
 
@@ -397,7 +429,8 @@ class AsyncBatch:
     handle's pipeline; ``wait()`` returns the filled result object. The input arrays are kept alive here
     (the library reads them until the batch is complete)."""
 
-    def __init__(self, aligner: "Aligner", handle, result, keep, levels: bool = False, rescale: bool = False):
+    def __init__(self, aligner: "Aligner", handle, result, keep, levels: bool = False, rescale: bool = False,
+                 scores: bool = False):
         self._al = aligner
         self._L = N.lib()
         self._h = handle
@@ -406,6 +439,7 @@ class AsyncBatch:
         self._waited = False
         self._levels = levels  # an align ticket submitted with the event-stats switch on (and calc_probabilities)
         self._rescale = rescale  # ... with the rescale switch on
+        self._scores = scores  # ... with the segment-scores switch on
 
     def wait(self):
         if not self._waited:
@@ -416,10 +450,12 @@ class AsyncBatch:
             if isinstance(self.result, AlignBatchResult):
                 self.result._fetch_levels(self._L, self._h, self._al, self._levels)
                 self.result._fetch_rescale(self._L, self._h, self._al, self._rescale)
+                self.result._fetch_scores(self._L, self._h, self._al, self._scores)
         return self.result
 
     fetch_events = Batch.fetch_events
     fetch_rescale = Batch.fetch_rescale
+    fetch_scores = Batch.fetch_scores
 
     def timing(self) -> dict:
         self.wait()
@@ -510,6 +546,7 @@ class Aligner:
 
     _event_stats = False  # set_event_stats
     _rescale = 0  # set_rescale
+    _segment_scores = 0  # set_segment_scores
 
     def __init__(self, model_file: str, pore, mode: str = "basic", threads: int = 1, band: int = 400,
                  device=None):
@@ -608,6 +645,16 @@ class Aligner:
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
         self._event_stats = bool(on)
+
+    def set_segment_scores(self, window: int) -> None:
+        """dyn_aligner_set_segment_scores: align(calc_probabilities=True) jobs submitted while ``window`` (0 .. 256) > 0 also
+        compute the per-border segment scores (median_delta / mad_delta over ``window`` samples either side of every border,
+        homogeneity of every segment) on the GPU; results carry them as
+        ``AlignBatchResult.median_delta`` / ``.mad_delta`` / ``.homogeneity`` and ``read(i)`` adds the three keys."""
+        rc = self._L.dyn_aligner_set_segment_scores(self._h, int(window))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        self._segment_scores = int(window)
 
     def set_rescale(self, iters: int) -> None:
         """dyn_aligner_set_rescale: align(calc_probabilities=True) jobs submitted while ``iters`` (0 .. 8) > 0 align every
@@ -730,7 +777,8 @@ class Aligner:
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
         return AsyncBatch(self, h, out, (sig, sig_off, seqs, seq_off), levels=self._event_stats and bool(calc_probabilities),
-                          rescale=self._rescale > 0 and bool(calc_probabilities))
+                          rescale=self._rescale > 0 and bool(calc_probabilities),
+                          scores=self._segment_scores > 0 and bool(calc_probabilities))
 
     def _raw_args(self, raw, shift, scale, calibration=None):
         scattered = isinstance(raw, (list, tuple))
@@ -781,7 +829,8 @@ class Aligner:
             _raise(rc, self.last_error())
         return AsyncBatch(self, h, out, (raw, raw_off, shift, scale, seqs, seq_off, cal),
                           levels=self._event_stats and bool(calc_probabilities),
-                          rescale=self._rescale > 0 and bool(calc_probabilities))
+                          rescale=self._rescale > 0 and bool(calc_probabilities),
+                          scores=self._segment_scores > 0 and bool(calc_probabilities))
 
     def align_vbz_async(self, chunks, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 3,
                         n_sigmas: float = 3.0, f32: bool = False, calc_probabilities: bool = True,
@@ -816,7 +865,8 @@ class Aligner:
             _raise(rc, self.last_error())
         return AsyncBatch(self, h, out, (ptrs, nbytes, samples, read_off, skip, raw_off, shift, scale, seqs, seq_off, cal),
                           levels=self._event_stats and bool(calc_probabilities),
-                          rescale=self._rescale > 0 and bool(calc_probabilities))
+                          rescale=self._rescale > 0 and bool(calc_probabilities),
+                          scores=self._segment_scores > 0 and bool(calc_probabilities))
 
     def train_raw_async(self, raw, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 7,
                         n_sigmas: float = 5.0, f32: bool = True, pooled: bool = False,

@@ -97,6 +97,7 @@ struct Args {
   int k, rna;
   const dyn_align_out* res;
   const dyn_event_out* ev;  // nullptr: no level columns
+  const dyn_score_out* sc;  // nullptr: no segment-score columns
   const char* seqs;
   const uint64_t* seq_offsets;
   const char* const* readids;
@@ -124,6 +125,12 @@ uint64_t read_bound(const Args& a, uint64_t i) {
     b += 3 * n;  // the commas
     for (uint64_t s = o; s < o + n; ++s)
       b += event_value_bound(a.ev->mean[s]) + event_value_bound(a.ev->stdev[s]) + event_value_bound(a.ev->median[s]);
+  }
+  if (a.sc) {
+    const uint64_t o = a.res->seg_offsets[i];
+    b += 3 * n;  // the commas
+    for (uint64_t s = o; s < o + n; ++s)
+      b += event_value_bound(a.sc->median_delta[s]) + event_value_bound(a.sc->mad_delta[s]) + event_value_bound(a.sc->homogeneity[s]);
   }
   return b;
 }
@@ -169,6 +176,14 @@ char* format_read(const Args& a, uint64_t i, char* p) {
       *p++ = ',';
       p = put_prob6<true>(p, a.ev->median[o + s]);
     }
+    if (a.sc) {  // (a NaN prints as "nan", like Python's f"{x:.6f}")
+      *p++ = ',';
+      p = put_prob6<true>(p, a.sc->median_delta[o + s]);
+      *p++ = ',';
+      p = put_prob6<true>(p, a.sc->mad_delta[o + s]);
+      *p++ = ',';
+      p = put_prob6<true>(p, a.sc->homogeneity[o + s]);
+    }
     *p++ = '\n';
   }
   return p;
@@ -184,8 +199,16 @@ extern "C" uint64_t dyn_format_csv_bound(const dyn_aligner* a, uint64_t n_reads,
 extern "C" uint64_t dyn_format_csv_bound_events(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
                                                 const dyn_event_out* ev, const char* const* readids,
                                                 const char* const* signalids) {
-  if (!a || !res || (ev && (!ev->mean || !ev->stdev || !ev->median))) return 0;
-  Args args{0, 0, res, ev, nullptr, nullptr, readids, signalids, nullptr, nullptr};
+  return dyn_format_csv_bound_scores(a, n_reads, res, ev, nullptr, readids, signalids);
+}
+
+extern "C" uint64_t dyn_format_csv_bound_scores(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
+                                                const dyn_event_out* ev, const dyn_score_out* sc, const char* const* readids,
+                                                const char* const* signalids) {
+  if (!a || !res || (ev && (!ev->mean || !ev->stdev || !ev->median)) ||
+      (sc && (!sc->median_delta || !sc->mad_delta || !sc->homogeneity)))
+    return 0;
+  Args args{0, 0, res, ev, sc, nullptr, nullptr, readids, signalids, nullptr, nullptr};
   uint64_t total = 0;
   for (uint64_t i = 0; i < n_reads; ++i) total += read_bound(args, i);
   return total;
@@ -205,14 +228,23 @@ extern "C" int dyn_format_csv_events(const dyn_aligner* a, uint64_t n_reads, con
                                      const char* const* readids, const char* const* signalids,
                                      const int64_t* sig_offsets, const int64_t* last_index, int threads,
                                      char* out, uint64_t out_cap, uint64_t* row_begin, uint64_t* row_end) {
+  return dyn_format_csv_scores(a, n_reads, res, ev, nullptr, seqs, seq_offsets, readids, signalids, sig_offsets, last_index,
+                               threads, out, out_cap, row_begin, row_end);
+}
+
+extern "C" int dyn_format_csv_scores(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
+                                     const dyn_event_out* ev, const dyn_score_out* sc, const char* seqs,
+                                     const uint64_t* seq_offsets, const char* const* readids, const char* const* signalids,
+                                     const int64_t* sig_offsets, const int64_t* last_index, int threads,
+                                     char* out, uint64_t out_cap, uint64_t* row_begin, uint64_t* row_end) {
   if (!a || !res || !res->status || !res->n_segments || !res->seg_offsets || !res->sequence_positions ||
       !res->signal_positions || !res->probabilities || !out || !row_begin || !row_end ||
-      (ev && (!ev->mean || !ev->stdev || !ev->median)))
+      (ev && (!ev->mean || !ev->stdev || !ev->median)) || (sc && (!sc->median_delta || !sc->mad_delta || !sc->homogeneity)))
     return DYN_ERR_INVALID_ARGUMENT;
   dyn_info info;
   dyn_aligner_info(a, &info);
   if (info.kmer_size > 31) return DYN_ERR_INVALID_ARGUMENT;
-  Args args{info.kmer_size, info.rna, res, ev, seqs, seq_offsets, readids, signalids, sig_offsets, last_index};
+  Args args{info.kmer_size, info.rna, res, ev, sc, seqs, seq_offsets, readids, signalids, sig_offsets, last_index};
   // every read formats straight into its own worst-case slot of the caller's buffer: no allocation,
   // no shared cache lines between threads
   uint64_t pos = 0;

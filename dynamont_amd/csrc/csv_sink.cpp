@@ -42,6 +42,8 @@ const char kHeader[] = "readid,signalid,start,end,basepos,base,motif,state,poste
 const char kHeaderEvents[] =
     "readid,signalid,start,end,basepos,base,motif,state,posterior_probability,polish,level_mean,level_stdv,level_median\n";
 
+const char kHeaderScores[] = ",median_delta,mad_delta,homogeneity";
+
 struct Blob {  // the formatted rows of one batch; freed when its last job has been compressed
   std::unique_ptr<char[]> data;
   size_t cap = 0;
@@ -79,6 +81,7 @@ struct Item {
 namespace dyneng {
 // DYN_OK when the ticket was submitted with the handle's event-stats switch on (dynamont_mi.cpp); else the handle's message
 int batch_check_events(dyn_batch* b);
+int batch_check_scores(dyn_batch* b);
 }
 
 struct dyn_csv_sink {
@@ -100,6 +103,8 @@ struct dyn_csv_sink {
   bool first_part = true, last_part = true;  // dyn_csv_sink_open_part: a part of a frame that several processes write
   bool events = false;                        // DYN_CSV_EVENT_STATS
   std::vector<double> ev_cols;                // [3][capacity] the batch's levels (dyn_batch_fetch_events)
+  bool scores = false;                        // DYN_CSV_SEGMENT_SCORES
+  std::vector<double> sc_cols;                // [3][capacity] the batch's segment scores (dyn_batch_fetch_scores)
   std::thread t_sink, t_writer;
   std::vector<std::thread> t_comp;
   std::vector<std::shared_ptr<Blob>> spare;  // recycled row buffers (first-touch page faults cost more than formatting)
@@ -271,7 +276,19 @@ struct dyn_csv_sink {
       }
     }
     const dyn_event_out* evp = events ? &ev : nullptr;
-    const uint64_t bound = dyn_format_csv_bound_events(it.a, it.n, it.res, evp, it.readids, it.signalids);
+    dyn_score_out sc{};
+    if (scores) {
+      const uint64_t cap = it.res->seg_offsets ? it.res->seg_offsets[it.n] : 0;
+      sc_cols.resize(std::max<uint64_t>(1, 3 * cap));
+      sc = dyn_score_out{sc_cols.data(), sc_cols.data() + cap, sc_cols.data() + 2 * cap, cap};
+      if (dyn_batch_fetch_scores(it.ticket, &sc) != DYN_OK) {
+        std::lock_guard<std::mutex> lk(m);
+        fail(std::string("batch segment scores: ") + dyn_aligner_last_error(it.a));
+        return;
+      }
+    }
+    const dyn_score_out* scp = scores ? &sc : nullptr;
+    const uint64_t bound = dyn_format_csv_bound_scores(it.a, it.n, it.res, evp, scp, it.readids, it.signalids);
     std::shared_ptr<Blob> blob;
     {
       std::lock_guard<std::mutex> lk(m);
@@ -289,7 +306,7 @@ struct dyn_csv_sink {
       if (spare.size() < 4) spare.push_back(blob);
     }
     const double c2 = now_ms();
-    const int frc = dyn_format_csv_events(it.a, it.n, it.res, evp, it.seqs, it.seq_offsets, it.readids, it.signalids, it.sig_offsets,
+    const int frc = dyn_format_csv_scores(it.a, it.n, it.res, evp, scp, it.seqs, it.seq_offsets, it.readids, it.signalids, it.sig_offsets,
                                           last_index.data(), std::min(threads, 8), blob->data.get(), blob->cap, begin.data(), end.data());
     if (frc != DYN_OK) {
       std::lock_guard<std::mutex> lk(m);
@@ -332,11 +349,12 @@ struct dyn_csv_sink {
   void sink_loop() {
     if (first_part) {
       auto hdr = std::make_shared<Blob>();
-      const char* text = events ? kHeaderEvents : kHeader;
-      const size_t len = std::strlen(text);
+      std::string text = events ? kHeaderEvents : kHeader;
+      if (scores) text.insert(text.size() - 1, kHeaderScores);  // before the newline
+      const size_t len = text.size();
       hdr->cap = len + 1;
       hdr->data.reset(new char[hdr->cap]);
-      std::memcpy(hdr->data.get(), text, len);
+      std::memcpy(hdr->data.get(), text.data(), len);
       hdr->begin = {0};
       hdr->end = {len};
       hdr->prefix = {0, len};
@@ -392,7 +410,7 @@ int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int 
   };
   if (!csv_zst_path || !errors_path || !out) return DYN_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  if (flags & ~DYN_CSV_EVENT_STATS) {
+  if (flags & ~(DYN_CSV_EVENT_STATS | DYN_CSV_SEGMENT_SCORES)) {
     put("dyn_csv_sink_open_ex: unknown flags");
     return DYN_ERR_INVALID_ARGUMENT;
   }
@@ -414,6 +432,7 @@ int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int 
   s->first_part = first != 0;
   s->last_part = last != 0;
   s->events = (flags & DYN_CSV_EVENT_STATS) != 0;
+  s->scores = (flags & DYN_CSV_SEGMENT_SCORES) != 0;
   dyn_csv_sink* p = s.release();
   for (int t = 0; t < p->threads; ++t) p->t_comp.emplace_back([p] { p->compress_loop(); });
   p->t_writer = std::thread([p] { p->writer_loop(); });
@@ -436,6 +455,8 @@ int dyn_csv_sink_submit_bases(dyn_csv_sink* s, dyn_aligner* a, dyn_batch* ticket
     return DYN_ERR_INVALID_ARGUMENT;
   if (s->events)
     if (int rc = dyneng::batch_check_events(ticket)) return rc;  // the message is the handle's (dyn_aligner_last_error)
+  if (s->scores)
+    if (int rc = dyneng::batch_check_scores(ticket)) return rc;
   {
     std::lock_guard<std::mutex> lk(s->m);
     if (s->closing) return DYN_ERR_INVALID_ARGUMENT;

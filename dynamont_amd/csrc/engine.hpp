@@ -149,6 +149,7 @@ struct dyn_aligner {
   bool event_stats = false;   // dyn_aligner_set_event_stats: read by every batch / ticket at its submission
   int rescale_iters = 0;      // dyn_aligner_set_rescale (0 .. 8): read by every batch / ticket at its submission
   bool kmer_summary = false;  // dyn_aligner_set_kmer_summary: read by every batch / ticket at its submission
+  int segment_scores = 0;     // dyn_aligner_set_segment_scores (window, 0 = off): read by every batch / ticket at its submission
   dyneng::DevBuf d_ksum;      // [6 num_kmers + 4] u64: the per-k-mer accumulator and its totals (kmer_summary_kernels.hpp),
                               // allocated and zeroed by the first dyn_aligner_set_kmer_summary(a, 1)
   bool ntk = false;     // created with mode "resquiggle" / "ntk"
@@ -242,6 +243,9 @@ struct dyn_batch {
   dyneng::DevBuf d_ev;                         // [3][capacity] level mean / stdev / median (event_stats.hip), when asked for
   bool ev_want = false;                        // the handle's event-stats switch when this batch / ticket was submitted
   bool ev_ready = false;                       // the last job computed the event columns into d_ev
+  dyneng::DevBuf d_sc;                         // [4][capacity] median_delta / mad_delta / homogeneity / scratch (segment_scores.hip)
+  int sc_want = 0;                             // the handle's segment-score window when this batch / ticket was submitted
+  bool sc_ready = false;                       // the last job computed the score columns into d_sc
   // per-read rescaling (rescale.hip, dyn_aligner_set_rescale)
   dyneng::DevBuf d_sig0;                       // the preprocessed signal x0, kept while d_sig holds a rescaled one
   dyneng::DevBuf d_rs;                         // [n] dynk::RescaleState | [capacity] row means of the fit (scratch)

@@ -620,11 +620,21 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     evc = dynk::EventCols{q.sig, e, e + b->capacity, e + 2 * b->capacity};
     b->ev_ready = true;
   }
+  dynk::ScoreCols scc{};
+  b->sc_ready = false;
+  if (calc && b->sc_want) {
+    // [median_delta | mad_delta | homogeneity | scratch] x capacity; rows of reads that fail keep the zeros
+    HIP_TRY(a, b->d_sc.ensure(std::max<uint64_t>(32, b->capacity * 32)));
+    if (b->capacity) HIP_TRY(a, hipMemsetAsync(b->d_sc.p, 0, b->capacity * 32, a->stream));
+    double* e = b->d_sc.as<double>();
+    scc = dynk::ScoreCols{q.sig, e, e + b->capacity, e + 2 * b->capacity, e + 3 * b->capacity, b->sc_want};
+    b->sc_ready = true;
+  }
   if (calc) {
     // the per-k-mer summary (once per job, after the last pass: the signal of a rescaling job is its last pass's)
     const std::vector<dynk::KmerSummary> ks = kmer_summary_args(b);
     dynk::launch_segments(q.descs, nr_all, rows_total, max_N, q.st, q.tb, b->d_rows.as<SegRow>(), m.k, a->stream, evc,
-                          ks.empty() ? dynk::KmerSummary{} : ks[0]);
+                          ks.empty() ? dynk::KmerSummary{} : ks[0], scc);
     for (size_t k = 1; k < ks.size(); ++k) dynk::launch_kmer_summary(q.descs, nr_all, max_N, q.st, q.tb, ks[k], a->stream);
   }
   if (job == DynJob::Train) {

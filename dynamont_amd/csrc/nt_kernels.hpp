@@ -244,11 +244,23 @@ struct KmerSummary {
 };
 void launch_kmer_summary(const ReadDesc* descs, int n_reads, uint32_t max_N, const ReadState* st, const TraceBuffers& tb,
                          const KmerSummary& ks, hipStream_t s);
+// per-border segment quality scores (segment_scores.hip, dyn_aligner_set_segment_scores): columns indexed like the output
+// rows, zeroed by the caller; median_delta == nullptr: not asked for
+struct ScoreCols {
+  const double* sig;  // the signal the read queue aligned (ReadDesc::sig_off counts from here)
+  double* median_delta;
+  double* mad_delta;
+  double* homogeneity;
+  double* scratch;    // one more column: the trimmed median of a row between the two homogeneity launches
+  int window;         // W, 1 .. 256
+};
+void launch_segment_scores(const ReadDesc* descs, int n_reads, uint64_t rows_total, uint32_t max_N, const ReadState* st,
+                           const TraceBuffers& tb, const ScoreCols& sc, hipStream_t s);
 // per-segment median posterior + output rows for all reads of descs (after launch_read_queue), then the signal levels when
-// `ev` asks for them and the per-k-mer summary when `ks` does
+// `ev` asks for them, the per-k-mer summary when `ks` does and the segment scores when `sc` does
 void launch_segments(const ReadDesc* descs, int n_reads, uint64_t rows_total, uint32_t max_N, const ReadState* st,
                      TraceBuffers tb, SegRow* rows, int kmer_size, hipStream_t s, const EventCols& ev = EventCols{},
-                     const KmerSummary& ks = KmerSummary{});
+                     const KmerSummary& ks = KmerSummary{}, const ScoreCols& sc = ScoreCols{});
 // per-read signal rescaling (rescale.hip, dyn_aligner_set_rescale): the transform x = (x0 - A) / B of read `read`
 struct RescaleState {
   double A;         // shift: 0.0 until a fit is applied

@@ -375,6 +375,8 @@ int session_publish(dyn_batch* b) {
   HIP_TRY(a, b->d_medlo.ensure(std::max<uint64_t>(8, b->capacity * 8)));
   b->ev_ready = b->ev_want;  // the columns are filled by session_finish_enqueue, behind the per-segment kernels
   if (b->ev_want) HIP_TRY(a, b->d_ev.ensure(std::max<uint64_t>(24, b->capacity * 24)));
+  b->sc_ready = b->sc_want != 0;
+  if (b->sc_want) HIP_TRY(a, b->d_sc.ensure(std::max<uint64_t>(32, b->capacity * 32)));
   ReadState* st = b->h_state.as<ReadState>();
   for (uint64_t i = 0; i < b->n; ++i) {
     st[i].Zb = 0.0;
@@ -535,9 +537,15 @@ int session_finish_enqueue(dyn_batch* b, hipStream_t s) {
     double* e = b->d_ev.as<double>();
     evc = dynk::EventCols{b->d_sig.as<double>(), e, e + b->capacity, e + 2 * b->capacity};
   }
+  dynk::ScoreCols scc{};
+  if (b->sc_ready) {
+    if (b->capacity) HIP_TRY(a, hipMemsetAsync(b->d_sc.p, 0, b->capacity * 32, s));
+    double* e = b->d_sc.as<double>();
+    scc = dynk::ScoreCols{b->d_sig.as<double>(), e, e + b->capacity, e + 2 * b->capacity, e + 3 * b->capacity, b->sc_want};
+  }
   const std::vector<dynk::KmerSummary> ks = kmer_summary_args(b);
   dynk::launch_segments(b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_rows_total, b->sess_max_N, b->d_state.as<ReadState>(), tb,
-                        b->d_rows.as<SegRow>(), a->model.k, s, evc, ks.empty() ? dynk::KmerSummary{} : ks[0]);
+                        b->d_rows.as<SegRow>(), a->model.k, s, evc, ks.empty() ? dynk::KmerSummary{} : ks[0], scc);
   for (size_t k = 1; k < ks.size(); ++k)
     dynk::launch_kmer_summary(b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_max_N, b->d_state.as<ReadState>(), tb, ks[k], s);
   HIP_TRY(a, hipGetLastError());

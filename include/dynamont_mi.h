@@ -150,6 +150,31 @@ typedef struct dyn_event_out {
   uint64_t capacity;
 } dyn_event_out;
 
+/* (added within ABI 10: a caller that must know looks the symbol up) Per-border segment quality scores of an
+ * align(calc_probabilities = 1) job whose handle had dyn_aligner_set_segment_scores(a, W) with W > 0 when the batch was
+ * submitted: caller-allocated columns indexed like the segment arrays of dyn_align_out; rows of failed reads are 0. For an
+ * OK read, x[0 .. S) is the ALIGNED signal (what dyn_batch_signals returns; with rescaling on, the last pass's), n its output
+ * rows, sp[j] row j's signal_positions, e[j] = sp[j+1] and e[n-1] = S. Units are the model's normalised units (not pA).
+ *   med(v)          v non-empty, L elements sorted as s: s[L/2] (odd L) or (s[L/2 - 1] + s[L/2]) / 2.0 (even L), one IEEE
+ *                   add and one IEEE divide
+ *   mad(v)          med(|v_i - med(v)|), one IEEE subtraction and fabs per element
+ *   median_delta[j] |med(B) - med(A)|, A = x[max(0, sp[j] - W) : sp[j]], B = x[sp[j] : min(sp[j] + W, S)]
+ *   mad_delta[j]    |mad(B) - mad(A)|;  a row with sp[j] == 0 (every read's row 0) has no A: both deltas are NaN
+ *   homogeneity[j]  L = e[j] - sp[j] >= 10: mad(x[sp[j] + trim : e[j] - trim]) with trim = max(L / 10, 1) in integer
+ *                   division (= the reference's int(0.1 * L) for every L <= 5 000 000); otherwise NaN
+ * NaN is always 0x7ff8000000000000; no result is -0.0 (fabs is last). These are the scores of the reference's
+ * src/dynamont/misc/compareTools.py (processReadScores), with these deviations: the reference works on the whole raw POD5
+ * signal with absolute positions and in raw units, we on the aligned slice, so windows are cut at the slice's ends; it skips
+ * the first border and the last segment and casts to float32 -- given x and sp, its `scores` array equals our rows
+ * 1 .. n-2 cast to float32 (tests/test_segment_scores_host.py). */
+#define DYN_SEGMENT_SCORES_MAX_WINDOW 256
+typedef struct dyn_score_out {
+  double* median_delta;  /* [capacity] */
+  double* mad_delta;     /* [capacity] */
+  double* homogeneity;   /* [capacity] */
+  uint64_t capacity;
+} dyn_score_out;
+
 /* (ABI 10) Per-read signal rescaling of an align(calc_probabilities = 1) job whose handle had dyn_aligner_set_rescale(a, K)
  * with K > 0 when the batch was submitted. Read r is aligned K + 1 times. x0 = its preprocessed signal (what
  * dyn_batch_signals returns with the switch off); A_0 = 0.0, B_0 = 1.0; pass k = 0 .. K aligns x_k, x_0 = x0 and
@@ -355,6 +380,12 @@ int dyn_aligner_set_event_stats(dyn_aligner* a, int on);
  * Each pass costs about one alignment; device memory: a copy of the batch's signal, 32 bytes per read, 8 per segment row.
  * dyn_multi_*: set it on each device's handle (dyn_multi_handle). */
 int dyn_aligner_set_rescale(dyn_aligner* a, int iters);
+/* (added within ABI 10) align(calc_probabilities = 1) also computes the per-border segment scores (dyn_score_out) with a
+ * window of `window` samples on the device, behind the per-segment kernels, for every batch or ticket SUBMITTED while
+ * window > 0; 4 x 8 bytes of device memory per segment row for those batches only. window = 0 ..
+ * DYN_SEGMENT_SCORES_MAX_WINDOW, default 0 = off: nothing is allocated, launched or changed. DYN_ERR_INVALID_ARGUMENT +
+ * message outside that range. Tickets merge into one launch only with tickets of the same window. */
+int dyn_aligner_set_segment_scores(dyn_aligner* a, int window);
 /* (added within ABI 10: a caller that must know looks the symbol up) Per-k-mer level summary of a run. While it is on, every output row (segment) of every read with status 0 of an
  * align(calc_probabilities = 1) batch or ticket SUBMITTED on this handle is added, on the device behind the per-segment
  * kernels, to its k-mer's entry of an accumulator that lives on the handle: six u64 per k-mer code (48 bytes x num_kmers of
@@ -436,6 +467,17 @@ int dyn_format_csv_events(const dyn_aligner* a, uint64_t n_reads, const dyn_alig
                           const int64_t* last_index, int threads, char* out, uint64_t out_cap,
                           uint64_t* row_begin, uint64_t* row_end);
 
+/* (added within ABI 10) The same with the segment scores of dyn_batch_fetch_scores as well: after the level columns (if ev
+ * is given) every row gets ",{median_delta:.6f},{mad_delta:.6f},{homogeneity:.6f}", NaN as "nan" like Python's f"{x:.6f}".
+ * ev and sc may each be NULL; sc == NULL: dyn_format_csv_events / dyn_format_csv_bound_events, byte for byte. */
+uint64_t dyn_format_csv_bound_scores(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                                     const dyn_score_out* sc, const char* const* readids, const char* const* signalids);
+int dyn_format_csv_scores(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                          const dyn_score_out* sc, const char* seqs, const uint64_t* seq_offsets, const char* const* readids,
+                          const char* const* signalids, const int64_t* sig_offsets,
+                          const int64_t* last_index, int threads, char* out, uint64_t out_cap,
+                          uint64_t* row_begin, uint64_t* row_end);
+
 /* Closes the gaps between the per-read ranges dyn_format_csv produced: all rows become one contiguous run at the
  * front of `out`, in read order; row_begin/row_end are updated. Returns the total byte count. */
 uint64_t dyn_csv_compact(char* out, uint64_t n_reads, uint64_t* row_begin, uint64_t* row_end);
@@ -473,6 +515,11 @@ int dyn_csv_sink_open_part(const char* csv_zst_path, const char* errors_path, in
  * whose ticket was submitted without dyn_aligner_set_event_stats on fails with DYN_ERR_INVALID_ARGUMENT. `.errors` lines
  * are unchanged. flags = 0 is dyn_csv_sink_open_part. */
 #define DYN_CSV_EVENT_STATS 0x1u
+/* (added within ABI 10) DYN_CSV_SEGMENT_SCORES: the header gains ",median_delta,mad_delta,homogeneity" (after the level
+ * columns, if any), every row the three columns (dyn_format_csv_scores); the sink fetches each ticket's scores after its
+ * wait, and a submit whose ticket was submitted with dyn_aligner_set_segment_scores off fails with
+ * DYN_ERR_INVALID_ARGUMENT. */
+#define DYN_CSV_SEGMENT_SCORES 0x2u
 int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int level, int threads, int first, int last,
                          uint32_t flags, dyn_csv_sink** out, char* err, uint64_t errcap);
 #define DYN_ZSTD_FRAME_END "\x01\x00\x00" /* an empty last block (raw, size 0): 3 bytes; the frames carry no checksum */
@@ -588,6 +635,10 @@ int dyn_batch_fetch_train(dyn_batch* b, dyn_train_out* out, double* pooled3n);
  * (capacity >= dyn_segment_capacity()). DYN_ERR_INVALID_ARGUMENT + message for a batch submitted without
  * dyn_aligner_set_event_stats on, or aligned with calc_probabilities = 0. */
 int dyn_batch_fetch_events(dyn_batch* b, dyn_event_out* out);
+/* (added within ABI 10) The segment scores of the batch's last align(calc_probabilities = 1) job, copied on the handle's
+ * own non-blocking stream. DYN_ERR_INVALID_ARGUMENT (with a message) when the batch was submitted with
+ * dyn_aligner_set_segment_scores off, or aligned with calc_probabilities = 0, or out->capacity is too small. */
+int dyn_batch_fetch_scores(dyn_batch* b, dyn_score_out* out);
 /* (ABI 10) Copy the per-read transforms of the last dyn_batch_align (or of a completed ticket, merged launch or not) into
  * `out` (n >= the batch's read count). DYN_ERR_INVALID_ARGUMENT + message for a batch submitted with
  * dyn_aligner_set_rescale(a, 0), or aligned with calc_probabilities = 0. */

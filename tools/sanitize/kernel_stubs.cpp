@@ -23,11 +23,19 @@ void launch_prep_params(const int32_t*, const Emis*, Emis*, uint64_t, uint32_t, 
 void launch_pool_init(const PagePool&, uint32_t, int, hipStream_t) { no_device("launch_pool_init"); }
 void launch_read_queue(QueueJob, bool, const QueueArgs&, int, hipStream_t) { no_device("launch_read_queue"); }
 void launch_segments(const ReadDesc*, int, uint64_t, uint32_t, const ReadState*, TraceBuffers, SegRow*, int, hipStream_t, const EventCols&,
-                     const KmerSummary&) {
+                     const KmerSummary&, const ScoreCols&) {
   no_device("launch_segments");
+}
+void launch_segment_scores(const ReadDesc*, int, uint64_t, uint32_t, const ReadState*, const TraceBuffers&, const ScoreCols&, hipStream_t) {
+  no_device("launch_segment_scores");
 }
 void launch_kmer_summary(const ReadDesc*, int, uint32_t, const ReadState*, const TraceBuffers&, const KmerSummary&, hipStream_t) {
   no_device("launch_kmer_summary");
+}
+void launch_rescale_init(RescaleState*, uint64_t, hipStream_t) { no_device("launch_rescale_init"); }
+void launch_rescale_pass(const ReadDesc*, int, uint32_t, const ReadState*, const TraceBuffers&, const double*, double*, const Emis*, double*,
+                         RescaleState*, hipStream_t) {
+  no_device("launch_rescale_pass");
 }
 size_t pool_stats_temp_bytes(uint64_t, uint64_t) { return 8; }
 size_t pool_stats_work_bytes(uint64_t) { return 8; }
