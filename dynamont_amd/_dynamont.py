@@ -110,6 +110,21 @@ class AlignBatchResult:
         self.rescale_shift = self.rescale_scale = self.rescale_iters = None
         # per-border segment scores (Aligner.set_segment_scores): float64 [cap] like the segment columns, None when off
         self.median_delta = self.mad_delta = self.homogeneity = None
+        # per-border posterior confidence (Aligner.set_border_confidence): float64 [cap] like the segment columns, None when off
+        self.border_probability = self.border_window_probability = None
+
+    def _fetch_borders(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
+        """dyn_batch_fetch_borders into this object's border columns (allocated on first use), or drop them."""
+        if not wanted:
+            self.border_probability = self.border_window_probability = None
+            return
+        if self.border_probability is None:
+            self.border_probability, self.border_window_probability = (np.zeros(self.cap) for _ in range(2))
+        bd = N.DynBorderOut(_ptr(self.border_probability, N.c_double_p), _ptr(self.border_window_probability, N.c_double_p),
+                            self.cap)
+        rc = L.dyn_batch_fetch_borders(handle, C.byref(bd))
+        if rc != N.DYN_OK:
+            _raise(rc, aligner.last_error())
 
     def _fetch_scores(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
         """dyn_batch_fetch_scores into this object's score columns (allocated on first use), or drop them."""
@@ -179,6 +194,9 @@ class AlignBatchResult:
             d["median_delta"] = self.median_delta[a:b].copy()
             d["mad_delta"] = self.mad_delta[a:b].copy()
             d["homogeneity"] = self.homogeneity[a:b].copy()
+        if self.border_probability is not None:  # only when requested (Aligner.set_border_confidence)
+            d["border_probability"] = self.border_probability[a:b].copy()
+            d["border_window_probability"] = self.border_window_probability[a:b].copy()
         if self.rescale_shift is not None:  # only when requested (Aligner.set_rescale)
             d["rescale_shift"] = float(self.rescale_shift[i])
             d["rescale_scale"] = float(self.rescale_scale[i])
@@ -217,13 +235,18 @@ def format_csv(aligner: "Aligner", res: AlignBatchResult, sequences: Sequence[st
     if res.median_delta is not None:
         sc = C.byref(N.DynScoreOut(_ptr(res.median_delta, N.c_double_p), _ptr(res.mad_delta, N.c_double_p),
                                    _ptr(res.homogeneity, N.c_double_p), res.cap))
-    cap = int(L.dyn_format_csv_bound_scores(aligner._h, n, C.byref(res._c), ev, sc, rid, sid))
+    # ... and the border confidence (Aligner.set_border_confidence): two more after those
+    bd = None
+    if res.border_probability is not None:
+        bd = C.byref(N.DynBorderOut(_ptr(res.border_probability, N.c_double_p),
+                                    _ptr(res.border_window_probability, N.c_double_p), res.cap))
+    cap = int(L.dyn_format_csv_bound_borders(aligner._h, n, C.byref(res._c), ev, sc, bd, rid, sid))
     # one grow-only buffer per handle: first-touch page faults of a fresh 350 MB buffer cost ~100x
     # the formatting itself (15 ms per 1 024-read batch with warm pages)
     buf = getattr(aligner, "_csv_buf", None)
     if buf is None or buf.size < cap:
         buf = aligner._csv_buf = np.empty(max(cap, 1), dtype=np.uint8)
-    rc = L.dyn_format_csv_scores(aligner._h, n, C.byref(res._c), ev, sc, seqs, _ptr(seq_off, N.c_u64_p), rid, sid,
+    rc = L.dyn_format_csv_borders(aligner._h, n, C.byref(res._c), ev, sc, bd, seqs, _ptr(seq_off, N.c_u64_p), rid, sid,
                           so.ctypes.data_as(C.POINTER(C.c_int64)), li.ctypes.data_as(C.POINTER(C.c_int64)),
                           int(threads), buf.ctypes.data, cap, _ptr(begin, N.c_u64_p), _ptr(end, N.c_u64_p))
     if rc != N.DYN_OK:
@@ -343,6 +366,7 @@ class Batch:
         self._levels = bool(calc_probabilities) and self._al._event_stats  # the switch at submission decides
         self._rescale = bool(calc_probabilities) and self._al._rescale > 0
         self._scores = bool(calc_probabilities) and self._al._segment_scores > 0
+        self._borders = bool(calc_probabilities) and self._al._border_confidence > 0
         rc = self._L.dyn_batch_align(self._h, int(bool(calc_probabilities)))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
@@ -364,6 +388,7 @@ class Batch:
         out._fetch_levels(self._L, self._h, self._al, getattr(self, "_levels", False))
         out._fetch_rescale(self._L, self._h, self._al, getattr(self, "_rescale", False))
         out._fetch_scores(self._L, self._h, self._al, getattr(self, "_scores", False))
+        out._fetch_borders(self._L, self._h, self._al, getattr(self, "_borders", False))
         return out
 
     def fetch_events(self, out: N.DynEventOut) -> None:
@@ -375,6 +400,12 @@ class Batch:
     def fetch_scores(self, out: N.DynScoreOut) -> None:
         """dyn_batch_fetch_scores into caller-owned columns (raises ValueError for a batch that did not ask)."""
         rc = self._L.dyn_batch_fetch_scores(self._h, C.byref(out))
+        if rc != N.DYN_OK:
+            _raise(rc, self._al.last_error())
+
+    def fetch_borders(self, out: N.DynBorderOut) -> None:
+        """dyn_batch_fetch_borders into caller-owned columns (raises ValueError for a batch that did not ask)."""
+        rc = self._L.dyn_batch_fetch_borders(self._h, C.byref(out))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
 
@@ -430,7 +461,7 @@ class AsyncBatch:
     (the library reads them until the batch is complete)."""
 
     def __init__(self, aligner: "Aligner", handle, result, keep, levels: bool = False, rescale: bool = False,
-                 scores: bool = False):
+                 scores: bool = False, borders: bool = False):
         self._al = aligner
         self._L = N.lib()
         self._h = handle
@@ -440,6 +471,7 @@ class AsyncBatch:
         self._levels = levels  # an align ticket submitted with the event-stats switch on (and calc_probabilities)
         self._rescale = rescale  # ... with the rescale switch on
         self._scores = scores  # ... with the segment-scores switch on
+        self._borders = borders  # ... with the border-confidence switch on
 
     def wait(self):
         if not self._waited:
@@ -451,11 +483,13 @@ class AsyncBatch:
                 self.result._fetch_levels(self._L, self._h, self._al, self._levels)
                 self.result._fetch_rescale(self._L, self._h, self._al, self._rescale)
                 self.result._fetch_scores(self._L, self._h, self._al, self._scores)
+                self.result._fetch_borders(self._L, self._h, self._al, self._borders)
         return self.result
 
     fetch_events = Batch.fetch_events
     fetch_rescale = Batch.fetch_rescale
     fetch_scores = Batch.fetch_scores
+    fetch_borders = Batch.fetch_borders
 
     def timing(self) -> dict:
         self.wait()
@@ -547,6 +581,7 @@ class Aligner:
     _event_stats = False  # set_event_stats
     _rescale = 0  # set_rescale
     _segment_scores = 0  # set_segment_scores
+    _border_confidence = 0  # set_border_confidence
 
     def __init__(self, model_file: str, pore, mode: str = "basic", threads: int = 1, band: int = 400,
                  device=None):
@@ -655,6 +690,17 @@ class Aligner:
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
         self._segment_scores = int(window)
+
+    def set_border_confidence(self, window: int) -> None:
+        """dyn_aligner_set_border_confidence: align(calc_probabilities=True) jobs submitted while ``window`` (0 .. 256) > 0 also
+        compute, from the lattice's own posteriors, how sure every border is: ``border_probability`` (the posterior mass on the
+        called border) and ``border_window_probability`` (the mass within ``window`` samples of it).
+        Results carry them as ``AlignBatchResult.border_probability`` / ``.border_window_probability`` and ``read(i)`` adds
+        the two keys."""
+        rc = self._L.dyn_aligner_set_border_confidence(self._h, int(window))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        self._border_confidence = int(window)
 
     def set_rescale(self, iters: int) -> None:
         """dyn_aligner_set_rescale: align(calc_probabilities=True) jobs submitted while ``iters`` (0 .. 8) > 0 align every
@@ -778,7 +824,8 @@ class Aligner:
             _raise(rc, self.last_error())
         return AsyncBatch(self, h, out, (sig, sig_off, seqs, seq_off), levels=self._event_stats and bool(calc_probabilities),
                           rescale=self._rescale > 0 and bool(calc_probabilities),
-                          scores=self._segment_scores > 0 and bool(calc_probabilities))
+                          scores=self._segment_scores > 0 and bool(calc_probabilities),
+                          borders=self._border_confidence > 0 and bool(calc_probabilities))
 
     def _raw_args(self, raw, shift, scale, calibration=None):
         scattered = isinstance(raw, (list, tuple))
@@ -830,7 +877,8 @@ class Aligner:
         return AsyncBatch(self, h, out, (raw, raw_off, shift, scale, seqs, seq_off, cal),
                           levels=self._event_stats and bool(calc_probabilities),
                           rescale=self._rescale > 0 and bool(calc_probabilities),
-                          scores=self._segment_scores > 0 and bool(calc_probabilities))
+                          scores=self._segment_scores > 0 and bool(calc_probabilities),
+                          borders=self._border_confidence > 0 and bool(calc_probabilities))
 
     def align_vbz_async(self, chunks, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 3,
                         n_sigmas: float = 3.0, f32: bool = False, calc_probabilities: bool = True,
@@ -866,7 +914,8 @@ class Aligner:
         return AsyncBatch(self, h, out, (ptrs, nbytes, samples, read_off, skip, raw_off, shift, scale, seqs, seq_off, cal),
                           levels=self._event_stats and bool(calc_probabilities),
                           rescale=self._rescale > 0 and bool(calc_probabilities),
-                          scores=self._segment_scores > 0 and bool(calc_probabilities))
+                          scores=self._segment_scores > 0 and bool(calc_probabilities),
+                          borders=self._border_confidence > 0 and bool(calc_probabilities))
 
     def train_raw_async(self, raw, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 7,
                         n_sigmas: float = 5.0, f32: bool = True, pooled: bool = False,

@@ -15,12 +15,14 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("DYN_LIB_PATH") or os.path.join(HERE, "libdynamont_mi.so")
 SOURCES = ["dynamont_mi.cpp", "buffers.cpp", "launch.cpp", "session.cpp", "async_engine.cpp", "pore_model.cpp", "csv_format.cpp", "csv_sink.cpp", "vbz_decode.cpp", "bam_reader.cpp", "rccl_comm.cpp", "model_format.cpp",
            "nt_kernels.hip", "pool_stats.hip", "wide_band.hip", "event_stats.hip", "rescale.hip", "kmer_summary.hip", "segment_scores.hip"]
-HEADERS = ["engine.hpp", "engine_internal.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "dp_cell.hpp", "segment_kernels.hpp", "kmer_summary_kernels.hpp", "segment_score_kernels.hpp", "band_runs.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
+HEADERS = ["engine.hpp", "engine_internal.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "dp_cell.hpp", "segment_kernels.hpp", "kmer_summary_kernels.hpp", "segment_score_kernels.hpp", "border_kernels.hpp", "band_runs.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
 
 DYN_DEVICE_HOST_ONLY = -2
 DYN_CSV_EVENT_STATS = 0x1  # dyn_csv_sink_open_ex flag
 DYN_CSV_SEGMENT_SCORES = 0x2  # dyn_csv_sink_open_ex flag
 DYN_SEGMENT_SCORES_MAX_WINDOW = 256
+DYN_CSV_BORDER_CONFIDENCE = 0x8  # dyn_csv_sink_open_ex flag
+DYN_BORDER_CONFIDENCE_MAX_WINDOW = 256
 DYN_OK, DYN_ERR_INVALID_ARGUMENT, DYN_ERR_RUNTIME, DYN_ERR_DEVICE, DYN_ERR_OUT_OF_MEMORY = range(5)
 
 c_double_p = C.POINTER(C.c_double)
@@ -49,6 +51,10 @@ class DynEventOut(C.Structure):
 
 class DynScoreOut(C.Structure):
     _fields_ = [("median_delta", c_double_p), ("mad_delta", c_double_p), ("homogeneity", c_double_p), ("capacity", C.c_uint64)]
+
+
+class DynBorderOut(C.Structure):
+    _fields_ = [("border_probability", c_double_p), ("border_window_probability", c_double_p), ("capacity", C.c_uint64)]
 
 
 class DynRescaleOut(C.Structure):
@@ -113,6 +119,7 @@ SIGNATURES = {
     "dyn_aligner_set_event_stats": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_aligner_set_rescale": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_aligner_set_segment_scores": (C.c_int, [C.c_void_p, C.c_int]),
+    "dyn_aligner_set_border_confidence": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_aligner_set_kmer_summary": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_aligner_kmer_summary_fetch": (C.c_int, [C.c_void_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p]),
     "dyn_aligner_kmer_summary_reset": (C.c_int, [C.c_void_p]),
@@ -142,6 +149,13 @@ SIGNATURES = {
                                         C.POINTER(DynScoreOut), C.c_char_p, c_u64_p, C.POINTER(C.c_char_p),
                                         C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_void_p,
                                         C.c_uint64, c_u64_p, c_u64_p]),
+    "dyn_format_csv_bound_borders": (C.c_uint64, [C.c_void_p, C.c_uint64, C.POINTER(DynAlignOut), C.POINTER(DynEventOut),
+                                                  C.POINTER(DynScoreOut), C.POINTER(DynBorderOut), C.POINTER(C.c_char_p),
+                                                  C.POINTER(C.c_char_p)]),
+    "dyn_format_csv_borders": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(DynAlignOut), C.POINTER(DynEventOut),
+                                         C.POINTER(DynScoreOut), C.POINTER(DynBorderOut), C.c_char_p, c_u64_p,
+                                         C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                         C.c_int, C.c_void_p, C.c_uint64, c_u64_p, c_u64_p]),
     "dyn_csv_compact": (C.c_uint64, [C.c_void_p, C.c_uint64, c_u64_p, c_u64_p]),
     "dyn_csv_sink_open": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_uint64]),
     "dyn_csv_sink_open_part": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_uint64]),
@@ -172,6 +186,7 @@ SIGNATURES = {
     "dyn_batch_fetch": (C.c_int, [C.c_void_p, C.POINTER(DynAlignOut)]),
     "dyn_batch_fetch_events": (C.c_int, [C.c_void_p, C.POINTER(DynEventOut)]),
     "dyn_batch_fetch_scores": (C.c_int, [C.c_void_p, C.POINTER(DynScoreOut)]),
+    "dyn_batch_fetch_borders": (C.c_int, [C.c_void_p, C.POINTER(DynBorderOut)]),
     "dyn_batch_fetch_rescale": (C.c_int, [C.c_void_p, C.POINTER(DynRescaleOut)]),
     "dyn_batch_fetch_train": (C.c_int, [C.c_void_p, C.POINTER(DynTrainOut), c_double_p]),
     "dyn_batch_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_u64_p, C.POINTER(C.c_void_p)]),

@@ -151,7 +151,8 @@ static bool mergeable(const dyn_batch* x) {
   return x->job != DynJob::Train && x->n > 0 && 2 * x->n <= 3 * (uint64_t)x->a->n_cus * dynk::WAVES_PER_CU;
 }
 static bool same_kind(const dyn_batch* x, const dyn_batch* y) {
-  if (x->job != y->job || x->has_raw != y->has_raw || x->ev_want != y->ev_want || x->rs_want != y->rs_want || x->sc_want != y->sc_want)
+  if (x->job != y->job || x->has_raw != y->has_raw || x->ev_want != y->ev_want || x->rs_want != y->rs_want || x->sc_want != y->sc_want ||
+      x->bc_want != y->bc_want)
     return false;
   if (!x->has_raw) return true;
   const RawSource &p = x->raw_src, &q = y->raw_src;
@@ -214,6 +215,7 @@ std::shared_ptr<BatchGroup> Pipeline::merge(const std::vector<dyn_batch*>& ticke
   g->ev_want = first->ev_want;  // (same_kind: every member asked alike)
   g->rs_want = first->rs_want;
   g->sc_want = first->sc_want;
+  g->bc_want = first->bc_want;
   // the per-k-mer summary is snapshot per ticket and same_kind does not look at it: the launch sums the members that asked
   for (dyn_batch* t : tickets) {
     if (!t->ks_want || !t->n) continue;
@@ -768,6 +770,7 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
   b->rs_want = a->rescale_iters;
   b->ks_want = a->kmer_summary;
   b->sc_want = a->segment_scores;
+  b->bc_want = a->border_confidence;
   b->in_signals = signals;
   if (rs) {
     b->has_raw = true;

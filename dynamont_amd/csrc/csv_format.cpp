@@ -98,6 +98,7 @@ struct Args {
   const dyn_align_out* res;
   const dyn_event_out* ev;  // nullptr: no level columns
   const dyn_score_out* sc;  // nullptr: no segment-score columns
+  const dyn_border_out* bd;  // nullptr: no border-confidence columns
   const char* seqs;
   const uint64_t* seq_offsets;
   const char* const* readids;
@@ -131,6 +132,12 @@ uint64_t read_bound(const Args& a, uint64_t i) {
     b += 3 * n;  // the commas
     for (uint64_t s = o; s < o + n; ++s)
       b += event_value_bound(a.sc->median_delta[s]) + event_value_bound(a.sc->mad_delta[s]) + event_value_bound(a.sc->homogeneity[s]);
+  }
+  if (a.bd) {
+    const uint64_t o = a.res->seg_offsets[i];
+    b += 2 * n;  // the commas
+    for (uint64_t s = o; s < o + n; ++s)
+      b += event_value_bound(a.bd->border_probability[s]) + event_value_bound(a.bd->border_window_probability[s]);
   }
   return b;
 }
@@ -184,6 +191,12 @@ char* format_read(const Args& a, uint64_t i, char* p) {
       *p++ = ',';
       p = put_prob6<true>(p, a.sc->homogeneity[o + s]);
     }
+    if (a.bd) {  // (a window sum may exceed 1 by rounding: printed as any other value, "1.000000")
+      *p++ = ',';
+      p = put_prob6<true>(p, a.bd->border_probability[o + s]);
+      *p++ = ',';
+      p = put_prob6<true>(p, a.bd->border_window_probability[o + s]);
+    }
     *p++ = '\n';
   }
   return p;
@@ -205,10 +218,17 @@ extern "C" uint64_t dyn_format_csv_bound_events(const dyn_aligner* a, uint64_t n
 extern "C" uint64_t dyn_format_csv_bound_scores(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
                                                 const dyn_event_out* ev, const dyn_score_out* sc, const char* const* readids,
                                                 const char* const* signalids) {
+  return dyn_format_csv_bound_borders(a, n_reads, res, ev, sc, nullptr, readids, signalids);
+}
+
+extern "C" uint64_t dyn_format_csv_bound_borders(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
+                                                 const dyn_event_out* ev, const dyn_score_out* sc, const dyn_border_out* bd,
+                                                 const char* const* readids, const char* const* signalids) {
   if (!a || !res || (ev && (!ev->mean || !ev->stdev || !ev->median)) ||
-      (sc && (!sc->median_delta || !sc->mad_delta || !sc->homogeneity)))
+      (sc && (!sc->median_delta || !sc->mad_delta || !sc->homogeneity)) ||
+      (bd && (!bd->border_probability || !bd->border_window_probability)))
     return 0;
-  Args args{0, 0, res, ev, sc, nullptr, nullptr, readids, signalids, nullptr, nullptr};
+  Args args{0, 0, res, ev, sc, bd, nullptr, nullptr, readids, signalids, nullptr, nullptr};
   uint64_t total = 0;
   for (uint64_t i = 0; i < n_reads; ++i) total += read_bound(args, i);
   return total;
@@ -237,14 +257,24 @@ extern "C" int dyn_format_csv_scores(const dyn_aligner* a, uint64_t n_reads, con
                                      const uint64_t* seq_offsets, const char* const* readids, const char* const* signalids,
                                      const int64_t* sig_offsets, const int64_t* last_index, int threads,
                                      char* out, uint64_t out_cap, uint64_t* row_begin, uint64_t* row_end) {
+  return dyn_format_csv_borders(a, n_reads, res, ev, sc, nullptr, seqs, seq_offsets, readids, signalids, sig_offsets, last_index,
+                                threads, out, out_cap, row_begin, row_end);
+}
+
+extern "C" int dyn_format_csv_borders(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
+                                      const dyn_event_out* ev, const dyn_score_out* sc, const dyn_border_out* bd,
+                                      const char* seqs, const uint64_t* seq_offsets, const char* const* readids,
+                                      const char* const* signalids, const int64_t* sig_offsets, const int64_t* last_index,
+                                      int threads, char* out, uint64_t out_cap, uint64_t* row_begin, uint64_t* row_end) {
   if (!a || !res || !res->status || !res->n_segments || !res->seg_offsets || !res->sequence_positions ||
       !res->signal_positions || !res->probabilities || !out || !row_begin || !row_end ||
-      (ev && (!ev->mean || !ev->stdev || !ev->median)) || (sc && (!sc->median_delta || !sc->mad_delta || !sc->homogeneity)))
+      (ev && (!ev->mean || !ev->stdev || !ev->median)) || (sc && (!sc->median_delta || !sc->mad_delta || !sc->homogeneity)) ||
+      (bd && (!bd->border_probability || !bd->border_window_probability)))
     return DYN_ERR_INVALID_ARGUMENT;
   dyn_info info;
   dyn_aligner_info(a, &info);
   if (info.kmer_size > 31) return DYN_ERR_INVALID_ARGUMENT;
-  Args args{info.kmer_size, info.rna, res, ev, sc, seqs, seq_offsets, readids, signalids, sig_offsets, last_index};
+  Args args{info.kmer_size, info.rna, res, ev, sc, bd, seqs, seq_offsets, readids, signalids, sig_offsets, last_index};
   // every read formats straight into its own worst-case slot of the caller's buffer: no allocation,
   // no shared cache lines between threads
   uint64_t pos = 0;

@@ -43,6 +43,7 @@ const char kHeaderEvents[] =
     "readid,signalid,start,end,basepos,base,motif,state,posterior_probability,polish,level_mean,level_stdv,level_median\n";
 
 const char kHeaderScores[] = ",median_delta,mad_delta,homogeneity";
+const char kHeaderBorders[] = ",border_probability,border_window_probability";
 
 struct Blob {  // the formatted rows of one batch; freed when its last job has been compressed
   std::unique_ptr<char[]> data;
@@ -82,6 +83,7 @@ namespace dyneng {
 // DYN_OK when the ticket was submitted with the handle's event-stats switch on (dynamont_mi.cpp); else the handle's message
 int batch_check_events(dyn_batch* b);
 int batch_check_scores(dyn_batch* b);
+int batch_check_borders(dyn_batch* b);
 }
 
 struct dyn_csv_sink {
@@ -105,6 +107,8 @@ struct dyn_csv_sink {
   std::vector<double> ev_cols;                // [3][capacity] the batch's levels (dyn_batch_fetch_events)
   bool scores = false;                        // DYN_CSV_SEGMENT_SCORES
   std::vector<double> sc_cols;                // [3][capacity] the batch's segment scores (dyn_batch_fetch_scores)
+  bool borders = false;                       // DYN_CSV_BORDER_CONFIDENCE
+  std::vector<double> bd_cols;                // [2][capacity] the batch's border confidence (dyn_batch_fetch_borders)
   std::thread t_sink, t_writer;
   std::vector<std::thread> t_comp;
   std::vector<std::shared_ptr<Blob>> spare;  // recycled row buffers (first-touch page faults cost more than formatting)
@@ -288,7 +292,19 @@ struct dyn_csv_sink {
       }
     }
     const dyn_score_out* scp = scores ? &sc : nullptr;
-    const uint64_t bound = dyn_format_csv_bound_scores(it.a, it.n, it.res, evp, scp, it.readids, it.signalids);
+    dyn_border_out bd{};
+    if (borders) {
+      const uint64_t cap = it.res->seg_offsets ? it.res->seg_offsets[it.n] : 0;
+      bd_cols.resize(std::max<uint64_t>(1, 2 * cap));
+      bd = dyn_border_out{bd_cols.data(), bd_cols.data() + cap, cap};
+      if (dyn_batch_fetch_borders(it.ticket, &bd) != DYN_OK) {
+        std::lock_guard<std::mutex> lk(m);
+        fail(std::string("batch border confidence: ") + dyn_aligner_last_error(it.a));
+        return;
+      }
+    }
+    const dyn_border_out* bdp = borders ? &bd : nullptr;
+    const uint64_t bound = dyn_format_csv_bound_borders(it.a, it.n, it.res, evp, scp, bdp, it.readids, it.signalids);
     std::shared_ptr<Blob> blob;
     {
       std::lock_guard<std::mutex> lk(m);
@@ -306,7 +322,7 @@ struct dyn_csv_sink {
       if (spare.size() < 4) spare.push_back(blob);
     }
     const double c2 = now_ms();
-    const int frc = dyn_format_csv_scores(it.a, it.n, it.res, evp, scp, it.seqs, it.seq_offsets, it.readids, it.signalids, it.sig_offsets,
+    const int frc = dyn_format_csv_borders(it.a, it.n, it.res, evp, scp, bdp, it.seqs, it.seq_offsets, it.readids, it.signalids, it.sig_offsets,
                                           last_index.data(), std::min(threads, 8), blob->data.get(), blob->cap, begin.data(), end.data());
     if (frc != DYN_OK) {
       std::lock_guard<std::mutex> lk(m);
@@ -351,6 +367,7 @@ struct dyn_csv_sink {
       auto hdr = std::make_shared<Blob>();
       std::string text = events ? kHeaderEvents : kHeader;
       if (scores) text.insert(text.size() - 1, kHeaderScores);  // before the newline
+      if (borders) text.insert(text.size() - 1, kHeaderBorders);
       const size_t len = text.size();
       hdr->cap = len + 1;
       hdr->data.reset(new char[hdr->cap]);
@@ -410,7 +427,7 @@ int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int 
   };
   if (!csv_zst_path || !errors_path || !out) return DYN_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  if (flags & ~(DYN_CSV_EVENT_STATS | DYN_CSV_SEGMENT_SCORES)) {
+  if (flags & ~(DYN_CSV_EVENT_STATS | DYN_CSV_SEGMENT_SCORES | DYN_CSV_BORDER_CONFIDENCE)) {
     put("dyn_csv_sink_open_ex: unknown flags");
     return DYN_ERR_INVALID_ARGUMENT;
   }
@@ -433,6 +450,7 @@ int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int 
   s->last_part = last != 0;
   s->events = (flags & DYN_CSV_EVENT_STATS) != 0;
   s->scores = (flags & DYN_CSV_SEGMENT_SCORES) != 0;
+  s->borders = (flags & DYN_CSV_BORDER_CONFIDENCE) != 0;
   dyn_csv_sink* p = s.release();
   for (int t = 0; t < p->threads; ++t) p->t_comp.emplace_back([p] { p->compress_loop(); });
   p->t_writer = std::thread([p] { p->writer_loop(); });
@@ -457,6 +475,8 @@ int dyn_csv_sink_submit_bases(dyn_csv_sink* s, dyn_aligner* a, dyn_batch* ticket
     if (int rc = dyneng::batch_check_events(ticket)) return rc;  // the message is the handle's (dyn_aligner_last_error)
   if (s->scores)
     if (int rc = dyneng::batch_check_scores(ticket)) return rc;
+  if (s->borders)
+    if (int rc = dyneng::batch_check_borders(ticket)) return rc;
   {
     std::lock_guard<std::mutex> lk(s->m);
     if (s->closing) return DYN_ERR_INVALID_ARGUMENT;

@@ -59,7 +59,7 @@ void attach_cache(dyn_batch* b) {
   dyneng::BufCache* c = &b->a->cache;
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_wide})
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_wide})
     d->cache = c;
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->cache = c;
 }
@@ -551,6 +551,17 @@ int dyn_aligner_set_segment_scores(dyn_aligner* a, int window) {
   return DYN_OK;
 }
 
+int dyn_aligner_set_border_confidence(dyn_aligner* a, int window) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  if (window < 0 || window > DYN_BORDER_CONFIDENCE_MAX_WINDOW) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = "dyn_aligner_set_border_confidence: window must be 0 .. 256, got " + std::to_string(window);
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  a->border_confidence = window;
+  return DYN_OK;
+}
+
 int dyn_aligner_set_kmer_summary(dyn_aligner* a, int on) {
   if (!a) return DYN_ERR_INVALID_ARGUMENT;
   if (a->ntk) {
@@ -863,7 +874,7 @@ void dyn_batch_destroy(dyn_batch* b) {
   if (b->a && !b->a->host_only) (void)hipSetDevice(b->a->device);
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl})
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl})
     d->release();
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->release();
   for (hipEvent_t e : b->events) (void)hipEventDestroy(e);
@@ -1006,6 +1017,7 @@ int run_job_sync(dyn_batch* b, DynJob job) {
     b->rs_want = a->rescale_iters;
     b->ks_want = a->kmer_summary;
     b->sc_want = a->segment_scores;
+    b->bc_want = a->border_confidence;
     rc = enqueue_job(b, job);
     if (rc != DYN_OK) {
       (void)hipStreamSynchronize(a->stream);
@@ -1102,9 +1114,41 @@ int batch_check_scores(dyn_batch* b) {
                      "submitted without dyn_aligner_set_segment_scores(a, window > 0) or with calc_probabilities = 0";
   return DYN_ERR_INVALID_ARGUMENT;
 }
+int batch_check_borders(dyn_batch* b) {
+  if (b->bc_want && b->job == DynJob::AlignFull) return DYN_OK;
+  std::lock_guard<std::mutex> lk(b->a->err_mu);
+  b->a->last_error = "dyn_csv_sink_submit: the sink writes the border confidence (DYN_CSV_BORDER_CONFIDENCE) and this ticket was "
+                     "submitted without dyn_aligner_set_border_confidence(a, window > 0) or with calc_probabilities = 0";
+  return DYN_ERR_INVALID_ARGUMENT;
+}
 }  // namespace dyneng
 
 extern "C" {
+
+int dyn_batch_fetch_borders(dyn_batch* b, dyn_border_out* out) {
+  if (!b || !out || !out->border_probability || !out->border_window_probability) return DYN_ERR_INVALID_ARGUMENT;
+  dyn_aligner* a = b->a;
+  // a member of a merged launch: rows [g_seg0, g_seg0 + capacity) of the group's columns (dyn_batch_fetch)
+  const dyn_batch* src = (b->group && b->group->g) ? b->group->g : b;
+  const uint64_t seg0 = src == b ? 0 : b->g_seg0;
+  if (!b->aligned || !b->last_calc || !src->bc_ready) {
+    a->last_error = !b->aligned || !b->last_calc
+                        ? "dyn_batch_fetch_borders: the batch was not aligned with calc_probabilities = 1"
+                        : "dyn_batch_fetch_borders: the batch was submitted without dyn_aligner_set_border_confidence(a, window > 0)";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  if (out->capacity < b->capacity) {
+    a->last_error = "dyn_border_out.capacity is smaller than dyn_segment_capacity()";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  int rc = need_device(a);
+  if (rc != DYN_OK) return rc;
+  if (!b->capacity) return DYN_OK;
+  const double* e = src->d_bc.as<double>() + seg0;
+  HIP_TRY(a, copy_out(a, out->border_probability, e, b->capacity * 8));
+  HIP_TRY(a, copy_out(a, out->border_window_probability, e + src->capacity, b->capacity * 8));
+  return DYN_OK;
+}
 
 int dyn_batch_fetch_scores(dyn_batch* b, dyn_score_out* out) {
   if (!b || !out || !out->median_delta || !out->mad_delta || !out->homogeneity) return DYN_ERR_INVALID_ARGUMENT;

@@ -150,6 +150,7 @@ struct dyn_aligner {
   int rescale_iters = 0;      // dyn_aligner_set_rescale (0 .. 8): read by every batch / ticket at its submission
   bool kmer_summary = false;  // dyn_aligner_set_kmer_summary: read by every batch / ticket at its submission
   int segment_scores = 0;     // dyn_aligner_set_segment_scores (window, 0 = off): read by every batch / ticket at its submission
+  int border_confidence = 0;  // dyn_aligner_set_border_confidence (window, 0 = off): read by every batch / ticket at its submission
   dyneng::DevBuf d_ksum;      // [6 num_kmers + 4] u64: the per-k-mer accumulator and its totals (kmer_summary_kernels.hpp),
                               // allocated and zeroed by the first dyn_aligner_set_kmer_summary(a, 1)
   bool ntk = false;     // created with mode "resquiggle" / "ntk"
@@ -246,6 +247,9 @@ struct dyn_batch {
   dyneng::DevBuf d_sc;                         // [4][capacity] median_delta / mad_delta / homogeneity / scratch (segment_scores.hip)
   int sc_want = 0;                             // the handle's segment-score window when this batch / ticket was submitted
   bool sc_ready = false;                       // the last job computed the score columns into d_sc
+  dyneng::DevBuf d_bc;                         // [2][capacity] border_probability / border_window_probability (border_kernels.hpp)
+  int bc_want = 0;                             // the handle's border-confidence window when this batch / ticket was submitted
+  bool bc_ready = false;                       // the last job computed the border columns into d_bc
   // per-read rescaling (rescale.hip, dyn_aligner_set_rescale)
   dyneng::DevBuf d_sig0;                       // the preprocessed signal x0, kept while d_sig holds a rescaled one
   dyneng::DevBuf d_rs;                         // [n] dynk::RescaleState | [capacity] row means of the fit (scratch)

@@ -559,6 +559,16 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   q.e2 = m.log_e2;
   q.sp_tab = a->d_sptab.as<dynmath::SoftplusNode>();
   q.z_fail_status = z_fail;
+  // per-border posterior confidence: [border_probability | border_window_probability] x capacity, zeroed here (rows of reads
+  // that fail keep the zeros), written by the read queue / the wide-band kernel of the LAST pass behind every read
+  double* bc_cols = nullptr;
+  b->bc_ready = false;
+  if (calc && b->bc_want) {
+    HIP_TRY(a, b->d_bc.ensure(std::max<uint64_t>(16, b->capacity * 16)));
+    if (b->capacity) HIP_TRY(a, hipMemsetAsync(b->d_bc.p, 0, b->capacity * 16, a->stream));
+    bc_cols = b->d_bc.as<double>();
+    b->bc_ready = true;
+  }
   const dynk::QueueJob qjob = job == DynJob::Train ? (a->train_zcheck ? dynk::JOB_TRAIN_ZCHECK : dynk::JOB_TRAIN)
                               : !calc              ? dynk::JOB_Z
                               : lpe_separate       ? dynk::JOB_ALIGN
@@ -569,6 +579,11 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   for (int pass = 0; pass < n_pass; ++pass) {
     if (pass > 0 && b->n) HIP_TRY(a, hipMemcpyAsync(b->d_state.p, st, b->n * sizeof(ReadState), hipMemcpyHostToDevice, a->stream));
     dynk::launch_pool_init(pool, used_pages, (int)n_static, a->stream);
+    if (bc_cols && pass + 1 == n_pass) {
+      q.border_window = b->bc_want;
+      q.border_p = bc_cols;
+      q.border_window_p = bc_cols + b->capacity;
+    }
     if (pass == 0) HIP_TRY(a, hipEventRecord(ev[0], a->stream));
     dynk::launch_read_queue(qjob, n_strict != 0, q, a->n_cus, a->stream);
     if (pass + 1 == n_pass) HIP_TRY(a, hipEventRecord(ev[1], a->stream));
@@ -602,6 +617,9 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       wa.m1 = m.log_m1;
       wa.e2 = m.log_e2;
       wa.z_fail_status = z_fail;
+      wa.border_window = q.border_window;
+      wa.border_p = q.border_p;
+      wa.border_window_p = q.border_window_p;
       dynk::launch_wide_reads(job == DynJob::Train ? 2 : calc ? 1 : 0, wa, wide_groups, a->stream);
     }
     // between two passes: the fit of every read and its signal recomputed from x0. (The per-segment kernels run once, after

@@ -48,6 +48,7 @@
 #include <algorithm>
 
 #include "band_runs.hpp"
+#include "border_kernels.hpp"
 #include "dp_cell.hpp"
 #include "dp_math_strict.hpp"
 #include "segment_kernels.hpp"
@@ -1479,10 +1480,16 @@ __global__ void k_pool_init(PagePool pool, uint32_t first_free, uint32_t n_stati
 // guarded by s_waitcnt vmcnt(0) -- which drains the forward sweep's DMA ring every ~13 rows.
 // MIXED: the launch holds reads flagged READ_STRICT; such a read takes the sweeps instantiated with the bit-for-bit
 // arithmetic (dp_math_strict.hpp). The default launches (MIXED = false) do not contain that code at all.
-template <int JOB, bool MIXED>
+// JOBX: the job, plus JOB_BORDER for the launches that carry the border-confidence phase (border_kernels.hpp) behind every
+// read. The phase is a bit of the job number and not a template parameter of its own, so that the instantiations without
+// it keep the names (and the code) they have always had.
+template <int JOBX, bool MIXED>
 __global__ DYN_ONE_WAVE_PER_SIMD void k_read_queue(const QueueArgs q, const ReadDesc* __restrict__ descs,
                                                    const double* __restrict__ sig, const Emis* __restrict__ par,
                                                    const SoftplusNode* __restrict__ sp_tab) {
+  constexpr int JOB = JOBX & ~JOB_BORDER;
+  constexpr bool BORDER = (JOBX & JOB_BORDER) != 0;
+  static_assert(!BORDER || JOB == JOB_ALIGN || JOB == JOB_ALIGN_INPLACE, "borders exist for align(calc=true) only");
   constexpr bool LATTICE = JOB != JOB_Z;
   // + 2^(i/128) as plain doubles (exp_table128_vec) + glibc's table of the strict exp (dp_math_strict.hpp)
   constexpr int TAB_NODES = SP_NODES + dynmath::EXP128_NODES + dynmath::STRICT_EXP_WORDS / 2;
@@ -1543,6 +1550,25 @@ __global__ DYN_ONE_WAVE_PER_SIMD void k_read_queue(const QueueArgs q, const Read
     const uint64_t t1 = __builtin_amdgcn_s_memtime();
     ws.cyc_w += t1 - t0;
     run_read<JOB, MIXED>(rd, w, q.pool, ReadIO{q.st, q.tb, q.tr, q.m1, q.e2, q.z_fail_status}, sig, par, s_tab, ring_base, sb, ws, t1);
+    if constexpr (BORDER) {
+      // the read's lattice is still in this wave's pages; its state and segrow were written by lanes of this wave
+      const uint64_t t5 = __builtin_amdgcn_s_memtime();
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      const ReadState* rs = q.st + rd.read;
+      if (__builtin_amdgcn_readfirstlane((int)ctl_load(reinterpret_cast<const uint32_t*>(&rs->status))) == 0) {
+        const BorderBand band{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio};
+        auto row = [&w](int t) { return pool_row(w, t); };
+        if constexpr (JOB == JOB_ALIGN) {
+          const double Zb = __hip_atomic_load(&rs->Zb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const BorderCellSeparate<decltype(row)> cell{band, q.pool.lpe, q.pool.ws, sig + rd.sig_off, par + rd.par_off, Zb, q.m1, row};
+          border_confidence_read(cell, rd, q.tb.segrow, q.border_p, q.border_window_p, q.border_window, w.lane, 64);
+        } else {
+          const BorderCellInplace<decltype(row)> cell{band, reinterpret_cast<const float*>(q.pool.ws), row};
+          border_confidence_read(cell, rd, q.tb.segrow, q.border_p, q.border_window_p, q.border_window, w.lane, 64);
+        }
+      }
+      ws.cyc_t += __builtin_amdgcn_s_memtime() - t5;
+    }
   }
   // leaving: while a claimed read still lacks its pages, somebody may be waiting for these
   if (LATTICE && have && (uint32_t)__builtin_amdgcn_readfirstlane((int)ctl_load(&ctl[CTL_PROVISIONED])) < (uint32_t)q.n_reads)
@@ -1928,6 +1954,18 @@ void launch_read_queue(QueueJob job, bool with_strict, const QueueArgs& q, int n
   if (q.n_reads <= 0) return;
   const int groups = std::min((q.n_reads + DYN_WAVES_PER_GROUP - 1) / DYN_WAVES_PER_GROUP, std::max(1, n_cus));
   const dim3 grid(groups), block(64 * DYN_WAVES_PER_GROUP);
+  if (q.border_window > 0 && (job == JOB_ALIGN || job == JOB_ALIGN_INPLACE)) {  // dyn_aligner_set_border_confidence
+#define DYN_BORDER_LAUNCH(J, M) hipLaunchKernelGGL((k_read_queue<J | JOB_BORDER, M>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab)
+    if (job == JOB_ALIGN) {
+      if (with_strict) DYN_BORDER_LAUNCH(JOB_ALIGN, true);
+      else DYN_BORDER_LAUNCH(JOB_ALIGN, false);
+    } else {
+      if (with_strict) DYN_BORDER_LAUNCH(JOB_ALIGN_INPLACE, true);
+      else DYN_BORDER_LAUNCH(JOB_ALIGN_INPLACE, false);
+    }
+#undef DYN_BORDER_LAUNCH
+    return;
+  }
   if (with_strict) {  // only jobs with integer outputs have strict reads
     if (job == JOB_ALIGN) hipLaunchKernelGGL((k_read_queue<JOB_ALIGN, true>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab);
     else hipLaunchKernelGGL((k_read_queue<JOB_ALIGN_INPLACE, true>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab);

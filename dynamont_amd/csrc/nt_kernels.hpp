@@ -103,6 +103,8 @@ constexpr int QUEUE_STATS = 8;        // first stats word (as uint32 index)
 constexpr int QUEUE_N_STATS = 10;
 
 enum QueueJob { JOB_Z = 0, JOB_ALIGN = 1, JOB_ALIGN_INPLACE = 2, JOB_TRAIN = 3, JOB_TRAIN_ZCHECK = 4 };
+constexpr int JOB_BORDER = 8;  // a bit on top of JOB_ALIGN / JOB_ALIGN_INPLACE in k_read_queue's template argument: the launch
+                               // carries the border-confidence phase (border_kernels.hpp)
 
 struct QueueArgs {
   const ReadDesc* descs;   // in processing order
@@ -117,6 +119,11 @@ struct QueueArgs {
   double m1, e2;          // log transition probabilities (NT_aligner_api.cpp:84-86)
   const dynmath::SoftplusNode* sp_tab;
   int z_fail_status;
+  // per-border posterior confidence (dyn_aligner_set_border_confidence): columns indexed like the output rows, zeroed by the
+  // caller; border_window == 0: not asked for (and the launch is the one it has always been)
+  int border_window = 0;             // W, 1 .. 256
+  double* border_p = nullptr;
+  double* border_window_p = nullptr;
 };
 
 // ---- the RESIDENT read queue (round 5) ---------------------------------------------------------------------------
@@ -201,6 +208,9 @@ struct WideArgs {
   const uint64_t* exp_tab; // dynmath::strict_exp_table on the device
   double m1, e2;
   int z_fail_status;
+  int border_window = 0;   // as QueueArgs: W, and the two columns of dyn_aligner_set_border_confidence
+  double* border_p = nullptr;
+  double* border_window_p = nullptr;
 };
 uint64_t wide_arena_bytes(uint64_t T, uint64_t bw, bool calc);
 // job: 0 = Z only, 1 = align(calc_probabilities = true) up to the per-row path arrays (launch_segments follows), 2 = train

@@ -20,6 +20,7 @@
 // Per-row outputs (pp, pathn, segrow) are those of nt_kernels.hip's traceback: k_median / k_final follow unchanged.
 #include "nt_kernels.hpp"
 
+#include "border_kernels.hpp"
 #include "dp_math_strict.hpp"
 
 namespace dynk {
@@ -277,6 +278,35 @@ __global__ __launch_bounds__(WIDE_THREADS) void k_wide_reads(const WideArgs a) {
   }
 }
 
+// k_wide_reads<true, false> with the border-confidence phase (border_kernels.hpp) behind every read, as a kernel of its own:
+// the launches without the phase are the ones they have always been. The read's lattice is still in the arena when
+// wide_read returns (its closing barrier has made the state and segrow that thread 0 wrote visible to the workgroup).
+__global__ __launch_bounds__(WIDE_THREADS) void k_wide_reads_border(const WideArgs a) {
+  __shared__ __attribute__((aligned(16))) double s_row[4][WIDE_MAX_B];
+  __shared__ uint64_t s_exp[dynmath::STRICT_EXP_WORDS];
+  __shared__ int s_next;
+  for (int i = threadIdx.x; i < dynmath::STRICT_EXP_WORDS; i += WIDE_THREADS) s_exp[i] = a.exp_tab[i];
+  char* arena = a.arena + (size_t)blockIdx.x * a.arena_bytes;
+  for (;;) {
+    __syncthreads();
+    if (threadIdx.x == 0) s_next = (int)atomicAdd(a.head, 1u);
+    __syncthreads();
+    const int k = s_next;
+    if (k >= a.n_reads) break;
+    const ReadDesc rd = a.descs[k];
+    const size_t cells = (size_t)rd.T * (size_t)(2 * rd.bw + 3);
+    double* bE = reinterpret_cast<double*>(arena);
+    double* bM = bE + cells;
+    float* lp = reinterpret_cast<float*>(bM + cells);
+    uint8_t* bit = reinterpret_cast<uint8_t*>(lp + 2 * cells);
+    wide_read<true, false>(rd, a, bE, bM, lp, bit, s_row, s_exp);
+    if (__hip_atomic_load(&a.st[rd.read].status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) {
+      const BorderCellWide cell{BorderBand{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio}, lp};
+      border_confidence_read(cell, rd, a.tb.segrow, a.border_p, a.border_window_p, a.border_window, (int)threadIdx.x, WIDE_THREADS);
+    }
+  }
+}
+
 uint64_t wide_arena_bytes(uint64_t T, uint64_t bw, bool calc) {
   const uint64_t cells = T * (2 * bw + 3);
   return (cells * (16 + (calc ? 9 : 0)) + 255) & ~255ull;  // bE, bM doubles; (float LPM, float LPE); one byte per decision
@@ -286,6 +316,7 @@ void launch_wide_reads(int job, const WideArgs& a, int n_groups, hipStream_t s) 
   if (a.n_reads <= 0 || n_groups <= 0) return;
   (void)hipMemsetAsync(a.head, 0, 4, s);
   if (job == 2) hipLaunchKernelGGL((k_wide_reads<false, true>), dim3(n_groups), dim3(WIDE_THREADS), 0, s, a);
+  else if (job == 1 && a.border_window > 0) hipLaunchKernelGGL(k_wide_reads_border, dim3(n_groups), dim3(WIDE_THREADS), 0, s, a);
   else if (job == 1) hipLaunchKernelGGL((k_wide_reads<true, false>), dim3(n_groups), dim3(WIDE_THREADS), 0, s, a);
   else hipLaunchKernelGGL((k_wide_reads<false, false>), dim3(n_groups), dim3(WIDE_THREADS), 0, s, a);
 }

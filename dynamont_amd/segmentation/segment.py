@@ -46,6 +46,8 @@ CSV_HEADER = b"readid,signalid,start,end,basepos,base,motif,state,posterior_prob
 CSV_HEADER_EVENTS = CSV_HEADER[:-1] + b",level_mean,level_stdv,level_median\n"
 # --segment-scores W: ... and, after those, the per-border segment scores (Aligner.set_segment_scores)
 CSV_COLUMNS_SCORES = b",median_delta,mad_delta,homogeneity"
+# --border-confidence W: ... and, after those, the per-border posterior confidence (Aligner.set_border_confidence)
+CSV_COLUMNS_BORDERS = b",border_probability,border_window_probability"
 POLYA = "AAAAAAAAA"
 
 MAX_SAMPLES_IN_FLIGHT = 512 << 20  # ~1 GB of pinned int16 staging + ~4 GB of float64 on the device, whatever --depth says
@@ -95,6 +97,11 @@ def parse(argv=None) -> Namespace:
                         "after the segment's first sample, and the MAD of the segment with 10 %% trimmed from either end (nan "
                         "below 10 samples; the deltas are nan in a read's first row) -- the segmentation scores of the reference's "
                         "compareTools.py, on the normalised signal, computed on the GPU")
+    p.add_argument("--border-confidence", type=int, default=0, choices=range(0, 257), metavar="W",
+                   help="add border_probability,border_window_probability to every row (after the level and score columns, if "
+                        "any): the posterior probability, over all segmentations, that the segment starts exactly at the called "
+                        "sample, and that it starts within W samples (1 .. 256, default 0 = off) of it -- computed on the GPU from "
+                        "the forward-backward lattice of the alignment")
     p.add_argument("--rescale-iters", type=int, default=0, choices=range(0, 9), metavar="N",
                    help="align every read N + 1 times (0 .. 8, default 0 = off), refitting the read's signal shift and scale "
                         "on the GPU between the passes: a least-squares fit of the segment levels on the model levels. "
@@ -525,6 +532,8 @@ class _NativePipeline:
         flags = N.DYN_CSV_EVENT_STATS if aligner._event_stats else 0  # the rows carry the signal levels (--event-stats)
         if aligner._segment_scores:
             flags |= N.DYN_CSV_SEGMENT_SCORES  # ... and the segment scores (--segment-scores)
+        if aligner._border_confidence:
+            flags |= N.DYN_CSV_BORDER_CONFIDENCE  # ... and the border confidence (--border-confidence)
         rc = self.L.dyn_csv_sink_open_ex(outfile.encode(), errfile.encode(), int(os.environ.get("DYN_SINK_LEVEL", level)), int(threads),
                                          int(first), int(last), flags, C.byref(h), err, 1024)
         if rc != N.DYN_OK:
@@ -718,7 +727,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             minq: float = 0, device: int = 0, batch_reads: int = 1024, mem_budget_gib: float = 0.0,
             host_preprocess: bool = False, depth: int = 12, strict_ties: str = "ties", host_threads: int = 0,
             zstd_level: int = 3, event_stats: bool = False, rescale_iters: int = 0, kmer_summary: str = "",
-            segment_scores: int = 0) -> None:
+            segment_scores: int = 0, border_confidence: int = 0) -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
@@ -743,6 +752,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
         header = CSV_HEADER_EVENTS if event_stats else CSV_HEADER
         if segment_scores:
             header = header[:-1] + CSV_COLUMNS_SCORES + b"\n"
+        if border_confidence:
+            header = header[:-1] + CSV_COLUMNS_BORDERS + b"\n"
         writer = threading.Thread(target=listener, args=(q, outfile, header), daemon=True)
         writer.start()
     sink = None if native else (q if comm is None else _Collector())
@@ -800,6 +811,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                 aligner.set_rescale(rescale_iters)
             if segment_scores:
                 aligner.set_segment_scores(segment_scores)
+            if border_confidence:
+                aligner.set_border_confidence(border_confidence)
             if kmer_summary:
                 aligner.set_kmer_summary(True)
             if native:
@@ -949,7 +962,8 @@ def main(argv=None) -> None:
             device=args.device, batch_reads=args.batch_reads, mem_budget_gib=args.mem_budget,
             host_preprocess=args.host_preprocess, depth=args.depth, strict_ties=args.strict_ties, host_threads=args.host_threads,
             zstd_level=args.zstd_level, event_stats=args.event_stats, rescale_iters=args.rescale_iters,
-            kmer_summary=args.kmer_summary, segment_scores=args.segment_scores)
+            kmer_summary=args.kmer_summary, segment_scores=args.segment_scores,
+            border_confidence=args.border_confidence)
     _stamp("segment() returned (aligner closed)")
     if argv is None and not int(__import__("os").environ.get("WORLD_SIZE", "1") or 1) > 1:
         # Invoked as the command (console script / python -m), single process, everything written and closed: leave without

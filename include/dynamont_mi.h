@@ -175,6 +175,23 @@ typedef struct dyn_score_out {
   uint64_t capacity;
 } dyn_score_out;
 
+/* (added within ABI 10: a caller that must know looks the symbol up) Per-border posterior confidence of an
+ * align(calc_probabilities = 1) job whose handle had dyn_aligner_set_border_confidence(a, W) with W > 0 when the batch was
+ * submitted: caller-allocated columns indexed like the segment arrays of dyn_align_out; rows of failed reads are 0. For
+ * output row j of an OK read with T - 1 samples: n = j + 1 is its lattice column, r = signal_positions[j] + 1 the row of its
+ * M cell, LPM(t, n) = (fM(t, n) + bM(t, n)) - Z the log-posterior of "segment n starts in row t" (NT_aligner_api.cpp:213-224),
+ * -inf for every cell outside the reference's band window of row t (computeBounds, :90-108) and in row 0.
+ *   border_probability[j]         exp(LPM(r, n)): the posterior mass on the called border itself
+ *   border_window_probability[j]  sum over t = max(1, r - W) .. min(T - 1, r + W) of exp(LPM(t, n)): the mass within W samples
+ *                                 of it; fp64, ascending t, one IEEE add per term, not clamped (may exceed 1 by rounding)
+ * Over all rows t the masses of one column sum to 1. With dyn_aligner_set_rescale on, the values are the last pass's. */
+#define DYN_BORDER_CONFIDENCE_MAX_WINDOW 256
+typedef struct dyn_border_out {
+  double* border_probability;         /* [capacity] */
+  double* border_window_probability;  /* [capacity] */
+  uint64_t capacity;
+} dyn_border_out;
+
 /* (ABI 10) Per-read signal rescaling of an align(calc_probabilities = 1) job whose handle had dyn_aligner_set_rescale(a, K)
  * with K > 0 when the batch was submitted. Read r is aligned K + 1 times. x0 = its preprocessed signal (what
  * dyn_batch_signals returns with the switch off); A_0 = 0.0, B_0 = 1.0; pass k = 0 .. K aligns x_k, x_0 = x0 and
@@ -386,6 +403,13 @@ int dyn_aligner_set_rescale(dyn_aligner* a, int iters);
  * DYN_SEGMENT_SCORES_MAX_WINDOW, default 0 = off: nothing is allocated, launched or changed. DYN_ERR_INVALID_ARGUMENT +
  * message outside that range. Tickets merge into one launch only with tickets of the same window. */
 int dyn_aligner_set_segment_scores(dyn_aligner* a, int window);
+/* (added within ABI 10) align(calc_probabilities = 1) also computes the per-border posterior confidence (dyn_border_out)
+ * with a window of `window` rows, on the device behind every read's traceback while its lattice is still in place, for every
+ * batch or ticket SUBMITTED while window > 0; 2 x 8 bytes of device memory per segment row for those batches only.
+ * window = 0 .. DYN_BORDER_CONFIDENCE_MAX_WINDOW, default 0 = off: nothing is allocated or changed, and every launch is the
+ * one it would have been. DYN_ERR_INVALID_ARGUMENT + message outside that range. A ticket submitted with window > 0 takes
+ * one launch per batch (not the resident session) and merges only with tickets of the same window. */
+int dyn_aligner_set_border_confidence(dyn_aligner* a, int window);
 /* (added within ABI 10: a caller that must know looks the symbol up) Per-k-mer level summary of a run. While it is on, every output row (segment) of every read with status 0 of an
  * align(calc_probabilities = 1) batch or ticket SUBMITTED on this handle is added, on the device behind the per-segment
  * kernels, to its k-mer's entry of an accumulator that lives on the handle: six u64 per k-mer code (48 bytes x num_kmers of
@@ -478,6 +502,18 @@ int dyn_format_csv_scores(const dyn_aligner* a, uint64_t n_reads, const dyn_alig
                           const int64_t* last_index, int threads, char* out, uint64_t out_cap,
                           uint64_t* row_begin, uint64_t* row_end);
 
+/* (added within ABI 10) The same with the border confidence of dyn_batch_fetch_borders as well: after the score columns (if
+ * sc is given) every row gets ",{border_probability:.6f},{border_window_probability:.6f}". ev, sc and bd may each be NULL;
+ * bd == NULL: dyn_format_csv_scores / dyn_format_csv_bound_scores, byte for byte. */
+uint64_t dyn_format_csv_bound_borders(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                                      const dyn_score_out* sc, const dyn_border_out* bd, const char* const* readids,
+                                      const char* const* signalids);
+int dyn_format_csv_borders(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                           const dyn_score_out* sc, const dyn_border_out* bd, const char* seqs, const uint64_t* seq_offsets,
+                           const char* const* readids, const char* const* signalids, const int64_t* sig_offsets,
+                           const int64_t* last_index, int threads, char* out, uint64_t out_cap,
+                           uint64_t* row_begin, uint64_t* row_end);
+
 /* Closes the gaps between the per-read ranges dyn_format_csv produced: all rows become one contiguous run at the
  * front of `out`, in read order; row_begin/row_end are updated. Returns the total byte count. */
 uint64_t dyn_csv_compact(char* out, uint64_t n_reads, uint64_t* row_begin, uint64_t* row_end);
@@ -520,6 +556,12 @@ int dyn_csv_sink_open_part(const char* csv_zst_path, const char* errors_path, in
  * wait, and a submit whose ticket was submitted with dyn_aligner_set_segment_scores off fails with
  * DYN_ERR_INVALID_ARGUMENT. */
 #define DYN_CSV_SEGMENT_SCORES 0x2u
+/* (added within ABI 10) DYN_CSV_BORDER_CONFIDENCE: the header gains ",border_probability,border_window_probability" (after
+ * the level and score columns, if any), every row the two columns (dyn_format_csv_borders); the sink fetches each ticket's
+ * columns after its wait, and a submit whose ticket was submitted with dyn_aligner_set_border_confidence off fails with
+ * DYN_ERR_INVALID_ARGUMENT. (0x8, not 0x4: bit 2 stays unassigned, and a sink opened with it is
+ * refused as before.) */
+#define DYN_CSV_BORDER_CONFIDENCE 0x8u
 int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int level, int threads, int first, int last,
                          uint32_t flags, dyn_csv_sink** out, char* err, uint64_t errcap);
 #define DYN_ZSTD_FRAME_END "\x01\x00\x00" /* an empty last block (raw, size 0): 3 bytes; the frames carry no checksum */
@@ -639,6 +681,10 @@ int dyn_batch_fetch_events(dyn_batch* b, dyn_event_out* out);
  * own non-blocking stream. DYN_ERR_INVALID_ARGUMENT (with a message) when the batch was submitted with
  * dyn_aligner_set_segment_scores off, or aligned with calc_probabilities = 0, or out->capacity is too small. */
 int dyn_batch_fetch_scores(dyn_batch* b, dyn_score_out* out);
+/* (added within ABI 10) The border confidence of the batch's last align(calc_probabilities = 1) job, copied on the handle's
+ * own non-blocking stream. DYN_ERR_INVALID_ARGUMENT (with a message) when the batch was submitted with
+ * dyn_aligner_set_border_confidence off, or aligned with calc_probabilities = 0, or out->capacity is too small. */
+int dyn_batch_fetch_borders(dyn_batch* b, dyn_border_out* out);
 /* (ABI 10) Copy the per-read transforms of the last dyn_batch_align (or of a completed ticket, merged launch or not) into
  * `out` (n >= the batch's read count). DYN_ERR_INVALID_ARGUMENT + message for a batch submitted with
  * dyn_aligner_set_rescale(a, 0), or aligned with calc_probabilities = 0. */
