@@ -112,6 +112,24 @@ class AlignBatchResult:
         self.median_delta = self.mad_delta = self.homogeneity = None
         # per-border posterior confidence (Aligner.set_border_confidence): float64 [cap] like the segment columns, None when off
         self.border_probability = self.border_window_probability = None
+        # band-margin diagnostics (Aligner.set_band_margin): uint32 [n] each, None when off; band_used (uint32 [n]): the band
+        # every read's rows come from, only with Aligner.set_band_retry
+        self.band_margin_low = self.band_margin_high = self.band_edge_rows = None
+        self.band_used = None
+
+    def _fetch_band_margin(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
+        """dyn_batch_fetch_band_margin into this object's per-read columns (allocated on first use), or drop them."""
+        self.band_used = None
+        if not wanted:
+            self.band_margin_low = self.band_margin_high = self.band_edge_rows = None
+            return
+        if self.band_margin_low is None:
+            self.band_margin_low, self.band_margin_high, self.band_edge_rows = (np.zeros(self.n, dtype=np.uint32) for _ in range(3))
+        out = N.DynBandMarginOut(_ptr(self.band_margin_low, N.c_u32_p), _ptr(self.band_margin_high, N.c_u32_p),
+                                 _ptr(self.band_edge_rows, N.c_u32_p), self.n)
+        rc = L.dyn_batch_fetch_band_margin(handle, C.byref(out))
+        if rc != N.DYN_OK:
+            _raise(rc, aligner.last_error())
 
     def _fetch_borders(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
         """dyn_batch_fetch_borders into this object's border columns (allocated on first use), or drop them."""
@@ -201,6 +219,10 @@ class AlignBatchResult:
             d["rescale_shift"] = float(self.rescale_shift[i])
             d["rescale_scale"] = float(self.rescale_scale[i])
             d["rescale_iters"] = int(self.rescale_iters[i])
+        if self.band_margin_low is not None:  # only when requested (Aligner.set_band_margin)
+            d["band_margin_low"] = int(self.band_margin_low[i])
+            d["band_margin_high"] = int(self.band_margin_high[i])
+            d["band_edge_rows"] = int(self.band_edge_rows[i])
         return d
 
 
@@ -367,6 +389,7 @@ class Batch:
         self._rescale = bool(calc_probabilities) and self._al._rescale > 0
         self._scores = bool(calc_probabilities) and self._al._segment_scores > 0
         self._borders = bool(calc_probabilities) and self._al._border_confidence > 0
+        self._margins = bool(calc_probabilities) and self._al._band_margin
         rc = self._L.dyn_batch_align(self._h, int(bool(calc_probabilities)))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
@@ -389,6 +412,7 @@ class Batch:
         out._fetch_rescale(self._L, self._h, self._al, getattr(self, "_rescale", False))
         out._fetch_scores(self._L, self._h, self._al, getattr(self, "_scores", False))
         out._fetch_borders(self._L, self._h, self._al, getattr(self, "_borders", False))
+        out._fetch_band_margin(self._L, self._h, self._al, getattr(self, "_margins", False))
         return out
 
     def fetch_events(self, out: N.DynEventOut) -> None:
@@ -406,6 +430,12 @@ class Batch:
     def fetch_borders(self, out: N.DynBorderOut) -> None:
         """dyn_batch_fetch_borders into caller-owned columns (raises ValueError for a batch that did not ask)."""
         rc = self._L.dyn_batch_fetch_borders(self._h, C.byref(out))
+        if rc != N.DYN_OK:
+            _raise(rc, self._al.last_error())
+
+    def fetch_band_margin(self, out: N.DynBandMarginOut) -> None:
+        """dyn_batch_fetch_band_margin into caller-owned arrays (raises ValueError for a batch that did not ask)."""
+        rc = self._L.dyn_batch_fetch_band_margin(self._h, C.byref(out))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
 
@@ -461,7 +491,7 @@ class AsyncBatch:
     (the library reads them until the batch is complete)."""
 
     def __init__(self, aligner: "Aligner", handle, result, keep, levels: bool = False, rescale: bool = False,
-                 scores: bool = False, borders: bool = False):
+                 scores: bool = False, borders: bool = False, margins: bool = False):
         self._al = aligner
         self._L = N.lib()
         self._h = handle
@@ -472,6 +502,7 @@ class AsyncBatch:
         self._rescale = rescale  # ... with the rescale switch on
         self._scores = scores  # ... with the segment-scores switch on
         self._borders = borders  # ... with the border-confidence switch on
+        self._margins = margins  # ... with the band-margin switch on (tickets report margins; they are never retried)
 
     def wait(self):
         if not self._waited:
@@ -484,12 +515,14 @@ class AsyncBatch:
                 self.result._fetch_rescale(self._L, self._h, self._al, self._rescale)
                 self.result._fetch_scores(self._L, self._h, self._al, self._scores)
                 self.result._fetch_borders(self._L, self._h, self._al, self._borders)
+                self.result._fetch_band_margin(self._L, self._h, self._al, self._margins)
         return self.result
 
     fetch_events = Batch.fetch_events
     fetch_rescale = Batch.fetch_rescale
     fetch_scores = Batch.fetch_scores
     fetch_borders = Batch.fetch_borders
+    fetch_band_margin = Batch.fetch_band_margin
 
     def timing(self) -> dict:
         self.wait()
@@ -582,6 +615,11 @@ class Aligner:
     _rescale = 0  # set_rescale
     _segment_scores = 0  # set_segment_scores
     _border_confidence = 0  # set_border_confidence
+    _band_margin = False  # set_band_margin
+    _band_retry = None  # set_band_retry: (min_margin, max_band, factor)
+    _kmer_summary = False  # set_kmer_summary
+    _strict = 1  # set_strict
+    _model_override = None  # set_model: (mean, stdev)
 
     def __init__(self, model_file: str, pore, mode: str = "basic", threads: int = 1, band: int = 400,
                  device=None):
@@ -603,6 +641,9 @@ class Aligner:
         if rc != N.DYN_OK:
             _raise(rc, err.value.decode())
         self._h = h
+        self._ctor = (str(model_file), int(pore), str(mode), int(threads), device)  # what a retry handle is created with
+        self.band = int(band)
+        self._retry_handles = {}  # band -> Aligner (set_band_retry)
         info = N.DynInfo()
         self._L.dyn_aligner_info(h, C.byref(info))
         self.info = info
@@ -613,6 +654,9 @@ class Aligner:
         self._model = None
 
     def close(self):
+        for al in getattr(self, "_retry_handles", {}).values():
+            al.close()
+        self._retry_handles = {}
         if getattr(self, "_h", None):
             self._L.dyn_aligner_destroy(self._h)
             self._h = None
@@ -637,6 +681,7 @@ class Aligner:
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
         self._model = None  # model_table() reads it back
+        self._model_override = (np.array(mean, dtype=np.float64), np.array(stdev, dtype=np.float64))
 
     def set_strict(self, mode) -> None:
         """dyn_aligner_set_strict: 0/"off" plain arithmetic; 1/"ties" (the default of a new handle) reads that carry a
@@ -646,6 +691,7 @@ class Aligner:
         rc = self._L.dyn_aligner_set_strict(self._h, m)
         if rc != N.DYN_OK:
             raise ValueError(self.last_error() or "strict mode must be 0 (off), 1 (ties) or 2 (all)")
+        self._strict = m
 
     def set_session_mode(self, enabled: bool, reserved_cus: int = 0) -> None:
         """dyn_aligner_set_session_mode: the resident read queue on / off, and compute units kept free of it (for RCCL's
@@ -715,9 +761,97 @@ class Aligner:
         """dyn_aligner_set_kmer_summary: while on, every segment of every ok read of the align(calc_probabilities=True) jobs
         submitted on this aligner is added to its k-mer's entry of a per-k-mer summary kept on the GPU as exact integers
         (INTEGRATION.md section 3); ``kmer_summary()`` fetches it, ``reset_kmer_summary()`` zeroes it."""
+        if on and self._band_retry:
+            raise ValueError("set_kmer_summary with set_band_retry: the retried reads would be summed twice")
         rc = self._L.dyn_aligner_set_kmer_summary(self._h, 1 if on else 0)
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
+        self._kmer_summary = bool(on)
+
+    def set_band_margin(self, on: bool) -> None:
+        """dyn_aligner_set_band_margin: align(calc_probabilities=True) jobs submitted while on also report, per read, how
+        close the called path came to a real edge of its band: ``AlignBatchResult.band_margin_low``
+        / ``.band_margin_high`` (uint32 [n], ``DYN_BAND_MARGIN_NONE`` = 0xFFFFFFFF where that edge was never a real one) and
+        ``.band_edge_rows`` (path rows on a real edge); ``read(i)`` adds the three keys. A margin of 0 says that the band may
+        have decided the alignment."""
+        rc = self._L.dyn_aligner_set_band_margin(self._h, 1 if on else 0)
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        self._band_margin = bool(on)
+
+    def set_band_retry(self, min_margin: int, max_band: int = 4093, factor: int = 2) -> None:
+        """The synchronous ``align_batch`` aligns every ok read whose ``min(band_margin_low, band_margin_high)`` is below
+        ``min_margin`` again at the band ``min(band * factor, max_band)``, on a second handle with this one's model, pore,
+        device and settings, and repeats until the margin passes or ``max_band`` is reached. A read's row count does not
+        depend on the band: the new rows, Z, margins and every opt-in column that is on replace the read's entries of the
+        first result in place, and ``band_used`` (uint32 [n]) records the band each read's rows come from. A read whose
+        retry fails keeps its last good result. Implies ``set_band_margin(True)``; ``min_margin = 0`` turns the retry off
+        (the margins stay on). ``align_async`` tickets report margins but are never retried. Not together with
+        ``set_kmer_summary(True)``: the retried reads would be summed twice (ValueError)."""
+        min_margin, max_band, factor = int(min_margin), int(max_band), int(factor)
+        if min_margin < 0 or factor < 2 or max_band < 1:
+            raise ValueError("set_band_retry: min_margin >= 0, factor >= 2 and max_band >= 1 are required")
+        if min_margin == 0:
+            self._band_retry = None
+            return
+        if self._kmer_summary:
+            raise ValueError("set_band_retry with set_kmer_summary: the retried reads would be summed twice")
+        self.set_band_margin(True)
+        self._band_retry = (min_margin, max_band, factor)
+
+    def _retry_handle(self, band: int) -> "Aligner":
+        """the handle the retried reads run on at ``band``, with this handle's settings as they stand now"""
+        al = self._retry_handles.get(band)
+        if al is None:
+            model_file, pore, mode, threads, device = self._ctor
+            if device is None or device == "host":
+                device = int(self.info.device)
+            al = self._retry_handles[band] = Aligner(model_file, pore, mode=mode, threads=threads, band=band, device=device)
+        if self._model_override is not None:
+            al.set_model(*self._model_override)
+        al.set_strict(self._strict)
+        al.set_event_stats(self._event_stats)
+        al.set_rescale(self._rescale)
+        al.set_segment_scores(self._segment_scores)
+        al.set_border_confidence(self._border_confidence)
+        al.set_band_margin(True)
+        return al
+
+    # per-row and per-read columns a retried read's entries are spliced into (those that are on)
+    _ROW_COLUMNS = ("sequence_positions", "signal_positions", "probabilities", "states", "level_mean", "level_stdv", "level_median",
+                    "median_delta", "mad_delta", "homogeneity", "border_probability", "border_window_probability")
+    _READ_COLUMNS = ("Z", "rescale_shift", "rescale_scale", "rescale_iters", "band_margin_low", "band_margin_high", "band_edge_rows")
+
+    def _retry_bands(self, res: AlignBatchResult, signals: Sequence, sequences: Sequence[str]) -> None:
+        min_margin, max_band, factor = self._band_retry
+        band = self.band
+        res.band_used = np.full(res.n, band, dtype=np.uint32)
+
+        def flagged(r, idx):
+            m = np.minimum(r.band_margin_low[idx], r.band_margin_high[idx])
+            return (r.status[idx] == 0) & (m < min_margin)
+
+        every = np.arange(res.n)
+        pending = every[flagged(res, every)]
+        while pending.size and band < max_band:
+            band = min(band * factor, max_band)
+            r2 = self._retry_handle(band).align_batch([signals[i] for i in pending], [sequences[i] for i in pending], True)
+            for k, i in enumerate(pending):
+                ns = int(res.n_segments[i])
+                if r2.status[k] != 0 or int(r2.n_segments[k]) != ns:
+                    continue  # the read keeps its last good result
+                a, a2 = int(res.seg_offsets[i]), int(r2.seg_offsets[k])
+                for name in self._ROW_COLUMNS:
+                    col = getattr(res, name)
+                    if col is not None:
+                        col[a:a + ns] = getattr(r2, name)[a2:a2 + ns]
+                for name in self._READ_COLUMNS:
+                    col = getattr(res, name)
+                    if col is not None:
+                        col[i] = getattr(r2, name)[k]
+                res.band_used[i] = band
+            sub = np.arange(pending.size)
+            pending = pending[(r2.status[sub] == 0) & flagged(r2, sub)]
 
     def reset_kmer_summary(self) -> None:
         rc = self._L.dyn_aligner_kmer_summary_reset(self._h)
@@ -825,7 +959,8 @@ class Aligner:
         return AsyncBatch(self, h, out, (sig, sig_off, seqs, seq_off), levels=self._event_stats and bool(calc_probabilities),
                           rescale=self._rescale > 0 and bool(calc_probabilities),
                           scores=self._segment_scores > 0 and bool(calc_probabilities),
-                          borders=self._border_confidence > 0 and bool(calc_probabilities))
+                          borders=self._border_confidence > 0 and bool(calc_probabilities),
+                          margins=self._band_margin and bool(calc_probabilities))
 
     def _raw_args(self, raw, shift, scale, calibration=None):
         scattered = isinstance(raw, (list, tuple))
@@ -878,7 +1013,8 @@ class Aligner:
                           levels=self._event_stats and bool(calc_probabilities),
                           rescale=self._rescale > 0 and bool(calc_probabilities),
                           scores=self._segment_scores > 0 and bool(calc_probabilities),
-                          borders=self._border_confidence > 0 and bool(calc_probabilities))
+                          borders=self._border_confidence > 0 and bool(calc_probabilities),
+                          margins=self._band_margin and bool(calc_probabilities))
 
     def align_vbz_async(self, chunks, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 3,
                         n_sigmas: float = 3.0, f32: bool = False, calc_probabilities: bool = True,
@@ -915,7 +1051,8 @@ class Aligner:
                           levels=self._event_stats and bool(calc_probabilities),
                           rescale=self._rescale > 0 and bool(calc_probabilities),
                           scores=self._segment_scores > 0 and bool(calc_probabilities),
-                          borders=self._border_confidence > 0 and bool(calc_probabilities))
+                          borders=self._border_confidence > 0 and bool(calc_probabilities),
+                          margins=self._band_margin and bool(calc_probabilities))
 
     def train_raw_async(self, raw, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 7,
                         n_sigmas: float = 5.0, f32: bool = True, pooled: bool = False,
@@ -963,7 +1100,10 @@ class Aligner:
     def align_batch(self, signals: Sequence, sequences: Sequence[str], calc_probabilities: bool = True) -> AlignBatchResult:
         with self.batch(signals, sequences) as b:
             b.align(calc_probabilities)
-            return b.fetch()
+            res = b.fetch()
+        if self._band_retry and calc_probabilities and res.band_margin_low is not None:
+            self._retry_bands(res, signals, sequences)
+        return res
 
     def train_batch(self, signals: Sequence, sequences: Sequence[str], pooled: bool = False) -> TrainBatchResult:
         with self.batch(signals, sequences) as b:

@@ -14,8 +14,8 @@ CSRC = os.path.join(HERE, "csrc")
 # DYN_LIB_PATH: another build of the SAME sources (tools/sanitize: the host side under ASan / UBSan / TSan on the CPU)
 LIB_PATH = os.environ.get("DYN_LIB_PATH") or os.path.join(HERE, "libdynamont_mi.so")
 SOURCES = ["dynamont_mi.cpp", "buffers.cpp", "launch.cpp", "session.cpp", "async_engine.cpp", "pore_model.cpp", "csv_format.cpp", "csv_sink.cpp", "vbz_decode.cpp", "bam_reader.cpp", "rccl_comm.cpp", "model_format.cpp",
-           "nt_kernels.hip", "pool_stats.hip", "wide_band.hip", "event_stats.hip", "rescale.hip", "kmer_summary.hip", "segment_scores.hip"]
-HEADERS = ["engine.hpp", "engine_internal.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "dp_cell.hpp", "segment_kernels.hpp", "kmer_summary_kernels.hpp", "segment_score_kernels.hpp", "border_kernels.hpp", "band_runs.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
+           "nt_kernels.hip", "pool_stats.hip", "wide_band.hip", "event_stats.hip", "rescale.hip", "kmer_summary.hip", "segment_scores.hip", "band_margin.hip"]
+HEADERS = ["engine.hpp", "engine_internal.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "dp_cell.hpp", "segment_kernels.hpp", "kmer_summary_kernels.hpp", "segment_score_kernels.hpp", "border_kernels.hpp", "band_margin_kernels.hpp", "band_runs.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
 
 DYN_DEVICE_HOST_ONLY = -2
 DYN_CSV_EVENT_STATS = 0x1  # dyn_csv_sink_open_ex flag
@@ -23,6 +23,7 @@ DYN_CSV_SEGMENT_SCORES = 0x2  # dyn_csv_sink_open_ex flag
 DYN_SEGMENT_SCORES_MAX_WINDOW = 256
 DYN_CSV_BORDER_CONFIDENCE = 0x8  # dyn_csv_sink_open_ex flag
 DYN_BORDER_CONFIDENCE_MAX_WINDOW = 256
+DYN_BAND_MARGIN_NONE = 0xFFFFFFFF  # dyn_band_margin_out: the edge was never a real one
 DYN_OK, DYN_ERR_INVALID_ARGUMENT, DYN_ERR_RUNTIME, DYN_ERR_DEVICE, DYN_ERR_OUT_OF_MEMORY = range(5)
 
 c_double_p = C.POINTER(C.c_double)
@@ -30,6 +31,7 @@ c_float_p = C.POINTER(C.c_float)
 c_u64_p = C.POINTER(C.c_uint64)
 c_i32_p = C.POINTER(C.c_int32)
 c_u8_p = C.POINTER(C.c_uint8)
+c_u32_p = C.POINTER(C.c_uint32)
 
 
 class DynInfo(C.Structure):
@@ -59,6 +61,11 @@ class DynBorderOut(C.Structure):
 
 class DynRescaleOut(C.Structure):
     _fields_ = [("shift", c_double_p), ("scale", c_double_p), ("iters_applied", c_i32_p), ("n", C.c_uint64)]
+
+
+class DynBandMarginOut(C.Structure):
+    _fields_ = [("low", C.POINTER(C.c_uint32)), ("high", C.POINTER(C.c_uint32)), ("edge_rows", C.POINTER(C.c_uint32)),
+                ("n", C.c_uint64)]
 
 
 class DynTrainOut(C.Structure):
@@ -121,6 +128,7 @@ SIGNATURES = {
     "dyn_aligner_set_segment_scores": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_aligner_set_border_confidence": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_aligner_set_kmer_summary": (C.c_int, [C.c_void_p, C.c_int]),
+    "dyn_aligner_set_band_margin": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_aligner_kmer_summary_fetch": (C.c_int, [C.c_void_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p]),
     "dyn_aligner_kmer_summary_reset": (C.c_int, [C.c_void_p]),
     "dyn_tie_rows": (C.c_uint32, [C.c_void_p, c_i32_p, C.c_uint64, C.c_uint64]),
@@ -188,6 +196,7 @@ SIGNATURES = {
     "dyn_batch_fetch_scores": (C.c_int, [C.c_void_p, C.POINTER(DynScoreOut)]),
     "dyn_batch_fetch_borders": (C.c_int, [C.c_void_p, C.POINTER(DynBorderOut)]),
     "dyn_batch_fetch_rescale": (C.c_int, [C.c_void_p, C.POINTER(DynRescaleOut)]),
+    "dyn_batch_fetch_band_margin": (C.c_int, [C.c_void_p, C.POINTER(DynBandMarginOut)]),
     "dyn_batch_fetch_train": (C.c_int, [C.c_void_p, C.POINTER(DynTrainOut), c_double_p]),
     "dyn_batch_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_u64_p, C.POINTER(C.c_void_p)]),
     "dyn_batch_device_pooled": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_u64_p]),

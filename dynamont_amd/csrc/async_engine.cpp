@@ -224,6 +224,14 @@ std::shared_ptr<BatchGroup> Pipeline::merge(const std::vector<dyn_batch*>& ticke
     if (!g->ks_ranges.empty() && g->ks_ranges.back().second == lo) g->ks_ranges.back().second = hi;
     else g->ks_ranges.emplace_back(lo, hi);
   }
+  // ... and so are the band margins: the launch computes them for the members that asked
+  for (dyn_batch* t : tickets) {
+    if (!t->bm_want || !t->n) continue;
+    g->bm_want = true;
+    const uint32_t lo = (uint32_t)t->g_read0, hi = (uint32_t)(t->g_read0 + t->n);
+    if (!g->bm_ranges.empty() && g->bm_ranges.back().second == lo) g->bm_ranges.back().second = hi;
+    else g->bm_ranges.emplace_back(lo, hi);
+  }
   g->in_sig_offsets = grp->sig_offsets.data();
   g->in_seqs = grp->seqs.data();
   g->in_seq_offsets = grp->seq_offsets.data();
@@ -769,6 +777,7 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
   b->ev_want = a->event_stats;
   b->rs_want = a->rescale_iters;
   b->ks_want = a->kmer_summary;
+  b->bm_want = a->band_margin;
   b->sc_want = a->segment_scores;
   b->bc_want = a->border_confidence;
   b->in_signals = signals;

@@ -59,7 +59,7 @@ void attach_cache(dyn_batch* b) {
   dyneng::BufCache* c = &b->a->cache;
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_wide})
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_wide})
     d->cache = c;
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->cache = c;
 }
@@ -562,6 +562,19 @@ int dyn_aligner_set_border_confidence(dyn_aligner* a, int window) {
   return DYN_OK;
 }
 
+int dyn_aligner_set_band_margin(dyn_aligner* a, int on) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  if (a->ntk) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = "dyn_aligner_set_band_margin: modes ntk / resquiggle have no align(calc_probabilities = 1) job to report on";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = need_device(a)) return rc;
+  a->band_margin = on != 0;
+  return DYN_OK;
+}
+
 int dyn_aligner_set_kmer_summary(dyn_aligner* a, int on) {
   if (!a) return DYN_ERR_INVALID_ARGUMENT;
   if (a->ntk) {
@@ -874,7 +887,7 @@ void dyn_batch_destroy(dyn_batch* b) {
   if (b->a && !b->a->host_only) (void)hipSetDevice(b->a->device);
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl})
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl})
     d->release();
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->release();
   for (hipEvent_t e : b->events) (void)hipEventDestroy(e);
@@ -1016,6 +1029,7 @@ int run_job_sync(dyn_batch* b, DynJob job) {
     b->ev_want = a->event_stats;
     b->rs_want = a->rescale_iters;
     b->ks_want = a->kmer_summary;
+    b->bm_want = a->band_margin;
     b->sc_want = a->segment_scores;
     b->bc_want = a->border_confidence;
     rc = enqueue_job(b, job);
@@ -1228,6 +1242,32 @@ int dyn_batch_fetch_rescale(dyn_batch* b, dyn_rescale_out* out) {
     out->scale[i] = h[i].B;
     out->iters_applied[i] = h[i].applied;
   }
+  return DYN_OK;
+}
+
+int dyn_batch_fetch_band_margin(dyn_batch* b, dyn_band_margin_out* out) {
+  if (!b || !out || !out->low || !out->high || !out->edge_rows) return DYN_ERR_INVALID_ARGUMENT;
+  dyn_aligner* a = b->a;
+  // a member of a merged launch: reads [g_read0, g_read0 + n) of the group's margins, if THIS member asked
+  const dyn_batch* src = (b->group && b->group->g) ? b->group->g : b;
+  const uint64_t read0 = src == b ? 0 : b->g_read0;
+  if (!b->aligned || !b->last_calc || !b->bm_want || !src->bm_ready) {
+    a->last_error = !b->aligned || !b->last_calc
+                        ? "dyn_batch_fetch_band_margin: the batch was not aligned with calc_probabilities = 1"
+                        : "dyn_batch_fetch_band_margin: the batch was submitted without dyn_aligner_set_band_margin(a, 1)";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  if (out->n < b->n) {
+    a->last_error = "dyn_band_margin_out.n is smaller than the batch's read count";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  int rc = need_device(a);
+  if (rc != DYN_OK) return rc;
+  if (!b->n) return DYN_OK;
+  const uint32_t* m = src->d_bm.as<uint32_t>() + read0;
+  HIP_TRY(a, copy_out(a, out->low, m, b->n * 4));
+  HIP_TRY(a, copy_out(a, out->high, m + src->n, b->n * 4));
+  HIP_TRY(a, copy_out(a, out->edge_rows, m + 2 * src->n, b->n * 4));
   return DYN_OK;
 }
 

@@ -151,6 +151,7 @@ struct dyn_aligner {
   bool kmer_summary = false;  // dyn_aligner_set_kmer_summary: read by every batch / ticket at its submission
   int segment_scores = 0;     // dyn_aligner_set_segment_scores (window, 0 = off): read by every batch / ticket at its submission
   int border_confidence = 0;  // dyn_aligner_set_border_confidence (window, 0 = off): read by every batch / ticket at its submission
+  bool band_margin = false;   // dyn_aligner_set_band_margin: read by every batch / ticket at its submission
   dyneng::DevBuf d_ksum;      // [6 num_kmers + 4] u64: the per-k-mer accumulator and its totals (kmer_summary_kernels.hpp),
                               // allocated and zeroed by the first dyn_aligner_set_kmer_summary(a, 1)
   bool ntk = false;     // created with mode "resquiggle" / "ntk"
@@ -262,6 +263,11 @@ struct dyn_batch {
   // launch's batch lists the read ranges of the members that asked (same_kind does not look at the switch)
   bool ks_want = false;
   std::vector<std::pair<uint32_t, uint32_t>> ks_ranges;
+  // band-margin diagnostics (dyn_aligner_set_band_margin): the switch likewise, and likewise a merged launch's read ranges
+  bool bm_want = false;
+  std::vector<std::pair<uint32_t, uint32_t>> bm_ranges;
+  dyneng::DevBuf d_bm;                         // [3][n] uint32 low / high / edge_rows (band_margin_kernels.hpp), when asked for
+  bool bm_ready = false;                       // the last job computed the margins into d_bm
   dyneng::PinnedBuf h_descs, h_state, h_rows;  // h_state/h_rows: D2H targets of the asynchronous path
   dyneng::PinnedBuf h_stats;                   // wave-cycle statistics of the read-queue launch
   dyneng::PinnedBuf h_sig;                     // staging of pageable caller signals (asynchronous path)
@@ -369,6 +375,10 @@ int session_recover(dyn_batch* b, bool* republished);
 // what launch_segments and launch_kmer_summary get for this batch's align(calc = 1) job: one entry per range of reads whose
 // ticket asked for the summary (empty: none did)
 std::vector<dynk::KmerSummary> kmer_summary_args(const dyn_batch* b);
+// the same for the band margins (b->d_bm must hold 3 * n uint32: band_margin_prepare)
+std::vector<dynk::BandMargin> band_margin_args(const dyn_batch* b);
+// bm_ready and the room for the margins of an align(calc = 1) job of this batch / ticket
+int band_margin_prepare(dyn_batch* b, bool calc);
 // the per-segment kernels and the statistics copy of a COMPLETED session ticket, on `s`
 int session_finish_enqueue(dyn_batch* b, hipStream_t s);
 int session_collect_timing(dyn_batch* b);

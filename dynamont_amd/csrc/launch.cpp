@@ -648,12 +648,16 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     scc = dynk::ScoreCols{q.sig, e, e + b->capacity, e + 2 * b->capacity, e + 3 * b->capacity, b->sc_want};
     b->sc_ready = true;
   }
+  if (int rc = band_margin_prepare(b, calc != 0)) return rc;
   if (calc) {
     // the per-k-mer summary (once per job, after the last pass: the signal of a rescaling job is its last pass's)
     const std::vector<dynk::KmerSummary> ks = kmer_summary_args(b);
+    // the band margins (likewise once, from the last pass's borders)
+    const std::vector<dynk::BandMargin> bm = band_margin_args(b);
     dynk::launch_segments(q.descs, nr_all, rows_total, max_N, q.st, q.tb, b->d_rows.as<SegRow>(), m.k, a->stream, evc,
-                          ks.empty() ? dynk::KmerSummary{} : ks[0], scc);
+                          ks.empty() ? dynk::KmerSummary{} : ks[0], scc, bm.empty() ? dynk::BandMargin{} : bm[0]);
     for (size_t k = 1; k < ks.size(); ++k) dynk::launch_kmer_summary(q.descs, nr_all, max_N, q.st, q.tb, ks[k], a->stream);
+    for (size_t k = 1; k < bm.size(); ++k) dynk::launch_band_margin(q.descs, nr_all, max_N, q.st, q.tb, bm[k], a->stream);
   }
   if (job == DynJob::Train) {
     b->pool_nr = nr_all;
@@ -696,6 +700,31 @@ std::vector<dynk::KmerSummary> kmer_summary_args(const dyn_batch* b) {
       ks.read_lo = r.first;
       ks.read_hi = r.second;
       out.push_back(ks);
+    }
+  }
+  return out;
+}
+
+int band_margin_prepare(dyn_batch* b, bool calc) {
+  b->bm_ready = false;
+  if (!calc || !b->bm_want) return DYN_OK;
+  HIP_TRY(b->a, b->d_bm.ensure(std::max<uint64_t>(12, b->n * 12)));
+  b->bm_ready = true;
+  return DYN_OK;
+}
+
+std::vector<dynk::BandMargin> band_margin_args(const dyn_batch* b) {
+  std::vector<dynk::BandMargin> out;
+  if (!b->bm_ready || !b->n) return out;
+  uint32_t* m = b->d_bm.as<uint32_t>();
+  dynk::BandMargin bm{m, m + b->n, m + 2 * b->n, 0u, (uint32_t)b->n};
+  if (b->bm_ranges.empty()) {
+    out.push_back(bm);
+  } else {
+    for (const auto& r : b->bm_ranges) {
+      bm.read_lo = r.first;
+      bm.read_hi = r.second;
+      out.push_back(bm);
     }
   }
   return out;

@@ -2006,11 +2006,12 @@ void launch_session_close(uint32_t* ctl, hipStream_t s) { hipLaunchKernelGGL(k_s
 
 void launch_segments(const ReadDesc* descs, int n_reads, uint64_t rows_total, uint32_t max_N, const ReadState* st,
                      TraceBuffers tb, SegRow* rows, int kmer_size, hipStream_t s, const EventCols& ev, const KmerSummary& ks,
-                     const ScoreCols& sc) {
+                     const ScoreCols& sc, const BandMargin& bm) {
   launch_segment_medians(descs, n_reads, rows_total, max_N, st, tb, rows, kmer_size, s);
   launch_event_stats(descs, n_reads, rows_total, st, tb, ev, s);
   launch_kmer_summary(descs, n_reads, max_N, st, tb, ks, s);
   launch_segment_scores(descs, n_reads, rows_total, max_N, st, tb, sc, s);
+  launch_band_margin(descs, n_reads, max_N, st, tb, bm, s);
 }
 
 }  // namespace dynk

@@ -266,11 +266,22 @@ struct ScoreCols {
 };
 void launch_segment_scores(const ReadDesc* descs, int n_reads, uint64_t rows_total, uint32_t max_N, const ReadState* st,
                            const TraceBuffers& tb, const ScoreCols& sc, hipStream_t s);
+// band-margin diagnostics (band_margin.hip, dyn_aligner_set_band_margin): three uint32 per read, indexed by ReadDesc::read;
+// low == nullptr: not asked for
+struct BandMargin {
+  uint32_t* low;              // smallest slack of the called path to a real lower band edge (0xFFFFFFFF: never real)
+  uint32_t* high;             // ... to a real upper band edge
+  uint32_t* edge_rows;        // path rows with a real slack of 0
+  uint32_t read_lo, read_hi;  // the reads [read_lo, read_hi) (ReadDesc::read) are initialised and computed: the members of a
+                              // merged launch whose handle had the switch on when they were submitted
+};
+void launch_band_margin(const ReadDesc* descs, int n_reads, uint32_t max_N, const ReadState* st, const TraceBuffers& tb,
+                        const BandMargin& bm, hipStream_t s);
 // per-segment median posterior + output rows for all reads of descs (after launch_read_queue), then the signal levels when
-// `ev` asks for them, the per-k-mer summary when `ks` does and the segment scores when `sc` does
+// `ev` asks for them, the per-k-mer summary when `ks` does, the segment scores when `sc` does and the band margins when `bm` does
 void launch_segments(const ReadDesc* descs, int n_reads, uint64_t rows_total, uint32_t max_N, const ReadState* st,
                      TraceBuffers tb, SegRow* rows, int kmer_size, hipStream_t s, const EventCols& ev = EventCols{},
-                     const KmerSummary& ks = KmerSummary{}, const ScoreCols& sc = ScoreCols{});
+                     const KmerSummary& ks = KmerSummary{}, const ScoreCols& sc = ScoreCols{}, const BandMargin& bm = BandMargin{});
 // per-read signal rescaling (rescale.hip, dyn_aligner_set_rescale): the transform x = (x0 - A) / B of read `read`
 struct RescaleState {
   double A;         // shift: 0.0 until a fit is applied

@@ -377,6 +377,7 @@ int session_publish(dyn_batch* b) {
   if (b->ev_want) HIP_TRY(a, b->d_ev.ensure(std::max<uint64_t>(24, b->capacity * 24)));
   b->sc_ready = b->sc_want != 0;
   if (b->sc_want) HIP_TRY(a, b->d_sc.ensure(std::max<uint64_t>(32, b->capacity * 32)));
+  if (int rc = band_margin_prepare(b, true)) return rc;  // filled by session_finish_enqueue as well
   ReadState* st = b->h_state.as<ReadState>();
   for (uint64_t i = 0; i < b->n; ++i) {
     st[i].Zb = 0.0;
@@ -544,10 +545,14 @@ int session_finish_enqueue(dyn_batch* b, hipStream_t s) {
     scc = dynk::ScoreCols{b->d_sig.as<double>(), e, e + b->capacity, e + 2 * b->capacity, e + 3 * b->capacity, b->sc_want};
   }
   const std::vector<dynk::KmerSummary> ks = kmer_summary_args(b);
+  const std::vector<dynk::BandMargin> bm = band_margin_args(b);
   dynk::launch_segments(b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_rows_total, b->sess_max_N, b->d_state.as<ReadState>(), tb,
-                        b->d_rows.as<SegRow>(), a->model.k, s, evc, ks.empty() ? dynk::KmerSummary{} : ks[0], scc);
+                        b->d_rows.as<SegRow>(), a->model.k, s, evc, ks.empty() ? dynk::KmerSummary{} : ks[0], scc,
+                        bm.empty() ? dynk::BandMargin{} : bm[0]);
   for (size_t k = 1; k < ks.size(); ++k)
     dynk::launch_kmer_summary(b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_max_N, b->d_state.as<ReadState>(), tb, ks[k], s);
+  for (size_t k = 1; k < bm.size(); ++k)
+    dynk::launch_band_margin(b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_max_N, b->d_state.as<ReadState>(), tb, bm[k], s);
   HIP_TRY(a, hipGetLastError());
   HIP_TRY(a, hipEventRecord(ev[2], s));
   HIP_TRY(a, hipMemcpyAsync(b->h_stats.p, b->d_tctl.p, dynk::SESSION_TCTL_WORDS * 4, hipMemcpyDeviceToHost, s));

@@ -112,6 +112,15 @@ def parse(argv=None) -> Namespace:
                         "level (mean, stdev of the normalised signal) and dwell the run's segments showed per k-mer beside the "
                         "model's values, summed on the GPU as exact integers (the same bytes for any number of GPUs). Its "
                         "first three columns load as a model file; k-mers the run never met keep the model's values")
+    p.add_argument("--band-report", default="", metavar="FILE",
+                   help="also write FILE, a TSV with one line per read the aligner took: readid, T (signal samples + 1), N "
+                        "(k-mers + 1), band, band_margin_low, band_margin_high, band_edge_rows -- how close the called path came "
+                        "to a real edge of its band (the smallest distance in columns below and above; empty where that edge was "
+                        "never a real one or the read failed) and on how many rows it sat on one. A margin of 0 says that the band "
+                        "may have decided the alignment: run those reads again with a larger --band. Lines are sorted by readid "
+                        "(the same bytes for any number of GPUs); the CSV is unchanged")
+    p.add_argument("--band", type=int, default=400, metavar="COLUMNS",
+                   help="band width of the alignment lattice in columns (default 400, the reference's; up to 4093)")
     p.add_argument("--parallel-zstd-frames", action="store_true",
                    help="write the CSV as consecutive independent zstd frames (readers must read across frames: "
                         "python-zstandard's defaults stop after the first). Default: one frame, like the reference, "
@@ -345,6 +354,34 @@ def prepare_job(job, is_rna: bool):
     return signal, read
 
 
+BAND_REPORT_HEADER = b"readid\tT\tN\tband\tband_margin_low\tband_margin_high\tband_edge_rows\n"
+
+
+def band_report_lines(readids, T, N, band: int, low, high, edge_rows) -> list:
+    """--band-report: one line (no newline) per read; an empty field for DYN_BAND_MARGIN_NONE"""
+    none = 0xFFFFFFFF
+    field = lambda v: "" if int(v) == none else str(int(v))  # noqa: E731
+    return [f"{rid}\t{int(t)}\t{int(n)}\t{int(band)}\t{field(lo)}\t{field(hi)}\t{int(e)}"
+            for rid, t, n, lo, hi, e in zip(readids, T, N, low, high, edge_rows)]
+
+
+def band_report_bytes(lines) -> bytes:
+    """the report file: the header, then the lines sorted (by readid first: the order does not depend on batches or ranks)"""
+    return BAND_REPORT_HEADER + "".join(ln + "\n" for ln in sorted(lines)).encode()
+
+
+def _ticket_band_lines(aligner, t, readids, lengths, seq_off) -> list:
+    """the report lines of a COMPLETED align ticket submitted with the band-margin switch on"""
+    from dynamont_amd import _native as N
+    n = len(readids)
+    low, high, edge = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+    t.fetch_band_margin(N.DynBandMarginOut(low.ctypes.data_as(N.c_u32_p), high.ctypes.data_as(N.c_u32_p),
+                                           edge.ctypes.data_as(N.c_u32_p), n))
+    bases = np.diff(np.asarray(seq_off, dtype=np.int64))
+    cols = np.maximum(bases - aligner.kmer_size + 1, 0) + 1
+    return band_report_lines(readids, np.asarray(lengths, dtype=np.int64) + 1, cols, aligner.band, low, high, edge)
+
+
 def _stored_bases(p) -> int:
     """bases of the basecall as the BAM stores it -- what the reference's worker line reports as N (segment.py:178-187).
     ``p`` = (signal, read, job, cal[, stored bases]): the fifth element where job[5] is already in aligner orientation"""
@@ -425,6 +462,7 @@ class _Pipeline:
         self.aligner, self.sink, self.raw, self.threads = aligner, sink, raw, threads
         self.inflight = queue_mod.Queue(maxsize=max(1, depth))
         self.free = []            # result objects of completed batches, refilled instead of reallocated
+        self.band_lines = []      # --band-report: the lines of the tickets completed so far
         self.error = None
         self.rounds_done = queue_mod.Queue()
         self.consumer = threading.Thread(target=self._drain, daemon=True)
@@ -473,6 +511,10 @@ class _Pipeline:
     def _finish(self, t, g, seqs, seq_off) -> None:
         from dynamont_amd._dynamont import format_csv
         res = t.wait()
+        if self.aligner._band_margin:
+            self.band_lines += band_report_lines([p[2][6] for p in g], [len(p[0]) + 1 for p in g],
+                                                 np.maximum(np.diff(np.asarray(seq_off, dtype=np.int64)) - self.aligner.kmer_size + 1, 0) + 1,
+                                                 self.aligner.band, res.band_margin_low, res.band_margin_high, res.band_edge_rows)
         starts = [p[2][3] for p in g]
         buf, begin, end = format_csv(self.aligner, res, None, [p[2][6] for p in g], [p[2][7] for p in g], starts,
                                      [len(p[0]) + st for p, st in zip(g, starts)], threads=self.threads, compact=True,
@@ -543,6 +585,8 @@ class _NativePipeline:
         self.samples = {}  # batch number -> signal samples (in flight: bounded by MAX_SAMPLES_IN_FLIGHT as well as by depth)
         self.keep = {}   # batch number -> (ticket, arrays the sink still reads)
         self.free = []   # result objects of consumed batches
+        self.band_meta = {}   # --band-report: batch number -> (readids, signal lengths, sequence offsets)
+        self.band_lines = []  # ... and the lines of the tickets the sink has consumed
 
     def put(self, line: str) -> None:
         """an error line from the producer (reads that failed before the aligner, segment.py:178-187)"""
@@ -557,12 +601,19 @@ class _NativePipeline:
             for k in [k for k in self.keep if k < done]:
                 t, res = self.keep.pop(k)[:2]
                 self.samples.pop(k, None)
+                self._band_collect(k, t)
                 t.close()
                 self.free.append(res)
             if block_until is None or self.submitted - done <= block_until:
                 return
             self.check()
             self.L.dyn_csv_sink_wait(self.h, self.submitted - block_until, 200)
+
+    def _band_collect(self, k: int, t) -> None:
+        """--band-report: the margins of a ticket the sink is done with, before the ticket goes"""
+        meta = self.band_meta.pop(k, None)
+        if meta is not None:
+            self.band_lines += _ticket_band_lines(self.aligner, t, *meta)
 
     def submit(self, pending, end_of_round: bool = False) -> None:
         C, N = self.C, self.N
@@ -602,6 +653,8 @@ class _NativePipeline:
                 self.check()  # the sink's own failure, with its message
                 raise RuntimeError("dyn_csv_sink_submit failed")
             self.keep[self.submitted] = (t, res, seqs, seq_off, rid, sid, starts, lengths, g, bases)  # g: the slices (and their readers) stay alive
+            if self.aligner._band_margin:
+                self.band_meta[self.submitted] = ([str(p[2][6]) for p in g], lengths, seq_off)
             self.samples[self.submitted] = int(sig_off[-1])
             self.submitted += 1
 
@@ -656,6 +709,10 @@ class _NativePipeline:
             self.check()
             raise RuntimeError("dyn_csv_sink_submit failed")
         self.keep[self.submitted] = (t, res, jb, seq_off, rid, sid, starts, lengths, chunks, raw_off, cal, owners, bases)
+        if self.aligner._band_margin:
+            names = jb.names.tobytes()
+            self.band_meta[self.submitted] = ([names[int(a):int(b) - 1].decode() for a, b in zip(jb.name_off[:-1], jb.name_off[1:])],
+                                              lengths, seq_off)
         self.samples[self.submitted] = int(raw_off[-1])
         self.submitted += 1
 
@@ -677,7 +734,9 @@ class _NativePipeline:
         self.h = None
         LAST_RUN.update(csv_bytes=int(csv.value), compressed_bytes=int(zst.value), error_lines=int(nerr.value), batches=self.submitted,
                         depth=self.depth, compress_threads=self.threads)
-        for t, *_ in self.keep.values():
+        for k, (t, *_) in self.keep.items():
+            if rc == self.N.DYN_OK:
+                self._band_collect(k, t)  # (the sink has waited for every ticket)
             t.close()
         self.keep = {}
         _stamp("tickets released")
@@ -727,7 +786,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             minq: float = 0, device: int = 0, batch_reads: int = 1024, mem_budget_gib: float = 0.0,
             host_preprocess: bool = False, depth: int = 12, strict_ties: str = "ties", host_threads: int = 0,
             zstd_level: int = 3, event_stats: bool = False, rescale_iters: int = 0, kmer_summary: str = "",
-            segment_scores: int = 0, border_confidence: int = 0) -> None:
+            segment_scores: int = 0, border_confidence: int = 0, band_report: str = "", band: int = 400) -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
@@ -794,13 +853,27 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
         write_kmer_summary(kmer_summary, merge_kmer_summaries(parts), model_path, mean, stdev, aligner.rna)
         print(f"k-mer summary written: {kmer_summary}", file=sys.stderr, flush=True)
 
+    def write_band_report(lines):
+        # --band-report, with the pipeline dry: every rank's lines travel to rank 0 (one more gather), which sorts and writes
+        # them -- the same bytes for any number of ranks
+        if not band_report:
+            return
+        if comm is not None:
+            blobs = parallel.gather_bytes(comm, "\n".join(lines).encode())
+            if rank != 0:
+                return
+            lines = [ln for blob in blobs if blob for ln in blob.decode().split("\n")]
+        with open(band_report, "wb") as f:
+            f.write(band_report_bytes(lines))
+        print(f"band report written: {band_report}", file=sys.stderr, flush=True)
+
     # A failing rank ends the whole job (parallel.abort): a barrier in a `finally` would leave the other ranks in
     # their next collective until the process-group timeout.
     with parallel.abort_on_error(comm):
         pipe = None
         try:
             _stamp("segment(): creating the aligner")
-            aligner = Aligner(model_path, pore, mode=mode, threads=1, band=400, device=device)
+            aligner = Aligner(model_path, pore, mode=mode, threads=1, band=band, device=device)
             _stamp("aligner ready (model parsed, device initialised, tables uploaded)")
             if mem_budget_gib:
                 aligner.set_mem_budget(int(mem_budget_gib * (1 << 30)))
@@ -815,6 +888,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                 aligner.set_border_confidence(border_confidence)
             if kmer_summary:
                 aligner.set_kmer_summary(True)
+            if band_report:
+                aligner.set_band_margin(True)
             if native:
                 import os
                 import tempfile
@@ -873,11 +948,12 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                         pipe.submit(pending)
                 _stamp("every batch submitted")
                 pipe.close()
-                pipe = None
+                band_lines, pipe = pipe.band_lines, None
                 _stamp("pipeline closed: output complete")
                 if comm is not None:
                     _gather_parts(comm, parallel, outfile, part, part_err)
                 write_summary(aligner)
+                write_band_report(band_lines)
                 parallel.remove_scratch()
                 print("Done with segmentation.", file=sys.stderr, flush=True)
                 return
@@ -919,8 +995,9 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                     ship()
                     break
             pipe.close()
-            pipe = None
+            band_lines, pipe = pipe.band_lines, None
             write_summary(aligner)
+            write_band_report(band_lines)
             print("Done with segmentation.", file=sys.stderr, flush=True)
         finally:
             if pipe is not None:  # an exception is on its way: release what is queued, keep the first error
@@ -963,7 +1040,7 @@ def main(argv=None) -> None:
             host_preprocess=args.host_preprocess, depth=args.depth, strict_ties=args.strict_ties, host_threads=args.host_threads,
             zstd_level=args.zstd_level, event_stats=args.event_stats, rescale_iters=args.rescale_iters,
             kmer_summary=args.kmer_summary, segment_scores=args.segment_scores,
-            border_confidence=args.border_confidence)
+            border_confidence=args.border_confidence, band_report=args.band_report, band=args.band)
     _stamp("segment() returned (aligner closed)")
     if argv is None and not int(__import__("os").environ.get("WORLD_SIZE", "1") or 1) > 1:
         # Invoked as the command (console script / python -m), single process, everything written and closed: leave without

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DYN_ABI_VERSION 10 /* 10 (number kept; look the symbols up): per-k-mer level summary of a run: dyn_aligner_set_kmer_summary, dyn_aligner_kmer_summary_fetch / _reset (additive). 10: per-read signal rescaling: dyn_aligner_set_rescale, dyn_batch_fetch_rescale (additive). 9: per-segment signal levels: dyn_aligner_set_event_stats, dyn_batch_fetch_events, dyn_format_csv[_bound]_events, dyn_csv_sink_open_ex (additive). 8: dyn_aligner_session_idle_split (additive). 7: dyn_aligner_session_page_wait, dyn_comm_gather_bytes / _gathered_bytes / _allreduce_f64 (additive). 7: half bands 224 .. 2 046 are computed (wide_band.hip). 5: any band constructs (DYN_READ_BAND_TOO_WIDE per read); dyn_bam_*, dyn_csv_sink_wait / _open_part */
+#define DYN_ABI_VERSION 10 /* 10 (number kept; look the symbols up): band-margin diagnostics: dyn_aligner_set_band_margin, dyn_batch_fetch_band_margin (additive). 10 (number kept): per-k-mer level summary of a run: dyn_aligner_set_kmer_summary, dyn_aligner_kmer_summary_fetch / _reset (additive). 10: per-read signal rescaling: dyn_aligner_set_rescale, dyn_batch_fetch_rescale (additive). 9: per-segment signal levels: dyn_aligner_set_event_stats, dyn_batch_fetch_events, dyn_format_csv[_bound]_events, dyn_csv_sink_open_ex (additive). 8: dyn_aligner_session_idle_split (additive). 7: dyn_aligner_session_page_wait, dyn_comm_gather_bytes / _gathered_bytes / _allreduce_f64 (additive). 7: half bands 224 .. 2 046 are computed (wide_band.hip). 5: any band constructs (DYN_READ_BAND_TOO_WIDE per read); dyn_bam_*, dyn_csv_sink_wait / _open_part */
 
 /* device argument of dyn_aligner_create: bind no GPU. Such a handle serves the host-side
  * contract only (model loading, dyn_aligner_info/_model, dyn_validate_batch); every compute
@@ -216,6 +216,26 @@ typedef struct dyn_rescale_out {
   uint64_t n;              /* entries of each array: at least the batch's read count */
 } dyn_rescale_out;
 
+/* (added within ABI 10) Band-margin diagnostics: how close the called path of a read came to a REAL edge of its band, for
+ * every ok read of an align(calc_probabilities = 1) job whose handle had dyn_aligner_set_band_margin(a, 1) when the batch was
+ * submitted. Row t of the lattice is banded around mid(t) = size_t(t * N / T) (one fp64 product, truncated) with
+ * bw = min(band / 2, N / 2) columns on either side. Output row j (column n = j + 1) covers the lattice rows from its
+ * signal_position + 1 up to the next row's (the last one up to T = signal length + 1).
+ *   lower edge: real at row t iff mid(t) - bw >= 2; slack n - (mid(t) - bw)
+ *   upper edge: real at row t iff mid(t) + bw + 1 < N; slack (mid(t) + bw) - n
+ *   an edge that is not real is the lattice's own border and contributes nothing
+ * low / high: the minimum slack over all path rows where that edge is real, DYN_BAND_MARGIN_NONE where it never is;
+ * edge_rows: the path rows with a real slack of 0 (a row where both are 0 counts once). A failed read gets NONE, NONE, 0.
+ * A margin of 0 says that the band, not the signal, may have decided the alignment: align the read again at a wider band.
+ * With dyn_aligner_set_rescale on, the values are the last pass's. */
+#define DYN_BAND_MARGIN_NONE 0xFFFFFFFFu
+typedef struct dyn_band_margin_out {
+  uint32_t* low;        /* [n] band_margin_low */
+  uint32_t* high;       /* [n] band_margin_high */
+  uint32_t* edge_rows;  /* [n] band_edge_rows */
+  uint64_t n;           /* entries of each array: at least the batch's read count */
+} dyn_band_margin_out;
+
 /* Per-read training results (replaces dynamont::TrainingResult, aligner.hpp:48-53, whose
  * pybind form is a list of num_kmers dicts per read, aligner_bindings.cpp:86-107). The emission
  * update is returned SPARSE: only k-mers with weight > 0 (all others keep the loaded model,
@@ -397,6 +417,13 @@ int dyn_aligner_set_event_stats(dyn_aligner* a, int on);
  * Each pass costs about one alignment; device memory: a copy of the batch's signal, 32 bytes per read, 8 per segment row.
  * dyn_multi_*: set it on each device's handle (dyn_multi_handle). */
 int dyn_aligner_set_rescale(dyn_aligner* a, int iters);
+/* (added within ABI 10: a caller that must know looks the symbol up) align(calc_probabilities = 1) also computes the band
+ * margins (dyn_band_margin_out) on the device, behind the per-segment kernels, for every batch or ticket SUBMITTED while it is
+ * on; 12 bytes of device memory per read for those batches only. Such tickets stay in the resident session and merge with
+ * tickets that did not ask. Default off: nothing is allocated, launched or changed. DYN_ERR_INVALID_ARGUMENT for a handle of
+ * mode "ntk" / "resquiggle", DYN_ERR_DEVICE for one without a device. dyn_multi_*: set it on each
+ * device's handle (dyn_multi_handle). */
+int dyn_aligner_set_band_margin(dyn_aligner* a, int on);
 /* (added within ABI 10) align(calc_probabilities = 1) also computes the per-border segment scores (dyn_score_out) with a
  * window of `window` samples on the device, behind the per-segment kernels, for every batch or ticket SUBMITTED while
  * window > 0; 4 x 8 bytes of device memory per segment row for those batches only. window = 0 ..
@@ -689,6 +716,11 @@ int dyn_batch_fetch_borders(dyn_batch* b, dyn_border_out* out);
  * `out` (n >= the batch's read count). DYN_ERR_INVALID_ARGUMENT + message for a batch submitted with
  * dyn_aligner_set_rescale(a, 0), or aligned with calc_probabilities = 0. */
 int dyn_batch_fetch_rescale(dyn_batch* b, dyn_rescale_out* out);
+/* (added within ABI 10) The band margins of the batch's last align(calc_probabilities = 1) job (or of a completed ticket,
+ * merged launch or not), copied on the handle's own non-blocking stream into `out` (n >= the batch's read count).
+ * DYN_ERR_INVALID_ARGUMENT + message for a batch submitted with dyn_aligner_set_band_margin off, or aligned with
+ * calc_probabilities = 0. */
+int dyn_batch_fetch_band_margin(dyn_batch* b, dyn_band_margin_out* out);
 /* Device-resident results of the last dyn_batch_align, for an RCCL gather without a host hop:
  * rows = dyn_segment_row[capacity] (read i at seg_offsets[i], as in dyn_align_out);
  * z_status = per read {double Z; int32 status; uint32 n_segments}. Pointers stay valid until the

@@ -23,8 +23,11 @@ void launch_prep_params(const int32_t*, const Emis*, Emis*, uint64_t, uint32_t, 
 void launch_pool_init(const PagePool&, uint32_t, int, hipStream_t) { no_device("launch_pool_init"); }
 void launch_read_queue(QueueJob, bool, const QueueArgs&, int, hipStream_t) { no_device("launch_read_queue"); }
 void launch_segments(const ReadDesc*, int, uint64_t, uint32_t, const ReadState*, TraceBuffers, SegRow*, int, hipStream_t, const EventCols&,
-                     const KmerSummary&, const ScoreCols&) {
+                     const KmerSummary&, const ScoreCols&, const BandMargin&) {
   no_device("launch_segments");
+}
+void launch_band_margin(const ReadDesc*, int, uint32_t, const ReadState*, const TraceBuffers&, const BandMargin&, hipStream_t) {
+  no_device("launch_band_margin");
 }
 void launch_segment_scores(const ReadDesc*, int, uint64_t, uint32_t, const ReadState*, const TraceBuffers&, const ScoreCols&, hipStream_t) {
   no_device("launch_segment_scores");
