@@ -394,6 +394,17 @@ class Batch:
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
 
+    def set_guide(self, centres, half_width: int) -> None:
+        """dyn_batch_set_guide: the next ``align()`` runs every read inside a window of ``half_width`` lattice columns on either
+        side of a per-sample guide path. ``centres``: int32, one entry per signal sample of the
+        batch in batch order (``dynamont_amd.guide`` builds them); copied to the device before the call returns."""
+        g = np.ascontiguousarray(centres, dtype=np.int32)
+        if g.ndim != 1:
+            raise ValueError("centres must be a one-dimensional int32 array")
+        rc = self._L.dyn_batch_set_guide(self._h, _ptr(g, N.c_i32_p), g.size, int(half_width))
+        if rc != N.DYN_OK:
+            _raise(rc, self._al.last_error())
+
     def train(self) -> None:
         rc = self._L.dyn_batch_train(self._h)
         if rc != N.DYN_OK:
@@ -460,6 +471,13 @@ class Batch:
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
         return out
+
+    def arena_bytes(self) -> int:
+        """dyn_batch_arena_bytes: device bytes the last job allocated for per-workgroup lattice arenas (the guided kernel's, or the
+        wide-band kernel's); 0 for a batch that took only the paged read queue, and for a Z-only guided job"""
+        v = C.c_uint64(0)
+        self._L.dyn_batch_arena_bytes(self._h, C.byref(v))
+        return int(v.value)
 
     def timing(self) -> dict:
         t = N.DynTiming()
@@ -1104,6 +1122,25 @@ class Aligner:
         if self._band_retry and calc_probabilities and res.band_margin_low is not None:
             self._retry_bands(res, signals, sequences)
         return res
+
+    def align_batch_guided(self, signals: Sequence, sequences: Sequence[str], guides: Sequence, half_width: int,
+                           calc_probabilities: bool = True) -> AlignBatchResult:
+        """``align_batch`` inside a guided band: ``guides[i]`` is read i's int32 guide, one lattice column per signal sample
+        (``dynamont_amd.guide.guide_from_moves`` / ``guide_from_starts`` / ``diagonal_guide``), and every read is aligned in a
+        window of ``half_width`` columns on either side of it instead of the band around the fixed diagonal. With
+        ``set_band_margin(True)`` the three margin fields are taken against that window. Never retried (``set_band_retry``
+        applies to ``align_batch``); not together with ``set_rescale`` / ``set_border_confidence`` (ValueError)."""
+        if len(guides) != len(signals):
+            raise ValueError("signals and guides differ in length")
+        parts = [np.ascontiguousarray(g, dtype=np.int32).ravel() for g in guides]
+        for i, (g, s) in enumerate(zip(parts, signals)):
+            if g.size != len(s):
+                raise ValueError(f"guide {i} holds {g.size} entries for a signal of {len(s)} samples")
+        centres = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
+        with self.batch(signals, sequences) as b:
+            b.set_guide(centres, half_width)
+            b.align(calc_probabilities)
+            return b.fetch()
 
     def train_batch(self, signals: Sequence, sequences: Sequence[str], pooled: bool = False) -> TrainBatchResult:
         with self.batch(signals, sequences) as b:

@@ -59,7 +59,7 @@ void attach_cache(dyn_batch* b) {
   dyneng::BufCache* c = &b->a->cache;
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_wide})
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_wide, &b->d_guide, &b->d_garena})
     d->cache = c;
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->cache = c;
 }
@@ -762,6 +762,21 @@ int create_impl(dyn_aligner* a, uint64_t n_reads, const double* signals, const R
   if (!a || !out) return DYN_ERR_INVALID_ARGUMENT;
   *out = nullptr;
   std::lock_guard<std::mutex> lk(a->mu);
+  if (a->host_only) {
+    // A handle without a device gets the read table alone (validateInput + sequenceToKmers in plain memory): what the host-side
+    // checks of a batch need (dyn_batch_set_guide). Every job and every getter of such a batch reports the missing device.
+    if (n_reads && (!sig_offsets || !seqs || !seq_offsets)) return DYN_ERR_INVALID_ARGUMENT;
+    dyn_batch* hb = new dyn_batch();
+    hb->a = a;
+    hb->host_only = true;
+    const int hrc = host_prepare(hb, a->model, false, n_reads, sig_offsets, seqs, seq_offsets, nullptr);
+    if (hrc != DYN_OK) {
+      dyn_batch_destroy(hb);
+      return hrc;
+    }
+    *out = hb;
+    return DYN_OK;
+  }
   int rc = need_device(a);
   if (rc != DYN_OK) return rc;
   dyn_batch* b = new dyn_batch();
@@ -885,9 +900,13 @@ void dyn_batch_destroy(dyn_batch* b) {
   if (!b) return;
   if (b->async && b->a && b->a->pipe) (void)b->a->pipe->wait(b);  // returns at once when the batch is done
   if (b->a && !b->a->host_only) (void)hipSetDevice(b->a->device);
+  if (b->host_only) {  // the k-mer codes of a batch without a device are plain memory (host_prepare)
+    std::free(b->h_kmers.p);
+    b->h_kmers.p = nullptr;
+  }
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl})
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl, &b->d_wide, &b->d_guide, &b->d_garena})
     d->release();
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->release();
   for (hipEvent_t e : b->events) (void)hipEventDestroy(e);
@@ -1022,6 +1041,16 @@ int run_job_sync(dyn_batch* b, DynJob job) {
     a->last_error = "dyn_batch_align / dyn_batch_train on an asynchronous ticket: submit a new ticket, or use dyn_batch_create";
     return DYN_ERR_INVALID_ARGUMENT;
   }
+  // a guided batch (dyn_batch_set_guide) runs align jobs only, and none that re-aligns or reads the lattice after the traceback
+  if (b->guided && job == DynJob::Train) {
+    a->last_error = "dyn_batch_train: the batch carries a guide (dyn_batch_set_guide) and training inside a guided band is not supported";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  if (b->guided && (a->rescale_iters > 0 || a->border_confidence > 0)) {
+    a->last_error = std::string("dyn_batch_align: the batch carries a guide (dyn_batch_set_guide), which does not combine with ") +
+                    (a->rescale_iters > 0 ? "dyn_aligner_set_rescale(a, iters > 0)" : "dyn_aligner_set_border_confidence(a, window > 0)");
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
   {
     std::lock_guard<std::mutex> lk(a->mu);
     int rc = need_device(a);
@@ -1054,6 +1083,53 @@ int dyn_batch_align(dyn_batch* b, int calc_probabilities) {
 int dyn_batch_train(dyn_batch* b) {
   if (!b) return DYN_ERR_INVALID_ARGUMENT;
   return run_job_sync(b, DynJob::Train);
+}
+
+int dyn_batch_set_guide(dyn_batch* b, const int32_t* centres, uint64_t count, uint32_t half_width) {
+  if (!b) return DYN_ERR_INVALID_ARGUMENT;
+  dyn_aligner* a = b->a;
+  std::lock_guard<std::mutex> lk(a->mu);
+  auto fail = [&](const std::string& msg) {
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = "dyn_batch_set_guide: " + msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  };
+  if (b->async || b->group) return fail("the batch is an asynchronous ticket; a guide is set on a batch from dyn_batch_create / dyn_batch_create_raw");
+  if (b->aligned || b->trained) return fail("the batch has already run; set the guide before dyn_batch_align");
+  if (half_width < 1 || half_width > (uint32_t)dynk::WIDE_MAX_HALF_BAND)
+    return fail("half_width " + std::to_string(half_width) + " is outside [1, " + std::to_string(dynk::WIDE_MAX_HALF_BAND) + "]");
+  const uint64_t total = b->n ? b->reads[b->n - 1].sig_off + b->reads[b->n - 1].S : 0;
+  if (count != total) return fail("count " + std::to_string(count) + " differs from the batch's " + std::to_string(total) + " samples");
+  if (count && !centres) return fail("centres is null");
+  for (uint64_t i = 0; i < b->n; ++i) {
+    const HostRead& r = b->reads[i];
+    if (r.status != DYN_READ_OK) continue;  // (a read that failed validation has no lattice to guide)
+    const int32_t* g = centres + r.sig_off;
+    const int64_t top = (int64_t)r.kc;  // N - 1
+    for (uint64_t s = 0; s < r.S; ++s) {
+      if (g[s] < 0 || (int64_t)g[s] > top)
+        return fail("read " + std::to_string(i) + ", sample " + std::to_string(s) + ": centre " + std::to_string(g[s]) +
+                    " is outside [0, " + std::to_string(top) + "] (lattice columns 0 .. N - 1)");
+      if (s && g[s] < g[s - 1])
+        return fail("read " + std::to_string(i) + ", sample " + std::to_string(s) + ": centre " + std::to_string(g[s]) +
+                    " is below the previous sample's " + std::to_string(g[s - 1]) + " (a guide never decreases)");
+    }
+  }
+  if (!b->host_only) {
+    if (int rc = need_device(a)) return rc;
+    HIP_TRY(a, b->d_guide.ensure(std::max<uint64_t>(4, count * 4)));
+    if (count) HIP_TRY(a, hipMemcpyAsync(b->d_guide.p, centres, count * 4, hipMemcpyHostToDevice, a->stream));
+    HIP_TRY(a, hipStreamSynchronize(a->stream));  // the caller's array is free again on return
+  }
+  b->guided = true;
+  b->guide_hw = half_width;
+  return DYN_OK;
+}
+
+int dyn_batch_arena_bytes(const dyn_batch* b, uint64_t* bytes) {
+  if (!b || !bytes) return DYN_ERR_INVALID_ARGUMENT;
+  *bytes = b->arena_bytes;
+  return DYN_OK;
 }
 
 int dyn_batch_timing(const dyn_batch* b, dyn_timing* t) {

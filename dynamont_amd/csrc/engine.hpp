@@ -275,6 +275,14 @@ struct dyn_batch {
   dyneng::DevBuf d_norm, d_meta;
   dyneng::DevBuf d_wide;        // wide-band reads (wide_band.hip): queue head + one lattice arena per workgroup
   uint64_t n_wide = 0;          // reads of this batch that take the generic kernel
+  // guided band (guided_band.hip, dyn_batch_set_guide): every ok read of a guided batch takes the guided kernel, inside a window
+  // of half width guide_hw around its guide; a synchronous batch only, so it never joins a session or a merged launch
+  bool guided = false;
+  uint32_t guide_hw = 0;
+  dyneng::DevBuf d_guide;       // [samples of the batch] int32 centres (HostRead::sig_off counts from here)
+  dyneng::DevBuf d_garena;      // queue head + one lattice arena per workgroup
+  uint64_t arena_bytes = 0;     // what the last job asked of d_garena / d_wide: queue head + every workgroup's lattice arena
+  bool host_only = false;       // created on a handle without a device: the read table alone (validation, no job)
   dyneng::SessionGeom sess_geom;  // session_plan's decision for this ticket (ok = false: none taken)
   bool has_raw = false;
   RawSource raw_src;

@@ -4,6 +4,7 @@
 // the body of NTAligner::align / train (NT_aligner_api.cpp:230-312, 567-639) for one read at a time.
 #include "engine_internal.hpp"
 #include "dp_math_strict.hpp"
+#include "guided_band_kernels.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -256,7 +257,9 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     const HostRead& r = b->reads[i];
     if (r.status != DYN_READ_OK) continue;
     if (a->ntk) continue;  // no read reaches the device; its status is set below
-    if (r.wide) {  // the generic kernel (wide_band.hip): the reference's own arithmetic in every cell, no queue, no pages
+    // a guided batch (dyn_batch_set_guide): every read takes the guided kernel (guided_band.hip), whatever its N -- its
+    // descriptors and its arena are laid out like the wide reads', which such a batch then has none of
+    if (r.wide || b->guided) {  // the generic kernel (wide_band.hip): the reference's own arithmetic in every cell, no queue, no pages
       wide.push_back((uint32_t)i);
       continue;
     }
@@ -463,11 +466,13 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   if (!wide.empty()) {
     size_t free_b = 0, total_b = 0;
     HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
-    const uint64_t room = (uint64_t)((double)(free_b + b->d_wide.bytes + parked_bytes(a->device)) * 0.8);
+    uint64_t room = (uint64_t)((double)(free_b + (b->guided ? b->d_garena.bytes : b->d_wide.bytes) + parked_bytes(a->device)) * 0.8);
+    if (b->guided && a->mem_budget && room > a->mem_budget) room = a->mem_budget;
     size_t wr = 0;
     for (uint32_t i : wide) {
       const HostRead& r = b->reads[i];
-      const uint64_t need = dynk::wide_arena_bytes(r.S + 1, std::min<uint64_t>(m.half_band, (r.kc + 1) / 2), calc);
+      const uint64_t need = b->guided ? dynk::guided_arena_bytes(r.S + 1, b->guide_hw, calc)
+                                      : dynk::wide_arena_bytes(r.S + 1, std::min<uint64_t>(m.half_band, (r.kc + 1) / 2), calc);
       if (need > room) st[i].status = DYN_READ_TOO_LARGE;
       else {
         wide_arena = std::max(wide_arena, need);
@@ -478,8 +483,12 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       wide.resize(wr);
       if (b->n) HIP_TRY(a, hipMemcpyAsync(b->d_state.p, st, b->n * sizeof(ReadState), hipMemcpyHostToDevice, a->stream));
     }
-    if (!wide.empty()) wide_groups = (int)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)wide.size(), (uint64_t)a->n_cus, room / wide_arena}));
+    if (!wide.empty() && b->guided)
+      wide_groups = (int)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)wide.size(), (uint64_t)a->n_cus * (uint64_t)dynk::guided_groups_per_cu((int)b->guide_hw),
+                                                                   wide_arena ? room / wide_arena : ~0ull}));
+    else if (!wide.empty()) wide_groups = (int)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)wide.size(), (uint64_t)a->n_cus, room / wide_arena}));
   }
+  b->arena_bytes = 0;
   const size_t n_all = n_ok + wide.size();
   for (size_t k = 0; k < wide.size(); ++k) {
     const uint32_t i = wide[k];
@@ -498,7 +507,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     rows_total += d.T;
     max_N = std::max(max_N, d.N);
     descs[n_ok + k] = d;
-    tm.cells += (uint64_t)d.T * std::min<uint64_t>(2ull * d.bw + 1, d.N);
+    tm.cells += b->guided ? (uint64_t)d.T * (2ull * b->guide_hw + 1) : (uint64_t)d.T * std::min<uint64_t>(2ull * d.bw + 1, d.N);
     tm.samples += r.S;
   }
   if (calc) {
@@ -592,7 +601,34 @@ int enqueue_job(dyn_batch* b, DynJob job) {
                               hipMemcpyDeviceToHost, a->stream));
     // (Running the per-segment kernels on a stream of their own, beside the next batch's read queue, was measured:
     //  the 0.35 ms gap it closes comes back as a 0.4 ms slower start of that read queue -- same-box A/B, no gain.)
-    if (!wide.empty()) {
+    if (!wide.empty() && b->guided) {
+      // the guided kernel: a queue of its own behind the (empty) read queue, one lattice arena per workgroup (none for Z only)
+      if (pass == 0) {
+        const uint64_t want = 256 + (uint64_t)wide_groups * wide_arena;
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
+        if (want > b->d_garena.bytes && want > (uint64_t)((double)free_b * 0.95)) free_parked(a->device);  // (counted as room above)
+        HIP_TRY(a, b->d_garena.ensure(want));
+        b->arena_bytes = want - 256;
+      }
+      dynk::GuidedArgs ga{};
+      ga.descs = q.descs + n_ok;
+      ga.n_reads = (int)wide.size();
+      ga.bw = (int)b->guide_hw;
+      ga.sig = q.sig;
+      ga.par = q.par;
+      ga.guide = b->d_guide.as<int32_t>();
+      ga.st = q.st;
+      ga.tb = q.tb;
+      ga.head = b->d_garena.as<uint32_t>();
+      ga.arena = b->d_garena.as<char>() + 256;
+      ga.arena_bytes = wide_arena;
+      ga.exp_tab = reinterpret_cast<const uint64_t*>(a->d_sptab.as<dynmath::SoftplusNode>() + dynmath::SP_NODES + dynmath::EXP128_NODES);
+      ga.m1 = m.log_m1;
+      ga.e2 = m.log_e2;
+      ga.z_fail_status = z_fail;
+      HIP_TRY(a, dynk::launch_guided_reads(calc ? 1 : 0, ga, wide_groups, a->stream));
+    } else if (!wide.empty()) {
       // one workgroup per wide read at a time, each with a lattice arena for the largest of them; behind the read queue on the
       // compute stream (its results feed the same per-segment kernels / the same host finalisation)
       if (pass == 0) {
@@ -601,6 +637,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
         HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
         if (want > b->d_wide.bytes && want > (uint64_t)((double)free_b * 0.95)) free_parked(a->device);  // (counted as room above)
         HIP_TRY(a, b->d_wide.ensure(want));
+        b->arena_bytes = want - 256;
       }
       dynk::WideArgs wa{};
       wa.descs = q.descs + n_ok;
@@ -654,10 +691,14 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     const std::vector<dynk::KmerSummary> ks = kmer_summary_args(b);
     // the band margins (likewise once, from the last pass's borders)
     const std::vector<dynk::BandMargin> bm = band_margin_args(b);
+    // (a guided batch's margins are taken against its own window: k_bmargin_guided below, not the diagonal's staircase kernel)
     dynk::launch_segments(q.descs, nr_all, rows_total, max_N, q.st, q.tb, b->d_rows.as<SegRow>(), m.k, a->stream, evc,
-                          ks.empty() ? dynk::KmerSummary{} : ks[0], scc, bm.empty() ? dynk::BandMargin{} : bm[0]);
+                          ks.empty() ? dynk::KmerSummary{} : ks[0], scc, (bm.empty() || b->guided) ? dynk::BandMargin{} : bm[0]);
     for (size_t k = 1; k < ks.size(); ++k) dynk::launch_kmer_summary(q.descs, nr_all, max_N, q.st, q.tb, ks[k], a->stream);
-    for (size_t k = 1; k < bm.size(); ++k) dynk::launch_band_margin(q.descs, nr_all, max_N, q.st, q.tb, bm[k], a->stream);
+    for (size_t k = b->guided ? 0 : 1; k < bm.size(); ++k) {
+      if (b->guided) dynk::launch_guided_band_margin(q.descs, nr_all, b->max_T, q.st, q.tb, b->d_guide.as<int32_t>(), (int)b->guide_hw, bm[k], a->stream);
+      else dynk::launch_band_margin(q.descs, nr_all, max_N, q.st, q.tb, bm[k], a->stream);
+    }
   }
   if (job == DynJob::Train) {
     b->pool_nr = nr_all;

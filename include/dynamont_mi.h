@@ -26,11 +26,13 @@
 extern "C" {
 #endif
 
-#define DYN_ABI_VERSION 10 /* 10 (number kept; look the symbols up): band-margin diagnostics: dyn_aligner_set_band_margin, dyn_batch_fetch_band_margin (additive). 10 (number kept): per-k-mer level summary of a run: dyn_aligner_set_kmer_summary, dyn_aligner_kmer_summary_fetch / _reset (additive). 10: per-read signal rescaling: dyn_aligner_set_rescale, dyn_batch_fetch_rescale (additive). 9: per-segment signal levels: dyn_aligner_set_event_stats, dyn_batch_fetch_events, dyn_format_csv[_bound]_events, dyn_csv_sink_open_ex (additive). 8: dyn_aligner_session_idle_split (additive). 7: dyn_aligner_session_page_wait, dyn_comm_gather_bytes / _gathered_bytes / _allreduce_f64 (additive). 7: half bands 224 .. 2 046 are computed (wide_band.hip). 5: any band constructs (DYN_READ_BAND_TOO_WIDE per read); dyn_bam_*, dyn_csv_sink_wait / _open_part */
+#define DYN_ABI_VERSION 10 /* 10 (number kept; look the symbols up): guided band: dyn_batch_set_guide, dyn_batch_arena_bytes (additive). 10 (number kept; look the symbols up): band-margin diagnostics: dyn_aligner_set_band_margin, dyn_batch_fetch_band_margin (additive). 10 (number kept): per-k-mer level summary of a run: dyn_aligner_set_kmer_summary, dyn_aligner_kmer_summary_fetch / _reset (additive). 10: per-read signal rescaling: dyn_aligner_set_rescale, dyn_batch_fetch_rescale (additive). 9: per-segment signal levels: dyn_aligner_set_event_stats, dyn_batch_fetch_events, dyn_format_csv[_bound]_events, dyn_csv_sink_open_ex (additive). 8: dyn_aligner_session_idle_split (additive). 7: dyn_aligner_session_page_wait, dyn_comm_gather_bytes / _gathered_bytes / _allreduce_f64 (additive). 7: half bands 224 .. 2 046 are computed (wide_band.hip). 5: any band constructs (DYN_READ_BAND_TOO_WIDE per read); dyn_bam_*, dyn_csv_sink_wait / _open_part */
 
 /* device argument of dyn_aligner_create: bind no GPU. Such a handle serves the host-side
- * contract only (model loading, dyn_aligner_info/_model, dyn_validate_batch); every compute
- * entry point fails with DYN_ERR_DEVICE -- there is no CPU compute path in this library. */
+ * contract only (model loading, dyn_aligner_info/_model, dyn_validate_batch, and dyn_batch_create[_raw] as far as the
+ * read table: validation and k-mer coding, nothing uploaded -- what dyn_batch_set_guide's checks need); every compute
+ * entry point (dyn_batch_align / _train, the getters, the asynchronous API) fails with DYN_ERR_DEVICE -- there is no CPU
+ * compute path in this library. */
 #define DYN_DEVICE_HOST_ONLY (-2)
 
 /* dynamont::PoreType (include/dynamont/aligner.hpp:26-33), same numbering as the pybind enum
@@ -673,7 +675,9 @@ void dyn_bam_close(dyn_bam_reader* r);
 
 /* ---- staged form: inputs resident in HBM before the timed region (bench.py, pipelining) ---- */
 
-/* Validate (aligner.cpp:145-164), k-mer-code (aligner.cpp:166-205), and upload one batch. */
+/* Validate (aligner.cpp:145-164), k-mer-code (aligner.cpp:166-205), and upload one batch. On a DYN_DEVICE_HOST_ONLY handle:
+ * validate and k-mer-code only (`signals` is not read); the batch serves dyn_batch_set_guide's validation and
+ * dyn_batch_destroy, every job on it returns DYN_ERR_DEVICE. */
 int dyn_batch_create(dyn_aligner* a, uint64_t n_reads, const double* signals,
                      const uint64_t* sig_offsets, const char* seqs, const uint64_t* seq_offsets,
                      dyn_batch** out);
@@ -721,6 +725,27 @@ int dyn_batch_fetch_rescale(dyn_batch* b, dyn_rescale_out* out);
  * DYN_ERR_INVALID_ARGUMENT + message for a batch submitted with dyn_aligner_set_band_margin off, or aligned with
  * calc_probabilities = 0. */
 int dyn_batch_fetch_band_margin(dyn_batch* b, dyn_band_margin_out* out);
+/* (added within ABI 10) Guided band: the batch's next dyn_batch_align runs every ok read inside a window of `half_width`
+ * lattice columns on either side of a per-sample guide path instead of the band around the fixed diagonal
+ * (INTEGRATION.md section 3). centres[count]: one int32 per signal sample of the batch, read i's at the read's own signal
+ * offset (sig_offsets[i] - sig_offsets[0]); centres of lattice row t >= 1 of a read = its entry t - 1, a lattice column of
+ * 0 .. N - 1 (N = k-mers + 1), never decreasing along a read; row 0 is centred on column 0. half_width: 1 .. 2046, used as
+ * given (not clamped to N / 2). The array is copied to the device before the call returns. A diagonal guide at
+ * half_width = min(band / 2, N / 2) is the unguided band: same bits. A guide whose windows do not connect (0, 0) with
+ * (T - 1, N - 1) costs that read DYN_READ_Z_MISMATCH and no other read anything; a read whose lattice of
+ * 25 * T * (2 half_width + 3) bytes does not fit 0.8 of the free memory (or dyn_aligner_set_mem_budget) gets
+ * DYN_READ_TOO_LARGE. For batches from dyn_batch_create / dyn_batch_create_raw that have not run yet (a batch created on a
+ * DYN_DEVICE_HOST_ONLY handle is validated and nothing else). DYN_ERR_INVALID_ARGUMENT + a message that names the read and
+ * the sample: count differs from the batch's samples, a centre outside [0, N - 1], a decreasing pair, half_width outside
+ * [1, 2046], a batch that has already run, an asynchronous ticket. On a guided batch dyn_batch_train is refused, and so is
+ * dyn_batch_align while dyn_aligner_set_rescale(iters > 0) or dyn_aligner_set_border_confidence(window > 0) is on (both
+ * DYN_ERR_INVALID_ARGUMENT + message); event stats, segment scores, the k-mer summary and the band margins (taken against
+ * the guided window) work. dyn_batch_timing counts T * (2 half_width + 1) cells per read. */
+int dyn_batch_set_guide(dyn_batch* b, const int32_t* centres, uint64_t count, uint32_t half_width);
+/* (added within ABI 10) Device bytes the batch's last job allocated for per-workgroup lattice arenas: workgroups x the largest
+ * read's lattice, for the guided kernel (dyn_batch_set_guide) or the generic wide-band kernel; 0 for a batch whose reads all took
+ * the paged read queue (its pool: dyn_timing.pool_pages) and for a Z-only guided job. */
+int dyn_batch_arena_bytes(const dyn_batch* b, uint64_t* bytes);
 /* Device-resident results of the last dyn_batch_align, for an RCCL gather without a host hop:
  * rows = dyn_segment_row[capacity] (read i at seg_offsets[i], as in dyn_align_out);
  * z_status = per read {double Z; int32 status; uint32 n_segments}. Pointers stay valid until the
