@@ -410,6 +410,13 @@ class Batch:
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
 
+    def train_guided(self) -> None:
+        """dyn_batch_train_guided: ``train()`` inside the guide that ``set_guide`` put on the batch (ValueError without one);
+        the results are fetched with ``fetch_train`` / ``pooled_device`` as after ``train()``."""
+        rc = self._L.dyn_batch_train_guided(self._h)
+        if rc != N.DYN_OK:
+            _raise(rc, self._al.last_error())
+
     def fetch(self, out: AlignBatchResult | None = None) -> AlignBatchResult:
         """Results of the last align(). ``out``: a result object of an earlier batch to refill (same
         number of reads, enough segment capacity) instead of allocating and page-faulting in ~50 MB of
@@ -1130,17 +1137,33 @@ class Aligner:
         window of ``half_width`` columns on either side of it instead of the band around the fixed diagonal. With
         ``set_band_margin(True)`` the three margin fields are taken against that window. Never retried (``set_band_retry``
         applies to ``align_batch``); not together with ``set_rescale`` / ``set_border_confidence`` (ValueError)."""
+        centres = self._guide_centres(signals, guides)
+        with self.batch(signals, sequences) as b:
+            b.set_guide(centres, half_width)
+            b.align(calc_probabilities)
+            return b.fetch()
+
+    @staticmethod
+    def _guide_centres(signals: Sequence, guides: Sequence) -> np.ndarray:
+        """the batch's guide array: one int32 per signal sample, the reads' guides in batch order"""
         if len(guides) != len(signals):
             raise ValueError("signals and guides differ in length")
         parts = [np.ascontiguousarray(g, dtype=np.int32).ravel() for g in guides]
         for i, (g, s) in enumerate(zip(parts, signals)):
             if g.size != len(s):
                 raise ValueError(f"guide {i} holds {g.size} entries for a signal of {len(s)} samples")
-        centres = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
+        return np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
+
+    def train_batch_guided(self, signals: Sequence, sequences: Sequence[str], guides: Sequence, half_width: int,
+                           pooled: bool = False) -> TrainBatchResult:
+        """``train_batch`` inside a guided band: the Baum-Welch statistics of every read over the window of
+        ``align_batch_guided`` (``half_width`` columns on either side of ``guides[i]``) instead of the band around the fixed
+        diagonal. A read whose guide is infeasible fails alone with the training Z-mismatch status."""
+        centres = self._guide_centres(signals, guides)
         with self.batch(signals, sequences) as b:
             b.set_guide(centres, half_width)
-            b.align(calc_probabilities)
-            return b.fetch()
+            b.train_guided()
+            return b.fetch_train(pooled)
 
     def train_batch(self, signals: Sequence, sequences: Sequence[str], pooled: bool = False) -> TrainBatchResult:
         with self.batch(signals, sequences) as b:

@@ -198,6 +198,7 @@ SIGNATURES = {
     "dyn_batch_fetch_rescale": (C.c_int, [C.c_void_p, C.POINTER(DynRescaleOut)]),
     "dyn_batch_fetch_band_margin": (C.c_int, [C.c_void_p, C.POINTER(DynBandMarginOut)]),
     "dyn_batch_set_guide": (C.c_int, [C.c_void_p, c_i32_p, C.c_uint64, C.c_uint32]),
+    "dyn_batch_train_guided": (C.c_int, [C.c_void_p]),
     "dyn_batch_arena_bytes": (C.c_int, [C.c_void_p, c_u64_p]),
     "dyn_batch_fetch_train": (C.c_int, [C.c_void_p, C.POINTER(DynTrainOut), c_double_p]),
     "dyn_batch_device_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_u64_p, C.POINTER(C.c_void_p)]),

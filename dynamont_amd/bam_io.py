@@ -177,7 +177,8 @@ def _bgzf_block(payload: bytes) -> bytes:
 
 def write_bam(path: str, records) -> None:
     """Minimal uBAM writer (tests / synthetic datasets): floats as 'f' (single precision, as dorado
-    writes sm/sd/qs), ints as 'i', strings as 'Z'."""
+    writes sm/sd/qs), ints as 'i', NumPy arrays as 'B' arrays of their own element type (an int8 array is dorado's
+    move table, mv:B:c), strings as 'Z'."""
     enc_lut = np.full(256, 15, dtype=np.uint8)  # anything outside the 16 IUPAC codes is stored as N
     for i, c in enumerate(_SEQ_DECODE):
         enc_lut[ord(c)] = i
@@ -196,6 +197,9 @@ def write_bam(path: str, records) -> None:
                 tagb += k.encode() + b"i" + struct.pack("<i", v)
             elif isinstance(v, float):
                 tagb += k.encode() + b"f" + struct.pack("<f", v)
+            elif isinstance(v, np.ndarray):
+                sub = next(c for c, dt in _TAG_NP.items() if np.dtype(dt) == v.dtype)
+                tagb += k.encode() + b"B" + sub.encode() + struct.pack("<i", v.size) + np.ascontiguousarray(v).tobytes()
             else:
                 tagb += k.encode() + b"Z" + str(v).encode() + b"\0"
         body = struct.pack("<iiBBHHHiiii", -1, -1, len(nm), 0, 4680, 0, 4, len(seq), -1, -1, 0) + nm + packed + b"\xff" * len(seq) + bytes(tagb)

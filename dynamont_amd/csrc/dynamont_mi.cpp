@@ -1033,20 +1033,32 @@ void finalise_train(const dyn_batch* b, const ReadState* st, const double* cw, c
 
 namespace {
 
-int run_job_sync(dyn_batch* b, DynJob job) {
+// guided_train: the call is dyn_batch_train_guided (the one way a Train job reaches a guided batch)
+int run_job_sync(dyn_batch* b, DynJob job, bool guided_train = false) {
   dyn_aligner* a = b->a;
+  if (guided_train) {
+    if (b->async || b->group) {
+      a->last_error = "dyn_batch_train_guided: the batch is an asynchronous ticket; guided training runs on a batch from dyn_batch_create / dyn_batch_create_raw";
+      return DYN_ERR_INVALID_ARGUMENT;
+    }
+    if (!b->guided) {
+      a->last_error = "dyn_batch_train_guided: the batch carries no guide; call dyn_batch_set_guide first (dyn_batch_train trains inside the diagonal band)";
+      return DYN_ERR_INVALID_ARGUMENT;
+    }
+  }
   if (b->async) {
     // An asynchronous ticket is a one-shot submission: its inputs were staged by the pipeline, and when it shared a launch
     // with other tickets it owns neither device buffers nor a read table (dyn_batch.group) -- there is nothing to run again.
     a->last_error = "dyn_batch_align / dyn_batch_train on an asynchronous ticket: submit a new ticket, or use dyn_batch_create";
     return DYN_ERR_INVALID_ARGUMENT;
   }
-  // a guided batch (dyn_batch_set_guide) runs align jobs only, and none that re-aligns or reads the lattice after the traceback
-  if (b->guided && job == DynJob::Train) {
+  // a guided batch (dyn_batch_set_guide) trains through dyn_batch_train_guided only; its align jobs are none that re-align or
+  // read the lattice after the traceback (training does neither: the two switches are align's)
+  if (b->guided && job == DynJob::Train && !guided_train) {
     a->last_error = "dyn_batch_train: the batch carries a guide (dyn_batch_set_guide) and training inside a guided band is not supported";
     return DYN_ERR_INVALID_ARGUMENT;
   }
-  if (b->guided && (a->rescale_iters > 0 || a->border_confidence > 0)) {
+  if (b->guided && job != DynJob::Train && (a->rescale_iters > 0 || a->border_confidence > 0)) {
     a->last_error = std::string("dyn_batch_align: the batch carries a guide (dyn_batch_set_guide), which does not combine with ") +
                     (a->rescale_iters > 0 ? "dyn_aligner_set_rescale(a, iters > 0)" : "dyn_aligner_set_border_confidence(a, window > 0)");
     return DYN_ERR_INVALID_ARGUMENT;
@@ -1083,6 +1095,11 @@ int dyn_batch_align(dyn_batch* b, int calc_probabilities) {
 int dyn_batch_train(dyn_batch* b) {
   if (!b) return DYN_ERR_INVALID_ARGUMENT;
   return run_job_sync(b, DynJob::Train);
+}
+
+int dyn_batch_train_guided(dyn_batch* b) {
+  if (!b) return DYN_ERR_INVALID_ARGUMENT;
+  return run_job_sync(b, DynJob::Train, true);
 }
 
 int dyn_batch_set_guide(dyn_batch* b, const int32_t* centres, uint64_t count, uint32_t half_width) {

@@ -276,7 +276,8 @@ struct dyn_batch {
   dyneng::DevBuf d_wide;        // wide-band reads (wide_band.hip): queue head + one lattice arena per workgroup
   uint64_t n_wide = 0;          // reads of this batch that take the generic kernel
   // guided band (guided_band.hip, dyn_batch_set_guide): every ok read of a guided batch takes the guided kernel, inside a window
-  // of half width guide_hw around its guide; a synchronous batch only, so it never joins a session or a merged launch
+  // of half width guide_hw around its guide (align jobs, and the train job through dyn_batch_train_guided alone); a synchronous
+  // batch only, so it never joins a session or a merged launch
   bool guided = false;
   uint32_t guide_hw = 0;
   dyneng::DevBuf d_guide;       // [samples of the batch] int32 centres (HostRead::sig_off counts from here)

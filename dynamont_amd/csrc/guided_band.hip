@@ -11,6 +11,14 @@
 //               every carve a multiple of 16 B), the per-thread row registers by CPT; shapes of CPT <= 4 are fully unrolled
 //               (registers, no scratch), several workgroups share a CU
 //   Z only      nothing of the lattice is stored: the backward rows live in LDS, no arena
+//   train       (dyn_batch_train_guided) the backward sweep stores bE / bM (16 B per cell, nothing else in the arena); the
+//               forward sweep forms LPM / LPE as the align job does and, instead of posterior-Viterbi and the traceback, adds
+//               g = exp(LPM) + exp(LPE) into the read's per-column sums (w, s1, s2) of TrainBuffers. Scheme: a per-row
+//               read-modify-write of the column sums in global memory -- the lanes of a row own distinct lattice columns and
+//               the row's barrier separates it from the next row, whose owner of a column may be another lane after a shift
+//               of any size. Nothing is held across rows, so there is nothing to flush and no index depends on the shift:
+//               every access is entry n - 1 of a cell's own column n in [1, N). Each column's sum is formed in ascending t,
+//               without atomics: the same bits whichever workgroup takes the read. Two LDS rows (the forward rows) only.
 // A diagonal guide at bw = min(band / 2, N / 2) is the reference's band: the results are the reference's bit for bit.
 #include "guided_band_kernels.hpp"
 
@@ -26,8 +34,9 @@ constexpr uint32_t GBM_NONE = 0xffffffffu;  // DYN_BAND_MARGIN_NONE
 
 __host__ __device__ constexpr int guided_row_stride(int B) { return (B + 1) & ~1; }  // doubles per LDS row: rows stay 16 B aligned
 
-// one read; lds: [STRICT_EXP_WORDS u64 | 4 rows of `stride` doubles | 4 ints]
-template <int THREADS, int CPT, bool CALC>
+// one read; lds: [STRICT_EXP_WORDS u64 | 4 rows (TRAIN: 2) of `stride` doubles | 4 ints]
+// TRAIN: the statistics pass instead of posterior-Viterbi + traceback. CALC: align(calc_probabilities = true).
+template <int THREADS, int CPT, bool CALC, bool TRAIN>
 __device__ void guided_read(const ReadDesc& rd, const GuidedArgs& a, double* __restrict__ bE, double* __restrict__ bM,
                             float* __restrict__ lp, uint8_t* __restrict__ bit, double* s_rows, int stride, const uint64_t* s_exp,
                             int* s_bad) {
@@ -40,8 +49,8 @@ __device__ void guided_read(const ReadDesc& rd, const GuidedArgs& a, double* __r
   const Emis* __restrict__ pr = a.par + rd.par_off;        // entry n - 1 <-> lattice column n
   double* nxE = s_rows;               // backward: row t + 1;  forward: fE of row t - 1
   double* nxM = s_rows + stride;      //                         forward: fM of row t - 1
-  double* pvE = s_rows + 2 * stride;  // forward: vE of row t - 1
-  double* pvM = s_rows + 3 * stride;  // forward: vM of row t - 1
+  double* pvE = TRAIN ? nullptr : s_rows + 2 * stride;  // forward: vE of row t - 1 (TRAIN: no such rows in LDS)
+  double* pvM = TRAIN ? nullptr : s_rows + 3 * stride;  // forward: vM of row t - 1
   if (tid == 0) *s_bad = 0;
   auto at = [&](const double* row, int c) { return (c >= 0 && c < B) ? row[c] : NEG_INF; };  // guard columns and beyond: -inf
   auto centre = [&](int t) { return t > 0 ? (int)gd[t - 1] : 0; };
@@ -56,7 +65,7 @@ __device__ void guided_read(const ReadDesc& rd, const GuidedArgs& a, double* __r
         const double v = (c == c_seed && c >= 1 && c <= 2 * bw + 1) ? 0.0 : NEG_INF;
         nxE[c] = v;
         nxM[c] = NEG_INF;
-        if (CALC) {
+        if (CALC || TRAIN) {
           bE[(size_t)(T - 1) * B + c] = v;
           bM[(size_t)(T - 1) * B + c] = NEG_INF;
         }
@@ -101,7 +110,7 @@ __device__ void guided_read(const ReadDesc& rd, const GuidedArgs& a, double* __r
       if (c < B) {
         nxE[c] = oE[k];
         nxM[c] = oM[k];
-        if (CALC) {
+        if (CALC || TRAIN) {
           bE[(size_t)t * B + c] = oE[k];
           bM[(size_t)t * B + c] = oM[k];
         }
@@ -122,9 +131,19 @@ __device__ void guided_read(const ReadDesc& rd, const GuidedArgs& a, double* __r
       const double v = (c == bw + 1) ? 0.0 : NEG_INF;  // (0, 0)
       nxE[c] = v;
       nxM[c] = NEG_INF;
-      pvE[c] = v;
-      pvM[c] = NEG_INF;
+      if (!TRAIN) {
+        pvE[c] = v;
+        pvM[c] = NEG_INF;
+      }
     }
+  }
+  // TRAIN: the read's column sums start at 0 (entry n - 1 <-> lattice column n, N - 1 entries). Not __restrict__: a column's
+  // word is written by one lane and read by another in the next row
+  double* cw = TRAIN ? a.tr.col_w + rd.par_off : nullptr;
+  double* cs1 = TRAIN ? a.tr.col_s1 + rd.par_off : nullptr;
+  double* cs2 = TRAIN ? a.tr.col_s2 + rd.par_off : nullptr;
+  if (TRAIN) {
+    for (int n = tid; n < N - 1; n += THREADS) cw[n] = cs1[n] = cs2[n] = 0.0;
   }
   __syncthreads();
   int start_prev = -bw;
@@ -134,7 +153,7 @@ __device__ void guided_read(const ReadDesc& rd, const GuidedArgs& a, double* __r
     const int shift = start - start_prev;  // >= 0
     start_prev = start;
     const double x = sg[t - 1];
-    double ofE[CPT], ofM[CPT], ovE[CPT], ovM[CPT];
+    double ofE[CPT], ofM[CPT], ovE[CALC ? CPT : 1], ovM[CALC ? CPT : 1];
 #pragma unroll UNROLL
     for (int k = 0; k < CPT; ++k) {
       const int c = tid + k * THREADS;
@@ -146,7 +165,16 @@ __device__ void guided_read(const ReadDesc& rd, const GuidedArgs& a, double* __r
           const double score = dynmath::log_normal_pdf_strict(x, pr[n - 1]);
           fM = (at(nxE, cp - 1) + score) + m1;
           fE = dynmath::log_plus_strict((at(nxM, cp) + score) + 0.0, (at(nxE, cp) + score) + e2, s_exp);
-          if (CALC) {
+          if (TRAIN) {
+            // n in [max(start, 1), min(centre + bw + 1, N)): entry n - 1 lies in the read's N - 1 entries whatever the shift.
+            // This lane alone owns column n in this row; the barrier below orders it against the next row's owner.
+            const size_t cell = (size_t)t * B + c;
+            const double LPM = (fM + bM[cell]) - Zb, LPE = (fE + bE[cell]) - Zb;
+            const double g = exp(LPM) + exp(LPE);
+            cw[n - 1] += g;
+            cs1[n - 1] += g * x;
+            cs2[n - 1] += (g * x) * x;
+          } else if (CALC) {
             const size_t cell = (size_t)t * B + c;
             const double LPM = (fM + bM[cell]) - Zb, LPE = (fE + bE[cell]) - Zb;
             vM = at(pvE, cp - 1) + LPM;
@@ -160,8 +188,10 @@ __device__ void guided_read(const ReadDesc& rd, const GuidedArgs& a, double* __r
       }
       ofE[k] = fE;
       ofM[k] = fM;
-      ovE[k] = vE;
-      ovM[k] = vM;
+      if (CALC) {
+        ovE[k] = vE;
+        ovM[k] = vM;
+      }
     }
     __syncthreads();
 #pragma unroll UNROLL
@@ -222,6 +252,11 @@ __device__ void guided_read(const ReadDesc& rd, const GuidedArgs& a, double* __r
     if (*s_bad == 2) status = 7;  // DYN_READ_INTERNAL
     else n_seg = rd.N - 1;
   }
+  if (TRAIN && tid == 0 && ok) {
+    // expected transition counts: every path makes N - 1 moves and T - 1 - 2 (N - 1) extensions
+    a.tr.trans[2 * rd.read] = (double)(N - 1);
+    a.tr.trans[2 * rd.read + 1] = (double)(T - 1 - 2 * (N - 1));
+  }
   if (tid == 0) {
     ReadState s;
     s.Zb = Zb;
@@ -235,14 +270,14 @@ __device__ void guided_read(const ReadDesc& rd, const GuidedArgs& a, double* __r
 
 }  // namespace
 
-// one workgroup takes reads off a queue until it is empty; its lattice arena (job 1) holds one read at a time
-template <int THREADS, int CPT, bool CALC>
+// one workgroup takes reads off a queue until it is empty; its lattice arena (jobs 1 and 2) holds one read at a time
+template <int THREADS, int CPT, bool CALC, bool TRAIN>
 __global__ __launch_bounds__(THREADS) void k_guided_reads(const GuidedArgs a) {
   extern __shared__ __attribute__((aligned(16))) char g_lds[];
   const int stride = guided_row_stride(2 * a.bw + 3);
   uint64_t* s_exp = reinterpret_cast<uint64_t*>(g_lds);
   double* s_rows = reinterpret_cast<double*>(g_lds + dynmath::STRICT_EXP_WORDS * 8);
-  int* s_ctl = reinterpret_cast<int*>(s_rows + 4 * stride);  // [0] next read, [1] s_bad
+  int* s_ctl = reinterpret_cast<int*>(s_rows + (TRAIN ? 2 : 4) * stride);  // [0] next read, [1] s_bad
   for (int i = threadIdx.x; i < dynmath::STRICT_EXP_WORDS; i += THREADS) s_exp[i] = a.exp_tab[i];
   char* arena = a.arena + (size_t)blockIdx.x * a.arena_bytes;
   for (;;) {
@@ -257,7 +292,7 @@ __global__ __launch_bounds__(THREADS) void k_guided_reads(const GuidedArgs a) {
     double* bM = bE + cells;
     float* lp = reinterpret_cast<float*>(bM + cells);
     uint8_t* bit = reinterpret_cast<uint8_t*>(lp + 2 * cells);
-    guided_read<THREADS, CPT, CALC>(rd, a, bE, bM, lp, bit, s_rows, stride, s_exp, s_ctl + 1);
+    guided_read<THREADS, CPT, CALC, TRAIN>(rd, a, bE, bM, lp, bit, s_rows, stride, s_exp, s_ctl + 1);
   }
 }
 
@@ -316,10 +351,10 @@ void launch_guided_band_margin(const ReadDesc* descs, int n_reads, uint32_t max_
                      tb.segrow, guide, bw, bm);
 }
 
-uint64_t guided_arena_bytes(uint64_t T, uint64_t bw, bool calc) {
-  if (!calc) return 0;
+uint64_t guided_arena_bytes(uint64_t T, uint64_t bw, int job) {
+  if (job == 0) return 0;
   const uint64_t cells = T * (2 * bw + 3);
-  return (cells * 25 + 255) & ~255ull;  // bE, bM doubles; (float LPM, float LPE); one byte per decision
+  return (cells * (job == 2 ? 16 : 25) + 255) & ~255ull;  // bE, bM doubles; align: (float LPM, float LPE), one byte per decision
 }
 
 namespace {
@@ -336,35 +371,39 @@ const Shape& shape_of(int bw) {
     if (B <= s.threads * s.cpt) return s;
   return SHAPES[2];
 }
-size_t lds_bytes(int bw) {
-  return (size_t)dynmath::STRICT_EXP_WORDS * 8 + 4 * (size_t)guided_row_stride(2 * bw + 3) * 8 + 16;
+size_t lds_bytes(int bw, int job) {  // the train job keeps the two forward rows only
+  return (size_t)dynmath::STRICT_EXP_WORDS * 8 + (job == 2 ? 2 : 4) * (size_t)guided_row_stride(2 * bw + 3) * 8 + 16;
 }
 template <int THREADS, int CPT>
 hipError_t launch_shape(int job, const GuidedArgs& a, int n_groups, size_t lds, hipStream_t s) {
   if (lds > 48 * 1024) {  // (a wide window: the request exceeds the default dynamic-LDS limit)
-    const void* fn = job == 1 ? reinterpret_cast<const void*>(&k_guided_reads<THREADS, CPT, true>)
-                              : reinterpret_cast<const void*>(&k_guided_reads<THREADS, CPT, false>);
+    const void* fn = job == 2   ? reinterpret_cast<const void*>(&k_guided_reads<THREADS, CPT, false, true>)
+                     : job == 1 ? reinterpret_cast<const void*>(&k_guided_reads<THREADS, CPT, true, false>)
+                                : reinterpret_cast<const void*>(&k_guided_reads<THREADS, CPT, false, false>);
     const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  if (job == 1) hipLaunchKernelGGL((k_guided_reads<THREADS, CPT, true>), dim3(n_groups), dim3(THREADS), lds, s, a);
-  else hipLaunchKernelGGL((k_guided_reads<THREADS, CPT, false>), dim3(n_groups), dim3(THREADS), lds, s, a);
+  if (job == 2) hipLaunchKernelGGL((k_guided_reads<THREADS, CPT, false, true>), dim3(n_groups), dim3(THREADS), lds, s, a);
+  else if (job == 1) hipLaunchKernelGGL((k_guided_reads<THREADS, CPT, true, false>), dim3(n_groups), dim3(THREADS), lds, s, a);
+  else hipLaunchKernelGGL((k_guided_reads<THREADS, CPT, false, false>), dim3(n_groups), dim3(THREADS), lds, s, a);
   return hipGetLastError();
 }
 }  // namespace
 
 // as many workgroups as a CU's 160 KiB of LDS and its registers hold beside each other
-int guided_groups_per_cu(int bw) {
-  const int by_lds = (int)((150 * 1024) / lds_bytes(bw));
+int guided_groups_per_cu(int bw, int job) {
+  const int by_lds = (int)((150 * 1024) / lds_bytes(bw, job));
   const int by_waves = shape_of(bw).groups;
   return by_lds < 1 ? 1 : by_lds < by_waves ? by_lds : by_waves;
 }
 
 hipError_t launch_guided_reads(int job, const GuidedArgs& a, int n_groups, hipStream_t s) {
   if (a.n_reads <= 0 || n_groups <= 0) return hipSuccess;
-  if (a.bw < 1 || a.bw > WIDE_MAX_HALF_BAND) return hipErrorInvalidValue;
+  if (a.bw < 1 || a.bw > WIDE_MAX_HALF_BAND || job < 0 || job > 2) return hipErrorInvalidValue;
+  if (job == 2 && !(a.tr.col_w && a.tr.col_s1 && a.tr.col_s2 && a.tr.trans)) return hipErrorInvalidValue;
+  if (job != 0 && !a.arena) return hipErrorInvalidValue;
   if (const hipError_t e = hipMemsetAsync(a.head, 0, 4, s)) return e;
-  const size_t lds = lds_bytes(a.bw);
+  const size_t lds = lds_bytes(a.bw, job);
   const Shape& sh = shape_of(a.bw);
   if (sh.cpt == 1) return launch_shape<64, 1>(job, a, n_groups, lds, s);
   if (sh.threads == 64) return launch_shape<64, 4>(job, a, n_groups, lds, s);

@@ -22,7 +22,8 @@ struct GuidedArgs {
   const int32_t* guide;    // [samples of the batch]: ReadDesc::sig_off counts from here, as it does into sig
   ReadState* st;
   TraceBuffers tb;
-  char* arena;             // n_groups arenas of arena_bytes: the lattice of the read a workgroup is working on (job 1 only)
+  TrainBuffers tr;         // job 2 only: the read's column sums at col_* + ReadDesc::par_off, trans[2 * read]
+  char* arena;             // n_groups arenas of arena_bytes: the lattice of the read a workgroup is working on (jobs 1 and 2)
   uint64_t arena_bytes;    // >= guided_arena_bytes of the largest read
   uint32_t* head;          // queue head (cleared by launch_guided_reads)
   const uint64_t* exp_tab; // dynmath::strict_exp_table on the device
@@ -31,12 +32,14 @@ struct GuidedArgs {
 };
 
 // bytes of lattice one workgroup needs for a read of T rows: 25 B per band slot with probabilities (bE, bM doubles; float LPM,
-// float LPE; one decision byte), nothing for the Z-only job (its backward rows never leave LDS)
-uint64_t guided_arena_bytes(uint64_t T, uint64_t bw, bool calc);
+// float LPE; one decision byte), 16 B for the train job (bE, bM), nothing for the Z-only job (its backward rows never leave
+// LDS). job as launch_guided_reads takes it.
+uint64_t guided_arena_bytes(uint64_t T, uint64_t bw, int job);
 // the most workgroups per compute unit the shape chosen for this half width is launched with (an upper bound: it limits the
 // arenas a launch allocates)
-int guided_groups_per_cu(int bw);
-// job: 0 = Z only, 1 = align(calc_probabilities = true) up to the per-row path arrays (launch_segments follows). Returns what
+int guided_groups_per_cu(int bw, int job);
+// job: 0 = Z only, 1 = align(calc_probabilities = true) up to the per-row path arrays (launch_segments follows), 2 = train:
+// the read's (w, s1, s2) column sums and transition counts in GuidedArgs::tr (finalise_train / pool_stats follow). Returns what
 // raising the dynamic-LDS limit (windows above 48 KiB of rows) or the launch reported.
 hipError_t launch_guided_reads(int job, const GuidedArgs& a, int n_groups, hipStream_t s);
 

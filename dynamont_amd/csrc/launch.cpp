@@ -229,6 +229,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   const bool calc = job == DynJob::AlignFull;
   const PoreModel& m = a->model;
   const int z_fail = job == DynJob::Train ? DYN_READ_TRAIN_Z_MISMATCH : DYN_READ_Z_MISMATCH;
+  const int guided_job = job == DynJob::Train ? 2 : calc ? 1 : 0;  // launch_guided_reads' job
 
   // mode "resquiggle"/"ntk": what the reference's NTKAligner does in this snapshot, as observed with the compiled
   // reference (tests/golden/g11_ntk_messages.json): validateInput / sequenceToKmers errors first, then EVERY read fails
@@ -471,7 +472,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     size_t wr = 0;
     for (uint32_t i : wide) {
       const HostRead& r = b->reads[i];
-      const uint64_t need = b->guided ? dynk::guided_arena_bytes(r.S + 1, b->guide_hw, calc)
+      const uint64_t need = b->guided ? dynk::guided_arena_bytes(r.S + 1, b->guide_hw, guided_job)
                                       : dynk::wide_arena_bytes(r.S + 1, std::min<uint64_t>(m.half_band, (r.kc + 1) / 2), calc);
       if (need > room) st[i].status = DYN_READ_TOO_LARGE;
       else {
@@ -484,7 +485,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       if (b->n) HIP_TRY(a, hipMemcpyAsync(b->d_state.p, st, b->n * sizeof(ReadState), hipMemcpyHostToDevice, a->stream));
     }
     if (!wide.empty() && b->guided)
-      wide_groups = (int)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)wide.size(), (uint64_t)a->n_cus * (uint64_t)dynk::guided_groups_per_cu((int)b->guide_hw),
+      wide_groups = (int)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)wide.size(), (uint64_t)a->n_cus * (uint64_t)dynk::guided_groups_per_cu((int)b->guide_hw, guided_job),
                                                                    wide_arena ? room / wide_arena : ~0ull}));
     else if (!wide.empty()) wide_groups = (int)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)wide.size(), (uint64_t)a->n_cus, room / wide_arena}));
   }
@@ -620,6 +621,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       ga.guide = b->d_guide.as<int32_t>();
       ga.st = q.st;
       ga.tb = q.tb;
+      ga.tr = q.tr;
       ga.head = b->d_garena.as<uint32_t>();
       ga.arena = b->d_garena.as<char>() + 256;
       ga.arena_bytes = wide_arena;
@@ -627,7 +629,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       ga.m1 = m.log_m1;
       ga.e2 = m.log_e2;
       ga.z_fail_status = z_fail;
-      HIP_TRY(a, dynk::launch_guided_reads(calc ? 1 : 0, ga, wide_groups, a->stream));
+      HIP_TRY(a, dynk::launch_guided_reads(guided_job, ga, wide_groups, a->stream));
     } else if (!wide.empty()) {
       // one workgroup per wide read at a time, each with a lattice arena for the largest of them; behind the read queue on the
       // compute stream (its results feed the same per-segment kernels / the same host finalisation)

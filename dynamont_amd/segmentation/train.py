@@ -16,6 +16,10 @@ Deliberate differences from the reference (not silently 
     (utils.py:171-175), which mislabels RNA models;
   * as in the reference, updated TRANSITIONS are logged but never reach the native aligner
     (no setter exists, aligner_bindings.cpp:191-216): every read trains with the pore defaults.
+
+``--guide-moves HW`` (build-only, default 0 = off): every read is trained, and its Z re-evaluated, inside a window of HW
+lattice columns around the guide its basecaller move table (``mv:B:c``) gives (``Aligner.train_batch_guided``, INTEGRATION.md
+section 3) instead of the band around the fixed diagonal; a read without a usable move table is skipped and counted.
 """
 from __future__ import annotations
 
@@ -29,6 +33,7 @@ from os.path import basename, dirname, exists, join
 import numpy as np
 
 from dynamont_amd import Aligner, __version__
+from dynamont_amd import guide as guide_mod
 from dynamont_amd.pod5_io import get_signal, iter_basecalls, open_pod5
 from dynamont_amd.segmentation.utils import (cnt_nts_ratios, get_model, hampel, kmer_of_code, read_kmer_model,
                                              write_kmer_model, write_kmer_model_arrays)
@@ -103,6 +108,9 @@ def parse(argv=None) -> Namespace:
     p.add_argument("--reference-zcheck", action="store_true",
                    help="also refuse the reads the reference's |Zf - Zb| / size > 1e-8 rule refuses (NT_aligner_api.cpp:619-625): "
                         "one more Z-only forward sweep per read; default: the posterior chain's own mass check")
+    p.add_argument("--guide-moves", type=int, default=0, metavar="HW",
+                   help="train inside a window of HW lattice columns on either side of the guide the basecaller's move table "
+                        "(mv:B:c) gives, instead of the band around the diagonal; reads without a move table are skipped (0: off)")
     return p.parse_args(argv)
 
 
@@ -114,11 +122,25 @@ def _code_order(model: dict, k: int, rna: bool):
     return names, mean, sd
 
 
-def read_items(data_path, basecalls, pore, minq, raw: bool = False):
+def _move_guide(rec, n_samples: int, n_bases: int, k: int):
+    """the read's guide from its ``mv`` tag, or None: no tag, no move in the table, or a sequence shorter than a k-mer. The
+    signal starts at sp + ts, where the move table begins (ts = 0 for guide_from_moves); the sequence is the aligner's (RNA:
+    reversed into signal order and padded, so reverse=False -- INTEGRATION.md section 3's orientation rule)."""
+    if not rec.has_tag("mv"):
+        return None
+    try:
+        return guide_mod.guide_from_moves(rec.get_tag("mv"), n_samples, n_bases, k, ts=0, reverse=False)
+    except ValueError:
+        return None
+
+
+def read_items(data_path, basecalls, pore, minq, raw: bool = False, guide_moves: int = 0, k: int = 0):
     """Read filters + preprocessing of train.py:125-176, one item per accepted read:
     (signal, sequence, readid). With ``raw=True`` the arithmetic is left to the device and the item
     is ((raw float32 slice, shift, scale), sequence, readid) for ``Aligner.batch_raw(..., window=7,
-    n_sigmas=5.0, f32=True)``."""
+    n_sigmas=5.0, f32=True)``. With ``guide_moves`` > 0 (``k``: the model's k-mer size) an item carries a fourth entry, the
+    read's int32 guide from its move table (one lattice column per sample of the cut signal), and a read without a usable
+    table yields "noguide"."""
     old_file, r5 = None, None
     for rec in iter_basecalls(basecalls):
         if minq and rec.get_tag("qs") < minq:
@@ -145,43 +167,67 @@ def read_items(data_path, basecalls, pore, minq, raw: bool = False):
             seq = seq[::-1]
             if not seq.startswith("AAAAAAAAA"):
                 seq = "AAAAAAAAA" + seq
+        extra = ()
+        if guide_moves > 0:  # after the reversal and the pad: the guide is over the aligner's own sequence
+            g = _move_guide(rec, len(signal), len(seq), k)
+            if g is None:
+                yield "noguide"
+                continue
+            extra = (g,)
         if raw:
-            yield ((signal, float(shift), float(scale)), seq, readid)
+            yield ((signal, float(shift), float(scale)), seq, readid) + extra
             continue
         signal -= shift   # float32 arithmetic when the reader returns float32, as in train.py:168-169
         signal /= scale
         hampel(signal, 7, 5.0)
-        yield (signal, seq, readid)
+        yield (signal, seq, readid) + extra
 
 
-def _train_items(al: Aligner, items, pooled: bool, raw: bool):
+def _train_items(al: Aligner, items, pooled: bool, raw: bool, guide_moves: int = 0):
+    """guide_moves > 0: the items carry their guides (read_items) and the batch trains inside them"""
     if not raw:
+        if guide_moves > 0:
+            return al.train_batch_guided([x[0] for x in items], [x[1] for x in items], [x[3] for x in items], guide_moves, pooled=pooled)
         return al.train_batch([x[0] for x in items], [x[1] for x in items], pooled=pooled)
     f32 = items[0][0][0].dtype == np.float32
     with al.batch_raw([x[0][0] for x in items], [x[1] for x in items], [x[0][1] for x in items],
                       [x[0][2] for x in items], window=7, n_sigmas=5.0, f32=f32) as b:
-        b.train()
+        if guide_moves > 0:
+            b.set_guide(np.concatenate([x[3] for x in items]), guide_moves)
+            b.train_guided()
+        else:
+            b.train()
         return b.fetch_train(pooled)
 
 
-def _z_items(al: Aligner, items, raw: bool):
+def _z_items(al: Aligner, items, raw: bool, guide_moves: int = 0):
+    """guide_moves > 0: the guided Z-only job over the same guides, so that the Z change compares like with like"""
     if not raw:
+        if guide_moves > 0:
+            return al.align_batch_guided([x[0] for x in items], [x[1] for x in items], [x[3] for x in items], guide_moves,
+                                         calc_probabilities=False)
         return al.align_batch([x[0] for x in items], [x[1] for x in items], calc_probabilities=False)
     f32 = items[0][0][0].dtype == np.float32
     with al.batch_raw([x[0][0] for x in items], [x[1] for x in items], [x[0][1] for x in items],
                       [x[0][2] for x in items], window=7, n_sigmas=5.0, f32=f32) as b:
+        if guide_moves > 0:
+            b.set_guide(np.concatenate([x[3] for x in items]), guide_moves)
         b.align(False)
         return b.fetch()
 
 
 def train(data_path: str, basecalls: str, batch_size: int, epochs: int, param_file: str, mode: str, model_path: str,
           max_batches, pore: str, minq=None, device: int = 0, aggregate: str = "window-mean", comm=None,
-          host_preprocess: bool = False, reference_zcheck: bool = False) -> None:
+          host_preprocess: bool = False, reference_zcheck: bool = False, guide_moves: int = 0) -> None:
     """Counterpart of train.py:68-253. ``comm`` (optional, dynamont_amd.parallel.Comm): multi-GPU
     run -- accepted reads are dealt round-robin to the ranks (each rank fills ``batch_size`` reads of
     its own per batch, so all ranks reach a batch boundary on the same read), the pooled sufficient
     statistics, transition counts and Z changes are summed over ranks, every rank computes the same
-    model, and rank 0 owns params.csv and the model files in ``outdir``."""
+    model, and rank 0 owns params.csv and the model files in ``outdir``. ``guide_moves`` > 0: the guided band around every
+    read's move-table guide at that half width (the guide travels with its item, so a rank trains the reads it is dealt with
+    their own guides; run with one rank so far)."""
+    if guide_moves < 0:
+        raise ValueError("--guide-moves must be >= 0")
     if mode != "basic":
         print(f"Mode {mode} not implemented", file=sys.stderr)
         sys.exit(1)
@@ -208,12 +254,15 @@ def train(data_path: str, basecalls: str, batch_size: int, epochs: int, param_fi
     trans = {p: ManagedList([v]) for p, v in transition_params.items()}
     any_seen = False
     al = None
-    i = qskips = mismatches = 0
+    i = qskips = mismatches = noguides = 0
     with open(param_file, "w") as pw:
         pw.write("epoch,batch,read," + "".join(p + "," for p in transition_params) + "Zchange\n")
         for e in range(epochs):
             items, cbatch, accepted = [], 0, 0
-            for it in read_items(data_path, basecalls, pore, minq, raw=not host_preprocess):
+            for it in read_items(data_path, basecalls, pore, minq, raw=not host_preprocess, guide_moves=guide_moves, k=k):
+                if it == "noguide":
+                    noguides += 1
+                    continue
                 if it == "qskip":
                     qskips += 1
                     continue
@@ -234,9 +283,9 @@ def train(data_path: str, basecalls: str, batch_size: int, epochs: int, param_fi
                     al = Aligner(trained_model, pore, mode="basic", threads=4, band=400, device=device)
                     al.set_train_zcheck(reference_zcheck)
                 cur_mean, cur_sd = al.model_table()
-                res = _train_items(al, items, aggregate == "pooled", raw=not host_preprocess)
+                res = _train_items(al, items, aggregate == "pooled", raw=not host_preprocess, guide_moves=guide_moves)
                 preZ = {}
-                for j, (_, _, readid) in enumerate(items):
+                for j, readid in enumerate(x[2] for x in items):
                     if res.status[j] != 0:
                         print(f"error: native, {res.error(j)} T: {len(items[j][0][0] if not host_preprocess else items[j][0])} N: {len(items[j][1])} Sid: {readid}", file=sys.stderr)
                         print(f"No segmentation calculated for {readid} in {e}: {trained_model}.", file=sys.stderr)
@@ -292,7 +341,7 @@ def train(data_path: str, basecalls: str, batch_size: int, epochs: int, param_fi
                 pw.flush()
                 # rerun with the new model to compare Zs (train.py:226-242)
                 al.set_model(new_mean, new_sd)  # = Aligner(trained_model, ...) of train.py:227
-                post = _z_items(al, items, raw=not host_preprocess)
+                post = _z_items(al, items, raw=not host_preprocess, guide_moves=guide_moves)
                 dZ = np.array([float(post.Z[j]) - z for j, z in preZ.items() if post.status[j] == 0])
                 print(f"Z changes: {dZ}", file=sys.stderr)
                 if comm is not None:
@@ -308,6 +357,9 @@ def train(data_path: str, basecalls: str, batch_size: int, epochs: int, param_fi
     train._i_global = 0
     print("Done training", file=sys.stderr)
     print(f"Skipped reads due to low quality: {qskips}", file=sys.stderr)
+    if guide_moves > 0:
+        print(f"Skipped reads due to a signal mismatch: {mismatches}", file=sys.stderr)
+        print(f"Skipped reads without a move table (mv): {noguides}", file=sys.stderr)
 
 
 def main(argv=None) -> None:
@@ -334,7 +386,7 @@ def main(argv=None) -> None:
     with parallel.abort_on_error(comm):
         train(args.raw, args.basecalls, args.batch_size, args.epochs, param_file, "basic", model_path, args.max_batches,
               args.pore, args.qscore, device=local_rank if comm else args.device, aggregate=args.aggregate, comm=comm,
-              host_preprocess=args.host_preprocess, reference_zcheck=args.reference_zcheck)
+              host_preprocess=args.host_preprocess, reference_zcheck=args.reference_zcheck, guide_moves=args.guide_moves)
         if comm is not None:
             comm.close()  # (collective: every rank has finished its exchanges)
 

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DYN_ABI_VERSION 10 /* 10 (number kept; look the symbols up): guided band: dyn_batch_set_guide, dyn_batch_arena_bytes (additive). 10 (number kept; look the symbols up): band-margin diagnostics: dyn_aligner_set_band_margin, dyn_batch_fetch_band_margin (additive). 10 (number kept): per-k-mer level summary of a run: dyn_aligner_set_kmer_summary, dyn_aligner_kmer_summary_fetch / _reset (additive). 10: per-read signal rescaling: dyn_aligner_set_rescale, dyn_batch_fetch_rescale (additive). 9: per-segment signal levels: dyn_aligner_set_event_stats, dyn_batch_fetch_events, dyn_format_csv[_bound]_events, dyn_csv_sink_open_ex (additive). 8: dyn_aligner_session_idle_split (additive). 7: dyn_aligner_session_page_wait, dyn_comm_gather_bytes / _gathered_bytes / _allreduce_f64 (additive). 7: half bands 224 .. 2 046 are computed (wide_band.hip). 5: any band constructs (DYN_READ_BAND_TOO_WIDE per read); dyn_bam_*, dyn_csv_sink_wait / _open_part */
+#define DYN_ABI_VERSION 10 /* 10 (number kept; look the symbol up): guided-band training: dyn_batch_train_guided (additive). 10 (number kept; look the symbols up): guided band: dyn_batch_set_guide, dyn_batch_arena_bytes (additive). 10 (number kept; look the symbols up): band-margin diagnostics: dyn_aligner_set_band_margin, dyn_batch_fetch_band_margin (additive). 10 (number kept): per-k-mer level summary of a run: dyn_aligner_set_kmer_summary, dyn_aligner_kmer_summary_fetch / _reset (additive). 10: per-read signal rescaling: dyn_aligner_set_rescale, dyn_batch_fetch_rescale (additive). 9: per-segment signal levels: dyn_aligner_set_event_stats, dyn_batch_fetch_events, dyn_format_csv[_bound]_events, dyn_csv_sink_open_ex (additive). 8: dyn_aligner_session_idle_split (additive). 7: dyn_aligner_session_page_wait, dyn_comm_gather_bytes / _gathered_bytes / _allreduce_f64 (additive). 7: half bands 224 .. 2 046 are computed (wide_band.hip). 5: any band constructs (DYN_READ_BAND_TOO_WIDE per read); dyn_bam_*, dyn_csv_sink_wait / _open_part */
 
 /* device argument of dyn_aligner_create: bind no GPU. Such a handle serves the host-side
  * contract only (model loading, dyn_aligner_info/_model, dyn_validate_batch, and dyn_batch_create[_raw] as far as the
@@ -737,14 +737,25 @@ int dyn_batch_fetch_band_margin(dyn_batch* b, dyn_band_margin_out* out);
  * DYN_READ_TOO_LARGE. For batches from dyn_batch_create / dyn_batch_create_raw that have not run yet (a batch created on a
  * DYN_DEVICE_HOST_ONLY handle is validated and nothing else). DYN_ERR_INVALID_ARGUMENT + a message that names the read and
  * the sample: count differs from the batch's samples, a centre outside [0, N - 1], a decreasing pair, half_width outside
- * [1, 2046], a batch that has already run, an asynchronous ticket. On a guided batch dyn_batch_train is refused, and so is
+ * [1, 2046], a batch that has already run, an asynchronous ticket. On a guided batch dyn_batch_train is refused (the guided
+ * training job is a call of its own, dyn_batch_train_guided), and so is
  * dyn_batch_align while dyn_aligner_set_rescale(iters > 0) or dyn_aligner_set_border_confidence(window > 0) is on (both
  * DYN_ERR_INVALID_ARGUMENT + message); event stats, segment scores, the k-mer summary and the band margins (taken against
  * the guided window) work. dyn_batch_timing counts T * (2 half_width + 1) cells per read. */
 int dyn_batch_set_guide(dyn_batch* b, const int32_t* centres, uint64_t count, uint32_t half_width);
+/* (added within ABI 10) dyn_batch_train inside the guide that dyn_batch_set_guide put on the batch */
+int dyn_batch_train_guided(dyn_batch* b);
+/* The Baum-Welch statistics of every ok read over the cells of the guided window (the window of the guided dyn_batch_align,
+ * INTEGRATION.md section 3): per lattice column the sums w, s1, s2 of g = exp(LPM) + exp(LPE), g x, (g x) x, each formed in
+ * ascending row order without atomics (the same bits run to run, whatever the launch), and the transition counts N - 1 and
+ * T - 1 - 2 (N - 1). Results are fetched as after dyn_batch_train (dyn_batch_fetch_train, dyn_batch_pooled_device). A read
+ * whose guide is infeasible gets DYN_READ_TRAIN_Z_MISMATCH alone; a read whose 16 * T * (2 half_width + 3) bytes of lattice do
+ * not fit gets DYN_READ_TOO_LARGE. DYN_ERR_INVALID_ARGUMENT + message: NULL, a batch without a guide, an asynchronous ticket.
+ * dyn_aligner_set_rescale and dyn_aligner_set_border_confidence are align's switches and are ignored, as dyn_batch_train
+ * ignores them. */
 /* (added within ABI 10) Device bytes the batch's last job allocated for per-workgroup lattice arenas: workgroups x the largest
  * read's lattice, for the guided kernel (dyn_batch_set_guide) or the generic wide-band kernel; 0 for a batch whose reads all took
- * the paged read queue (its pool: dyn_timing.pool_pages) and for a Z-only guided job. */
+ * the paged read queue (its pool: dyn_timing.pool_pages) and for a Z-only guided job; 16 B per cell for dyn_batch_train_guided. */
 int dyn_batch_arena_bytes(const dyn_batch* b, uint64_t* bytes);
 /* Device-resident results of the last dyn_batch_align, for an RCCL gather without a host hop:
  * rows = dyn_segment_row[capacity] (read i at seg_offsets[i], as in dyn_align_out);
