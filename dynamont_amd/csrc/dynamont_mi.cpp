@@ -367,6 +367,12 @@ int dyn_aligner_create(const char* model_path, int pore, const char* mode, int t
   if (trace_create) std::fprintf(stderr, "[dyn] create: HIP runtime up (hipSetDevice) at %.1f ms\n", tc_ms());
   if ((e = hipDeviceGetAttribute(&a->n_cus, hipDeviceAttributeMultiprocessorCount, device)) != hipSuccess) return fail(e, "hipDeviceGetAttribute");
   if (const char* f = std::getenv("DYN_QUEUE_CUS")) a->n_cus = std::max(1, std::atoi(f));  // experiments: fewer persistent workgroups
+  if (const char* f = std::getenv("DYN_LPE_STORE_FLOOR")) {  // debugging: a dense control run, or a floor that reaches path cells
+    char* end = nullptr;
+    const float v = std::strtof(f, &end);
+    if (std::string(f) == "dense") a->lpe_dense = true;
+    else if (end != f && *end == '\0' && !(v != v)) a->lpe_floor = v;
+  }
   if ((e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
   if ((e = hipStreamCreateWithFlags(&a->s_in, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
   if ((e = hipStreamCreateWithFlags(&a->s_out, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");

@@ -146,6 +146,10 @@ struct dyn_aligner {
   uint64_t mem_budget = 0;
   int strict_mode = 1;  // dyn_aligner_set_strict: reads with a structural tie run bit for bit by default
   bool train_zcheck = false;  // dyn_aligner_set_train_zcheck
+  // DYN_LPE_STORE_FLOOR, read once when the handle is created (debugging): `dense`, or the floor below which the forward
+  // sweep does not store a lane group's float LPE (lpe_liveness.hpp)
+  float lpe_floor = -750.0f;
+  bool lpe_dense = false;
   bool event_stats = false;   // dyn_aligner_set_event_stats: read by every batch / ticket at its submission
   int rescale_iters = 0;      // dyn_aligner_set_rescale (0 .. 8): read by every batch / ticket at its submission
   bool kmer_summary = false;  // dyn_aligner_set_kmer_summary: read by every batch / ticket at its submission

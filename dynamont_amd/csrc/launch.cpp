@@ -329,7 +329,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   // 17 % faster but costs 12 instead of 8 bytes of HBM per band slot. When the pool cannot hold a
   // separate-layout lattice for every wave slot, waves wait for pages; in place then, if the wider
   // concurrency is worth more than the faster sweep.
-  const uint64_t row_sep = (uint64_t)dynk::P * 12 + dynk::CPL * 8, row_inp = (uint64_t)dynk::P * 8 + dynk::CPL * 8;
+  const uint64_t row_sep = (uint64_t)dynk::P * 12 + dynk::ROW_WORDS * 8, row_inp = (uint64_t)dynk::P * 8 + dynk::ROW_WORDS * 8;
   bool lpe_separate = calc;
   if (calc) {
     const double c_sep = std::min(1.0, (double)budget / ((double)wanted * page_rows * row_sep + 1.0));
@@ -370,7 +370,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   if (lattice && n_ok) {
     const uint64_t cap_pages = budget / page_bytes;
     const uint64_t target = std::min<uint64_t>(wanted, cap_pages);
-    const uint64_t ws_pp = page_rows * dynk::P * 8, lpe_pp = page_rows * dynk::P * 4, bits_pp = page_rows * dynk::CPL * 8;
+    const uint64_t ws_pp = page_rows * dynk::P * 8, lpe_pp = page_rows * dynk::P * 4, bits_pp = page_rows * dynk::ROW_WORDS * 8;
     const bool grow = a->ws.bytes < target * ws_pp || (calc && lpe_separate && a->lpe.bytes < target * lpe_pp) ||
                       (calc && a->bits.bytes < target * bits_pp);
     if (grow) {  // growing releases the old buffer, which earlier work on the compute stream may still be using
@@ -569,6 +569,8 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   q.e2 = m.log_e2;
   q.sp_tab = a->d_sptab.as<dynmath::SoftplusNode>();
   q.z_fail_status = z_fail;
+  q.lpe_floor = a->lpe_floor;
+  q.lpe_dense = a->lpe_dense ? 1 : 0;
   // per-border posterior confidence: [border_probability | border_window_probability] x capacity, zeroed here (rows of reads
   // that fail keep the zeros), written by the read queue / the wide-band kernel of the LAST pass behind every read
   double* bc_cols = nullptr;
@@ -591,6 +593,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     dynk::launch_pool_init(pool, used_pages, (int)n_static, a->stream);
     if (bc_cols && pass + 1 == n_pass) {
       q.border_window = b->bc_want;
+      q.lpe_dense = 1;  // the border phase reads whole windows of LPE (the kernel variant that carries it stores densely anyway)
       q.border_p = bc_cols;
       q.border_window_p = bc_cols + b->capacity;
     }

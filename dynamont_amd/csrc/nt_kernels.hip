@@ -44,6 +44,7 @@
 // four waves (dp_math.hpp), a 4-row-deep ring per wave that the forward sweep fills straight from HBM
 // with global_load_lds_dwordx4 (see ring_dma_row), and each wave's page table.
 #include "nt_kernels.hpp"
+#include "lpe_liveness.hpp"
 
 #include <algorithm>
 
@@ -544,8 +545,10 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
                                                 const double* __restrict__ sig, const Emis* __restrict__ par,
                                                 const double* __restrict__ ws_rd, float* __restrict__ lp_out,
                                                 uint64_t* __restrict__ bits, double Z, double m1, double e2,
-                                                const SoftplusNode* s_tab, unsigned ring_base, int strict_rows = 0,
-                                                uint32_t* fallbacks = nullptr) {
+                                                const SoftplusNode* s_tab, unsigned ring_base, float lpe_floor,
+                                                int strict_rows = 0, uint32_t* fallbacks = nullptr) {
+  // lpe_floor (wave-uniform; separate layout only): the float LPE of a 16-lane group is stored only in rows where one of its
+  // cells has !(LPE < lpe_floor); -inf stores every group (lpe_liveness.hpp)
   uint32_t nfb = 0;
   // STRICT instantiation: rows t <= strict_rows are computed with the certified (bit-for-bit) arithmetic, later rows with the
   // default one (strict_rows = INT_MAX: the whole sweep). The Viterbi values of a row depend on forward values of rows <= t only,
@@ -558,7 +561,9 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
   // Two layouts for the log-posteriors the traceback needs (one cell per row):
   //  * separate (default): the bE rows stay intact and ONE float per slot, LPE, goes to its own array
   //    (same [row][row_pos] indexing); the ~10 % M cells of the path (segment starts) get LPM rebuilt
-  //    from LPE of the diagonal predecessor and two bE cells (mpost). 12 B per slot per row here.
+  //    from LPE of the diagonal predecessor and two bE cells (mpost). 8 B read per slot per row, and
+  //    4 B written in the lane groups that hold a cell whose posterior does not underflow (about one
+  //    group of four per row; the row's record says which).
   //  * INPLACE: (float LPM, float LPE) overwrite the bE slot of row t while rows t+1.. are still
   //    being read (lp_out then aliases ws_rd; no address is read after it has been written within one
   //    sweep). 16 B per slot per row make this sweep HBM-bound, but the footprint is 8 instead of
@@ -725,6 +730,18 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
       for (int j = 0; j < CPL; ++j) LPM[j] = (out.fM[j] + (out.b[j] + out.e[j])) - Z;  // bM(t,n) = bE(t+1,n) + e(t+1,n)
 #pragma unroll
       for (int j = 0; j < CPL; ++j) LPE[j] = (out.fE[j] + in.b[j]) - Z;
+      // The row's record has one more word, kept by lane CPL: the lanes whose float LPE this row stores (separate layout:
+      // the groups that hold a cell a reader can tell from -inf, whole groups so that no store covers part of a sector;
+      // in-place layout: every lane, and its traceback does not look). A ballot like the others: same asm block below.
+      // Taken here, ahead of the Viterbi arithmetic: its dependent chain of lane exchanges then has fp64 work to hide behind.
+      float f[CPL];
+      uint64_t stored = ~0ull;
+      if constexpr (!INPLACE) {
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) f[j] = (float)LPE[j];
+        stored = lpe_store_mask(lpe_lane_live(f, lpe_floor));
+        if constexpr (MASKED) stored &= out_mask;
+      }
 #pragma unroll
       for (int j = 0; j < CPL; ++j) out.vM[j] = vEl[j] + LPM[j];
 #pragma unroll
@@ -742,18 +759,18 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
       static_assert(CPL == 7, "one v_writelane pair per cell register");
 #define DYN_WL(J, LO, HI) "v_writelane_b32 %0, %" #LO ", " #J "\n\tv_writelane_b32 %1, %" #HI ", " #J "\n\t"
       asm("s_nop 4\n\t"
-          DYN_WL(0, 2, 3) DYN_WL(1, 4, 5) DYN_WL(2, 6, 7) DYN_WL(3, 8, 9) DYN_WL(4, 10, 11) DYN_WL(5, 12, 13) DYN_WL(6, 14, 15)
+          DYN_WL(0, 2, 3) DYN_WL(1, 4, 5) DYN_WL(2, 6, 7) DYN_WL(3, 8, 9) DYN_WL(4, 10, 11) DYN_WL(5, 12, 13) DYN_WL(6, 14, 15) DYN_WL(7, 16, 17)
           : "=&v"(wlo), "=&v"(whi)
           : "s"((unsigned)bj[0]), "s"((unsigned)(bj[0] >> 32)), "s"((unsigned)bj[1]), "s"((unsigned)(bj[1] >> 32)),
             "s"((unsigned)bj[2]), "s"((unsigned)(bj[2] >> 32)), "s"((unsigned)bj[3]), "s"((unsigned)(bj[3] >> 32)),
             "s"((unsigned)bj[4]), "s"((unsigned)(bj[4] >> 32)), "s"((unsigned)bj[5]), "s"((unsigned)(bj[5] >> 32)),
-            "s"((unsigned)bj[6]), "s"((unsigned)(bj[6] >> 32)));
+            "s"((unsigned)bj[6]), "s"((unsigned)(bj[6] >> 32)), "s"((unsigned)stored), "s"((unsigned)(stored >> 32)));
 #undef DYN_WL
       const uint64_t mybits = ((uint64_t)whi << 32) | wlo;
       const uint32_t prow = cur_out.at(w, t);
       const size_t rt = (size_t)prow * P;
       // read again only by the traceback, one cell per row: non-temporal; same pairing as the bE rows
-      const bool out_live = MASKED ? __builtin_amdgcn_inverse_ballot_w64(out_mask) : true;
+      const bool out_live = (MASKED && INPLACE) ? __builtin_amdgcn_inverse_ballot_w64(out_mask) : true;
       if (!out_live) {
         // (DYN_SKIP_OOB: nothing of this lane lies in the row's band)
       } else if (INPLACE) {
@@ -770,17 +787,33 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
         v2.x = (float)LPM[6];
         v2.y = (float)LPE[6];
         __builtin_nontemporal_store(v2, reinterpret_cast<dyn_f2*>(&lat_lp[2 * (rt + 384 + lane)]));
-      } else {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-          dyn_f2 v2;
-          v2.x = (float)LPE[2 * q];
-          v2.y = (float)LPE[2 * q + 1];
-          __builtin_nontemporal_store(v2, reinterpret_cast<dyn_f2*>(&lat_lp[rt + q * 128 + lane * 2]));
-        }
-        __builtin_nontemporal_store((float)LPE[6], &lat_lp[rt + 384 + lane]);
       }
-      if (lane < CPL) bits[(size_t)prow * CPL + lane] = mybits;
+      if constexpr (INPLACE) {
+        if (lane < ROW_WORDS) bits[(size_t)prow * ROW_WORDS + lane] = mybits;
+      } else {
+        // The four LPE stores under exec = stored, the record under exec = lanes 0 .. ROW_WORDS-1, then every lane again
+        // (all 64 are active here, as ring_dma_row assumes): three scalar moves. Written as two divergent branches the
+        // same stores cost a save, a branch and a restore of exec each -- and a wave pays for every instruction.
+        // Same addresses as store_row_f64's: (f0,f1) (f2,f3) (f4,f5) at 8 bytes per lane in runs of 512, f6 at 4 behind them.
+        static_assert(ROW_WORDS == 8 && CPL == 7, "exec = 0xff; three pairs and a single");
+        dyn_f2 p0, p1, p2;
+        p0.x = f[0], p0.y = f[1], p1.x = f[2], p1.y = f[3], p2.x = f[4], p2.y = f[5];
+        float* const lp_row = lat_lp + rt;
+        uint64_t* const rec_row = bits + (size_t)prow * ROW_WORDS;
+        const int off8 = lane * 8, off4 = lane * 4;
+        const float f6 = f[6];
+        asm volatile(
+            "s_mov_b64 exec, %0\n\t"
+            "global_store_dwordx2 %1, %3, %7 nt\n\t"
+            "global_store_dwordx2 %1, %4, %7 offset:512 nt\n\t"
+            "global_store_dwordx2 %1, %5, %7 offset:1024 nt\n\t"
+            "global_store_dword %2, %6, %7 offset:1536 nt\n\t"
+            "s_mov_b64 exec, 0xff\n\t"
+            "global_store_dwordx2 %1, %8, %9\n\t"
+            "s_mov_b64 exec, -1\n\t"
+            :: "s"(stored), "v"(off8), "v"(off4), "v"(p0), "v"(p1), "v"(p2), "v"(f6), "s"(lp_row), "v"(mybits), "s"(rec_row)
+            : "memory");
+      }
     }
   };
 
@@ -876,16 +909,19 @@ __device__ __forceinline__ bool traceback(const ReadDesc& rd, const WaveCtx& w, 
   // the next block's decision bits are fetched while this one is walked, and a block's path posteriors -- one dependent
   // load per row -- are finished one block later: the walk pays neither HBM latency.
   uint64_t nb[CPL];          // the bits of the block about to be walked (row base + lane)
+  uint64_t nstored = 0;      // ... and the lanes of that row whose float LPE the forward sweep stored
   uint32_t nprow = 0;
   auto fetch = [&](int base_) {
     const int row_ = base_ + lane;
     nprow = 0;
 #pragma unroll
     for (int j = 0; j < CPL; ++j) nb[j] = 0;
+    nstored = 0;
     if (row_ >= 1) {
       nprow = pool_row(w, row_);
 #pragma unroll
-      for (int j = 0; j < CPL; ++j) nb[j] = bits[(size_t)nprow * CPL + j];
+      for (int j = 0; j < CPL; ++j) nb[j] = bits[(size_t)nprow * ROW_WORDS + j];
+      nstored = bits[(size_t)nprow * ROW_WORDS + CPL];
     }
   };
   int pend_row = 0, pend_n = 0, pend_st = -1;   // this lane's path cell of the previous block, its posterior in flight
@@ -904,6 +940,7 @@ __device__ __forceinline__ bool traceback(const ReadDesc& rd, const WaveCtx& w, 
     const int base = t - 63;
     const int row = base + lane;
     const uint32_t prow = nprow;
+    const uint64_t stored = nstored;
 #pragma unroll
     for (int j = 0; j < CPL; ++j) sb[lane * CPL + j] = nb[j];
     wave_lds_sync_local();
@@ -974,8 +1011,10 @@ __device__ __forceinline__ bool traceback(const ReadDesc& rd, const WaveCtx& w, 
       // E cell of the path: the forward sweep stored its log-posterior. M cells (segment starts, ~1 row in
       // 10) get theirs from mpost, one lane per segment, instead of ~6 dependent loads in this walk.
       const size_t cell = (size_t)prow * P + row_pos(my_n % P);
+      // a cell the sweep did not store lies below the floor: exp() of it is exactly 0.0, as exp(-inf) is (lpe_liveness.hpp);
+      // what the array holds there is another read's
       if (inplace) pend_lp = lp[2 * cell + (my_st ? 0 : 1)];
-      else if (my_st == 0) pend_lp = lp[cell];
+      else if (my_st == 0) pend_lp = lpe_slot_stored(stored, my_n % P) ? lp[cell] : -INFINITY;
       pend_row = row;
       pend_n = my_n;
       pend_st = my_st;
@@ -988,10 +1027,12 @@ __device__ __forceinline__ bool traceback(const ReadDesc& rd, const WaveCtx& w, 
     const int base = t - 63;
     const int row = base + lane;
     uint32_t prow = 0;
+    uint64_t stored = 0;
     if (row >= 1) {
       prow = pool_row(w, row);
 #pragma unroll
-      for (int j = 0; j < CPL; ++j) sb[lane * CPL + j] = bits[(size_t)prow * CPL + j];
+      for (int j = 0; j < CPL; ++j) sb[lane * CPL + j] = bits[(size_t)prow * ROW_WORDS + j];
+      stored = bits[(size_t)prow * ROW_WORDS + CPL];
     }
     wave_lds_sync();
     int my_n = 0, my_slot = 0, my_st = -1;
@@ -1032,7 +1073,7 @@ __device__ __forceinline__ bool traceback(const ReadDesc& rd, const WaveCtx& w, 
       // 10) get theirs from mpost, one lane per segment, instead of ~6 dependent loads in this walk.
       const size_t cell = (size_t)prow * P + row_pos(my_slot);
       if (inplace) pp[row] = exp((double)lp[2 * cell + (my_st ? 0 : 1)]);
-      else if (my_st == 0) pp[row] = exp((double)lp[cell]);
+      else if (my_st == 0) pp[row] = exp((double)(lpe_slot_stored(stored, my_slot) ? lp[cell] : -INFINITY));
       pathn[row] = (uint32_t)my_n | (my_st ? 0x80000000u : 0u);
       if (my_st) segrow[my_n - 1] = (uint32_t)row;
     }
@@ -1050,9 +1091,11 @@ __device__ __forceinline__ bool traceback(const ReadDesc& rd, const WaveCtx& w, 
 //   bM(row, n)     = bE(row+1, n) + e(row+1, n)                   (:200; row T of the workspace is -inf)
 //   LPM(row, n)    = (fM + bM) - Zb                               (:222)
 // The float LPE costs <= 6e-8 * |LPE| here; every other term is fp64. One lane per segment.
+// An LPE the forward sweep did not store (the row's record says so) lies below the floor, and LPM(row, n) <= LPE(row-1, n-1):
+// -inf in its place gives the same exp() = 0.0 (lpe_liveness.hpp).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void mpost(const ReadDesc& rd, const WaveCtx& w, const double* __restrict__ bE,
-                                      const float* __restrict__ lp, const double* __restrict__ sig,
+                                      const float* __restrict__ lp, const uint64_t* __restrict__ bits, const double* __restrict__ sig,
                                       const Emis* __restrict__ par, TraceBuffers tb, double Zb, double m1) {
   const int T = (int)rd.T, N = (int)rd.N;
   const double* __restrict__ sg = sig + rd.sig_off;
@@ -1063,8 +1106,10 @@ __device__ __forceinline__ void mpost(const ReadDesc& rd, const WaveCtx& w, cons
     if (row == 1) {
       fE_prev = n == 1 ? 0.0 : NEG_INF;  // fE(0, 0) = 0, nothing else in row 0 (:120)
     } else {
-      const size_t pcell = (size_t)pool_row(w, row - 1) * P + row_pos(pslot);
-      fE_prev = ((double)lp[pcell] - bE[pcell]) + Zb;
+      const uint32_t prow = pool_row(w, row - 1);
+      const size_t pcell = (size_t)prow * P + row_pos(pslot);
+      const double lpe = lpe_slot_stored(bits[(size_t)prow * ROW_WORDS + CPL], pslot) ? (double)lp[pcell] : NEG_INF;
+      fE_prev = (lpe - bE[pcell]) + Zb;
     }
     const Emis em = par[rd.par_off + n - 1];
     const double e_here = dynmath::log_normal_pdf(sg[row - 1], em);
@@ -1346,6 +1391,7 @@ struct ReadIO {
   TrainBuffers tr;
   double m1, e2;
   int z_fail_status;
+  float lpe_floor;  // forward_sweep: -inf = every LPE is stored
 };
 
 // wave-cycles per phase, accumulated over the reads of a wave
@@ -1376,9 +1422,9 @@ __device__ __forceinline__ void run_read(const ReadDesc& rd, const WaveCtx& w, c
     t2 = __builtin_amdgcn_s_memtime();
     ws.rows_cert += (uint64_t)rd.T + (uint64_t)min((int)rd.T, strict_rows);
     if (JOB == JOB_ALIGN_INPLACE)
-      Zf = forward_sweep<true, true, MIXED>(rd, w, sig, par, pool.ws, reinterpret_cast<float*>(pool.ws), pool.bits, Zb, io.m1, io.e2, s_tab, ring_base, strict_rows, &ws.n_fallback);
+      Zf = forward_sweep<true, true, MIXED>(rd, w, sig, par, pool.ws, reinterpret_cast<float*>(pool.ws), pool.bits, Zb, io.m1, io.e2, s_tab, ring_base, io.lpe_floor, strict_rows, &ws.n_fallback);
     else
-      Zf = forward_sweep<true, false, MIXED>(rd, w, sig, par, pool.ws, pool.lpe, pool.bits, Zb, io.m1, io.e2, s_tab, ring_base, strict_rows, &ws.n_fallback);
+      Zf = forward_sweep<true, false, MIXED>(rd, w, sig, par, pool.ws, pool.lpe, pool.bits, Zb, io.m1, io.e2, s_tab, ring_base, io.lpe_floor, strict_rows, &ws.n_fallback);
   } else {
     if constexpr (JOB == JOB_TRAIN || JOB == JOB_TRAIN_ZCHECK) {
       // backward sweep in the log domain (the emission's constant folded), then the posterior chain
@@ -1389,18 +1435,18 @@ __device__ __forceinline__ void run_read(const ReadDesc& rd, const WaveCtx& w, c
         // dyn_aligner_set_train_zcheck: the reference's own refusal rule (NT_aligner_api.cpp:619-625) on top of the
         // chain's -- a forward value of Z (the cheap Z-only sweep: no lattice traffic) must agree with the backward one
         // to 1e-8 per lattice cell, so that `.errors` lists the reads the reference lists (|Z| ~ 1e12 and beyond)
-        const double Zf_log = forward_sweep<false, false, false>(rd, w, sig, par, nullptr, nullptr, nullptr, 0.0, io.m1, io.e2, s_tab, ring_base);
+        const double Zf_log = forward_sweep<false, false, false>(rd, w, sig, par, nullptr, nullptr, nullptr, 0.0, io.m1, io.e2, s_tab, ring_base, 0.0f);
         if (!z_ok(rd, Zf_log, Zb)) Zf = NEG_INF;
       }
     } else {
       Zb = backward_sweep<LATTICE, JOB == JOB_Z ? ARITH_FOLDED : ARITH_DEFAULT>(rd, w, sig, par, pool.ws, io.m1, io.e2, s_tab);
       t2 = __builtin_amdgcn_s_memtime();
       if (JOB == JOB_ALIGN) {
-        Zf = forward_sweep<true, false, false>(rd, w, sig, par, pool.ws, pool.lpe, pool.bits, Zb, io.m1, io.e2, s_tab, ring_base);
+        Zf = forward_sweep<true, false, false>(rd, w, sig, par, pool.ws, pool.lpe, pool.bits, Zb, io.m1, io.e2, s_tab, ring_base, io.lpe_floor);
       } else if (JOB == JOB_ALIGN_INPLACE) {
-        Zf = forward_sweep<true, true, false>(rd, w, sig, par, pool.ws, reinterpret_cast<float*>(pool.ws), pool.bits, Zb, io.m1, io.e2, s_tab, ring_base);
+        Zf = forward_sweep<true, true, false>(rd, w, sig, par, pool.ws, reinterpret_cast<float*>(pool.ws), pool.bits, Zb, io.m1, io.e2, s_tab, ring_base, io.lpe_floor);
       } else {
-        Zf = forward_sweep<false, false, false>(rd, w, sig, par, nullptr, nullptr, nullptr, 0.0, io.m1, io.e2, s_tab, ring_base);
+        Zf = forward_sweep<false, false, false>(rd, w, sig, par, nullptr, nullptr, nullptr, 0.0, io.m1, io.e2, s_tab, ring_base, 0.0f);
       }
     }
   }
@@ -1425,7 +1471,7 @@ __device__ __forceinline__ void run_read(const ReadDesc& rd, const WaveCtx& w, c
       if (JOB == JOB_ALIGN) {
         // segrow was written by other lanes of this wave through global memory
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        mpost(rd, w, pool.ws, pool.lpe, sig, par, io.tb, Zb, io.m1);
+        mpost(rd, w, pool.ws, pool.lpe, pool.bits, sig, par, io.tb, Zb, io.m1);
       }
 #ifdef DYN_EXP_TRACE_SPLIT
       ws.cyc_fs += __builtin_amdgcn_s_memtime() - t4;
@@ -1511,6 +1557,8 @@ __global__ DYN_ONE_WAVE_PER_SIMD void k_read_queue(const QueueArgs q, const Read
   lds_u64_t* sb = (lds_u64_t*)&s_ring[wave][0][0];  // traceback staging: the ring is idle by then
 
   WaveStats ws;
+  // the border-confidence phase reads whole windows of LPE: every cell is stored then
+  const float lpe_floor = (BORDER || q.lpe_dense) ? -INFINITY : q.lpe_floor;
   const uint64_t t_start = __builtin_amdgcn_s_memtime();
   uint32_t* ctl = q.pool.ctl;
   uint32_t have = 0;  // pages in this wave's table
@@ -1549,7 +1597,7 @@ __global__ DYN_ONE_WAVE_PER_SIMD void k_read_queue(const QueueArgs q, const Read
     wave_lds_sync();
     const uint64_t t1 = __builtin_amdgcn_s_memtime();
     ws.cyc_w += t1 - t0;
-    run_read<JOB, MIXED>(rd, w, q.pool, ReadIO{q.st, q.tb, q.tr, q.m1, q.e2, q.z_fail_status}, sig, par, s_tab, ring_base, sb, ws, t1);
+    run_read<JOB, MIXED>(rd, w, q.pool, ReadIO{q.st, q.tb, q.tr, q.m1, q.e2, q.z_fail_status, lpe_floor}, sig, par, s_tab, ring_base, sb, ws, t1);
     if constexpr (BORDER) {
       // the read's lattice is still in this wave's pages; its state and segrow were written by lanes of this wave
       const uint64_t t5 = __builtin_amdgcn_s_memtime();
@@ -1748,6 +1796,7 @@ __global__ DYN_ONE_WAVE_PER_SIMD void k_session(const SessionArgs sa, const char
     io.m1 = sa.m1;
     io.e2 = sa.e2;
     io.z_fail_status = tk.z_fail_status;
+    io.lpe_floor = sa.lpe_dense ? -INFINITY : sa.lpe_floor;
     run_read<JOB, MIXED>(rd, w, sa.pool, io, sig, par, s_tab, ring_base, sb, ws, t1);
     // everything this wave wrote for the read (state, path arrays, segment rows) must have left this XCD's L2 before the
     // ticket's counter says so: the per-segment kernels and the copies that follow run elsewhere

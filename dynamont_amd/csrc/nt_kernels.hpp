@@ -20,6 +20,9 @@ using dynmath::Emis;
 constexpr int CPL = 7;                       // cells per lane
 constexpr int P = 64 * CPL;                  // 448 slots per row
 constexpr int MAX_HALF_BAND = (P - 2) / 2;   // 2*bw+1 <= P-1  ->  bw <= 223 (band <= 447)
+// 64-bit words of a row's record in PagePool::bits: the CPL decision ballots, then the lane mask of the float LPE cells the
+// forward sweep stored (lpe_liveness.hpp; in-place layout: every lane). 64 bytes per row.
+constexpr int ROW_WORDS = CPL + 1;
 
 // The lattice of a read lives in PAGES of 2^log_rows rows taken from a pool that all reads of a
 // launch share: a read holds ceil((T+1) / rows_per_page) pages from the moment a wave starts its
@@ -84,7 +87,7 @@ struct TrainBuffers {
 struct PagePool {
   double* ws;           // [n_pages][rows_per_page][P]   backward-E (8 B per slot); in place: (float LPM, float LPE)
   float* lpe;           // [n_pages][rows_per_page][P]   float LPE per slot (separate layout) or nullptr
-  uint64_t* bits;       // [n_pages][rows_per_page][CPL] decision ballots
+  uint64_t* bits;       // [n_pages][rows_per_page][ROW_WORDS] decision ballots, then the mask of the lanes whose LPE was stored
   uint32_t* free_list;  // stack of free page numbers
   // ctl (32-bit words): [0] lock of the free-page stack, [1] queue head (next read), [2] free pages on the
   // stack, [3] abort (a wave gave up waiting: the queue drains, the host reports the launch as failed),
@@ -119,6 +122,10 @@ struct QueueArgs {
   double m1, e2;          // log transition probabilities (NT_aligner_api.cpp:84-86)
   const dynmath::SoftplusNode* sp_tab;
   int z_fail_status;
+  // the forward sweep stores the float LPE of a lane group only where a cell has !(LPE < lpe_floor) (lpe_liveness.hpp);
+  // lpe_dense: every group is stored. Launches whose border-confidence phase reads whole windows of LPE are dense anyway.
+  float lpe_floor = -750.0f;
+  int lpe_dense = 0;
   // per-border posterior confidence (dyn_aligner_set_border_confidence): columns indexed like the output rows, zeroed by the
   // caller; border_window == 0: not asked for (and the launch is the one it has always been)
   int border_window = 0;             // W, 1 .. 256
@@ -179,6 +186,8 @@ struct SessionArgs {
   PagePool pool;               // ws, lpe, bits, log_rows; layouts 1 / 2 (paged): free_list and ctl as well (k_pool_init first)
   double m1, e2;
   uint64_t idle_limit_ticks;   // s_memrealtime ticks (100 MHz)
+  float lpe_floor = -750.0f;   // as QueueArgs
+  int lpe_dense = 0;
 };
 
 // n_cus workgroups of four waves on `s` -- which must own its hardware queue (hipExtStreamCreateWithCUMask)

@@ -27,7 +27,7 @@ namespace {
 // workgroups of a session = CUs it occupies (dyn_aligner_set_session_mode leaves the others free)
 int session_wgs(const dyn_aligner* a) { return std::max(1, a->sess_cus); }
 // bytes of one lattice row in the pool (separate LPE layout): bE 8 B + float LPE 4 B per slot + the decision ballots
-constexpr uint64_t SESSION_ROW_BYTES = (uint64_t)dynk::P * 12 + dynk::CPL * 8;
+constexpr uint64_t SESSION_ROW_BYTES = (uint64_t)dynk::P * 12 + dynk::ROW_WORDS * 8;
 
 uint32_t session_pages_of(uint64_t S, int log_r) { return (uint32_t)((S + 2 + (1ull << log_r) - 1) >> log_r); }
 
@@ -111,7 +111,7 @@ int session_open(dyn_aligner* a, bool mixed, const SessionGeom& g) {
   // classic launches of the compute stream and the previous session (its kernel precedes this one on the session stream
   // anyway; the host-side wait is for the hipFree).
   const uint64_t page_rows = 1ull << log_r;
-  const uint64_t ws_pp = page_rows * dynk::P * 8, lpe_pp = page_rows * dynk::P * 4, bits_pp = page_rows * dynk::CPL * 8;
+  const uint64_t ws_pp = page_rows * dynk::P * 8, lpe_pp = page_rows * dynk::P * 4, bits_pp = page_rows * dynk::ROW_WORDS * 8;
   HIP_TRY(a, hipStreamSynchronize(a->stream));
   if (a->ws.bytes < n_pages_total * ws_pp || (separate && a->lpe.bytes < n_pages_total * lpe_pp) || a->bits.bytes < n_pages_total * bits_pp ||
       (paged && a->free_list.bytes < (size_t)n_pages_total * 4)) {
@@ -144,6 +144,8 @@ int session_open(dyn_aligner* a, bool mixed, const SessionGeom& g) {
   sa.m1 = a->model.log_m1;
   sa.e2 = a->model.log_e2;
   sa.idle_limit_ticks = (uint64_t)(a->sess_idle_s * 1e8);
+  sa.lpe_floor = a->lpe_floor;
+  sa.lpe_dense = a->lpe_dense ? 1 : 0;
   if (paged) dynk::launch_pool_init(sa.pool, 0, 0, a->s_session);  // every page on the free list, control words cleared
   HIP_TRY(a, hipEventRecord(ss.ev_begin[blk], a->s_session));
   dynk::launch_session(mixed, g.layout, sa, a->d_model.p, a->sess_anchor.p, a->d_sptab.as<dynmath::SoftplusNode>(), session_wgs(a), a->s_session);
@@ -251,7 +253,7 @@ static int session_choose(dyn_aligner* a, const dyn_batch* b, const SessionNeed&
   for (size_t k = 0; k < top; ++k) wanted += pg[k];
   wanted = std::max<uint64_t>(wanted, 1);
   // separate float LPE: the forward sweep is 17 % faster, 12 instead of 8 bytes per band slot (enqueue_job's rule)
-  const uint64_t row_sep = (uint64_t)dynk::P * 12 + dynk::CPL * 8, row_inp = (uint64_t)dynk::P * 8 + dynk::CPL * 8;
+  const uint64_t row_sep = (uint64_t)dynk::P * 12 + dynk::ROW_WORDS * 8, row_inp = (uint64_t)dynk::P * 8 + dynk::ROW_WORDS * 8;
   const double c_sep = std::min(1.0, (double)budget / ((double)wanted * page_rows * row_sep + 1.0));
   const double c_inp = std::min(1.0, (double)budget / ((double)wanted * page_rows * row_inp + 1.0));
   bool separate = !(c_sep < 1.0 && c_inp * 0.92 > c_sep);

@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "../../dynamont_amd/csrc/nt_kernels.hpp"
+#include "../../dynamont_amd/csrc/guided_band_kernels.hpp"
 
 namespace dynk {
 
@@ -48,5 +49,12 @@ hipError_t launch_pool_stats(const ReadDesc*, int, uint32_t, const ReadState*, c
 }
 uint64_t wide_arena_bytes(uint64_t T, uint64_t bw, bool calc) { return T * (2 * bw + 3) * (16 + (calc ? 9 : 0)); }
 void launch_wide_reads(int, const WideArgs&, int, hipStream_t) { no_device("launch_wide_reads"); }
+uint64_t guided_arena_bytes(uint64_t T, uint64_t bw, int job) { return T * (2 * bw + 3) * (16 + (job == 1 ? 9 : 0)); }
+int guided_groups_per_cu(int, int) { return 1; }
+hipError_t launch_guided_reads(int, const GuidedArgs&, int, hipStream_t) { no_device("launch_guided_reads"); }
+void launch_guided_band_margin(const ReadDesc*, int, uint32_t, const ReadState*, const TraceBuffers&, const int32_t*, int, const BandMargin&,
+                               hipStream_t) {
+  no_device("launch_guided_band_margin");
+}
 
 }  // namespace dynk

@@ -4,6 +4,10 @@
 //   F  "forward" : per row the same 3 584 B through the 4-deep LDS-DMA ring (global_load_lds_dwordx4), rows ascending,
 //                  + 1 792 B of float stores (3 x 8 B/lane + 4 B/lane) + 56 B of decision bits
 //   M  mix       : 2 of every 5 waves run B, the others F (the time shares of the two sweeps in the real launch)
+//   F16 / F8     : F with the float stores of a row issued by ONE lane group only (posteriors stored only where exp() does not
+//                  underflow: about one group per row holds such a cell). The group follows the path: it moves on every 512 /
+//                  256 rows. 16-lane group: 3 x 128 B + 64 B per row. 8-lane group: 3 x 64 B, and the 4 B/lane store by the
+//                  enclosing 16 lanes (64 B; 8 lanes would write half a 64-byte sector). Ring reads and decision bits as in F.
 // Build: hipcc --offload-arch=gfx950 -O3 -o stream_pattern stream_pattern.hip ;  ./stream_pattern [rows_per_wave=20000]
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -35,7 +39,8 @@ __device__ __forceinline__ void store_row(double* row, int lane, double v) {
   __builtin_nontemporal_store(h, reinterpret_cast<f2*>(row + 384 + lane));
 }
 
-// mode: 0 = B on every wave, 1 = F on every wave, 2 = mix, 3 = F with the LPE / bits stores of two rows issued together
+// mode: 0 = B on every wave, 1 = F on every wave, 2 = mix, 3 = F with the LPE / bits stores of two rows issued together,
+//       4 / 5 = F with the LPE stores of one 16-lane / 8-lane group per row
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k(double* ws, float* lpe, unsigned long long* bits, int rows, int mode, double* sink) {
   __shared__ __attribute__((aligned(16))) double ring[4][D][P];
@@ -59,7 +64,19 @@ void k(double* ws, float* lpe, unsigned long long* bits, int rows, int mode, dou
       const int nx = t + D < rows ? t + D : rows - 1;
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       dma_row(src + (size_t)nx * P, base + (t % D) * ROWB);
-      if (mode != 3 || (t & 1)) {
+      if (mode >= 4) {
+        // wave-uniform group of the row, as a lane predicate (the sweep would hold it as an exec mask)
+        const bool live2 = mode == 4 ? (lane >> 4) == ((t >> 9) & 3) : (lane >> 3) == ((t >> 8) & 7);
+        const bool live1 = mode == 4 ? live2 : (lane >> 4) == ((t >> 9) & 3);
+        float* o = my_lp + (size_t)t * P;
+        f2 h; h.x = h.y = (float)t;
+        if (live2) {
+#pragma unroll
+          for (int q = 0; q < 3; ++q) __builtin_nontemporal_store(h, reinterpret_cast<f2*>(o + q * 128 + lane * 2));
+        }
+        if (live1) __builtin_nontemporal_store((float)t, o + 384 + lane);
+        if (lane < 7) my_bits[(size_t)t * 7 + lane] = (unsigned long long)t;
+      } else if (mode != 3 || (t & 1)) {
         for (int tt = (mode == 3 ? t - 1 : t); tt <= t; ++tt) {
           float* o = my_lp + (size_t)tt * P;
           f2 h; h.x = h.y = (float)tt;
@@ -83,17 +100,20 @@ int main(int argc, char** argv) {
   CK(hipMalloc(&ws, cells * 8)); CK(hipMalloc(&lpe, cells * 4)); CK(hipMalloc(&bits, slots * (size_t)rows * 56)); CK(hipMalloc(&sink, 8));
   CK(hipMemset(ws, 0, cells * 8));
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-  const char* names[4] = {"B (backward: 3584 B/row written)", "F (forward: 3584 B/row read by LDS-DMA + 1848 B/row written)", "M (2 of 5 waves B, 3 of 5 F)",
-                          "F2 (forward, the float / bit stores of two rows issued together)"};
-  for (int mode = 0; mode < 4; ++mode) {
-    for (int rep = 0; rep < 3; ++rep) {
+  const char* names[6] = {"B (backward: 3584 B/row written)", "F (forward: 3584 B/row read by LDS-DMA + 1848 B/row written)", "M (2 of 5 waves B, 3 of 5 F)",
+                          "F2 (forward, the float / bit stores of two rows issued together)",
+                          "F16 (forward, float stores of one 16-lane group per row: 448 B)",
+                          "F8 (forward, float stores of one 8-lane group per row: 256 B)"};
+  for (int mode = 0; mode < 6; ++mode) {
+    for (int rep = 0; rep < 6; ++rep) {
       CK(hipEventRecord(e0));
       hipLaunchKernelGGL(k, dim3(256), dim3(256), 0, 0, ws, lpe, bits, rows, mode, sink);
       CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
       float ms; CK(hipEventElapsedTime(&ms, e0, e1));
-      const double nb = mode == 0 ? 1.0 : (mode == 1 || mode == 3) ? 0.0 : 410.0 / 1024.0;  // 1024 slots: slot % 5 < 2 -> 410 of them
-      const double bytes = (double)slots * rows * (nb * ROWB + (1.0 - nb) * (ROWB + P * 4 + 56));
-      if (rep) printf("%-64s rep %d  %.3f ms  %.2f TB/s\n", names[mode], rep, ms, bytes / ms * 1e-9);
+      const double nb = mode == 0 ? 1.0 : mode != 2 ? 0.0 : 410.0 / 1024.0;  // 1024 slots: slot % 5 < 2 -> 410 of them
+      const double lpb = mode == 4 ? 448.0 : mode == 5 ? 256.0 : P * 4.0;
+      const double bytes = (double)slots * rows * (nb * ROWB + (1.0 - nb) * (ROWB + lpb + 56));
+      if (rep) printf("%-64s rep %d  %.3f ms  %.2f TB/s  %.1f Mrows/s\n", names[mode], rep, ms, bytes / ms * 1e-9, (double)slots * rows / ms * 1e-3);
     }
   }
   return 0;
