@@ -115,6 +115,7 @@ class AlignBatchResult:
         # band-margin diagnostics (Aligner.set_band_margin): uint32 [n] each, None when off; band_used (uint32 [n]): the band
         # every read's rows come from, only with Aligner.set_band_retry
         self.band_margin_low = self.band_margin_high = self.band_edge_rows = None
+        self.guide_rounds = self.guide_converged = self.guides = None  # Aligner.align_batch_auto / align_batch_guided(refine > 1)
         self.band_used = None
 
     def _fetch_band_margin(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
@@ -404,6 +405,39 @@ class Batch:
         rc = self._L.dyn_batch_set_guide(self._h, _ptr(g, N.c_i32_p), g.size, int(half_width))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
+
+    def auto_guide(self, half_width: int) -> None:
+        """dyn_batch_auto_guide: the library makes the batch's guide itself -- a forward max-plus pre-pass on the device whose
+        window of ``half_width`` columns follows the row's best cell -- and installs it as
+        ``set_guide`` would. ``guide()`` returns it."""
+        rc = self._L.dyn_batch_auto_guide(self._h, int(half_width))
+        if rc != N.DYN_OK:
+            _raise(rc, self._al.last_error())
+
+    def set_guide_refine(self, max_rounds: int) -> None:
+        """dyn_batch_set_guide_refine: the next guided ``align(True)`` re-aligns every read inside the path its last alignment
+        called until that path reproduces the guide, ``max_rounds`` (1 .. 64) alignments at the most; 1 = no refinement."""
+        rc = self._L.dyn_batch_set_guide_refine(self._h, int(max_rounds))
+        if rc != N.DYN_OK:
+            _raise(rc, self._al.last_error())
+
+    def guide(self) -> list:
+        """dyn_batch_fetch_guide: the batch's current guide as a list of per-read int32 arrays (one entry per sample); after a
+        refined alignment every read's guide of its last round"""
+        off = (self._sig_off - self._sig_off[0]).astype(np.int64)
+        flat = np.zeros(int(off[-1]) if self.n else 0, dtype=np.int32)
+        rc = self._L.dyn_batch_fetch_guide(self._h, _ptr(flat, N.c_i32_p), flat.size)
+        if rc != N.DYN_OK:
+            _raise(rc, self._al.last_error())
+        return [flat[int(off[i]):int(off[i + 1])].copy() for i in range(self.n)]
+
+    def guide_rounds(self):
+        """dyn_batch_fetch_guide_rounds: (rounds, converged), two uint32 arrays with one entry per read"""
+        rounds, conv = np.zeros(self.n, dtype=np.uint32), np.zeros(self.n, dtype=np.uint32)
+        rc = self._L.dyn_batch_fetch_guide_rounds(self._h, _ptr(rounds, N.c_u32_p), _ptr(conv, N.c_u32_p), self.n)
+        if rc != N.DYN_OK:
+            _raise(rc, self._al.last_error())
+        return rounds, conv
 
     def train(self) -> None:
         rc = self._L.dyn_batch_train(self._h)
@@ -1131,17 +1165,56 @@ class Aligner:
         return res
 
     def align_batch_guided(self, signals: Sequence, sequences: Sequence[str], guides: Sequence, half_width: int,
-                           calc_probabilities: bool = True) -> AlignBatchResult:
+                           calc_probabilities: bool = True, refine: int = 1) -> AlignBatchResult:
         """``align_batch`` inside a guided band: ``guides[i]`` is read i's int32 guide, one lattice column per signal sample
         (``dynamont_amd.guide.guide_from_moves`` / ``guide_from_starts`` / ``diagonal_guide``), and every read is aligned in a
         window of ``half_width`` columns on either side of it instead of the band around the fixed diagonal. With
         ``set_band_margin(True)`` the three margin fields are taken against that window. Never retried (``set_band_retry``
-        applies to ``align_batch``); not together with ``set_rescale`` / ``set_border_confidence`` (ValueError)."""
+        applies to ``align_batch``); not together with ``set_rescale`` / ``set_border_confidence`` (ValueError).
+        ``refine`` > 1 (``Batch.set_guide_refine``): up to that many alignments per read, each inside the path the one before
+        called, until the guide reproduces itself; the result then carries ``guide_rounds``, ``guide_converged`` (uint32 per
+        read) and ``guides`` (every read's guide of its last alignment)."""
         centres = self._guide_centres(signals, guides)
         with self.batch(signals, sequences) as b:
             b.set_guide(centres, half_width)
+            if refine != 1:
+                b.set_guide_refine(refine)
             b.align(calc_probabilities)
-            return b.fetch()
+            res = b.fetch()
+            if refine != 1:
+                res.guide_rounds, res.guide_converged = b.guide_rounds()
+                res.guides = b.guide()
+            return res
+
+    def align_batch_auto(self, signals: Sequence, sequences: Sequence[str], half_width: int = 32, refine: int = 8,
+                         guides: bool = False) -> AlignBatchResult:
+        """``align_batch`` inside a guide the library makes itself: the pre-pass of ``Batch.auto_guide(half_width)``, then a
+        guided alignment refined up to ``refine`` times (``Batch.set_guide_refine``). No move table, no known starts. The
+        result carries ``guide_rounds`` and ``guide_converged`` (uint32 per read) and, with ``guides=True``, ``guides``: every
+        read's int32 guide of its last alignment (what ``train_batch_guided`` takes). Restrictions as ``align_batch_guided``."""
+        with self.batch(signals, sequences) as b:
+            b.auto_guide(half_width)
+            if refine != 1:
+                b.set_guide_refine(refine)
+            b.align(True)
+            res = b.fetch()
+            res.guide_rounds, res.guide_converged = b.guide_rounds()
+            if guides:
+                res.guides = b.guide()
+            return res
+
+    def train_batch_auto(self, signals: Sequence, sequences: Sequence[str], half_width: int = 32, refine: int = 8,
+                         pooled: bool = False) -> TrainBatchResult:
+        """``train_batch_guided`` inside self-made guides: ``align_batch_auto`` first, then the Baum-Welch statistics of the
+        reads that aligned ok inside their final guides. The result covers those reads only, in input order:
+        ``result.reads`` holds their indices into ``signals``, ``result.guide_converged`` the flag of each."""
+        al = self.align_batch_auto(signals, sequences, half_width, refine, guides=True)
+        keep = [i for i in range(al.n) if al.status[i] == 0]
+        tr = self.train_batch_guided([signals[i] for i in keep], [sequences[i] for i in keep], [al.guides[i] for i in keep],
+                                     half_width, pooled=pooled)
+        tr.reads = np.asarray(keep, dtype=np.int64)
+        tr.guide_converged = al.guide_converged[keep] if keep else np.zeros(0, dtype=np.uint32)
+        return tr
 
     @staticmethod
     def _guide_centres(signals: Sequence, guides: Sequence) -> np.ndarray:

@@ -16,6 +16,7 @@
 // DYN_ERR_DEVICE.
 #include "engine_internal.hpp"
 #include "dp_math_strict.hpp"
+#include "auto_guide_kernels.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -59,7 +60,7 @@ void attach_cache(dyn_batch* b) {
   dyneng::BufCache* c = &b->a->cache;
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_wide, &b->d_guide, &b->d_garena})
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_wide, &b->d_guide, &b->d_garena, &b->d_gref})
     d->cache = c;
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->cache = c;
 }
@@ -912,7 +913,7 @@ void dyn_batch_destroy(dyn_batch* b) {
   }
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl, &b->d_wide, &b->d_guide, &b->d_garena})
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl, &b->d_wide, &b->d_guide, &b->d_garena, &b->d_gref})
     d->release();
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->release();
   for (hipEvent_t e : b->events) (void)hipEventDestroy(e);
@@ -1064,6 +1065,13 @@ int run_job_sync(dyn_batch* b, DynJob job, bool guided_train = false) {
     a->last_error = "dyn_batch_train: the batch carries a guide (dyn_batch_set_guide) and training inside a guided band is not supported";
     return DYN_ERR_INVALID_ARGUMENT;
   }
+  // guide refinement reads the called path: neither the Z-only job nor the train job has one
+  if (b->guided && b->guide_refine > 1 && job != DynJob::AlignFull) {
+    a->last_error = std::string(job == DynJob::Train ? "dyn_batch_train_guided" : "dyn_batch_align") +
+                    ": the batch refines its guide (dyn_batch_set_guide_refine, max_rounds " + std::to_string(b->guide_refine) +
+                    "), which needs the called path of dyn_batch_align(b, 1); set max_rounds to 1 first";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
   if (b->guided && job != DynJob::Train && (a->rescale_iters > 0 || a->border_confidence > 0)) {
     a->last_error = std::string("dyn_batch_align: the batch carries a guide (dyn_batch_set_guide), which does not combine with ") +
                     (a->rescale_iters > 0 ? "dyn_aligner_set_rescale(a, iters > 0)" : "dyn_aligner_set_border_confidence(a, window > 0)");
@@ -1146,6 +1154,130 @@ int dyn_batch_set_guide(dyn_batch* b, const int32_t* centres, uint64_t count, ui
   }
   b->guided = true;
   b->guide_hw = half_width;
+  return DYN_OK;
+}
+
+int dyn_batch_auto_guide(dyn_batch* b, uint32_t half_width) {
+  if (!b) return DYN_ERR_INVALID_ARGUMENT;
+  dyn_aligner* a = b->a;
+  std::lock_guard<std::mutex> lk(a->mu);
+  auto fail = [&](const std::string& msg) {
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = "dyn_batch_auto_guide: " + msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  };
+  if (b->async || b->group) return fail("the batch is an asynchronous ticket; a guide is made for a batch from dyn_batch_create / dyn_batch_create_raw");
+  if (b->aligned || b->trained) return fail("the batch has already run; make the guide before dyn_batch_align");
+  if (half_width < 1 || half_width > (uint32_t)dynk::WIDE_MAX_HALF_BAND)
+    return fail("half_width " + std::to_string(half_width) + " is outside [1, " + std::to_string(dynk::WIDE_MAX_HALF_BAND) + "]");
+  if (int rc = need_device(a)) return rc;  // ("no GPU bound to this handle": the pre-pass is a kernel)
+  if (int rc = dyneng::session_quiesce(a)) return rc;
+  const uint64_t total = b->n ? b->reads[b->n - 1].sig_off + b->reads[b->n - 1].S : 0;
+  HIP_TRY(a, b->d_guide.ensure(std::max<uint64_t>(4, total * 4)));
+  // entries of reads that failed validation are never read; they are 0 in what dyn_batch_fetch_guide returns
+  if (total) HIP_TRY(a, hipMemsetAsync(b->d_guide.p, 0, total * 4, a->stream));
+  std::vector<uint32_t> order;
+  for (uint64_t i = 0; i < b->n; ++i)
+    if (b->reads[i].status == DYN_READ_OK) order.push_back((uint32_t)i);
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return b->reads[x].S > b->reads[y].S; });  // longest first
+  if (!order.empty()) {
+    std::vector<ReadDesc> descs(order.size());
+    for (size_t k = 0; k < order.size(); ++k) {
+      const HostRead& r = b->reads[order[k]];
+      ReadDesc d{};
+      d.T = (uint32_t)(r.S + 1);
+      d.N = (uint32_t)(r.kc + 1);
+      d.read = order[k];
+      d.sig_off = r.sig_off;
+      d.par_off = r.flat_off;
+      d.seg_off = r.seg_off;
+      d.first_page = dynk::NO_PAGE;
+      descs[k] = d;
+    }
+    HIP_TRY(a, b->d_descs.ensure(descs.size() * sizeof(ReadDesc)));
+    HIP_TRY(a, b->d_garena.ensure(256));
+    HIP_TRY(a, hipMemcpyAsync(b->d_descs.p, descs.data(), descs.size() * sizeof(ReadDesc), hipMemcpyHostToDevice, a->stream));
+    dynk::AutoGuideArgs ag{};
+    ag.descs = b->d_descs.as<ReadDesc>();
+    ag.n_reads = (int)descs.size();
+    ag.bw = (int)half_width;
+    ag.sig = b->d_sig.as<double>();
+    ag.par = b->d_par.as<Emis>();
+    ag.guide = b->d_guide.as<int32_t>();
+    ag.head = b->d_garena.as<uint32_t>();
+    ag.m1 = a->model.log_m1;
+    ag.e2 = a->model.log_e2;
+    const int groups = (int)std::min<uint64_t>(descs.size(), (uint64_t)a->n_cus * (uint64_t)dynk::auto_guide_groups_per_cu((int)half_width));
+    const hipError_t le = dynk::launch_auto_guide(ag, groups, a->stream);
+    const hipError_t se = hipStreamSynchronize(a->stream);  // descs is a local vector; a fault of the kernel surfaces here
+    HIP_TRY(a, le);
+    HIP_TRY(a, se);
+  } else {
+    HIP_TRY(a, hipStreamSynchronize(a->stream));
+  }
+  b->guided = true;
+  b->guide_hw = half_width;
+  return DYN_OK;
+}
+
+int dyn_batch_set_guide_refine(dyn_batch* b, uint32_t max_rounds) {
+  if (!b) return DYN_ERR_INVALID_ARGUMENT;
+  dyn_aligner* a = b->a;
+  std::lock_guard<std::mutex> lk(a->mu);
+  auto fail = [&](const std::string& msg) {
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = "dyn_batch_set_guide_refine: " + msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  };
+  if (b->async || b->group) return fail("the batch is an asynchronous ticket; a guide is refined on a batch from dyn_batch_create / dyn_batch_create_raw");
+  if (max_rounds < 1 || max_rounds > 64) return fail("max_rounds " + std::to_string(max_rounds) + " is outside [1, 64]");
+  if (!b->guided) return fail("the batch carries no guide; call dyn_batch_set_guide or dyn_batch_auto_guide first");
+  b->guide_refine = max_rounds;
+  return DYN_OK;
+}
+
+int dyn_batch_fetch_guide(dyn_batch* b, int32_t* out, uint64_t count) {
+  if (!b) return DYN_ERR_INVALID_ARGUMENT;
+  dyn_aligner* a = b->a;
+  auto fail = [&](const std::string& msg) {
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = "dyn_batch_fetch_guide: " + msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  };
+  if (!b->guided) return fail("the batch carries no guide; call dyn_batch_set_guide or dyn_batch_auto_guide first");
+  const uint64_t total = b->n ? b->reads[b->n - 1].sig_off + b->reads[b->n - 1].S : 0;
+  if (count != total) return fail("count " + std::to_string(count) + " differs from the batch's " + std::to_string(total) + " samples");
+  if (count && !out) return fail("out is null");
+  if (int rc = need_device(a)) return rc;
+  if (count) HIP_TRY(a, copy_out(a, out, b->d_guide.p, count * 4));
+  return DYN_OK;
+}
+
+int dyn_batch_fetch_guide_rounds(dyn_batch* b, uint32_t* rounds, uint32_t* converged, uint64_t n) {
+  if (!b || !rounds || !converged) return DYN_ERR_INVALID_ARGUMENT;
+  dyn_aligner* a = b->a;
+  auto fail = [&](const std::string& msg) {
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = "dyn_batch_fetch_guide_rounds: " + msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  };
+  if (!b->guided) return fail("the batch carries no guide; call dyn_batch_set_guide or dyn_batch_auto_guide first");
+  if (!b->aligned || !b->last_calc) return fail("the batch was not aligned with calc_probabilities = 1");
+  if (n < b->n) return fail("n is smaller than the batch's read count");
+  if (int rc = need_device(a)) return rc;
+  if (!b->n) return DYN_OK;
+  if (b->gref_ready) {
+    HIP_TRY(a, copy_out(a, rounds, b->d_gref.as<uint32_t>(), b->n * 4));
+    HIP_TRY(a, copy_out(a, converged, b->d_gref.as<uint32_t>() + b->n, b->n * 4));
+    return DYN_OK;
+  }
+  // one alignment and no comparison: every read the device took ran once
+  std::vector<ReadState> st(b->n);
+  HIP_TRY(a, copy_out(a, st.data(), b->d_state.p, b->n * sizeof(ReadState)));
+  for (uint64_t i = 0; i < b->n; ++i) {
+    rounds[i] = (b->reads[i].status == DYN_READ_OK && st[i].status != DYN_READ_TOO_LARGE) ? 1u : 0u;
+    converged[i] = 0u;
+  }
   return DYN_OK;
 }
 

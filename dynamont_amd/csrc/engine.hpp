@@ -286,6 +286,11 @@ struct dyn_batch {
   uint32_t guide_hw = 0;
   dyneng::DevBuf d_guide;       // [samples of the batch] int32 centres (HostRead::sig_off counts from here)
   dyneng::DevBuf d_garena;      // queue head + one lattice arena per workgroup
+  // guide refinement (dyn_batch_set_guide_refine): the next guided align(calc = 1) runs up to guide_refine alignments per read,
+  // each inside the path the one before called, until a read's guide reproduces itself
+  uint32_t guide_refine = 1;
+  dyneng::DevBuf d_gref;        // uint32 [n] rounds | [n] converged | [64] the two list lengths | [n] | [n] the two lists of reads
+  bool gref_ready = false;      // the last job refined: d_gref holds rounds / converged
   uint64_t arena_bytes = 0;     // what the last job asked of d_garena / d_wide: queue head + every workgroup's lattice arena
   bool host_only = false;       // created on a handle without a device: the read table alone (validation, no job)
   dyneng::SessionGeom sess_geom;  // session_plan's decision for this ticket (ok = false: none taken)

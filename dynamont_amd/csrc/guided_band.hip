@@ -285,8 +285,9 @@ __global__ __launch_bounds__(THREADS) void k_guided_reads(const GuidedArgs a) {
     if (threadIdx.x == 0) s_ctl[0] = (int)atomicAdd(a.head, 1u);
     __syncthreads();
     const int k = s_ctl[0];
-    if (k >= a.n_reads) break;
-    const ReadDesc rd = a.descs[k];
+    // a refinement round (launch_guide_refine) hands over the list of the reads still to align and its length on the device
+    if (k >= (a.active ? (int)*a.n_active : a.n_reads)) break;
+    const ReadDesc rd = a.descs[a.active ? a.active[k] : (uint32_t)k];
     const size_t cells = (size_t)rd.T * (size_t)(2 * a.bw + 3);
     double* bE = reinterpret_cast<double*>(arena);
     double* bM = bE + cells;
@@ -349,6 +350,45 @@ void launch_guided_band_margin(const ReadDesc* descs, int n_reads, uint32_t max_
   if (n_reads <= 0 || max_T < 2) return;
   hipLaunchKernelGGL(k_bmargin_guided, dim3((unsigned)n_reads, (max_T + 255u) / 256u), dim3(256), 0, s, descs, st, tb.pathn,
                      tb.segrow, guide, bw, bm);
+}
+
+// ---- guide refinement (dyn_batch_set_guide_refine): the called path becomes the next guide ----
+// grid n_reads x 256 threads: block k owns entry k of the list of reads the launch before it aligned (active_in; null: every
+// descriptor). The read's alignment is counted; an ok read's next guide g'[s] = pathn[s + 1] (0 before the first border) is
+// compared with its guide. Equal in every entry: the read has converged, its result stands. Otherwise, unless this was the last
+// round, g' replaces the guide and the read joins active_out, the list of the next launch.
+__global__ __launch_bounds__(256) void k_guide_refine(const GuideRefine r) {
+  const uint32_t n_in = r.active_in ? *r.n_in : (uint32_t)r.n_reads;
+  if (blockIdx.x >= n_in) return;
+  const uint32_t idx = r.active_in ? r.active_in[blockIdx.x] : blockIdx.x;
+  if (idx >= (uint32_t)r.n_reads) return;
+  const ReadDesc rd = r.descs[idx];
+  if (threadIdx.x == 0) r.rounds[rd.read] += 1u;
+  if (r.st[rd.read].status != 0) return;  // (the read's last alignment failed: that is its result)
+  const int T = (int)rd.T;
+  const int first = rd.N >= 2 ? (int)r.segrow[rd.seg_off] : T;  // lattice row of the first border
+  const uint32_t* __restrict__ pathn = r.pathn + rd.path_off;
+  int32_t* gd = r.guide + rd.sig_off;
+  int differs = 0;
+  for (int s = (int)threadIdx.x; s < T - 1; s += 256) {
+    const int32_t g = s + 1 >= first ? (int32_t)(pathn[s + 1] & 0x7fffffffu) : 0;
+    differs |= g != gd[s];
+  }
+  if (!__syncthreads_or(differs)) {
+    if (threadIdx.x == 0) r.converged[rd.read] = 1u;
+    return;
+  }
+  if (r.last) return;
+  for (int s = (int)threadIdx.x; s < T - 1; s += 256) gd[s] = s + 1 >= first ? (int32_t)(pathn[s + 1] & 0x7fffffffu) : 0;
+  if (threadIdx.x == 0) r.active_out[atomicAdd(r.n_out, 1u)] = idx;
+}
+
+hipError_t launch_guide_refine(const GuideRefine& r, hipStream_t s) {
+  if (r.n_reads <= 0) return hipSuccess;
+  if (!r.rounds || !r.converged || !r.guide || !r.active_out || !r.n_out || (r.active_in && !r.n_in)) return hipErrorInvalidValue;
+  if (const hipError_t e = hipMemsetAsync(r.n_out, 0, 4, s)) return e;
+  hipLaunchKernelGGL(k_guide_refine, dim3((unsigned)r.n_reads), dim3(256), 0, s, r);
+  return hipGetLastError();
 }
 
 uint64_t guided_arena_bytes(uint64_t T, uint64_t bw, int job) {

@@ -29,7 +29,29 @@ struct GuidedArgs {
   const uint64_t* exp_tab; // dynmath::strict_exp_table on the device
   double m1, e2;
   int z_fail_status;
+  // a refinement round (dyn_batch_set_guide_refine): the reads to align are descs[active[0 .. *n_active)], list and length
+  // written on the device by launch_guide_refine. Null: every descriptor
+  const uint32_t* active;
+  const uint32_t* n_active;
 };
+
+// one step of the guide refinement, behind a launch_guided_reads(job 1) over the same descriptors
+struct GuideRefine {
+  const ReadDesc* descs;
+  int n_reads;
+  const ReadState* st;
+  const uint32_t* pathn;      // TraceBuffers::pathn
+  const uint32_t* segrow;     // TraceBuffers::segrow
+  int32_t* guide;             // the batch's guide: rewritten for the reads that go on
+  uint32_t* rounds;           // [reads of the batch] alignments run so far (+1 for every read of active_in)
+  uint32_t* converged;        // [reads of the batch] set to 1 where the called path reproduces the guide
+  const uint32_t* active_in;  // the reads the launch before this step aligned, and their number (null: every descriptor)
+  const uint32_t* n_in;
+  uint32_t* active_out;       // [n_reads] the reads of the next launch, and their number (cleared by launch_guide_refine)
+  uint32_t* n_out;
+  int last;                   // the last round: compare only, the guide stays the one the last alignment used
+};
+hipError_t launch_guide_refine(const GuideRefine& r, hipStream_t s);
 
 // bytes of lattice one workgroup needs for a read of T rows: 25 B per band slot with probabilities (bE, bM doubles; float LPM,
 // float LPE; one decision byte), 16 B for the train job (bE, bM), nothing for the Z-only job (its backward rows never leave

@@ -230,6 +230,8 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   const PoreModel& m = a->model;
   const int z_fail = job == DynJob::Train ? DYN_READ_TRAIN_Z_MISMATCH : DYN_READ_Z_MISMATCH;
   const int guided_job = job == DynJob::Train ? 2 : calc ? 1 : 0;  // launch_guided_reads' job
+  const uint32_t refine_rounds = (b->guided && calc) ? b->guide_refine : 1;  // dyn_batch_set_guide_refine
+  b->gref_ready = false;
 
   // mode "resquiggle"/"ntk": what the reference's NTKAligner does in this snapshot, as observed with the compiled
   // reference (tests/golden/g11_ntk_messages.json): validateInput / sequenceToKmers errors first, then EVERY read fails
@@ -633,6 +635,41 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       ga.e2 = m.log_e2;
       ga.z_fail_status = z_fail;
       HIP_TRY(a, dynk::launch_guided_reads(guided_job, ga, wide_groups, a->stream));
+      // guide refinement (dyn_batch_set_guide_refine): behind every alignment a step that makes the called path the next
+      // guide of the reads whose guide it does not reproduce, and the list of those reads the next alignment's queue. Every
+      // round is enqueued; a round whose list is empty ends at its first queue read. What follows the traceback
+      // (launch_segments and the riders below) runs once, behind the last round
+      if (refine_rounds > 1) {
+        const uint64_t nb = b->n, nw = wide.size();
+        HIP_TRY(a, b->d_gref.ensure((2 * nb + 64 + 2 * nw) * 4));
+        uint32_t* g = b->d_gref.as<uint32_t>();
+        HIP_TRY(a, hipMemsetAsync(g, 0, 2 * nb * 4, a->stream));
+        uint32_t* cnt[2] = {g + 2 * nb, g + 2 * nb + 32};
+        uint32_t* act[2] = {g + 2 * nb + 64, g + 2 * nb + 64 + nw};
+        dynk::GuideRefine gr{};
+        gr.descs = ga.descs;
+        gr.n_reads = ga.n_reads;
+        gr.st = q.st;
+        gr.pathn = q.tb.pathn;
+        gr.segrow = q.tb.segrow;
+        gr.guide = b->d_guide.as<int32_t>();
+        gr.rounds = g;
+        gr.converged = g + nb;
+        for (uint32_t r = 0; r < refine_rounds; ++r) {
+          if (r > 0) {
+            ga.active = act[(r - 1) & 1];
+            ga.n_active = cnt[(r - 1) & 1];
+            HIP_TRY(a, dynk::launch_guided_reads(guided_job, ga, wide_groups, a->stream));
+          }
+          gr.active_in = ga.active;
+          gr.n_in = ga.n_active;
+          gr.active_out = act[r & 1];
+          gr.n_out = cnt[r & 1];
+          gr.last = r + 1 == refine_rounds ? 1 : 0;
+          HIP_TRY(a, dynk::launch_guide_refine(gr, a->stream));
+        }
+        b->gref_ready = true;
+      }
     } else if (!wide.empty()) {
       // one workgroup per wide read at a time, each with a lattice arena for the largest of them; behind the read queue on the
       // compute stream (its results feed the same per-segment kernels / the same host finalisation)

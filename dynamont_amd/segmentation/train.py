@@ -20,6 +20,11 @@ Deliberate differences from the reference (not silently 
 ``--guide-moves HW`` (build-only, default 0 = off): every read is trained, and its Z re-evaluated, inside a window of HW
 lattice columns around the guide its basecaller move table (``mv:B:c``) gives (``Aligner.train_batch_guided``, INTEGRATION.md
 section 3) instead of the band around the fixed diagonal; a read without a usable move table is skipped and counted.
+
+``--guide-auto HW [--guide-rounds R]`` (build-only, default 0 = off; not together with ``--guide-moves``): the same guided
+training path with a guide the library makes itself -- ``Batch.auto_guide(HW)``, refined up to R alignments
+(``Batch.set_guide_refine``) -- so that no ``mv`` tag is needed. A read that does not align inside its own guide is reported
+and left out of its batch; the reads whose guide did not reproduce itself within R alignments are trained and counted.
 """
 from __future__ import annotations
 
@@ -111,7 +116,15 @@ def parse(argv=None) -> Namespace:
     p.add_argument("--guide-moves", type=int, default=0, metavar="HW",
                    help="train inside a window of HW lattice columns on either side of the guide the basecaller's move table "
                         "(mv:B:c) gives, instead of the band around the diagonal; reads without a move table are skipped (0: off)")
-    return p.parse_args(argv)
+    p.add_argument("--guide-auto", type=int, default=0, metavar="HW",
+                   help="train inside a window of HW lattice columns on either side of a guide made on the GPU from the signal and "
+                        "the sequence alone (no move table needed); not together with --guide-moves (0: off)")
+    p.add_argument("--guide-rounds", type=int, default=8, metavar="R",
+                   help="with --guide-auto: alignments per read at the most while its guide is refined (1 .. 64)")
+    args = p.parse_args(argv)
+    if args.guide_auto and args.guide_moves:
+        p.error("--guide-auto and --guide-moves are mutually exclusive")
+    return args
 
 
 def _code_order(model: dict, k: int, rna: bool):
@@ -200,6 +213,29 @@ def _train_items(al: Aligner, items, pooled: bool, raw: bool, guide_moves: int =
         return b.fetch_train(pooled)
 
 
+def _attach_auto_guides(al: Aligner, items, raw: bool, half_width: int, rounds: int):
+    """--guide-auto: one refined, self-guided alignment of the batch (Batch.auto_guide, Batch.set_guide_refine). Returns the items
+    that aligned ok, each with its final guide as fourth entry (what the guided training path takes), the (readid, error) pairs
+    of the others and the number of kept reads whose guide did not converge."""
+    if raw:
+        f32 = items[0][0][0].dtype == np.float32
+        b = al.batch_raw([x[0][0] for x in items], [x[1] for x in items], [x[0][1] for x in items], [x[0][2] for x in items],
+                         window=7, n_sigmas=5.0, f32=f32)
+    else:
+        b = al.batch([x[0] for x in items], [x[1] for x in items])
+    with b:
+        b.auto_guide(half_width)
+        if rounds != 1:
+            b.set_guide_refine(rounds)
+        b.align(True)
+        res = b.fetch()
+        _, converged = b.guide_rounds()
+        guides = b.guide()
+    kept = [tuple(x[:3]) + (guides[j],) for j, x in enumerate(items) if res.status[j] == 0]
+    failed = [(x[2], res.error(j)) for j, x in enumerate(items) if res.status[j] != 0]
+    return kept, failed, int(sum(1 for j in range(len(items)) if res.status[j] == 0 and not converged[j]))
+
+
 def _z_items(al: Aligner, items, raw: bool, guide_moves: int = 0):
     """guide_moves > 0: the guided Z-only job over the same guides, so that the Z change compares like with like"""
     if not raw:
@@ -218,16 +254,21 @@ def _z_items(al: Aligner, items, raw: bool, guide_moves: int = 0):
 
 def train(data_path: str, basecalls: str, batch_size: int, epochs: int, param_file: str, mode: str, model_path: str,
           max_batches, pore: str, minq=None, device: int = 0, aggregate: str = "window-mean", comm=None,
-          host_preprocess: bool = False, reference_zcheck: bool = False, guide_moves: int = 0) -> None:
+          host_preprocess: bool = False, reference_zcheck: bool = False, guide_moves: int = 0, guide_auto: int = 0,
+          guide_rounds: int = 8) -> None:
     """Counterpart of train.py:68-253. ``comm`` (optional, dynamont_amd.parallel.Comm): multi-GPU
     run -- accepted reads are dealt round-robin to the ranks (each rank fills ``batch_size`` reads of
     its own per batch, so all ranks reach a batch boundary on the same read), the pooled sufficient
     statistics, transition counts and Z changes are summed over ranks, every rank computes the same
     model, and rank 0 owns params.csv and the model files in ``outdir``. ``guide_moves`` > 0: the guided band around every
     read's move-table guide at that half width (the guide travels with its item, so a rank trains the reads it is dealt with
-    their own guides; run with one rank so far)."""
+    their own guides; run with one rank so far). ``guide_auto`` > 0: the same path with guides the library makes itself at
+    that half width, refined up to ``guide_rounds`` alignments (no move table needed)."""
     if guide_moves < 0:
         raise ValueError("--guide-moves must be >= 0")
+    if guide_auto < 0 or (guide_auto and guide_moves):
+        raise ValueError("--guide-auto must be >= 0 and is not combined with --guide-moves")
+    guide_hw = guide_moves or guide_auto  # the half width of the guided training path, whichever made the guides
     if mode != "basic":
         print(f"Mode {mode} not implemented", file=sys.stderr)
         sys.exit(1)
@@ -254,7 +295,7 @@ def train(data_path: str, basecalls: str, batch_size: int, epochs: int, param_fi
     trans = {p: ManagedList([v]) for p, v in transition_params.items()}
     any_seen = False
     al = None
-    i = qskips = mismatches = noguides = 0
+    i = qskips = mismatches = noguides = auto_failed = auto_open = 0
     with open(param_file, "w") as pw:
         pw.write("epoch,batch,read," + "".join(p + "," for p in transition_params) + "Zchange\n")
         for e in range(epochs):
@@ -283,7 +324,15 @@ def train(data_path: str, basecalls: str, batch_size: int, epochs: int, param_fi
                     al = Aligner(trained_model, pore, mode="basic", threads=4, band=400, device=device)
                     al.set_train_zcheck(reference_zcheck)
                 cur_mean, cur_sd = al.model_table()
-                res = _train_items(al, items, aggregate == "pooled", raw=not host_preprocess, guide_moves=guide_moves)
+                if guide_auto > 0:
+                    items, failed, not_converged = _attach_auto_guides(al, items, not host_preprocess, guide_auto, guide_rounds)
+                    auto_failed += len(failed)
+                    auto_open += not_converged
+                    for readid, err in failed:
+                        print(f"error: native, {err} Sid: {readid} (no alignment inside its own guide: left out)", file=sys.stderr)
+                    if not items:
+                        continue
+                res = _train_items(al, items, aggregate == "pooled", raw=not host_preprocess, guide_moves=guide_hw)
                 preZ = {}
                 for j, readid in enumerate(x[2] for x in items):
                     if res.status[j] != 0:
@@ -341,7 +390,7 @@ def train(data_path: str, basecalls: str, batch_size: int, epochs: int, param_fi
                 pw.flush()
                 # rerun with the new model to compare Zs (train.py:226-242)
                 al.set_model(new_mean, new_sd)  # = Aligner(trained_model, ...) of train.py:227
-                post = _z_items(al, items, raw=not host_preprocess, guide_moves=guide_moves)
+                post = _z_items(al, items, raw=not host_preprocess, guide_moves=guide_hw)
                 dZ = np.array([float(post.Z[j]) - z for j, z in preZ.items() if post.status[j] == 0])
                 print(f"Z changes: {dZ}", file=sys.stderr)
                 if comm is not None:
@@ -360,6 +409,10 @@ def train(data_path: str, basecalls: str, batch_size: int, epochs: int, param_fi
     if guide_moves > 0:
         print(f"Skipped reads due to a signal mismatch: {mismatches}", file=sys.stderr)
         print(f"Skipped reads without a move table (mv): {noguides}", file=sys.stderr)
+    if guide_auto > 0:
+        print(f"Skipped reads due to a signal mismatch: {mismatches}", file=sys.stderr)
+        print(f"Reads left out (no alignment inside their own guide): {auto_failed}", file=sys.stderr)
+        print(f"Reads whose guide did not converge within {guide_rounds} alignments: {auto_open}", file=sys.stderr)
 
 
 def main(argv=None) -> None:
@@ -386,7 +439,8 @@ def main(argv=None) -> None:
     with parallel.abort_on_error(comm):
         train(args.raw, args.basecalls, args.batch_size, args.epochs, param_file, "basic", model_path, args.max_batches,
               args.pore, args.qscore, device=local_rank if comm else args.device, aggregate=args.aggregate, comm=comm,
-              host_preprocess=args.host_preprocess, reference_zcheck=args.reference_zcheck, guide_moves=args.guide_moves)
+              host_preprocess=args.host_preprocess, reference_zcheck=args.reference_zcheck, guide_moves=args.guide_moves,
+              guide_auto=args.guide_auto, guide_rounds=args.guide_rounds)
         if comm is not None:
             comm.close()  # (collective: every rank has finished its exchanges)
 

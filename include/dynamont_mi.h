@@ -753,6 +753,31 @@ int dyn_batch_train_guided(dyn_batch* b);
  * not fit gets DYN_READ_TOO_LARGE. DYN_ERR_INVALID_ARGUMENT + message: NULL, a batch without a guide, an asynchronous ticket.
  * dyn_aligner_set_rescale and dyn_aligner_set_border_confidence are align's switches and are ignored, as dyn_batch_train
  * ignores them. */
+/* (added within ABI 10) Self-guided band: the library makes the batch's guide itself. A pre-pass kernel (k_auto_guide) runs a
+ * forward max-plus sweep over every ok read, inside a window of `half_width` columns on either side of a centre that follows
+ * the row's best cell, and installs the centres as the batch's guide exactly as dyn_batch_set_guide would (definition:
+ * INTEGRATION.md section 3). The guide never decreases, lies in [0, N - 1] and connects the lattice's corners. half_width:
+ * 1 .. 2046; it is also the half width of the batch's guided jobs. For batches from dyn_batch_create / dyn_batch_create_raw
+ * that have not run yet. DYN_ERR_INVALID_ARGUMENT + message: half_width outside [1, 2046], an asynchronous ticket, a batch
+ * that has already run; DYN_ERR_RUNTIME on a DYN_DEVICE_HOST_ONLY handle ("no GPU bound to this handle"). */
+int dyn_batch_auto_guide(dyn_batch* b, uint32_t half_width);
+/* (added within ABI 10) Guide refinement: the batch's next dyn_batch_align(b, 1) runs up to max_rounds alignments per read.
+ * After an alignment, an ok read's called path becomes its next guide, g'[s] = the path's column at lattice row s + 1 (0
+ * before the first border); where g' equals the guide in every entry the read has converged and its result stands, otherwise
+ * it is aligned again inside g', at the same half width. Converged reads are not computed again. A read's status and outputs
+ * are those of its last alignment; event stats, segment scores, band margins and the k-mer summary are computed once, after
+ * that. max_rounds: 1 .. 64, 1 (the default) = one alignment and no comparison. DYN_ERR_INVALID_ARGUMENT + message:
+ * max_rounds outside [1, 64], a batch without a guide, an asynchronous ticket. With max_rounds > 1 dyn_batch_align(b, 0) and
+ * dyn_batch_train_guided are refused (neither has a called path). */
+int dyn_batch_set_guide_refine(dyn_batch* b, uint32_t max_rounds);
+/* (added within ABI 10) The batch's current guide, out[count] laid out as dyn_batch_set_guide's centres (count = the batch's
+ * samples): what dyn_batch_set_guide or dyn_batch_auto_guide installed, and after a refined alignment every read's guide of
+ * its last round. Entries of reads that failed validation: as set (0 after dyn_batch_auto_guide). */
+int dyn_batch_fetch_guide(dyn_batch* b, int32_t* out, uint64_t count);
+/* (added within ABI 10) Per read of a guided batch after dyn_batch_align(b, 1): rounds[i] = the alignments read i ran (0 for a
+ * read that never reached the device), converged[i] = 1 where its last called path reproduced its guide (always 0 without
+ * dyn_batch_set_guide_refine(max_rounds > 1)). n >= the batch's read count. */
+int dyn_batch_fetch_guide_rounds(dyn_batch* b, uint32_t* rounds, uint32_t* converged, uint64_t n);
 /* (added within ABI 10) Device bytes the batch's last job allocated for per-workgroup lattice arenas: workgroups x the largest
  * read's lattice, for the guided kernel (dyn_batch_set_guide) or the generic wide-band kernel; 0 for a batch whose reads all took
  * the paged read queue (its pool: dyn_timing.pool_pages) and for a Z-only guided job; 16 B per cell for dyn_batch_train_guided. */

@@ -5,6 +5,7 @@
 
 #include "../../dynamont_amd/csrc/nt_kernels.hpp"
 #include "../../dynamont_amd/csrc/guided_band_kernels.hpp"
+#include "../../dynamont_amd/csrc/auto_guide_kernels.hpp"
 
 namespace dynk {
 
@@ -56,5 +57,8 @@ void launch_guided_band_margin(const ReadDesc*, int, uint32_t, const ReadState*,
                                hipStream_t) {
   no_device("launch_guided_band_margin");
 }
+hipError_t launch_guide_refine(const GuideRefine&, hipStream_t) { no_device("launch_guide_refine"); }
+int auto_guide_groups_per_cu(int) { return 1; }
+hipError_t launch_auto_guide(const AutoGuideArgs&, int, hipStream_t) { no_device("launch_auto_guide"); }
 
 }  // namespace dynk
