@@ -592,6 +592,16 @@ class AsyncBatch:
     device_results = Batch.device_results
     device_pooled = Batch.device_pooled
 
+    def signals(self, count: int) -> np.ndarray:
+        """The ticket's device-resident (normalised, Hampel-filtered) samples, concatenated: ``count`` = the number of
+        samples submitted. Served after ``wait()`` and before ``close()``, whether or not the launch was shared."""
+        self.wait()
+        out = np.empty(int(count))
+        rc = self._L.dyn_batch_signals(self._h, _ptr(out, N.c_double_p), out.size)
+        if rc != N.DYN_OK:
+            _raise(rc, self._al.last_error())
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.dyn_batch_destroy(self._h)  # waits first if the batch is still in flight
