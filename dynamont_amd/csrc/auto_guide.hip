@@ -1,6 +1,6 @@
 // auto_guide.hip -- the pre-pass of dyn_batch_auto_guide: k_auto_guide derives every read's guide on the device from the signal
 // and the emission parameters the batch already holds there (definition and per-cell arithmetic: auto_guide_kernels.hpp).
-// Modelled on guided_read (guided_band.hip): the same band-column addressing (B = 2 hw + 3 band columns per row incl. the two
+// Modelled on band_read (band_reads.hip): the same band-column addressing (B = 2 hw + 3 band columns per row incl. the two
 // guards, start_t = c_t - hw, band column b <-> lattice column n = start_t + b - 1, a shift >= 0 of any size between rows, a
 // neighbour row's column outside [0, B) reads as -inf), the same THREADS x CPT shapes picked from B, one workgroup per read,
 // reads taken off a queue. What differs:
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(THREADS) void k_auto_guide(const AutoGuideArgs a) {
 }
 
 namespace {
-// shapes, narrowest first: B = 2 hw + 3 <= THREADS * CPT (guided_band.hip's); groups: an upper bound on the workgroups per CU
+// shapes, narrowest first: B = 2 hw + 3 <= THREADS * CPT (band_reads.hip's); groups: an upper bound on the workgroups per CU
 struct Shape { int threads, cpt, groups; };
 constexpr Shape SHAPES[] = {{64, 1, 16}, {64, 4, 16}, {256, 16, 2}};
 const Shape& shape_of(int bw) {

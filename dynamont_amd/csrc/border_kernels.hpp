@@ -1,6 +1,6 @@
 // border_kernels.hpp -- per-border posterior confidence (dyn_aligner_set_border_confidence): how much of the lattice's
 // posterior mass for "segment n starts here" lies on the called border, and within W rows of it. Included by nt_kernels.hip
-// and wide_band.hip (the phase behind traceback / mpost, while the read's lattice is still in its pages or arena) and by
+// and band_reads.hip (the phase behind traceback / mpost, while the read's lattice is still in its pages or arena) and by
 // tests/device_math/border_confidence.hip, which runs border_window_sum on lattices the test writes itself.
 //
 // Definition (include/dynamont_mi.h). Output row j of an ok read is lattice column n = j + 1, the row
@@ -13,7 +13,7 @@
 //   BorderCellSeparate  separate layout (JOB_ALIGN): LPM rebuilt the way mpost does, from the float LPE and bE of (t-1, n-1),
 //                       bE(t+1, n), the two emissions of column n, Zb and m1
 //   BorderCellInplace   in-place layout (JOB_ALIGN_INPLACE): the float LPM half of the slot
-//   BorderCellWide      wide_band.hip: lp[2 * cell] in the reference's band-column addressing
+//   BorderCellWide      band_reads.hip (diagonal window): lp[2 * cell] in the reference's band-column addressing
 // EVERY accessor checks the band explicitly, for every cell it reads: a band slot is n mod 448, and a slot outside the band
 // carries "no k-mer" values, another column's values or whatever the arena held before -- never something to rely on.
 // Lane mapping: one lane per border (as mpost), the window rows in groups of eight whose loads are in flight together; no
@@ -32,11 +32,14 @@ __device__ __forceinline__ int border_row_pos(int s) {
   return j < 6 ? (j >> 1) * 128 + lane * 2 + (j & 1) : 384 + lane;
 }
 
+// centre of the reference's band in lattice row t: size_t(t * RATIO) of NT_aligner_api.cpp:100, ratio = double(N) / double(T)
+__device__ __forceinline__ int diagonal_centre(int t, double ratio) { return (int)__dmul_rn((double)t, ratio); }
+
 // the band of a read: which cells (t, n) the reference's sweeps fill (computeBounds; rows 1 .. T-1, columns 1 .. N-1)
 struct BorderBand {
   int T, N, bw;
   double ratio;
-  __device__ __forceinline__ int start(int t) const { return (int)__dmul_rn((double)t, ratio) - bw; }  // size_t(t * RATIO) - bw
+  __device__ __forceinline__ int start(int t) const { return diagonal_centre(t, ratio) - bw; }
   __device__ __forceinline__ bool holds(int t, int n) const {
     if (t < 1 || t >= T) return false;
     const int s = start(t);

@@ -60,7 +60,7 @@ void attach_cache(dyn_batch* b) {
   dyneng::BufCache* c = &b->a->cache;
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_wide, &b->d_guide, &b->d_garena, &b->d_gref})
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_arena, &b->d_guide, &b->d_gref})
     d->cache = c;
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->cache = c;
 }
@@ -99,7 +99,7 @@ int host_prepare(dyn_batch* b, const PoreModel& m, bool pinned, uint64_t n, cons
     cap += r.kc;
     r.status = m.validate(r.S, r.L);
     // 448 band slots per lattice row in the register sweeps: a read whose half band min(band / 2, columns / 2) does not fit
-    // them takes the generic kernel (wide_band.hip), which holds a row of up to 4 096 band columns in LDS
+    // them takes the banded-lattice kernel (band_reads.hip), which holds a row of up to 4 096 band columns in LDS
     if (r.status == DYN_READ_OK) {
       const uint64_t hb = std::min<uint64_t>(m.half_band, (r.kc + 1) / 2);
       if (hb > (uint64_t)dynk::WIDE_MAX_HALF_BAND) r.status = DYN_READ_BAND_TOO_WIDE;
@@ -913,7 +913,7 @@ void dyn_batch_destroy(dyn_batch* b) {
   }
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl, &b->d_wide, &b->d_guide, &b->d_garena, &b->d_gref})
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl, &b->d_arena, &b->d_guide, &b->d_gref})
     d->release();
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->release();
   for (hipEvent_t e : b->events) (void)hipEventDestroy(e);
@@ -1195,7 +1195,7 @@ int dyn_batch_auto_guide(dyn_batch* b, uint32_t half_width) {
       descs[k] = d;
     }
     HIP_TRY(a, b->d_descs.ensure(descs.size() * sizeof(ReadDesc)));
-    HIP_TRY(a, b->d_garena.ensure(256));
+    HIP_TRY(a, b->d_arena.ensure(256));
     HIP_TRY(a, hipMemcpyAsync(b->d_descs.p, descs.data(), descs.size() * sizeof(ReadDesc), hipMemcpyHostToDevice, a->stream));
     dynk::AutoGuideArgs ag{};
     ag.descs = b->d_descs.as<ReadDesc>();
@@ -1204,7 +1204,7 @@ int dyn_batch_auto_guide(dyn_batch* b, uint32_t half_width) {
     ag.sig = b->d_sig.as<double>();
     ag.par = b->d_par.as<Emis>();
     ag.guide = b->d_guide.as<int32_t>();
-    ag.head = b->d_garena.as<uint32_t>();
+    ag.head = b->d_arena.as<uint32_t>();
     ag.m1 = a->model.log_m1;
     ag.e2 = a->model.log_e2;
     const int groups = (int)std::min<uint64_t>(descs.size(), (uint64_t)a->n_cus * (uint64_t)dynk::auto_guide_groups_per_cu((int)half_width));

@@ -203,7 +203,7 @@ struct HostRead {
   uint64_t sig_off = 0, flat_off = 0 /* into kmers / per-column tables */, seg_off = 0;
   int32_t status = 0;
   char bad = 0;
-  bool wide = false;  // half band above the register sweeps' 223: the read takes the generic kernel (wide_band.hip)
+  bool wide = false;  // half band above the register sweeps' 223: the read takes the banded-lattice kernel (band_reads.hip)
 };
 
 enum class DynJob { AlignZ, AlignFull, Train };
@@ -277,21 +277,20 @@ struct dyn_batch {
   dyneng::PinnedBuf h_sig;                     // staging of pageable caller signals (asynchronous path)
   // raw asynchronous path: [offsets | shift | scale | raw samples] staged in h_sig; device-side scratch of the preprocessing
   dyneng::DevBuf d_norm, d_meta;
-  dyneng::DevBuf d_wide;        // wide-band reads (wide_band.hip): queue head + one lattice arena per workgroup
-  uint64_t n_wide = 0;          // reads of this batch that take the generic kernel
-  // guided band (guided_band.hip, dyn_batch_set_guide): every ok read of a guided batch takes the guided kernel, inside a window
+  uint64_t n_wide = 0;          // reads of this batch that take the banded-lattice kernel for their half band
+  dyneng::DevBuf d_arena;       // band_reads.hip (wide reads, or every read of a guided batch): queue head + one lattice arena per workgroup
+  // guided band (dyn_batch_set_guide): every ok read of a guided batch takes the banded-lattice kernel, inside a window
   // of half width guide_hw around its guide (align jobs, and the train job through dyn_batch_train_guided alone); a synchronous
   // batch only, so it never joins a session or a merged launch
   bool guided = false;
   uint32_t guide_hw = 0;
   dyneng::DevBuf d_guide;       // [samples of the batch] int32 centres (HostRead::sig_off counts from here)
-  dyneng::DevBuf d_garena;      // queue head + one lattice arena per workgroup
   // guide refinement (dyn_batch_set_guide_refine): the next guided align(calc = 1) runs up to guide_refine alignments per read,
   // each inside the path the one before called, until a read's guide reproduces itself
   uint32_t guide_refine = 1;
   dyneng::DevBuf d_gref;        // uint32 [n] rounds | [n] converged | [64] the two list lengths | [n] | [n] the two lists of reads
   bool gref_ready = false;      // the last job refined: d_gref holds rounds / converged
-  uint64_t arena_bytes = 0;     // what the last job asked of d_garena / d_wide: queue head + every workgroup's lattice arena
+  uint64_t arena_bytes = 0;     // what the last job asked of d_arena beyond the queue head: every workgroup's lattice arena
   bool host_only = false;       // created on a handle without a device: the read table alone (validation, no job)
   dyneng::SessionGeom sess_geom;  // session_plan's decision for this ticket (ok = false: none taken)
   bool has_raw = false;

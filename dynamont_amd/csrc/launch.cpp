@@ -1,8 +1,9 @@
 // launch.cpp -- one CLASSIC launch per (merged) batch: the planner of page-starved queues (plan_queue), the spread order of
-// paged sessions, enqueue_job (read descriptors, lattice pool, k_read_queue, the generic wide-band kernel, the per-segment
+// paged sessions, enqueue_job (read descriptors, lattice pool, k_read_queue, the banded-lattice kernel, the per-segment
 // kernels -- everything enqueued on the compute stream without a host synchronisation) and collect_timing. Reference counterpart:
 // the body of NTAligner::align / train (NT_aligner_api.cpp:230-312, 567-639) for one read at a time.
 #include "engine_internal.hpp"
+#include "band_reads.hpp"
 #include "dp_math_strict.hpp"
 #include "guided_band_kernels.hpp"
 
@@ -229,7 +230,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   const bool calc = job == DynJob::AlignFull;
   const PoreModel& m = a->model;
   const int z_fail = job == DynJob::Train ? DYN_READ_TRAIN_Z_MISMATCH : DYN_READ_Z_MISMATCH;
-  const int guided_job = job == DynJob::Train ? 2 : calc ? 1 : 0;  // launch_guided_reads' job
+  const int band_job = job == DynJob::Train ? 2 : calc ? 1 : 0;  // launch_band_reads' job
   const uint32_t refine_rounds = (b->guided && calc) ? b->guide_refine : 1;  // dyn_batch_set_guide_refine
   b->gref_ready = false;
 
@@ -260,9 +261,10 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     const HostRead& r = b->reads[i];
     if (r.status != DYN_READ_OK) continue;
     if (a->ntk) continue;  // no read reaches the device; its status is set below
-    // a guided batch (dyn_batch_set_guide): every read takes the guided kernel (guided_band.hip), whatever its N -- its
-    // descriptors and its arena are laid out like the wide reads', which such a batch then has none of
-    if (r.wide || b->guided) {  // the generic kernel (wide_band.hip): the reference's own arithmetic in every cell, no queue, no pages
+    // the banded-lattice kernel (band_reads.hip): the reference's own arithmetic in every cell, no pages. A wide read takes it
+    // inside the reference's band, and every read of a guided batch (dyn_batch_set_guide), whatever its N, inside its guide's
+    // window (such a batch then has no read for the read queue)
+    if (r.wide || b->guided) {
       wide.push_back((uint32_t)i);
       continue;
     }
@@ -463,19 +465,19 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     tm.cells += (uint64_t)d.T * std::min<uint64_t>(2ull * d.bw + 1, d.N);
     tm.samples += r.S;
   }
-  // wide-band reads: their descriptors FOLLOW the queue's (the read queue sees the first n_ok, the per-segment kernels all)
+  // the reads of the banded-lattice kernel: their descriptors FOLLOW the queue's (the read queue sees the first n_ok, the
+  // per-segment kernels all). One lattice arena per workgroup, sized for the largest of them (none for Z only)
   uint64_t wide_arena = 0;
   int wide_groups = 0;
   if (!wide.empty()) {
     size_t free_b = 0, total_b = 0;
     HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
-    uint64_t room = (uint64_t)((double)(free_b + (b->guided ? b->d_garena.bytes : b->d_wide.bytes) + parked_bytes(a->device)) * 0.8);
+    uint64_t room = (uint64_t)((double)(free_b + b->d_arena.bytes + parked_bytes(a->device)) * 0.8);
     if (b->guided && a->mem_budget && room > a->mem_budget) room = a->mem_budget;
     size_t wr = 0;
     for (uint32_t i : wide) {
       const HostRead& r = b->reads[i];
-      const uint64_t need = b->guided ? dynk::guided_arena_bytes(r.S + 1, b->guide_hw, guided_job)
-                                      : dynk::wide_arena_bytes(r.S + 1, std::min<uint64_t>(m.half_band, (r.kc + 1) / 2), calc);
+      const uint64_t need = dynk::band_arena_bytes(r.S + 1, b->guided ? b->guide_hw : std::min<uint64_t>(m.half_band, (r.kc + 1) / 2), band_job);
       if (need > room) st[i].status = DYN_READ_TOO_LARGE;
       else {
         wide_arena = std::max(wide_arena, need);
@@ -486,10 +488,9 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       wide.resize(wr);
       if (b->n) HIP_TRY(a, hipMemcpyAsync(b->d_state.p, st, b->n * sizeof(ReadState), hipMemcpyHostToDevice, a->stream));
     }
-    if (!wide.empty() && b->guided)
-      wide_groups = (int)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)wide.size(), (uint64_t)a->n_cus * (uint64_t)dynk::guided_groups_per_cu((int)b->guide_hw, guided_job),
+    if (!wide.empty())
+      wide_groups = (int)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)wide.size(), (uint64_t)a->n_cus * (uint64_t)dynk::band_groups_per_cu(b->guided, (int)b->guide_hw, band_job),
                                                                    wide_arena ? room / wide_arena : ~0ull}));
-    else if (!wide.empty()) wide_groups = (int)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)wide.size(), (uint64_t)a->n_cus, room / wide_arena}));
   }
   b->arena_bytes = 0;
   const size_t n_all = n_ok + wide.size();
@@ -589,7 +590,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
                                                    : dynk::JOB_ALIGN_INPLACE;
   if (!b->ev_done) HIP_TRY(a, hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
   // The plan above (order, pages, strict rows) depends on T, N and the k-mers only: every pass reuses it. Each pass resets
-  // what a launch resets -- per-read state, queue head and page pool (k_pool_init), the wide-band head (launch_wide_reads).
+  // what a launch resets -- per-read state, queue head and page pool (k_pool_init), the banded-lattice kernel's head (launch_band_reads).
   for (int pass = 0; pass < n_pass; ++pass) {
     if (pass > 0 && b->n) HIP_TRY(a, hipMemcpyAsync(b->d_state.p, st, b->n * sizeof(ReadState), hipMemcpyHostToDevice, a->stream));
     dynk::launch_pool_init(pool, used_pages, (int)n_static, a->stream);
@@ -607,34 +608,38 @@ int enqueue_job(dyn_batch* b, DynJob job) {
                               hipMemcpyDeviceToHost, a->stream));
     // (Running the per-segment kernels on a stream of their own, beside the next batch's read queue, was measured:
     //  the 0.35 ms gap it closes comes back as a 0.4 ms slower start of that read queue -- same-box A/B, no gain.)
-    if (!wide.empty() && b->guided) {
-      // the guided kernel: a queue of its own behind the (empty) read queue, one lattice arena per workgroup (none for Z only)
+    if (!wide.empty()) {
+      // a queue of its own behind the read queue on the compute stream (its results feed the same per-segment kernels / the
+      // same host finalisation)
       if (pass == 0) {
         const uint64_t want = 256 + (uint64_t)wide_groups * wide_arena;
         size_t free_b = 0, total_b = 0;
         HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
-        if (want > b->d_garena.bytes && want > (uint64_t)((double)free_b * 0.95)) free_parked(a->device);  // (counted as room above)
-        HIP_TRY(a, b->d_garena.ensure(want));
+        if (want > b->d_arena.bytes && want > (uint64_t)((double)free_b * 0.95)) free_parked(a->device);  // (counted as room above)
+        HIP_TRY(a, b->d_arena.ensure(want));
         b->arena_bytes = want - 256;
       }
-      dynk::GuidedArgs ga{};
-      ga.descs = q.descs + n_ok;
-      ga.n_reads = (int)wide.size();
-      ga.bw = (int)b->guide_hw;
-      ga.sig = q.sig;
-      ga.par = q.par;
-      ga.guide = b->d_guide.as<int32_t>();
-      ga.st = q.st;
-      ga.tb = q.tb;
-      ga.tr = q.tr;
-      ga.head = b->d_garena.as<uint32_t>();
-      ga.arena = b->d_garena.as<char>() + 256;
-      ga.arena_bytes = wide_arena;
-      ga.exp_tab = reinterpret_cast<const uint64_t*>(a->d_sptab.as<dynmath::SoftplusNode>() + dynmath::SP_NODES + dynmath::EXP128_NODES);
-      ga.m1 = m.log_m1;
-      ga.e2 = m.log_e2;
-      ga.z_fail_status = z_fail;
-      HIP_TRY(a, dynk::launch_guided_reads(guided_job, ga, wide_groups, a->stream));
+      dynk::BandArgs ba{};
+      ba.descs = q.descs + n_ok;
+      ba.n_reads = (int)wide.size();
+      ba.bw = (int)b->guide_hw;
+      ba.sig = q.sig;
+      ba.par = q.par;
+      ba.guide = b->guided ? b->d_guide.as<int32_t>() : nullptr;  // null: the diagonal window
+      ba.st = q.st;
+      ba.tb = q.tb;
+      ba.tr = q.tr;
+      ba.head = b->d_arena.as<uint32_t>();
+      ba.arena = b->d_arena.as<char>() + 256;
+      ba.arena_bytes = wide_arena;
+      ba.exp_tab = reinterpret_cast<const uint64_t*>(a->d_sptab.as<dynmath::SoftplusNode>() + dynmath::SP_NODES + dynmath::EXP128_NODES);
+      ba.m1 = m.log_m1;
+      ba.e2 = m.log_e2;
+      ba.z_fail_status = z_fail;
+      ba.border_window = q.border_window;  // (guided batches refuse the rider: dynamont_mi.cpp)
+      ba.border_p = q.border_p;
+      ba.border_window_p = q.border_window_p;
+      HIP_TRY(a, dynk::launch_band_reads(band_job, ba, wide_groups, a->stream));
       // guide refinement (dyn_batch_set_guide_refine): behind every alignment a step that makes the called path the next
       // guide of the reads whose guide it does not reproduce, and the list of those reads the next alignment's queue. Every
       // round is enqueued; a round whose list is empty ends at its first queue read. What follows the traceback
@@ -647,8 +652,8 @@ int enqueue_job(dyn_batch* b, DynJob job) {
         uint32_t* cnt[2] = {g + 2 * nb, g + 2 * nb + 32};
         uint32_t* act[2] = {g + 2 * nb + 64, g + 2 * nb + 64 + nw};
         dynk::GuideRefine gr{};
-        gr.descs = ga.descs;
-        gr.n_reads = ga.n_reads;
+        gr.descs = ba.descs;
+        gr.n_reads = ba.n_reads;
         gr.st = q.st;
         gr.pathn = q.tb.pathn;
         gr.segrow = q.tb.segrow;
@@ -657,12 +662,12 @@ int enqueue_job(dyn_batch* b, DynJob job) {
         gr.converged = g + nb;
         for (uint32_t r = 0; r < refine_rounds; ++r) {
           if (r > 0) {
-            ga.active = act[(r - 1) & 1];
-            ga.n_active = cnt[(r - 1) & 1];
-            HIP_TRY(a, dynk::launch_guided_reads(guided_job, ga, wide_groups, a->stream));
+            ba.active = act[(r - 1) & 1];
+            ba.n_active = cnt[(r - 1) & 1];
+            HIP_TRY(a, dynk::launch_band_reads(band_job, ba, wide_groups, a->stream));
           }
-          gr.active_in = ga.active;
-          gr.n_in = ga.n_active;
+          gr.active_in = ba.active;
+          gr.n_in = ba.n_active;
           gr.active_out = act[r & 1];
           gr.n_out = cnt[r & 1];
           gr.last = r + 1 == refine_rounds ? 1 : 0;
@@ -670,36 +675,6 @@ int enqueue_job(dyn_batch* b, DynJob job) {
         }
         b->gref_ready = true;
       }
-    } else if (!wide.empty()) {
-      // one workgroup per wide read at a time, each with a lattice arena for the largest of them; behind the read queue on the
-      // compute stream (its results feed the same per-segment kernels / the same host finalisation)
-      if (pass == 0) {
-        const uint64_t want = 256 + (uint64_t)wide_groups * wide_arena;
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
-        if (want > b->d_wide.bytes && want > (uint64_t)((double)free_b * 0.95)) free_parked(a->device);  // (counted as room above)
-        HIP_TRY(a, b->d_wide.ensure(want));
-        b->arena_bytes = want - 256;
-      }
-      dynk::WideArgs wa{};
-      wa.descs = q.descs + n_ok;
-      wa.n_reads = (int)wide.size();
-      wa.sig = q.sig;
-      wa.par = q.par;
-      wa.st = q.st;
-      wa.tb = q.tb;
-      wa.tr = q.tr;
-      wa.head = b->d_wide.as<uint32_t>();
-      wa.arena = b->d_wide.as<char>() + 256;
-      wa.arena_bytes = wide_arena;
-      wa.exp_tab = reinterpret_cast<const uint64_t*>(a->d_sptab.as<dynmath::SoftplusNode>() + dynmath::SP_NODES + dynmath::EXP128_NODES);
-      wa.m1 = m.log_m1;
-      wa.e2 = m.log_e2;
-      wa.z_fail_status = z_fail;
-      wa.border_window = q.border_window;
-      wa.border_p = q.border_p;
-      wa.border_window_p = q.border_window_p;
-      dynk::launch_wide_reads(job == DynJob::Train ? 2 : calc ? 1 : 0, wa, wide_groups, a->stream);
     }
     // between two passes: the fit of every read and its signal recomputed from x0. (The per-segment kernels run once, after
     // the last pass: the fit reads the borders the traceback wrote, segrow, and nothing of k_median / k_final.)

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DYN_ABI_VERSION 10 /* 10 (number kept; look the symbol up): guided-band training: dyn_batch_train_guided (additive). 10 (number kept; look the symbols up): guided band: dyn_batch_set_guide, dyn_batch_arena_bytes (additive). 10 (number kept; look the symbols up): band-margin diagnostics: dyn_aligner_set_band_margin, dyn_batch_fetch_band_margin (additive). 10 (number kept): per-k-mer level summary of a run: dyn_aligner_set_kmer_summary, dyn_aligner_kmer_summary_fetch / _reset (additive). 10: per-read signal rescaling: dyn_aligner_set_rescale, dyn_batch_fetch_rescale (additive). 9: per-segment signal levels: dyn_aligner_set_event_stats, dyn_batch_fetch_events, dyn_format_csv[_bound]_events, dyn_csv_sink_open_ex (additive). 8: dyn_aligner_session_idle_split (additive). 7: dyn_aligner_session_page_wait, dyn_comm_gather_bytes / _gathered_bytes / _allreduce_f64 (additive). 7: half bands 224 .. 2 046 are computed (wide_band.hip). 5: any band constructs (DYN_READ_BAND_TOO_WIDE per read); dyn_bam_*, dyn_csv_sink_wait / _open_part */
+#define DYN_ABI_VERSION 10 /* 10 (number kept; look the symbol up): guided-band training: dyn_batch_train_guided (additive). 10 (number kept; look the symbols up): guided band: dyn_batch_set_guide, dyn_batch_arena_bytes (additive). 10 (number kept; look the symbols up): band-margin diagnostics: dyn_aligner_set_band_margin, dyn_batch_fetch_band_margin (additive). 10 (number kept): per-k-mer level summary of a run: dyn_aligner_set_kmer_summary, dyn_aligner_kmer_summary_fetch / _reset (additive). 10: per-read signal rescaling: dyn_aligner_set_rescale, dyn_batch_fetch_rescale (additive). 9: per-segment signal levels: dyn_aligner_set_event_stats, dyn_batch_fetch_events, dyn_format_csv[_bound]_events, dyn_csv_sink_open_ex (additive). 8: dyn_aligner_session_idle_split (additive). 7: dyn_aligner_session_page_wait, dyn_comm_gather_bytes / _gathered_bytes / _allreduce_f64 (additive). 7: half bands 224 .. 2 046 are computed (the generic kernel, today band_reads.hip). 5: any band constructs (DYN_READ_BAND_TOO_WIDE per read); dyn_bam_*, dyn_csv_sink_wait / _open_part */
 
 /* device argument of dyn_aligner_create: bind no GPU. Such a handle serves the host-side
  * contract only (model loading, dyn_aligner_info/_model, dyn_validate_batch, and dyn_batch_create[_raw] as far as the
@@ -80,7 +80,7 @@ enum dyn_read_status {
   DYN_READ_BAND_TOO_WIDE = 11,   /* "Band wider than this build's 4096 band columns for a read of this length": the handle was
                                     created with band > 4 093 and the read has more than 4 093 lattice columns, so that its
                                     half band min(band / 2, columns / 2) exceeds 2 046 -- what the generic kernel's rows hold
-                                    (wide_band.hip). Every other read is computed as the reference computes it: half bands up
+                                    (band_reads.hip). Every other read is computed as the reference computes it: half bands up
                                     to 223 by the register sweeps, 224 .. 2 046 by the generic kernel. */
   DYN_READ_BAD_SIGNAL = 10       /* "Signal could not be decoded" (dyn_batch_align_vbz_async): a POD5 chunk of this read is
                                     corrupt, truncated or shorter than the read's [start:end) slice. In the reference the
@@ -333,7 +333,7 @@ int dyn_pore_from_string(const char* s, int* pore_out, char* err, uint64_t errca
  * band: any value, as in the reference (aligner.cpp:21). The tuned sweeps hold 448 band slots per lattice row (half bands
  * up to 223: every caller in the reference fixes band = 400, segment.py:45, utils.py:161). A read whose half band
  * min(band / 2, columns / 2) exceeds that -- band > 447 AND more than 447 lattice columns -- takes a generic kernel in the
- * same batch (wide_band.hip: one workgroup per read, rows of up to 4 096 band columns in LDS, the reference's own
+ * same batch (band_reads.hip: one workgroup per read, rows of up to 4 096 band columns in LDS, the reference's own
  * arithmetic in every cell: Z bit for bit; align, the Z-only call and train alike; a fraction of the tuned sweeps' rate).
  * Only a half band above 2 046 is refused, per read: DYN_READ_BAND_TOO_WIDE. device < 0 -> current HIP device. */
 int dyn_aligner_create(const char* model_path, int pore, const char* mode, int threads,
@@ -779,8 +779,10 @@ int dyn_batch_fetch_guide(dyn_batch* b, int32_t* out, uint64_t count);
  * dyn_batch_set_guide_refine(max_rounds > 1)). n >= the batch's read count. */
 int dyn_batch_fetch_guide_rounds(dyn_batch* b, uint32_t* rounds, uint32_t* converged, uint64_t n);
 /* (added within ABI 10) Device bytes the batch's last job allocated for per-workgroup lattice arenas: workgroups x the largest
- * read's lattice, for the guided kernel (dyn_batch_set_guide) or the generic wide-band kernel; 0 for a batch whose reads all took
- * the paged read queue (its pool: dyn_timing.pool_pages) and for a Z-only guided job; 16 B per cell for dyn_batch_train_guided. */
+ * read's lattice, for the guided kernel (dyn_batch_set_guide) or the generic wide-band kernel (one kernel: band_reads.hip); 25 B per band slot
+ * for align with probabilities, 16 B for dyn_batch_train / dyn_batch_train_guided; 0 for a batch whose reads all took the paged
+ * read queue (its pool: dyn_timing.pool_pages) and for a Z-only job, guided or wide: it stores nothing of the lattice, so a wide
+ * read is never DYN_READ_TOO_LARGE in a Z-only call. */
 int dyn_batch_arena_bytes(const dyn_batch* b, uint64_t* bytes);
 /* Device-resident results of the last dyn_batch_align, for an RCCL gather without a host hop:
  * rows = dyn_segment_row[capacity] (read i at seg_offsets[i], as in dyn_align_out);

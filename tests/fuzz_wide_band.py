@@ -2,7 +2,7 @@
 
     python tests/fuzz_wide_band.py > gpurun_out/fuzz_wide.txt
 
-Random reads under bands the register sweeps cannot hold (round 6, wide_band.hip): five pore types x two random bands out of
+Random reads under bands the register sweeps cannot hold (round 6; the wide-band kernel, today band_reads.hip): five pore types x two random bands out of
 {448 .. 3000}, 40 reads each of k .. 1 600 bases with dwells 2 .. 10 -- so that a batch MIXES reads the tuned sweeps compute at
 that band (half band <= 223 because the read is short) with reads the generic kernel computes --, a homopolymer stretch in every
 fourth read (structural ties), one read with an N, one with a NaN sample. Against the oracle at the same band: integer columns

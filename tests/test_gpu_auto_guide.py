@@ -1,5 +1,5 @@
 """GPU (-m gpu): the self-guided band (Batch.auto_guide / dyn_batch_auto_guide, auto_guide.hip; Batch.set_guide_refine /
-dyn_batch_set_guide_refine, guided_band.hip).
+dyn_batch_set_guide_refine; k_guide_refine in guided_band.hip, the alignments in band_reads.hip).
   1. k_auto_guide on descriptors of the test's own (tests/device_math/auto_guide.hip, built with the product's flags): every
      guide entry equals the g++ build of the same header in all three shapes, on the edge reads, on the empty range and with
      600 reads through a few workgroups

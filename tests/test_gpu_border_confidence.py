@@ -194,7 +194,7 @@ def test_inplace_layout_and_page_starved_pool(models, sets, want, monkeypatch, n
 # ---- 5. wide band -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("W", [8, 256])
 def test_wide_band(models, sets, want, W):
-    """one rna002 read of 600 bases at band = 600: half band 298, above the register sweeps' 223 -- wide_band.hip"""
+    """one rna002 read of 600 bases at band = 600: half band 298, above the register sweeps' 223 -- the wide-band kernel (band_reads.hip)"""
     pore, band, reads = sets["wide"]
     assert min(band // 2, (len(reads[0].sequence) - 5 + 2) // 2) == 298
     res, _ = run(models["syn5"], pore, band, reads, W)

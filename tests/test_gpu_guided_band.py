@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the guided band (Aligner.align_batch_guided / dyn_batch_set_guide, guided_band.hip).
+"""GPU (-m gpu): the guided band (Aligner.align_batch_guided / dyn_batch_set_guide, band_reads.hip).
   a. a diagonal guide at half_width = min(band / 2, N / 2) is the reference's band: borders and Z bits of the CPU oracle, at one
      band column per lane (64 threads), at 67 / 203 / 255 band columns (64 threads, up to four columns per lane), at 273 (256
      threads, two columns per thread) and at 4 095 (16 per thread, the raised LDS limit); the Z-only job of each shape
@@ -10,6 +10,8 @@
   e. 600 reads through far fewer workgroups: arena and LDS rows reused across reads of different sizes
   f. riders: event stats, segment scores, k-mer summary bit-equal to the unguided call; guided band margins exact
   g. the refusals that need a device, the memory budget, the cell count
+  h. the kernel's two windows against each other: an unguided batch of wide reads (the diagonal window) equals, bit for bit, each
+     read guided by the diagonal at its own half band; train to the bar of the wide band; the arena a job of wide reads allocates
 Oracle results are computed once per module. No torch in this process."""
 import numpy as np
 import pytest
@@ -335,3 +337,98 @@ def test_refusals_budget_and_cells(ctx):
     finally:
         al.set_mem_budget(0)
     assert res.status.tolist() == [0, 0, 8, 0, 0] and res.error(2) == "Read too large for the device memory budget"
+
+
+# ---- h: the two windows of the banded-lattice kernel against each other -----------------------------------------------------------
+WIDE_BAND = 600
+
+
+@pytest.fixture(scope="module")
+def wide(models):
+    """ONE unguided batch at band 600 whose launch holds three different B = 2 bw + 3: two reads of 620-700 k-mers (bw = 300, one
+    of them behind pad + 20-60 A's: a structural tie at its start) and one read each with N = 501 and N = 560 lattice columns
+    (bw = N / 2 = 250 and 280). Its align, Z-only, asynchronous and train results, computed once."""
+    _, mean, sd = synth.read_model_file(models["syn9"])
+    reads = synth.make_reads(6101, 1, "rna004", mean, sd, (628, 708))
+    reads += synth.make_reads(6102, 1, "rna004", mean, sd, (628, 708), polya=(20, 60))
+    reads += synth.make_reads(6103, 1, "rna004", mean, sd, 508) + synth.make_reads(6104, 1, "rna004", mean, sd, 567)
+    N = [len(r.sequence) - 9 + 2 for r in reads]
+    bw = [min(WIDE_BAND // 2, n // 2) for n in N]
+    assert all(621 <= n <= 701 for n in N[:2]) and N[2:] == [501, 560] and bw == [300, 300, 250, 280]
+    assert reads[1].sequence[:29] == "A" * 29
+    al = Aligner(models["syn9"], "rna004", band=WIDE_BAND)
+    sig, seq = [r.signal for r in reads], [r.sequence for r in reads]
+    w = dict(al=al, reads=reads, sig=sig, seq=seq, N=N, bw=bw, guides=[G.diagonal_guide(len(r.signal), n) for r, n in zip(reads, N)])
+    w["align"] = al.align_batch(sig, seq, True)
+    w["zonly"] = al.align_batch(sig, seq, False)
+    with al.align_async(*synth.pack_reads(reads), True) as t:
+        w["async"] = t.wait()
+    w["train"] = al.train_batch(sig, seq)
+    yield w
+    al.close()
+
+
+def u64(x):
+    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+
+
+def test_the_diagonal_window_is_a_diagonal_guide_bit_for_bit(wide):
+    """Every read of the unguided batch again, alone, through the guide window: a diagonal guide at half_width = the read's own
+    bw. What separates the two window policies is all here: per-read against per-launch half width, the N / 2 clamp with odd N,
+    the fixed against the computed seed column, an LDS row stride larger than a read's B."""
+    al = wide["al"]
+    for i, r in enumerate(wide["reads"]):
+        g = al.align_batch_guided([r.signal], [r.sequence], [wide["guides"][i]], wide["bw"][i])
+        gz = al.align_batch_guided([r.signal], [r.sequence], [wide["guides"][i]], wide["bw"][i], calc_probabilities=False)
+        assert g.status[0] == 0 and gz.status[0] == 0, (i, g.error(0), gz.error(0))
+        want = g.read(0)
+        for what in ("align", "async"):
+            res = wide[what]
+            assert res.status[i] == 0, (what, i, res.error(i))
+            got = res.read(i)
+            assert np.array_equal(got["signal_positions"], want["signal_positions"]), (what, i)
+            assert np.array_equal(got["sequence_positions"], want["sequence_positions"]), (what, i)
+            assert len(got["signal_positions"]) == wide["N"][i] - 1
+            assert np.array_equal(u64(got["Z"]), u64(want["Z"])), (what, i, got["Z"], want["Z"])
+            assert np.array_equal(u64(got["probabilities"]), u64(want["probabilities"])), (what, i)
+        z = wide["zonly"]
+        assert z.status[i] == 0 and z.n_segments[i] == 0 and gz.n_segments[0] == 0
+        assert np.array_equal(u64(z.Z[i]), u64(gz.Z[0])) and np.array_equal(u64(z.Z[i]), u64(want["Z"])), i
+
+
+def test_diagonal_window_train_against_a_diagonal_guide(wide):
+    """train_batch against train_batch_guided(diagonal guide, the read's bw). Z and both transition counts: the same bits. The
+    emission sums are held to rtol 1e-7 / atol 1e-9 (the bar of test_any_band_long_reads_equal_the_oracle_bit_for_bit), NOT to
+    array_equal, by design: under the diagonal window a thread keeps a column's running sum in a register and flushes it when
+    the band moves, under the guide window every row adds into the column's word in memory -- the same terms in the same
+    order, grouped differently, so the last bits differ."""
+    al, tr = wide["al"], wide["train"]
+    for i, r in enumerate(wide["reads"]):
+        g = al.train_batch_guided([r.signal], [r.sequence], [wide["guides"][i]], wide["bw"][i])
+        assert tr.status[i] == 0 and g.status[0] == 0, (i, tr.error(i), g.error(0))
+        assert np.array_equal(u64(tr.Z[i]), u64(g.Z[0])), i
+        assert np.array_equal(u64(tr.trans_counts[2 * i:2 * i + 2]), u64(g.trans_counts[:2])), i
+        a0, cnt = int(tr.em_offsets[i]), int(tr.em_count[i])
+        assert cnt > 100 and cnt == int(g.em_count[0]) and np.array_equal(tr.em_code[a0:a0 + cnt], g.em_code[:cnt]), i
+        assert np.allclose(tr.em_weight[a0:a0 + cnt], g.em_weight[:cnt], rtol=1e-7, atol=1e-9), i
+        assert np.allclose(tr.em_sum[a0:a0 + cnt], g.em_sum[:cnt], rtol=1e-7, atol=1e-9), i
+
+
+def test_wide_reads_arena(wide):
+    """dyn_batch_arena_bytes of the wide reads' batch: one arena per workgroup, min(reads, compute units) of them (the API does
+    not report the compute units; an MI355X has 256, and no GPU this suite runs on has fewer than the four reads), each the
+    largest read's lattice at 25 B per band slot for align, 16 B for train, nothing for the Z-only job"""
+    al, reads = wide["al"], wide["reads"]
+    max_T = max(len(r.signal) + 1 for r in reads)
+    assert max(range(4), key=lambda i: (len(reads[i].signal) + 1) * (2 * wide["bw"][i] + 3)) < 2    # the largest lattice: a bw = 300 read
+    assert max_T == max(len(r.signal) + 1 for r in reads[:2])
+    groups = min(len(reads), 256)
+    slots = max_T * (2 * 300 + 3)
+    with al.batch(wide["sig"], wide["seq"]) as b:
+        b.align(True)
+        assert b.arena_bytes() == groups * ((25 * slots + 255) // 256 * 256)
+        b.train()
+        assert b.arena_bytes() == groups * ((16 * slots + 255) // 256 * 256)
+        b.align(False)
+        assert b.arena_bytes() == 0
+        assert (b.fetch().status == 0).all()

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): guided-band training (Aligner.train_batch_guided / dyn_batch_train_guided, the TRAIN job of guided_band.hip).
+"""GPU (-m gpu): guided-band training (Aligner.train_batch_guided / dyn_batch_train_guided, the TRAIN job of band_reads.hip under its guide window).
   a. a diagonal guide at half_width = min(band / 2, N / 2) is the oracle's train(): once per kernel shape and LDS regime (B =
      53, 67, 203, 255, 273 and 4 095, the raised LDS limit), Z with the oracle's bits
   b. any covering guide (diagonal, the true staircase, random steps of 0 .. 7) is oracle(band 4093).train

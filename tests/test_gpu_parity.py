@@ -883,7 +883,7 @@ def test_band_above_447_short_reads_equal_the_oracle_and_long_reads_take_the_gen
     """The reference takes any band (aligner.cpp:21). A handle created with band 1 000 computes every read whose half band
     min(band / 2, columns / 2) fits the register sweeps' 448 band slots -- here reads of 60 .. 446 k-mers, for the longer of
     which (402+ columns) the band is WIDER than at band 400 -- exactly as the oracle does at band 1 000, train() included. A read
-    with more columns (half band 348 here) takes the generic kernel (wide_band.hip) IN THE SAME BATCH: the reference's own
+    with more columns (half band 348 here) takes the generic kernel (band_reads.hip) IN THE SAME BATCH: the reference's own
     arithmetic in every cell, so its Z has the oracle's bits."""
     model = models["syn5"]
     _, mean, sd = synth.read_model_file(model)

@@ -253,7 +253,7 @@ def test_rescaling_and_levels_scored_over_the_last_pass(models):
 
 
 def test_wide_band_strict_ties_failed_reads_and_a_stall(models):
-    """band 1000 (wide_band.hip) with polyA reads (strict tie rows), two reads that fail, and a read with a stalled pore"""
+    """band 1000 (the wide-band kernel, band_reads.hip) with polyA reads (strict tie rows), two reads that fail, and a read with a stalled pore"""
     pore = "rna004"
     model = model_for(models, pore)
     _, mean, sd = synth.read_model_file(model)

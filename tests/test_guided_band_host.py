@@ -111,7 +111,7 @@ def test_symbol_header_and_abi(native_lib):
     assert re.search(r"#define DYN_ABI_VERSION 10\b", hdr)
     assert re.search(r"int dyn_batch_set_guide\(dyn_batch\* b, const int32_t\* centres, uint64_t count, uint32_t half_width\);", hdr)
     assert "dyn_batch_set_guide" in N.SIGNATURES and getattr(native_lib, "dyn_batch_set_guide") is not None
-    assert "guided_band.hip" in N.SOURCES and "guided_band_kernels.hpp" in N.HEADERS
+    assert {"band_reads.hip", "guided_band.hip"} <= set(N.SOURCES) and {"band_reads.hpp", "guided_band_kernels.hpp", "border_kernels.hpp"} <= set(N.HEADERS)
     assert native_lib.dyn_batch_set_guide(None, None, 0, 8) == N.DYN_ERR_INVALID_ARGUMENT
     assert re.search(r"int dyn_batch_arena_bytes\(const dyn_batch\* b, uint64_t\* bytes\);", hdr) and "dyn_batch_arena_bytes" in N.SIGNATURES
     assert native_lib.dyn_batch_arena_bytes(None, None) == N.DYN_ERR_INVALID_ARGUMENT

@@ -32,7 +32,7 @@ def merge(path, rec):
 if len(sys.argv) > 1 and sys.argv[1] == "resources":
     from dynamont_amd import _native
     res = {}
-    for src in ("nt_kernels.hip", "wide_band.hip"):
+    for src in ("nt_kernels.hip", "band_reads.hip"):
         cmd = [_native.hipcc_path()] + _native.hipcc_flags() + ["-Rpass-analysis=kernel-resource-usage", "-x", "hip", "-c",
                                                                 os.path.join(_native.CSRC, src), "-o", os.devnull]
         text = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
@@ -43,7 +43,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "resources":
                 name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip().split("(")[0] or m.group(1)
                 name = name.replace("void ", "").replace("dynk::", "")
                 # k_read_queue<9 | 10, .>: JOB_ALIGN | JOB_BORDER, JOB_ALIGN_INPLACE | JOB_BORDER
-                keep = "k_wide_reads_border" in name or re.search(r"k_read_queue<(9|10),", name)
+                keep = "k_band_reads<DiagonalWindow, 256, 16, true, false, true>" in name or re.search(r"k_read_queue<(9|10),", name)
                 name = name if keep else None
                 if name:
                     res[name] = {}

@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "../../dynamont_amd/csrc/nt_kernels.hpp"
+#include "../../dynamont_amd/csrc/band_reads.hpp"
 #include "../../dynamont_amd/csrc/guided_band_kernels.hpp"
 #include "../../dynamont_amd/csrc/auto_guide_kernels.hpp"
 
@@ -48,11 +49,9 @@ hipError_t launch_pool_stats(const ReadDesc*, int, uint32_t, const ReadState*, c
                              size_t, hipStream_t) {
   no_device("launch_pool_stats");
 }
-uint64_t wide_arena_bytes(uint64_t T, uint64_t bw, bool calc) { return T * (2 * bw + 3) * (16 + (calc ? 9 : 0)); }
-void launch_wide_reads(int, const WideArgs&, int, hipStream_t) { no_device("launch_wide_reads"); }
-uint64_t guided_arena_bytes(uint64_t T, uint64_t bw, int job) { return T * (2 * bw + 3) * (16 + (job == 1 ? 9 : 0)); }
-int guided_groups_per_cu(int, int) { return 1; }
-hipError_t launch_guided_reads(int, const GuidedArgs&, int, hipStream_t) { no_device("launch_guided_reads"); }
+uint64_t band_arena_bytes(uint64_t T, uint64_t bw, int job) { return job == 0 ? 0 : T * (2 * bw + 3) * (job == 2 ? 16 : 25); }
+int band_groups_per_cu(bool, int, int) { return 1; }
+hipError_t launch_band_reads(int, const BandArgs&, int, hipStream_t) { no_device("launch_band_reads"); }
 void launch_guided_band_margin(const ReadDesc*, int, uint32_t, const ReadState*, const TraceBuffers&, const int32_t*, int, const BandMargin&,
                                hipStream_t) {
   no_device("launch_guided_band_margin");
