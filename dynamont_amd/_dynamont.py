@@ -550,7 +550,7 @@ class AsyncBatch:
     (the library reads them until the batch is complete)."""
 
     def __init__(self, aligner: "Aligner", handle, result, keep, levels: bool = False, rescale: bool = False,
-                 scores: bool = False, borders: bool = False, margins: bool = False):
+                 scores: bool = False, borders: bool = False, margins: bool = False, auto_guide=None):
         self._al = aligner
         self._L = N.lib()
         self._h = handle
@@ -562,6 +562,9 @@ class AsyncBatch:
         self._scores = scores  # ... with the segment-scores switch on
         self._borders = borders  # ... with the border-confidence switch on
         self._margins = margins  # ... with the band-margin switch on (tickets report margins; they are never retried)
+        # ... with the auto-guide switch on (Aligner.set_auto_guide): (alignments per read, the ticket's sample offsets), else None
+        self._auto_guide = auto_guide
+        self._sig_off = auto_guide[1] if auto_guide is not None else None  # what Batch.guide cuts the flat guide at
 
     def wait(self):
         if not self._waited:
@@ -575,7 +578,23 @@ class AsyncBatch:
                 self.result._fetch_scores(self._L, self._h, self._al, self._scores)
                 self.result._fetch_borders(self._L, self._h, self._al, self._borders)
                 self.result._fetch_band_margin(self._L, self._h, self._al, self._margins)
+                # a result object refilled from an earlier ticket must not keep that ticket's counts
+                self.result.guide_rounds = self.result.guide_converged = self.result.guides = None
+                if self._auto_guide is not None and self._auto_guide[0] != 1:
+                    self.result.guide_rounds, self.result.guide_converged = Batch.guide_rounds(self)
         return self.result
+
+    @property
+    def n(self) -> int:
+        return self.result.n
+
+    def guide(self) -> list:
+        """dyn_batch_fetch_guide on a ticket submitted under ``Aligner.set_auto_guide``: every read's int32 guide of its last
+        alignment, one entry per sample (ValueError for a ticket that was not guided)"""
+        self.wait()
+        if self._auto_guide is None:
+            raise ValueError("AsyncBatch.guide: the ticket was submitted without Aligner.set_auto_guide")
+        return Batch.guide(self)
 
     fetch_events = Batch.fetch_events
     fetch_rescale = Batch.fetch_rescale
@@ -685,6 +704,7 @@ class Aligner:
     _segment_scores = 0  # set_segment_scores
     _border_confidence = 0  # set_border_confidence
     _band_margin = False  # set_band_margin
+    _auto_guide = (0, 8)  # set_auto_guide: (half_width, refine)
     _band_retry = None  # set_band_retry: (min_margin, max_band, factor)
     _kmer_summary = False  # set_kmer_summary
     _strict = 1  # set_strict
@@ -816,6 +836,25 @@ class Aligner:
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
         self._border_confidence = int(window)
+
+    def set_auto_guide(self, half_width: int, refine: int = 8) -> None:
+        """dyn_aligner_set_auto_guide: ``align_async`` / ``align_raw_async`` / ``align_vbz_async`` tickets with
+        ``calc_probabilities=True`` submitted while ``half_width`` (1 .. 2046) > 0 are aligned inside a guide the library makes
+        itself and refines up to ``refine`` (1 .. 64) alignments per read -- what ``align_batch_auto(signals, sequences,
+        half_width, refine)`` computes, bit for bit, in one launch per ticket. The result of ``AsyncBatch.wait()`` then carries
+        ``guide_rounds`` / ``guide_converged`` (``None`` with ``refine == 1``) and ``AsyncBatch.guide()`` returns the final
+        guides. 0 turns it off. Synchronous batches, Z-only and train tickets and ``MultiAligner`` are untouched; a ticket
+        submitted with ``set_rescale`` / ``set_border_confidence`` on as well is refused (ValueError)."""
+        rc = self._L.dyn_aligner_set_auto_guide(self._h, int(half_width), int(refine))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        self._auto_guide = (int(half_width), int(refine))
+
+    def _ticket_guide(self, calc_probabilities: bool, offsets):
+        """what AsyncBatch keeps of the auto-guide switch for an align ticket submitted now"""
+        if not (self._auto_guide[0] > 0 and calc_probabilities and self._ctor[2] not in ("ntk", "resquiggle")):
+            return None
+        return (self._auto_guide[1], offsets)
 
     def set_rescale(self, iters: int) -> None:
         """dyn_aligner_set_rescale: align(calc_probabilities=True) jobs submitted while ``iters`` (0 .. 8) > 0 align every
@@ -1029,7 +1068,8 @@ class Aligner:
                           rescale=self._rescale > 0 and bool(calc_probabilities),
                           scores=self._segment_scores > 0 and bool(calc_probabilities),
                           borders=self._border_confidence > 0 and bool(calc_probabilities),
-                          margins=self._band_margin and bool(calc_probabilities))
+                          margins=self._band_margin and bool(calc_probabilities),
+                          auto_guide=self._ticket_guide(bool(calc_probabilities), sig_off))
 
     def _raw_args(self, raw, shift, scale, calibration=None):
         scattered = isinstance(raw, (list, tuple))
@@ -1083,7 +1123,8 @@ class Aligner:
                           rescale=self._rescale > 0 and bool(calc_probabilities),
                           scores=self._segment_scores > 0 and bool(calc_probabilities),
                           borders=self._border_confidence > 0 and bool(calc_probabilities),
-                          margins=self._band_margin and bool(calc_probabilities))
+                          margins=self._band_margin and bool(calc_probabilities),
+                          auto_guide=self._ticket_guide(bool(calc_probabilities), raw_off))
 
     def align_vbz_async(self, chunks, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 3,
                         n_sigmas: float = 3.0, f32: bool = False, calc_probabilities: bool = True,
@@ -1121,7 +1162,8 @@ class Aligner:
                           rescale=self._rescale > 0 and bool(calc_probabilities),
                           scores=self._segment_scores > 0 and bool(calc_probabilities),
                           borders=self._border_confidence > 0 and bool(calc_probabilities),
-                          margins=self._band_margin and bool(calc_probabilities))
+                          margins=self._band_margin and bool(calc_probabilities),
+                          auto_guide=self._ticket_guide(bool(calc_probabilities), raw_off))
 
     def train_raw_async(self, raw, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 7,
                         n_sigmas: float = 5.0, f32: bool = True, pooled: bool = False,

@@ -200,6 +200,7 @@ SIGNATURES = {
     "dyn_batch_set_guide": (C.c_int, [C.c_void_p, c_i32_p, C.c_uint64, C.c_uint32]),
     "dyn_batch_train_guided": (C.c_int, [C.c_void_p]),
     "dyn_batch_auto_guide": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "dyn_aligner_set_auto_guide": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "dyn_batch_set_guide_refine": (C.c_int, [C.c_void_p, C.c_uint32]),
     "dyn_batch_fetch_guide": (C.c_int, [C.c_void_p, c_i32_p, C.c_uint64]),
     "dyn_batch_fetch_guide_rounds": (C.c_int, [C.c_void_p, c_u32_p, c_u32_p, C.c_uint64]),

@@ -148,7 +148,8 @@ static uint64_t merge_max_reads(const dyn_aligner* a) { return merge_reads_per_s
 static bool mergeable(const dyn_batch* x) {
   // batches that leave the waves underfilled (fewer than 1.5 reads per wave slot): a batch of four reads per slot balances
   // by itself, and merging those only makes the pipeline lumpy
-  return x->job != DynJob::Train && x->n > 0 && 2 * x->n <= 3 * (uint64_t)x->a->n_cus * dynk::WAVES_PER_CU;
+  // (a self-guided ticket carries a guide of its own and takes the banded-lattice kernel: never merged)
+  return x->job != DynJob::Train && x->ag_want == 0 && x->n > 0 && 2 * x->n <= 3 * (uint64_t)x->a->n_cus * dynk::WAVES_PER_CU;
 }
 static bool same_kind(const dyn_batch* x, const dyn_batch* y) {
   if (x->job != y->job || x->has_raw != y->has_raw || x->ev_want != y->ev_want || x->rs_want != y->rs_want || x->sc_want != y->sc_want ||
@@ -532,6 +533,16 @@ int Pipeline::front_stage(dyn_batch* b) {
                    t2 - t1, t3 - t2, t4 - t3, now_ms() - t4);
     return rc;  // the copies out are enqueued by the back thread, once the ticket's completion word has been seen
   }
+  // a self-guided ticket (dyn_aligner_set_auto_guide): its guide is made here, behind its preprocessing on the compute stream,
+  // and enqueue_job then sizes arenas and groups as for a synchronous guided batch
+  if (b->ag_want) {
+    rc = enqueue_auto_guide(b, b->ag_want);
+    if (rc != DYN_OK) {
+      b->error = last_error_of(a);
+      return rc;
+    }
+    b->guide_refine = b->ag_rounds;
+  }
   rc = enqueue_job(b, b->job);  // records ev_done behind the batch's last kernel
   if (rc != DYN_OK) {
     b->error = last_error_of(a);
@@ -540,6 +551,10 @@ int Pipeline::front_stage(dyn_batch* b) {
   P_TRY(b, hipStreamWaitEvent(a->s_out, b->ev_done, 0));
   // D2H into pinned per-batch buffers on the copy-out stream
   if (n) P_TRY(b, hipMemcpyAsync(b->h_state.p, b->d_state.p, n * sizeof(ReadState), hipMemcpyDeviceToHost, a->s_out));
+  if (n && b->gref_ready) {  // rounds | converged of a self-guided ticket
+    P_TRY(b, b->h_gref.ensure(2 * n * 4));
+    P_TRY(b, hipMemcpyAsync(b->h_gref.p, b->d_gref.p, 2 * n * 4, hipMemcpyDeviceToHost, a->s_out));
+  }
   if (b->job == DynJob::AlignFull && b->capacity) {
     P_TRY(b, b->h_rows.ensure(b->capacity * sizeof(SegRow)));
     P_TRY(b, hipMemcpyAsync(b->h_rows.p, b->d_rows.p, b->capacity * sizeof(SegRow), hipMemcpyDeviceToHost, a->s_out));
@@ -768,11 +783,22 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
       return DYN_ERR_INVALID_ARGUMENT;
     }
   }
+  // the self-guided band (dyn_aligner_set_auto_guide) concerns align tickets with probabilities; it pairs with neither of the two
+  // switches a synchronous guided batch refuses (run_job_sync)
+  const uint32_t ag_hw = (job == DynJob::AlignFull && !a->ntk) ? a->auto_guide_hw : 0u;
+  if (ag_hw && (a->rescale_iters > 0 || a->border_confidence > 0)) {
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = std::string("dyn_batch_align_async: dyn_aligner_set_auto_guide is on, which does not combine with ") +
+                    (a->rescale_iters > 0 ? "dyn_aligner_set_rescale(a, iters > 0)" : "dyn_aligner_set_border_confidence(a, window > 0)");
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
   dyn_batch* b = new dyn_batch();
   b->a = a;
   attach_cache(b);
   b->n = n_reads;
   b->async = true;
+  b->ag_want = ag_hw;
+  b->ag_rounds = ag_hw ? a->auto_guide_rounds : 1u;
   b->job = job;
   b->ev_want = a->event_stats;
   b->rs_want = a->rescale_iters;

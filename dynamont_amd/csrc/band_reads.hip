@@ -47,6 +47,8 @@
 //                      Either way a column's sum is formed in ascending t, without atomics: the same bits whichever workgroup
 //                      takes the read.
 // A diagonal guide at bw = min(band / 2, N / 2) is the reference's band: the results are the diagonal window's bit for bit.
+// A third policy, LiveGuideWindow, is GuideWindow for the launch that refines every read's guide inside the launch (k_band_reads
+// with REFINE, below): the same window, read through a pointer the kernel may write behind.
 #include "band_reads.hpp"
 
 #include "border_kernels.hpp"
@@ -71,6 +73,23 @@ struct GuideWindow {
   __device__ __forceinline__ int end_column(int start_last, int N) const { return (N - 1) - start_last + 1; }
   static __device__ __forceinline__ int row_stride(const BandArgs& a) { return guided_row_stride(2 * a.bw + 3); }
   static __device__ __forceinline__ char* lds(char* dynamic) { return dynamic; }  // sized per launch: lds_bytes below
+};
+
+// GuideWindow for the launch that refines every read's guide itself (BandArgs::refine_rounds > 1): the workgroup REWRITES the
+// guide between two alignments of a read, so the pointer is neither const nor __restrict__, and a centre is fetched by a relaxed
+// atomic load at workgroup scope -- a vector load the compiler neither hoists across the rewrite nor turns into a scalar load
+// (the scalar data cache is not updated by the kernel's own vector stores: a second alignment could run inside the old guide)
+struct LiveGuideWindow {
+  static constexpr bool DIAGONAL = false;
+  int32_t* gd;
+  int bw;
+  __device__ __forceinline__ LiveGuideWindow(const ReadDesc& rd, const BandArgs& a) : gd(a.guide + rd.sig_off), bw(a.bw) {}
+  __device__ __forceinline__ int centre(int t) const {
+    return t > 0 ? (int)__hip_atomic_load(gd + (t - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0;
+  }
+  __device__ __forceinline__ int end_column(int start_last, int N) const { return (N - 1) - start_last + 1; }
+  static __device__ __forceinline__ int row_stride(const BandArgs& a) { return guided_row_stride(2 * a.bw + 3); }
+  static __device__ __forceinline__ char* lds(char* dynamic) { return dynamic; }
 };
 
 struct DiagonalWindow {
@@ -368,14 +387,20 @@ __device__ void band_read(const ReadDesc& rd, const BandArgs& a, double* __restr
 // BORDER: the border-confidence phase (border_kernels.hpp) behind every read, as a kernel of its own: the launches without the
 // phase are the ones they have always been. The read's lattice is still in the arena when band_read returns (its closing
 // barrier has made the state and segrow that thread 0 wrote visible to the workgroup).
-template <class Window, int THREADS, int CPT, bool CALC, bool TRAIN, bool BORDER>
+// REFINE (LiveGuideWindow, align with probabilities): the workgroup that holds a read refines its guide, behind every band_read
+// what k_guide_refine (guided_band.hip) does for the read between two launches of the round scheme, rule for rule: the
+// alignment is counted; a failed read is finished; the called path g'[s] = pathn[s + 1] (0 before the first border) is compared
+// with the guide; equal everywhere: converged; otherwise, unless this was alignment refine_rounds, g' becomes the guide and the
+// read is aligned again in the same arena. Only then does the workgroup take the next read: a launch lasts as long as its
+// reads' alignments, not as refine_rounds times its longest read. BandArgs::active is not looked at.
+template <class Window, int THREADS, int CPT, bool CALC, bool TRAIN, bool BORDER, bool REFINE = false>
 __global__ __launch_bounds__(THREADS) void k_band_reads(const BandArgs a) {
   extern __shared__ __attribute__((aligned(16))) char g_lds[];
   char* lds = Window::lds(g_lds);
   const int stride = Window::row_stride(a);
   uint64_t* s_exp = reinterpret_cast<uint64_t*>(lds);
   double* s_rows = reinterpret_cast<double*>(lds + dynmath::STRICT_EXP_WORDS * 8);
-  int* s_ctl = reinterpret_cast<int*>(s_rows + (TRAIN && !Window::DIAGONAL ? 2 : 4) * stride);  // [0] next read, [1] s_bad
+  int* s_ctl = reinterpret_cast<int*>(s_rows + (TRAIN && !Window::DIAGONAL ? 2 : 4) * stride);  // [0] next read, [1] s_bad, [2] REFINE: the path differs from the guide
   for (int i = threadIdx.x; i < dynmath::STRICT_EXP_WORDS; i += THREADS) s_exp[i] = a.exp_tab[i];
   char* arena = a.arena + (size_t)blockIdx.x * a.arena_bytes;
   for (;;) {
@@ -384,14 +409,46 @@ __global__ __launch_bounds__(THREADS) void k_band_reads(const BandArgs a) {
     __syncthreads();
     const int k = s_ctl[0];
     // a refinement round (launch_guide_refine) hands over the list of the reads still to align and its length on the device
-    if (k >= (a.active ? (int)*a.n_active : a.n_reads)) break;
-    const ReadDesc rd = a.descs[a.active ? a.active[k] : (uint32_t)k];
+    const bool listed = !REFINE && a.active;
+    if (k >= (listed ? (int)*a.n_active : a.n_reads)) break;
+    const ReadDesc rd = a.descs[listed ? a.active[k] : (uint32_t)k];
     const size_t cells = (size_t)rd.T * (size_t)(2 * Window(rd, a).bw + 3);
     double* bE = reinterpret_cast<double*>(arena);
     double* bM = bE + cells;
     float* lp = reinterpret_cast<float*>(bM + cells);
     uint8_t* bit = reinterpret_cast<uint8_t*>(lp + 2 * cells);
-    band_read<Window, THREADS, CPT, CALC, TRAIN>(rd, a, bE, bM, lp, bit, s_rows, stride, s_exp, s_ctl + 1);
+    if constexpr (REFINE) {
+      const int T = (int)rd.T;
+      int32_t* gd = a.guide + rd.sig_off;
+      const uint32_t* pathn = a.tb.pathn + rd.path_off;  // written by thread 0 in this launch: neither const data nor __restrict__
+      uint32_t round = 1;
+      for (;; ++round) {
+        // cleared in front of the alignment: its barriers order this against the comparison below, and the barrier behind the
+        // rewrite against the last look at the word
+        if (threadIdx.x == 0) s_ctl[2] = 0;
+        band_read<Window, THREADS, CPT, CALC, TRAIN>(rd, a, bE, bM, lp, bit, s_rows, stride, s_exp, s_ctl + 1);
+        // behind band_read's closing barrier: the state, pathn and segrow of thread 0 are visible to the workgroup
+        if (__hip_atomic_load(&a.st[rd.read].status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0) break;  // failed: that is its result
+        const int first = rd.N >= 2 ? (int)__hip_atomic_load(a.tb.segrow + rd.seg_off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : T;
+        int differs = 0;
+        for (int s = (int)threadIdx.x; s < T - 1; s += THREADS) {
+          const int32_t g = s + 1 >= first ? (int32_t)(pathn[s + 1] & 0x7fffffffu) : 0;
+          differs |= g != gd[s];
+        }
+        if (differs) s_ctl[2] = 1;
+        __syncthreads();
+        if (!s_ctl[2]) {
+          if (threadIdx.x == 0) a.converged[rd.read] = 1u;
+          break;
+        }
+        if (round == (uint32_t)a.refine_rounds) break;  // the guide stays the one the last alignment used
+        for (int s = (int)threadIdx.x; s < T - 1; s += THREADS) gd[s] = s + 1 >= first ? (int32_t)(pathn[s + 1] & 0x7fffffffu) : 0;
+        __syncthreads();  // the whole guide is rewritten before the next alignment reads a centre
+      }
+      if (threadIdx.x == 0) a.rounds[rd.read] = round;  // alignments run (the launch cleared the counts)
+    } else {
+      band_read<Window, THREADS, CPT, CALC, TRAIN>(rd, a, bE, bM, lp, bit, s_rows, stride, s_exp, s_ctl + 1);
+    }
     if constexpr (BORDER) {
       if (__hip_atomic_load(&a.st[rd.read].status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) {
         const BorderCellWide cell{BorderBand{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio}, lp};
@@ -425,13 +482,13 @@ size_t lds_bytes(int bw, int job) {  // the train job keeps the two forward rows
   return (size_t)dynmath::STRICT_EXP_WORDS * 8 + (job == 2 ? 2 : 4) * (size_t)guided_row_stride(2 * bw + 3) * 8 + 16;
 }
 
-template <class Window, int THREADS, int CPT, bool CALC, bool TRAIN, bool BORDER = false>
+template <class Window, int THREADS, int CPT, bool CALC, bool TRAIN, bool BORDER = false, bool REFINE = false>
 hipError_t launch_kernel(const BandArgs& a, int n_groups, size_t lds, hipStream_t s) {
   if (lds > 48 * 1024) {  // (a wide guided window: the request exceeds the default dynamic-LDS limit; diagonal launches ask for none)
-    const void* fn = reinterpret_cast<const void*>(&k_band_reads<Window, THREADS, CPT, CALC, TRAIN, BORDER>);
+    const void* fn = reinterpret_cast<const void*>(&k_band_reads<Window, THREADS, CPT, CALC, TRAIN, BORDER, REFINE>);
     if (const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
   }
-  hipLaunchKernelGGL((k_band_reads<Window, THREADS, CPT, CALC, TRAIN, BORDER>), dim3(n_groups), dim3(THREADS), lds, s, a);
+  hipLaunchKernelGGL((k_band_reads<Window, THREADS, CPT, CALC, TRAIN, BORDER, REFINE>), dim3(n_groups), dim3(THREADS), lds, s, a);
   return hipGetLastError();
 }
 template <class Window, int THREADS, int CPT>
@@ -456,6 +513,8 @@ hipError_t launch_band_reads(int job, const BandArgs& a, int n_groups, hipStream
   if (job == 2 && !(a.tr.col_w && a.tr.col_s1 && a.tr.col_s2 && a.tr.trans)) return hipErrorInvalidValue;
   if (job != 0 && !a.arena) return hipErrorInvalidValue;
   if (a.border_window > 0 && (a.guide || job != 1 || !a.border_p || !a.border_window_p)) return hipErrorInvalidValue;
+  const bool refine = a.refine_rounds > 1;  // every read refined inside this launch
+  if (refine && (!a.guide || job != 1 || a.border_window > 0 || !a.rounds || !a.converged)) return hipErrorInvalidValue;
   if (const hipError_t e = hipMemsetAsync(a.head, 0, 4, s)) return e;
   if (!a.guide) {
     if (a.border_window > 0) return launch_kernel<DiagonalWindow, 256, 16, true, false, true>(a, n_groups, 0, s);
@@ -463,6 +522,11 @@ hipError_t launch_band_reads(int job, const BandArgs& a, int n_groups, hipStream
   }
   const size_t lds = lds_bytes(a.bw, job);
   const Shape& sh = shape_of(a.bw);
+  if (refine) {
+    if (sh.cpt == 1) return launch_kernel<LiveGuideWindow, 64, 1, true, false, false, true>(a, n_groups, lds, s);
+    if (sh.threads == 64) return launch_kernel<LiveGuideWindow, 64, 4, true, false, false, true>(a, n_groups, lds, s);
+    return launch_kernel<LiveGuideWindow, 256, 16, true, false, false, true>(a, n_groups, lds, s);
+  }
   if (sh.cpt == 1) return launch_shape<GuideWindow, 64, 1>(job, a, n_groups, lds, s);
   if (sh.threads == 64) return launch_shape<GuideWindow, 64, 4>(job, a, n_groups, lds, s);
   return launch_shape<GuideWindow, 256, 16>(job, a, n_groups, lds, s);

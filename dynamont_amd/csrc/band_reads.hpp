@@ -14,6 +14,8 @@
 //                   shift start_t - start_{t-1} is >= 0 (the guide is non-decreasing: validated on the host) and of any size;
 //                   the backward seed and Zf are read at the band column of (T-1, N-1), and a read whose windows do not connect
 //                   (0, 0) with it fails the reference's own Z check.
+//   LiveGuideWindow (BandArgs::refine_rounds > 1) GuideWindow's geometry for the launch that rewrites a read's guide between two
+//                   alignments of it: the centre is loaded so that the rewrite is seen (band_reads.hip).
 #pragma once
 
 #include "nt_kernels.hpp"
@@ -26,7 +28,8 @@ struct BandArgs {
   int bw;                  // guided: the half width, 1 .. WIDE_MAX_HALF_BAND (ReadDesc::bw is not used). Diagonal: not used
   const double* sig;
   const Emis* par;
-  const int32_t* guide;    // [samples of the batch]: ReadDesc::sig_off counts from here, as it does into sig. Null: the diagonal window
+  int32_t* guide;          // [samples of the batch]: ReadDesc::sig_off counts from here, as it does into sig. Null: the diagonal window.
+                           // Read only, except by a refining launch (refine_rounds > 1), which rewrites it
   ReadState* st;
   TraceBuffers tb;
   TrainBuffers tr;         // job 2 only: the read's column sums at col_* + ReadDesc::par_off, trans[2 * read]
@@ -43,6 +46,13 @@ struct BandArgs {
   int border_window = 0;   // as QueueArgs: W, and the two columns of dyn_aligner_set_border_confidence (diagonal, job 1 only)
   double* border_p = nullptr;
   double* border_window_p = nullptr;
+  // per-read refinement INSIDE the launch (guided, job 1, no border window): the workgroup that holds a read aligns it up to
+  // refine_rounds times, each time inside the path the alignment before called, by the rules of launch_guide_refine
+  // (guided_band_kernels.hpp) -- the round scheme's results bit for bit in one launch. 0 or 1: no refinement. active / n_active
+  // are not used by such a launch
+  int refine_rounds = 0;
+  uint32_t* rounds = nullptr;     // [reads of the batch] alignments run, written for every read of the launch (cleared by the caller)
+  uint32_t* converged = nullptr;  // [reads of the batch] set to 1 where the called path reproduces the guide (cleared by the caller)
 };
 
 // bytes of lattice one workgroup needs for a read of T rows: 25 B per band slot with probabilities (bE, bM doubles; float LPM,
@@ -54,7 +64,8 @@ uint64_t band_arena_bytes(uint64_t T, uint64_t bw, int job);
 int band_groups_per_cu(bool guided, int bw, int job);
 // job: 0 = Z only, 1 = align(calc_probabilities = true) up to the per-row path arrays (launch_segments follows), 2 = train:
 // the read's (w, s1, s2) column sums and transition counts in BandArgs::tr (finalise_train / pool_stats follow). Returns what
-// raising the dynamic-LDS limit (guided rows above 48 KiB) or the launch reported.
+// raising the dynamic-LDS limit (guided rows above 48 KiB) or the launch reported. hipErrorInvalidValue for a refining launch
+// (BandArgs::refine_rounds > 1) without a guide, with a job other than 1, with a border window or without rounds / converged.
 hipError_t launch_band_reads(int job, const BandArgs& a, int n_groups, hipStream_t s);
 
 }  // namespace dynk

@@ -62,7 +62,7 @@ void attach_cache(dyn_batch* b) {
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
                     &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_arena, &b->d_guide, &b->d_gref})
     d->cache = c;
-  for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->cache = c;
+  for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref}) h->cache = c;
 }
 
 int need_device(dyn_aligner* a) {
@@ -434,6 +434,7 @@ void dyn_aligner_destroy(dyn_aligner* a) {
     park_pool_buffer(a->device, 2, a->bits);
     a->free_list.release();
     a->ctl.release();
+    a->band_arena.release();
     a->h_rows.release();
     a->sess_anchor.release();
     for (int k = 0; k < 2; ++k) {
@@ -566,6 +567,25 @@ int dyn_aligner_set_border_confidence(dyn_aligner* a, int window) {
     return DYN_ERR_INVALID_ARGUMENT;
   }
   a->border_confidence = window;
+  return DYN_OK;
+}
+
+int dyn_aligner_set_auto_guide(dyn_aligner* a, uint32_t half_width, uint32_t max_rounds) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  auto fail = [&](const std::string& msg) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = "dyn_aligner_set_auto_guide: " + msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  };
+  if (half_width == 0) {  // off (max_rounds is not looked at)
+    a->auto_guide_hw = 0;
+    return DYN_OK;
+  }
+  if (half_width > (uint32_t)dynk::WIDE_MAX_HALF_BAND)
+    return fail("half_width " + std::to_string(half_width) + " is outside [1, " + std::to_string(dynk::WIDE_MAX_HALF_BAND) + "]");
+  if (max_rounds < 1 || max_rounds > 64) return fail("max_rounds " + std::to_string(max_rounds) + " is outside [1, 64]");
+  a->auto_guide_hw = half_width;
+  a->auto_guide_rounds = max_rounds;
   return DYN_OK;
 }
 
@@ -915,7 +935,7 @@ void dyn_batch_destroy(dyn_batch* b) {
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
                     &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl, &b->d_arena, &b->d_guide, &b->d_gref})
     d->release();
-  for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig}) h->release();
+  for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref}) h->release();
   for (hipEvent_t e : b->events) (void)hipEventDestroy(e);
   for (hipEvent_t e : {b->ev_in, b->ev_done, b->ev_out})
     if (e) (void)hipEventDestroy(e);
@@ -1036,6 +1056,57 @@ void finalise_train(const dyn_batch* b, const ReadState* st, const double* cw, c
   if (out->em_offsets) out->em_offsets[b->n] = b->capacity;
 }
 
+}  // namespace dyneng
+
+namespace dyneng {
+int enqueue_auto_guide(dyn_batch* b, uint32_t half_width) {
+  dyn_aligner* a = b->a;
+  const uint64_t total = b->n ? b->reads[b->n - 1].sig_off + b->reads[b->n - 1].S : 0;
+  // [guide | the pre-pass's queue head]. The head is not d_arena's: enqueue_job grows d_arena for the lattice arenas, and a buffer
+  // that grows goes back to the cache at once -- while the pre-pass of a ticket, which nobody waits for, may still be counting in it
+  const uint64_t head_off = (total * 4 + 255) / 256 * 256;
+  HIP_TRY(a, b->d_guide.ensure(head_off + 256));
+  // entries of reads that failed validation are never read; they are 0 in what dyn_batch_fetch_guide returns
+  if (total) HIP_TRY(a, hipMemsetAsync(b->d_guide.p, 0, total * 4, a->stream));
+  std::vector<uint32_t> order;
+  for (uint64_t i = 0; i < b->n; ++i)
+    if (b->reads[i].status == DYN_READ_OK) order.push_back((uint32_t)i);
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return b->reads[x].S > b->reads[y].S; });  // longest first
+  if (!order.empty()) {
+    // pinned and the batch's own: the copy below may still be pending when this returns
+    HIP_TRY(a, b->h_gdescs.ensure(order.size() * sizeof(ReadDesc)));
+    ReadDesc* descs = b->h_gdescs.as<ReadDesc>();
+    for (size_t k = 0; k < order.size(); ++k) {
+      const HostRead& r = b->reads[order[k]];
+      ReadDesc d{};
+      d.T = (uint32_t)(r.S + 1);
+      d.N = (uint32_t)(r.kc + 1);
+      d.read = order[k];
+      d.sig_off = r.sig_off;
+      d.par_off = r.flat_off;
+      d.seg_off = r.seg_off;
+      d.first_page = dynk::NO_PAGE;
+      descs[k] = d;
+    }
+    HIP_TRY(a, b->d_descs.ensure(order.size() * sizeof(ReadDesc)));  // (enqueue_job's table holds these reads at the most: it does not grow the buffer)
+    HIP_TRY(a, hipMemcpyAsync(b->d_descs.p, descs, order.size() * sizeof(ReadDesc), hipMemcpyHostToDevice, a->stream));
+    dynk::AutoGuideArgs ag{};
+    ag.descs = b->d_descs.as<ReadDesc>();
+    ag.n_reads = (int)order.size();
+    ag.bw = (int)half_width;
+    ag.sig = b->d_sig.as<double>();
+    ag.par = b->d_par.as<Emis>();
+    ag.guide = b->d_guide.as<int32_t>();
+    ag.head = reinterpret_cast<uint32_t*>(b->d_guide.as<char>() + head_off);
+    ag.m1 = a->model.log_m1;
+    ag.e2 = a->model.log_e2;
+    const int groups = (int)std::min<uint64_t>(order.size(), (uint64_t)a->n_cus * (uint64_t)dynk::auto_guide_groups_per_cu((int)half_width));
+    HIP_TRY(a, dynk::launch_auto_guide(ag, groups, a->stream));
+  }
+  b->guided = true;
+  b->guide_hw = half_width;
+  return DYN_OK;
+}
 }  // namespace dyneng
 
 namespace {
@@ -1172,51 +1243,10 @@ int dyn_batch_auto_guide(dyn_batch* b, uint32_t half_width) {
     return fail("half_width " + std::to_string(half_width) + " is outside [1, " + std::to_string(dynk::WIDE_MAX_HALF_BAND) + "]");
   if (int rc = need_device(a)) return rc;  // ("no GPU bound to this handle": the pre-pass is a kernel)
   if (int rc = dyneng::session_quiesce(a)) return rc;
-  const uint64_t total = b->n ? b->reads[b->n - 1].sig_off + b->reads[b->n - 1].S : 0;
-  HIP_TRY(a, b->d_guide.ensure(std::max<uint64_t>(4, total * 4)));
-  // entries of reads that failed validation are never read; they are 0 in what dyn_batch_fetch_guide returns
-  if (total) HIP_TRY(a, hipMemsetAsync(b->d_guide.p, 0, total * 4, a->stream));
-  std::vector<uint32_t> order;
-  for (uint64_t i = 0; i < b->n; ++i)
-    if (b->reads[i].status == DYN_READ_OK) order.push_back((uint32_t)i);
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return b->reads[x].S > b->reads[y].S; });  // longest first
-  if (!order.empty()) {
-    std::vector<ReadDesc> descs(order.size());
-    for (size_t k = 0; k < order.size(); ++k) {
-      const HostRead& r = b->reads[order[k]];
-      ReadDesc d{};
-      d.T = (uint32_t)(r.S + 1);
-      d.N = (uint32_t)(r.kc + 1);
-      d.read = order[k];
-      d.sig_off = r.sig_off;
-      d.par_off = r.flat_off;
-      d.seg_off = r.seg_off;
-      d.first_page = dynk::NO_PAGE;
-      descs[k] = d;
-    }
-    HIP_TRY(a, b->d_descs.ensure(descs.size() * sizeof(ReadDesc)));
-    HIP_TRY(a, b->d_arena.ensure(256));
-    HIP_TRY(a, hipMemcpyAsync(b->d_descs.p, descs.data(), descs.size() * sizeof(ReadDesc), hipMemcpyHostToDevice, a->stream));
-    dynk::AutoGuideArgs ag{};
-    ag.descs = b->d_descs.as<ReadDesc>();
-    ag.n_reads = (int)descs.size();
-    ag.bw = (int)half_width;
-    ag.sig = b->d_sig.as<double>();
-    ag.par = b->d_par.as<Emis>();
-    ag.guide = b->d_guide.as<int32_t>();
-    ag.head = b->d_arena.as<uint32_t>();
-    ag.m1 = a->model.log_m1;
-    ag.e2 = a->model.log_e2;
-    const int groups = (int)std::min<uint64_t>(descs.size(), (uint64_t)a->n_cus * (uint64_t)dynk::auto_guide_groups_per_cu((int)half_width));
-    const hipError_t le = dynk::launch_auto_guide(ag, groups, a->stream);
-    const hipError_t se = hipStreamSynchronize(a->stream);  // descs is a local vector; a fault of the kernel surfaces here
-    HIP_TRY(a, le);
-    HIP_TRY(a, se);
-  } else {
-    HIP_TRY(a, hipStreamSynchronize(a->stream));
-  }
-  b->guided = true;
-  b->guide_hw = half_width;
+  const int rc = dyneng::enqueue_auto_guide(b, half_width);
+  const hipError_t se = hipStreamSynchronize(a->stream);  // a fault of the kernel surfaces here
+  if (rc != DYN_OK) return rc;
+  HIP_TRY(a, se);
   return DYN_OK;
 }
 
@@ -1266,6 +1296,11 @@ int dyn_batch_fetch_guide_rounds(dyn_batch* b, uint32_t* rounds, uint32_t* conve
   if (n < b->n) return fail("n is smaller than the batch's read count");
   if (int rc = need_device(a)) return rc;
   if (!b->n) return DYN_OK;
+  if (b->gref_ready && b->async) {  // a ticket: the counts came home with its state
+    std::memcpy(rounds, b->h_gref.as<uint32_t>(), b->n * 4);
+    std::memcpy(converged, b->h_gref.as<uint32_t>() + b->n, b->n * 4);
+    return DYN_OK;
+  }
   if (b->gref_ready) {
     HIP_TRY(a, copy_out(a, rounds, b->d_gref.as<uint32_t>(), b->n * 4));
     HIP_TRY(a, copy_out(a, converged, b->d_gref.as<uint32_t>() + b->n, b->n * 4));

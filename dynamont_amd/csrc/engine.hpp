@@ -156,6 +156,11 @@ struct dyn_aligner {
   int segment_scores = 0;     // dyn_aligner_set_segment_scores (window, 0 = off): read by every batch / ticket at its submission
   int border_confidence = 0;  // dyn_aligner_set_border_confidence (window, 0 = off): read by every batch / ticket at its submission
   bool band_margin = false;   // dyn_aligner_set_band_margin: read by every batch / ticket at its submission
+  // dyn_aligner_set_auto_guide (half width, 0 = off; alignments per read): read by every align(calc = 1) TICKET at its submission
+  uint32_t auto_guide_hw = 0, auto_guide_rounds = 8;
+  // queue head + lattice arenas of the self-guided tickets (band_reads.hip): grow-only, the handle's, shared by every such ticket
+  // in stream order (launch.cpp, enqueue_job) and released with the handle
+  dyneng::DevBuf band_arena;
   dyneng::DevBuf d_ksum;      // [6 num_kmers + 4] u64: the per-k-mer accumulator and its totals (kmer_summary_kernels.hpp),
                               // allocated and zeroed by the first dyn_aligner_set_kmer_summary(a, 1)
   bool ntk = false;     // created with mode "resquiggle" / "ntk"
@@ -290,6 +295,13 @@ struct dyn_batch {
   uint32_t guide_refine = 1;
   dyneng::DevBuf d_gref;        // uint32 [n] rounds | [n] converged | [64] the two list lengths | [n] | [n] the two lists of reads
   bool gref_ready = false;      // the last job refined: d_gref holds rounds / converged
+  // the self-guided band of a TICKET (dyn_aligner_set_auto_guide): the handle's half width (0: a plain ticket) and alignments per
+  // read when the ticket was submitted. Such a ticket runs alone -- never merged, never published into a resident session: the
+  // front thread makes its guide on the compute stream (enqueue_auto_guide) and enqueue_job aligns it as a guided batch, every
+  // read refined inside ONE launch (band_reads.hpp, BandArgs::refine_rounds)
+  uint32_t ag_want = 0, ag_rounds = 1;
+  dyneng::PinnedBuf h_gdescs;   // the guide pre-pass's descriptor table (enqueue_job fills h_descs while that copy may be pending)
+  dyneng::PinnedBuf h_gref;     // a ticket's rounds | converged, copied out with its state
   uint64_t arena_bytes = 0;     // what the last job asked of d_arena beyond the queue head: every workgroup's lattice arena
   bool host_only = false;       // created on a handle without a device: the read table alone (validation, no job)
   dyneng::SessionGeom sess_geom;  // session_plan's decision for this ticket (ok = false: none taken)
@@ -375,6 +387,10 @@ int host_prepare(dyn_batch* b, const dynhost::PoreModel& m, bool pinned, uint64_
 int alloc_batch_buffers(dyn_batch* b, uint64_t total_sig);
 // enqueue every kernel of `job` on the handle's compute stream without synchronising the host
 int enqueue_job(dyn_batch* b, DynJob job);
+// the guide pre-pass of dyn_batch_auto_guide / of a ticket under dyn_aligner_set_auto_guide, on the compute stream behind the
+// batch's preprocessing: d_guide zero-filled, the descriptor table (longest read first, in the batch's pinned h_gdescs),
+// launch_auto_guide. Marks the batch guided at half_width; does not wait. Caller holds a->mu, the session is quiesced.
+int enqueue_auto_guide(dyn_batch* b, uint32_t half_width);
 // ---- resident read queue (session.cpp); all under a->mu ----
 // could this ticket run in a session at all? (before host_prepare: kind and size only)
 bool session_candidate(const dyn_batch* b);

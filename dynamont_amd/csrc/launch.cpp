@@ -469,10 +469,15 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   // per-segment kernels all). One lattice arena per workgroup, sized for the largest of them (none for Z only)
   uint64_t wide_arena = 0;
   int wide_groups = 0;
+  // The arenas are the batch's own -- except a self-guided TICKET's (dyn_aligner_set_auto_guide), which uses the handle's: a
+  // stream keeps many tickets in flight, each would hold workgroups x its largest lattice until the caller lets go of it (eight
+  // tickets of 1 024 reads of 20 k samples at half width 64: 67 GB each), and only the ticket the compute stream is working on
+  // needs them. Stream order hands the handle's arenas from one ticket to the next.
+  dyneng::DevBuf& arena_buf = (b->async && b->guided) ? a->band_arena : b->d_arena;
   if (!wide.empty()) {
     size_t free_b = 0, total_b = 0;
     HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
-    uint64_t room = (uint64_t)((double)(free_b + b->d_arena.bytes + parked_bytes(a->device)) * 0.8);
+    uint64_t room = (uint64_t)((double)(free_b + arena_buf.bytes + parked_bytes(a->device)) * 0.8);
     if (b->guided && a->mem_budget && room > a->mem_budget) room = a->mem_budget;
     size_t wr = 0;
     for (uint32_t i : wide) {
@@ -615,8 +620,10 @@ int enqueue_job(dyn_batch* b, DynJob job) {
         const uint64_t want = 256 + (uint64_t)wide_groups * wide_arena;
         size_t free_b = 0, total_b = 0;
         HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
-        if (want > b->d_arena.bytes && want > (uint64_t)((double)free_b * 0.95)) free_parked(a->device);  // (counted as room above)
-        HIP_TRY(a, b->d_arena.ensure(want));
+        if (want > arena_buf.bytes && want > (uint64_t)((double)free_b * 0.95)) free_parked(a->device);  // (counted as room above)
+        // (growing the handle's arenas releases the old ones, which the ticket before this one may still be working in)
+        if (want > arena_buf.bytes && &arena_buf == &a->band_arena) HIP_TRY(a, hipStreamSynchronize(a->stream));
+        HIP_TRY(a, arena_buf.ensure(want));
         b->arena_bytes = want - 256;
       }
       dynk::BandArgs ba{};
@@ -629,8 +636,8 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       ba.st = q.st;
       ba.tb = q.tb;
       ba.tr = q.tr;
-      ba.head = b->d_arena.as<uint32_t>();
-      ba.arena = b->d_arena.as<char>() + 256;
+      ba.head = arena_buf.as<uint32_t>();
+      ba.arena = arena_buf.as<char>() + 256;
       ba.arena_bytes = wide_arena;
       ba.exp_tab = reinterpret_cast<const uint64_t*>(a->d_sptab.as<dynmath::SoftplusNode>() + dynmath::SP_NODES + dynmath::EXP128_NODES);
       ba.m1 = m.log_m1;
@@ -639,12 +646,25 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       ba.border_window = q.border_window;  // (guided batches refuse the rider: dynamont_mi.cpp)
       ba.border_p = q.border_p;
       ba.border_window_p = q.border_window_p;
+      // A TICKET that refines (dyn_aligner_set_auto_guide): ONE launch in which the workgroup that holds a read aligns it until
+      // its guide reproduces itself (BandArgs::refine_rounds) -- a launch per round lasts as long as its longest read however
+      // few reads are still open, which a stream of tickets cannot afford. The synchronous batch keeps the round scheme below:
+      // it is what the refining launch is checked against, bit for bit.
+      const bool refine_in_launch = refine_rounds > 1 && b->async;
+      if (refine_in_launch) {
+        HIP_TRY(a, b->d_gref.ensure(std::max<uint64_t>(8, 2 * b->n * 4)));
+        HIP_TRY(a, hipMemsetAsync(b->d_gref.p, 0, 2 * b->n * 4, a->stream));
+        ba.refine_rounds = (int)refine_rounds;
+        ba.rounds = b->d_gref.as<uint32_t>();
+        ba.converged = b->d_gref.as<uint32_t>() + b->n;
+        b->gref_ready = true;
+      }
       HIP_TRY(a, dynk::launch_band_reads(band_job, ba, wide_groups, a->stream));
       // guide refinement (dyn_batch_set_guide_refine): behind every alignment a step that makes the called path the next
       // guide of the reads whose guide it does not reproduce, and the list of those reads the next alignment's queue. Every
       // round is enqueued; a round whose list is empty ends at its first queue read. What follows the traceback
       // (launch_segments and the riders below) runs once, behind the last round
-      if (refine_rounds > 1) {
+      if (refine_rounds > 1 && !refine_in_launch) {
         const uint64_t nb = b->n, nw = wide.size();
         HIP_TRY(a, b->d_gref.ensure((2 * nb + 64 + 2 * nw) * 4));
         uint32_t* g = b->d_gref.as<uint32_t>();

@@ -181,7 +181,9 @@ bool session_candidate(const dyn_batch* b) {
   // Tickets that rescale (dyn_aligner_set_rescale) stay on one launch per batch as well: their passes run back to back in
   // stream order (launch.cpp, enqueue_job), which costs what a session gains over it (README: 476 against 533 Msamp/s) for
   // every pass. Publishing such a ticket into the session once per pass is a follow-up.
-  return a->sess_enabled.load() && !a->host_only && !a->ntk && b->async && b->job == DynJob::AlignFull && b->rs_want == 0 && b->bc_want == 0 &&
+  // A self-guided ticket (dyn_aligner_set_auto_guide) takes the banded-lattice kernel, as a ticket that holds a wide read does:
+  // a launch of its own, for which an open session is quiesced.
+  return a->sess_enabled.load() && !a->host_only && !a->ntk && b->async && b->job == DynJob::AlignFull && b->rs_want == 0 && b->bc_want == 0 && b->ag_want == 0 &&
          (a->sess_open_hint.load() || b->n >= SESSION_MIN_READS);
 }
 

@@ -121,11 +121,22 @@ def parse(argv=None) -> Namespace:
                         "(the same bytes for any number of GPUs); the CSV is unchanged")
     p.add_argument("--band", type=int, default=400, metavar="COLUMNS",
                    help="band width of the alignment lattice in columns (default 400, the reference's; up to 4093)")
+    p.add_argument("--guide-auto", type=int, default=0, metavar="HW",
+                   help="align inside a window of HW lattice columns on either side of a guide made on the GPU from the signal and "
+                        "the sequence alone (no move table needed); not together with --rescale-iters or --border-confidence "
+                        "(0: off)")
+    p.add_argument("--guide-rounds", type=int, default=8, metavar="R",
+                   help="with --guide-auto: alignments per read at the most while its guide is refined (1 .. 64)")
     p.add_argument("--parallel-zstd-frames", action="store_true",
                    help="write the CSV as consecutive independent zstd frames (readers must read across frames: "
                         "python-zstandard's defaults stop after the first). Default: one frame, like the reference, "
                         "compressed on several threads either way")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.guide_auto and args.rescale_iters:
+        p.error("--guide-auto and --rescale-iters are mutually exclusive")
+    if args.guide_auto and args.border_confidence:
+        p.error("--guide-auto and --border-confidence are mutually exclusive")
+    return args
 
 
 def listener(q, outfile: str, header: bytes = CSV_HEADER) -> None:
@@ -370,6 +381,19 @@ def band_report_bytes(lines) -> bytes:
     return BAND_REPORT_HEADER + "".join(ln + "\n" for ln in sorted(lines)).encode()
 
 
+def _report_band(aligner) -> int:
+    """the ``band`` column of --band-report: under --guide-auto the margins are those against the guided window, 2 * HW wide"""
+    return 2 * aligner._auto_guide[0] if aligner._auto_guide[0] else aligner.band
+
+
+def _guide_counts(t) -> tuple:
+    """--guide-auto: (reads aligned inside their own guide, those of them whose guide did not converge) of a COMPLETED ticket"""
+    from dynamont_amd._dynamont import Batch
+    ok = np.asarray(t.result.status[:t.result.n]) == 0
+    _, converged = Batch.guide_rounds(t)
+    return int(ok.sum()), int((ok & (converged == 0)).sum())
+
+
 def _ticket_band_lines(aligner, t, readids, lengths, seq_off) -> list:
     """the report lines of a COMPLETED align ticket submitted with the band-margin switch on"""
     from dynamont_amd import _native as N
@@ -379,7 +403,7 @@ def _ticket_band_lines(aligner, t, readids, lengths, seq_off) -> list:
                                            edge.ctypes.data_as(N.c_u32_p), n))
     bases = np.diff(np.asarray(seq_off, dtype=np.int64))
     cols = np.maximum(bases - aligner.kmer_size + 1, 0) + 1
-    return band_report_lines(readids, np.asarray(lengths, dtype=np.int64) + 1, cols, aligner.band, low, high, edge)
+    return band_report_lines(readids, np.asarray(lengths, dtype=np.int64) + 1, cols, _report_band(aligner), low, high, edge)
 
 
 def _stored_bases(p) -> int:
@@ -463,6 +487,7 @@ class _Pipeline:
         self.inflight = queue_mod.Queue(maxsize=max(1, depth))
         self.free = []            # result objects of completed batches, refilled instead of reallocated
         self.band_lines = []      # --band-report: the lines of the tickets completed so far
+        self.guide_counts = [0, 0]  # --guide-auto: reads aligned inside their own guide, reads whose guide did not converge
         self.error = None
         self.rounds_done = queue_mod.Queue()
         self.consumer = threading.Thread(target=self._drain, daemon=True)
@@ -511,10 +536,13 @@ class _Pipeline:
     def _finish(self, t, g, seqs, seq_off) -> None:
         from dynamont_amd._dynamont import format_csv
         res = t.wait()
+        if self.aligner._auto_guide[0]:
+            for k, v in enumerate(_guide_counts(t)):
+                self.guide_counts[k] += v
         if self.aligner._band_margin:
             self.band_lines += band_report_lines([p[2][6] for p in g], [len(p[0]) + 1 for p in g],
                                                  np.maximum(np.diff(np.asarray(seq_off, dtype=np.int64)) - self.aligner.kmer_size + 1, 0) + 1,
-                                                 self.aligner.band, res.band_margin_low, res.band_margin_high, res.band_edge_rows)
+                                                 _report_band(self.aligner), res.band_margin_low, res.band_margin_high, res.band_edge_rows)
         starts = [p[2][3] for p in g]
         buf, begin, end = format_csv(self.aligner, res, None, [p[2][6] for p in g], [p[2][7] for p in g], starts,
                                      [len(p[0]) + st for p, st in zip(g, starts)], threads=self.threads, compact=True,
@@ -587,6 +615,7 @@ class _NativePipeline:
         self.free = []   # result objects of consumed batches
         self.band_meta = {}   # --band-report: batch number -> (readids, signal lengths, sequence offsets)
         self.band_lines = []  # ... and the lines of the tickets the sink has consumed
+        self.guide_counts = [0, 0]  # --guide-auto: reads aligned inside their own guide, reads whose guide did not converge
 
     def put(self, line: str) -> None:
         """an error line from the producer (reads that failed before the aligner, segment.py:178-187)"""
@@ -610,7 +639,10 @@ class _NativePipeline:
             self.L.dyn_csv_sink_wait(self.h, self.submitted - block_until, 200)
 
     def _band_collect(self, k: int, t) -> None:
-        """--band-report: the margins of a ticket the sink is done with, before the ticket goes"""
+        """--band-report: the margins of a ticket the sink is done with, before the ticket goes (and --guide-auto's counts)"""
+        if self.aligner._auto_guide[0]:
+            for j, v in enumerate(_guide_counts(t)):
+                self.guide_counts[j] += v
         meta = self.band_meta.pop(k, None)
         if meta is not None:
             self.band_lines += _ticket_band_lines(self.aligner, t, *meta)
@@ -786,11 +818,15 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             minq: float = 0, device: int = 0, batch_reads: int = 1024, mem_budget_gib: float = 0.0,
             host_preprocess: bool = False, depth: int = 12, strict_ties: str = "ties", host_threads: int = 0,
             zstd_level: int = 3, event_stats: bool = False, rescale_iters: int = 0, kmer_summary: str = "",
-            segment_scores: int = 0, border_confidence: int = 0, band_report: str = "", band: int = 400) -> None:
+            segment_scores: int = 0, border_confidence: int = 0, band_report: str = "", band: int = 400,
+            guide_auto: int = 0, guide_rounds: int = 8) -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
-    that gather at the end is the only exchange)."""
+    that gather at the end is the only exchange). ``guide_auto`` > 0: every batch is aligned inside guides the library
+    makes itself at that half width, refined up to ``guide_rounds`` alignments per read (``Aligner.set_auto_guide``)."""
+    if guide_auto < 0 or (guide_auto and (rescale_iters or border_confidence)):
+        raise ValueError("--guide-auto must be >= 0 and is not combined with --rescale-iters or --border-confidence")
     from dynamont_amd import parallel
     comm, local_rank = parallel.init_from_env()
     rank, world = (comm.rank, comm.world) if comm else (0, 1)
@@ -867,6 +903,12 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             f.write(band_report_bytes(lines))
         print(f"band report written: {band_report}", file=sys.stderr, flush=True)
 
+    def guide_summary(counts):
+        # --guide-auto: this process's reads (every rank reports its own)
+        if guide_auto:
+            print(f"Reads aligned inside their own guide: {counts[0]}; of those, reads whose guide did not converge within "
+                  f"{guide_rounds} alignments: {counts[1] if guide_rounds != 1 else 0}", file=sys.stderr, flush=True)
+
     # A failing rank ends the whole job (parallel.abort): a barrier in a `finally` would leave the other ranks in
     # their next collective until the process-group timeout.
     with parallel.abort_on_error(comm):
@@ -890,6 +932,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                 aligner.set_kmer_summary(True)
             if band_report:
                 aligner.set_band_margin(True)
+            if guide_auto:
+                aligner.set_auto_guide(guide_auto, guide_rounds)
             if native:
                 import os
                 import tempfile
@@ -948,6 +992,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                         pipe.submit(pending)
                 _stamp("every batch submitted")
                 pipe.close()
+                guide_summary(pipe.guide_counts)
                 band_lines, pipe = pipe.band_lines, None
                 _stamp("pipeline closed: output complete")
                 if comm is not None:
@@ -995,6 +1040,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                     ship()
                     break
             pipe.close()
+            guide_summary(pipe.guide_counts)
             band_lines, pipe = pipe.band_lines, None
             write_summary(aligner)
             write_band_report(band_lines)
@@ -1040,7 +1086,8 @@ def main(argv=None) -> None:
             host_preprocess=args.host_preprocess, depth=args.depth, strict_ties=args.strict_ties, host_threads=args.host_threads,
             zstd_level=args.zstd_level, event_stats=args.event_stats, rescale_iters=args.rescale_iters,
             kmer_summary=args.kmer_summary, segment_scores=args.segment_scores,
-            border_confidence=args.border_confidence, band_report=args.band_report, band=args.band)
+            border_confidence=args.border_confidence, band_report=args.band_report, band=args.band,
+            guide_auto=args.guide_auto, guide_rounds=args.guide_rounds)
     _stamp("segment() returned (aligner closed)")
     if argv is None and not int(__import__("os").environ.get("WORLD_SIZE", "1") or 1) > 1:
         # Invoked as the command (console script / python -m), single process, everything written and closed: leave without

@@ -778,6 +778,20 @@ int dyn_batch_fetch_guide(dyn_batch* b, int32_t* out, uint64_t count);
  * read that never reached the device), converged[i] = 1 where its last called path reproduced its guide (always 0 without
  * dyn_batch_set_guide_refine(max_rounds > 1)). n >= the batch's read count. */
 int dyn_batch_fetch_guide_rounds(dyn_batch* b, uint32_t* rounds, uint32_t* converged, uint64_t n);
+/* (added within ABI 10) The self-guided band for asynchronous tickets. While half_width > 0, every align ticket with
+ * calc_probabilities = 1 (dyn_batch_align_async, dyn_batch_align_raw_async, dyn_batch_align_vbz_async) is aligned as a
+ * synchronous batch is after dyn_batch_auto_guide(b, half_width) + dyn_batch_set_guide_refine(b, max_rounds): the same
+ * status, Z, rows, rounds, converged flags and final guides, bit for bit. The switch is read when a ticket is submitted;
+ * Z-only tickets, train tickets, synchronous batches and dyn_multi_* are untouched by it. Such a ticket is a launch of its
+ * own: it is not merged with others and not published into the resident read queue (an open session is closed and waited
+ * for first, as for a ticket that holds a wide read), and with max_rounds > 1 every read is refined inside that one launch,
+ * by the workgroup that holds it. After dyn_batch_wait, dyn_batch_fetch_guide_rounds and dyn_batch_fetch_guide work on the
+ * ticket; event stats, segment scores, the k-mer summary and the band margins (against the guided window) combine with it.
+ * half_width 0 (the default): off, max_rounds is not looked at. Otherwise half_width in [1, 2046] and max_rounds in [1, 64]
+ * (1 = the pre-pass and one alignment), else DYN_ERR_INVALID_ARGUMENT + message. A ticket submitted while the switch is on
+ * together with dyn_aligner_set_rescale(iters > 0) or dyn_aligner_set_border_confidence(window > 0) is refused at submission
+ * (DYN_ERR_INVALID_ARGUMENT + message), as dyn_batch_align refuses the pairing on a guided batch. */
+int dyn_aligner_set_auto_guide(dyn_aligner* a, uint32_t half_width, uint32_t max_rounds);
 /* (added within ABI 10) Device bytes the batch's last job allocated for per-workgroup lattice arenas: workgroups x the largest
  * read's lattice, for the guided kernel (dyn_batch_set_guide) or the generic wide-band kernel (one kernel: band_reads.hip); 25 B per band slot
  * for align with probabilities, 16 B for dyn_batch_train / dyn_batch_train_guided; 0 for a batch whose reads all took the paged
