@@ -117,6 +117,22 @@ class AlignBatchResult:
         self.band_margin_low = self.band_margin_high = self.band_edge_rows = None
         self.guide_rounds = self.guide_converged = self.guides = None  # Aligner.align_batch_auto / align_batch_guided(refine > 1)
         self.band_used = None
+        # guide rescue (Aligner.set_guide_rescue): uint8 [n] per-read code (0 not flagged, 1 rescued, 2 no room, 3 the rescue
+        # failed), None when off; guide_rounds / guide_converged then hold the rescued reads' counts (0 for every other read)
+        self.rescue = None
+
+    def _fetch_rescue(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
+        """dyn_batch_fetch_rescue into ``rescue`` / ``guide_rounds`` / ``guide_converged``, or drop what an earlier rescue left."""
+        if not wanted:
+            if self.rescue is not None:  # a result object refilled from a rescued job must not keep that job's counts
+                self.rescue = self.guide_rounds = self.guide_converged = None
+            return
+        self.rescue = np.zeros(self.n, dtype=np.uint8)
+        self.guide_rounds, self.guide_converged = np.zeros(self.n, dtype=np.uint32), np.zeros(self.n, dtype=np.uint32)
+        rc = L.dyn_batch_fetch_rescue(handle, _ptr(self.rescue, N.c_u8_p), _ptr(self.guide_rounds, N.c_u32_p),
+                                      _ptr(self.guide_converged, N.c_u32_p), self.n)
+        if rc != N.DYN_OK:
+            _raise(rc, aligner.last_error())
 
     def _fetch_band_margin(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
         """dyn_batch_fetch_band_margin into this object's per-read columns (allocated on first use), or drop them."""
@@ -224,6 +240,8 @@ class AlignBatchResult:
             d["band_margin_low"] = int(self.band_margin_low[i])
             d["band_margin_high"] = int(self.band_margin_high[i])
             d["band_edge_rows"] = int(self.band_edge_rows[i])
+        if self.rescue is not None:  # only when requested (Aligner.set_guide_rescue)
+            d["rescue"] = int(self.rescue[i])
         return d
 
 
@@ -391,6 +409,7 @@ class Batch:
         self._scores = bool(calc_probabilities) and self._al._segment_scores > 0
         self._borders = bool(calc_probabilities) and self._al._border_confidence > 0
         self._margins = bool(calc_probabilities) and self._al._band_margin
+        self._rescued = self._al._ticket_rescue(bool(calc_probabilities))
         rc = self._L.dyn_batch_align(self._h, int(bool(calc_probabilities)))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
@@ -465,6 +484,7 @@ class Batch:
         out._fetch_scores(self._L, self._h, self._al, getattr(self, "_scores", False))
         out._fetch_borders(self._L, self._h, self._al, getattr(self, "_borders", False))
         out._fetch_band_margin(self._L, self._h, self._al, getattr(self, "_margins", False))
+        out._fetch_rescue(self._L, self._h, self._al, getattr(self, "_rescued", False))
         return out
 
     def fetch_events(self, out: N.DynEventOut) -> None:
@@ -550,7 +570,7 @@ class AsyncBatch:
     (the library reads them until the batch is complete)."""
 
     def __init__(self, aligner: "Aligner", handle, result, keep, levels: bool = False, rescale: bool = False,
-                 scores: bool = False, borders: bool = False, margins: bool = False, auto_guide=None):
+                 scores: bool = False, borders: bool = False, margins: bool = False, auto_guide=None, rescue: bool = False):
         self._al = aligner
         self._L = N.lib()
         self._h = handle
@@ -564,6 +584,7 @@ class AsyncBatch:
         self._margins = margins  # ... with the band-margin switch on (tickets report margins; they are never retried)
         # ... with the auto-guide switch on (Aligner.set_auto_guide): (alignments per read, the ticket's sample offsets), else None
         self._auto_guide = auto_guide
+        self._rescued = rescue  # ... with the guide-rescue switch on (Aligner.set_guide_rescue)
         self._sig_off = auto_guide[1] if auto_guide is not None else None  # what Batch.guide cuts the flat guide at
 
     def wait(self):
@@ -582,6 +603,8 @@ class AsyncBatch:
                 self.result.guide_rounds = self.result.guide_converged = self.result.guides = None
                 if self._auto_guide is not None and self._auto_guide[0] != 1:
                     self.result.guide_rounds, self.result.guide_converged = Batch.guide_rounds(self)
+                self.result.rescue = None
+                self.result._fetch_rescue(self._L, self._h, self._al, self._rescued)
         return self.result
 
     @property
@@ -706,6 +729,7 @@ class Aligner:
     _band_margin = False  # set_band_margin
     _auto_guide = (0, 8)  # set_auto_guide: (half_width, refine)
     _band_retry = None  # set_band_retry: (min_margin, max_band, factor)
+    _guide_rescue = (0, 0, 8)  # set_guide_rescue: (min_margin, half_width, refine)
     _kmer_summary = False  # set_kmer_summary
     _strict = 1  # set_strict
     _model_override = None  # set_model: (mean, stdev)
@@ -850,6 +874,29 @@ class Aligner:
             _raise(rc, self.last_error())
         self._auto_guide = (int(half_width), int(refine))
 
+    def set_guide_rescue(self, min_margin: int, half_width: int, refine: int = 8) -> None:
+        """dyn_aligner_set_guide_rescue: while ``half_width`` (1 .. 2046) > 0, ``align_batch`` and the ``align_async`` /
+        ``align_raw_async`` / ``align_vbz_async`` tickets with ``calc_probabilities=True`` align every read as usual, take every
+        read's band margins against the diagonal band and align again -- inside a guide the library makes itself, refined up to
+        ``refine`` (1 .. 64) alignments, as ``align_batch_auto(.., half_width, refine)`` would -- only the ok reads whose
+        ``min(band_margin_low, band_margin_high)`` is below ``min_margin`` (>= 0; 0 flags nothing), all on the device within
+        the same batch or ticket. Results gain ``rescue`` (uint8 [n]: 0 not flagged, 1 rescued, 2 flagged but its lattice does
+        not fit the memory budget, 3 flagged but the rescue failed -- 2 and 3 keep the plain answer) and ``guide_rounds`` /
+        ``guide_converged`` (0 for reads that were not rescued); ``read(i)`` gains ``"rescue"``. A read the plain alignment
+        failed is not rescued. With ``set_band_margin(True)`` a rescued read reports margins against its guided window.
+        ``half_width = 0`` turns it off. Not together with ``set_band_retry`` (ValueError); a job started with ``set_rescale``,
+        ``set_border_confidence`` or ``set_auto_guide`` on as well is refused (ValueError). ``MultiAligner`` has no such switch."""
+        if int(half_width) > 0 and self._band_retry:
+            raise ValueError("set_guide_rescue with set_band_retry: both re-align the reads a margin flags; choose one")
+        rc = self._L.dyn_aligner_set_guide_rescue(self._h, int(min_margin), int(half_width), int(refine))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        self._guide_rescue = (int(min_margin), int(half_width), int(refine)) if int(half_width) > 0 else (0, 0, 8)
+
+    def _ticket_rescue(self, calc_probabilities: bool) -> bool:
+        """does an align job / ticket submitted now run under the guide-rescue switch?"""
+        return self._guide_rescue[1] > 0 and calc_probabilities and self._ctor[2] not in ("ntk", "resquiggle")
+
     def _ticket_guide(self, calc_probabilities: bool, offsets):
         """what AsyncBatch keeps of the auto-guide switch for an align ticket submitted now"""
         if not (self._auto_guide[0] > 0 and calc_probabilities and self._ctor[2] not in ("ntk", "resquiggle")):
@@ -902,6 +949,8 @@ class Aligner:
         if min_margin == 0:
             self._band_retry = None
             return
+        if self._guide_rescue[1] > 0:
+            raise ValueError("set_band_retry with set_guide_rescue: both re-align the reads a margin flags; choose one")
         if self._kmer_summary:
             raise ValueError("set_band_retry with set_kmer_summary: the retried reads would be summed twice")
         self.set_band_margin(True)
@@ -1069,7 +1118,8 @@ class Aligner:
                           scores=self._segment_scores > 0 and bool(calc_probabilities),
                           borders=self._border_confidence > 0 and bool(calc_probabilities),
                           margins=self._band_margin and bool(calc_probabilities),
-                          auto_guide=self._ticket_guide(bool(calc_probabilities), sig_off))
+                          auto_guide=self._ticket_guide(bool(calc_probabilities), sig_off),
+                          rescue=self._ticket_rescue(bool(calc_probabilities)))
 
     def _raw_args(self, raw, shift, scale, calibration=None):
         scattered = isinstance(raw, (list, tuple))
@@ -1124,7 +1174,8 @@ class Aligner:
                           scores=self._segment_scores > 0 and bool(calc_probabilities),
                           borders=self._border_confidence > 0 and bool(calc_probabilities),
                           margins=self._band_margin and bool(calc_probabilities),
-                          auto_guide=self._ticket_guide(bool(calc_probabilities), raw_off))
+                          auto_guide=self._ticket_guide(bool(calc_probabilities), raw_off),
+                          rescue=self._ticket_rescue(bool(calc_probabilities)))
 
     def align_vbz_async(self, chunks, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 3,
                         n_sigmas: float = 3.0, f32: bool = False, calc_probabilities: bool = True,
@@ -1163,7 +1214,8 @@ class Aligner:
                           scores=self._segment_scores > 0 and bool(calc_probabilities),
                           borders=self._border_confidence > 0 and bool(calc_probabilities),
                           margins=self._band_margin and bool(calc_probabilities),
-                          auto_guide=self._ticket_guide(bool(calc_probabilities), raw_off))
+                          auto_guide=self._ticket_guide(bool(calc_probabilities), raw_off),
+                          rescue=self._ticket_rescue(bool(calc_probabilities)))
 
     def train_raw_async(self, raw, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 7,
                         n_sigmas: float = 5.0, f32: bool = True, pooled: bool = False,

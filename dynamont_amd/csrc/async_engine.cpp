@@ -14,7 +14,7 @@
 //
 // Stream order does all GPU-side synchronisation (events between the three streams); the only host
 // waits are the back thread's hipEventSynchronize on a batch's last D2H and the caller's wait().
-#include "engine.hpp"
+#include "engine_internal.hpp"
 #include "vbz_decode.hpp"
 
 #include <algorithm>
@@ -149,7 +149,8 @@ static bool mergeable(const dyn_batch* x) {
   // batches that leave the waves underfilled (fewer than 1.5 reads per wave slot): a batch of four reads per slot balances
   // by itself, and merging those only makes the pipeline lumpy
   // (a self-guided ticket carries a guide of its own and takes the banded-lattice kernel: never merged)
-  return x->job != DynJob::Train && x->ag_want == 0 && x->n > 0 && 2 * x->n <= 3 * (uint64_t)x->a->n_cus * dynk::WAVES_PER_CU;
+  // (nor is a ticket under the guide rescue: its list of reads to re-align is its own)
+  return x->job != DynJob::Train && x->ag_want == 0 && x->gr_hw == 0 && x->n > 0 && 2 * x->n <= 3 * (uint64_t)x->a->n_cus * dynk::WAVES_PER_CU;
 }
 static bool same_kind(const dyn_batch* x, const dyn_batch* y) {
   if (x->job != y->job || x->has_raw != y->has_raw || x->ev_want != y->ev_want || x->rs_want != y->rs_want || x->sc_want != y->sc_want ||
@@ -555,6 +556,10 @@ int Pipeline::front_stage(dyn_batch* b) {
     P_TRY(b, b->h_gref.ensure(2 * n * 4));
     P_TRY(b, hipMemcpyAsync(b->h_gref.p, b->d_gref.p, 2 * n * 4, hipMemcpyDeviceToHost, a->s_out));
   }
+  if (n && b->gr_ready) {  // rounds | converged | code of a ticket under the guide rescue
+    P_TRY(b, b->h_resc.ensure(2 * n * 4 + n));
+    P_TRY(b, hipMemcpyAsync(b->h_resc.p, b->d_resc.p, 2 * n * 4 + n, hipMemcpyDeviceToHost, a->s_out));
+  }
   if (b->job == DynJob::AlignFull && b->capacity) {
     P_TRY(b, b->h_rows.ensure(b->capacity * sizeof(SegRow)));
     P_TRY(b, hipMemcpyAsync(b->h_rows.p, b->d_rows.p, b->capacity * sizeof(SegRow), hipMemcpyDeviceToHost, a->s_out));
@@ -761,6 +766,16 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
     return DYN_ERR_INVALID_ARGUMENT;
   }
   *ticket = nullptr;
+  // the guide rescue (dyn_aligner_set_guide_rescue) concerns align tickets with probabilities; it pairs with none of the switches
+  // that re-align or read the lattice (refused before anything is started: the same text with and without a device)
+  const uint32_t gr_hw = (job == DynJob::AlignFull && !a->ntk) ? a->rescue_hw : 0u;
+  if (gr_hw) {
+    if (const char* other = guide_rescue_conflict(a)) {
+      std::lock_guard<std::mutex> elk(a->err_mu);
+      a->last_error = std::string("dyn_batch_align_async: dyn_aligner_set_guide_rescue is on, which does not combine with ") + other;
+      return DYN_ERR_INVALID_ARGUMENT;
+    }
+  }
   {
     std::lock_guard<std::mutex> lk(a->mu);
     int rc = need_device(a);
@@ -797,6 +812,9 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
   attach_cache(b);
   b->n = n_reads;
   b->async = true;
+  b->gr_hw = gr_hw;
+  b->gr_margin = a->rescue_margin;
+  b->gr_rounds = gr_hw ? a->rescue_rounds : 1u;
   b->ag_want = ag_hw;
   b->ag_rounds = ag_hw ? a->auto_guide_rounds : 1u;
   b->job = job;

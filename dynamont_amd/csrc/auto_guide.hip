@@ -120,8 +120,10 @@ __global__ __launch_bounds__(THREADS) void k_auto_guide(const AutoGuideArgs a) {
     if (threadIdx.x == 0) s_ctl[0] = (int)atomicAdd(a.head, 1u);
     __syncthreads();
     const int k = s_ctl[0];
-    if (k >= a.n_reads) break;
-    const ReadDesc rd = a.descs[k];
+    // the guide rescue (launch_rescue_select) hands over the list of the reads to guide and its length on the device
+    const bool listed = a.active != nullptr;
+    if (k >= (listed ? (int)*a.n_active : a.n_reads)) break;
+    const ReadDesc rd = a.descs[listed ? a.active[k] : (uint32_t)k];
     auto_guide_read<THREADS, CPT>(rd, a, s_rows, stride, s_pv, s_pn);
   }
 }
@@ -157,7 +159,7 @@ int auto_guide_groups_per_cu(int bw) {
 
 hipError_t launch_auto_guide(const AutoGuideArgs& a, int n_groups, hipStream_t s) {
   if (a.n_reads <= 0 || n_groups <= 0) return hipSuccess;
-  if (a.bw < 1 || a.bw > WIDE_MAX_HALF_BAND || !a.guide || !a.head) return hipErrorInvalidValue;
+  if (a.bw < 1 || a.bw > WIDE_MAX_HALF_BAND || !a.guide || !a.head || (a.active && !a.n_active)) return hipErrorInvalidValue;
   if (const hipError_t e = hipMemsetAsync(a.head, 0, 4, s)) return e;
   const size_t lds = lds_bytes(a.bw);
   const Shape& sh = shape_of(a.bw);

@@ -107,6 +107,10 @@ struct AutoGuideArgs {
   int32_t* guide;         // [samples of the batch]: T - 1 entries per read at ReadDesc::sig_off
   uint32_t* head;         // queue head (cleared by launch_auto_guide)
   double m1, e2;
+  // the guide rescue (dyn_aligner_set_guide_rescue): the reads to guide are descs[active[0 .. *n_active)], list and length written
+  // on the device by launch_rescue_select. Null: every descriptor
+  const uint32_t* active = nullptr;
+  const uint32_t* n_active = nullptr;
 };
 
 // the most workgroups per compute unit worth launching at this half width

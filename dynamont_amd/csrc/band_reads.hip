@@ -392,7 +392,8 @@ __device__ void band_read(const ReadDesc& rd, const BandArgs& a, double* __restr
 // alignment is counted; a failed read is finished; the called path g'[s] = pathn[s + 1] (0 before the first border) is compared
 // with the guide; equal everywhere: converged; otherwise, unless this was alignment refine_rounds, g' becomes the guide and the
 // read is aligned again in the same arena. Only then does the workgroup take the next read: a launch lasts as long as its
-// reads' alignments, not as refine_rounds times its longest read. BandArgs::active is not looked at.
+// reads' alignments, not as refine_rounds times its longest read. With BandArgs::active the launch takes the listed descriptors
+// only (the guide rescue); a self-guided ticket passes none.
 template <class Window, int THREADS, int CPT, bool CALC, bool TRAIN, bool BORDER, bool REFINE = false>
 __global__ __launch_bounds__(THREADS) void k_band_reads(const BandArgs a) {
   extern __shared__ __attribute__((aligned(16))) char g_lds[];
@@ -408,8 +409,9 @@ __global__ __launch_bounds__(THREADS) void k_band_reads(const BandArgs a) {
     if (threadIdx.x == 0) s_ctl[0] = (int)atomicAdd(a.head, 1u);
     __syncthreads();
     const int k = s_ctl[0];
-    // a refinement round (launch_guide_refine) hands over the list of the reads still to align and its length on the device
-    const bool listed = !REFINE && a.active;
+    // a refinement round (launch_guide_refine) or the guide rescue (launch_rescue_select) hands over the list of the reads to
+    // align and its length on the device; an empty list ends the workgroup at this first queue read
+    const bool listed = a.active != nullptr;
     if (k >= (listed ? (int)*a.n_active : a.n_reads)) break;
     const ReadDesc rd = a.descs[listed ? a.active[k] : (uint32_t)k];
     const size_t cells = (size_t)rd.T * (size_t)(2 * Window(rd, a).bw + 3);

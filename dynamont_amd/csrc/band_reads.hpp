@@ -39,8 +39,9 @@ struct BandArgs {
   const uint64_t* exp_tab; // dynmath::strict_exp_table on the device
   double m1, e2;
   int z_fail_status;
-  // a refinement round (dyn_batch_set_guide_refine): the reads to align are descs[active[0 .. *n_active)], list and length
-  // written on the device by launch_guide_refine. Null: every descriptor
+  // a refinement round (dyn_batch_set_guide_refine) or the guide rescue (dyn_aligner_set_guide_rescue): the reads to align are
+  // descs[active[0 .. *n_active)], list and length written on the device by launch_guide_refine / launch_rescue_select.
+  // Null: every descriptor
   const uint32_t* active;
   const uint32_t* n_active;
   int border_window = 0;   // as QueueArgs: W, and the two columns of dyn_aligner_set_border_confidence (diagonal, job 1 only)
@@ -48,8 +49,8 @@ struct BandArgs {
   double* border_window_p = nullptr;
   // per-read refinement INSIDE the launch (guided, job 1, no border window): the workgroup that holds a read aligns it up to
   // refine_rounds times, each time inside the path the alignment before called, by the rules of launch_guide_refine
-  // (guided_band_kernels.hpp) -- the round scheme's results bit for bit in one launch. 0 or 1: no refinement. active / n_active
-  // are not used by such a launch
+  // (guided_band_kernels.hpp) -- the round scheme's results bit for bit in one launch. 0 or 1: no refinement. Such a launch
+  // honours active / n_active like any other (the guide rescue's list; a self-guided ticket passes none)
   int refine_rounds = 0;
   uint32_t* rounds = nullptr;     // [reads of the batch] alignments run, written for every read of the launch (cleared by the caller)
   uint32_t* converged = nullptr;  // [reads of the batch] set to 1 where the called path reproduces the guide (cleared by the caller)

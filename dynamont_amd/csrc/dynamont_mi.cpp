@@ -60,9 +60,10 @@ void attach_cache(dyn_batch* b) {
   dyneng::BufCache* c = &b->a->cache;
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_arena, &b->d_guide, &b->d_gref})
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
+                    &b->d_resc_st, &b->d_resc_pp, &b->d_resc_pathn, &b->d_resc_segrow})
     d->cache = c;
-  for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref}) h->cache = c;
+  for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref, &b->h_resc}) h->cache = c;
 }
 
 int need_device(dyn_aligner* a) {
@@ -589,6 +590,28 @@ int dyn_aligner_set_auto_guide(dyn_aligner* a, uint32_t half_width, uint32_t max
   return DYN_OK;
 }
 
+int dyn_aligner_set_guide_rescue(dyn_aligner* a, int min_margin, uint32_t half_width, uint32_t max_rounds) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  auto fail = [&](const std::string& msg) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = "dyn_aligner_set_guide_rescue: " + msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  };
+  if (half_width == 0) {  // off (the other two are not looked at)
+    a->rescue_hw = 0;
+    return DYN_OK;
+  }
+  if (a->ntk) return fail("modes ntk / resquiggle have no align(calc_probabilities = 1) job to rescue");
+  if (half_width > (uint32_t)dynk::WIDE_MAX_HALF_BAND)
+    return fail("half_width " + std::to_string(half_width) + " is outside [1, " + std::to_string(dynk::WIDE_MAX_HALF_BAND) + "]");
+  if (min_margin < 0) return fail("min_margin " + std::to_string(min_margin) + " is negative");
+  if (max_rounds < 1 || max_rounds > 64) return fail("max_rounds " + std::to_string(max_rounds) + " is outside [1, 64]");
+  a->rescue_margin = (uint32_t)min_margin;
+  a->rescue_rounds = max_rounds;
+  a->rescue_hw = half_width;
+  return DYN_OK;
+}
+
 int dyn_aligner_set_band_margin(dyn_aligner* a, int on) {
   if (!a) return DYN_ERR_INVALID_ARGUMENT;
   if (a->ntk) {
@@ -933,9 +956,10 @@ void dyn_batch_destroy(dyn_batch* b) {
   }
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl, &b->d_arena, &b->d_guide, &b->d_gref})
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
+                    &b->d_resc_st, &b->d_resc_pp, &b->d_resc_pathn, &b->d_resc_segrow})
     d->release();
-  for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref}) h->release();
+  for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref, &b->h_resc}) h->release();
   for (hipEvent_t e : b->events) (void)hipEventDestroy(e);
   for (hipEvent_t e : {b->ev_in, b->ev_done, b->ev_out})
     if (e) (void)hipEventDestroy(e);
@@ -1148,10 +1172,26 @@ int run_job_sync(dyn_batch* b, DynJob job, bool guided_train = false) {
                     (a->rescale_iters > 0 ? "dyn_aligner_set_rescale(a, iters > 0)" : "dyn_aligner_set_border_confidence(a, window > 0)");
     return DYN_ERR_INVALID_ARGUMENT;
   }
+  // the guide rescue (dyn_aligner_set_guide_rescue) concerns align jobs with probabilities; the Z-only and the train job ignore it
+  const uint32_t gr_hw = (job == DynJob::AlignFull && !a->ntk) ? a->rescue_hw : 0u;
+  if (gr_hw) {
+    if (const char* other = guide_rescue_conflict(a)) {
+      a->last_error = std::string("dyn_batch_align: dyn_aligner_set_guide_rescue is on, which does not combine with ") + other;
+      return DYN_ERR_INVALID_ARGUMENT;
+    }
+    if (b->guided) {
+      a->last_error = "dyn_batch_align: dyn_aligner_set_guide_rescue is on and the batch carries a guide (dyn_batch_set_guide / "
+                      "dyn_batch_auto_guide); a guided batch is not rescued";
+      return DYN_ERR_INVALID_ARGUMENT;
+    }
+  }
   {
     std::lock_guard<std::mutex> lk(a->mu);
     int rc = need_device(a);
     if (rc != DYN_OK) return rc;
+    b->gr_hw = gr_hw;
+    b->gr_margin = a->rescue_margin;
+    b->gr_rounds = gr_hw ? a->rescue_rounds : 1u;
     b->ev_want = a->event_stats;
     b->rs_want = a->rescale_iters;
     b->ks_want = a->kmer_summary;
@@ -1313,6 +1353,33 @@ int dyn_batch_fetch_guide_rounds(dyn_batch* b, uint32_t* rounds, uint32_t* conve
     rounds[i] = (b->reads[i].status == DYN_READ_OK && st[i].status != DYN_READ_TOO_LARGE) ? 1u : 0u;
     converged[i] = 0u;
   }
+  return DYN_OK;
+}
+
+int dyn_batch_fetch_rescue(dyn_batch* b, uint8_t* code, uint32_t* rounds, uint32_t* converged, uint64_t n) {
+  if (!b || !code || !rounds || !converged) return DYN_ERR_INVALID_ARGUMENT;
+  dyn_aligner* a = b->a;
+  auto fail = [&](const std::string& msg) {
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = "dyn_batch_fetch_rescue: " + msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  };
+  if (!b->aligned || !b->last_calc || !b->gr_ready)
+    return fail("the batch was not aligned with calc_probabilities = 1 under dyn_aligner_set_guide_rescue");
+  if (n < b->n) return fail("n is smaller than the batch's read count");
+  if (int rc = need_device(a)) return rc;
+  if (!b->n) return DYN_OK;
+  if (b->async) {  // a ticket: the three came home with its state
+    const char* h = b->h_resc.as<char>();
+    std::memcpy(rounds, h, b->n * 4);
+    std::memcpy(converged, h + b->n * 4, b->n * 4);
+    std::memcpy(code, h + 2 * b->n * 4, b->n);
+    return DYN_OK;
+  }
+  const char* d = b->d_resc.as<char>();
+  HIP_TRY(a, copy_out(a, rounds, d, b->n * 4));
+  HIP_TRY(a, copy_out(a, converged, d + b->n * 4, b->n * 4));
+  HIP_TRY(a, copy_out(a, code, d + 2 * b->n * 4, b->n));
   return DYN_OK;
 }
 

@@ -158,6 +158,9 @@ struct dyn_aligner {
   bool band_margin = false;   // dyn_aligner_set_band_margin: read by every batch / ticket at its submission
   // dyn_aligner_set_auto_guide (half width, 0 = off; alignments per read): read by every align(calc = 1) TICKET at its submission
   uint32_t auto_guide_hw = 0, auto_guide_rounds = 8;
+  // dyn_aligner_set_guide_rescue (minimum margin; half width, 0 = off; alignments per rescued read): read by every
+  // align(calc = 1) batch / ticket at its submission
+  uint32_t rescue_margin = 0, rescue_hw = 0, rescue_rounds = 8;
   // queue head + lattice arenas of the self-guided tickets (band_reads.hip): grow-only, the handle's, shared by every such ticket
   // in stream order (launch.cpp, enqueue_job) and released with the handle
   dyneng::DevBuf band_arena;
@@ -303,6 +306,15 @@ struct dyn_batch {
   dyneng::PinnedBuf h_gdescs;   // the guide pre-pass's descriptor table (enqueue_job fills h_descs while that copy may be pending)
   dyneng::PinnedBuf h_gref;     // a ticket's rounds | converged, copied out with its state
   uint64_t arena_bytes = 0;     // what the last job asked of d_arena beyond the queue head: every workgroup's lattice arena
+  // the guide rescue (dyn_aligner_set_guide_rescue, guide_rescue_kernels.hpp): the handle's switch when this batch / ticket was
+  // submitted (gr_hw 0: off). Such a job is a classic launch -- a ticket is never merged, never published into a resident session
+  uint32_t gr_margin = 0, gr_hw = 0, gr_rounds = 1;
+  // uint32 [n] rounds | [n] converged | uint8 [n] code (padded to 256 B) | uint32 [64] list length | [n] list | [3 n] margins
+  // (when the batch did not ask for them itself)
+  dyneng::DevBuf d_resc;
+  dyneng::DevBuf d_resc_st, d_resc_pp, d_resc_pathn, d_resc_segrow;  // the rescue alignment's own state / path rows / segment rows
+  dyneng::PinnedBuf h_resc;     // a ticket's rounds | converged | code, copied out with its state
+  bool gr_ready = false;        // the last job ran under the switch: d_resc holds rounds / converged / code
   bool host_only = false;       // created on a handle without a device: the read table alone (validation, no job)
   dyneng::SessionGeom sess_geom;  // session_plan's decision for this ticket (ok = false: none taken)
   bool has_raw = false;

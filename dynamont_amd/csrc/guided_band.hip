@@ -10,9 +10,11 @@ constexpr uint32_t GBM_NONE = 0xffffffffu;  // DYN_BAND_MARGIN_NONE
 
 // ---- guided band margins: one thread per path row ----
 // grid ceil((read_hi - read_lo) / 256)
-__global__ __launch_bounds__(256) void k_bmargin_guided_init(BandMargin bm) {
+// only: a per-read code (the guide rescue's); the reads whose code is 1 alone are initialised and computed. Null: every read
+__global__ __launch_bounds__(256) void k_bmargin_guided_init(BandMargin bm, const uint8_t* __restrict__ only) {
   const uint64_t i = (uint64_t)bm.read_lo + (uint64_t)blockIdx.x * 256u + threadIdx.x;
   if (i >= bm.read_hi) return;
+  if (only && only[i] != 1) return;
   bm.low[i] = GBM_NONE;
   bm.high[i] = GBM_NONE;
   bm.edge_rows[i] = 0u;
@@ -21,10 +23,12 @@ __global__ __launch_bounds__(256) void k_bmargin_guided_init(BandMargin bm) {
 // grid (n_reads, ceil(max_T / 256)): thread j of block (r, c) owns lattice row c * 256 + j of read descs[r]
 __global__ __launch_bounds__(256) void k_bmargin_guided(const ReadDesc* __restrict__ descs, const ReadState* __restrict__ st,
                                                         const uint32_t* __restrict__ pathn_all, const uint32_t* __restrict__ segrow_all,
-                                                        const int32_t* __restrict__ guide, int bw, BandMargin bm) {
+                                                        const int32_t* __restrict__ guide, int bw, BandMargin bm,
+                                                        const uint8_t* __restrict__ only) {
   const ReadDesc rd = descs[blockIdx.x];
   const int T = (int)rd.T, N = (int)rd.N;
   if ((int)(blockIdx.y * 256u) >= T || N < 2) return;
+  if (only && only[rd.read] != 1) return;
   if (rd.read < bm.read_lo || rd.read >= bm.read_hi || st[rd.read].status != 0) return;
   const int t = (int)(blockIdx.y * 256u + threadIdx.x);
   uint32_t low = GBM_NONE, high = GBM_NONE, edge = 0u;
@@ -55,12 +59,12 @@ __global__ __launch_bounds__(256) void k_bmargin_guided(const ReadDesc* __restri
 }
 
 void launch_guided_band_margin(const ReadDesc* descs, int n_reads, uint32_t max_T, const ReadState* st, const TraceBuffers& tb,
-                               const int32_t* guide, int bw, const BandMargin& bm, hipStream_t s) {
+                               const int32_t* guide, int bw, const BandMargin& bm, hipStream_t s, const uint8_t* only) {
   if (!bm.low || bm.read_lo >= bm.read_hi) return;
-  hipLaunchKernelGGL(k_bmargin_guided_init, dim3((bm.read_hi - bm.read_lo + 255u) / 256u), dim3(256), 0, s, bm);
+  hipLaunchKernelGGL(k_bmargin_guided_init, dim3((bm.read_hi - bm.read_lo + 255u) / 256u), dim3(256), 0, s, bm, only);
   if (n_reads <= 0 || max_T < 2) return;
   hipLaunchKernelGGL(k_bmargin_guided, dim3((unsigned)n_reads, (max_T + 255u) / 256u), dim3(256), 0, s, descs, st, tb.pathn,
-                     tb.segrow, guide, bw, bm);
+                     tb.segrow, guide, bw, bm, only);
 }
 
 // ---- guide refinement (dyn_batch_set_guide_refine): the called path becomes the next guide ----

@@ -27,7 +27,9 @@ hipError_t launch_guide_refine(const GuideRefine& r, hipStream_t s);
 
 // band margins of a guided batch: INTEGRATION.md section 3's definition with mid(t) -> centre(t), bw -> half width, over the
 // path rows [segrow[0], T). rows_total: the batch's path rows (sum of T over descs).
+// only: a per-read code, [reads of the batch] (the guide rescue's, guide_rescue_kernels.hpp): the margins of the reads whose code
+// is 1 are taken against the guide's window, every other read's entries are left as they are. Null: every read of bm's range.
 void launch_guided_band_margin(const ReadDesc* descs, int n_reads, uint32_t max_T, const ReadState* st, const TraceBuffers& tb,
-                               const int32_t* guide, int bw, const BandMargin& bm, hipStream_t s);
+                               const int32_t* guide, int bw, const BandMargin& bm, hipStream_t s, const uint8_t* only = nullptr);
 
 }  // namespace dynk

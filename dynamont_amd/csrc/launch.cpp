@@ -6,6 +6,8 @@
 #include "band_reads.hpp"
 #include "dp_math_strict.hpp"
 #include "guided_band_kernels.hpp"
+#include "auto_guide_kernels.hpp"
+#include "guide_rescue_kernels.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -233,6 +235,10 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   const int band_job = job == DynJob::Train ? 2 : calc ? 1 : 0;  // launch_band_reads' job
   const uint32_t refine_rounds = (b->guided && calc) ? b->guide_refine : 1;  // dyn_batch_set_guide_refine
   b->gref_ready = false;
+  // the guide rescue (dyn_aligner_set_guide_rescue): sampled per job by the caller; it concerns the unguided align job with
+  // probabilities alone (the callers refuse the combinations with rescale / border confidence / a guide)
+  const bool rescue = calc && b->gr_hw > 0 && !b->guided && !a->ntk && b->rs_want == 0 && b->bc_want == 0;
+  b->gr_ready = false;
 
   // mode "resquiggle"/"ntk": what the reference's NTKAligner does in this snapshot, as observed with the compiled
   // reference (tests/golden/g11_ntk_messages.json): validateInput / sequenceToKmers errors first, then EVERY read fails
@@ -526,6 +532,29 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   HIP_TRY(a, b->d_descs.ensure(std::max<size_t>(sizeof(ReadDesc), n_all * sizeof(ReadDesc))));
   if (n_all)
     HIP_TRY(a, hipMemcpyAsync(b->d_descs.p, descs, n_all * sizeof(ReadDesc), hipMemcpyHostToDevice, a->stream));
+  // ---- the guide rescue: what its stage needs is sized HERE, before anyone knows which reads will be flagged ----
+  // One lattice arena per workgroup of the refining launch, sized for T_fit: the longest ok read for which at least one arena fits
+  // what the page pool (allocated above) has left, within the handle's budget. A flagged read above T_fit gets code 2 on the
+  // device. A ticket's arenas are the handle's, handed from ticket to ticket in stream order (as a self-guided ticket's are, and
+  // for its reason); a synchronous batch's are the batch's own, shared with its wide reads' launch, which has ended by then.
+  dyneng::DevBuf& resc_arena_buf = b->async ? a->band_arena : b->d_arena;
+  uint64_t resc_arena = 0, resc_want = 0;
+  uint32_t resc_T_fit = 0;
+  int resc_groups = 0;
+  if (rescue && n_all) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
+    uint64_t room = (uint64_t)((double)(free_b + resc_arena_buf.bytes + parked_bytes(a->device)) * 0.8);
+    if (a->mem_budget && room > a->mem_budget) room = a->mem_budget;
+    for (size_t k = 0; k < n_all; ++k)
+      if (descs[k].T > resc_T_fit && dynk::band_arena_bytes(descs[k].T, b->gr_hw, 1) <= room) resc_T_fit = descs[k].T;
+    if (resc_T_fit) {
+      resc_arena = dynk::band_arena_bytes(resc_T_fit, b->gr_hw, 1);
+      resc_groups = (int)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)n_all, (uint64_t)a->n_cus * (uint64_t)dynk::band_groups_per_cu(true, (int)b->gr_hw, 1),
+                                                                    room / resc_arena}));
+      resc_want = 256 + (uint64_t)resc_groups * resc_arena;
+    }
+  }
   // per-read rescaling (dyn_aligner_set_rescale): align(calc = 1) runs 1 + iters passes of everything below, in stream order
   const int iters = calc ? b->rs_want : 0;
   const int n_pass = 1 + iters;
@@ -617,14 +646,15 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       // a queue of its own behind the read queue on the compute stream (its results feed the same per-segment kernels / the
       // same host finalisation)
       if (pass == 0) {
-        const uint64_t want = 256 + (uint64_t)wide_groups * wide_arena;
+        // (a synchronous batch under the guide rescue: the rescue stage below works in the same buffer, which must not grow again)
+        const uint64_t want = std::max<uint64_t>(256 + (uint64_t)wide_groups * wide_arena, &arena_buf == &resc_arena_buf ? resc_want : 0);
         size_t free_b = 0, total_b = 0;
         HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
         if (want > arena_buf.bytes && want > (uint64_t)((double)free_b * 0.95)) free_parked(a->device);  // (counted as room above)
         // (growing the handle's arenas releases the old ones, which the ticket before this one may still be working in)
         if (want > arena_buf.bytes && &arena_buf == &a->band_arena) HIP_TRY(a, hipStreamSynchronize(a->stream));
         HIP_TRY(a, arena_buf.ensure(want));
-        b->arena_bytes = want - 256;
+        b->arena_bytes = (uint64_t)wide_groups * wide_arena;
       }
       dynk::BandArgs ba{};
       ba.descs = q.descs + n_ok;
@@ -702,6 +732,118 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       dynk::launch_rescale_pass(q.descs, (int)n_all, max_T, q.st, q.tb, b->d_sig0.as<double>(), b->d_sig.as<double>(), q.par, rs_y, rs, a->stream);
   }
   const int nr_all = (int)n_all;
+  if (int rc = band_margin_prepare(b, calc != 0)) return rc;
+  // ---- the guide rescue stage: behind the read queue and the diagonal banded-lattice launch, in front of the riders ----
+  // (guide_rescue_kernels.hpp lists the launches). The host waits for none of them: a ticket's front thread enqueues the lot.
+  if (rescue) {
+    const uint64_t nb = b->n;
+    const uint64_t off_code = 2 * nb * 4, off_len = (off_code + nb + 255) / 256 * 256, off_list = off_len + 256;
+    const uint64_t off_bm = off_list + (uint64_t)n_all * 4;
+    HIP_TRY(a, b->d_resc.ensure(std::max<uint64_t>(512, off_bm + (b->bm_ready ? 0 : 3 * nb * 4))));
+    HIP_TRY(a, hipMemsetAsync(b->d_resc.p, 0, off_list, a->stream));  // rounds, converged, code, list length
+    char* rb = b->d_resc.as<char>();
+    uint32_t* g_rounds = reinterpret_cast<uint32_t*>(rb);
+    uint32_t* g_conv = g_rounds + nb;
+    uint8_t* g_code = reinterpret_cast<uint8_t*>(rb + off_code);
+    uint32_t* g_len = reinterpret_cast<uint32_t*>(rb + off_len);
+    uint32_t* g_list = reinterpret_cast<uint32_t*>(rb + off_list);
+    // the diagonal margins of every read, whether or not the job reports margins: into the job's own arrays when it does
+    uint32_t* marg = b->bm_ready ? b->d_bm.as<uint32_t>() : reinterpret_cast<uint32_t*>(rb + off_bm);
+    const dynk::BandMargin dm{marg, marg + nb, marg + 2 * nb, 0u, (uint32_t)nb};
+    dynk::launch_band_margin(q.descs, nr_all, max_N, q.st, q.tb, dm, a->stream);
+    dynk::RescueSelect sel{};
+    sel.descs = q.descs;
+    sel.n_reads = nr_all;
+    sel.st = q.st;
+    sel.low = dm.low;
+    sel.high = dm.high;
+    sel.min_margin = b->gr_margin;
+    sel.max_T = resc_T_fit;
+    sel.code = g_code;
+    sel.list = g_list;
+    sel.n_list = g_len;
+    HIP_TRY(a, dynk::launch_rescue_select(sel, a->stream));
+    if (resc_T_fit && nr_all) {
+      // the guide (zero-filled, one int32 per sample of the batch) and the pre-pass's queue head behind it
+      const uint64_t total = b->reads[b->n - 1].sig_off + b->reads[b->n - 1].S;
+      const uint64_t head_off = (total * 4 + 255) / 256 * 256;
+      HIP_TRY(a, b->d_guide.ensure(head_off + 256));
+      if (total) HIP_TRY(a, hipMemsetAsync(b->d_guide.p, 0, total * 4, a->stream));
+      dynk::AutoGuideArgs ag{};
+      ag.descs = q.descs;
+      ag.n_reads = nr_all;
+      ag.bw = (int)b->gr_hw;
+      ag.sig = q.sig;
+      ag.par = q.par;
+      ag.guide = b->d_guide.as<int32_t>();
+      ag.head = reinterpret_cast<uint32_t*>(b->d_guide.as<char>() + head_off);
+      ag.m1 = m.log_m1;
+      ag.e2 = m.log_e2;
+      ag.active = g_list;
+      ag.n_active = g_len;
+      const int ag_groups = (int)std::min<uint64_t>(n_all, (uint64_t)a->n_cus * (uint64_t)dynk::auto_guide_groups_per_cu((int)b->gr_hw));
+      HIP_TRY(a, dynk::launch_auto_guide(ag, ag_groups, a->stream));
+      // the rescue alignment writes a state, path rows and segment rows of its OWN (the read's offsets, other buffers): the
+      // plain answer stays whole until launch_rescue_merge has seen how the rescue ended
+      HIP_TRY(a, b->d_resc_st.ensure(std::max<uint64_t>(sizeof(ReadState), nb * sizeof(ReadState))));
+      HIP_TRY(a, b->d_resc_pp.ensure(std::max<uint64_t>(8, rows_total * 8)));
+      HIP_TRY(a, b->d_resc_pathn.ensure(std::max<uint64_t>(4, rows_total * 4)));
+      HIP_TRY(a, b->d_resc_segrow.ensure(std::max<uint64_t>(4, b->capacity * 4)));
+      {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
+        if (resc_want > resc_arena_buf.bytes && resc_want > (uint64_t)((double)free_b * 0.95)) free_parked(a->device);  // (counted as room above)
+        // (growing the handle's arenas releases the old ones, which the ticket before this one may still be working in)
+        if (resc_want > resc_arena_buf.bytes && &resc_arena_buf == &a->band_arena) HIP_TRY(a, hipStreamSynchronize(a->stream));
+        HIP_TRY(a, resc_arena_buf.ensure(resc_want));
+        b->arena_bytes = std::max<uint64_t>(b->arena_bytes, resc_want - 256);
+      }
+      dynk::BandArgs ra{};
+      ra.descs = q.descs;
+      ra.n_reads = nr_all;
+      ra.bw = (int)b->gr_hw;
+      ra.sig = q.sig;
+      ra.par = q.par;
+      ra.guide = b->d_guide.as<int32_t>();
+      ra.st = b->d_resc_st.as<ReadState>();
+      ra.tb = dynk::TraceBuffers{b->d_resc_pp.as<double>(), b->d_resc_pathn.as<uint32_t>(), b->d_resc_segrow.as<uint32_t>(), nullptr, nullptr};
+      ra.head = resc_arena_buf.as<uint32_t>();
+      ra.arena = resc_arena_buf.as<char>() + 256;
+      ra.arena_bytes = resc_arena;
+      ra.exp_tab = reinterpret_cast<const uint64_t*>(a->d_sptab.as<dynmath::SoftplusNode>() + dynmath::SP_NODES + dynmath::EXP128_NODES);
+      ra.m1 = m.log_m1;
+      ra.e2 = m.log_e2;
+      ra.z_fail_status = z_fail;
+      ra.active = g_list;
+      ra.n_active = g_len;
+      ra.refine_rounds = (int)b->gr_rounds;
+      ra.rounds = g_rounds;
+      ra.converged = g_conv;
+      HIP_TRY(a, dynk::launch_band_reads(1, ra, resc_groups, a->stream));
+      dynk::RescueMerge mg{};
+      mg.descs = q.descs;
+      mg.n_reads = nr_all;
+      mg.list = g_list;
+      mg.n_list = g_len;
+      mg.st_in = ra.st;
+      mg.pp_in = ra.tb.pp;
+      mg.pathn_in = ra.tb.pathn;
+      mg.segrow_in = ra.tb.segrow;
+      mg.st = q.st;
+      mg.pp = q.tb.pp;
+      mg.pathn = q.tb.pathn;
+      mg.segrow = q.tb.segrow;
+      mg.code = g_code;
+      mg.rounds = g_rounds;
+      mg.converged = g_conv;
+      mg.single = b->gr_rounds <= 1 ? 1 : 0;
+      HIP_TRY(a, dynk::launch_rescue_merge(mg, a->stream));
+      // a rescued read reports its margins against the window it was aligned in, every other read against the diagonal (above)
+      if (b->bm_ready)
+        dynk::launch_guided_band_margin(q.descs, nr_all, b->max_T, q.st, q.tb, b->d_guide.as<int32_t>(), (int)b->gr_hw, dm, a->stream, g_code);
+    }
+    b->gr_ready = true;
+  }
   dynk::EventCols evc{};
   b->ev_ready = false;
   if (calc && b->ev_want) {
@@ -722,7 +864,6 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     scc = dynk::ScoreCols{q.sig, e, e + b->capacity, e + 2 * b->capacity, e + 3 * b->capacity, b->sc_want};
     b->sc_ready = true;
   }
-  if (int rc = band_margin_prepare(b, calc != 0)) return rc;
   if (calc) {
     // the per-k-mer summary (once per job, after the last pass: the signal of a rescaling job is its last pass's)
     const std::vector<dynk::KmerSummary> ks = kmer_summary_args(b);
@@ -730,9 +871,10 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     const std::vector<dynk::BandMargin> bm = band_margin_args(b);
     // (a guided batch's margins are taken against its own window: k_bmargin_guided below, not the diagonal's staircase kernel)
     dynk::launch_segments(q.descs, nr_all, rows_total, max_N, q.st, q.tb, b->d_rows.as<SegRow>(), m.k, a->stream, evc,
-                          ks.empty() ? dynk::KmerSummary{} : ks[0], scc, (bm.empty() || b->guided) ? dynk::BandMargin{} : bm[0]);
+                          ks.empty() ? dynk::KmerSummary{} : ks[0], scc, (bm.empty() || b->guided || rescue) ? dynk::BandMargin{} : bm[0]);
     for (size_t k = 1; k < ks.size(); ++k) dynk::launch_kmer_summary(q.descs, nr_all, max_N, q.st, q.tb, ks[k], a->stream);
-    for (size_t k = b->guided ? 0 : 1; k < bm.size(); ++k) {
+    // (under the guide rescue the margins were taken above, in front of the selection: such a job is never a merged launch)
+    for (size_t k = b->guided ? 0 : 1; k < bm.size() && !rescue; ++k) {
       if (b->guided) dynk::launch_guided_band_margin(q.descs, nr_all, b->max_T, q.st, q.tb, b->d_guide.as<int32_t>(), (int)b->guide_hw, bm[k], a->stream);
       else dynk::launch_band_margin(q.descs, nr_all, max_N, q.st, q.tb, bm[k], a->stream);
     }

@@ -183,7 +183,9 @@ bool session_candidate(const dyn_batch* b) {
   // every pass. Publishing such a ticket into the session once per pass is a follow-up.
   // A self-guided ticket (dyn_aligner_set_auto_guide) takes the banded-lattice kernel, as a ticket that holds a wide read does:
   // a launch of its own, for which an open session is quiesced.
-  return a->sess_enabled.load() && !a->host_only && !a->ntk && b->async && b->job == DynJob::AlignFull && b->rs_want == 0 && b->bc_want == 0 && b->ag_want == 0 &&
+  // A ticket under the guide rescue (dyn_aligner_set_guide_rescue) is a classic launch too -- an INTERIM: its
+  // rescue stage is a guided kernel, and a guided kernel beside resident waves is what did not make progress before.
+  return a->sess_enabled.load() && !a->host_only && !a->ntk && b->async && b->job == DynJob::AlignFull && b->rs_want == 0 && b->bc_want == 0 && b->ag_want == 0 && b->gr_hw == 0 &&
          (a->sess_open_hint.load() || b->n >= SESSION_MIN_READS);
 }
 

@@ -126,7 +126,15 @@ def parse(argv=None) -> Namespace:
                         "the sequence alone (no move table needed); not together with --rescale-iters or --border-confidence "
                         "(0: off)")
     p.add_argument("--guide-rounds", type=int, default=8, metavar="R",
-                   help="with --guide-auto: alignments per read at the most while its guide is refined (1 .. 64)")
+                   help="with --guide-auto / --guide-rescue: alignments per read at the most while its guide is refined (1 .. 64)")
+    p.add_argument("--guide-rescue", type=int, default=0, metavar="HW",
+                   help="align every read as usual, then align again -- inside a window of HW lattice columns on either side of a "
+                        "guide made on the GPU, as --guide-auto does -- only the reads whose band margin is below "
+                        "--guide-rescue-margin: the cost of the plain run plus the flagged reads. A read the plain alignment "
+                        "failed is not rescued. Not together with --guide-auto, --rescale-iters or --border-confidence (0: off)")
+    p.add_argument("--guide-rescue-margin", type=int, default=1, metavar="M",
+                   help="with --guide-rescue: a read is flagged when the smaller of its two band margins (--band-report) is "
+                        "below M (default 1: the path touched a real edge of the band)")
     p.add_argument("--parallel-zstd-frames", action="store_true",
                    help="write the CSV as consecutive independent zstd frames (readers must read across frames: "
                         "python-zstandard's defaults stop after the first). Default: one frame, like the reference, "
@@ -136,6 +144,9 @@ def parse(argv=None) -> Namespace:
         p.error("--guide-auto and --rescale-iters are mutually exclusive")
     if args.guide_auto and args.border_confidence:
         p.error("--guide-auto and --border-confidence are mutually exclusive")
+    for other, name in ((args.guide_auto, "--guide-auto"), (args.rescale_iters, "--rescale-iters"), (args.border_confidence, "--border-confidence")):
+        if args.guide_rescue and other:
+            p.error("--guide-rescue and %s are mutually exclusive" % name)
     return args
 
 
@@ -368,12 +379,14 @@ def prepare_job(job, is_rna: bool):
 BAND_REPORT_HEADER = b"readid\tT\tN\tband\tband_margin_low\tband_margin_high\tband_edge_rows\n"
 
 
-def band_report_lines(readids, T, N, band: int, low, high, edge_rows) -> list:
-    """--band-report: one line (no newline) per read; an empty field for DYN_BAND_MARGIN_NONE"""
+def band_report_lines(readids, T, N, band, low, high, edge_rows) -> list:
+    """--band-report: one line (no newline) per read; an empty field for DYN_BAND_MARGIN_NONE. ``band``: one width for every
+    read, or one per read (--guide-rescue: a rescued read's margins are those against its guided window)"""
     none = 0xFFFFFFFF
     field = lambda v: "" if int(v) == none else str(int(v))  # noqa: E731
-    return [f"{rid}\t{int(t)}\t{int(n)}\t{int(band)}\t{field(lo)}\t{field(hi)}\t{int(e)}"
-            for rid, t, n, lo, hi, e in zip(readids, T, N, low, high, edge_rows)]
+    bands = [int(band)] * len(readids) if np.ndim(band) == 0 else band
+    return [f"{rid}\t{int(t)}\t{int(n)}\t{int(b)}\t{field(lo)}\t{field(hi)}\t{int(e)}"
+            for rid, t, n, b, lo, hi, e in zip(readids, T, N, bands, low, high, edge_rows)]
 
 
 def band_report_bytes(lines) -> bytes:
@@ -381,9 +394,27 @@ def band_report_bytes(lines) -> bytes:
     return BAND_REPORT_HEADER + "".join(ln + "\n" for ln in sorted(lines)).encode()
 
 
-def _report_band(aligner) -> int:
-    """the ``band`` column of --band-report: under --guide-auto the margins are those against the guided window, 2 * HW wide"""
+def _report_band(aligner, rescue=None):
+    """the ``band`` column of --band-report: under --guide-auto the margins are those against the guided window, 2 * HW wide;
+    under --guide-rescue (``rescue``: the ticket's per-read codes) those of the rescued reads are, the others' the band's"""
+    if rescue is not None and aligner._guide_rescue[1]:
+        return np.where(np.asarray(rescue) == 1, 2 * aligner._guide_rescue[1], aligner.band)
     return 2 * aligner._auto_guide[0] if aligner._auto_guide[0] else aligner.band
+
+
+def _rescue_codes(t):
+    """--guide-rescue: the per-read codes of a COMPLETED ticket (None for a ticket submitted without the switch)"""
+    if not getattr(t, "_rescued", False):
+        return None
+    t.result._fetch_rescue(t._L, t._h, t._al, True)
+    return t.result.rescue
+
+
+def _rescue_counts(t, codes) -> tuple:
+    """--guide-rescue: (flagged, rescued, rescued without converging, left for want of memory, left because the rescue failed)"""
+    codes = np.asarray(codes)
+    open_ = (codes == 1) & (np.asarray(t.result.guide_converged) == 0)
+    return int((codes != 0).sum()), int((codes == 1).sum()), int(open_.sum()), int((codes == 2).sum()), int((codes == 3).sum())
 
 
 def _guide_counts(t) -> tuple:
@@ -394,7 +425,7 @@ def _guide_counts(t) -> tuple:
     return int(ok.sum()), int((ok & (converged == 0)).sum())
 
 
-def _ticket_band_lines(aligner, t, readids, lengths, seq_off) -> list:
+def _ticket_band_lines(aligner, t, readids, lengths, seq_off, rescue=None) -> list:
     """the report lines of a COMPLETED align ticket submitted with the band-margin switch on"""
     from dynamont_amd import _native as N
     n = len(readids)
@@ -403,7 +434,7 @@ def _ticket_band_lines(aligner, t, readids, lengths, seq_off) -> list:
                                            edge.ctypes.data_as(N.c_u32_p), n))
     bases = np.diff(np.asarray(seq_off, dtype=np.int64))
     cols = np.maximum(bases - aligner.kmer_size + 1, 0) + 1
-    return band_report_lines(readids, np.asarray(lengths, dtype=np.int64) + 1, cols, _report_band(aligner), low, high, edge)
+    return band_report_lines(readids, np.asarray(lengths, dtype=np.int64) + 1, cols, _report_band(aligner, rescue), low, high, edge)
 
 
 def _stored_bases(p) -> int:
@@ -488,6 +519,7 @@ class _Pipeline:
         self.free = []            # result objects of completed batches, refilled instead of reallocated
         self.band_lines = []      # --band-report: the lines of the tickets completed so far
         self.guide_counts = [0, 0]  # --guide-auto: reads aligned inside their own guide, reads whose guide did not converge
+        self.rescue_counts = [0, 0, 0, 0, 0]  # --guide-rescue: _rescue_counts, summed over the tickets
         self.error = None
         self.rounds_done = queue_mod.Queue()
         self.consumer = threading.Thread(target=self._drain, daemon=True)
@@ -539,10 +571,14 @@ class _Pipeline:
         if self.aligner._auto_guide[0]:
             for k, v in enumerate(_guide_counts(t)):
                 self.guide_counts[k] += v
+        codes = _rescue_codes(t)
+        if codes is not None:
+            for k, v in enumerate(_rescue_counts(t, codes)):
+                self.rescue_counts[k] += v
         if self.aligner._band_margin:
             self.band_lines += band_report_lines([p[2][6] for p in g], [len(p[0]) + 1 for p in g],
                                                  np.maximum(np.diff(np.asarray(seq_off, dtype=np.int64)) - self.aligner.kmer_size + 1, 0) + 1,
-                                                 _report_band(self.aligner), res.band_margin_low, res.band_margin_high, res.band_edge_rows)
+                                                 _report_band(self.aligner, codes), res.band_margin_low, res.band_margin_high, res.band_edge_rows)
         starts = [p[2][3] for p in g]
         buf, begin, end = format_csv(self.aligner, res, None, [p[2][6] for p in g], [p[2][7] for p in g], starts,
                                      [len(p[0]) + st for p, st in zip(g, starts)], threads=self.threads, compact=True,
@@ -616,6 +652,7 @@ class _NativePipeline:
         self.band_meta = {}   # --band-report: batch number -> (readids, signal lengths, sequence offsets)
         self.band_lines = []  # ... and the lines of the tickets the sink has consumed
         self.guide_counts = [0, 0]  # --guide-auto: reads aligned inside their own guide, reads whose guide did not converge
+        self.rescue_counts = [0, 0, 0, 0, 0]  # --guide-rescue: _rescue_counts, summed over the tickets
 
     def put(self, line: str) -> None:
         """an error line from the producer (reads that failed before the aligner, segment.py:178-187)"""
@@ -643,9 +680,13 @@ class _NativePipeline:
         if self.aligner._auto_guide[0]:
             for j, v in enumerate(_guide_counts(t)):
                 self.guide_counts[j] += v
+        codes = _rescue_codes(t)
+        if codes is not None:
+            for j, v in enumerate(_rescue_counts(t, codes)):
+                self.rescue_counts[j] += v
         meta = self.band_meta.pop(k, None)
         if meta is not None:
-            self.band_lines += _ticket_band_lines(self.aligner, t, *meta)
+            self.band_lines += _ticket_band_lines(self.aligner, t, *meta, rescue=codes)
 
     def submit(self, pending, end_of_round: bool = False) -> None:
         C, N = self.C, self.N
@@ -819,14 +860,19 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             host_preprocess: bool = False, depth: int = 12, strict_ties: str = "ties", host_threads: int = 0,
             zstd_level: int = 3, event_stats: bool = False, rescale_iters: int = 0, kmer_summary: str = "",
             segment_scores: int = 0, border_confidence: int = 0, band_report: str = "", band: int = 400,
-            guide_auto: int = 0, guide_rounds: int = 8) -> None:
+            guide_auto: int = 0, guide_rounds: int = 8, guide_rescue: int = 0, guide_rescue_margin: int = 1) -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
     that gather at the end is the only exchange). ``guide_auto`` > 0: every batch is aligned inside guides the library
-    makes itself at that half width, refined up to ``guide_rounds`` alignments per read (``Aligner.set_auto_guide``)."""
+    makes itself at that half width, refined up to ``guide_rounds`` alignments per read (``Aligner.set_auto_guide``).
+    ``guide_rescue`` > 0: every batch is aligned as usual and only the reads whose band margin is below ``guide_rescue_margin``
+    are aligned again inside such a guide (``Aligner.set_guide_rescue``)."""
     if guide_auto < 0 or (guide_auto and (rescale_iters or border_confidence)):
         raise ValueError("--guide-auto must be >= 0 and is not combined with --rescale-iters or --border-confidence")
+    if guide_rescue < 0 or guide_rescue_margin < 0 or (guide_rescue and (guide_auto or rescale_iters or border_confidence)):
+        raise ValueError("--guide-rescue and --guide-rescue-margin must be >= 0; --guide-rescue is not combined with --guide-auto, "
+                         "--rescale-iters or --border-confidence")
     from dynamont_amd import parallel
     comm, local_rank = parallel.init_from_env()
     rank, world = (comm.rank, comm.world) if comm else (0, 1)
@@ -903,11 +949,15 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             f.write(band_report_bytes(lines))
         print(f"band report written: {band_report}", file=sys.stderr, flush=True)
 
-    def guide_summary(counts):
-        # --guide-auto: this process's reads (every rank reports its own)
+    def guide_summary(counts, rescue=(0, 0, 0, 0, 0)):
+        # --guide-auto / --guide-rescue: this process's reads (every rank reports its own)
         if guide_auto:
             print(f"Reads aligned inside their own guide: {counts[0]}; of those, reads whose guide did not converge within "
                   f"{guide_rounds} alignments: {counts[1] if guide_rounds != 1 else 0}", file=sys.stderr, flush=True)
+        if guide_rescue:
+            print(f"Reads flagged by their band margin (below {guide_rescue_margin}): {rescue[0]}; rescued inside their own guide: "
+                  f"{rescue[1]}, of those not converged within {guide_rounds} alignments: {rescue[2] if guide_rounds != 1 else 0}; "
+                  f"left as aligned for want of memory: {rescue[3]}, because the rescue failed: {rescue[4]}", file=sys.stderr, flush=True)
 
     # A failing rank ends the whole job (parallel.abort): a barrier in a `finally` would leave the other ranks in
     # their next collective until the process-group timeout.
@@ -934,6 +984,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                 aligner.set_band_margin(True)
             if guide_auto:
                 aligner.set_auto_guide(guide_auto, guide_rounds)
+            if guide_rescue:
+                aligner.set_guide_rescue(guide_rescue_margin, guide_rescue, guide_rounds)
             if native:
                 import os
                 import tempfile
@@ -992,7 +1044,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                         pipe.submit(pending)
                 _stamp("every batch submitted")
                 pipe.close()
-                guide_summary(pipe.guide_counts)
+                guide_summary(pipe.guide_counts, pipe.rescue_counts)
                 band_lines, pipe = pipe.band_lines, None
                 _stamp("pipeline closed: output complete")
                 if comm is not None:
@@ -1040,7 +1092,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                     ship()
                     break
             pipe.close()
-            guide_summary(pipe.guide_counts)
+            guide_summary(pipe.guide_counts, pipe.rescue_counts)
             band_lines, pipe = pipe.band_lines, None
             write_summary(aligner)
             write_band_report(band_lines)
@@ -1087,7 +1139,8 @@ def main(argv=None) -> None:
             zstd_level=args.zstd_level, event_stats=args.event_stats, rescale_iters=args.rescale_iters,
             kmer_summary=args.kmer_summary, segment_scores=args.segment_scores,
             border_confidence=args.border_confidence, band_report=args.band_report, band=args.band,
-            guide_auto=args.guide_auto, guide_rounds=args.guide_rounds)
+            guide_auto=args.guide_auto, guide_rounds=args.guide_rounds, guide_rescue=args.guide_rescue,
+            guide_rescue_margin=args.guide_rescue_margin)
     _stamp("segment() returned (aligner closed)")
     if argv is None and not int(__import__("os").environ.get("WORLD_SIZE", "1") or 1) > 1:
         # Invoked as the command (console script / python -m), single process, everything written and closed: leave without

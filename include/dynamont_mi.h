@@ -792,6 +792,34 @@ int dyn_batch_fetch_guide_rounds(dyn_batch* b, uint32_t* rounds, uint32_t* conve
  * together with dyn_aligner_set_rescale(iters > 0) or dyn_aligner_set_border_confidence(window > 0) is refused at submission
  * (DYN_ERR_INVALID_ARGUMENT + message), as dyn_batch_align refuses the pairing on a guided batch. */
 int dyn_aligner_set_auto_guide(dyn_aligner* a, uint32_t half_width, uint32_t max_rounds);
+/* (added within ABI 10) The guide rescue: self-guide only the reads whose band margin flags them. While half_width > 0, every
+ * dyn_batch_align(b, 1) of a synchronous, unguided batch and every align ticket with calc_probabilities = 1 (the switch is read
+ * when the job is started / the ticket is submitted)
+ *   1. aligns every read exactly as without the switch (read queue, diagonal banded-lattice kernel);
+ *   2. takes every read's band margins against the diagonal band, whether or not dyn_aligner_set_band_margin is on;
+ *   3. flags a read when its status is ok, N >= 2 and min(margin_low, margin_high) < min_margin, a margin of
+ *      DYN_BAND_MARGIN_NONE counting as +infinity;
+ *   4. aligns the flagged reads again as a self-guided ticket aligns them (the pre-pass at half_width, then up to max_rounds
+ *      alignments refined by the workgroup that holds the read): status, Z, rows, probabilities, rounds and converged of a
+ *      rescued read are what dyn_batch_auto_guide(half_width) + dyn_batch_set_guide_refine(max_rounds) give for it;
+ *   5. runs everything behind the traceback (segment rows, event stats, segment scores, k-mer summary) once, over all reads.
+ * All of it happens on the device, in stream order, without a host round trip. Per read a code (dyn_batch_fetch_rescue):
+ *   0 not flagged (a read the plain alignment failed included: such a read is NOT rescued), 1 rescued, 2 flagged but its
+ *   lattice arena does not fit the memory the job may use (dyn_aligner_set_mem_budget), 3 flagged but the rescue alignment ended
+ *   with a failure status; 2 and 3 keep the plain answer bit for bit.
+ * With dyn_aligner_set_band_margin a code-1 read reports its margins against its guided window (as a guided batch does), every
+ * other read against the diagonal. Z-only jobs, train jobs and dyn_multi_* ignore the switch. A ticket under the switch is a
+ * launch of its own: not merged, not published into the resident read queue (an open session is closed and waited for first).
+ * half_width 0 (the default): off. Otherwise half_width in [1, 2046], min_margin >= 0 (0 flags nothing) and max_rounds in
+ * [1, 64], else DYN_ERR_INVALID_ARGUMENT + message. Refused with a message naming both when the job is started / the ticket is
+ * submitted: together with dyn_aligner_set_rescale(iters > 0), dyn_aligner_set_border_confidence(window > 0) or
+ * dyn_aligner_set_auto_guide(half_width > 0); on a batch that carries a guide (dyn_batch_set_guide / dyn_batch_auto_guide). */
+int dyn_aligner_set_guide_rescue(dyn_aligner* a, int min_margin, uint32_t half_width, uint32_t max_rounds);
+/* (added within ABI 10) Per read of a batch / a waited ticket whose last dyn_batch_align(b, 1) ran under
+ * dyn_aligner_set_guide_rescue: code[i] as above; rounds[i] = the alignments the rescue ran for a code-1 read, converged[i] = 1
+ * where its last called path reproduced its guide; both 0 for every other read. n >= the batch's read count.
+ * DYN_ERR_INVALID_ARGUMENT + message for a batch that was not aligned under the switch. */
+int dyn_batch_fetch_rescue(dyn_batch* b, uint8_t* code, uint32_t* rounds, uint32_t* converged, uint64_t n);
 /* (added within ABI 10) Device bytes the batch's last job allocated for per-workgroup lattice arenas: workgroups x the largest
  * read's lattice, for the guided kernel (dyn_batch_set_guide) or the generic wide-band kernel (one kernel: band_reads.hip); 25 B per band slot
  * for align with probabilities, 16 B for dyn_batch_train / dyn_batch_train_guided; 0 for a batch whose reads all took the paged

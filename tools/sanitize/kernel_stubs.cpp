@@ -7,6 +7,7 @@
 #include "../../dynamont_amd/csrc/band_reads.hpp"
 #include "../../dynamont_amd/csrc/guided_band_kernels.hpp"
 #include "../../dynamont_amd/csrc/auto_guide_kernels.hpp"
+#include "../../dynamont_amd/csrc/guide_rescue_kernels.hpp"
 
 namespace dynk {
 
@@ -53,11 +54,13 @@ uint64_t band_arena_bytes(uint64_t T, uint64_t bw, int job) { return job == 0 ? 
 int band_groups_per_cu(bool, int, int) { return 1; }
 hipError_t launch_band_reads(int, const BandArgs&, int, hipStream_t) { no_device("launch_band_reads"); }
 void launch_guided_band_margin(const ReadDesc*, int, uint32_t, const ReadState*, const TraceBuffers&, const int32_t*, int, const BandMargin&,
-                               hipStream_t) {
+                               hipStream_t, const uint8_t*) {
   no_device("launch_guided_band_margin");
 }
 hipError_t launch_guide_refine(const GuideRefine&, hipStream_t) { no_device("launch_guide_refine"); }
 int auto_guide_groups_per_cu(int) { return 1; }
 hipError_t launch_auto_guide(const AutoGuideArgs&, int, hipStream_t) { no_device("launch_auto_guide"); }
+hipError_t launch_rescue_select(const RescueSelect&, hipStream_t) { no_device("launch_rescue_select"); }
+hipError_t launch_rescue_merge(const RescueMerge&, hipStream_t) { no_device("launch_rescue_merge"); }
 
 }  // namespace dynk
