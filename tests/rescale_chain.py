@@ -113,3 +113,21 @@ DISTORTIONS = [(1.2, 0.3), (0.9, -0.2)]   # (B, A): the aligner sees B x + A
 RECOVERY_ITERS = 3
 RECOVERY_PARAM_TOL = 0.05                  # |B_K - B| and |A_K - A|, every read
 RECOVERY_AGREEMENT = 0.90                  # mean border agreement with the undistorted read: >= at K = 3, < at K = 0
+
+
+# ---- one pass of the device kernels on one read (tests/test_gpu_rescale_kernels.py) ----
+def rescale_pass(x, x0, sp, m, state, failed=False):
+    """What k_rescale_fit and k_rescale_apply leave of one read. x: the signal the pass aligned, x0: the preprocessed signal,
+    sp: the first sample of every row, m: the rows' model means, state: (A, B, applied, frozen, fitted) on entry.
+    Returns (state', y, x'): y is None where the kernel returns before the row means (a failed or frozen read, fewer than
+    MIN_ROWS rows), x' is x itself (the same object) unless the fit was applied."""
+    A, B, applied, frozen, _ = state
+    if failed or frozen or len(m) < MIN_ROWS:
+        return (A, B, applied, 1, 0), None, x
+    y = segment_means(x[int(sp[0]):], np.asarray(sp, dtype=np.int64) - int(sp[0]))
+    a, b, ok = fit(m, y)
+    if not ok:
+        return (A, B, applied, 1, 0), y, x
+    A = np.float64(A) + np.float64(B) * a
+    B = np.float64(B) * b
+    return (A, B, applied + 1, 0, 1), y, (np.asarray(x0, dtype=np.float64) - A) / B

@@ -334,3 +334,98 @@ def build_batch(seg_by="read"):
         reads.append(dict(segments=[fill(3)], status=0, desc=True))
         b = Batch(reads, order + [len(reads) - 1], cases, seg_by)
     return b
+
+
+# ---- more reads than one launch of the per-read kernels takes ------------------------------------------------------------
+SLICE = 65535            # segment_kernels.hpp, MAX_GRID_Y: k_median_long and k_final put the read in gridDim.y
+TAIL = 6                 # descriptors 65 535 .. 65 540: the second launch of both
+
+
+def build_sliced_batch():
+    """65 541 reads of T = 3 .. 6 and N = 2 .. 3, built without a loop over the reads; one read of the first slice and one of
+    the last six descriptors have a third segment, 300 and 301 rows long (k_median_long has work in both launches). The
+    fields sm_run reads, as Batch has them (seg_off by read index), and the per-segment arrays reference_sliced() needs."""
+    rng = np.random.default_rng(4711)
+    n = SLICE + TAIL
+    rows = rng.integers(2, 6, n)                               # T - 1
+    two = rng.random(n) < 0.6
+    cut = 1 + (rng.random(n) * (rows - 1)).astype(np.int64)    # 1 .. rows - 1
+    lens3 = np.zeros((n, 3), dtype=np.int64)
+    lens3[:, 0] = np.where(two, cut, rows)
+    lens3[:, 1] = np.where(two, rows - cut, 0)
+    tail = np.sort(rng.choice(np.arange(1000, n - 1000), TAIL, replace=False))   # read indices from the middle of the input
+    long_reads = np.array([777, tail[2]])
+    lens3[long_reads] = [[3, 4, 300], [2, 301, 5]]
+    status = np.zeros(n, dtype=np.int32)
+    status[rng.choice(np.setdiff1d(np.arange(n), np.concatenate([tail, long_reads])), 300, replace=False)] = FAILED
+    rest = np.setdiff1d(np.arange(n), tail)
+    proc = np.concatenate([rest[rng.permutation(len(rest))], tail])
+    b = Batch.__new__(Batch)
+    nseg = (lens3 > 0).sum(axis=1)
+    rows = lens3.sum(axis=1)
+    T = rows + 1
+    b.status = status
+    b.read = proc.astype(np.uint32)
+    b.T, b.N = T[proc].astype(np.uint32), (nseg[proc] + 1).astype(np.uint32)
+    b.path_off = (np.cumsum(T[proc]) - T[proc]).astype(np.uint64)
+    b.rows_total = int(T.sum())
+    b.read_seg_off = (np.cumsum(nseg) - nseg).astype(np.uint64)
+    b.seg_off = b.read_seg_off[proc]
+    b.n_seg = int(nseg.sum())
+    path_of_read = np.zeros(n, dtype=np.int64)
+    path_of_read[proc] = b.path_off.astype(np.int64)
+    # per segment, in input order
+    seg_len = lens3[lens3 > 0]
+    seg_read = np.repeat(np.arange(n), nseg)
+    seg_j = np.arange(b.n_seg) - b.read_seg_off.astype(np.int64)[seg_read]
+    rows_before = np.cumsum(rows) - rows
+    seg_first = np.cumsum(seg_len) - seg_len                   # among the rows of all reads (row 0 of a read not counted)
+    seg_start = seg_first - rows_before[seg_read] + 1          # its first row inside the read
+    b.segrow = seg_start.astype(np.uint32)
+    # per row
+    total = int(seg_len.sum())
+    row_seg = np.repeat(np.arange(b.n_seg), seg_len)
+    row_t = np.arange(total) - rows_before[seg_read[row_seg]] + 1
+    at = path_of_read[seg_read[row_seg]] + row_t
+    vals = 1.0 - rng.random(total)
+    b.pp = np.full(b.rows_total, np.nan)
+    b.pp[at] = vals
+    b.pathn = np.zeros(b.rows_total, dtype=np.uint32)
+    b.pathn[at] = (seg_j[row_seg] + 1).astype(np.uint32) | np.where(row_t == seg_start[row_seg], np.uint32(0x80000000), np.uint32(0))
+    b.sliced = dict(seg_len=seg_len, seg_read=seg_read, seg_j=seg_j, seg_first=seg_first, seg_start=seg_start, vals=vals, tail=tail,
+                    long_reads=long_reads)
+    for a in (b.pp, b.pathn, b.segrow, b.path_off, b.seg_off, b.T, b.N, b.read, b.status):
+        a.setflags(write=False)
+    return b
+
+
+def reference_sliced(b, skip_descs=()):
+    """Batch.reference() for build_sliced_batch(): the segments of up to five rows by one sort of a padded matrix, the longer
+    ones by order_stats(). skip_descs: descriptors whose reads no per-read kernel was handed (their rows keep the poison)."""
+    s = b.sliced
+    L, first, vals = s["seg_len"], s["seg_first"], s["vals"]
+    n = b.n_seg + GUARD
+    hi, lo, prob = from_bits(np.full(n, POISON_U64)), from_bits(np.full(n, POISON_U64)), from_bits(np.full(n, POISON_U64))
+    sig, seq = np.full(n, POISON_U32), np.full(n, POISON_U32)
+    ok = b.status[s["seg_read"]] == 0
+    ok[np.isin(s["seg_read"], b.read[np.asarray(skip_descs, dtype=np.int64)])] = False
+    small = np.flatnonzero(ok & (L <= 5))
+    m = np.full((len(small), 5), np.inf)
+    for c in range(5):
+        has = L[small] > c
+        m[has, c] = vals[first[small[has]] + c]
+    m.sort(axis=1)
+    k = np.arange(len(small))
+    mid = L[small] // 2
+    even = L[small] % 2 == 0
+    hi[small] = m[k, mid]
+    lo[small[even]] = m[k[even], mid[even] - 1]
+    prob[small] = np.where(even, (m[k, np.maximum(mid - 1, 0)] + m[k, mid]) / 2.0, m[k, mid])
+    for i in np.flatnonzero(ok & (L > 5)):
+        h, l, p = order_stats(vals[first[i]:first[i] + L[i]])
+        hi[i], prob[i] = h, p
+        lo[i] = l if l is not None else (h if L[i] > MEDIAN_SHORT_MAX else from_bits(np.array([POISON_U64]))[0])
+    at = np.flatnonzero(ok)
+    sig[at] = (s["seg_start"][at] - 1).astype(np.uint32)
+    seq[at] = (s["seg_j"][at] + KMER_SIZE // 2).astype(np.uint32)
+    return dict(med_hi=hi, med_lo=lo, probability=prob, signal_pos=sig, sequence_pos=seq)

@@ -150,6 +150,109 @@ def build_batch():
     return b
 
 
+# ---- more reads than one launch of k_score_window takes ----------------------------------------------------------------------
+SLICE = 65535            # segment_score_kernels.hpp, SC_MAX_GRID_Y
+TAIL = 6                 # descriptors 65 535 .. 65 540: the second launch
+SLICED_WINDOWS = (8, 64)
+
+
+def build_sliced_batch():
+    """65 541 reads, built without a loop over the reads: T = 3 .. 6 and N = 2 .. 3, but for nine reads of three rows of
+    11 .. 30 samples (finite values in all three columns) -- three in the first slice, and descriptors 65 535 .. 65 540. The
+    fields ss_run reads, as build_batch() lays them out, and b.sliced for reference_sliced()."""
+    rng = np.random.default_rng(4712)
+    n = SLICE + TAIL
+    S = rng.integers(2, 6, n)
+    two = rng.random(n) < 0.6
+    cut = 1 + (rng.random(n) * (S - 1)).astype(np.int64)       # 1 .. S - 1: the first sample of row 1
+    lens3 = np.zeros((n, 3), dtype=np.int64)
+    lens3[:, 0] = np.where(two, cut, S)
+    lens3[:, 1] = np.where(two, S - cut, 0)
+    tail = np.sort(rng.choice(np.arange(1000, n - 1000), TAIL, replace=False))
+    long_reads = np.concatenate([[5, 30000, n - 7], tail])
+    lens3[long_reads] = rng.integers(11, 31, (len(long_reads), 3))
+    S = lens3.sum(axis=1)
+    nseg = (lens3 > 0).sum(axis=1)
+    status = np.zeros(n, dtype=np.int32)
+    status[rng.choice(np.setdiff1d(np.arange(n), long_reads), 300, replace=False)] = 3
+    rest = np.setdiff1d(np.arange(n), tail)
+    order = np.concatenate([rest[rng.permutation(len(rest))], tail])
+    b = Batch()
+    sig_off, seg_off = np.cumsum(S) - S, np.cumsum(nseg) - nseg
+    b.sig = np.ascontiguousarray(rng.choice(np.array([-1.25, -0.5, 0.0, 0.75, 2.0]), int(S.sum())) + 0.01 * rng.standard_normal(int(S.sum())))
+    seg_len = lens3[lens3 > 0]
+    seg_read = np.repeat(np.arange(n), nseg)
+    sp = (np.cumsum(seg_len) - seg_len) - sig_off[seg_read]   # the first sample of every row inside its read
+    b.segrow = (sp + 1).astype(np.uint32)
+    b.status = status
+    b.read = order.astype(np.uint32)
+    b.T, b.N = (S[order] + 1).astype(np.uint32), (nseg[order] + 1).astype(np.uint32)
+    b.sig_off, b.seg_off = sig_off[order].astype(np.uint64), seg_off[order].astype(np.uint64)
+    b.path_off = (np.cumsum(S[order] + 1) - (S[order] + 1)).astype(np.uint64)
+    b.rows_total = int((S + 1).sum())
+    b.n_seg = int(nseg.sum())
+    b.read_sig_off, b.read_seg_off = sig_off, seg_off
+    path_of_read = np.zeros(n, dtype=np.int64)
+    path_of_read[order] = b.path_off.astype(np.int64)
+    smp_seg = np.repeat(np.arange(b.n_seg), seg_len)          # per sample: its row, its read, its place in the read
+    smp_read = seg_read[smp_seg]
+    smp_t = np.arange(len(b.sig)) - sig_off[smp_read]
+    col = (smp_seg - seg_off[smp_read] + 1).astype(np.uint32) | np.where(smp_t == sp[smp_seg], np.uint32(0x80000000), np.uint32(0))
+    b.pathn = np.zeros(b.rows_total, dtype=np.uint32)
+    b.pathn[path_of_read[smp_read] + 1 + smp_t] = col
+    b.sliced = dict(S=S, nseg=nseg, cut=lens3[:, 0], tail=tail, long_reads=long_reads)
+    return b
+
+
+def _med_padded(m, L):
+    """med() of every row of m, whose first L[i] entries count"""
+    m = np.where(np.arange(m.shape[1])[None, :] < L[:, None], m, np.inf)
+    m = np.sort(m, axis=1)
+    k = np.arange(len(L))
+    return np.where(L % 2 == 1, m[k, L // 2], (m[k, np.maximum(L // 2 - 1, 0)] + m[k, L // 2]) / np.float64(2.0))
+
+
+def _mad_padded(m, L):
+    return _med_padded(np.abs(m - _med_padded(m, L)[:, None]), L)
+
+
+def reference_sliced(b, W, skip_descs=()):
+    """reference() for build_sliced_batch() and a window of 5 samples or more: a read of at most five samples has NaN in
+    row 0 and no homogeneity, and the windows of row 1 are cut by the read's ends: A = x[:p], B = x[p:] -- every such read at
+    once; the nine longer reads by scores(). skip_descs: descriptors k_score_window was not handed (median_delta and
+    mad_delta of their rows keep the zeros; homogeneity comes from the kernels that take the whole batch)."""
+    assert W >= 5
+    s = b.sliced
+    n = len(s["S"])
+    out = np.zeros((3, b.n_seg))
+    windowed = np.ones(n, dtype=bool)
+    windowed[b.read[np.asarray(skip_descs, dtype=np.int64)]] = False
+    small = (b.status == 0) & (s["S"] <= 5)
+    row0 = b.read_seg_off[small]
+    out[2, row0] = np.nan
+    out[:2, b.read_seg_off[small & windowed]] = np.nan
+    two = np.flatnonzero(small & (s["nseg"] == 2))
+    out[2, b.read_seg_off[two] + 1] = np.nan
+    two = two[windowed[two]]
+    x = np.full((len(two), 5), np.inf)
+    for c in range(5):
+        has = s["S"][two] > c
+        x[has, c] = b.sig[b.read_sig_off[two[has]] + c]
+    p, S = s["cut"][two], s["S"][two]
+    k = np.arange(len(two))[:, None]
+    right = x[k, np.minimum(p[:, None] + np.arange(4)[None, :], 4)]           # x[p:], shifted to the front
+    out[0, b.read_seg_off[two] + 1] = np.abs(_med_padded(right, S - p) - _med_padded(x[:, :4], p))
+    out[1, b.read_seg_off[two] + 1] = np.abs(_mad_padded(right, S - p) - _mad_padded(x[:, :4], p))
+    for i in s["long_reads"]:
+        a, m = int(b.read_seg_off[i]), int(s["nseg"][i])
+        x_i = b.sig[int(b.read_sig_off[i]):int(b.read_sig_off[i]) + int(s["S"][i])]
+        sc = scores(x_i, b.segrow[a:a + m].astype(np.int64) - 1, W)
+        out[2, a:a + m] = sc[2]
+        if windowed[i]:
+            out[:2, a:a + m] = sc[:2]
+    return out
+
+
 def reference(b, W, wrong=None):
     """the three columns [n_seg] of the batch: rows of failed reads are 0"""
     out = np.zeros((3, b.n_seg))

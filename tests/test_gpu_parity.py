@@ -644,6 +644,8 @@ def test_train_batch_against_oracle_and_pooled_stats(models, al9):
         rc = hip.hipMemcpy(ctypes.c_void_p(dev.ctypes.data), ctypes.c_void_p(ptr), ctypes.c_size_t(cnt * 8), 2)  # D2H
         assert rc == 0
     assert cnt == 3 * K and np.allclose(dev, pooled, rtol=1e-9, atol=1e-9)
+    # the documented contract (pool_stats.hip): bit for bit the sum dyn_batch_fetch_train formed on the host
+    assert np.array_equal(dev.view(np.uint64), res.pooled.view(np.uint64))
 
 
 def test_traceback_segments_spanning_many_64_row_blocks(models):

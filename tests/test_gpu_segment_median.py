@@ -219,7 +219,65 @@ def test_homopolymer_reads_expose_a_one_rank_error(models, oracle_built):
     assert kinds == {(True, 0), (True, 1), (False, 0), (False, 1)}   # both kernels, both parities
 
 
+@pytest.fixture(scope="module")
+def sliced():
+    return smc.build_sliced_batch()
+
+
+@pytest.fixture(scope="module")
+def sliced_want(sliced):
+    return smc.reference_sliced(sliced)
+
+
+def test_sliced_batch_and_its_reference(sliced, sliced_want):
+    """65 541 descriptors of T = 3 .. 6, N = 2 .. 3; the vectorised reference equals order_stats() segment by segment on a
+    sample; and a second launch of k_median_long / k_final that is handed the first descriptors again (descs in place of
+    descs + r0) shows: no row of descriptors 65 535 .. 65 540 is written, one of them holds a 301-row segment."""
+    b, s = sliced, sliced.sliced
+    n = len(b.read)
+    assert n == smc.SLICE + smc.TAIL and sorted(b.read.tolist()) == list(range(n))
+    bulk = np.ones(n, dtype=bool)
+    bulk[s["long_reads"]] = False
+    Tr, Nr = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    Tr[b.read], Nr[b.read] = b.T, b.N
+    assert set(Tr[bulk].tolist()) == {3, 4, 5, 6} and set(Nr[bulk].tolist()) == {2, 3}
+    assert np.array_equal(np.sort(b.read[smc.SLICE:]), s["tail"]) and (b.status[s["tail"]] == 0).all() and (b.status != 0).sum() == 300
+    long_segs = np.flatnonzero(s["seg_len"] > smc.MEDIAN_SHORT_MAX)
+    assert s["seg_len"][long_segs].tolist() == [300, 301]
+    assert s["seg_read"][long_segs[0]] in b.read[:smc.SLICE] and s["seg_read"][long_segs[1]] in b.read[smc.SLICE:]
+    rng = np.random.default_rng(3)
+    ok = np.flatnonzero(b.status[s["seg_read"]] == 0)
+    for i in np.concatenate([rng.choice(ok, 400, replace=False), long_segs]):
+        hi, lo, p = smc.order_stats(s["vals"][s["seg_first"][i]:s["seg_first"][i] + s["seg_len"][i]])
+        assert smc.bits(sliced_want["med_hi"][i:i + 1])[0] == smc.bits(np.array([hi]))[0]
+        assert smc.bits(sliced_want["probability"][i:i + 1])[0] == smc.bits(np.array([p]))[0]
+        if lo is not None:
+            assert smc.bits(sliced_want["med_lo"][i:i + 1])[0] == smc.bits(np.array([lo]))[0]
+        else:
+            assert sliced_want["med_lo"][i] == hi or smc.bits(sliced_want["med_lo"][i:i + 1])[0] == smc.POISON_U64
+    failed = np.flatnonzero(b.status[s["seg_read"]] != 0)
+    assert (sliced_want["signal_pos"][failed] == smc.POISON_U32).all() and (smc.bits(sliced_want["probability"])[failed] == smc.POISON_U64).all()
+    other = smc.reference_sliced(b, skip_descs=np.arange(smc.SLICE, n))
+    rows_of_tail = np.flatnonzero(np.isin(s["seg_read"], s["tail"]))
+    assert len(rows_of_tail) >= smc.TAIL + 3                                  # one segment at least per read, three in one
+    for name in ("signal_pos", "sequence_pos", "probability", "med_hi"):
+        assert (as_bits(other[name])[rows_of_tail] != as_bits(sliced_want[name])[rows_of_tail]).all(), name
+
+
 # ---- on the device -----------------------------------------------------------------------------------------------------------
+@gpu
+def test_more_reads_than_one_launch_slice(native_lib, harness_so, sliced, sliced_want):
+    """65 541 descriptors through launch_segment_medians: k_median_long and k_final run a second launch over descriptors
+    65 535 .. 65 540. Every output slot of the batch, bit for bit."""
+    other = smc.reference_sliced(sliced, skip_descs=np.arange(smc.SLICE, len(sliced.read)))   # a second launch handed descs, not descs + r0
+    assert all((as_bits(other[name]) != as_bits(sliced_want[name])).sum() >= smc.TAIL + 3 for name in ("signal_pos", "probability", "med_hi"))
+    lib = C.CDLL(harness_so)
+    lib.sm_run.restype = C.c_int
+    got = run_on_device(lib, sliced)
+    bad = mismatch(sliced, got, sliced_want, np.arange(sliced.n_seg + smc.GUARD))
+    assert bad is None, bad
+
+
 @gpu
 @pytest.mark.parametrize("position", smc.POSITIONS)
 @pytest.mark.parametrize("length", smc.LENGTHS)

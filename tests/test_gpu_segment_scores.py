@@ -77,6 +77,25 @@ def test_device_harness_every_bit(harness, batch, W):
         assert (g[:batch.n_seg][~ok_rows] == np.uint64(0xabababababababab)).all() and (g[batch.n_seg:] == np.uint64(0xabababababababab)).all()
 
 
+def test_more_reads_than_one_launch_slice(harness):
+    """65 541 descriptors: k_score_window runs a second launch over descriptors 65 535 .. 65 540, reads of three rows of 11 .. 30
+    samples. The whole batch bit for bit at W = 8 and W = 64 (k_score_window<8> and <64>); a second launch handed the first
+    descriptors again would leave zeros in median_delta and mad_delta of those reads (tests/test_segment_scores_host.py)."""
+    b = ssc.build_sliced_batch()
+    n = len(b.read)
+    assert n == ssc.SLICE + ssc.TAIL
+    for W in ssc.SLICED_WINDOWS:
+        want = ssc.bits(ssc.reference_sliced(b, W))
+        other = ssc.bits(ssc.reference_sliced(b, W, skip_descs=np.arange(ssc.SLICE, n)))
+        assert ((other[:2] != want[:2]).sum(axis=1) >= 3 * ssc.TAIL).all()
+        got = run_harness(harness, b, W)
+        for c in range(3):
+            g = ssc.bits(got[c])
+            bad = np.flatnonzero(g[:b.n_seg] != want[c])
+            assert bad.size == 0, (COLS[c], W, len(bad), bad[:5], got[c][bad[:5]], want[c][bad[:5]].view(np.float64))
+            assert not g[b.n_seg:].any()
+
+
 # ---- (b) whole reads -------------------------------------------------------------------------------------------------------------
 def check_scores(res, signals, W, n=None):
     """every ok read's three columns == the restatement over its own aligned signal and returned borders, bit for bit; rows of

@@ -130,6 +130,36 @@ def test_case_inputs_hold_what_the_issue_names(batch, right):
     assert np.array_equal(ssc.bits(r)[nan], np.full(int(nan.sum()), ssc.NAN_BITS))
 
 
+def test_sliced_batch_and_its_reference():
+    """The 65 541-descriptor batch of tests/test_gpu_segment_scores.py: its shape; its vectorised reference equals scores() read by
+    read on a sample; and a second launch of k_score_window that is handed the first descriptors again (descs in place of
+    descs + r0) shows in median_delta and mad_delta of every row of descriptors 65 535 .. 65 540."""
+    b = ssc.build_sliced_batch()
+    s = b.sliced
+    n = len(b.read)
+    assert n == ssc.SLICE + ssc.TAIL and sorted(b.read.tolist()) == list(range(n))
+    bulk = np.ones(n, dtype=bool)
+    bulk[s["long_reads"]] = False
+    assert set((s["S"][bulk] + 1).tolist()) == {3, 4, 5, 6} and set((s["nseg"][bulk] + 1).tolist()) == {2, 3}
+    assert np.array_equal(np.sort(b.read[ssc.SLICE:]), s["tail"]) and np.isin(s["long_reads"], b.read[:ssc.SLICE]).sum() == 3
+    assert (b.status[s["long_reads"]] == 0).all() and (b.status != 0).sum() == 300
+    rng = np.random.default_rng(9)
+    sample = np.concatenate([rng.choice(np.flatnonzero(bulk), 400, replace=False), s["long_reads"]])
+    tail_rows = np.concatenate([np.arange(int(b.read_seg_off[i]), int(b.read_seg_off[i]) + 3) for i in s["tail"]])
+    for W in ssc.SLICED_WINDOWS:
+        want = ssc.reference_sliced(b, W)
+        for i in sample:
+            a, m = int(b.read_seg_off[i]), int(s["nseg"][i])
+            x = b.sig[int(b.read_sig_off[i]):int(b.read_sig_off[i]) + int(s["S"][i])]
+            one = ssc.scores(x, b.segrow[a:a + m].astype(np.int64) - 1, W) if b.status[i] == 0 else np.zeros((3, m))
+            assert np.array_equal(ssc.bits(want[:, a:a + m]), ssc.bits(one)), (W, i)
+        assert np.isfinite(want[:2, tail_rows[1::3]]).all() and np.isfinite(want[2, tail_rows]).all()
+        other = ssc.reference_sliced(b, W, skip_descs=np.arange(ssc.SLICE, n))
+        assert (ssc.bits(other[:2, tail_rows]) != ssc.bits(want[:2, tail_rows])).all()
+        assert np.array_equal(ssc.bits(other[2]), ssc.bits(want[2]))               # homogeneity: no sliced launch
+    assert not np.array_equal(ssc.bits(ssc.reference_sliced(b, 8)), ssc.bits(ssc.reference_sliced(b, 64)))
+
+
 @pytest.mark.parametrize("pore", ["dna_r9", "rna004"])
 def test_random_read_seeds_meet_the_gpu_tests_condition(models, oracle_built, pore):
     """tests/test_gpu_segment_scores.py asserts that at least 25 % of the rows of its random reads have a finite homogeneity and
