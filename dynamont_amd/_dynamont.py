@@ -112,6 +112,9 @@ class AlignBatchResult:
         self.median_delta = self.mad_delta = self.homogeneity = None
         # per-border posterior confidence (Aligner.set_border_confidence): float64 [cap] like the segment columns, None when off
         self.border_probability = self.border_window_probability = None
+        # posterior path samples (Aligner.set_posterior_samples): sample_starts uint32 [K, cap] (sample k of output row s at
+        # [k, s]; DYN_SAMPLE_DEAD in every entry of a dead sample), sample_dead uint32 [n]; None when off
+        self.sample_starts = self.sample_dead = None
         # band-margin diagnostics (Aligner.set_band_margin): uint32 [n] each, None when off; band_used (uint32 [n]): the band
         # every read's rows come from, only with Aligner.set_band_retry
         self.band_margin_low = self.band_margin_high = self.band_edge_rows = None
@@ -145,6 +148,21 @@ class AlignBatchResult:
         out = N.DynBandMarginOut(_ptr(self.band_margin_low, N.c_u32_p), _ptr(self.band_margin_high, N.c_u32_p),
                                  _ptr(self.band_edge_rows, N.c_u32_p), self.n)
         rc = L.dyn_batch_fetch_band_margin(handle, C.byref(out))
+        if rc != N.DYN_OK:
+            _raise(rc, aligner.last_error())
+
+    def _fetch_samples(self, L, handle, aligner: "Aligner", count: int) -> None:
+        """dyn_batch_fetch_samples into ``sample_starts`` / ``sample_dead`` (``count`` = the K the job was submitted with), or
+        drop them."""
+        if not count:
+            self.sample_starts = self.sample_dead = None
+            return
+        if self.sample_starts is None or self.sample_starts.shape != (count, self.cap):
+            self.sample_starts = np.zeros((count, self.cap), dtype=np.uint32)
+        if self.sample_dead is None:
+            self.sample_dead = np.zeros(self.n, dtype=np.uint32)
+        sm = N.DynSampleOut(_ptr(self.sample_starts, N.c_u32_p), _ptr(self.sample_dead, N.c_u32_p), self.cap, self.n, count)
+        rc = L.dyn_batch_fetch_samples(handle, C.byref(sm))
         if rc != N.DYN_OK:
             _raise(rc, aligner.last_error())
 
@@ -232,6 +250,8 @@ class AlignBatchResult:
         if self.border_probability is not None:  # only when requested (Aligner.set_border_confidence)
             d["border_probability"] = self.border_probability[a:b].copy()
             d["border_window_probability"] = self.border_window_probability[a:b].copy()
+        if self.sample_starts is not None:  # only when requested (Aligner.set_posterior_samples): [K, n_segments]
+            d["sample_starts"] = self.sample_starts[:, a:b].copy()
         if self.rescale_shift is not None:  # only when requested (Aligner.set_rescale)
             d["rescale_shift"] = float(self.rescale_shift[i])
             d["rescale_scale"] = float(self.rescale_scale[i])
@@ -281,13 +301,18 @@ def format_csv(aligner: "Aligner", res: AlignBatchResult, sequences: Sequence[st
     if res.border_probability is not None:
         bd = C.byref(N.DynBorderOut(_ptr(res.border_probability, N.c_double_p),
                                     _ptr(res.border_window_probability, N.c_double_p), res.cap))
-    cap = int(L.dyn_format_csv_bound_borders(aligner._h, n, C.byref(res._c), ev, sc, bd, rid, sid))
+    # ... and the posterior samples (Aligner.set_posterior_samples): one more field after those
+    sm = None
+    if res.sample_starts is not None:
+        sm = C.byref(N.DynSampleOut(_ptr(res.sample_starts, N.c_u32_p), _ptr(res.sample_dead, N.c_u32_p), res.cap, res.n,
+                                    res.sample_starts.shape[0]))
+    cap = int(L.dyn_format_csv_bound_samples(aligner._h, n, C.byref(res._c), ev, sc, bd, sm, rid, sid))
     # one grow-only buffer per handle: first-touch page faults of a fresh 350 MB buffer cost ~100x
     # the formatting itself (15 ms per 1 024-read batch with warm pages)
     buf = getattr(aligner, "_csv_buf", None)
     if buf is None or buf.size < cap:
         buf = aligner._csv_buf = np.empty(max(cap, 1), dtype=np.uint8)
-    rc = L.dyn_format_csv_borders(aligner._h, n, C.byref(res._c), ev, sc, bd, seqs, _ptr(seq_off, N.c_u64_p), rid, sid,
+    rc = L.dyn_format_csv_samples(aligner._h, n, C.byref(res._c), ev, sc, bd, sm, seqs, _ptr(seq_off, N.c_u64_p), rid, sid,
                           so.ctypes.data_as(C.POINTER(C.c_int64)), li.ctypes.data_as(C.POINTER(C.c_int64)),
                           int(threads), buf.ctypes.data, cap, _ptr(begin, N.c_u64_p), _ptr(end, N.c_u64_p))
     if rc != N.DYN_OK:
@@ -408,6 +433,7 @@ class Batch:
         self._rescale = bool(calc_probabilities) and self._al._rescale > 0
         self._scores = bool(calc_probabilities) and self._al._segment_scores > 0
         self._borders = bool(calc_probabilities) and self._al._border_confidence > 0
+        self._samples = self._al._ticket_samples(bool(calc_probabilities))
         self._margins = bool(calc_probabilities) and self._al._band_margin
         self._rescued = self._al._ticket_rescue(bool(calc_probabilities))
         rc = self._L.dyn_batch_align(self._h, int(bool(calc_probabilities)))
@@ -483,6 +509,7 @@ class Batch:
         out._fetch_rescale(self._L, self._h, self._al, getattr(self, "_rescale", False))
         out._fetch_scores(self._L, self._h, self._al, getattr(self, "_scores", False))
         out._fetch_borders(self._L, self._h, self._al, getattr(self, "_borders", False))
+        out._fetch_samples(self._L, self._h, self._al, getattr(self, "_samples", 0))
         out._fetch_band_margin(self._L, self._h, self._al, getattr(self, "_margins", False))
         out._fetch_rescue(self._L, self._h, self._al, getattr(self, "_rescued", False))
         return out
@@ -502,6 +529,12 @@ class Batch:
     def fetch_borders(self, out: N.DynBorderOut) -> None:
         """dyn_batch_fetch_borders into caller-owned columns (raises ValueError for a batch that did not ask)."""
         rc = self._L.dyn_batch_fetch_borders(self._h, C.byref(out))
+        if rc != N.DYN_OK:
+            _raise(rc, self._al.last_error())
+
+    def fetch_samples(self, out: N.DynSampleOut) -> None:
+        """dyn_batch_fetch_samples into caller-owned arrays (raises ValueError for a batch that did not ask)."""
+        rc = self._L.dyn_batch_fetch_samples(self._h, C.byref(out))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
 
@@ -570,7 +603,8 @@ class AsyncBatch:
     (the library reads them until the batch is complete)."""
 
     def __init__(self, aligner: "Aligner", handle, result, keep, levels: bool = False, rescale: bool = False,
-                 scores: bool = False, borders: bool = False, margins: bool = False, auto_guide=None, rescue: bool = False):
+                 scores: bool = False, borders: bool = False, margins: bool = False, auto_guide=None, rescue: bool = False,
+                 samples: int = 0):
         self._al = aligner
         self._L = N.lib()
         self._h = handle
@@ -581,6 +615,7 @@ class AsyncBatch:
         self._rescale = rescale  # ... with the rescale switch on
         self._scores = scores  # ... with the segment-scores switch on
         self._borders = borders  # ... with the border-confidence switch on
+        self._samples = samples  # ... with the posterior-samples switch on: its count
         self._margins = margins  # ... with the band-margin switch on (tickets report margins; they are never retried)
         # ... with the auto-guide switch on (Aligner.set_auto_guide): (alignments per read, the ticket's sample offsets), else None
         self._auto_guide = auto_guide
@@ -598,6 +633,7 @@ class AsyncBatch:
                 self.result._fetch_rescale(self._L, self._h, self._al, self._rescale)
                 self.result._fetch_scores(self._L, self._h, self._al, self._scores)
                 self.result._fetch_borders(self._L, self._h, self._al, self._borders)
+                self.result._fetch_samples(self._L, self._h, self._al, self._samples)
                 self.result._fetch_band_margin(self._L, self._h, self._al, self._margins)
                 # a result object refilled from an earlier ticket must not keep that ticket's counts
                 self.result.guide_rounds = self.result.guide_converged = self.result.guides = None
@@ -623,6 +659,7 @@ class AsyncBatch:
     fetch_rescale = Batch.fetch_rescale
     fetch_scores = Batch.fetch_scores
     fetch_borders = Batch.fetch_borders
+    fetch_samples = Batch.fetch_samples
     fetch_band_margin = Batch.fetch_band_margin
 
     def timing(self) -> dict:
@@ -726,6 +763,7 @@ class Aligner:
     _rescale = 0  # set_rescale
     _segment_scores = 0  # set_segment_scores
     _border_confidence = 0  # set_border_confidence
+    _posterior_samples = (0, 0)  # set_posterior_samples: (count, seed)
     _band_margin = False  # set_band_margin
     _auto_guide = (0, 8)  # set_auto_guide: (half_width, refine)
     _band_retry = None  # set_band_retry: (min_margin, max_band, factor)
@@ -861,6 +899,27 @@ class Aligner:
             _raise(rc, self.last_error())
         self._border_confidence = int(window)
 
+    def set_posterior_samples(self, count: int, seed: int = 0) -> None:
+        """dyn_aligner_set_posterior_samples: align(calc_probabilities=True) jobs submitted while ``count`` (0 .. 64) > 0 also
+        draw ``count`` complete alignments of every read from the posterior distribution over alignments, on the GPU from the
+        read's own lattice, reproducibly from ``seed`` (0 .. 2^64 - 1) and the read's index in its
+        batch. Results carry ``AlignBatchResult.sample_starts`` (uint32 ``[count, cap]``: sample k's start of output row s, a
+        signal position like ``signal_positions``; ``DYN_SAMPLE_DEAD`` throughout a dead sample) and ``.sample_dead`` (uint32
+        ``[n]``); ``read(i)`` adds ``"sample_starts"`` (``[count, n_segments]``). Not together with ``set_band_retry``
+        (ValueError); a job started with ``set_rescale``, ``set_auto_guide`` or ``set_guide_rescue`` on as well, or on a guided
+        batch, is refused (ValueError). ``MultiAligner`` has no such switch."""
+        if int(count) > 0 and self._band_retry:
+            raise ValueError("set_posterior_samples with set_band_retry: a retried read's samples would come from another handle, "
+                             "keyed by another index")
+        rc = self._L.dyn_aligner_set_posterior_samples(self._h, int(count), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        self._posterior_samples = (int(count), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+    def _ticket_samples(self, calc_probabilities: bool) -> int:
+        """the sample count of an align job / ticket submitted now (0: it does not sample)"""
+        return self._posterior_samples[0] if calc_probabilities and self._ctor[2] not in ("ntk", "resquiggle") else 0
+
     def set_auto_guide(self, half_width: int, refine: int = 8) -> None:
         """dyn_aligner_set_auto_guide: ``align_async`` / ``align_raw_async`` / ``align_vbz_async`` tickets with
         ``calc_probabilities=True`` submitted while ``half_width`` (1 .. 2046) > 0 are aligned inside a guide the library makes
@@ -953,6 +1012,9 @@ class Aligner:
             raise ValueError("set_band_retry with set_guide_rescue: both re-align the reads a margin flags; choose one")
         if self._kmer_summary:
             raise ValueError("set_band_retry with set_kmer_summary: the retried reads would be summed twice")
+        if self._posterior_samples[0] > 0:
+            raise ValueError("set_band_retry with set_posterior_samples: a retried read's samples would come from another handle, "
+                             "keyed by another index")
         self.set_band_margin(True)
         self._band_retry = (min_margin, max_band, factor)
 
@@ -1119,7 +1181,8 @@ class Aligner:
                           borders=self._border_confidence > 0 and bool(calc_probabilities),
                           margins=self._band_margin and bool(calc_probabilities),
                           auto_guide=self._ticket_guide(bool(calc_probabilities), sig_off),
-                          rescue=self._ticket_rescue(bool(calc_probabilities)))
+                          rescue=self._ticket_rescue(bool(calc_probabilities)),
+                          samples=self._ticket_samples(bool(calc_probabilities)))
 
     def _raw_args(self, raw, shift, scale, calibration=None):
         scattered = isinstance(raw, (list, tuple))
@@ -1175,7 +1238,8 @@ class Aligner:
                           borders=self._border_confidence > 0 and bool(calc_probabilities),
                           margins=self._band_margin and bool(calc_probabilities),
                           auto_guide=self._ticket_guide(bool(calc_probabilities), raw_off),
-                          rescue=self._ticket_rescue(bool(calc_probabilities)))
+                          rescue=self._ticket_rescue(bool(calc_probabilities)),
+                          samples=self._ticket_samples(bool(calc_probabilities)))
 
     def align_vbz_async(self, chunks, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 3,
                         n_sigmas: float = 3.0, f32: bool = False, calc_probabilities: bool = True,
@@ -1215,7 +1279,8 @@ class Aligner:
                           borders=self._border_confidence > 0 and bool(calc_probabilities),
                           margins=self._band_margin and bool(calc_probabilities),
                           auto_guide=self._ticket_guide(bool(calc_probabilities), raw_off),
-                          rescue=self._ticket_rescue(bool(calc_probabilities)))
+                          rescue=self._ticket_rescue(bool(calc_probabilities)),
+                          samples=self._ticket_samples(bool(calc_probabilities)))
 
     def train_raw_async(self, raw, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 7,
                         n_sigmas: float = 5.0, f32: bool = True, pooled: bool = False,

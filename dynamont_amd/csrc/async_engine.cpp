@@ -146,6 +146,7 @@ static uint64_t merge_reads_per_slot() {  // DYN_MERGE_READS_PER_SLOT: experimen
 }
 static uint64_t merge_max_reads(const dyn_aligner* a) { return merge_reads_per_slot() * (uint64_t)a->n_cus * dynk::WAVES_PER_CU; }
 static bool mergeable(const dyn_batch* x) {
+  if (x->ps_want) return false;  // posterior samples: the read's index in its OWN ticket keys the random stream
   // batches that leave the waves underfilled (fewer than 1.5 reads per wave slot): a batch of four reads per slot balances
   // by itself, and merging those only makes the pipeline lumpy
   // (a self-guided ticket carries a guide of its own and takes the banded-lattice kernel: never merged)
@@ -807,6 +808,15 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
                     (a->rescale_iters > 0 ? "dyn_aligner_set_rescale(a, iters > 0)" : "dyn_aligner_set_border_confidence(a, window > 0)");
     return DYN_ERR_INVALID_ARGUMENT;
   }
+  // posterior samples (dyn_aligner_set_posterior_samples): as run_job_sync refuses them
+  const int ps = (job == DynJob::AlignFull && !a->ntk) ? a->posterior_samples : 0;
+  if (ps) {
+    if (const char* other = posterior_samples_conflict(a)) {
+      std::lock_guard<std::mutex> elk(a->err_mu);
+      a->last_error = std::string("dyn_batch_align_async: dyn_aligner_set_posterior_samples is on, which does not combine with ") + other;
+      return DYN_ERR_INVALID_ARGUMENT;
+    }
+  }
   dyn_batch* b = new dyn_batch();
   b->a = a;
   attach_cache(b);
@@ -824,6 +834,8 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
   b->bm_want = a->band_margin;
   b->sc_want = a->segment_scores;
   b->bc_want = a->border_confidence;
+  b->ps_want = ps;
+  b->ps_seed = a->sample_seed;
   b->in_signals = signals;
   if (rs) {
     b->has_raw = true;

@@ -52,6 +52,7 @@
 #include "band_reads.hpp"
 
 #include "border_kernels.hpp"
+#include "sample_kernels.hpp"
 #include "dp_math_strict.hpp"
 
 namespace dynk {
@@ -460,6 +461,45 @@ __global__ __launch_bounds__(THREADS) void k_band_reads(const BandArgs a) {
   }
 }
 
+// k_band_reads<DiagonalWindow, 256, 16, true, false, BORDER> with the posterior-sampling phase (sample_kernels.hpp) behind every
+// read (and behind the border phase), as a kernel of its own: the launches without it keep their names and their code. The
+// workgroup's first wave walks the samples, one lane each; band_read's closing barrier has made the lattice and the state
+// visible to it, and the barrier at the head of the loop keeps the arena until the walk is done.
+template <bool BORDER>
+__global__ __launch_bounds__(256) void k_band_reads_sample(const BandArgs a) {
+  constexpr int THREADS = 256, CPT = 16;
+  using Window = DiagonalWindow;
+  extern __shared__ __attribute__((aligned(16))) char g_lds[];
+  char* lds = Window::lds(g_lds);
+  const int stride = Window::row_stride(a);
+  uint64_t* s_exp = reinterpret_cast<uint64_t*>(lds);
+  double* s_rows = reinterpret_cast<double*>(lds + dynmath::STRICT_EXP_WORDS * 8);
+  int* s_ctl = reinterpret_cast<int*>(s_rows + 4 * stride);  // [0] next read, [1] s_bad
+  for (int i = threadIdx.x; i < dynmath::STRICT_EXP_WORDS; i += THREADS) s_exp[i] = a.exp_tab[i];
+  char* arena = a.arena + (size_t)blockIdx.x * a.arena_bytes;
+  for (;;) {
+    __syncthreads();
+    if (threadIdx.x == 0) s_ctl[0] = (int)atomicAdd(a.head, 1u);
+    __syncthreads();
+    const int k = s_ctl[0];
+    if (k >= a.n_reads) break;
+    const ReadDesc rd = a.descs[k];
+    const size_t cells = (size_t)rd.T * (size_t)(2 * Window(rd, a).bw + 3);
+    double* bE = reinterpret_cast<double*>(arena);
+    double* bM = bE + cells;
+    float* lp = reinterpret_cast<float*>(bM + cells);
+    uint8_t* bit = reinterpret_cast<uint8_t*>(lp + 2 * cells);
+    band_read<Window, THREADS, CPT, true, false>(rd, a, bE, bM, lp, bit, s_rows, stride, s_exp, s_ctl + 1);
+    if (__hip_atomic_load(&a.st[rd.read].status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) {
+      const BorderBand band{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio};
+      const BorderCellWide cell{band, lp};
+      if constexpr (BORDER)
+        border_confidence_read(cell, rd, a.tb.segrow, a.border_p, a.border_window_p, a.border_window, (int)threadIdx.x, THREADS);
+      if (threadIdx.x < 64) posterior_samples_read(cell, SampleLpeWide{band, lp}, rd, a.sample, (int)threadIdx.x);
+    }
+  }
+}
+
 uint64_t band_arena_bytes(uint64_t T, uint64_t bw, int job) {
   if (job == 0) return 0;
   const uint64_t cells = T * (2 * bw + 3);
@@ -515,10 +555,17 @@ hipError_t launch_band_reads(int job, const BandArgs& a, int n_groups, hipStream
   if (job == 2 && !(a.tr.col_w && a.tr.col_s1 && a.tr.col_s2 && a.tr.trans)) return hipErrorInvalidValue;
   if (job != 0 && !a.arena) return hipErrorInvalidValue;
   if (a.border_window > 0 && (a.guide || job != 1 || !a.border_p || !a.border_window_p)) return hipErrorInvalidValue;
+  if (job == 1 && a.sample.count != 0 && (a.sample.count < 0 || a.guide || a.active || job != 1 || a.sample.count > PS_MAX_SAMPLES || !a.sample.start))
+    return hipErrorInvalidValue;
   const bool refine = a.refine_rounds > 1;  // every read refined inside this launch
   if (refine && (!a.guide || job != 1 || a.border_window > 0 || !a.rounds || !a.converged)) return hipErrorInvalidValue;
   if (const hipError_t e = hipMemsetAsync(a.head, 0, 4, s)) return e;
   if (!a.guide) {
+    if (job == 1 && a.sample.count > 0) {  // (static LDS, as every diagonal launch)
+      if (a.border_window > 0) hipLaunchKernelGGL(k_band_reads_sample<true>, dim3(n_groups), dim3(256), 0, s, a);
+      else hipLaunchKernelGGL(k_band_reads_sample<false>, dim3(n_groups), dim3(256), 0, s, a);
+      return hipGetLastError();
+    }
     if (a.border_window > 0) return launch_kernel<DiagonalWindow, 256, 16, true, false, true>(a, n_groups, 0, s);
     return launch_shape<DiagonalWindow, 256, 16>(job, a, n_groups, 0, s);  // (static LDS)
   }

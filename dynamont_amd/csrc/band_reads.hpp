@@ -32,7 +32,10 @@ struct BandArgs {
                            // Read only, except by a refining launch (refine_rounds > 1), which rewrites it
   ReadState* st;
   TraceBuffers tb;
-  TrainBuffers tr;         // job 2 only: the read's column sums at col_* + ReadDesc::par_off, trans[2 * read]
+  union {                  // (as in QueueArgs: the two never meet, and the argument layout stays what it was)
+    TrainBuffers tr;       // job 2 only: the read's column sums at col_* + ReadDesc::par_off, trans[2 * read]
+    SampleOut sample;      // job 1 only, diagonal window, with or without a border window: posterior path samples, count > 0 when asked for
+  };
   char* arena;             // n_groups arenas of arena_bytes: the lattice of the read a workgroup is working on (jobs 1 and 2)
   uint64_t arena_bytes;    // >= band_arena_bytes of the largest read
   uint32_t* head;          // queue head (cleared by launch_band_reads)
@@ -66,7 +69,8 @@ int band_groups_per_cu(bool guided, int bw, int job);
 // job: 0 = Z only, 1 = align(calc_probabilities = true) up to the per-row path arrays (launch_segments follows), 2 = train:
 // the read's (w, s1, s2) column sums and transition counts in BandArgs::tr (finalise_train / pool_stats follow). Returns what
 // raising the dynamic-LDS limit (guided rows above 48 KiB) or the launch reported. hipErrorInvalidValue for a refining launch
-// (BandArgs::refine_rounds > 1) without a guide, with a job other than 1, with a border window or without rounds / converged.
+// (BandArgs::refine_rounds > 1) without a guide, with a job other than 1, with a border window or without rounds / converged,
+// and for posterior samples (BandArgs::sample.count > 0) with a guide, a job other than 1 or without their arrays.
 hipError_t launch_band_reads(int job, const BandArgs& a, int n_groups, hipStream_t s);
 
 }  // namespace dynk

@@ -99,6 +99,7 @@ struct Args {
   const dyn_event_out* ev;  // nullptr: no level columns
   const dyn_score_out* sc;  // nullptr: no segment-score columns
   const dyn_border_out* bd;  // nullptr: no border-confidence columns
+  const dyn_sample_out* sm;  // nullptr: no posterior-sample column
   const char* seqs;
   const uint64_t* seq_offsets;
   const char* const* readids;
@@ -139,6 +140,7 @@ uint64_t read_bound(const Args& a, uint64_t i) {
     for (uint64_t s = o; s < o + n; ++s)
       b += event_value_bound(a.bd->border_probability[s]) + event_value_bound(a.bd->border_window_probability[s]);
   }
+  if (a.sm) b += n * (1 + 21 * (uint64_t)a.sm->count);  // the comma; per sample an integer (<= 20 characters) and its ';'
   return b;
 }
 
@@ -197,6 +199,14 @@ char* format_read(const Args& a, uint64_t i, char* p) {
       *p++ = ',';
       p = put_prob6<true>(p, a.bd->border_window_probability[o + s]);
     }
+    if (a.sm) {  // one field: the K sampled starts of this segment
+      *p++ = ',';
+      for (uint32_t k = 0; k < a.sm->count; ++k) {
+        if (k) *p++ = ';';
+        const uint32_t v = a.sm->sample_start[(uint64_t)k * a.sm->capacity + o + s];
+        p = put_int(p, v == 0xFFFFFFFFu ? (int64_t)v : (int64_t)v + a.sig_offsets[i]);  // the `start` column's unit; dead as it is
+      }
+    }
     *p++ = '\n';
   }
   return p;
@@ -224,11 +234,17 @@ extern "C" uint64_t dyn_format_csv_bound_scores(const dyn_aligner* a, uint64_t n
 extern "C" uint64_t dyn_format_csv_bound_borders(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
                                                  const dyn_event_out* ev, const dyn_score_out* sc, const dyn_border_out* bd,
                                                  const char* const* readids, const char* const* signalids) {
+  return dyn_format_csv_bound_samples(a, n_reads, res, ev, sc, bd, nullptr, readids, signalids);
+}
+
+extern "C" uint64_t dyn_format_csv_bound_samples(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
+                                                 const dyn_event_out* ev, const dyn_score_out* sc, const dyn_border_out* bd,
+                                                 const dyn_sample_out* sm, const char* const* readids, const char* const* signalids) {
   if (!a || !res || (ev && (!ev->mean || !ev->stdev || !ev->median)) ||
       (sc && (!sc->median_delta || !sc->mad_delta || !sc->homogeneity)) ||
-      (bd && (!bd->border_probability || !bd->border_window_probability)))
+      (bd && (!bd->border_probability || !bd->border_window_probability)) || (sm && !sm->sample_start))
     return 0;
-  Args args{0, 0, res, ev, sc, bd, nullptr, nullptr, readids, signalids, nullptr, nullptr};
+  Args args{0, 0, res, ev, sc, bd, sm, nullptr, nullptr, readids, signalids, nullptr, nullptr};
   uint64_t total = 0;
   for (uint64_t i = 0; i < n_reads; ++i) total += read_bound(args, i);
   return total;
@@ -266,6 +282,17 @@ extern "C" int dyn_format_csv_borders(const dyn_aligner* a, uint64_t n_reads, co
                                       const char* seqs, const uint64_t* seq_offsets, const char* const* readids,
                                       const char* const* signalids, const int64_t* sig_offsets, const int64_t* last_index,
                                       int threads, char* out, uint64_t out_cap, uint64_t* row_begin, uint64_t* row_end) {
+  return dyn_format_csv_samples(a, n_reads, res, ev, sc, bd, nullptr, seqs, seq_offsets, readids, signalids, sig_offsets, last_index,
+                                threads, out, out_cap, row_begin, row_end);
+}
+
+extern "C" int dyn_format_csv_samples(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
+                                      const dyn_event_out* ev, const dyn_score_out* sc, const dyn_border_out* bd,
+                                      const dyn_sample_out* sm, const char* seqs, const uint64_t* seq_offsets,
+                                      const char* const* readids, const char* const* signalids, const int64_t* sig_offsets,
+                                      const int64_t* last_index, int threads, char* out, uint64_t out_cap, uint64_t* row_begin,
+                                      uint64_t* row_end) {
+  if (sm && !sm->sample_start) return DYN_ERR_INVALID_ARGUMENT;
   if (!a || !res || !res->status || !res->n_segments || !res->seg_offsets || !res->sequence_positions ||
       !res->signal_positions || !res->probabilities || !out || !row_begin || !row_end ||
       (ev && (!ev->mean || !ev->stdev || !ev->median)) || (sc && (!sc->median_delta || !sc->mad_delta || !sc->homogeneity)) ||
@@ -274,7 +301,7 @@ extern "C" int dyn_format_csv_borders(const dyn_aligner* a, uint64_t n_reads, co
   dyn_info info;
   dyn_aligner_info(a, &info);
   if (info.kmer_size > 31) return DYN_ERR_INVALID_ARGUMENT;
-  Args args{info.kmer_size, info.rna, res, ev, sc, bd, seqs, seq_offsets, readids, signalids, sig_offsets, last_index};
+  Args args{info.kmer_size, info.rna, res, ev, sc, bd, sm, seqs, seq_offsets, readids, signalids, sig_offsets, last_index};
   // every read formats straight into its own worst-case slot of the caller's buffer: no allocation,
   // no shared cache lines between threads
   uint64_t pos = 0;

@@ -60,7 +60,7 @@ void attach_cache(dyn_batch* b) {
   dyneng::BufCache* c = &b->a->cache;
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_ps, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
                     &b->d_resc_st, &b->d_resc_pp, &b->d_resc_pathn, &b->d_resc_segrow})
     d->cache = c;
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref, &b->h_resc}) h->cache = c;
@@ -571,6 +571,20 @@ int dyn_aligner_set_border_confidence(dyn_aligner* a, int window) {
   return DYN_OK;
 }
 
+int dyn_aligner_set_posterior_samples(dyn_aligner* a, int count, uint64_t seed) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  auto fail = [&](const std::string& msg) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = "dyn_aligner_set_posterior_samples: " + msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  };
+  if (count < 0 || count > DYN_POSTERIOR_SAMPLES_MAX) return fail("count must be 0 .. 64, got " + std::to_string(count));
+  if (count > 0 && a->ntk) return fail("modes ntk / resquiggle have no align(calc_probabilities = 1) job whose lattice could be sampled");
+  a->posterior_samples = count;
+  a->sample_seed = seed;
+  return DYN_OK;
+}
+
 int dyn_aligner_set_auto_guide(dyn_aligner* a, uint32_t half_width, uint32_t max_rounds) {
   if (!a) return DYN_ERR_INVALID_ARGUMENT;
   auto fail = [&](const std::string& msg) {
@@ -956,7 +970,7 @@ void dyn_batch_destroy(dyn_batch* b) {
   }
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_ps, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
                     &b->d_resc_st, &b->d_resc_pp, &b->d_resc_pathn, &b->d_resc_segrow})
     d->release();
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref, &b->h_resc}) h->release();
@@ -1172,6 +1186,19 @@ int run_job_sync(dyn_batch* b, DynJob job, bool guided_train = false) {
                     (a->rescale_iters > 0 ? "dyn_aligner_set_rescale(a, iters > 0)" : "dyn_aligner_set_border_confidence(a, window > 0)");
     return DYN_ERR_INVALID_ARGUMENT;
   }
+  // posterior samples (dyn_aligner_set_posterior_samples) concern align jobs with probabilities: a walk through the lattice of
+  // the read's one plain alignment in the diagonal band
+  if (job == DynJob::AlignFull && a->posterior_samples > 0) {
+    if (b->guided) {
+      a->last_error = "dyn_batch_align: the batch carries a guide (dyn_batch_set_guide / dyn_batch_auto_guide), which does not combine with "
+                      "dyn_aligner_set_posterior_samples(a, count > 0)";
+      return DYN_ERR_INVALID_ARGUMENT;
+    }
+    if (const char* other = posterior_samples_conflict(a)) {
+      a->last_error = std::string("dyn_batch_align: dyn_aligner_set_posterior_samples is on, which does not combine with ") + other;
+      return DYN_ERR_INVALID_ARGUMENT;
+    }
+  }
   // the guide rescue (dyn_aligner_set_guide_rescue) concerns align jobs with probabilities; the Z-only and the train job ignore it
   const uint32_t gr_hw = (job == DynJob::AlignFull && !a->ntk) ? a->rescue_hw : 0u;
   if (gr_hw) {
@@ -1198,6 +1225,8 @@ int run_job_sync(dyn_batch* b, DynJob job, bool guided_train = false) {
     b->bm_want = a->band_margin;
     b->sc_want = a->segment_scores;
     b->bc_want = a->border_confidence;
+    b->ps_want = a->posterior_samples;
+    b->ps_seed = a->sample_seed;
     rc = enqueue_job(b, job);
     if (rc != DYN_OK) {
       (void)hipStreamSynchronize(a->stream);
@@ -1468,9 +1497,49 @@ int batch_check_borders(dyn_batch* b) {
                      "submitted without dyn_aligner_set_border_confidence(a, window > 0) or with calc_probabilities = 0";
   return DYN_ERR_INVALID_ARGUMENT;
 }
+uint32_t batch_sample_count(const dyn_batch* b) { return (uint32_t)b->ps_want; }
+int batch_check_samples(dyn_batch* b) {
+  if (b->ps_want && b->job == DynJob::AlignFull) return DYN_OK;
+  std::lock_guard<std::mutex> lk(b->a->err_mu);
+  b->a->last_error = "dyn_csv_sink_submit: the sink writes the posterior samples (DYN_CSV_POSTERIOR_SAMPLES) and this ticket was "
+                     "submitted without dyn_aligner_set_posterior_samples(a, count > 0) or with calc_probabilities = 0";
+  return DYN_ERR_INVALID_ARGUMENT;
+}
 }  // namespace dyneng
 
 extern "C" {
+
+int dyn_batch_fetch_samples(dyn_batch* b, dyn_sample_out* out) {
+  if (!b || !out || !out->sample_start || !out->sample_dead) return DYN_ERR_INVALID_ARGUMENT;
+  dyn_aligner* a = b->a;
+  // (a sampling ticket is never a member of a merged launch: the read's index in its own ticket keys the random stream)
+  if (!b->aligned || !b->last_calc || !b->ps_ready) {
+    a->last_error = !b->aligned || !b->last_calc
+                        ? "dyn_batch_fetch_samples: the batch was not aligned with calc_probabilities = 1"
+                        : "dyn_batch_fetch_samples: the batch was submitted without dyn_aligner_set_posterior_samples(a, count > 0)";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  if (out->capacity < b->capacity || out->count < (uint32_t)b->ps_ready || out->n < b->n) {
+    a->last_error = out->capacity < b->capacity ? "dyn_sample_out.capacity is smaller than dyn_segment_capacity()"
+                    : out->n < b->n            ? "dyn_sample_out.n is smaller than the batch's read count"
+                                               : "dyn_sample_out.count is smaller than the batch's sample count (" + std::to_string(b->ps_ready) + ")";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  int rc = need_device(a);
+  if (rc != DYN_OK) return rc;
+  const uint32_t* d = b->d_ps.as<uint32_t>();
+  if (b->capacity) {
+    if (out->capacity == b->capacity) {
+      HIP_TRY(a, copy_out(a, out->sample_start, d, (uint64_t)b->ps_ready * b->capacity * 4));
+    } else {
+      for (int k = 0; k < b->ps_ready; ++k)
+        HIP_TRY(a, copy_out(a, out->sample_start + (uint64_t)k * out->capacity, d + (uint64_t)k * b->capacity, b->capacity * 4));
+    }
+  }
+  if (b->n) HIP_TRY(a, copy_out(a, out->sample_dead, d + (uint64_t)b->ps_ready * b->capacity, b->n * 4));
+  out->count = (uint32_t)b->ps_ready;
+  return DYN_OK;
+}
 
 int dyn_batch_fetch_borders(dyn_batch* b, dyn_border_out* out) {
   if (!b || !out || !out->border_probability || !out->border_window_probability) return DYN_ERR_INVALID_ARGUMENT;

@@ -155,6 +155,8 @@ struct dyn_aligner {
   bool kmer_summary = false;  // dyn_aligner_set_kmer_summary: read by every batch / ticket at its submission
   int segment_scores = 0;     // dyn_aligner_set_segment_scores (window, 0 = off): read by every batch / ticket at its submission
   int border_confidence = 0;  // dyn_aligner_set_border_confidence (window, 0 = off): read by every batch / ticket at its submission
+  int posterior_samples = 0;  // dyn_aligner_set_posterior_samples (count, 0 = off): read by every batch / ticket at its submission
+  uint64_t sample_seed = 0;   // ... and its seed
   bool band_margin = false;   // dyn_aligner_set_band_margin: read by every batch / ticket at its submission
   // dyn_aligner_set_auto_guide (half width, 0 = off; alignments per read): read by every align(calc = 1) TICKET at its submission
   uint32_t auto_guide_hw = 0, auto_guide_rounds = 8;
@@ -263,6 +265,10 @@ struct dyn_batch {
   dyneng::DevBuf d_bc;                         // [2][capacity] border_probability / border_window_probability (border_kernels.hpp)
   int bc_want = 0;                             // the handle's border-confidence window when this batch / ticket was submitted
   bool bc_ready = false;                       // the last job computed the border columns into d_bc
+  dyneng::DevBuf d_ps;                         // [ps_want][capacity] u32 sample starts | [n] u32 dead samples (sample_kernels.hpp)
+  int ps_want = 0;                             // the handle's posterior-sample count when this batch / ticket was submitted
+  uint64_t ps_seed = 0;                        // ... and its seed
+  int ps_ready = 0;                            // the count the last job sampled into d_ps (0: it did not)
   // per-read rescaling (rescale.hip, dyn_aligner_set_rescale)
   dyneng::DevBuf d_sig0;                       // the preprocessed signal x0, kept while d_sig holds a rescaled one
   dyneng::DevBuf d_rs;                         // [n] dynk::RescaleState | [capacity] row means of the fit (scratch)

@@ -48,5 +48,13 @@ inline const char* guide_rescue_conflict(const dyn_aligner* a) {
   if (a->auto_guide_hw > 0) return "dyn_aligner_set_auto_guide(a, half_width > 0)";
   return nullptr;
 }
+// likewise for dyn_aligner_set_posterior_samples: a sampled path is a walk through the lattice of the one plain alignment of a
+// read in the diagonal band; the switches that re-align a read or align it inside a guide window have no such lattice to offer
+inline const char* posterior_samples_conflict(const dyn_aligner* a) {
+  if (a->rescale_iters > 0) return "dyn_aligner_set_rescale(a, iters > 0)";
+  if (a->auto_guide_hw > 0) return "dyn_aligner_set_auto_guide(a, half_width > 0)";
+  if (a->rescue_hw > 0) return "dyn_aligner_set_guide_rescue(a, half_width > 0)";
+  return nullptr;
+}
 
 }  // namespace dyneng

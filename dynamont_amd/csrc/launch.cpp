@@ -601,7 +601,8 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   q.st = b->d_state.as<ReadState>();
   q.tb = dynk::TraceBuffers{b->d_pp.as<double>(), b->d_pathn.as<uint32_t>(), b->d_segrow.as<uint32_t>(),
                             b->d_medhi.as<double>(), b->d_medlo.as<double>()};
-  q.tr = dynk::TrainBuffers{b->d_colw.as<double>(), b->d_cols1.as<double>(), b->d_cols2.as<double>(), b->d_trans.as<double>()};
+  // (train jobs only: in an align job the posterior samples take their place, below)
+  if (job == DynJob::Train) q.tr = dynk::TrainBuffers{b->d_colw.as<double>(), b->d_cols1.as<double>(), b->d_cols2.as<double>(), b->d_trans.as<double>()};
   q.m1 = m.log_m1;
   q.e2 = m.log_e2;
   q.sp_tab = a->d_sptab.as<dynmath::SoftplusNode>();
@@ -617,6 +618,21 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     if (b->capacity) HIP_TRY(a, hipMemsetAsync(b->d_bc.p, 0, b->capacity * 16, a->stream));
     bc_cols = b->d_bc.as<double>();
     b->bc_ready = true;
+  }
+  // posterior path samples: [count][capacity] segment starts, then the per-read count of dead samples, zeroed here (rows of reads
+  // that fail keep the zeros), written by the read queue / the banded-lattice kernel behind every read. (The callers refuse the
+  // switches that would make this more than one pass.)
+  b->ps_ready = 0;
+  if (calc && b->ps_want) {
+    const uint64_t words = (uint64_t)b->ps_want * b->capacity + b->n;
+    HIP_TRY(a, b->d_ps.ensure(std::max<uint64_t>(16, words * 4)));
+    if (words) HIP_TRY(a, hipMemsetAsync(b->d_ps.p, 0, words * 4, a->stream));
+    q.sample.start = b->d_ps.as<uint32_t>();  // (the dead counts follow the planes)
+    q.sample.capacity = b->capacity;
+    q.sample.seed = b->ps_seed;
+    q.sample.count = b->ps_want;
+    q.lpe_dense = 1;  // a sampled path may visit any cell of the band (the kernel variant that carries the phase stores densely anyway)
+    b->ps_ready = b->ps_want;
   }
   const dynk::QueueJob qjob = job == DynJob::Train ? (a->train_zcheck ? dynk::JOB_TRAIN_ZCHECK : dynk::JOB_TRAIN)
                               : !calc              ? dynk::JOB_Z
@@ -665,7 +681,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       ba.guide = b->guided ? b->d_guide.as<int32_t>() : nullptr;  // null: the diagonal window
       ba.st = q.st;
       ba.tb = q.tb;
-      ba.tr = q.tr;
+      ba.tr = q.tr;  // (an align job: the posterior samples, which share the place)
       ba.head = arena_buf.as<uint32_t>();
       ba.arena = arena_buf.as<char>() + 256;
       ba.arena_bytes = wide_arena;

@@ -108,6 +108,18 @@ constexpr int QUEUE_N_STATS = 10;
 enum QueueJob { JOB_Z = 0, JOB_ALIGN = 1, JOB_ALIGN_INPLACE = 2, JOB_TRAIN = 3, JOB_TRAIN_ZCHECK = 4 };
 constexpr int JOB_BORDER = 8;  // a bit on top of JOB_ALIGN / JOB_ALIGN_INPLACE in k_read_queue's template argument: the launch
                                // carries the border-confidence phase (border_kernels.hpp)
+constexpr int JOB_SAMPLE = 16; // likewise: the launch carries the posterior-sampling phase (sample_kernels.hpp), behind the border
+                               // phase when both bits are set
+
+// posterior path samples (dyn_aligner_set_posterior_samples; sample_kernels.hpp). count == 0: not asked for (and the launch is
+// the one it has always been). The per-read counts of dead samples live behind the planes: start + count * capacity, one per
+// read of the batch.
+struct SampleOut {
+  uint32_t* start;    // [count][capacity] segment starts, sample-major, then [reads of the batch] dead samples; zeroed by the caller
+  uint64_t capacity;  // the batch's segment capacity: the stride between two samples' planes
+  uint64_t seed;
+  int count;          // K, 1 .. 64
+};
 
 struct QueueArgs {
   const ReadDesc* descs;   // in processing order
@@ -118,7 +130,12 @@ struct QueueArgs {
   PagePool pool;
   ReadState* st;
   TraceBuffers tb;
-  TrainBuffers tr;
+  // A train job has no path to sample and an align job no train buffers: the two share their place, so that the kernel-argument
+  // layout of every launch stays what it was before there were samples. All zero (what `QueueArgs q{}` leaves): neither.
+  union {
+    TrainBuffers tr;    // JOB_TRAIN / JOB_TRAIN_ZCHECK
+    SampleOut sample;   // JOB_ALIGN / JOB_ALIGN_INPLACE: posterior path samples, count > 0 when asked for
+  };
   double m1, e2;          // log transition probabilities (NT_aligner_api.cpp:84-86)
   const dynmath::SoftplusNode* sp_tab;
   int z_fail_status;
@@ -132,6 +149,7 @@ struct QueueArgs {
   double* border_p = nullptr;
   double* border_window_p = nullptr;
 };
+static_assert(sizeof(SampleOut) <= sizeof(TrainBuffers), "the samples take the train buffers' place in QueueArgs / BandArgs");
 
 // ---- the RESIDENT read queue (round 5) ---------------------------------------------------------------------------
 // k_read_queue drains ONE batch per launch: its waves finish up to one read apart, and the next launch -- queued on the same

@@ -48,6 +48,8 @@ CSV_HEADER_EVENTS = CSV_HEADER[:-1] + b",level_mean,level_stdv,level_median\n"
 CSV_COLUMNS_SCORES = b",median_delta,mad_delta,homogeneity"
 # --border-confidence W: ... and, after those, the per-border posterior confidence (Aligner.set_border_confidence)
 CSV_COLUMNS_BORDERS = b",border_probability,border_window_probability"
+# --posterior-samples K: ... and, after those, one field with the K sampled starts of the segment (Aligner.set_posterior_samples)
+CSV_COLUMNS_SAMPLES = b",sample_starts"
 POLYA = "AAAAAAAAA"
 
 MAX_SAMPLES_IN_FLIGHT = 512 << 20  # ~1 GB of pinned int16 staging + ~4 GB of float64 on the device, whatever --depth says
@@ -102,6 +104,13 @@ def parse(argv=None) -> Namespace:
                         "any): the posterior probability, over all segmentations, that the segment starts exactly at the called "
                         "sample, and that it starts within W samples (1 .. 256, default 0 = off) of it -- computed on the GPU from "
                         "the forward-backward lattice of the alignment")
+    p.add_argument("--posterior-samples", type=int, default=0, choices=range(0, 65), metavar="K",
+                   help="add sample_starts to every row (after the level, score and border columns, if any): K (1 .. 64, default 0 "
+                        "= off) alternative starts of the segment joined by ';', one from each of K complete segmentations of the "
+                        "read drawn on the GPU from the posterior distribution over alignments -- column k of the field, read down "
+                        "a read's rows, is one jointly consistent segmentation. Reproducible for the same input order, "
+                        "--batch-reads and --sample-seed. Not together with --rescale-iters, --guide-auto or --guide-rescue")
+    p.add_argument("--sample-seed", type=int, default=0, metavar="S", help="with --posterior-samples: the seed of the draws (default 0)")
     p.add_argument("--rescale-iters", type=int, default=0, choices=range(0, 9), metavar="N",
                    help="align every read N + 1 times (0 .. 8, default 0 = off), refitting the read's signal shift and scale "
                         "on the GPU between the passes: a least-squares fit of the segment levels on the model levels. "
@@ -147,6 +156,11 @@ def parse(argv=None) -> Namespace:
     for other, name in ((args.guide_auto, "--guide-auto"), (args.rescale_iters, "--rescale-iters"), (args.border_confidence, "--border-confidence")):
         if args.guide_rescue and other:
             p.error("--guide-rescue and %s are mutually exclusive" % name)
+    for other, name in ((args.guide_auto, "--guide-auto"), (args.rescale_iters, "--rescale-iters"), (args.guide_rescue, "--guide-rescue")):
+        if args.posterior_samples and other:
+            p.error("--posterior-samples and %s are mutually exclusive" % name)
+    if args.sample_seed < 0 or args.sample_seed >= 1 << 64:
+        p.error("--sample-seed must be 0 .. 2^64 - 1")
     return args
 
 
@@ -640,6 +654,8 @@ class _NativePipeline:
             flags |= N.DYN_CSV_SEGMENT_SCORES  # ... and the segment scores (--segment-scores)
         if aligner._border_confidence:
             flags |= N.DYN_CSV_BORDER_CONFIDENCE  # ... and the border confidence (--border-confidence)
+        if aligner._posterior_samples[0]:
+            flags |= N.DYN_CSV_POSTERIOR_SAMPLES  # ... and the posterior samples (--posterior-samples)
         rc = self.L.dyn_csv_sink_open_ex(outfile.encode(), errfile.encode(), int(os.environ.get("DYN_SINK_LEVEL", level)), int(threads),
                                          int(first), int(last), flags, C.byref(h), err, 1024)
         if rc != N.DYN_OK:
@@ -860,7 +876,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             host_preprocess: bool = False, depth: int = 12, strict_ties: str = "ties", host_threads: int = 0,
             zstd_level: int = 3, event_stats: bool = False, rescale_iters: int = 0, kmer_summary: str = "",
             segment_scores: int = 0, border_confidence: int = 0, band_report: str = "", band: int = 400,
-            guide_auto: int = 0, guide_rounds: int = 8, guide_rescue: int = 0, guide_rescue_margin: int = 1) -> None:
+            guide_auto: int = 0, guide_rounds: int = 8, guide_rescue: int = 0, guide_rescue_margin: int = 1,
+            posterior_samples: int = 0, sample_seed: int = 0) -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
@@ -873,6 +890,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
     if guide_rescue < 0 or guide_rescue_margin < 0 or (guide_rescue and (guide_auto or rescale_iters or border_confidence)):
         raise ValueError("--guide-rescue and --guide-rescue-margin must be >= 0; --guide-rescue is not combined with --guide-auto, "
                          "--rescale-iters or --border-confidence")
+    if not 0 <= posterior_samples <= 64 or (posterior_samples and (guide_auto or guide_rescue or rescale_iters)):
+        raise ValueError("--posterior-samples must be 0 .. 64 and is not combined with --guide-auto, --guide-rescue or --rescale-iters")
     from dynamont_amd import parallel
     comm, local_rank = parallel.init_from_env()
     rank, world = (comm.rank, comm.world) if comm else (0, 1)
@@ -895,6 +914,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             header = header[:-1] + CSV_COLUMNS_SCORES + b"\n"
         if border_confidence:
             header = header[:-1] + CSV_COLUMNS_BORDERS + b"\n"
+        if posterior_samples:
+            header = header[:-1] + CSV_COLUMNS_SAMPLES + b"\n"
         writer = threading.Thread(target=listener, args=(q, outfile, header), daemon=True)
         writer.start()
     sink = None if native else (q if comm is None else _Collector())
@@ -978,6 +999,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                 aligner.set_segment_scores(segment_scores)
             if border_confidence:
                 aligner.set_border_confidence(border_confidence)
+            if posterior_samples:
+                aligner.set_posterior_samples(posterior_samples, sample_seed)
             if kmer_summary:
                 aligner.set_kmer_summary(True)
             if band_report:
@@ -1140,7 +1163,7 @@ def main(argv=None) -> None:
             kmer_summary=args.kmer_summary, segment_scores=args.segment_scores,
             border_confidence=args.border_confidence, band_report=args.band_report, band=args.band,
             guide_auto=args.guide_auto, guide_rounds=args.guide_rounds, guide_rescue=args.guide_rescue,
-            guide_rescue_margin=args.guide_rescue_margin)
+            guide_rescue_margin=args.guide_rescue_margin, posterior_samples=args.posterior_samples, sample_seed=args.sample_seed)
     _stamp("segment() returned (aligner closed)")
     if argv is None and not int(__import__("os").environ.get("WORLD_SIZE", "1") or 1) > 1:
         # Invoked as the command (console script / python -m), single process, everything written and closed: leave without

@@ -194,6 +194,36 @@ typedef struct dyn_border_out {
   uint64_t capacity;
 } dyn_border_out;
 
+/* (added within ABI 10: a caller that must know looks the symbol up) Posterior path samples of an align(calc_probabilities = 1)
+ * job whose handle had dyn_aligner_set_posterior_samples(a, K, seed) with K > 0 when the batch was submitted: K complete
+ * alignments of every OK read drawn from the posterior distribution over alignments, each as its segment starts.
+ * Lattice rows t = 0 .. T-1 (T - 1 samples), columns n = 0 .. N-1 (N - 1 output rows). LPM(t, n) / LPE(t, n): the log-posteriors
+ * of the M and the E cell, both -inf outside the reference's band window of the row (computeBounds, NT_aligner_api.cpp:90-108),
+ * LPM -inf in row 0, LPE(0, 0) = 0 -- the values dyn_border_out is defined over.
+ *   u(seed, i, k, t) = (mix(mix(mix(seed + i) + k) + t) >> 11) * 2^-53, mix the SplitMix64 step
+ *     z = x + 0x9E3779B97F4A7C15;  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^ z >> 31
+ *   (all mod 2^64); i = the read's index in its batch or ticket, k = the sample, t = the row of the cell the choice is made at.
+ * Sample k of read i starts in E(0, 0). While (t, n) != (T-1, N-1): a = LPM(t+1, n+1) (-inf when n+1 >= N or t+1 > T-1),
+ * b = LPE(t+1, n). Both -inf: the sample is dead. Exactly one finite: that way is taken, no number is drawn. Both finite:
+ * p = exp(a - LPE(t, n)) in fp64, and the walk moves iff u(seed, i, k, t) < p. A move records sample_start[k][j = n] = t -- a
+ * signal position, the unit of signal_positions -- and continues in E(t+2, n+1) (an M cell has one way on); a stay continues in
+ * E(t+1, n). M(t+1, n+1) has the single predecessor E(t, n), so P(move | E(t, n)) = exp(LPM(t+1, n+1) - LPE(t, n)): the samples
+ * are exact draws from the posterior. A dead sample has all its entries 0xFFFFFFFF and is counted in sample_dead[i]; rows of
+ * failed reads are 0.
+ * Reproducibility: the same bits on every run of the same batch (same reads in the same order, same seed). The lattice's
+ * log-posteriors are floats in two of its three layouts and rebuilt in fp64 in the third (the layout follows the batch's size
+ * and the handle's memory budget), agreeing to 1e-6 and not to the bit: a draw within about 1e-6 p of its threshold may fall
+ * differently from one layout to another. A sample depends on the read's INDEX: the same read at another place of another
+ * batch gets other paths. */
+#define DYN_POSTERIOR_SAMPLES_MAX 64
+typedef struct dyn_sample_out {
+  uint32_t* sample_start; /* [count][capacity]: sample k of output row s at k * capacity + s, rows indexed like dyn_align_out's */
+  uint32_t* sample_dead;  /* [n]: dead samples of every read */
+  uint64_t capacity;      /* >= dyn_segment_capacity() */
+  uint64_t n;             /* >= the batch's read count */
+  uint32_t count;         /* in: planes of sample_start, >= the batch's K; out: the batch's K */
+} dyn_sample_out;
+
 /* (ABI 10) Per-read signal rescaling of an align(calc_probabilities = 1) job whose handle had dyn_aligner_set_rescale(a, K)
  * with K > 0 when the batch was submitted. Read r is aligned K + 1 times. x0 = its preprocessed signal (what
  * dyn_batch_signals returns with the switch off); A_0 = 0.0, B_0 = 1.0; pass k = 0 .. K aligns x_k, x_0 = x0 and
@@ -439,6 +469,16 @@ int dyn_aligner_set_segment_scores(dyn_aligner* a, int window);
  * one it would have been. DYN_ERR_INVALID_ARGUMENT + message outside that range. A ticket submitted with window > 0 takes
  * one launch per batch (not the resident session) and merges only with tickets of the same window. */
 int dyn_aligner_set_border_confidence(dyn_aligner* a, int window);
+/* (added within ABI 10) align(calc_probabilities = 1) also draws `count` posterior path samples per read (dyn_sample_out) with
+ * the given seed, on the device behind every read's traceback while its lattice is still in place, for every batch or ticket
+ * SUBMITTED while count > 0; 4 x count bytes of device memory per segment row for those batches only. count = 0 ..
+ * DYN_POSTERIOR_SAMPLES_MAX, default 0 = off: nothing is allocated or changed, and every launch is the one it would have been.
+ * DYN_ERR_INVALID_ARGUMENT + message outside that range and for count > 0 on a handle of mode ntk / resquiggle. A job or ticket
+ * started while count > 0 is refused (DYN_ERR_INVALID_ARGUMENT + message) together with dyn_aligner_set_rescale(iters > 0),
+ * dyn_aligner_set_auto_guide(half_width > 0), dyn_aligner_set_guide_rescue(half_width > 0) or a guided batch. Combines with
+ * dyn_aligner_set_border_confidence and the per-segment riders, none of whose outputs it changes. A ticket submitted with
+ * count > 0 takes one launch of its own: neither the resident session nor a merged launch. */
+int dyn_aligner_set_posterior_samples(dyn_aligner* a, int count, uint64_t seed);
 /* (added within ABI 10: a caller that must know looks the symbol up) Per-k-mer level summary of a run. While it is on, every output row (segment) of every read with status 0 of an
  * align(calc_probabilities = 1) batch or ticket SUBMITTED on this handle is added, on the device behind the per-segment
  * kernels, to its k-mer's entry of an accumulator that lives on the handle: six u64 per k-mer code (48 bytes x num_kmers of
@@ -543,6 +583,19 @@ int dyn_format_csv_borders(const dyn_aligner* a, uint64_t n_reads, const dyn_ali
                            const int64_t* last_index, int threads, char* out, uint64_t out_cap,
                            uint64_t* row_begin, uint64_t* row_end);
 
+/* (added within ABI 10) The same with the posterior samples of dyn_batch_fetch_samples as well: after the border columns (if
+ * bd is given) every row gets one field ",{s_0};{s_1};...;{s_K-1}", sm->count integers: sample k's start of that segment in the
+ * unit of the `start` column (the fetched value + sig_offsets[i]; 4294967295 for a dead sample). ev, sc, bd and
+ * sm may each be NULL; sm == NULL: dyn_format_csv_borders / dyn_format_csv_bound_borders, byte for byte. */
+uint64_t dyn_format_csv_bound_samples(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                                      const dyn_score_out* sc, const dyn_border_out* bd, const dyn_sample_out* sm,
+                                      const char* const* readids, const char* const* signalids);
+int dyn_format_csv_samples(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                           const dyn_score_out* sc, const dyn_border_out* bd, const dyn_sample_out* sm, const char* seqs,
+                           const uint64_t* seq_offsets, const char* const* readids, const char* const* signalids,
+                           const int64_t* sig_offsets, const int64_t* last_index, int threads, char* out, uint64_t out_cap,
+                           uint64_t* row_begin, uint64_t* row_end);
+
 /* Closes the gaps between the per-read ranges dyn_format_csv produced: all rows become one contiguous run at the
  * front of `out`, in read order; row_begin/row_end are updated. Returns the total byte count. */
 uint64_t dyn_csv_compact(char* out, uint64_t n_reads, uint64_t* row_begin, uint64_t* row_end);
@@ -591,6 +644,11 @@ int dyn_csv_sink_open_part(const char* csv_zst_path, const char* errors_path, in
  * DYN_ERR_INVALID_ARGUMENT. (0x8, not 0x4: bit 2 stays unassigned, and a sink opened with it is
  * refused as before.) */
 #define DYN_CSV_BORDER_CONFIDENCE 0x8u
+/* (added within ABI 10) DYN_CSV_POSTERIOR_SAMPLES: the header gains ",sample_starts" (after the level, score and border columns,
+ * if any), every row one field: the K sampled starts of its segment, integers joined by ';' (4294967295 for a dead sample); the
+ * sink fetches each ticket's samples after its wait, and a submit whose ticket was submitted with
+ * dyn_aligner_set_posterior_samples off fails with DYN_ERR_INVALID_ARGUMENT. Bit 0x4 and every bit above 0x10 stay refused. */
+#define DYN_CSV_POSTERIOR_SAMPLES 0x10u
 int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int level, int threads, int first, int last,
                          uint32_t flags, dyn_csv_sink** out, char* err, uint64_t errcap);
 #define DYN_ZSTD_FRAME_END "\x01\x00\x00" /* an empty last block (raw, size 0): 3 bytes; the frames carry no checksum */
@@ -716,6 +774,10 @@ int dyn_batch_fetch_scores(dyn_batch* b, dyn_score_out* out);
  * own non-blocking stream. DYN_ERR_INVALID_ARGUMENT (with a message) when the batch was submitted with
  * dyn_aligner_set_border_confidence off, or aligned with calc_probabilities = 0, or out->capacity is too small. */
 int dyn_batch_fetch_borders(dyn_batch* b, dyn_border_out* out);
+/* (added within ABI 10) The posterior path samples of the batch's last align(calc_probabilities = 1) job, copied on the handle's
+ * own non-blocking stream; out->count is set to the batch's K. DYN_ERR_INVALID_ARGUMENT (with a message) when the batch was
+ * submitted with dyn_aligner_set_posterior_samples off, or was a Z-only or train job, or out's capacity, n or count is too small. */
+int dyn_batch_fetch_samples(dyn_batch* b, dyn_sample_out* out);
 /* (ABI 10) Copy the per-read transforms of the last dyn_batch_align (or of a completed ticket, merged launch or not) into
  * `out` (n >= the batch's read count). DYN_ERR_INVALID_ARGUMENT + message for a batch submitted with
  * dyn_aligner_set_rescale(a, 0), or aligned with calc_probabilities = 0. */
