@@ -115,6 +115,9 @@ class AlignBatchResult:
         # posterior path samples (Aligner.set_posterior_samples): sample_starts uint32 [K, cap] (sample k of output row s at
         # [k, s]; DYN_SAMPLE_DEAD in every entry of a dead sample), sample_dead uint32 [n]; None when off
         self.sample_starts = self.sample_dead = None
+        # per-border credible intervals (Aligner.set_border_interval): border_lo / border_hi uint32 [cap], border_mean / border_sd
+        # float64 [cap], indexed like the segment columns; None when off
+        self.border_lo = self.border_hi = self.border_mean = self.border_sd = None
         # band-margin diagnostics (Aligner.set_band_margin): uint32 [n] each, None when off; band_used (uint32 [n]): the band
         # every read's rows come from, only with Aligner.set_band_retry
         self.band_margin_low = self.band_margin_high = self.band_edge_rows = None
@@ -163,6 +166,23 @@ class AlignBatchResult:
             self.sample_dead = np.zeros(self.n, dtype=np.uint32)
         sm = N.DynSampleOut(_ptr(self.sample_starts, N.c_u32_p), _ptr(self.sample_dead, N.c_u32_p), self.cap, self.n, count)
         rc = L.dyn_batch_fetch_samples(handle, C.byref(sm))
+        if rc != N.DYN_OK:
+            _raise(rc, aligner.last_error())
+
+    def _interval_out(self) -> N.DynBorderIntervalOut:
+        return N.DynBorderIntervalOut(_ptr(self.border_lo, N.c_u32_p), _ptr(self.border_hi, N.c_u32_p),
+                                      _ptr(self.border_mean, N.c_double_p), _ptr(self.border_sd, N.c_double_p), self.cap)
+
+    def _fetch_intervals(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
+        """dyn_batch_fetch_intervals into this object's interval columns (allocated on first use), or drop them."""
+        if not wanted:
+            self.border_lo = self.border_hi = self.border_mean = self.border_sd = None
+            return
+        if self.border_lo is None:
+            self.border_lo, self.border_hi = (np.zeros(self.cap, dtype=np.uint32) for _ in range(2))
+            self.border_mean, self.border_sd = (np.zeros(self.cap) for _ in range(2))
+        bi = self._interval_out()
+        rc = L.dyn_batch_fetch_intervals(handle, C.byref(bi))
         if rc != N.DYN_OK:
             _raise(rc, aligner.last_error())
 
@@ -252,6 +272,9 @@ class AlignBatchResult:
             d["border_window_probability"] = self.border_window_probability[a:b].copy()
         if self.sample_starts is not None:  # only when requested (Aligner.set_posterior_samples): [K, n_segments]
             d["sample_starts"] = self.sample_starts[:, a:b].copy()
+        if self.border_lo is not None:  # only when requested (Aligner.set_border_interval)
+            for key in ("border_lo", "border_hi", "border_mean", "border_sd"):
+                d[key] = getattr(self, key)[a:b].copy()
         if self.rescale_shift is not None:  # only when requested (Aligner.set_rescale)
             d["rescale_shift"] = float(self.rescale_shift[i])
             d["rescale_scale"] = float(self.rescale_scale[i])
@@ -306,13 +329,15 @@ def format_csv(aligner: "Aligner", res: AlignBatchResult, sequences: Sequence[st
     if res.sample_starts is not None:
         sm = C.byref(N.DynSampleOut(_ptr(res.sample_starts, N.c_u32_p), _ptr(res.sample_dead, N.c_u32_p), res.cap, res.n,
                                     res.sample_starts.shape[0]))
-    cap = int(L.dyn_format_csv_bound_samples(aligner._h, n, C.byref(res._c), ev, sc, bd, sm, rid, sid))
+    # ... and the credible intervals (Aligner.set_border_interval): four more after those
+    bi = C.byref(res._interval_out()) if res.border_lo is not None else None
+    cap = int(L.dyn_format_csv_bound_intervals(aligner._h, n, C.byref(res._c), ev, sc, bd, sm, bi, rid, sid))
     # one grow-only buffer per handle: first-touch page faults of a fresh 350 MB buffer cost ~100x
     # the formatting itself (15 ms per 1 024-read batch with warm pages)
     buf = getattr(aligner, "_csv_buf", None)
     if buf is None or buf.size < cap:
         buf = aligner._csv_buf = np.empty(max(cap, 1), dtype=np.uint8)
-    rc = L.dyn_format_csv_samples(aligner._h, n, C.byref(res._c), ev, sc, bd, sm, seqs, _ptr(seq_off, N.c_u64_p), rid, sid,
+    rc = L.dyn_format_csv_intervals(aligner._h, n, C.byref(res._c), ev, sc, bd, sm, bi, seqs, _ptr(seq_off, N.c_u64_p), rid, sid,
                           so.ctypes.data_as(C.POINTER(C.c_int64)), li.ctypes.data_as(C.POINTER(C.c_int64)),
                           int(threads), buf.ctypes.data, cap, _ptr(begin, N.c_u64_p), _ptr(end, N.c_u64_p))
     if rc != N.DYN_OK:
@@ -434,6 +459,7 @@ class Batch:
         self._scores = bool(calc_probabilities) and self._al._segment_scores > 0
         self._borders = bool(calc_probabilities) and self._al._border_confidence > 0
         self._samples = self._al._ticket_samples(bool(calc_probabilities))
+        self._intervals = self._al._ticket_intervals(bool(calc_probabilities))
         self._margins = bool(calc_probabilities) and self._al._band_margin
         self._rescued = self._al._ticket_rescue(bool(calc_probabilities))
         rc = self._L.dyn_batch_align(self._h, int(bool(calc_probabilities)))
@@ -510,6 +536,7 @@ class Batch:
         out._fetch_scores(self._L, self._h, self._al, getattr(self, "_scores", False))
         out._fetch_borders(self._L, self._h, self._al, getattr(self, "_borders", False))
         out._fetch_samples(self._L, self._h, self._al, getattr(self, "_samples", 0))
+        out._fetch_intervals(self._L, self._h, self._al, getattr(self, "_intervals", False))
         out._fetch_band_margin(self._L, self._h, self._al, getattr(self, "_margins", False))
         out._fetch_rescue(self._L, self._h, self._al, getattr(self, "_rescued", False))
         return out
@@ -535,6 +562,12 @@ class Batch:
     def fetch_samples(self, out: N.DynSampleOut) -> None:
         """dyn_batch_fetch_samples into caller-owned arrays (raises ValueError for a batch that did not ask)."""
         rc = self._L.dyn_batch_fetch_samples(self._h, C.byref(out))
+        if rc != N.DYN_OK:
+            _raise(rc, self._al.last_error())
+
+    def fetch_intervals(self, out: N.DynBorderIntervalOut) -> None:
+        """dyn_batch_fetch_intervals into caller-owned arrays (raises ValueError for a batch that did not ask)."""
+        rc = self._L.dyn_batch_fetch_intervals(self._h, C.byref(out))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
 
@@ -604,7 +637,7 @@ class AsyncBatch:
 
     def __init__(self, aligner: "Aligner", handle, result, keep, levels: bool = False, rescale: bool = False,
                  scores: bool = False, borders: bool = False, margins: bool = False, auto_guide=None, rescue: bool = False,
-                 samples: int = 0):
+                 samples: int = 0, intervals: bool = False):
         self._al = aligner
         self._L = N.lib()
         self._h = handle
@@ -616,6 +649,7 @@ class AsyncBatch:
         self._scores = scores  # ... with the segment-scores switch on
         self._borders = borders  # ... with the border-confidence switch on
         self._samples = samples  # ... with the posterior-samples switch on: its count
+        self._intervals = intervals  # ... with the border-interval switch on
         self._margins = margins  # ... with the band-margin switch on (tickets report margins; they are never retried)
         # ... with the auto-guide switch on (Aligner.set_auto_guide): (alignments per read, the ticket's sample offsets), else None
         self._auto_guide = auto_guide
@@ -634,6 +668,7 @@ class AsyncBatch:
                 self.result._fetch_scores(self._L, self._h, self._al, self._scores)
                 self.result._fetch_borders(self._L, self._h, self._al, self._borders)
                 self.result._fetch_samples(self._L, self._h, self._al, self._samples)
+                self.result._fetch_intervals(self._L, self._h, self._al, self._intervals)
                 self.result._fetch_band_margin(self._L, self._h, self._al, self._margins)
                 # a result object refilled from an earlier ticket must not keep that ticket's counts
                 self.result.guide_rounds = self.result.guide_converged = self.result.guides = None
@@ -660,6 +695,7 @@ class AsyncBatch:
     fetch_scores = Batch.fetch_scores
     fetch_borders = Batch.fetch_borders
     fetch_samples = Batch.fetch_samples
+    fetch_intervals = Batch.fetch_intervals
     fetch_band_margin = Batch.fetch_band_margin
 
     def timing(self) -> dict:
@@ -764,6 +800,7 @@ class Aligner:
     _segment_scores = 0  # set_segment_scores
     _border_confidence = 0  # set_border_confidence
     _posterior_samples = (0, 0)  # set_posterior_samples: (count, seed)
+    _border_interval = 0.0  # set_border_interval: the mass
     _band_margin = False  # set_band_margin
     _auto_guide = (0, 8)  # set_auto_guide: (half_width, refine)
     _band_retry = None  # set_band_retry: (min_margin, max_band, factor)
@@ -899,6 +936,24 @@ class Aligner:
             _raise(rc, self.last_error())
         self._border_confidence = int(window)
 
+    def set_border_interval(self, mass: float) -> None:
+        """dyn_aligner_set_border_interval: align(calc_probabilities=True) jobs submitted while ``mass`` (0.01 .. 0.999) > 0 also
+        compute, on the GPU from every read's own lattice, the credible interval and the spread of every segment's start
+        (INTEGRATION.md section 3): ``AlignBatchResult.border_lo`` / ``.border_hi`` (uint32 ``[cap]``: the quantiles
+        ``(1 - mass) / 2`` and ``1 - (1 - mass) / 2`` of the posterior over the start, signal positions like
+        ``signal_positions``) and ``.border_mean`` / ``.border_sd`` (float64 ``[cap]``); ``read(i)`` gains the four keys.
+        ``mass = 0`` (the default) is off. A job started with ``set_border_confidence``, ``set_posterior_samples``,
+        ``set_auto_guide`` or ``set_guide_rescue`` on as well, or on a guided batch, is refused (ValueError); with
+        ``set_rescale`` the values are the last pass's. ``MultiAligner`` has no such switch."""
+        rc = self._L.dyn_aligner_set_border_interval(self._h, float(mass))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        self._border_interval = float(mass)
+
+    def _ticket_intervals(self, calc_probabilities: bool) -> bool:
+        """whether an align job / ticket submitted now carries the interval columns"""
+        return bool(calc_probabilities) and self._border_interval > 0 and self._ctor[2] not in ("ntk", "resquiggle")
+
     def set_posterior_samples(self, count: int, seed: int = 0) -> None:
         """dyn_aligner_set_posterior_samples: align(calc_probabilities=True) jobs submitted while ``count`` (0 .. 64) > 0 also
         draw ``count`` complete alignments of every read from the posterior distribution over alignments, on the GPU from the
@@ -1033,12 +1088,14 @@ class Aligner:
         al.set_rescale(self._rescale)
         al.set_segment_scores(self._segment_scores)
         al.set_border_confidence(self._border_confidence)
+        al.set_border_interval(self._border_interval)
         al.set_band_margin(True)
         return al
 
     # per-row and per-read columns a retried read's entries are spliced into (those that are on)
     _ROW_COLUMNS = ("sequence_positions", "signal_positions", "probabilities", "states", "level_mean", "level_stdv", "level_median",
-                    "median_delta", "mad_delta", "homogeneity", "border_probability", "border_window_probability")
+                    "median_delta", "mad_delta", "homogeneity", "border_probability", "border_window_probability",
+                    "border_lo", "border_hi", "border_mean", "border_sd")
     _READ_COLUMNS = ("Z", "rescale_shift", "rescale_scale", "rescale_iters", "band_margin_low", "band_margin_high", "band_edge_rows")
 
     def _retry_bands(self, res: AlignBatchResult, signals: Sequence, sequences: Sequence[str]) -> None:
@@ -1182,7 +1239,8 @@ class Aligner:
                           margins=self._band_margin and bool(calc_probabilities),
                           auto_guide=self._ticket_guide(bool(calc_probabilities), sig_off),
                           rescue=self._ticket_rescue(bool(calc_probabilities)),
-                          samples=self._ticket_samples(bool(calc_probabilities)))
+                          samples=self._ticket_samples(bool(calc_probabilities)),
+                          intervals=self._ticket_intervals(bool(calc_probabilities)))
 
     def _raw_args(self, raw, shift, scale, calibration=None):
         scattered = isinstance(raw, (list, tuple))
@@ -1239,7 +1297,8 @@ class Aligner:
                           margins=self._band_margin and bool(calc_probabilities),
                           auto_guide=self._ticket_guide(bool(calc_probabilities), raw_off),
                           rescue=self._ticket_rescue(bool(calc_probabilities)),
-                          samples=self._ticket_samples(bool(calc_probabilities)))
+                          samples=self._ticket_samples(bool(calc_probabilities)),
+                          intervals=self._ticket_intervals(bool(calc_probabilities)))
 
     def align_vbz_async(self, chunks, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 3,
                         n_sigmas: float = 3.0, f32: bool = False, calc_probabilities: bool = True,
@@ -1280,7 +1339,8 @@ class Aligner:
                           margins=self._band_margin and bool(calc_probabilities),
                           auto_guide=self._ticket_guide(bool(calc_probabilities), raw_off),
                           rescue=self._ticket_rescue(bool(calc_probabilities)),
-                          samples=self._ticket_samples(bool(calc_probabilities)))
+                          samples=self._ticket_samples(bool(calc_probabilities)),
+                          intervals=self._ticket_intervals(bool(calc_probabilities)))
 
     def train_raw_async(self, raw, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 7,
                         n_sigmas: float = 5.0, f32: bool = True, pooled: bool = False,

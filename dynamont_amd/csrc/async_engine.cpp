@@ -155,7 +155,7 @@ static bool mergeable(const dyn_batch* x) {
 }
 static bool same_kind(const dyn_batch* x, const dyn_batch* y) {
   if (x->job != y->job || x->has_raw != y->has_raw || x->ev_want != y->ev_want || x->rs_want != y->rs_want || x->sc_want != y->sc_want ||
-      x->bc_want != y->bc_want)
+      x->bc_want != y->bc_want || x->bi_want != y->bi_want)
     return false;
   if (!x->has_raw) return true;
   const RawSource &p = x->raw_src, &q = y->raw_src;
@@ -219,6 +219,7 @@ std::shared_ptr<BatchGroup> Pipeline::merge(const std::vector<dyn_batch*>& ticke
   g->rs_want = first->rs_want;
   g->sc_want = first->sc_want;
   g->bc_want = first->bc_want;
+  g->bi_want = first->bi_want;
   // the per-k-mer summary is snapshot per ticket and same_kind does not look at it: the launch sums the members that asked
   for (dyn_batch* t : tickets) {
     if (!t->ks_want || !t->n) continue;
@@ -817,6 +818,15 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
       return DYN_ERR_INVALID_ARGUMENT;
     }
   }
+  // credible intervals (dyn_aligner_set_border_interval): as run_job_sync refuses them
+  const double bi = (job == DynJob::AlignFull && !a->ntk) ? a->border_interval : 0.0;
+  if (bi > 0) {
+    if (const char* other = border_interval_conflict(a)) {
+      std::lock_guard<std::mutex> elk(a->err_mu);
+      a->last_error = std::string("dyn_batch_align_async: dyn_aligner_set_border_interval is on, which does not combine with ") + other;
+      return DYN_ERR_INVALID_ARGUMENT;
+    }
+  }
   dyn_batch* b = new dyn_batch();
   b->a = a;
   attach_cache(b);
@@ -834,6 +844,7 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
   b->bm_want = a->band_margin;
   b->sc_want = a->segment_scores;
   b->bc_want = a->border_confidence;
+  b->bi_want = bi;
   b->ps_want = ps;
   b->ps_seed = a->sample_seed;
   b->in_signals = signals;

@@ -100,6 +100,7 @@ struct Args {
   const dyn_score_out* sc;  // nullptr: no segment-score columns
   const dyn_border_out* bd;  // nullptr: no border-confidence columns
   const dyn_sample_out* sm;  // nullptr: no posterior-sample column
+  const dyn_border_interval_out* bi;  // nullptr: no border-interval columns
   const char* seqs;
   const uint64_t* seq_offsets;
   const char* const* readids;
@@ -141,6 +142,13 @@ uint64_t read_bound(const Args& a, uint64_t i) {
       b += event_value_bound(a.bd->border_probability[s]) + event_value_bound(a.bd->border_window_probability[s]);
   }
   if (a.sm) b += n * (1 + 21 * (uint64_t)a.sm->count);  // the comma; per sample an integer (<= 20 characters) and its ';'
+  if (a.bi) {
+    const uint64_t o = a.res->seg_offsets[i];
+    b += n * (4 + 2 * 20);  // the commas and two integers (<= 20 characters each)
+    for (uint64_t s = o; s < o + n; ++s)
+      // (the mean is written with the read's offset added, an int64: 20 integer digits at most below 1e15 + 2^63)
+      b += (std::fabs(a.bi->border_mean[s]) < 1e15 ? kEventSmallBound + 4 : kEventValueBound) + event_value_bound(a.bi->border_sd[s]);
+  }
   return b;
 }
 
@@ -207,6 +215,16 @@ char* format_read(const Args& a, uint64_t i, char* p) {
         p = put_int(p, v == 0xFFFFFFFFu ? (int64_t)v : (int64_t)v + a.sig_offsets[i]);  // the `start` column's unit; dead as it is
       }
     }
+    if (a.bi) {  // the `start` column's unit: the fetched positions + the read's offset; the spread is a length
+      *p++ = ',';
+      p = put_int(p, (int64_t)a.bi->border_lo[o + s] + a.sig_offsets[i]);
+      *p++ = ',';
+      p = put_int(p, (int64_t)a.bi->border_hi[o + s] + a.sig_offsets[i]);
+      *p++ = ',';
+      p = put_prob6<true>(p, a.bi->border_mean[o + s] + (double)a.sig_offsets[i]);
+      *p++ = ',';
+      p = put_prob6<true>(p, a.bi->border_sd[o + s]);
+    }
     *p++ = '\n';
   }
   return p;
@@ -240,11 +258,19 @@ extern "C" uint64_t dyn_format_csv_bound_borders(const dyn_aligner* a, uint64_t 
 extern "C" uint64_t dyn_format_csv_bound_samples(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
                                                  const dyn_event_out* ev, const dyn_score_out* sc, const dyn_border_out* bd,
                                                  const dyn_sample_out* sm, const char* const* readids, const char* const* signalids) {
+  return dyn_format_csv_bound_intervals(a, n_reads, res, ev, sc, bd, sm, nullptr, readids, signalids);
+}
+
+extern "C" uint64_t dyn_format_csv_bound_intervals(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
+                                                   const dyn_event_out* ev, const dyn_score_out* sc, const dyn_border_out* bd,
+                                                   const dyn_sample_out* sm, const dyn_border_interval_out* bi,
+                                                   const char* const* readids, const char* const* signalids) {
+  if (bi && (!bi->border_lo || !bi->border_hi || !bi->border_mean || !bi->border_sd)) return 0;
   if (!a || !res || (ev && (!ev->mean || !ev->stdev || !ev->median)) ||
       (sc && (!sc->median_delta || !sc->mad_delta || !sc->homogeneity)) ||
       (bd && (!bd->border_probability || !bd->border_window_probability)) || (sm && !sm->sample_start))
     return 0;
-  Args args{0, 0, res, ev, sc, bd, sm, nullptr, nullptr, readids, signalids, nullptr, nullptr};
+  Args args{0, 0, res, ev, sc, bd, sm, bi, nullptr, nullptr, readids, signalids, nullptr, nullptr};
   uint64_t total = 0;
   for (uint64_t i = 0; i < n_reads; ++i) total += read_bound(args, i);
   return total;
@@ -292,6 +318,17 @@ extern "C" int dyn_format_csv_samples(const dyn_aligner* a, uint64_t n_reads, co
                                       const char* const* readids, const char* const* signalids, const int64_t* sig_offsets,
                                       const int64_t* last_index, int threads, char* out, uint64_t out_cap, uint64_t* row_begin,
                                       uint64_t* row_end) {
+  return dyn_format_csv_intervals(a, n_reads, res, ev, sc, bd, sm, nullptr, seqs, seq_offsets, readids, signalids, sig_offsets, last_index,
+                                  threads, out, out_cap, row_begin, row_end);
+}
+
+extern "C" int dyn_format_csv_intervals(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
+                                        const dyn_event_out* ev, const dyn_score_out* sc, const dyn_border_out* bd,
+                                        const dyn_sample_out* sm, const dyn_border_interval_out* bi, const char* seqs,
+                                        const uint64_t* seq_offsets, const char* const* readids, const char* const* signalids,
+                                        const int64_t* sig_offsets, const int64_t* last_index, int threads, char* out,
+                                        uint64_t out_cap, uint64_t* row_begin, uint64_t* row_end) {
+  if (bi && (!bi->border_lo || !bi->border_hi || !bi->border_mean || !bi->border_sd)) return DYN_ERR_INVALID_ARGUMENT;
   if (sm && !sm->sample_start) return DYN_ERR_INVALID_ARGUMENT;
   if (!a || !res || !res->status || !res->n_segments || !res->seg_offsets || !res->sequence_positions ||
       !res->signal_positions || !res->probabilities || !out || !row_begin || !row_end ||
@@ -301,7 +338,7 @@ extern "C" int dyn_format_csv_samples(const dyn_aligner* a, uint64_t n_reads, co
   dyn_info info;
   dyn_aligner_info(a, &info);
   if (info.kmer_size > 31) return DYN_ERR_INVALID_ARGUMENT;
-  Args args{info.kmer_size, info.rna, res, ev, sc, bd, sm, seqs, seq_offsets, readids, signalids, sig_offsets, last_index};
+  Args args{info.kmer_size, info.rna, res, ev, sc, bd, sm, bi, seqs, seq_offsets, readids, signalids, sig_offsets, last_index};
   // every read formats straight into its own worst-case slot of the caller's buffer: no allocation,
   // no shared cache lines between threads
   uint64_t pos = 0;

@@ -45,6 +45,7 @@ const char kHeaderEvents[] =
 const char kHeaderScores[] = ",median_delta,mad_delta,homogeneity";
 const char kHeaderBorders[] = ",border_probability,border_window_probability";
 const char kHeaderSamples[] = ",sample_starts";
+const char kHeaderIntervals[] = ",border_lo,border_hi,border_mean,border_sd";
 
 struct Blob {  // the formatted rows of one batch; freed when its last job has been compressed
   std::unique_ptr<char[]> data;
@@ -86,6 +87,7 @@ int batch_check_events(dyn_batch* b);
 int batch_check_scores(dyn_batch* b);
 int batch_check_borders(dyn_batch* b);
 int batch_check_samples(dyn_batch* b);
+int batch_check_intervals(dyn_batch* b);
 uint32_t batch_sample_count(const dyn_batch* b);  // the ticket's K
 }
 
@@ -114,6 +116,8 @@ struct dyn_csv_sink {
   std::vector<double> bd_cols;                // [2][capacity] the batch's border confidence (dyn_batch_fetch_borders)
   bool samples = false;                       // DYN_CSV_POSTERIOR_SAMPLES
   std::vector<uint32_t> sm_cols;              // [K][capacity] the batch's sample starts, then [n] its dead counts (dyn_batch_fetch_samples)
+  bool intervals = false;                     // DYN_CSV_BORDER_INTERVAL
+  std::vector<double> bi_cols;                // [2][capacity] f64 mean / sd, then [2][capacity] u32 lo / hi (dyn_batch_fetch_intervals)
   std::thread t_sink, t_writer;
   std::vector<std::thread> t_comp;
   std::vector<std::shared_ptr<Blob>> spare;  // recycled row buffers (first-touch page faults cost more than formatting)
@@ -322,7 +326,20 @@ struct dyn_csv_sink {
       }
     }
     const dyn_sample_out* smp = samples ? &sm : nullptr;
-    const uint64_t bound = dyn_format_csv_bound_samples(it.a, it.n, it.res, evp, scp, bdp, smp, it.readids, it.signalids);
+    dyn_border_interval_out bi{};
+    if (intervals) {
+      const uint64_t cap = it.res->seg_offsets ? it.res->seg_offsets[it.n] : 0;
+      bi_cols.resize(std::max<uint64_t>(1, 3 * cap));
+      uint32_t* q = reinterpret_cast<uint32_t*>(bi_cols.data() + 2 * cap);
+      bi = dyn_border_interval_out{q, q + cap, bi_cols.data(), bi_cols.data() + cap, cap};
+      if (dyn_batch_fetch_intervals(it.ticket, &bi) != DYN_OK) {
+        std::lock_guard<std::mutex> lk(m);
+        fail(std::string("batch border intervals: ") + dyn_aligner_last_error(it.a));
+        return;
+      }
+    }
+    const dyn_border_interval_out* bip = intervals ? &bi : nullptr;
+    const uint64_t bound = dyn_format_csv_bound_intervals(it.a, it.n, it.res, evp, scp, bdp, smp, bip, it.readids, it.signalids);
     std::shared_ptr<Blob> blob;
     {
       std::lock_guard<std::mutex> lk(m);
@@ -340,7 +357,7 @@ struct dyn_csv_sink {
       if (spare.size() < 4) spare.push_back(blob);
     }
     const double c2 = now_ms();
-    const int frc = dyn_format_csv_samples(it.a, it.n, it.res, evp, scp, bdp, smp, it.seqs, it.seq_offsets, it.readids, it.signalids, it.sig_offsets,
+    const int frc = dyn_format_csv_intervals(it.a, it.n, it.res, evp, scp, bdp, smp, bip, it.seqs, it.seq_offsets, it.readids, it.signalids, it.sig_offsets,
                                           last_index.data(), std::min(threads, 8), blob->data.get(), blob->cap, begin.data(), end.data());
     if (frc != DYN_OK) {
       std::lock_guard<std::mutex> lk(m);
@@ -387,6 +404,7 @@ struct dyn_csv_sink {
       if (scores) text.insert(text.size() - 1, kHeaderScores);  // before the newline
       if (borders) text.insert(text.size() - 1, kHeaderBorders);
       if (samples) text.insert(text.size() - 1, kHeaderSamples);
+      if (intervals) text.insert(text.size() - 1, kHeaderIntervals);
       const size_t len = text.size();
       hdr->cap = len + 1;
       hdr->data.reset(new char[hdr->cap]);
@@ -446,7 +464,7 @@ int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int 
   };
   if (!csv_zst_path || !errors_path || !out) return DYN_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  if (flags & ~(DYN_CSV_EVENT_STATS | DYN_CSV_SEGMENT_SCORES | DYN_CSV_BORDER_CONFIDENCE | DYN_CSV_POSTERIOR_SAMPLES)) {
+  if (flags & ~(DYN_CSV_EVENT_STATS | DYN_CSV_SEGMENT_SCORES | DYN_CSV_BORDER_CONFIDENCE | DYN_CSV_POSTERIOR_SAMPLES | DYN_CSV_BORDER_INTERVAL)) {
     put("dyn_csv_sink_open_ex: unknown flags");
     return DYN_ERR_INVALID_ARGUMENT;
   }
@@ -471,6 +489,7 @@ int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int 
   s->scores = (flags & DYN_CSV_SEGMENT_SCORES) != 0;
   s->borders = (flags & DYN_CSV_BORDER_CONFIDENCE) != 0;
   s->samples = (flags & DYN_CSV_POSTERIOR_SAMPLES) != 0;
+  s->intervals = (flags & DYN_CSV_BORDER_INTERVAL) != 0;
   dyn_csv_sink* p = s.release();
   for (int t = 0; t < p->threads; ++t) p->t_comp.emplace_back([p] { p->compress_loop(); });
   p->t_writer = std::thread([p] { p->writer_loop(); });
@@ -499,6 +518,8 @@ int dyn_csv_sink_submit_bases(dyn_csv_sink* s, dyn_aligner* a, dyn_batch* ticket
     if (int rc = dyneng::batch_check_borders(ticket)) return rc;
   if (s->samples)
     if (int rc = dyneng::batch_check_samples(ticket)) return rc;
+  if (s->intervals)
+    if (int rc = dyneng::batch_check_intervals(ticket)) return rc;
   {
     std::lock_guard<std::mutex> lk(s->m);
     if (s->closing) return DYN_ERR_INVALID_ARGUMENT;

@@ -60,7 +60,7 @@ void attach_cache(dyn_batch* b) {
   dyneng::BufCache* c = &b->a->cache;
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_ps, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bi, &b->d_ps, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
                     &b->d_resc_st, &b->d_resc_pp, &b->d_resc_pathn, &b->d_resc_segrow})
     d->cache = c;
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref, &b->h_resc}) h->cache = c;
@@ -571,6 +571,19 @@ int dyn_aligner_set_border_confidence(dyn_aligner* a, int window) {
   return DYN_OK;
 }
 
+int dyn_aligner_set_border_interval(dyn_aligner* a, double mass) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  if (!(mass == 0.0 || (mass >= DYN_BORDER_INTERVAL_MIN_MASS && mass <= DYN_BORDER_INTERVAL_MAX_MASS))) {
+    char num[64];
+    std::snprintf(num, sizeof num, "%g", mass);
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = std::string("dyn_aligner_set_border_interval: mass must be 0 or 0.01 .. 0.999, got ") + num;
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  a->border_interval = mass;
+  return DYN_OK;
+}
+
 int dyn_aligner_set_posterior_samples(dyn_aligner* a, int count, uint64_t seed) {
   if (!a) return DYN_ERR_INVALID_ARGUMENT;
   auto fail = [&](const std::string& msg) {
@@ -970,7 +983,7 @@ void dyn_batch_destroy(dyn_batch* b) {
   }
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_ps, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
+                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bi, &b->d_ps, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
                     &b->d_resc_st, &b->d_resc_pp, &b->d_resc_pathn, &b->d_resc_segrow})
     d->release();
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref, &b->h_resc}) h->release();
@@ -1199,6 +1212,20 @@ int run_job_sync(dyn_batch* b, DynJob job, bool guided_train = false) {
       return DYN_ERR_INVALID_ARGUMENT;
     }
   }
+  // credible intervals (dyn_aligner_set_border_interval) concern align jobs with probabilities: a summary of every column of the
+  // read's lattice in the diagonal band, the one lattice phase of its launch
+  const double bi = (job == DynJob::AlignFull && !a->ntk) ? a->border_interval : 0.0;
+  if (bi > 0) {
+    if (b->guided) {
+      a->last_error = "dyn_batch_align: the batch carries a guide (dyn_batch_set_guide / dyn_batch_auto_guide), which does not combine with "
+                      "dyn_aligner_set_border_interval(a, mass > 0)";
+      return DYN_ERR_INVALID_ARGUMENT;
+    }
+    if (const char* other = border_interval_conflict(a)) {
+      a->last_error = std::string("dyn_batch_align: dyn_aligner_set_border_interval is on, which does not combine with ") + other;
+      return DYN_ERR_INVALID_ARGUMENT;
+    }
+  }
   // the guide rescue (dyn_aligner_set_guide_rescue) concerns align jobs with probabilities; the Z-only and the train job ignore it
   const uint32_t gr_hw = (job == DynJob::AlignFull && !a->ntk) ? a->rescue_hw : 0u;
   if (gr_hw) {
@@ -1225,6 +1252,7 @@ int run_job_sync(dyn_batch* b, DynJob job, bool guided_train = false) {
     b->bm_want = a->band_margin;
     b->sc_want = a->segment_scores;
     b->bc_want = a->border_confidence;
+    b->bi_want = bi;
     b->ps_want = a->posterior_samples;
     b->ps_seed = a->sample_seed;
     rc = enqueue_job(b, job);
@@ -1497,6 +1525,13 @@ int batch_check_borders(dyn_batch* b) {
                      "submitted without dyn_aligner_set_border_confidence(a, window > 0) or with calc_probabilities = 0";
   return DYN_ERR_INVALID_ARGUMENT;
 }
+int batch_check_intervals(dyn_batch* b) {
+  if (b->bi_want > 0 && b->job == DynJob::AlignFull) return DYN_OK;
+  std::lock_guard<std::mutex> lk(b->a->err_mu);
+  b->a->last_error = "dyn_csv_sink_submit: the sink writes the border intervals (DYN_CSV_BORDER_INTERVAL) and this ticket was "
+                     "submitted without dyn_aligner_set_border_interval(a, mass > 0) or with calc_probabilities = 0";
+  return DYN_ERR_INVALID_ARGUMENT;
+}
 uint32_t batch_sample_count(const dyn_batch* b) { return (uint32_t)b->ps_want; }
 int batch_check_samples(dyn_batch* b) {
   if (b->ps_want && b->job == DynJob::AlignFull) return DYN_OK;
@@ -1538,6 +1573,34 @@ int dyn_batch_fetch_samples(dyn_batch* b, dyn_sample_out* out) {
   }
   if (b->n) HIP_TRY(a, copy_out(a, out->sample_dead, d + (uint64_t)b->ps_ready * b->capacity, b->n * 4));
   out->count = (uint32_t)b->ps_ready;
+  return DYN_OK;
+}
+
+int dyn_batch_fetch_intervals(dyn_batch* b, dyn_border_interval_out* out) {
+  if (!b || !out || !out->border_lo || !out->border_hi || !out->border_mean || !out->border_sd) return DYN_ERR_INVALID_ARGUMENT;
+  dyn_aligner* a = b->a;
+  // a member of a merged launch: rows [g_seg0, g_seg0 + capacity) of the group's columns (dyn_batch_fetch)
+  const dyn_batch* src = (b->group && b->group->g) ? b->group->g : b;
+  const uint64_t seg0 = src == b ? 0 : b->g_seg0;
+  if (!b->aligned || !b->last_calc || !src->bi_ready) {
+    a->last_error = !b->aligned || !b->last_calc
+                        ? "dyn_batch_fetch_intervals: the batch was not aligned with calc_probabilities = 1"
+                        : "dyn_batch_fetch_intervals: the batch was submitted without dyn_aligner_set_border_interval(a, mass > 0)";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  if (out->capacity < b->capacity) {
+    a->last_error = "dyn_border_interval_out.capacity is smaller than dyn_segment_capacity()";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  int rc = need_device(a);
+  if (rc != DYN_OK) return rc;
+  if (!b->capacity) return DYN_OK;
+  const double* e = src->d_bi.as<double>();
+  const uint32_t* q = reinterpret_cast<const uint32_t*>(e + 2 * src->capacity);
+  HIP_TRY(a, copy_out(a, out->border_mean, e + seg0, b->capacity * 8));
+  HIP_TRY(a, copy_out(a, out->border_sd, e + src->capacity + seg0, b->capacity * 8));
+  HIP_TRY(a, copy_out(a, out->border_lo, q + seg0, b->capacity * 4));
+  HIP_TRY(a, copy_out(a, out->border_hi, q + src->capacity + seg0, b->capacity * 4));
   return DYN_OK;
 }
 

@@ -155,6 +155,7 @@ struct dyn_aligner {
   bool kmer_summary = false;  // dyn_aligner_set_kmer_summary: read by every batch / ticket at its submission
   int segment_scores = 0;     // dyn_aligner_set_segment_scores (window, 0 = off): read by every batch / ticket at its submission
   int border_confidence = 0;  // dyn_aligner_set_border_confidence (window, 0 = off): read by every batch / ticket at its submission
+  double border_interval = 0; // dyn_aligner_set_border_interval (mass, 0 = off): read by every batch / ticket at its submission
   int posterior_samples = 0;  // dyn_aligner_set_posterior_samples (count, 0 = off): read by every batch / ticket at its submission
   uint64_t sample_seed = 0;   // ... and its seed
   bool band_margin = false;   // dyn_aligner_set_band_margin: read by every batch / ticket at its submission
@@ -265,6 +266,9 @@ struct dyn_batch {
   dyneng::DevBuf d_bc;                         // [2][capacity] border_probability / border_window_probability (border_kernels.hpp)
   int bc_want = 0;                             // the handle's border-confidence window when this batch / ticket was submitted
   bool bc_ready = false;                       // the last job computed the border columns into d_bc
+  dyneng::DevBuf d_bi;                         // [capacity] f64 mean | [capacity] f64 sd | [capacity] u32 lo | [capacity] u32 hi (interval_kernels.hpp)
+  double bi_want = 0;                          // the handle's border-interval mass when this batch / ticket was submitted (0: off)
+  bool bi_ready = false;                       // the last job computed the interval columns into d_bi
   dyneng::DevBuf d_ps;                         // [ps_want][capacity] u32 sample starts | [n] u32 dead samples (sample_kernels.hpp)
   int ps_want = 0;                             // the handle's posterior-sample count when this batch / ticket was submitted
   uint64_t ps_seed = 0;                        // ... and its seed

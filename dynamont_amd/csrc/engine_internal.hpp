@@ -56,5 +56,14 @@ inline const char* posterior_samples_conflict(const dyn_aligner* a) {
   if (a->rescue_hw > 0) return "dyn_aligner_set_guide_rescue(a, half_width > 0)";
   return nullptr;
 }
+// likewise for dyn_aligner_set_border_interval: one lattice phase runs per launch for now (an INTERIM), and the
+// switches that align a read inside a guide window have no diagonal lattice to offer
+inline const char* border_interval_conflict(const dyn_aligner* a) {
+  if (a->border_confidence > 0) return "dyn_aligner_set_border_confidence(a, window > 0)";
+  if (a->posterior_samples > 0) return "dyn_aligner_set_posterior_samples(a, count > 0)";
+  if (a->auto_guide_hw > 0) return "dyn_aligner_set_auto_guide(a, half_width > 0)";
+  if (a->rescue_hw > 0) return "dyn_aligner_set_guide_rescue(a, half_width > 0)";
+  return nullptr;
+}
 
 }  // namespace dyneng

@@ -619,6 +619,15 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     bc_cols = b->d_bc.as<double>();
     b->bc_ready = true;
   }
+  // credible intervals: [mean | sd] f64 and [lo | hi] u32 x capacity in one buffer, zeroed here (rows of reads that fail keep the
+  // zeros), written by the read queue / the banded-lattice kernel of the LAST pass behind every read
+  b->bi_ready = false;
+  const bool bi_on = calc && b->bi_want > 0;
+  if (bi_on) {
+    HIP_TRY(a, b->d_bi.ensure(std::max<uint64_t>(24, b->capacity * 24)));
+    if (b->capacity) HIP_TRY(a, hipMemsetAsync(b->d_bi.p, 0, b->capacity * 24, a->stream));
+    b->bi_ready = true;
+  }
   // posterior path samples: [count][capacity] segment starts, then the per-read count of dead samples, zeroed here (rows of reads
   // that fail keep the zeros), written by the read queue / the banded-lattice kernel behind every read. (The callers refuse the
   // switches that would make this more than one pass.)
@@ -649,6 +658,10 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       q.lpe_dense = 1;  // the border phase reads whole windows of LPE (the kernel variant that carries it stores densely anyway)
       q.border_p = bc_cols;
       q.border_window_p = bc_cols + b->capacity;
+    }
+    if (bi_on && pass + 1 == n_pass) {  // (the callers refuse the border confidence and the samples beside it)
+      q.interval = dynk::IntervalOut{b->d_bi.as<double>(), b->capacity, (1.0 - b->bi_want) / 2, 0};
+      q.lpe_dense = 1;  // the phase reads whole columns of LPE (the kernel variant that carries it stores densely anyway)
     }
     if (pass == 0) HIP_TRY(a, hipEventRecord(ev[0], a->stream));
     dynk::launch_read_queue(qjob, n_strict != 0, q, a->n_cus, a->stream);
@@ -681,7 +694,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       ba.guide = b->guided ? b->d_guide.as<int32_t>() : nullptr;  // null: the diagonal window
       ba.st = q.st;
       ba.tb = q.tb;
-      ba.tr = q.tr;  // (an align job: the posterior samples, which share the place)
+      ba.tr = q.tr;  // (an align job: the posterior samples or the credible intervals, which share the place)
       ba.head = arena_buf.as<uint32_t>();
       ba.arena = arena_buf.as<char>() + 256;
       ba.arena_bytes = wide_arena;

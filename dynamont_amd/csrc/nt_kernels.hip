@@ -52,6 +52,7 @@
 #include "border_kernels.hpp"
 #include "dp_cell.hpp"
 #include "dp_math_strict.hpp"
+#include "interval_kernels.hpp"
 #include "sample_kernels.hpp"
 #include "segment_kernels.hpp"
 #include "preprocess_kernels.hpp"
@@ -1530,15 +1531,18 @@ __global__ void k_pool_init(PagePool pool, uint32_t first_free, uint32_t n_stati
 // arithmetic (dp_math_strict.hpp). The default launches (MIXED = false) do not contain that code at all.
 // JOBX: the job, plus JOB_BORDER for the launches that carry the border-confidence phase (border_kernels.hpp) behind every
 // read. The phase is a bit of the job number and not a template parameter of its own, so that the instantiations without
-// it keep the names (and the code) they have always had. JOB_SAMPLE likewise: the posterior-sampling phase (sample_kernels.hpp).
+// it keep the names (and the code) they have always had. JOB_SAMPLE likewise: the posterior-sampling phase (sample_kernels.hpp),
+// and JOB_INTERVAL: the credible-interval phase (interval_kernels.hpp), which runs alone.
 template <int JOBX, bool MIXED>
 __global__ DYN_ONE_WAVE_PER_SIMD void k_read_queue(const QueueArgs q, const ReadDesc* __restrict__ descs,
                                                    const double* __restrict__ sig, const Emis* __restrict__ par,
                                                    const SoftplusNode* __restrict__ sp_tab) {
-  constexpr int JOB = JOBX & ~(JOB_BORDER | JOB_SAMPLE);
+  constexpr int JOB = JOBX & ~(JOB_BORDER | JOB_SAMPLE | JOB_INTERVAL);
   constexpr bool BORDER = (JOBX & JOB_BORDER) != 0;
   constexpr bool SAMPLE = (JOBX & JOB_SAMPLE) != 0;
-  static_assert(!(BORDER || SAMPLE) || JOB == JOB_ALIGN || JOB == JOB_ALIGN_INPLACE, "borders and samples exist for align(calc=true) only");
+  constexpr bool INTERVAL = (JOBX & JOB_INTERVAL) != 0;
+  static_assert(!(BORDER || SAMPLE || INTERVAL) || JOB == JOB_ALIGN || JOB == JOB_ALIGN_INPLACE, "borders and samples exist for align(calc=true) only");
+  static_assert(!INTERVAL || !(BORDER || SAMPLE), "one lattice phase per launch");
   constexpr bool LATTICE = JOB != JOB_Z;
   // + 2^(i/128) as plain doubles (exp_table128_vec) + glibc's table of the strict exp (dp_math_strict.hpp)
   constexpr int TAB_NODES = SP_NODES + dynmath::EXP128_NODES + dynmath::STRICT_EXP_WORDS / 2;
@@ -1560,8 +1564,9 @@ __global__ DYN_ONE_WAVE_PER_SIMD void k_read_queue(const QueueArgs q, const Read
   lds_u64_t* sb = (lds_u64_t*)&s_ring[wave][0][0];  // traceback staging: the ring is idle by then
 
   WaveStats ws;
-  // the border-confidence phase reads whole windows of LPE, a sampled path any cell of the band: every cell is stored then
-  const float lpe_floor = (BORDER || SAMPLE || q.lpe_dense) ? -INFINITY : q.lpe_floor;
+  // the border-confidence phase reads whole windows of LPE, a sampled path any cell of the band, the interval phase whole
+  // columns: every cell is stored then
+  const float lpe_floor = (BORDER || SAMPLE || INTERVAL || q.lpe_dense) ? -INFINITY : q.lpe_floor;
   const uint64_t t_start = __builtin_amdgcn_s_memtime();
   uint32_t* ctl = q.pool.ctl;
   uint32_t have = 0;  // pages in this wave's table
@@ -1641,6 +1646,26 @@ __global__ DYN_ONE_WAVE_PER_SIMD void k_read_queue(const QueueArgs q, const Read
         }
       }
       ws.cyc_t += __builtin_amdgcn_s_memtime() - t6;
+    }
+    if constexpr (INTERVAL) {
+      // as the border phase: the lattice is still in this wave's pages, state and segrow were written by lanes of this wave. The
+      // whole wave sweeps the read's rows once, every lane at the band slots the sweeps gave it
+      const uint64_t t7 = __builtin_amdgcn_s_memtime();
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      const ReadState* rs = q.st + rd.read;
+      if (__builtin_amdgcn_readfirstlane((int)ctl_load(reinterpret_cast<const uint32_t*>(&rs->status))) == 0) {
+        const BorderBand band{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio};
+        auto row = [&w](int t) { return pool_row(w, t); };
+        if constexpr (JOB == JOB_ALIGN) {
+          const double Zb = __hip_atomic_load(&rs->Zb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const BorderCellSeparate<decltype(row)> cell{band, q.pool.lpe, q.pool.ws, sig + rd.sig_off, par + rd.par_off, Zb, q.m1, row};
+          border_interval_read_wave(cell, band, rd, q.tb.segrow, q.interval, w.lane);
+        } else {
+          const BorderCellInplace<decltype(row)> cell{band, reinterpret_cast<const float*>(q.pool.ws), row};
+          border_interval_read_wave(cell, band, rd, q.tb.segrow, q.interval, w.lane);
+        }
+      }
+      ws.cyc_t += __builtin_amdgcn_s_memtime() - t7;
     }
   }
   // leaving: while a claimed read still lacks its pages, somebody may be waiting for these
@@ -1920,6 +1945,18 @@ void launch_read_queue(QueueJob job, bool with_strict, const QueueArgs& q, int n
   if (q.n_reads <= 0) return;
   const int groups = std::min((q.n_reads + DYN_WAVES_PER_GROUP - 1) / DYN_WAVES_PER_GROUP, std::max(1, n_cus));
   const dim3 grid(groups), block(64 * DYN_WAVES_PER_GROUP);
+  if (q.sample.count == 0 && q.interval.tail > 0.0 && (job == JOB_ALIGN || job == JOB_ALIGN_INPLACE)) {  // dyn_aligner_set_border_interval
+#define DYN_INTERVAL_LAUNCH(J, M) hipLaunchKernelGGL((k_read_queue<J | JOB_INTERVAL, M>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab)
+    if (job == JOB_ALIGN) {
+      if (with_strict) DYN_INTERVAL_LAUNCH(JOB_ALIGN, true);
+      else DYN_INTERVAL_LAUNCH(JOB_ALIGN, false);
+    } else {
+      if (with_strict) DYN_INTERVAL_LAUNCH(JOB_ALIGN_INPLACE, true);
+      else DYN_INTERVAL_LAUNCH(JOB_ALIGN_INPLACE, false);
+    }
+#undef DYN_INTERVAL_LAUNCH
+    return;
+  }
   if (q.sample.count > 0 && (job == JOB_ALIGN || job == JOB_ALIGN_INPLACE)) {  // dyn_aligner_set_posterior_samples
 #define DYN_SAMPLE_LAUNCH(J, M) hipLaunchKernelGGL((k_read_queue<J | JOB_SAMPLE, M>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab)
     if (q.border_window > 0) {  // ... behind the border-confidence phase

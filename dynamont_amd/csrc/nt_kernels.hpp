@@ -1,6 +1,7 @@
 // nt_kernels.hpp -- device-side data layout and launch interface of the NT hot path.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 #include <hip/hip_runtime.h>
@@ -108,6 +109,8 @@ constexpr int QUEUE_N_STATS = 10;
 enum QueueJob { JOB_Z = 0, JOB_ALIGN = 1, JOB_ALIGN_INPLACE = 2, JOB_TRAIN = 3, JOB_TRAIN_ZCHECK = 4 };
 constexpr int JOB_BORDER = 8;  // a bit on top of JOB_ALIGN / JOB_ALIGN_INPLACE in k_read_queue's template argument: the launch
                                // carries the border-confidence phase (border_kernels.hpp)
+constexpr int JOB_INTERVAL = 32;  // likewise: the launch carries the credible-interval phase (interval_kernels.hpp); never together
+                                  // with the other two
 constexpr int JOB_SAMPLE = 16; // likewise: the launch carries the posterior-sampling phase (sample_kernels.hpp), behind the border
                                // phase when both bits are set
 
@@ -120,6 +123,18 @@ struct SampleOut {
   uint64_t seed;
   int count;          // K, 1 .. 64
 };
+
+// per-border credible intervals (dyn_aligner_set_border_interval; interval_kernels.hpp): the four columns of a launch, in ONE buffer of 24 bytes per output row:
+//   double mean[capacity] | double sd[capacity] | uint32 lo[capacity] | uint32 hi[capacity]       (zeroed by the caller)
+// tail == 0: not asked for. It shares the train buffers' / the samples' place in QueueArgs and BandArgs (nt_kernels.hpp): `none`
+// lies on SampleOut::count and stays 0, which is how a launch tells the two apart.
+struct IntervalOut {
+  double* mean;
+  uint64_t capacity;
+  double tail;  // a = (1 - mass) / 2, formed by the host
+  int none;     // = SampleOut::count: 0
+};
+static_assert(offsetof(IntervalOut, none) == offsetof(SampleOut, count), "an interval launch reads as a launch without samples");
 
 struct QueueArgs {
   const ReadDesc* descs;   // in processing order
@@ -135,6 +150,7 @@ struct QueueArgs {
   union {
     TrainBuffers tr;    // JOB_TRAIN / JOB_TRAIN_ZCHECK
     SampleOut sample;   // JOB_ALIGN / JOB_ALIGN_INPLACE: posterior path samples, count > 0 when asked for
+    IntervalOut interval;  // JOB_ALIGN / JOB_ALIGN_INPLACE: per-border credible intervals, tail > 0 (and sample.count == 0) when asked for
   };
   double m1, e2;          // log transition probabilities (NT_aligner_api.cpp:84-86)
   const dynmath::SoftplusNode* sp_tab;
@@ -150,6 +166,7 @@ struct QueueArgs {
   double* border_window_p = nullptr;
 };
 static_assert(sizeof(SampleOut) <= sizeof(TrainBuffers), "the samples take the train buffers' place in QueueArgs / BandArgs");
+static_assert(sizeof(IntervalOut) <= sizeof(TrainBuffers), "the intervals take the train buffers' place in QueueArgs / BandArgs");
 
 // ---- the RESIDENT read queue (round 5) ---------------------------------------------------------------------------
 // k_read_queue drains ONE batch per launch: its waves finish up to one read apart, and the next launch -- queued on the same

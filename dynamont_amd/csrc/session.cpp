@@ -185,7 +185,7 @@ bool session_candidate(const dyn_batch* b) {
   // a launch of its own, for which an open session is quiesced.
   // A ticket under the guide rescue (dyn_aligner_set_guide_rescue) is a classic launch too -- an INTERIM: its
   // rescue stage is a guided kernel, and a guided kernel beside resident waves is what did not make progress before.
-  return a->sess_enabled.load() && !a->host_only && !a->ntk && b->async && b->job == DynJob::AlignFull && b->rs_want == 0 && b->bc_want == 0 && b->ps_want == 0 && b->ag_want == 0 && b->gr_hw == 0 &&
+  return a->sess_enabled.load() && !a->host_only && !a->ntk && b->async && b->job == DynJob::AlignFull && b->rs_want == 0 && b->bc_want == 0 && b->bi_want == 0 && b->ps_want == 0 && b->ag_want == 0 && b->gr_hw == 0 &&
          (a->sess_open_hint.load() || b->n >= SESSION_MIN_READS);
 }
 

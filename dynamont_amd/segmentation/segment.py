@@ -50,6 +50,8 @@ CSV_COLUMNS_SCORES = b",median_delta,mad_delta,homogeneity"
 CSV_COLUMNS_BORDERS = b",border_probability,border_window_probability"
 # --posterior-samples K: ... and, after those, one field with the K sampled starts of the segment (Aligner.set_posterior_samples)
 CSV_COLUMNS_SAMPLES = b",sample_starts"
+# --border-interval MASS: ... and, after those, the credible interval and spread of the segment's start (Aligner.set_border_interval)
+CSV_COLUMNS_INTERVALS = b",border_lo,border_hi,border_mean,border_sd"
 POLYA = "AAAAAAAAA"
 
 MAX_SAMPLES_IN_FLIGHT = 512 << 20  # ~1 GB of pinned int16 staging + ~4 GB of float64 on the device, whatever --depth says
@@ -110,6 +112,12 @@ def parse(argv=None) -> Namespace:
                         "read drawn on the GPU from the posterior distribution over alignments -- column k of the field, read down "
                         "a read's rows, is one jointly consistent segmentation. Reproducible for the same input order, "
                         "--batch-reads and --sample-seed. Not together with --rescale-iters, --guide-auto or --guide-rescue")
+    p.add_argument("--border-interval", type=float, default=0.0, metavar="MASS",
+                   help="add border_lo, border_hi, border_mean, border_sd to every row (after every other optional column): the "
+                        "central credible interval of posterior mass MASS (0.01 .. 0.999, default 0 = off) of the segment's start, "
+                        "and the mean and standard deviation of that posterior, in the unit of the start column -- computed on the "
+                        "GPU from the forward-backward lattice of the alignment. Not together with --border-confidence, "
+                        "--posterior-samples, --guide-auto or --guide-rescue")
     p.add_argument("--sample-seed", type=int, default=0, metavar="S", help="with --posterior-samples: the seed of the draws (default 0)")
     p.add_argument("--rescale-iters", type=int, default=0, choices=range(0, 9), metavar="N",
                    help="align every read N + 1 times (0 .. 8, default 0 = off), refitting the read's signal shift and scale "
@@ -159,6 +167,12 @@ def parse(argv=None) -> Namespace:
     for other, name in ((args.guide_auto, "--guide-auto"), (args.rescale_iters, "--rescale-iters"), (args.guide_rescue, "--guide-rescue")):
         if args.posterior_samples and other:
             p.error("--posterior-samples and %s are mutually exclusive" % name)
+    if args.border_interval != 0 and not 0.01 <= args.border_interval <= 0.999:
+        p.error("--border-interval must be 0 or 0.01 .. 0.999")
+    for other, name in ((args.border_confidence, "--border-confidence"), (args.posterior_samples, "--posterior-samples"),
+                        (args.guide_auto, "--guide-auto"), (args.guide_rescue, "--guide-rescue")):
+        if args.border_interval and other:
+            p.error("--border-interval and %s are mutually exclusive" % name)
     if args.sample_seed < 0 or args.sample_seed >= 1 << 64:
         p.error("--sample-seed must be 0 .. 2^64 - 1")
     return args
@@ -656,6 +670,8 @@ class _NativePipeline:
             flags |= N.DYN_CSV_BORDER_CONFIDENCE  # ... and the border confidence (--border-confidence)
         if aligner._posterior_samples[0]:
             flags |= N.DYN_CSV_POSTERIOR_SAMPLES  # ... and the posterior samples (--posterior-samples)
+        if aligner._border_interval:
+            flags |= N.DYN_CSV_BORDER_INTERVAL  # ... and the credible intervals (--border-interval)
         rc = self.L.dyn_csv_sink_open_ex(outfile.encode(), errfile.encode(), int(os.environ.get("DYN_SINK_LEVEL", level)), int(threads),
                                          int(first), int(last), flags, C.byref(h), err, 1024)
         if rc != N.DYN_OK:
@@ -877,7 +893,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             zstd_level: int = 3, event_stats: bool = False, rescale_iters: int = 0, kmer_summary: str = "",
             segment_scores: int = 0, border_confidence: int = 0, band_report: str = "", band: int = 400,
             guide_auto: int = 0, guide_rounds: int = 8, guide_rescue: int = 0, guide_rescue_margin: int = 1,
-            posterior_samples: int = 0, sample_seed: int = 0) -> None:
+            posterior_samples: int = 0, sample_seed: int = 0, border_interval: float = 0.0) -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
@@ -892,6 +908,9 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                          "--rescale-iters or --border-confidence")
     if not 0 <= posterior_samples <= 64 or (posterior_samples and (guide_auto or guide_rescue or rescale_iters)):
         raise ValueError("--posterior-samples must be 0 .. 64 and is not combined with --guide-auto, --guide-rescue or --rescale-iters")
+    if border_interval and (not 0.01 <= border_interval <= 0.999 or border_confidence or posterior_samples or guide_auto or guide_rescue):
+        raise ValueError("--border-interval must be 0 or 0.01 .. 0.999 and is not combined with --border-confidence, "
+                         "--posterior-samples, --guide-auto or --guide-rescue")
     from dynamont_amd import parallel
     comm, local_rank = parallel.init_from_env()
     rank, world = (comm.rank, comm.world) if comm else (0, 1)
@@ -916,6 +935,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             header = header[:-1] + CSV_COLUMNS_BORDERS + b"\n"
         if posterior_samples:
             header = header[:-1] + CSV_COLUMNS_SAMPLES + b"\n"
+        if border_interval:
+            header = header[:-1] + CSV_COLUMNS_INTERVALS + b"\n"
         writer = threading.Thread(target=listener, args=(q, outfile, header), daemon=True)
         writer.start()
     sink = None if native else (q if comm is None else _Collector())
@@ -1001,6 +1022,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                 aligner.set_border_confidence(border_confidence)
             if posterior_samples:
                 aligner.set_posterior_samples(posterior_samples, sample_seed)
+            if border_interval:
+                aligner.set_border_interval(border_interval)
             if kmer_summary:
                 aligner.set_kmer_summary(True)
             if band_report:
@@ -1163,7 +1186,8 @@ def main(argv=None) -> None:
             kmer_summary=args.kmer_summary, segment_scores=args.segment_scores,
             border_confidence=args.border_confidence, band_report=args.band_report, band=args.band,
             guide_auto=args.guide_auto, guide_rounds=args.guide_rounds, guide_rescue=args.guide_rescue,
-            guide_rescue_margin=args.guide_rescue_margin, posterior_samples=args.posterior_samples, sample_seed=args.sample_seed)
+            guide_rescue_margin=args.guide_rescue_margin, posterior_samples=args.posterior_samples, sample_seed=args.sample_seed,
+            border_interval=args.border_interval)
     _stamp("segment() returned (aligner closed)")
     if argv is None and not int(__import__("os").environ.get("WORLD_SIZE", "1") or 1) > 1:
         # Invoked as the command (console script / python -m), single process, everything written and closed: leave without

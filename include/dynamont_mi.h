@@ -224,6 +224,35 @@ typedef struct dyn_sample_out {
   uint32_t count;         /* in: planes of sample_start, >= the batch's K; out: the batch's K */
 } dyn_sample_out;
 
+/* (added within ABI 10: a caller that must know looks the symbol up) Per-border credible intervals of an
+ * align(calc_probabilities = 1) job whose handle had dyn_aligner_set_border_interval(a, mass) with mass > 0 when the batch was
+ * submitted: how far the start of every segment could move, in samples, from the lattice's own posteriors.
+ * Output row j of an ok read has lattice column n = j + 1 and called row r = signal_positions[j] + 1. LPM(t, n) is exactly the
+ * value dyn_border_out is defined over: (fM(t, n) + bM(t, n)) - Z, -inf outside the reference's band window of row t
+ * (computeBounds, NT_aligner_api.cpp:90-108) and in row 0. p(t) = exp(LPM(t, n)), taken as 0 where LPM is -inf, for
+ * t = 1 .. T-1: the distribution of "base n starts at row t". a = (1 - mass) / 2. All sums are fp64, in ascending t, one IEEE
+ * add per term, no contraction:
+ *   C(t) the running sum of p;  S the sum of p over the column;
+ *   A    the sum of d * p, d = t - r (exact as a double), each product one IEEE multiplication;
+ *   B    the sum of (d * d) * p, d * d formed first.
+ *   border_lo[j]   = (first t with C(t) >= a) - 1
+ *   border_hi[j]   = (first t with C(t) >= 1 - a) - 1; if no row reaches the threshold (either one), the last in-band row of
+ *                    the column, minus 1
+ *   border_mean[j] = (r - 1) + A / S
+ *   border_sd[j]   = sqrt(max(B / S - (A / S)^2, 0))
+ * Positions are signal positions, the unit of signal_positions. The thresholds are absolute, not relative to S: S is 1 within
+ * 1e-6 on the device (the lattice's log-posteriors are floats in two of its three layouts) and known only when the column
+ * ends. The same bits on every run of the same batch in the same layout. Rows of failed reads are 0. */
+#define DYN_BORDER_INTERVAL_MIN_MASS 0.01
+#define DYN_BORDER_INTERVAL_MAX_MASS 0.999
+typedef struct dyn_border_interval_out {
+  uint32_t* border_lo;  /* [capacity] each, rows indexed like dyn_align_out's */
+  uint32_t* border_hi;
+  double* border_mean;
+  double* border_sd;
+  uint64_t capacity;    /* >= dyn_segment_capacity() */
+} dyn_border_interval_out;
+
 /* (ABI 10) Per-read signal rescaling of an align(calc_probabilities = 1) job whose handle had dyn_aligner_set_rescale(a, K)
  * with K > 0 when the batch was submitted. Read r is aligned K + 1 times. x0 = its preprocessed signal (what
  * dyn_batch_signals returns with the switch off); A_0 = 0.0, B_0 = 1.0; pass k = 0 .. K aligns x_k, x_0 = x0 and
@@ -479,6 +508,18 @@ int dyn_aligner_set_border_confidence(dyn_aligner* a, int window);
  * dyn_aligner_set_border_confidence and the per-segment riders, none of whose outputs it changes. A ticket submitted with
  * count > 0 takes one launch of its own: neither the resident session nor a merged launch. */
 int dyn_aligner_set_posterior_samples(dyn_aligner* a, int count, uint64_t seed);
+/* (added within ABI 10) align(calc_probabilities = 1) also computes the per-border credible intervals of the given posterior
+ * mass (dyn_border_interval_out) on the device behind every read's traceback, while its lattice is still in place, for every
+ * batch or ticket SUBMITTED while mass > 0; 24 bytes of device memory per segment row for those batches only. mass = 0 (the
+ * default) is off: nothing is allocated or changed, and every launch is the one it would have been. Valid: 0 and
+ * DYN_BORDER_INTERVAL_MIN_MASS .. DYN_BORDER_INTERVAL_MAX_MASS; anything else (a NaN too): DYN_ERR_INVALID_ARGUMENT + message,
+ * and the switch stays as it was. One lattice phase runs per launch for now: a job or ticket started while mass > 0 is refused
+ * (DYN_ERR_INVALID_ARGUMENT + message) together with dyn_aligner_set_border_confidence(window > 0),
+ * dyn_aligner_set_posterior_samples(count > 0), dyn_aligner_set_auto_guide(half_width > 0),
+ * dyn_aligner_set_guide_rescue(half_width > 0) or a guided batch. With dyn_aligner_set_rescale the values are the last pass's.
+ * A ticket submitted with mass > 0 takes one launch per batch (not the resident session) and merges only with tickets of the
+ * same mass. Handles of mode ntk / resquiggle ignore the switch. */
+int dyn_aligner_set_border_interval(dyn_aligner* a, double mass);
 /* (added within ABI 10: a caller that must know looks the symbol up) Per-k-mer level summary of a run. While it is on, every output row (segment) of every read with status 0 of an
  * align(calc_probabilities = 1) batch or ticket SUBMITTED on this handle is added, on the device behind the per-segment
  * kernels, to its k-mer's entry of an accumulator that lives on the handle: six u64 per k-mer code (48 bytes x num_kmers of
@@ -596,6 +637,21 @@ int dyn_format_csv_samples(const dyn_aligner* a, uint64_t n_reads, const dyn_ali
                            const int64_t* sig_offsets, const int64_t* last_index, int threads, char* out, uint64_t out_cap,
                            uint64_t* row_begin, uint64_t* row_end);
 
+/* (added within ABI 10) The same with the credible intervals of dyn_batch_fetch_intervals as well: after every other optional
+ * column each row gets ",{lo},{hi},{mean:.6f},{sd:.6f}": border_lo and border_hi as integers and border_mean in the unit of the
+ * `start` column (the fetched value + sig_offsets[i]), border_sd as it is; the floats as Python's f"{x:.6f}". ev, sc, bd, sm and
+ * bi may each be NULL; bi == NULL: dyn_format_csv_samples / dyn_format_csv_bound_samples, byte for byte. */
+uint64_t dyn_format_csv_bound_intervals(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                                        const dyn_score_out* sc, const dyn_border_out* bd, const dyn_sample_out* sm,
+                                        const dyn_border_interval_out* bi, const char* const* readids,
+                                        const char* const* signalids);
+int dyn_format_csv_intervals(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                             const dyn_score_out* sc, const dyn_border_out* bd, const dyn_sample_out* sm,
+                             const dyn_border_interval_out* bi, const char* seqs, const uint64_t* seq_offsets,
+                             const char* const* readids, const char* const* signalids, const int64_t* sig_offsets,
+                             const int64_t* last_index, int threads, char* out, uint64_t out_cap, uint64_t* row_begin,
+                             uint64_t* row_end);
+
 /* Closes the gaps between the per-read ranges dyn_format_csv produced: all rows become one contiguous run at the
  * front of `out`, in read order; row_begin/row_end are updated. Returns the total byte count. */
 uint64_t dyn_csv_compact(char* out, uint64_t n_reads, uint64_t* row_begin, uint64_t* row_end);
@@ -649,6 +705,12 @@ int dyn_csv_sink_open_part(const char* csv_zst_path, const char* errors_path, in
  * sink fetches each ticket's samples after its wait, and a submit whose ticket was submitted with
  * dyn_aligner_set_posterior_samples off fails with DYN_ERR_INVALID_ARGUMENT. Bit 0x4 and every bit above 0x10 stay refused. */
 #define DYN_CSV_POSTERIOR_SAMPLES 0x10u
+/* (added within ABI 10) DYN_CSV_BORDER_INTERVAL: the header gains ",border_lo,border_hi,border_mean,border_sd" after every other
+ * optional column, every row the four fields of dyn_format_csv_intervals; the sink fetches each ticket's intervals after its
+ * wait, and a submit whose ticket was submitted with dyn_aligner_set_border_interval off fails with DYN_ERR_INVALID_ARGUMENT.
+ * (0x40, not 0x20: bits 0x4 and 0x20 stay unassigned, and a sink opened with either is refused as before; so is every bit
+ * above 0x40.) */
+#define DYN_CSV_BORDER_INTERVAL 0x40u
 int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int level, int threads, int first, int last,
                          uint32_t flags, dyn_csv_sink** out, char* err, uint64_t errcap);
 #define DYN_ZSTD_FRAME_END "\x01\x00\x00" /* an empty last block (raw, size 0): 3 bytes; the frames carry no checksum */
@@ -778,6 +840,11 @@ int dyn_batch_fetch_borders(dyn_batch* b, dyn_border_out* out);
  * own non-blocking stream; out->count is set to the batch's K. DYN_ERR_INVALID_ARGUMENT (with a message) when the batch was
  * submitted with dyn_aligner_set_posterior_samples off, or was a Z-only or train job, or out's capacity, n or count is too small. */
 int dyn_batch_fetch_samples(dyn_batch* b, dyn_sample_out* out);
+/* (added within ABI 10) The credible intervals of the batch's last align(calc_probabilities = 1) job (of a completed ticket,
+ * merged launch or not), copied on the handle's own non-blocking stream. DYN_ERR_INVALID_ARGUMENT (with a message) when the
+ * batch was submitted with dyn_aligner_set_border_interval off, or aligned with calc_probabilities = 0, or out->capacity is too
+ * small. */
+int dyn_batch_fetch_intervals(dyn_batch* b, dyn_border_interval_out* out);
 /* (ABI 10) Copy the per-read transforms of the last dyn_batch_align (or of a completed ticket, merged launch or not) into
  * `out` (n >= the batch's read count). DYN_ERR_INVALID_ARGUMENT + message for a batch submitted with
  * dyn_aligner_set_rescale(a, 0), or aligned with calc_probabilities = 0. */
