@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import enum
-from typing import Sequence
+from typing import NamedTuple, Sequence
 
 import numpy as np
 
@@ -127,117 +127,44 @@ class AlignBatchResult:
         # failed), None when off; guide_rounds / guide_converged then hold the rescued reads' counts (0 for every other read)
         self.rescue = None
 
-    def _fetch_rescue(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
-        """dyn_batch_fetch_rescue into ``rescue`` / ``guide_rounds`` / ``guide_converged``, or drop what an earlier rescue left."""
-        if not wanted:
-            if self.rescue is not None:  # a result object refilled from a rescued job must not keep that job's counts
-                self.rescue = self.guide_rounds = self.guide_converged = None
+    def _out_struct(self, name: str):
+        """the C out-struct of optional result ``name`` (a key of ``_OPTIONAL``) over this object's arrays"""
+        cols, struct, _ = _OPTIONAL[name]
+        ptrs = [_ptr(getattr(self, attr), ptype) for (attr, _, _), (_, ptype) in zip(cols, struct._fields_)]
+        if name == "samples":
+            return struct(*ptrs, self.cap, self.n, self.sample_starts.shape[0])
+        return struct(*ptrs, self.n if cols[0][2] == "n" else self.cap)
+
+    def _fetch_one(self, L, handle, aligner: "Aligner", name: str, want) -> None:
+        """Optional result ``name`` of the job behind ``handle`` into this object's arrays (allocated on first use), or -- ``want``
+        false -- drop what an earlier job left there. ``want`` is the job's ``JobWants`` field: the sample count for "samples"."""
+        cols, struct, fetch = _OPTIONAL[name]
+        if name == "margins":
+            self.band_used = None
+        if not want:
+            if name != "rescue" or self.rescue is not None:  # (without a rescue the guide counts are an auto-guided job's)
+                for attr, _, _ in cols:
+                    setattr(self, attr, None)
             return
-        self.rescue = np.zeros(self.n, dtype=np.uint8)
-        self.guide_rounds, self.guide_converged = np.zeros(self.n, dtype=np.uint32), np.zeros(self.n, dtype=np.uint32)
-        rc = L.dyn_batch_fetch_rescue(handle, _ptr(self.rescue, N.c_u8_p), _ptr(self.guide_rounds, N.c_u32_p),
-                                      _ptr(self.guide_converged, N.c_u32_p), self.n)
+        shapes = [{"n": (self.n,), "cap": (self.cap,), "Kcap": (int(want), self.cap)}[dim] for _, _, dim in cols]
+        first = getattr(self, cols[0][0])
+        # (the sample planes are reallocated when K changes; a rescue's arrays are fresh every time: the guide counts are shared)
+        if first is None or first.shape != shapes[0] or name == "rescue":
+            for (attr, dtype, _), shape in zip(cols, shapes):
+                setattr(self, attr, np.zeros(shape, dtype=dtype))
+        if struct is None:  # dyn_batch_fetch_rescue takes its three arrays as they are
+            rc = getattr(L, fetch)(handle, _ptr(self.rescue, N.c_u8_p), _ptr(self.guide_rounds, N.c_u32_p),
+                                   _ptr(self.guide_converged, N.c_u32_p), self.n)
+        else:
+            rc = getattr(L, fetch)(handle, C.byref(self._out_struct(name)))
         if rc != N.DYN_OK:
             _raise(rc, aligner.last_error())
 
-    def _fetch_band_margin(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
-        """dyn_batch_fetch_band_margin into this object's per-read columns (allocated on first use), or drop them."""
-        self.band_used = None
-        if not wanted:
-            self.band_margin_low = self.band_margin_high = self.band_edge_rows = None
-            return
-        if self.band_margin_low is None:
-            self.band_margin_low, self.band_margin_high, self.band_edge_rows = (np.zeros(self.n, dtype=np.uint32) for _ in range(3))
-        out = N.DynBandMarginOut(_ptr(self.band_margin_low, N.c_u32_p), _ptr(self.band_margin_high, N.c_u32_p),
-                                 _ptr(self.band_edge_rows, N.c_u32_p), self.n)
-        rc = L.dyn_batch_fetch_band_margin(handle, C.byref(out))
-        if rc != N.DYN_OK:
-            _raise(rc, aligner.last_error())
-
-    def _fetch_samples(self, L, handle, aligner: "Aligner", count: int) -> None:
-        """dyn_batch_fetch_samples into ``sample_starts`` / ``sample_dead`` (``count`` = the K the job was submitted with), or
-        drop them."""
-        if not count:
-            self.sample_starts = self.sample_dead = None
-            return
-        if self.sample_starts is None or self.sample_starts.shape != (count, self.cap):
-            self.sample_starts = np.zeros((count, self.cap), dtype=np.uint32)
-        if self.sample_dead is None:
-            self.sample_dead = np.zeros(self.n, dtype=np.uint32)
-        sm = N.DynSampleOut(_ptr(self.sample_starts, N.c_u32_p), _ptr(self.sample_dead, N.c_u32_p), self.cap, self.n, count)
-        rc = L.dyn_batch_fetch_samples(handle, C.byref(sm))
-        if rc != N.DYN_OK:
-            _raise(rc, aligner.last_error())
-
-    def _interval_out(self) -> N.DynBorderIntervalOut:
-        return N.DynBorderIntervalOut(_ptr(self.border_lo, N.c_u32_p), _ptr(self.border_hi, N.c_u32_p),
-                                      _ptr(self.border_mean, N.c_double_p), _ptr(self.border_sd, N.c_double_p), self.cap)
-
-    def _fetch_intervals(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
-        """dyn_batch_fetch_intervals into this object's interval columns (allocated on first use), or drop them."""
-        if not wanted:
-            self.border_lo = self.border_hi = self.border_mean = self.border_sd = None
-            return
-        if self.border_lo is None:
-            self.border_lo, self.border_hi = (np.zeros(self.cap, dtype=np.uint32) for _ in range(2))
-            self.border_mean, self.border_sd = (np.zeros(self.cap) for _ in range(2))
-        bi = self._interval_out()
-        rc = L.dyn_batch_fetch_intervals(handle, C.byref(bi))
-        if rc != N.DYN_OK:
-            _raise(rc, aligner.last_error())
-
-    def _fetch_borders(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
-        """dyn_batch_fetch_borders into this object's border columns (allocated on first use), or drop them."""
-        if not wanted:
-            self.border_probability = self.border_window_probability = None
-            return
-        if self.border_probability is None:
-            self.border_probability, self.border_window_probability = (np.zeros(self.cap) for _ in range(2))
-        bd = N.DynBorderOut(_ptr(self.border_probability, N.c_double_p), _ptr(self.border_window_probability, N.c_double_p),
-                            self.cap)
-        rc = L.dyn_batch_fetch_borders(handle, C.byref(bd))
-        if rc != N.DYN_OK:
-            _raise(rc, aligner.last_error())
-
-    def _fetch_scores(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
-        """dyn_batch_fetch_scores into this object's score columns (allocated on first use), or drop them."""
-        if not wanted:
-            self.median_delta = self.mad_delta = self.homogeneity = None
-            return
-        if self.median_delta is None:
-            self.median_delta, self.mad_delta, self.homogeneity = (np.zeros(self.cap) for _ in range(3))
-        sc = N.DynScoreOut(_ptr(self.median_delta, N.c_double_p), _ptr(self.mad_delta, N.c_double_p),
-                           _ptr(self.homogeneity, N.c_double_p), self.cap)
-        rc = L.dyn_batch_fetch_scores(handle, C.byref(sc))
-        if rc != N.DYN_OK:
-            _raise(rc, aligner.last_error())
-
-    def _fetch_rescale(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
-        """dyn_batch_fetch_rescale into this object's per-read columns (allocated on first use), or drop them."""
-        if not wanted:
-            self.rescale_shift = self.rescale_scale = self.rescale_iters = None
-            return
-        if self.rescale_shift is None:
-            self.rescale_shift, self.rescale_scale = np.zeros(self.n), np.ones(self.n)
-            self.rescale_iters = np.zeros(self.n, dtype=np.int32)
-        out = N.DynRescaleOut(_ptr(self.rescale_shift, N.c_double_p), _ptr(self.rescale_scale, N.c_double_p),
-                              _ptr(self.rescale_iters, N.c_i32_p), self.n)
-        rc = L.dyn_batch_fetch_rescale(handle, C.byref(out))
-        if rc != N.DYN_OK:
-            _raise(rc, aligner.last_error())
-
-    def _fetch_levels(self, L, handle, aligner: "Aligner", wanted: bool) -> None:
-        """dyn_batch_fetch_events into this object's level columns (allocated on first use), or drop them."""
-        if not wanted:
-            self.level_mean = self.level_stdv = self.level_median = None
-            return
-        if self.level_mean is None:
-            self.level_mean, self.level_stdv, self.level_median = (np.zeros(self.cap) for _ in range(3))
-        ev = N.DynEventOut(_ptr(self.level_mean, N.c_double_p), _ptr(self.level_stdv, N.c_double_p),
-                           _ptr(self.level_median, N.c_double_p), self.cap)
-        rc = L.dyn_batch_fetch_events(handle, C.byref(ev))
-        if rc != N.DYN_OK:
-            _raise(rc, aligner.last_error())
+    def _fetch_optional(self, L, handle, aligner: "Aligner", wants: "JobWants") -> None:
+        """every optional result of a completed align job, in the order of ``_OPTIONAL``: fetched where ``wants`` says the job
+        computed it, dropped where it did not"""
+        for name in _OPTIONAL:
+            self._fetch_one(L, handle, aligner, name, getattr(wants, name))
 
     def error(self, i: int) -> str | None:
         if self.status[i] == 0:
@@ -288,6 +215,43 @@ class AlignBatchResult:
         return d
 
 
+class JobWants(NamedTuple):
+    """What ONE align job / ticket took of the aligner's opt-in switches at its submission (``Aligner._job_wants``). All off: a
+    Z-only or a train job, a batch never aligned."""
+    levels: bool = False     # set_event_stats
+    rescale: bool = False    # set_rescale
+    scores: bool = False     # set_segment_scores
+    borders: bool = False    # set_border_confidence
+    samples: int = 0         # set_posterior_samples: the count
+    intervals: bool = False  # set_border_interval
+    margins: bool = False    # set_band_margin (tickets report margins; they are never retried)
+    rescue: bool = False     # set_guide_rescue
+    auto_guide: tuple | None = None  # set_auto_guide, tickets only: (alignments per read, the ticket's sample offsets)
+
+
+# the optional results of an align job in the order they are fetched: JobWants field -> ((AlignBatchResult attribute, dtype, one
+# entry per read "n" / per segment row "cap" / per sample and segment row "Kcap") in the order of the out-struct's pointers,
+# the out-struct, the fetcher)
+_F64, _U32 = np.float64, np.uint32
+_OPTIONAL = {
+    "levels": ((("level_mean", _F64, "cap"), ("level_stdv", _F64, "cap"), ("level_median", _F64, "cap")),
+               N.DynEventOut, "dyn_batch_fetch_events"),
+    "rescale": ((("rescale_shift", _F64, "n"), ("rescale_scale", _F64, "n"), ("rescale_iters", np.int32, "n")),
+                N.DynRescaleOut, "dyn_batch_fetch_rescale"),
+    "scores": ((("median_delta", _F64, "cap"), ("mad_delta", _F64, "cap"), ("homogeneity", _F64, "cap")),
+               N.DynScoreOut, "dyn_batch_fetch_scores"),
+    "borders": ((("border_probability", _F64, "cap"), ("border_window_probability", _F64, "cap")),
+                N.DynBorderOut, "dyn_batch_fetch_borders"),
+    "samples": ((("sample_starts", _U32, "Kcap"), ("sample_dead", _U32, "n")), N.DynSampleOut, "dyn_batch_fetch_samples"),
+    "intervals": ((("border_lo", _U32, "cap"), ("border_hi", _U32, "cap"), ("border_mean", _F64, "cap"), ("border_sd", _F64, "cap")),
+                  N.DynBorderIntervalOut, "dyn_batch_fetch_intervals"),
+    "margins": ((("band_margin_low", _U32, "n"), ("band_margin_high", _U32, "n"), ("band_edge_rows", _U32, "n")),
+                N.DynBandMarginOut, "dyn_batch_fetch_band_margin"),
+    "rescue": ((("rescue", np.uint8, "n"), ("guide_rounds", _U32, "n"), ("guide_converged", _U32, "n")),
+               None, "dyn_batch_fetch_rescue"),
+}
+
+
 def format_csv(aligner: "Aligner", res: AlignBatchResult, sequences: Sequence[str], readids: Sequence[str],
                signalids: Sequence[str], sig_offsets: Sequence[int], last_index: Sequence[int],
                threads: int = 8, compact: bool = False, seqs_packed=None):
@@ -309,28 +273,11 @@ def format_csv(aligner: "Aligner", res: AlignBatchResult, sequences: Sequence[st
     begin = np.zeros(n, dtype=np.uint64)
     end = np.zeros(n, dtype=np.uint64)
     L = N.lib()
-    # the signal levels when the result carries them (Aligner.set_event_stats): three more columns per row
-    ev = None
-    if res.level_mean is not None:
-        ev = C.byref(N.DynEventOut(_ptr(res.level_mean, N.c_double_p), _ptr(res.level_stdv, N.c_double_p),
-                                   _ptr(res.level_median, N.c_double_p), res.cap))
-    # ... and the segment scores (Aligner.set_segment_scores): three more after those
-    sc = None
-    if res.median_delta is not None:
-        sc = C.byref(N.DynScoreOut(_ptr(res.median_delta, N.c_double_p), _ptr(res.mad_delta, N.c_double_p),
-                                   _ptr(res.homogeneity, N.c_double_p), res.cap))
-    # ... and the border confidence (Aligner.set_border_confidence): two more after those
-    bd = None
-    if res.border_probability is not None:
-        bd = C.byref(N.DynBorderOut(_ptr(res.border_probability, N.c_double_p),
-                                    _ptr(res.border_window_probability, N.c_double_p), res.cap))
-    # ... and the posterior samples (Aligner.set_posterior_samples): one more field after those
-    sm = None
-    if res.sample_starts is not None:
-        sm = C.byref(N.DynSampleOut(_ptr(res.sample_starts, N.c_u32_p), _ptr(res.sample_dead, N.c_u32_p), res.cap, res.n,
-                                    res.sample_starts.shape[0]))
-    # ... and the credible intervals (Aligner.set_border_interval): four more after those
-    bi = C.byref(res._interval_out()) if res.border_lo is not None else None
+    # the optional columns the result carries, in the order the rows hold them: the signal levels (Aligner.set_event_stats), the
+    # segment scores (set_segment_scores), the border confidence (set_border_confidence), the posterior samples
+    # (set_posterior_samples), the credible intervals (set_border_interval)
+    ev, sc, bd, sm, bi = (C.byref(res._out_struct(name)) if getattr(res, _OPTIONAL[name][0][0][0]) is not None else None
+                          for name in ("levels", "scores", "borders", "samples", "intervals"))
     cap = int(L.dyn_format_csv_bound_intervals(aligner._h, n, C.byref(res._c), ev, sc, bd, sm, bi, rid, sid))
     # one grow-only buffer per handle: first-touch page faults of a fresh 350 MB buffer cost ~100x
     # the formatting itself (15 ms per 1 024-read batch with warm pages)
@@ -405,9 +352,21 @@ class TrainBatchResult:
         }
 
 
+def _fetch_into(fetcher: str):
+    """the Batch / AsyncBatch method that calls ``fetcher`` (a dyn_batch_fetch_* of an optional result) on caller-owned arrays"""
+    def fetch(self, out) -> None:
+        rc = getattr(self._L, fetcher)(self._h, C.byref(out))
+        if rc != N.DYN_OK:
+            _raise(rc, self._al.last_error())
+    fetch.__doc__ = fetcher + " into caller-owned arrays (raises ValueError for a batch that did not ask)."
+    return fetch
+
+
 class Batch:
     """Staged form (dyn_batch_*): inputs are validated, k-mer coded and resident in HBM after
     construction; align()/train() only launch kernels; fetch() copies results back."""
+
+    _wants = JobWants()  # of the last align(): a batch never aligned has nothing optional to fetch
 
     def __init__(self, aligner: "Aligner", signals, sig_offsets, seqs: bytes, seq_offsets, raw=None):
         """raw = None: ``signals`` are normalised float64 samples. raw = dict(shift, scale, window,
@@ -454,14 +413,7 @@ class Batch:
         self.close()
 
     def align(self, calc_probabilities: bool = True) -> None:
-        self._levels = bool(calc_probabilities) and self._al._event_stats  # the switch at submission decides
-        self._rescale = bool(calc_probabilities) and self._al._rescale > 0
-        self._scores = bool(calc_probabilities) and self._al._segment_scores > 0
-        self._borders = bool(calc_probabilities) and self._al._border_confidence > 0
-        self._samples = self._al._ticket_samples(bool(calc_probabilities))
-        self._intervals = self._al._ticket_intervals(bool(calc_probabilities))
-        self._margins = bool(calc_probabilities) and self._al._band_margin
-        self._rescued = self._al._ticket_rescue(bool(calc_probabilities))
+        self._wants = self._al._job_wants(calc_probabilities)  # the switches at submission decide what fetch() brings
         rc = self._L.dyn_batch_align(self._h, int(bool(calc_probabilities)))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
@@ -531,57 +483,16 @@ class Batch:
         rc = self._L.dyn_batch_fetch(self._h, C.byref(out._c))
         if rc != N.DYN_OK:
             _raise(rc, self._al.last_error())
-        out._fetch_levels(self._L, self._h, self._al, getattr(self, "_levels", False))
-        out._fetch_rescale(self._L, self._h, self._al, getattr(self, "_rescale", False))
-        out._fetch_scores(self._L, self._h, self._al, getattr(self, "_scores", False))
-        out._fetch_borders(self._L, self._h, self._al, getattr(self, "_borders", False))
-        out._fetch_samples(self._L, self._h, self._al, getattr(self, "_samples", 0))
-        out._fetch_intervals(self._L, self._h, self._al, getattr(self, "_intervals", False))
-        out._fetch_band_margin(self._L, self._h, self._al, getattr(self, "_margins", False))
-        out._fetch_rescue(self._L, self._h, self._al, getattr(self, "_rescued", False))
+        out._fetch_optional(self._L, self._h, self._al, self._wants)
         return out
 
-    def fetch_events(self, out: N.DynEventOut) -> None:
-        """dyn_batch_fetch_events into caller-owned columns (raises ValueError for a batch that did not ask)."""
-        rc = self._L.dyn_batch_fetch_events(self._h, C.byref(out))
-        if rc != N.DYN_OK:
-            _raise(rc, self._al.last_error())
-
-    def fetch_scores(self, out: N.DynScoreOut) -> None:
-        """dyn_batch_fetch_scores into caller-owned columns (raises ValueError for a batch that did not ask)."""
-        rc = self._L.dyn_batch_fetch_scores(self._h, C.byref(out))
-        if rc != N.DYN_OK:
-            _raise(rc, self._al.last_error())
-
-    def fetch_borders(self, out: N.DynBorderOut) -> None:
-        """dyn_batch_fetch_borders into caller-owned columns (raises ValueError for a batch that did not ask)."""
-        rc = self._L.dyn_batch_fetch_borders(self._h, C.byref(out))
-        if rc != N.DYN_OK:
-            _raise(rc, self._al.last_error())
-
-    def fetch_samples(self, out: N.DynSampleOut) -> None:
-        """dyn_batch_fetch_samples into caller-owned arrays (raises ValueError for a batch that did not ask)."""
-        rc = self._L.dyn_batch_fetch_samples(self._h, C.byref(out))
-        if rc != N.DYN_OK:
-            _raise(rc, self._al.last_error())
-
-    def fetch_intervals(self, out: N.DynBorderIntervalOut) -> None:
-        """dyn_batch_fetch_intervals into caller-owned arrays (raises ValueError for a batch that did not ask)."""
-        rc = self._L.dyn_batch_fetch_intervals(self._h, C.byref(out))
-        if rc != N.DYN_OK:
-            _raise(rc, self._al.last_error())
-
-    def fetch_band_margin(self, out: N.DynBandMarginOut) -> None:
-        """dyn_batch_fetch_band_margin into caller-owned arrays (raises ValueError for a batch that did not ask)."""
-        rc = self._L.dyn_batch_fetch_band_margin(self._h, C.byref(out))
-        if rc != N.DYN_OK:
-            _raise(rc, self._al.last_error())
-
-    def fetch_rescale(self, out: N.DynRescaleOut) -> None:
-        """dyn_batch_fetch_rescale into caller-owned arrays (raises ValueError for a batch that did not ask)."""
-        rc = self._L.dyn_batch_fetch_rescale(self._h, C.byref(out))
-        if rc != N.DYN_OK:
-            _raise(rc, self._al.last_error())
+    fetch_events = _fetch_into("dyn_batch_fetch_events")              # out: N.DynEventOut
+    fetch_scores = _fetch_into("dyn_batch_fetch_scores")              # N.DynScoreOut
+    fetch_borders = _fetch_into("dyn_batch_fetch_borders")            # N.DynBorderOut
+    fetch_samples = _fetch_into("dyn_batch_fetch_samples")            # N.DynSampleOut
+    fetch_intervals = _fetch_into("dyn_batch_fetch_intervals")        # N.DynBorderIntervalOut
+    fetch_band_margin = _fetch_into("dyn_batch_fetch_band_margin")    # N.DynBandMarginOut
+    fetch_rescale = _fetch_into("dyn_batch_fetch_rescale")            # N.DynRescaleOut
 
     def fetch_train(self, pooled: bool = False) -> TrainBatchResult:
         out = TrainBatchResult(self.n, self.capacity, self._al.num_kmers, pooled)
@@ -635,26 +546,15 @@ class AsyncBatch:
     handle's pipeline; ``wait()`` returns the filled result object. The input arrays are kept alive here
     (the library reads them until the batch is complete)."""
 
-    def __init__(self, aligner: "Aligner", handle, result, keep, levels: bool = False, rescale: bool = False,
-                 scores: bool = False, borders: bool = False, margins: bool = False, auto_guide=None, rescue: bool = False,
-                 samples: int = 0, intervals: bool = False):
+    def __init__(self, aligner: "Aligner", handle, result, keep, wants: JobWants):
         self._al = aligner
         self._L = N.lib()
         self._h = handle
         self.result = result
         self._keep = keep
         self._waited = False
-        self._levels = levels  # an align ticket submitted with the event-stats switch on (and calc_probabilities)
-        self._rescale = rescale  # ... with the rescale switch on
-        self._scores = scores  # ... with the segment-scores switch on
-        self._borders = borders  # ... with the border-confidence switch on
-        self._samples = samples  # ... with the posterior-samples switch on: its count
-        self._intervals = intervals  # ... with the border-interval switch on
-        self._margins = margins  # ... with the band-margin switch on (tickets report margins; they are never retried)
-        # ... with the auto-guide switch on (Aligner.set_auto_guide): (alignments per read, the ticket's sample offsets), else None
-        self._auto_guide = auto_guide
-        self._rescued = rescue  # ... with the guide-rescue switch on (Aligner.set_guide_rescue)
-        self._sig_off = auto_guide[1] if auto_guide is not None else None  # what Batch.guide cuts the flat guide at
+        self._wants = wants  # what an align ticket took of the aligner's switches at its submission (a train ticket: all off)
+        self._sig_off = wants.auto_guide[1] if wants.auto_guide is not None else None  # what Batch.guide cuts the flat guide at
 
     def wait(self):
         if not self._waited:
@@ -663,19 +563,11 @@ class AsyncBatch:
             if rc != N.DYN_OK:
                 _raise(rc, self._al.last_error())
             if isinstance(self.result, AlignBatchResult):
-                self.result._fetch_levels(self._L, self._h, self._al, self._levels)
-                self.result._fetch_rescale(self._L, self._h, self._al, self._rescale)
-                self.result._fetch_scores(self._L, self._h, self._al, self._scores)
-                self.result._fetch_borders(self._L, self._h, self._al, self._borders)
-                self.result._fetch_samples(self._L, self._h, self._al, self._samples)
-                self.result._fetch_intervals(self._L, self._h, self._al, self._intervals)
-                self.result._fetch_band_margin(self._L, self._h, self._al, self._margins)
                 # a result object refilled from an earlier ticket must not keep that ticket's counts
-                self.result.guide_rounds = self.result.guide_converged = self.result.guides = None
-                if self._auto_guide is not None and self._auto_guide[0] != 1:
+                self.result.rescue = self.result.guide_rounds = self.result.guide_converged = self.result.guides = None
+                self.result._fetch_optional(self._L, self._h, self._al, self._wants)
+                if self._wants.auto_guide is not None and self._wants.auto_guide[0] != 1:
                     self.result.guide_rounds, self.result.guide_converged = Batch.guide_rounds(self)
-                self.result.rescue = None
-                self.result._fetch_rescue(self._L, self._h, self._al, self._rescued)
         return self.result
 
     @property
@@ -686,7 +578,7 @@ class AsyncBatch:
         """dyn_batch_fetch_guide on a ticket submitted under ``Aligner.set_auto_guide``: every read's int32 guide of its last
         alignment, one entry per sample (ValueError for a ticket that was not guided)"""
         self.wait()
-        if self._auto_guide is None:
+        if self._wants.auto_guide is None:
             raise ValueError("AsyncBatch.guide: the ticket was submitted without Aligner.set_auto_guide")
         return Batch.guide(self)
 
@@ -950,10 +842,6 @@ class Aligner:
             _raise(rc, self.last_error())
         self._border_interval = float(mass)
 
-    def _ticket_intervals(self, calc_probabilities: bool) -> bool:
-        """whether an align job / ticket submitted now carries the interval columns"""
-        return bool(calc_probabilities) and self._border_interval > 0 and self._ctor[2] not in ("ntk", "resquiggle")
-
     def set_posterior_samples(self, count: int, seed: int = 0) -> None:
         """dyn_aligner_set_posterior_samples: align(calc_probabilities=True) jobs submitted while ``count`` (0 .. 64) > 0 also
         draw ``count`` complete alignments of every read from the posterior distribution over alignments, on the GPU from the
@@ -970,10 +858,6 @@ class Aligner:
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
         self._posterior_samples = (int(count), int(seed) & 0xFFFFFFFFFFFFFFFF)
-
-    def _ticket_samples(self, calc_probabilities: bool) -> int:
-        """the sample count of an align job / ticket submitted now (0: it does not sample)"""
-        return self._posterior_samples[0] if calc_probabilities and self._ctor[2] not in ("ntk", "resquiggle") else 0
 
     def set_auto_guide(self, half_width: int, refine: int = 8) -> None:
         """dyn_aligner_set_auto_guide: ``align_async`` / ``align_raw_async`` / ``align_vbz_async`` tickets with
@@ -1007,15 +891,17 @@ class Aligner:
             _raise(rc, self.last_error())
         self._guide_rescue = (int(min_margin), int(half_width), int(refine)) if int(half_width) > 0 else (0, 0, 8)
 
-    def _ticket_rescue(self, calc_probabilities: bool) -> bool:
-        """does an align job / ticket submitted now run under the guide-rescue switch?"""
-        return self._guide_rescue[1] > 0 and calc_probabilities and self._ctor[2] not in ("ntk", "resquiggle")
-
-    def _ticket_guide(self, calc_probabilities: bool, offsets):
-        """what AsyncBatch keeps of the auto-guide switch for an align ticket submitted now"""
-        if not (self._auto_guide[0] > 0 and calc_probabilities and self._ctor[2] not in ("ntk", "resquiggle")):
-            return None
-        return (self._auto_guide[1], offsets)
+    def _job_wants(self, calc_probabilities: bool, sig_off=None) -> JobWants:
+        """What an align job submitted NOW takes of the switches. ``sig_off``: the sample offsets of a TICKET (the auto-guide switch
+        concerns tickets alone). The Z-only job takes nothing; modes ntk / resquiggle have no samples, intervals, rescue or guide."""
+        if not calc_probabilities:
+            return JobWants()
+        plain = self._ctor[2] not in ("ntk", "resquiggle")
+        return JobWants(levels=bool(self._event_stats), rescale=self._rescale > 0, scores=self._segment_scores > 0,
+                        borders=self._border_confidence > 0, samples=self._posterior_samples[0] if plain else 0,
+                        intervals=plain and self._border_interval > 0, margins=bool(self._band_margin),
+                        rescue=plain and self._guide_rescue[1] > 0,
+                        auto_guide=(self._auto_guide[1], sig_off) if plain and sig_off is not None and self._auto_guide[0] > 0 else None)
 
     def set_rescale(self, iters: int) -> None:
         """dyn_aligner_set_rescale: align(calc_probabilities=True) jobs submitted while ``iters`` (0 .. 8) > 0 align every
@@ -1232,15 +1118,7 @@ class Aligner:
                                            C.byref(h))
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
-        return AsyncBatch(self, h, out, (sig, sig_off, seqs, seq_off), levels=self._event_stats and bool(calc_probabilities),
-                          rescale=self._rescale > 0 and bool(calc_probabilities),
-                          scores=self._segment_scores > 0 and bool(calc_probabilities),
-                          borders=self._border_confidence > 0 and bool(calc_probabilities),
-                          margins=self._band_margin and bool(calc_probabilities),
-                          auto_guide=self._ticket_guide(bool(calc_probabilities), sig_off),
-                          rescue=self._ticket_rescue(bool(calc_probabilities)),
-                          samples=self._ticket_samples(bool(calc_probabilities)),
-                          intervals=self._ticket_intervals(bool(calc_probabilities)))
+        return AsyncBatch(self, h, out, (sig, sig_off, seqs, seq_off), wants=self._job_wants(calc_probabilities, sig_off))
 
     def _raw_args(self, raw, shift, scale, calibration=None):
         scattered = isinstance(raw, (list, tuple))
@@ -1290,15 +1168,7 @@ class Aligner:
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
         return AsyncBatch(self, h, out, (raw, raw_off, shift, scale, seqs, seq_off, cal),
-                          levels=self._event_stats and bool(calc_probabilities),
-                          rescale=self._rescale > 0 and bool(calc_probabilities),
-                          scores=self._segment_scores > 0 and bool(calc_probabilities),
-                          borders=self._border_confidence > 0 and bool(calc_probabilities),
-                          margins=self._band_margin and bool(calc_probabilities),
-                          auto_guide=self._ticket_guide(bool(calc_probabilities), raw_off),
-                          rescue=self._ticket_rescue(bool(calc_probabilities)),
-                          samples=self._ticket_samples(bool(calc_probabilities)),
-                          intervals=self._ticket_intervals(bool(calc_probabilities)))
+                          wants=self._job_wants(calc_probabilities, raw_off))
 
     def align_vbz_async(self, chunks, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 3,
                         n_sigmas: float = 3.0, f32: bool = False, calc_probabilities: bool = True,
@@ -1332,15 +1202,7 @@ class Aligner:
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
         return AsyncBatch(self, h, out, (ptrs, nbytes, samples, read_off, skip, raw_off, shift, scale, seqs, seq_off, cal),
-                          levels=self._event_stats and bool(calc_probabilities),
-                          rescale=self._rescale > 0 and bool(calc_probabilities),
-                          scores=self._segment_scores > 0 and bool(calc_probabilities),
-                          borders=self._border_confidence > 0 and bool(calc_probabilities),
-                          margins=self._band_margin and bool(calc_probabilities),
-                          auto_guide=self._ticket_guide(bool(calc_probabilities), raw_off),
-                          rescue=self._ticket_rescue(bool(calc_probabilities)),
-                          samples=self._ticket_samples(bool(calc_probabilities)),
-                          intervals=self._ticket_intervals(bool(calc_probabilities)))
+                          wants=self._job_wants(calc_probabilities, raw_off))
 
     def train_raw_async(self, raw, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 7,
                         n_sigmas: float = 5.0, f32: bool = True, pooled: bool = False,
@@ -1361,7 +1223,7 @@ class Aligner:
                                                C.byref(h))
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
-        return AsyncBatch(self, h, out, (raw, raw_off, shift, scale, seqs, seq_off, cal))
+        return AsyncBatch(self, h, out, (raw, raw_off, shift, scale, seqs, seq_off, cal), wants=JobWants())
 
     def segment_capacity(self, seq_offsets) -> int:
         """dyn_segment_capacity: rows to allocate for a batch with these sequence offsets."""
@@ -1383,7 +1245,7 @@ class Aligner:
                                            _ptr(out.pooled, N.c_double_p) if pooled else None, C.byref(h))
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
-        return AsyncBatch(self, h, out, (sig, sig_off, seqs, seq_off))
+        return AsyncBatch(self, h, out, (sig, sig_off, seqs, seq_off), wants=JobWants())
 
     def align_batch(self, signals: Sequence, sequences: Sequence[str], calc_probabilities: bool = True) -> AlignBatchResult:
         with self.batch(signals, sequences) as b:

@@ -146,17 +146,13 @@ static uint64_t merge_reads_per_slot() {  // DYN_MERGE_READS_PER_SLOT: experimen
 }
 static uint64_t merge_max_reads(const dyn_aligner* a) { return merge_reads_per_slot() * (uint64_t)a->n_cus * dynk::WAVES_PER_CU; }
 static bool mergeable(const dyn_batch* x) {
-  if (x->ps_want) return false;  // posterior samples: the read's index in its OWN ticket keys the random stream
   // batches that leave the waves underfilled (fewer than 1.5 reads per wave slot): a batch of four reads per slot balances
   // by itself, and merging those only makes the pipeline lumpy
-  // (a self-guided ticket carries a guide of its own and takes the banded-lattice kernel: never merged)
-  // (nor is a ticket under the guide rescue: its list of reads to re-align is its own)
-  return x->job != DynJob::Train && x->ag_want == 0 && x->gr_hw == 0 && x->n > 0 && 2 * x->n <= 3 * (uint64_t)x->a->n_cus * dynk::WAVES_PER_CU;
+  // (JobOptions::merges: a sampling ticket, a self-guided one and one under the guide rescue run alone)
+  return x->job != DynJob::Train && x->want.merges() && x->n > 0 && 2 * x->n <= 3 * (uint64_t)x->a->n_cus * dynk::WAVES_PER_CU;
 }
 static bool same_kind(const dyn_batch* x, const dyn_batch* y) {
-  if (x->job != y->job || x->has_raw != y->has_raw || x->ev_want != y->ev_want || x->rs_want != y->rs_want || x->sc_want != y->sc_want ||
-      x->bc_want != y->bc_want || x->bi_want != y->bi_want)
-    return false;
+  if (x->job != y->job || x->has_raw != y->has_raw || !x->want.same_launch(y->want)) return false;
   if (!x->has_raw) return true;
   const RawSource &p = x->raw_src, &q = y->raw_src;
   return p.vbz == q.vbz && p.dtype == q.dtype && p.window == q.window && p.n_sigmas == q.n_sigmas && p.compute_f32 == q.compute_f32;
@@ -215,27 +211,21 @@ std::shared_ptr<BatchGroup> Pipeline::merge(const std::vector<dyn_batch*>& ticke
   attach_cache(g);
   g->n = n;
   g->job = first->job;
-  g->ev_want = first->ev_want;  // (same_kind: every member asked alike)
-  g->rs_want = first->rs_want;
-  g->sc_want = first->sc_want;
-  g->bc_want = first->bc_want;
-  g->bi_want = first->bi_want;
-  // the per-k-mer summary is snapshot per ticket and same_kind does not look at it: the launch sums the members that asked
-  for (dyn_batch* t : tickets) {
-    if (!t->ks_want || !t->n) continue;
-    g->ks_want = true;
+  g->want = first->want.launch_wide();  // (same_kind: every member asked alike)
+  // the per-k-mer summary and the band margins are snapshot per ticket and same_kind does not look at them: the launch sums /
+  // computes them for the members that asked
+  auto add_range = [](std::vector<std::pair<uint32_t, uint32_t>>& ranges, const dyn_batch* t) {
     const uint32_t lo = (uint32_t)t->g_read0, hi = (uint32_t)(t->g_read0 + t->n);
-    if (!g->ks_ranges.empty() && g->ks_ranges.back().second == lo) g->ks_ranges.back().second = hi;
-    else g->ks_ranges.emplace_back(lo, hi);
-  }
-  // ... and so are the band margins: the launch computes them for the members that asked
+    if (!ranges.empty() && ranges.back().second == lo) ranges.back().second = hi;
+    else ranges.emplace_back(lo, hi);
+  };
   for (dyn_batch* t : tickets) {
-    if (!t->bm_want || !t->n) continue;
-    g->bm_want = true;
-    const uint32_t lo = (uint32_t)t->g_read0, hi = (uint32_t)(t->g_read0 + t->n);
-    if (!g->bm_ranges.empty() && g->bm_ranges.back().second == lo) g->bm_ranges.back().second = hi;
-    else g->bm_ranges.emplace_back(lo, hi);
+    if (!t->n) continue;
+    if (t->want.kmer_summary) add_range(g->ks_ranges, t);
+    if (t->want.band_margin) add_range(g->bm_ranges, t);
   }
+  g->want.kmer_summary = !g->ks_ranges.empty();
+  g->want.band_margin = !g->bm_ranges.empty();
   g->in_sig_offsets = grp->sig_offsets.data();
   g->in_seqs = grp->seqs.data();
   g->in_seq_offsets = grp->seq_offsets.data();
@@ -538,13 +528,13 @@ int Pipeline::front_stage(dyn_batch* b) {
   }
   // a self-guided ticket (dyn_aligner_set_auto_guide): its guide is made here, behind its preprocessing on the compute stream,
   // and enqueue_job then sizes arenas and groups as for a synchronous guided batch
-  if (b->ag_want) {
-    rc = enqueue_auto_guide(b, b->ag_want);
+  if (b->want.auto_guide_hw) {
+    rc = enqueue_auto_guide(b, b->want.auto_guide_hw);
     if (rc != DYN_OK) {
       b->error = last_error_of(a);
       return rc;
     }
-    b->guide_refine = b->ag_rounds;
+    b->guide_refine = b->want.auto_guide_rounds;
   }
   rc = enqueue_job(b, b->job);  // records ev_done behind the batch's last kernel
   if (rc != DYN_OK) {
@@ -768,16 +758,9 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
     return DYN_ERR_INVALID_ARGUMENT;
   }
   *ticket = nullptr;
-  // the guide rescue (dyn_aligner_set_guide_rescue) concerns align tickets with probabilities; it pairs with none of the switches
-  // that re-align or read the lattice (refused before anything is started: the same text with and without a device)
-  const uint32_t gr_hw = (job == DynJob::AlignFull && !a->ntk) ? a->rescue_hw : 0u;
-  if (gr_hw) {
-    if (const char* other = guide_rescue_conflict(a)) {
-      std::lock_guard<std::mutex> elk(a->err_mu);
-      a->last_error = std::string("dyn_batch_align_async: dyn_aligner_set_guide_rescue is on, which does not combine with ") + other;
-      return DYN_ERR_INVALID_ARGUMENT;
-    }
-  }
+  // what the ticket takes of the handle's switches (refused before anything is started: the same text with and without a device)
+  JobOptions want;
+  if (int rc = resolve_job_options(a, job, true, false, "dyn_batch_align_async", &want)) return rc;
   {
     std::lock_guard<std::mutex> lk(a->mu);
     int rc = need_device(a);
@@ -800,53 +783,13 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
       return DYN_ERR_INVALID_ARGUMENT;
     }
   }
-  // the self-guided band (dyn_aligner_set_auto_guide) concerns align tickets with probabilities; it pairs with neither of the two
-  // switches a synchronous guided batch refuses (run_job_sync)
-  const uint32_t ag_hw = (job == DynJob::AlignFull && !a->ntk) ? a->auto_guide_hw : 0u;
-  if (ag_hw && (a->rescale_iters > 0 || a->border_confidence > 0)) {
-    std::lock_guard<std::mutex> elk(a->err_mu);
-    a->last_error = std::string("dyn_batch_align_async: dyn_aligner_set_auto_guide is on, which does not combine with ") +
-                    (a->rescale_iters > 0 ? "dyn_aligner_set_rescale(a, iters > 0)" : "dyn_aligner_set_border_confidence(a, window > 0)");
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  // posterior samples (dyn_aligner_set_posterior_samples): as run_job_sync refuses them
-  const int ps = (job == DynJob::AlignFull && !a->ntk) ? a->posterior_samples : 0;
-  if (ps) {
-    if (const char* other = posterior_samples_conflict(a)) {
-      std::lock_guard<std::mutex> elk(a->err_mu);
-      a->last_error = std::string("dyn_batch_align_async: dyn_aligner_set_posterior_samples is on, which does not combine with ") + other;
-      return DYN_ERR_INVALID_ARGUMENT;
-    }
-  }
-  // credible intervals (dyn_aligner_set_border_interval): as run_job_sync refuses them
-  const double bi = (job == DynJob::AlignFull && !a->ntk) ? a->border_interval : 0.0;
-  if (bi > 0) {
-    if (const char* other = border_interval_conflict(a)) {
-      std::lock_guard<std::mutex> elk(a->err_mu);
-      a->last_error = std::string("dyn_batch_align_async: dyn_aligner_set_border_interval is on, which does not combine with ") + other;
-      return DYN_ERR_INVALID_ARGUMENT;
-    }
-  }
   dyn_batch* b = new dyn_batch();
   b->a = a;
   attach_cache(b);
   b->n = n_reads;
   b->async = true;
-  b->gr_hw = gr_hw;
-  b->gr_margin = a->rescue_margin;
-  b->gr_rounds = gr_hw ? a->rescue_rounds : 1u;
-  b->ag_want = ag_hw;
-  b->ag_rounds = ag_hw ? a->auto_guide_rounds : 1u;
   b->job = job;
-  b->ev_want = a->event_stats;
-  b->rs_want = a->rescale_iters;
-  b->ks_want = a->kmer_summary;
-  b->bm_want = a->band_margin;
-  b->sc_want = a->segment_scores;
-  b->bc_want = a->border_confidence;
-  b->bi_want = bi;
-  b->ps_want = ps;
-  b->ps_seed = a->sample_seed;
+  b->want = want;
   b->in_signals = signals;
   if (rs) {
     b->has_raw = true;

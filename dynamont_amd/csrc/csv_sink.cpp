@@ -82,12 +82,9 @@ struct Item {
 }  // namespace
 
 namespace dyneng {
-// DYN_OK when the ticket was submitted with the handle's event-stats switch on (dynamont_mi.cpp); else the handle's message
-int batch_check_events(dyn_batch* b);
-int batch_check_scores(dyn_batch* b);
-int batch_check_borders(dyn_batch* b);
-int batch_check_samples(dyn_batch* b);
-int batch_check_intervals(dyn_batch* b);
+// DYN_OK when the ticket was submitted with the switch on whose output `csv_flag` (one DYN_CSV_* bit) writes (dynamont_mi.cpp);
+// else the handle's message
+int batch_check_output(dyn_batch* b, uint32_t csv_flag);
 uint32_t batch_sample_count(const dyn_batch* b);  // the ticket's K
 }
 
@@ -277,67 +274,51 @@ struct dyn_csv_sink {
     begin.resize(it.n);
     end.resize(it.n);
     for (uint64_t i = 0; i < it.n; ++i) last_index[i] = (int64_t)it.signal_lengths[i] + it.sig_offsets[i];
+    const uint64_t cap = it.res->seg_offsets ? it.res->seg_offsets[it.n] : 0;
+    // the columns of one opt-in output: room for `elems`, the batch's values fetched into them
+    auto fetch = [&](auto& cols, uint64_t elems, auto&& fetch_into, const char* label) {
+      cols.resize(std::max<uint64_t>(1, elems));
+      if (fetch_into() == DYN_OK) return true;
+      std::lock_guard<std::mutex> lk(m);
+      fail(std::string(label) + dyn_aligner_last_error(it.a));
+      return false;
+    };
     dyn_event_out ev{};
-    if (events) {
-      const uint64_t cap = it.res->seg_offsets ? it.res->seg_offsets[it.n] : 0;
-      ev_cols.resize(std::max<uint64_t>(1, 3 * cap));
-      ev = dyn_event_out{ev_cols.data(), ev_cols.data() + cap, ev_cols.data() + 2 * cap, cap};
-      if (dyn_batch_fetch_events(it.ticket, &ev) != DYN_OK) {
-        std::lock_guard<std::mutex> lk(m);
-        fail(std::string("batch levels: ") + dyn_aligner_last_error(it.a));
-        return;
-      }
-    }
-    const dyn_event_out* evp = events ? &ev : nullptr;
+    if (events && !fetch(ev_cols, 3 * cap, [&] {
+          ev = dyn_event_out{ev_cols.data(), ev_cols.data() + cap, ev_cols.data() + 2 * cap, cap};
+          return dyn_batch_fetch_events(it.ticket, &ev);
+        }, "batch levels: "))
+      return;
     dyn_score_out sc{};
-    if (scores) {
-      const uint64_t cap = it.res->seg_offsets ? it.res->seg_offsets[it.n] : 0;
-      sc_cols.resize(std::max<uint64_t>(1, 3 * cap));
-      sc = dyn_score_out{sc_cols.data(), sc_cols.data() + cap, sc_cols.data() + 2 * cap, cap};
-      if (dyn_batch_fetch_scores(it.ticket, &sc) != DYN_OK) {
-        std::lock_guard<std::mutex> lk(m);
-        fail(std::string("batch segment scores: ") + dyn_aligner_last_error(it.a));
-        return;
-      }
-    }
-    const dyn_score_out* scp = scores ? &sc : nullptr;
+    if (scores && !fetch(sc_cols, 3 * cap, [&] {
+          sc = dyn_score_out{sc_cols.data(), sc_cols.data() + cap, sc_cols.data() + 2 * cap, cap};
+          return dyn_batch_fetch_scores(it.ticket, &sc);
+        }, "batch segment scores: "))
+      return;
     dyn_border_out bd{};
-    if (borders) {
-      const uint64_t cap = it.res->seg_offsets ? it.res->seg_offsets[it.n] : 0;
-      bd_cols.resize(std::max<uint64_t>(1, 2 * cap));
-      bd = dyn_border_out{bd_cols.data(), bd_cols.data() + cap, cap};
-      if (dyn_batch_fetch_borders(it.ticket, &bd) != DYN_OK) {
-        std::lock_guard<std::mutex> lk(m);
-        fail(std::string("batch border confidence: ") + dyn_aligner_last_error(it.a));
-        return;
-      }
-    }
-    const dyn_border_out* bdp = borders ? &bd : nullptr;
+    if (borders && !fetch(bd_cols, 2 * cap, [&] {
+          bd = dyn_border_out{bd_cols.data(), bd_cols.data() + cap, cap};
+          return dyn_batch_fetch_borders(it.ticket, &bd);
+        }, "batch border confidence: "))
+      return;
     dyn_sample_out sm{};
-    if (samples) {
-      const uint64_t cap = it.res->seg_offsets ? it.res->seg_offsets[it.n] : 0;
-      const uint32_t K = dyneng::batch_sample_count(it.ticket);
-      sm_cols.resize(std::max<uint64_t>(1, K * cap + it.n));
-      sm = dyn_sample_out{sm_cols.data(), sm_cols.data() + K * cap, cap, it.n, K};
-      if (dyn_batch_fetch_samples(it.ticket, &sm) != DYN_OK) {
-        std::lock_guard<std::mutex> lk(m);
-        fail(std::string("batch posterior samples: ") + dyn_aligner_last_error(it.a));
-        return;
-      }
-    }
-    const dyn_sample_out* smp = samples ? &sm : nullptr;
+    const uint32_t K = samples ? dyneng::batch_sample_count(it.ticket) : 0;
+    if (samples && !fetch(sm_cols, K * cap + it.n, [&] {
+          sm = dyn_sample_out{sm_cols.data(), sm_cols.data() + K * cap, cap, it.n, K};
+          return dyn_batch_fetch_samples(it.ticket, &sm);
+        }, "batch posterior samples: "))
+      return;
     dyn_border_interval_out bi{};
-    if (intervals) {
-      const uint64_t cap = it.res->seg_offsets ? it.res->seg_offsets[it.n] : 0;
-      bi_cols.resize(std::max<uint64_t>(1, 3 * cap));
-      uint32_t* q = reinterpret_cast<uint32_t*>(bi_cols.data() + 2 * cap);
-      bi = dyn_border_interval_out{q, q + cap, bi_cols.data(), bi_cols.data() + cap, cap};
-      if (dyn_batch_fetch_intervals(it.ticket, &bi) != DYN_OK) {
-        std::lock_guard<std::mutex> lk(m);
-        fail(std::string("batch border intervals: ") + dyn_aligner_last_error(it.a));
-        return;
-      }
-    }
+    if (intervals && !fetch(bi_cols, 3 * cap, [&] {
+          uint32_t* q = reinterpret_cast<uint32_t*>(bi_cols.data() + 2 * cap);
+          bi = dyn_border_interval_out{q, q + cap, bi_cols.data(), bi_cols.data() + cap, cap};
+          return dyn_batch_fetch_intervals(it.ticket, &bi);
+        }, "batch border intervals: "))
+      return;
+    const dyn_event_out* evp = events ? &ev : nullptr;
+    const dyn_score_out* scp = scores ? &sc : nullptr;
+    const dyn_border_out* bdp = borders ? &bd : nullptr;
+    const dyn_sample_out* smp = samples ? &sm : nullptr;
     const dyn_border_interval_out* bip = intervals ? &bi : nullptr;
     const uint64_t bound = dyn_format_csv_bound_intervals(it.a, it.n, it.res, evp, scp, bdp, smp, bip, it.readids, it.signalids);
     std::shared_ptr<Blob> blob;
@@ -510,16 +491,14 @@ int dyn_csv_sink_submit_bases(dyn_csv_sink* s, dyn_aligner* a, dyn_batch* ticket
                               const uint32_t* stored_bases) {
   if (!s || !a || !ticket || !res || !seq_offsets || (n_reads && (!seqs || !readids || !signalids || !sig_offsets || !signal_lengths)))
     return DYN_ERR_INVALID_ARGUMENT;
-  if (s->events)
-    if (int rc = dyneng::batch_check_events(ticket)) return rc;  // the message is the handle's (dyn_aligner_last_error)
-  if (s->scores)
-    if (int rc = dyneng::batch_check_scores(ticket)) return rc;
-  if (s->borders)
-    if (int rc = dyneng::batch_check_borders(ticket)) return rc;
-  if (s->samples)
-    if (int rc = dyneng::batch_check_samples(ticket)) return rc;
-  if (s->intervals)
-    if (int rc = dyneng::batch_check_intervals(ticket)) return rc;
+  const std::pair<bool, uint32_t> written[] = {{s->events, DYN_CSV_EVENT_STATS},
+                                               {s->scores, DYN_CSV_SEGMENT_SCORES},
+                                               {s->borders, DYN_CSV_BORDER_CONFIDENCE},
+                                               {s->samples, DYN_CSV_POSTERIOR_SAMPLES},
+                                               {s->intervals, DYN_CSV_BORDER_INTERVAL}};
+  for (const auto& w : written)
+    if (w.first)
+      if (int rc = dyneng::batch_check_output(ticket, w.second)) return rc;  // the message is the handle's (dyn_aligner_last_error)
   {
     std::lock_guard<std::mutex> lk(s->m);
     if (s->closing) return DYN_ERR_INVALID_ARGUMENT;

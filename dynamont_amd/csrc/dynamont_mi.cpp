@@ -60,9 +60,10 @@ void attach_cache(dyn_batch* b) {
   dyneng::BufCache* c = &b->a->cache;
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bi, &b->d_ps, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
+                    &b->d_pathn, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
                     &b->d_resc_st, &b->d_resc_pp, &b->d_resc_pathn, &b->d_resc_segrow})
     d->cache = c;
+  for (OutputBuf& o : b->out) o.d.cache = c;
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref, &b->h_resc}) h->cache = c;
 }
 
@@ -534,7 +535,7 @@ int dyn_aligner_set_train_zcheck(dyn_aligner* a, int on) {
 
 int dyn_aligner_set_event_stats(dyn_aligner* a, int on) {
   if (!a) return DYN_ERR_INVALID_ARGUMENT;
-  a->event_stats = on != 0;
+  a->opt.event_stats = on != 0;
   return DYN_OK;
 }
 
@@ -545,7 +546,7 @@ int dyn_aligner_set_rescale(dyn_aligner* a, int iters) {
     a->last_error = "dyn_aligner_set_rescale: iters must be 0 .. 8, got " + std::to_string(iters);
     return DYN_ERR_INVALID_ARGUMENT;
   }
-  a->rescale_iters = iters;
+  a->opt.rescale_iters = iters;
   return DYN_OK;
 }
 
@@ -556,7 +557,7 @@ int dyn_aligner_set_segment_scores(dyn_aligner* a, int window) {
     a->last_error = "dyn_aligner_set_segment_scores: window must be 0 .. 256, got " + std::to_string(window);
     return DYN_ERR_INVALID_ARGUMENT;
   }
-  a->segment_scores = window;
+  a->opt.segment_scores = window;
   return DYN_OK;
 }
 
@@ -567,7 +568,7 @@ int dyn_aligner_set_border_confidence(dyn_aligner* a, int window) {
     a->last_error = "dyn_aligner_set_border_confidence: window must be 0 .. 256, got " + std::to_string(window);
     return DYN_ERR_INVALID_ARGUMENT;
   }
-  a->border_confidence = window;
+  a->opt.border_confidence = window;
   return DYN_OK;
 }
 
@@ -580,7 +581,7 @@ int dyn_aligner_set_border_interval(dyn_aligner* a, double mass) {
     a->last_error = std::string("dyn_aligner_set_border_interval: mass must be 0 or 0.01 .. 0.999, got ") + num;
     return DYN_ERR_INVALID_ARGUMENT;
   }
-  a->border_interval = mass;
+  a->opt.border_interval = mass;
   return DYN_OK;
 }
 
@@ -593,8 +594,8 @@ int dyn_aligner_set_posterior_samples(dyn_aligner* a, int count, uint64_t seed) 
   };
   if (count < 0 || count > DYN_POSTERIOR_SAMPLES_MAX) return fail("count must be 0 .. 64, got " + std::to_string(count));
   if (count > 0 && a->ntk) return fail("modes ntk / resquiggle have no align(calc_probabilities = 1) job whose lattice could be sampled");
-  a->posterior_samples = count;
-  a->sample_seed = seed;
+  a->opt.posterior_samples = count;
+  a->opt.sample_seed = seed;
   return DYN_OK;
 }
 
@@ -606,14 +607,14 @@ int dyn_aligner_set_auto_guide(dyn_aligner* a, uint32_t half_width, uint32_t max
     return DYN_ERR_INVALID_ARGUMENT;
   };
   if (half_width == 0) {  // off (max_rounds is not looked at)
-    a->auto_guide_hw = 0;
+    a->opt.auto_guide_hw = 0;
     return DYN_OK;
   }
   if (half_width > (uint32_t)dynk::WIDE_MAX_HALF_BAND)
     return fail("half_width " + std::to_string(half_width) + " is outside [1, " + std::to_string(dynk::WIDE_MAX_HALF_BAND) + "]");
   if (max_rounds < 1 || max_rounds > 64) return fail("max_rounds " + std::to_string(max_rounds) + " is outside [1, 64]");
-  a->auto_guide_hw = half_width;
-  a->auto_guide_rounds = max_rounds;
+  a->opt.auto_guide_hw = half_width;
+  a->opt.auto_guide_rounds = max_rounds;
   return DYN_OK;
 }
 
@@ -625,7 +626,7 @@ int dyn_aligner_set_guide_rescue(dyn_aligner* a, int min_margin, uint32_t half_w
     return DYN_ERR_INVALID_ARGUMENT;
   };
   if (half_width == 0) {  // off (the other two are not looked at)
-    a->rescue_hw = 0;
+    a->opt.rescue_hw = 0;
     return DYN_OK;
   }
   if (a->ntk) return fail("modes ntk / resquiggle have no align(calc_probabilities = 1) job to rescue");
@@ -633,9 +634,9 @@ int dyn_aligner_set_guide_rescue(dyn_aligner* a, int min_margin, uint32_t half_w
     return fail("half_width " + std::to_string(half_width) + " is outside [1, " + std::to_string(dynk::WIDE_MAX_HALF_BAND) + "]");
   if (min_margin < 0) return fail("min_margin " + std::to_string(min_margin) + " is negative");
   if (max_rounds < 1 || max_rounds > 64) return fail("max_rounds " + std::to_string(max_rounds) + " is outside [1, 64]");
-  a->rescue_margin = (uint32_t)min_margin;
-  a->rescue_rounds = max_rounds;
-  a->rescue_hw = half_width;
+  a->opt.rescue_margin = (uint32_t)min_margin;
+  a->opt.rescue_rounds = max_rounds;
+  a->opt.rescue_hw = half_width;
   return DYN_OK;
 }
 
@@ -648,7 +649,7 @@ int dyn_aligner_set_band_margin(dyn_aligner* a, int on) {
   }
   std::lock_guard<std::mutex> lk(a->mu);
   if (int rc = need_device(a)) return rc;
-  a->band_margin = on != 0;
+  a->opt.band_margin = on != 0;
   return DYN_OK;
 }
 
@@ -668,7 +669,7 @@ int dyn_aligner_set_kmer_summary(dyn_aligner* a, int on) {
     HIP_TRY(a, hipMemsetAsync(a->d_ksum.p, 0, bytes, a->s_get));
     HIP_TRY(a, hipStreamSynchronize(a->s_get));
   }
-  a->kmer_summary = on != 0;
+  a->opt.kmer_summary = on != 0;
   return DYN_OK;
 }
 
@@ -983,9 +984,10 @@ void dyn_batch_destroy(dyn_batch* b) {
   }
   for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
-                    &b->d_pathn, &b->d_ev, &b->d_sc, &b->d_bc, &b->d_bi, &b->d_ps, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
+                    &b->d_pathn, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
                     &b->d_resc_st, &b->d_resc_pp, &b->d_resc_pathn, &b->d_resc_segrow})
     d->release();
+  for (OutputBuf& o : b->out) o.d.release();
   for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref, &b->h_resc}) h->release();
   for (hipEvent_t e : b->events) (void)hipEventDestroy(e);
   for (hipEvent_t e : {b->ev_in, b->ev_done, b->ev_out})
@@ -1160,6 +1162,64 @@ int enqueue_auto_guide(dyn_batch* b, uint32_t half_width) {
 }
 }  // namespace dyneng
 
+namespace dyneng {
+namespace {
+// the switches the rules below speak of: the setter, and how a refusal names the switch when it is the OTHER one
+// (SW_GUIDE: no handle switch -- the batch carries a guide of its own, dyn_batch_set_guide / dyn_batch_auto_guide)
+enum Sw { SW_RESCALE, SW_CONFIDENCE, SW_INTERVAL, SW_SAMPLES, SW_AUTO_GUIDE, SW_RESCUE, SW_GUIDE };
+struct SwText {
+  const char *setter, *on;
+};
+const SwText SW_TEXT[] = {{"dyn_aligner_set_rescale", "(a, iters > 0)"},        {"dyn_aligner_set_border_confidence", "(a, window > 0)"},
+                          {"dyn_aligner_set_border_interval", "(a, mass > 0)"}, {"dyn_aligner_set_posterior_samples", "(a, count > 0)"},
+                          {"dyn_aligner_set_auto_guide", "(a, half_width > 0)"}, {"dyn_aligner_set_guide_rescue", "(a, half_width > 0)"},
+                          {nullptr, nullptr}};
+// (switch, what it does not combine with), in the order a job is checked: the first rule it violates is the one its refusal names.
+//   guide rescue: the three re-align or read the lattice of every read -- the rescue's second alignment has no place in their
+//     order; and a guided batch is not rescued
+//   auto-guide (the tickets' switch): what a synchronous guided batch refuses
+//   posterior samples: a sampled path is a walk through the lattice of the one plain alignment of a read in the diagonal band;
+//     the switches that re-align a read or align it inside a guide window have no such lattice to offer
+//   border interval: one lattice phase runs per launch for now (an INTERIM), and the switches that align a read
+//     inside a guide window have no diagonal lattice to offer
+const struct {
+  Sw sw, other;
+} RULES[] = {{SW_RESCUE, SW_RESCALE},     {SW_RESCUE, SW_CONFIDENCE},  {SW_RESCUE, SW_AUTO_GUIDE},   {SW_RESCUE, SW_GUIDE},
+             {SW_AUTO_GUIDE, SW_RESCALE}, {SW_AUTO_GUIDE, SW_CONFIDENCE},
+             {SW_SAMPLES, SW_GUIDE},      {SW_SAMPLES, SW_RESCALE},    {SW_SAMPLES, SW_AUTO_GUIDE},  {SW_SAMPLES, SW_RESCUE},
+             {SW_INTERVAL, SW_GUIDE},     {SW_INTERVAL, SW_CONFIDENCE}, {SW_INTERVAL, SW_SAMPLES},   {SW_INTERVAL, SW_AUTO_GUIDE},
+             {SW_INTERVAL, SW_RESCUE}};
+}  // namespace
+
+int resolve_job_options(dyn_aligner* a, DynJob job, bool ticket, bool guided, const char* api, JobOptions* out) {
+  JobOptions w = a->opt;
+  if (job != DynJob::AlignFull || a->ntk) {  // the four that concern align jobs with probabilities alone; the Z-only and the train job ignore them
+    w.rescue_hw = 0;
+    w.auto_guide_hw = 0;
+    w.posterior_samples = 0;
+    w.border_interval = 0.0;
+  }
+  const bool on[] = {w.rescale_iters > 0, w.border_confidence > 0, w.border_interval > 0, w.posterior_samples > 0,
+                     w.auto_guide_hw > 0, w.rescue_hw > 0,         guided};
+  for (const auto& r : RULES) {
+    if (!on[r.sw] || !on[r.other] || (r.sw == SW_AUTO_GUIDE && !ticket)) continue;
+    const SwText &x = SW_TEXT[r.sw], &y = SW_TEXT[r.other];
+    std::string msg = std::string(api) + ": ";
+    if (r.other != SW_GUIDE) msg += std::string(x.setter) + " is on, which does not combine with " + y.setter + y.on;
+    else if (r.sw == SW_RESCUE)
+      msg += "dyn_aligner_set_guide_rescue is on and the batch carries a guide (dyn_batch_set_guide / dyn_batch_auto_guide); a guided batch is not rescued";
+    else
+      msg += std::string("the batch carries a guide (dyn_batch_set_guide / dyn_batch_auto_guide), which does not combine with ") + x.setter + x.on;
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  if (!ticket) w.auto_guide_hw = 0;  // (a synchronous batch makes its guide through dyn_batch_auto_guide)
+  *out = w;
+  return DYN_OK;
+}
+}  // namespace dyneng
+
 namespace {
 
 // guided_train: the call is dyn_batch_train_guided (the one way a Train job reaches a guided batch)
@@ -1194,67 +1254,18 @@ int run_job_sync(dyn_batch* b, DynJob job, bool guided_train = false) {
                     "), which needs the called path of dyn_batch_align(b, 1); set max_rounds to 1 first";
     return DYN_ERR_INVALID_ARGUMENT;
   }
-  if (b->guided && job != DynJob::Train && (a->rescale_iters > 0 || a->border_confidence > 0)) {
+  if (b->guided && job != DynJob::Train && (a->opt.rescale_iters > 0 || a->opt.border_confidence > 0)) {
     a->last_error = std::string("dyn_batch_align: the batch carries a guide (dyn_batch_set_guide), which does not combine with ") +
-                    (a->rescale_iters > 0 ? "dyn_aligner_set_rescale(a, iters > 0)" : "dyn_aligner_set_border_confidence(a, window > 0)");
+                    (a->opt.rescale_iters > 0 ? "dyn_aligner_set_rescale(a, iters > 0)" : "dyn_aligner_set_border_confidence(a, window > 0)");
     return DYN_ERR_INVALID_ARGUMENT;
   }
-  // posterior samples (dyn_aligner_set_posterior_samples) concern align jobs with probabilities: a walk through the lattice of
-  // the read's one plain alignment in the diagonal band
-  if (job == DynJob::AlignFull && a->posterior_samples > 0) {
-    if (b->guided) {
-      a->last_error = "dyn_batch_align: the batch carries a guide (dyn_batch_set_guide / dyn_batch_auto_guide), which does not combine with "
-                      "dyn_aligner_set_posterior_samples(a, count > 0)";
-      return DYN_ERR_INVALID_ARGUMENT;
-    }
-    if (const char* other = posterior_samples_conflict(a)) {
-      a->last_error = std::string("dyn_batch_align: dyn_aligner_set_posterior_samples is on, which does not combine with ") + other;
-      return DYN_ERR_INVALID_ARGUMENT;
-    }
-  }
-  // credible intervals (dyn_aligner_set_border_interval) concern align jobs with probabilities: a summary of every column of the
-  // read's lattice in the diagonal band, the one lattice phase of its launch
-  const double bi = (job == DynJob::AlignFull && !a->ntk) ? a->border_interval : 0.0;
-  if (bi > 0) {
-    if (b->guided) {
-      a->last_error = "dyn_batch_align: the batch carries a guide (dyn_batch_set_guide / dyn_batch_auto_guide), which does not combine with "
-                      "dyn_aligner_set_border_interval(a, mass > 0)";
-      return DYN_ERR_INVALID_ARGUMENT;
-    }
-    if (const char* other = border_interval_conflict(a)) {
-      a->last_error = std::string("dyn_batch_align: dyn_aligner_set_border_interval is on, which does not combine with ") + other;
-      return DYN_ERR_INVALID_ARGUMENT;
-    }
-  }
-  // the guide rescue (dyn_aligner_set_guide_rescue) concerns align jobs with probabilities; the Z-only and the train job ignore it
-  const uint32_t gr_hw = (job == DynJob::AlignFull && !a->ntk) ? a->rescue_hw : 0u;
-  if (gr_hw) {
-    if (const char* other = guide_rescue_conflict(a)) {
-      a->last_error = std::string("dyn_batch_align: dyn_aligner_set_guide_rescue is on, which does not combine with ") + other;
-      return DYN_ERR_INVALID_ARGUMENT;
-    }
-    if (b->guided) {
-      a->last_error = "dyn_batch_align: dyn_aligner_set_guide_rescue is on and the batch carries a guide (dyn_batch_set_guide / "
-                      "dyn_batch_auto_guide); a guided batch is not rescued";
-      return DYN_ERR_INVALID_ARGUMENT;
-    }
-  }
+  JobOptions want;
+  if (int rc = resolve_job_options(a, job, false, b->guided, "dyn_batch_align", &want)) return rc;
   {
     std::lock_guard<std::mutex> lk(a->mu);
     int rc = need_device(a);
     if (rc != DYN_OK) return rc;
-    b->gr_hw = gr_hw;
-    b->gr_margin = a->rescue_margin;
-    b->gr_rounds = gr_hw ? a->rescue_rounds : 1u;
-    b->ev_want = a->event_stats;
-    b->rs_want = a->rescale_iters;
-    b->ks_want = a->kmer_summary;
-    b->bm_want = a->band_margin;
-    b->sc_want = a->segment_scores;
-    b->bc_want = a->border_confidence;
-    b->bi_want = bi;
-    b->ps_want = a->posterior_samples;
-    b->ps_seed = a->sample_seed;
+    b->want = want;
     rc = enqueue_job(b, job);
     if (rc != DYN_OK) {
       (void)hipStreamSynchronize(a->stream);
@@ -1504,43 +1515,74 @@ int dyn_batch_fetch(dyn_batch* b, dyn_align_out* out) {
 }  // extern "C"
 
 namespace dyneng {
-int batch_check_events(dyn_batch* b) {
-  if (b->ev_want && b->job == DynJob::AlignFull) return DYN_OK;
-  std::lock_guard<std::mutex> lk(b->a->err_mu);
-  b->a->last_error = "dyn_csv_sink_submit: the sink writes the signal levels (DYN_CSV_EVENT_STATS) and this ticket was submitted "
-                     "without dyn_aligner_set_event_stats(a, 1) or with calc_probabilities = 0";
+const OutputDesc OUTPUTS[OUT_COUNT] = {
+    {24, "dyn_batch_fetch_events", "dyn_event_out", "dyn_aligner_set_event_stats(a, 1)", DYN_CSV_EVENT_STATS, "the signal levels (DYN_CSV_EVENT_STATS)"},
+    {32, "dyn_batch_fetch_scores", "dyn_score_out", "dyn_aligner_set_segment_scores(a, window > 0)", DYN_CSV_SEGMENT_SCORES,
+     "the segment scores (DYN_CSV_SEGMENT_SCORES)"},
+    {16, "dyn_batch_fetch_borders", "dyn_border_out", "dyn_aligner_set_border_confidence(a, window > 0)", DYN_CSV_BORDER_CONFIDENCE,
+     "the border confidence (DYN_CSV_BORDER_CONFIDENCE)"},
+    {24, "dyn_batch_fetch_intervals", "dyn_border_interval_out", "dyn_aligner_set_border_interval(a, mass > 0)", DYN_CSV_BORDER_INTERVAL,
+     "the border intervals (DYN_CSV_BORDER_INTERVAL)"},
+    {4, "dyn_batch_fetch_samples", "dyn_sample_out", "dyn_aligner_set_posterior_samples(a, count > 0)", DYN_CSV_POSTERIOR_SAMPLES,
+     "the posterior samples (DYN_CSV_POSTERIOR_SAMPLES)"},
+};
+
+int output_wanted(const JobOptions& w, Output k) {
+  switch (k) {
+    case OUT_LEVELS: return w.event_stats ? 1 : 0;
+    case OUT_SCORES: return w.segment_scores ? 1 : 0;
+    case OUT_BORDERS: return w.border_confidence ? 1 : 0;
+    case OUT_INTERVALS: return w.border_interval > 0 ? 1 : 0;
+    default: return w.posterior_samples;
+  }
+}
+
+// the CSV sink's check (csv_sink.cpp) that a ticket was submitted with the output of `csv_flag` on; else the handle's message
+int batch_check_output(dyn_batch* b, uint32_t csv_flag) {
+  for (int k = 0; k < OUT_COUNT; ++k) {
+    if (OUTPUTS[k].csv_flag != csv_flag) continue;
+    if (output_wanted(b->want, (Output)k) && b->job == DynJob::AlignFull) return DYN_OK;
+    std::lock_guard<std::mutex> lk(b->a->err_mu);
+    b->a->last_error = std::string("dyn_csv_sink_submit: the sink writes ") + OUTPUTS[k].csv_what + " and this ticket was submitted without " +
+                       OUTPUTS[k].setter_hint + " or with calc_probabilities = 0";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
   return DYN_ERR_INVALID_ARGUMENT;
 }
-int batch_check_scores(dyn_batch* b) {
-  if (b->sc_want && b->job == DynJob::AlignFull) return DYN_OK;
-  std::lock_guard<std::mutex> lk(b->a->err_mu);
-  b->a->last_error = "dyn_csv_sink_submit: the sink writes the segment scores (DYN_CSV_SEGMENT_SCORES) and this ticket was "
-                     "submitted without dyn_aligner_set_segment_scores(a, window > 0) or with calc_probabilities = 0";
-  return DYN_ERR_INVALID_ARGUMENT;
-}
-int batch_check_borders(dyn_batch* b) {
-  if (b->bc_want && b->job == DynJob::AlignFull) return DYN_OK;
-  std::lock_guard<std::mutex> lk(b->a->err_mu);
-  b->a->last_error = "dyn_csv_sink_submit: the sink writes the border confidence (DYN_CSV_BORDER_CONFIDENCE) and this ticket was "
-                     "submitted without dyn_aligner_set_border_confidence(a, window > 0) or with calc_probabilities = 0";
-  return DYN_ERR_INVALID_ARGUMENT;
-}
-int batch_check_intervals(dyn_batch* b) {
-  if (b->bi_want > 0 && b->job == DynJob::AlignFull) return DYN_OK;
-  std::lock_guard<std::mutex> lk(b->a->err_mu);
-  b->a->last_error = "dyn_csv_sink_submit: the sink writes the border intervals (DYN_CSV_BORDER_INTERVAL) and this ticket was "
-                     "submitted without dyn_aligner_set_border_interval(a, mass > 0) or with calc_probabilities = 0";
-  return DYN_ERR_INVALID_ARGUMENT;
-}
-uint32_t batch_sample_count(const dyn_batch* b) { return (uint32_t)b->ps_want; }
-int batch_check_samples(dyn_batch* b) {
-  if (b->ps_want && b->job == DynJob::AlignFull) return DYN_OK;
-  std::lock_guard<std::mutex> lk(b->a->err_mu);
-  b->a->last_error = "dyn_csv_sink_submit: the sink writes the posterior samples (DYN_CSV_POSTERIOR_SAMPLES) and this ticket was "
-                     "submitted without dyn_aligner_set_posterior_samples(a, count > 0) or with calc_probabilities = 0";
-  return DYN_ERR_INVALID_ARGUMENT;
-}
+uint32_t batch_sample_count(const dyn_batch* b) { return (uint32_t)b->want.posterior_samples; }
 }  // namespace dyneng
+
+namespace {
+// A ticket that shared its launch with others owns no device buffers: its results are reads [g_read0, g_read0 + n) and rows
+// [g_seg0, g_seg0 + capacity) of the group's batch (dyn_batch_fetch)
+struct FetchSrc {
+  const dyn_batch* src;
+  uint64_t read0, seg0;
+};
+FetchSrc fetch_src(const dyn_batch* b) {
+  const dyn_batch* src = (b->group && b->group->g) ? b->group->g : b;
+  return FetchSrc{src, src == b ? 0 : b->g_read0, src == b ? 0 : b->g_seg0};
+}
+// what every fetcher of an opt-in result checks before it copies, in this order: the job ran with probabilities; it ran under the
+// switch (`ready`); the caller's arrays are large enough (`small`: the complaint, or nullptr); a device is bound
+int fetch_checks(dyn_batch* b, const char* fetch, const char* setter_hint, bool ready, const char* small) {
+  dyn_aligner* a = b->a;
+  const bool ran = b->aligned && b->last_calc;
+  if (!ran || !ready || small) {
+    a->last_error = !ran     ? std::string(fetch) + ": the batch was not aligned with calc_probabilities = 1"
+                    : !ready ? std::string(fetch) + ": the batch was submitted without " + setter_hint
+                             : std::string(small);
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  return need_device(a);
+}
+// ... for per-segment output k: where the member's rows are, and the checks (the fetcher returns at once when rc != DYN_OK)
+int fetch_prologue(dyn_batch* b, Output k, uint64_t out_capacity, FetchSrc* f) {
+  *f = fetch_src(b);
+  const std::string small = std::string(OUTPUTS[k].out_struct) + ".capacity is smaller than dyn_segment_capacity()";
+  return fetch_checks(b, OUTPUTS[k].fetch, OUTPUTS[k].setter_hint, f->src->out[k].ready != 0, out_capacity < b->capacity ? small.c_str() : nullptr);
+}
+}  // namespace
 
 extern "C" {
 
@@ -1548,160 +1590,90 @@ int dyn_batch_fetch_samples(dyn_batch* b, dyn_sample_out* out) {
   if (!b || !out || !out->sample_start || !out->sample_dead) return DYN_ERR_INVALID_ARGUMENT;
   dyn_aligner* a = b->a;
   // (a sampling ticket is never a member of a merged launch: the read's index in its own ticket keys the random stream)
-  if (!b->aligned || !b->last_calc || !b->ps_ready) {
-    a->last_error = !b->aligned || !b->last_calc
-                        ? "dyn_batch_fetch_samples: the batch was not aligned with calc_probabilities = 1"
-                        : "dyn_batch_fetch_samples: the batch was submitted without dyn_aligner_set_posterior_samples(a, count > 0)";
+  FetchSrc f;
+  if (int rc = fetch_prologue(b, OUT_SAMPLES, out->capacity, &f)) return rc;
+  const int K = b->out[OUT_SAMPLES].ready;
+  if (out->n < b->n || out->count < (uint32_t)K) {
+    a->last_error = out->n < b->n ? "dyn_sample_out.n is smaller than the batch's read count"
+                                  : "dyn_sample_out.count is smaller than the batch's sample count (" + std::to_string(K) + ")";
     return DYN_ERR_INVALID_ARGUMENT;
   }
-  if (out->capacity < b->capacity || out->count < (uint32_t)b->ps_ready || out->n < b->n) {
-    a->last_error = out->capacity < b->capacity ? "dyn_sample_out.capacity is smaller than dyn_segment_capacity()"
-                    : out->n < b->n            ? "dyn_sample_out.n is smaller than the batch's read count"
-                                               : "dyn_sample_out.count is smaller than the batch's sample count (" + std::to_string(b->ps_ready) + ")";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  int rc = need_device(a);
-  if (rc != DYN_OK) return rc;
-  const uint32_t* d = b->d_ps.as<uint32_t>();
+  const uint32_t* d = b->out[OUT_SAMPLES].d.as<uint32_t>();
   if (b->capacity) {
     if (out->capacity == b->capacity) {
-      HIP_TRY(a, copy_out(a, out->sample_start, d, (uint64_t)b->ps_ready * b->capacity * 4));
+      HIP_TRY(a, copy_out(a, out->sample_start, d, (uint64_t)K * b->capacity * 4));
     } else {
-      for (int k = 0; k < b->ps_ready; ++k)
+      for (int k = 0; k < K; ++k)
         HIP_TRY(a, copy_out(a, out->sample_start + (uint64_t)k * out->capacity, d + (uint64_t)k * b->capacity, b->capacity * 4));
     }
   }
-  if (b->n) HIP_TRY(a, copy_out(a, out->sample_dead, d + (uint64_t)b->ps_ready * b->capacity, b->n * 4));
-  out->count = (uint32_t)b->ps_ready;
+  if (b->n) HIP_TRY(a, copy_out(a, out->sample_dead, d + (uint64_t)K * b->capacity, b->n * 4));
+  out->count = (uint32_t)K;
   return DYN_OK;
 }
 
 int dyn_batch_fetch_intervals(dyn_batch* b, dyn_border_interval_out* out) {
   if (!b || !out || !out->border_lo || !out->border_hi || !out->border_mean || !out->border_sd) return DYN_ERR_INVALID_ARGUMENT;
   dyn_aligner* a = b->a;
-  // a member of a merged launch: rows [g_seg0, g_seg0 + capacity) of the group's columns (dyn_batch_fetch)
-  const dyn_batch* src = (b->group && b->group->g) ? b->group->g : b;
-  const uint64_t seg0 = src == b ? 0 : b->g_seg0;
-  if (!b->aligned || !b->last_calc || !src->bi_ready) {
-    a->last_error = !b->aligned || !b->last_calc
-                        ? "dyn_batch_fetch_intervals: the batch was not aligned with calc_probabilities = 1"
-                        : "dyn_batch_fetch_intervals: the batch was submitted without dyn_aligner_set_border_interval(a, mass > 0)";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  if (out->capacity < b->capacity) {
-    a->last_error = "dyn_border_interval_out.capacity is smaller than dyn_segment_capacity()";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  int rc = need_device(a);
-  if (rc != DYN_OK) return rc;
-  if (!b->capacity) return DYN_OK;
-  const double* e = src->d_bi.as<double>();
-  const uint32_t* q = reinterpret_cast<const uint32_t*>(e + 2 * src->capacity);
-  HIP_TRY(a, copy_out(a, out->border_mean, e + seg0, b->capacity * 8));
-  HIP_TRY(a, copy_out(a, out->border_sd, e + src->capacity + seg0, b->capacity * 8));
-  HIP_TRY(a, copy_out(a, out->border_lo, q + seg0, b->capacity * 4));
-  HIP_TRY(a, copy_out(a, out->border_hi, q + src->capacity + seg0, b->capacity * 4));
+  FetchSrc f;
+  const int rc = fetch_prologue(b, OUT_INTERVALS, out->capacity, &f);
+  if (rc != DYN_OK || !b->capacity) return rc;
+  const double* e = f.src->out[OUT_INTERVALS].d.as<double>();
+  const uint32_t* q = reinterpret_cast<const uint32_t*>(e + 2 * f.src->capacity);
+  HIP_TRY(a, copy_out(a, out->border_mean, e + f.seg0, b->capacity * 8));
+  HIP_TRY(a, copy_out(a, out->border_sd, e + f.src->capacity + f.seg0, b->capacity * 8));
+  HIP_TRY(a, copy_out(a, out->border_lo, q + f.seg0, b->capacity * 4));
+  HIP_TRY(a, copy_out(a, out->border_hi, q + f.src->capacity + f.seg0, b->capacity * 4));
   return DYN_OK;
 }
 
 int dyn_batch_fetch_borders(dyn_batch* b, dyn_border_out* out) {
   if (!b || !out || !out->border_probability || !out->border_window_probability) return DYN_ERR_INVALID_ARGUMENT;
   dyn_aligner* a = b->a;
-  // a member of a merged launch: rows [g_seg0, g_seg0 + capacity) of the group's columns (dyn_batch_fetch)
-  const dyn_batch* src = (b->group && b->group->g) ? b->group->g : b;
-  const uint64_t seg0 = src == b ? 0 : b->g_seg0;
-  if (!b->aligned || !b->last_calc || !src->bc_ready) {
-    a->last_error = !b->aligned || !b->last_calc
-                        ? "dyn_batch_fetch_borders: the batch was not aligned with calc_probabilities = 1"
-                        : "dyn_batch_fetch_borders: the batch was submitted without dyn_aligner_set_border_confidence(a, window > 0)";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  if (out->capacity < b->capacity) {
-    a->last_error = "dyn_border_out.capacity is smaller than dyn_segment_capacity()";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  int rc = need_device(a);
-  if (rc != DYN_OK) return rc;
-  if (!b->capacity) return DYN_OK;
-  const double* e = src->d_bc.as<double>() + seg0;
+  FetchSrc f;
+  const int rc = fetch_prologue(b, OUT_BORDERS, out->capacity, &f);
+  if (rc != DYN_OK || !b->capacity) return rc;
+  const double* e = f.src->out[OUT_BORDERS].d.as<double>() + f.seg0;
   HIP_TRY(a, copy_out(a, out->border_probability, e, b->capacity * 8));
-  HIP_TRY(a, copy_out(a, out->border_window_probability, e + src->capacity, b->capacity * 8));
+  HIP_TRY(a, copy_out(a, out->border_window_probability, e + f.src->capacity, b->capacity * 8));
   return DYN_OK;
 }
 
 int dyn_batch_fetch_scores(dyn_batch* b, dyn_score_out* out) {
   if (!b || !out || !out->median_delta || !out->mad_delta || !out->homogeneity) return DYN_ERR_INVALID_ARGUMENT;
   dyn_aligner* a = b->a;
-  // a member of a merged launch: rows [g_seg0, g_seg0 + capacity) of the group's columns (dyn_batch_fetch)
-  const dyn_batch* src = (b->group && b->group->g) ? b->group->g : b;
-  const uint64_t seg0 = src == b ? 0 : b->g_seg0;
-  if (!b->aligned || !b->last_calc || !src->sc_ready) {
-    a->last_error = !b->aligned || !b->last_calc
-                        ? "dyn_batch_fetch_scores: the batch was not aligned with calc_probabilities = 1"
-                        : "dyn_batch_fetch_scores: the batch was submitted without dyn_aligner_set_segment_scores(a, window > 0)";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  if (out->capacity < b->capacity) {
-    a->last_error = "dyn_score_out.capacity is smaller than dyn_segment_capacity()";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  int rc = need_device(a);
-  if (rc != DYN_OK) return rc;
-  if (!b->capacity) return DYN_OK;
-  const double* e = src->d_sc.as<double>() + seg0;
+  FetchSrc f;
+  const int rc = fetch_prologue(b, OUT_SCORES, out->capacity, &f);
+  if (rc != DYN_OK || !b->capacity) return rc;
+  const double* e = f.src->out[OUT_SCORES].d.as<double>() + f.seg0;
   HIP_TRY(a, copy_out(a, out->median_delta, e, b->capacity * 8));
-  HIP_TRY(a, copy_out(a, out->mad_delta, e + src->capacity, b->capacity * 8));
-  HIP_TRY(a, copy_out(a, out->homogeneity, e + 2 * src->capacity, b->capacity * 8));
+  HIP_TRY(a, copy_out(a, out->mad_delta, e + f.src->capacity, b->capacity * 8));
+  HIP_TRY(a, copy_out(a, out->homogeneity, e + 2 * f.src->capacity, b->capacity * 8));
   return DYN_OK;
 }
 
 int dyn_batch_fetch_events(dyn_batch* b, dyn_event_out* out) {
   if (!b || !out || !out->mean || !out->stdev || !out->median) return DYN_ERR_INVALID_ARGUMENT;
   dyn_aligner* a = b->a;
-  // a member of a merged launch: rows [g_seg0, g_seg0 + capacity) of the group's columns (dyn_batch_fetch)
-  const dyn_batch* src = (b->group && b->group->g) ? b->group->g : b;
-  const uint64_t seg0 = src == b ? 0 : b->g_seg0;
-  if (!b->aligned || !b->last_calc || !src->ev_ready) {
-    a->last_error = !b->aligned || !b->last_calc
-                        ? "dyn_batch_fetch_events: the batch was not aligned with calc_probabilities = 1"
-                        : "dyn_batch_fetch_events: the batch was submitted without dyn_aligner_set_event_stats(a, 1)";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  if (out->capacity < b->capacity) {
-    a->last_error = "dyn_event_out.capacity is smaller than dyn_segment_capacity()";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  int rc = need_device(a);
-  if (rc != DYN_OK) return rc;
-  if (!b->capacity) return DYN_OK;
-  const double* e = src->d_ev.as<double>() + seg0;
+  FetchSrc f;
+  const int rc = fetch_prologue(b, OUT_LEVELS, out->capacity, &f);
+  if (rc != DYN_OK || !b->capacity) return rc;
+  const double* e = f.src->out[OUT_LEVELS].d.as<double>() + f.seg0;
   HIP_TRY(a, copy_out(a, out->mean, e, b->capacity * 8));
-  HIP_TRY(a, copy_out(a, out->stdev, e + src->capacity, b->capacity * 8));
-  HIP_TRY(a, copy_out(a, out->median, e + 2 * src->capacity, b->capacity * 8));
+  HIP_TRY(a, copy_out(a, out->stdev, e + f.src->capacity, b->capacity * 8));
+  HIP_TRY(a, copy_out(a, out->median, e + 2 * f.src->capacity, b->capacity * 8));
   return DYN_OK;
 }
 
 int dyn_batch_fetch_rescale(dyn_batch* b, dyn_rescale_out* out) {
   if (!b || !out || !out->shift || !out->scale || !out->iters_applied) return DYN_ERR_INVALID_ARGUMENT;
   dyn_aligner* a = b->a;
-  // a member of a merged launch: reads [g_read0, g_read0 + n) of the group's transforms
-  const dyn_batch* src = (b->group && b->group->g) ? b->group->g : b;
-  const uint64_t read0 = src == b ? 0 : b->g_read0;
-  if (!b->aligned || !b->last_calc || !src->rs_ready) {
-    a->last_error = !b->aligned || !b->last_calc
-                        ? "dyn_batch_fetch_rescale: the batch was not aligned with calc_probabilities = 1"
-                        : "dyn_batch_fetch_rescale: the batch was submitted without dyn_aligner_set_rescale(a, iters > 0)";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  if (out->n < b->n) {
-    a->last_error = "dyn_rescale_out.n is smaller than the batch's read count";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  int rc = need_device(a);
-  if (rc != DYN_OK) return rc;
-  if (!b->n) return DYN_OK;
+  const FetchSrc f = fetch_src(b);
+  const int rc = fetch_checks(b, "dyn_batch_fetch_rescale", "dyn_aligner_set_rescale(a, iters > 0)", f.src->rs_ready,
+                              out->n < b->n ? "dyn_rescale_out.n is smaller than the batch's read count" : nullptr);
+  if (rc != DYN_OK || !b->n) return rc;
   std::vector<dynk::RescaleState> h(b->n);
-  HIP_TRY(a, copy_out(a, h.data(), src->d_rs.as<dynk::RescaleState>() + read0, b->n * sizeof(dynk::RescaleState)));
+  HIP_TRY(a, copy_out(a, h.data(), f.src->d_rs.as<dynk::RescaleState>() + f.read0, b->n * sizeof(dynk::RescaleState)));
   for (uint64_t i = 0; i < b->n; ++i) {
     out->shift[i] = h[i].A;
     out->scale[i] = h[i].B;
@@ -1713,26 +1685,14 @@ int dyn_batch_fetch_rescale(dyn_batch* b, dyn_rescale_out* out) {
 int dyn_batch_fetch_band_margin(dyn_batch* b, dyn_band_margin_out* out) {
   if (!b || !out || !out->low || !out->high || !out->edge_rows) return DYN_ERR_INVALID_ARGUMENT;
   dyn_aligner* a = b->a;
-  // a member of a merged launch: reads [g_read0, g_read0 + n) of the group's margins, if THIS member asked
-  const dyn_batch* src = (b->group && b->group->g) ? b->group->g : b;
-  const uint64_t read0 = src == b ? 0 : b->g_read0;
-  if (!b->aligned || !b->last_calc || !b->bm_want || !src->bm_ready) {
-    a->last_error = !b->aligned || !b->last_calc
-                        ? "dyn_batch_fetch_band_margin: the batch was not aligned with calc_probabilities = 1"
-                        : "dyn_batch_fetch_band_margin: the batch was submitted without dyn_aligner_set_band_margin(a, 1)";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  if (out->n < b->n) {
-    a->last_error = "dyn_band_margin_out.n is smaller than the batch's read count";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  int rc = need_device(a);
-  if (rc != DYN_OK) return rc;
-  if (!b->n) return DYN_OK;
-  const uint32_t* m = src->d_bm.as<uint32_t>() + read0;
+  const FetchSrc f = fetch_src(b);  // (the group's margins, if THIS member asked)
+  const int rc = fetch_checks(b, "dyn_batch_fetch_band_margin", "dyn_aligner_set_band_margin(a, 1)", b->want.band_margin && f.src->bm_ready,
+                              out->n < b->n ? "dyn_band_margin_out.n is smaller than the batch's read count" : nullptr);
+  if (rc != DYN_OK || !b->n) return rc;
+  const uint32_t* m = f.src->d_bm.as<uint32_t>() + f.read0;
   HIP_TRY(a, copy_out(a, out->low, m, b->n * 4));
-  HIP_TRY(a, copy_out(a, out->high, m + src->n, b->n * 4));
-  HIP_TRY(a, copy_out(a, out->edge_rows, m + 2 * src->n, b->n * 4));
+  HIP_TRY(a, copy_out(a, out->high, m + f.src->n, b->n * 4));
+  HIP_TRY(a, copy_out(a, out->edge_rows, m + 2 * f.src->n, b->n * 4));
   return DYN_OK;
 }
 

@@ -129,6 +129,63 @@ struct Session {
   uint64_t gen = 0;
 };
 
+// ---- the opt-in switches of a handle, as a job reads them ------------------------------------------------------------------
+// dyn_aligner::opt is what the dyn_aligner_set_<switch> calls last said; dyn_batch::want is what ONE job took of it at its
+// submission (resolve_job_options: masked by the job's kind and the handle's mode, refused where two switches do not combine).
+struct JobOptions {
+  bool event_stats = false;     // dyn_aligner_set_event_stats
+  int rescale_iters = 0;        // dyn_aligner_set_rescale (0 .. 8)
+  bool kmer_summary = false;    // dyn_aligner_set_kmer_summary
+  bool band_margin = false;     // dyn_aligner_set_band_margin
+  int segment_scores = 0;       // dyn_aligner_set_segment_scores (window, 0 = off)
+  int border_confidence = 0;    // dyn_aligner_set_border_confidence (window, 0 = off)
+  double border_interval = 0;   // dyn_aligner_set_border_interval (mass, 0 = off)
+  int posterior_samples = 0;    // dyn_aligner_set_posterior_samples (count, 0 = off)
+  uint64_t sample_seed = 0;     // ... and its seed
+  uint32_t auto_guide_hw = 0, auto_guide_rounds = 8;               // dyn_aligner_set_auto_guide (half width, 0 = off; alignments per read)
+  uint32_t rescue_margin = 0, rescue_hw = 0, rescue_rounds = 8;    // dyn_aligner_set_guide_rescue (minimum margin; half width, 0 = off; alignments)
+  // May tickets x and y share ONE launch (Pipeline::merge)? Three kinds of fields:
+  //   launch-wide: event_stats, rescale_iters, segment_scores, border_confidence, border_interval -- one value per launch, so the
+  //                members must agree; the launch's batch takes them from its first member
+  //   per-ticket:  kmer_summary, band_margin -- not compared: the launch's batch lists the read ranges of the members that asked
+  //   alone:       posterior_samples (the read's index in its OWN ticket keys the random stream), auto_guide_hw (a guide of its own
+  //                and the banded-lattice kernel), rescue_hw (its list of reads to re-align is its own) -- such a ticket never merges
+  bool merges() const { return posterior_samples == 0 && auto_guide_hw == 0 && rescue_hw == 0; }
+  bool same_launch(const JobOptions& y) const {
+    return event_stats == y.event_stats && rescale_iters == y.rescale_iters && segment_scores == y.segment_scores &&
+           border_confidence == y.border_confidence && border_interval == y.border_interval;
+  }
+  // the launch-wide part alone: what the batch of a merged launch runs under
+  JobOptions launch_wide() const {
+    JobOptions g;
+    g.event_stats = event_stats;
+    g.rescale_iters = rescale_iters;
+    g.segment_scores = segment_scores;
+    g.border_confidence = border_confidence;
+    g.border_interval = border_interval;
+    return g;
+  }
+};
+
+// ---- the per-segment outputs a job may add to its rows (one fetcher, one out-struct and one CSV flag each) ---------------------
+enum Output { OUT_LEVELS, OUT_SCORES, OUT_BORDERS, OUT_INTERVALS, OUT_SAMPLES, OUT_COUNT };
+struct OutputBuf {
+  DevBuf d;       // OUT_LEVELS [3][capacity] f64 mean / stdev / median (event_stats.hip); OUT_SCORES [4][capacity] f64 median_delta /
+                  // mad_delta / homogeneity / scratch (segment_scores.hip); OUT_BORDERS [2][capacity] f64 (border_kernels.hpp);
+                  // OUT_INTERVALS [2][capacity] f64 mean / sd, then [2][capacity] u32 lo / hi (interval_kernels.hpp); OUT_SAMPLES
+                  // [count][capacity] u32 sample starts, then [n] u32 dead samples (sample_kernels.hpp)
+  int ready = 0;  // the last job computed the columns into d (OUT_SAMPLES: the count it sampled)
+};
+struct OutputDesc {
+  uint32_t row_bytes;       // of d per segment row (OUT_SAMPLES: per sample; its [n] dead counts come on top)
+  const char* fetch;        // the C-ABI fetcher, as its messages name it
+  const char* out_struct;   // ... and its out-struct
+  const char* setter_hint;  // the call that would have switched the output on
+  uint32_t csv_flag;        // the dyn_csv_sink_open_ex flag that writes it
+  const char* csv_what;     // ... as the sink's refusal names it
+};
+extern const OutputDesc OUTPUTS[OUT_COUNT];  // dynamont_mi.cpp
+
 }  // namespace dyneng
 
 struct dyn_aligner {
@@ -150,20 +207,7 @@ struct dyn_aligner {
   // sweep does not store a lane group's float LPE (lpe_liveness.hpp)
   float lpe_floor = -750.0f;
   bool lpe_dense = false;
-  bool event_stats = false;   // dyn_aligner_set_event_stats: read by every batch / ticket at its submission
-  int rescale_iters = 0;      // dyn_aligner_set_rescale (0 .. 8): read by every batch / ticket at its submission
-  bool kmer_summary = false;  // dyn_aligner_set_kmer_summary: read by every batch / ticket at its submission
-  int segment_scores = 0;     // dyn_aligner_set_segment_scores (window, 0 = off): read by every batch / ticket at its submission
-  int border_confidence = 0;  // dyn_aligner_set_border_confidence (window, 0 = off): read by every batch / ticket at its submission
-  double border_interval = 0; // dyn_aligner_set_border_interval (mass, 0 = off): read by every batch / ticket at its submission
-  int posterior_samples = 0;  // dyn_aligner_set_posterior_samples (count, 0 = off): read by every batch / ticket at its submission
-  uint64_t sample_seed = 0;   // ... and its seed
-  bool band_margin = false;   // dyn_aligner_set_band_margin: read by every batch / ticket at its submission
-  // dyn_aligner_set_auto_guide (half width, 0 = off; alignments per read): read by every align(calc = 1) TICKET at its submission
-  uint32_t auto_guide_hw = 0, auto_guide_rounds = 8;
-  // dyn_aligner_set_guide_rescue (minimum margin; half width, 0 = off; alignments per rescued read): read by every
-  // align(calc = 1) batch / ticket at its submission
-  uint32_t rescue_margin = 0, rescue_hw = 0, rescue_rounds = 8;
+  dyneng::JobOptions opt;  // the dyn_aligner_set_<switch> calls write here; every batch / ticket takes its own copy at its submission
   // queue head + lattice arenas of the self-guided tickets (band_reads.hip): grow-only, the handle's, shared by every such ticket
   // in stream order (launch.cpp, enqueue_job) and released with the handle
   dyneng::DevBuf band_arena;
@@ -257,37 +301,20 @@ struct dyn_batch {
   dyneng::DevBuf d_sig, d_kmers, d_par, d_state, d_rows, d_segrow, d_medhi, d_medlo, d_descs;
   dyneng::DevBuf d_colw, d_cols1, d_cols2, d_trans, d_pooled, d_poolwork, d_pooltemp;
   dyneng::DevBuf d_pp, d_pathn;                // per-row path arrays (traceback -> k_median / k_final)
-  dyneng::DevBuf d_ev;                         // [3][capacity] level mean / stdev / median (event_stats.hip), when asked for
-  bool ev_want = false;                        // the handle's event-stats switch when this batch / ticket was submitted
-  bool ev_ready = false;                       // the last job computed the event columns into d_ev
-  dyneng::DevBuf d_sc;                         // [4][capacity] median_delta / mad_delta / homogeneity / scratch (segment_scores.hip)
-  int sc_want = 0;                             // the handle's segment-score window when this batch / ticket was submitted
-  bool sc_ready = false;                       // the last job computed the score columns into d_sc
-  dyneng::DevBuf d_bc;                         // [2][capacity] border_probability / border_window_probability (border_kernels.hpp)
-  int bc_want = 0;                             // the handle's border-confidence window when this batch / ticket was submitted
-  bool bc_ready = false;                       // the last job computed the border columns into d_bc
-  dyneng::DevBuf d_bi;                         // [capacity] f64 mean | [capacity] f64 sd | [capacity] u32 lo | [capacity] u32 hi (interval_kernels.hpp)
-  double bi_want = 0;                          // the handle's border-interval mass when this batch / ticket was submitted (0: off)
-  bool bi_ready = false;                       // the last job computed the interval columns into d_bi
-  dyneng::DevBuf d_ps;                         // [ps_want][capacity] u32 sample starts | [n] u32 dead samples (sample_kernels.hpp)
-  int ps_want = 0;                             // the handle's posterior-sample count when this batch / ticket was submitted
-  uint64_t ps_seed = 0;                        // ... and its seed
-  int ps_ready = 0;                            // the count the last job sampled into d_ps (0: it did not)
+  // what the handle's switches said when this batch / ticket was submitted (resolve_job_options)
+  dyneng::JobOptions want;
+  // the per-segment outputs (dyneng::Output), when asked for: the columns and whether the last job computed them
+  dyneng::OutputBuf out[dyneng::OUT_COUNT];
   // per-read rescaling (rescale.hip, dyn_aligner_set_rescale)
   dyneng::DevBuf d_sig0;                       // the preprocessed signal x0, kept while d_sig holds a rescaled one
   dyneng::DevBuf d_rs;                         // [n] dynk::RescaleState | [capacity] row means of the fit (scratch)
-  int rs_want = 0;                             // the handle's rescale iterations when this batch / ticket was submitted
   bool rs_ready = false;                       // the last job ran its passes: d_rs holds the per-read transforms
   bool sig0_kept = false;                      // d_sig0 holds x0 (a synchronous batch aligned again starts from it)
   uint64_t sig0_len = 0;                       // samples kept in d_sig0
   int n_passes = 1;                            // alignment passes of the last job (h_stats holds one record each)
-  // per-k-mer summary (dyn_aligner_set_kmer_summary): the handle's switch when this batch / ticket was submitted. A merged
-  // launch's batch lists the read ranges of the members that asked (same_kind does not look at the switch)
-  bool ks_want = false;
-  std::vector<std::pair<uint32_t, uint32_t>> ks_ranges;
-  // band-margin diagnostics (dyn_aligner_set_band_margin): the switch likewise, and likewise a merged launch's read ranges
-  bool bm_want = false;
-  std::vector<std::pair<uint32_t, uint32_t>> bm_ranges;
+  // per-k-mer summary and band-margin diagnostics (want.kmer_summary, want.band_margin): a merged launch's batch lists the read
+  // ranges of the members that asked (JobOptions::same_launch does not look at the two switches)
+  std::vector<std::pair<uint32_t, uint32_t>> ks_ranges, bm_ranges;
   dyneng::DevBuf d_bm;                         // [3][n] uint32 low / high / edge_rows (band_margin_kernels.hpp), when asked for
   bool bm_ready = false;                       // the last job computed the margins into d_bm
   dyneng::PinnedBuf h_descs, h_state, h_rows;  // h_state/h_rows: D2H targets of the asynchronous path
@@ -308,17 +335,14 @@ struct dyn_batch {
   uint32_t guide_refine = 1;
   dyneng::DevBuf d_gref;        // uint32 [n] rounds | [n] converged | [64] the two list lengths | [n] | [n] the two lists of reads
   bool gref_ready = false;      // the last job refined: d_gref holds rounds / converged
-  // the self-guided band of a TICKET (dyn_aligner_set_auto_guide): the handle's half width (0: a plain ticket) and alignments per
-  // read when the ticket was submitted. Such a ticket runs alone -- never merged, never published into a resident session: the
-  // front thread makes its guide on the compute stream (enqueue_auto_guide) and enqueue_job aligns it as a guided batch, every
-  // read refined inside ONE launch (band_reads.hpp, BandArgs::refine_rounds)
-  uint32_t ag_want = 0, ag_rounds = 1;
+  // the self-guided band of a TICKET (want.auto_guide_hw, 0: a plain ticket). Such a ticket runs alone -- never merged, never
+  // published into a resident session: the front thread makes its guide on the compute stream (enqueue_auto_guide) and enqueue_job
+  // aligns it as a guided batch, every read refined inside ONE launch (band_reads.hpp, BandArgs::refine_rounds)
   dyneng::PinnedBuf h_gdescs;   // the guide pre-pass's descriptor table (enqueue_job fills h_descs while that copy may be pending)
   dyneng::PinnedBuf h_gref;     // a ticket's rounds | converged, copied out with its state
   uint64_t arena_bytes = 0;     // what the last job asked of d_arena beyond the queue head: every workgroup's lattice arena
-  // the guide rescue (dyn_aligner_set_guide_rescue, guide_rescue_kernels.hpp): the handle's switch when this batch / ticket was
-  // submitted (gr_hw 0: off). Such a job is a classic launch -- a ticket is never merged, never published into a resident session
-  uint32_t gr_margin = 0, gr_hw = 0, gr_rounds = 1;
+  // the guide rescue (want.rescue_hw, 0: off; guide_rescue_kernels.hpp). Such a job is a classic launch -- a ticket is never merged,
+  // never published into a resident session
   // uint32 [n] rounds | [n] converged | uint8 [n] code (padded to 256 B) | uint32 [64] list length | [n] list | [3 n] margins
   // (when the batch did not ask for them itself)
   dyneng::DevBuf d_resc;
@@ -434,6 +458,18 @@ std::vector<dynk::KmerSummary> kmer_summary_args(const dyn_batch* b);
 std::vector<dynk::BandMargin> band_margin_args(const dyn_batch* b);
 // bm_ready and the room for the margins of an align(calc = 1) job of this batch / ticket
 int band_margin_prepare(dyn_batch* b, bool calc);
+// What a job of kind `job` submitted NOW through `api` ("dyn_batch_align", "dyn_batch_align_async": `ticket`) takes of the handle's
+// switches: the four that concern align(calc = 1) jobs outside modes ntk / resquiggle alone are masked (guide rescue, auto-guide
+// -- tickets only --, posterior samples, border interval), and a combination the rule table (dynamont_mi.cpp) or a guided batch
+// forbids is refused with its text in last_error. No HIP call, no lock but err_mu: the same answer with and without a device.
+int resolve_job_options(dyn_aligner* a, DynJob job, bool ticket, bool guided, const char* api, JobOptions* out);
+// what the job's switches ask of output k: 0 = nothing, else what OutputBuf::ready becomes (1; OUT_SAMPLES: the count)
+int output_wanted(const JobOptions& w, Output k);
+// room for output k of this job and ready = `ready` (0: the output is off); then its zeroing on `s` -- the rows of reads that fail
+// keep the zeros. output_prepare does both (classic launches); a session ticket ensures at publish and zeroes at finish.
+int output_ensure(dyn_batch* b, Output k, int ready);
+int output_zero(dyn_batch* b, Output k, hipStream_t s);
+int output_prepare(dyn_batch* b, Output k, int ready, hipStream_t s);
 // the per-segment kernels and the statistics copy of a COMPLETED session ticket, on `s`
 int session_finish_enqueue(dyn_batch* b, hipStream_t s);
 int session_collect_timing(dyn_batch* b);

@@ -40,30 +40,5 @@ void plan_queue(std::vector<uint32_t>& order, const std::vector<uint32_t>& need,
 // low-discrepancy order of a paged session's ticket (`order` comes in longest first)
 void spread_order(std::vector<uint32_t>& order, int tail_div);
 constexpr int SESSION_TAIL_DIV = 8;
-// the handle switch that dyn_aligner_set_guide_rescue does not combine with, as a job's / a ticket's refusal names it (nullptr:
-// none is on). All three re-align or read the lattice of every read: the rescue's second alignment has no place in their order
-inline const char* guide_rescue_conflict(const dyn_aligner* a) {
-  if (a->rescale_iters > 0) return "dyn_aligner_set_rescale(a, iters > 0)";
-  if (a->border_confidence > 0) return "dyn_aligner_set_border_confidence(a, window > 0)";
-  if (a->auto_guide_hw > 0) return "dyn_aligner_set_auto_guide(a, half_width > 0)";
-  return nullptr;
-}
-// likewise for dyn_aligner_set_posterior_samples: a sampled path is a walk through the lattice of the one plain alignment of a
-// read in the diagonal band; the switches that re-align a read or align it inside a guide window have no such lattice to offer
-inline const char* posterior_samples_conflict(const dyn_aligner* a) {
-  if (a->rescale_iters > 0) return "dyn_aligner_set_rescale(a, iters > 0)";
-  if (a->auto_guide_hw > 0) return "dyn_aligner_set_auto_guide(a, half_width > 0)";
-  if (a->rescue_hw > 0) return "dyn_aligner_set_guide_rescue(a, half_width > 0)";
-  return nullptr;
-}
-// likewise for dyn_aligner_set_border_interval: one lattice phase runs per launch for now (an INTERIM), and the
-// switches that align a read inside a guide window have no diagonal lattice to offer
-inline const char* border_interval_conflict(const dyn_aligner* a) {
-  if (a->border_confidence > 0) return "dyn_aligner_set_border_confidence(a, window > 0)";
-  if (a->posterior_samples > 0) return "dyn_aligner_set_posterior_samples(a, count > 0)";
-  if (a->auto_guide_hw > 0) return "dyn_aligner_set_auto_guide(a, half_width > 0)";
-  if (a->rescue_hw > 0) return "dyn_aligner_set_guide_rescue(a, half_width > 0)";
-  return nullptr;
-}
 
 }  // namespace dyneng

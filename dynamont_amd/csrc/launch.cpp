@@ -237,7 +237,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   b->gref_ready = false;
   // the guide rescue (dyn_aligner_set_guide_rescue): sampled per job by the caller; it concerns the unguided align job with
   // probabilities alone (the callers refuse the combinations with rescale / border confidence / a guide)
-  const bool rescue = calc && b->gr_hw > 0 && !b->guided && !a->ntk && b->rs_want == 0 && b->bc_want == 0;
+  const bool rescue = calc && b->want.rescue_hw > 0 && !b->guided && !a->ntk && b->want.rescale_iters == 0 && b->want.border_confidence == 0;
   b->gr_ready = false;
 
   // mode "resquiggle"/"ntk": what the reference's NTKAligner does in this snapshot, as observed with the compiled
@@ -547,16 +547,16 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     uint64_t room = (uint64_t)((double)(free_b + resc_arena_buf.bytes + parked_bytes(a->device)) * 0.8);
     if (a->mem_budget && room > a->mem_budget) room = a->mem_budget;
     for (size_t k = 0; k < n_all; ++k)
-      if (descs[k].T > resc_T_fit && dynk::band_arena_bytes(descs[k].T, b->gr_hw, 1) <= room) resc_T_fit = descs[k].T;
+      if (descs[k].T > resc_T_fit && dynk::band_arena_bytes(descs[k].T, b->want.rescue_hw, 1) <= room) resc_T_fit = descs[k].T;
     if (resc_T_fit) {
-      resc_arena = dynk::band_arena_bytes(resc_T_fit, b->gr_hw, 1);
-      resc_groups = (int)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)n_all, (uint64_t)a->n_cus * (uint64_t)dynk::band_groups_per_cu(true, (int)b->gr_hw, 1),
+      resc_arena = dynk::band_arena_bytes(resc_T_fit, b->want.rescue_hw, 1);
+      resc_groups = (int)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)n_all, (uint64_t)a->n_cus * (uint64_t)dynk::band_groups_per_cu(true, (int)b->want.rescue_hw, 1),
                                                                     room / resc_arena}));
       resc_want = 256 + (uint64_t)resc_groups * resc_arena;
     }
   }
   // per-read rescaling (dyn_aligner_set_rescale): align(calc = 1) runs 1 + iters passes of everything below, in stream order
-  const int iters = calc ? b->rs_want : 0;
+  const int iters = calc ? b->want.rescale_iters : 0;
   const int n_pass = 1 + iters;
   HIP_TRY(a, b->h_stats.ensure((size_t)n_pass * dynk::QUEUE_CTL_WORDS * 4));
   std::memset(b->h_stats.p, 0, (size_t)n_pass * dynk::QUEUE_CTL_WORDS * 4);
@@ -611,37 +611,22 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   q.lpe_dense = a->lpe_dense ? 1 : 0;
   // per-border posterior confidence: [border_probability | border_window_probability] x capacity, zeroed here (rows of reads
   // that fail keep the zeros), written by the read queue / the wide-band kernel of the LAST pass behind every read
-  double* bc_cols = nullptr;
-  b->bc_ready = false;
-  if (calc && b->bc_want) {
-    HIP_TRY(a, b->d_bc.ensure(std::max<uint64_t>(16, b->capacity * 16)));
-    if (b->capacity) HIP_TRY(a, hipMemsetAsync(b->d_bc.p, 0, b->capacity * 16, a->stream));
-    bc_cols = b->d_bc.as<double>();
-    b->bc_ready = true;
-  }
+  if (int rc = output_prepare(b, OUT_BORDERS, calc ? output_wanted(b->want, OUT_BORDERS) : 0, a->stream)) return rc;
+  double* bc_cols = b->out[OUT_BORDERS].ready ? b->out[OUT_BORDERS].d.as<double>() : nullptr;
   // credible intervals: [mean | sd] f64 and [lo | hi] u32 x capacity in one buffer, zeroed here (rows of reads that fail keep the
   // zeros), written by the read queue / the banded-lattice kernel of the LAST pass behind every read
-  b->bi_ready = false;
-  const bool bi_on = calc && b->bi_want > 0;
-  if (bi_on) {
-    HIP_TRY(a, b->d_bi.ensure(std::max<uint64_t>(24, b->capacity * 24)));
-    if (b->capacity) HIP_TRY(a, hipMemsetAsync(b->d_bi.p, 0, b->capacity * 24, a->stream));
-    b->bi_ready = true;
-  }
+  if (int rc = output_prepare(b, OUT_INTERVALS, calc ? output_wanted(b->want, OUT_INTERVALS) : 0, a->stream)) return rc;
+  const bool bi_on = b->out[OUT_INTERVALS].ready != 0;
   // posterior path samples: [count][capacity] segment starts, then the per-read count of dead samples, zeroed here (rows of reads
   // that fail keep the zeros), written by the read queue / the banded-lattice kernel behind every read. (The callers refuse the
   // switches that would make this more than one pass.)
-  b->ps_ready = 0;
-  if (calc && b->ps_want) {
-    const uint64_t words = (uint64_t)b->ps_want * b->capacity + b->n;
-    HIP_TRY(a, b->d_ps.ensure(std::max<uint64_t>(16, words * 4)));
-    if (words) HIP_TRY(a, hipMemsetAsync(b->d_ps.p, 0, words * 4, a->stream));
-    q.sample.start = b->d_ps.as<uint32_t>();  // (the dead counts follow the planes)
+  if (int rc = output_prepare(b, OUT_SAMPLES, calc ? output_wanted(b->want, OUT_SAMPLES) : 0, a->stream)) return rc;
+  if (b->out[OUT_SAMPLES].ready) {
+    q.sample.start = b->out[OUT_SAMPLES].d.as<uint32_t>();  // (the dead counts follow the planes)
     q.sample.capacity = b->capacity;
-    q.sample.seed = b->ps_seed;
-    q.sample.count = b->ps_want;
+    q.sample.seed = b->want.sample_seed;
+    q.sample.count = b->want.posterior_samples;
     q.lpe_dense = 1;  // a sampled path may visit any cell of the band (the kernel variant that carries the phase stores densely anyway)
-    b->ps_ready = b->ps_want;
   }
   const dynk::QueueJob qjob = job == DynJob::Train ? (a->train_zcheck ? dynk::JOB_TRAIN_ZCHECK : dynk::JOB_TRAIN)
                               : !calc              ? dynk::JOB_Z
@@ -654,13 +639,13 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     if (pass > 0 && b->n) HIP_TRY(a, hipMemcpyAsync(b->d_state.p, st, b->n * sizeof(ReadState), hipMemcpyHostToDevice, a->stream));
     dynk::launch_pool_init(pool, used_pages, (int)n_static, a->stream);
     if (bc_cols && pass + 1 == n_pass) {
-      q.border_window = b->bc_want;
+      q.border_window = b->want.border_confidence;
       q.lpe_dense = 1;  // the border phase reads whole windows of LPE (the kernel variant that carries it stores densely anyway)
       q.border_p = bc_cols;
       q.border_window_p = bc_cols + b->capacity;
     }
     if (bi_on && pass + 1 == n_pass) {  // (the callers refuse the border confidence and the samples beside it)
-      q.interval = dynk::IntervalOut{b->d_bi.as<double>(), b->capacity, (1.0 - b->bi_want) / 2, 0};
+      q.interval = dynk::IntervalOut{b->out[OUT_INTERVALS].d.as<double>(), b->capacity, (1.0 - b->want.border_interval) / 2, 0};
       q.lpe_dense = 1;  // the phase reads whole columns of LPE (the kernel variant that carries it stores densely anyway)
     }
     if (pass == 0) HIP_TRY(a, hipEventRecord(ev[0], a->stream));
@@ -786,7 +771,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     sel.st = q.st;
     sel.low = dm.low;
     sel.high = dm.high;
-    sel.min_margin = b->gr_margin;
+    sel.min_margin = b->want.rescue_margin;
     sel.max_T = resc_T_fit;
     sel.code = g_code;
     sel.list = g_list;
@@ -801,7 +786,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       dynk::AutoGuideArgs ag{};
       ag.descs = q.descs;
       ag.n_reads = nr_all;
-      ag.bw = (int)b->gr_hw;
+      ag.bw = (int)b->want.rescue_hw;
       ag.sig = q.sig;
       ag.par = q.par;
       ag.guide = b->d_guide.as<int32_t>();
@@ -810,7 +795,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       ag.e2 = m.log_e2;
       ag.active = g_list;
       ag.n_active = g_len;
-      const int ag_groups = (int)std::min<uint64_t>(n_all, (uint64_t)a->n_cus * (uint64_t)dynk::auto_guide_groups_per_cu((int)b->gr_hw));
+      const int ag_groups = (int)std::min<uint64_t>(n_all, (uint64_t)a->n_cus * (uint64_t)dynk::auto_guide_groups_per_cu((int)b->want.rescue_hw));
       HIP_TRY(a, dynk::launch_auto_guide(ag, ag_groups, a->stream));
       // the rescue alignment writes a state, path rows and segment rows of its OWN (the read's offsets, other buffers): the
       // plain answer stays whole until launch_rescue_merge has seen how the rescue ended
@@ -830,7 +815,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       dynk::BandArgs ra{};
       ra.descs = q.descs;
       ra.n_reads = nr_all;
-      ra.bw = (int)b->gr_hw;
+      ra.bw = (int)b->want.rescue_hw;
       ra.sig = q.sig;
       ra.par = q.par;
       ra.guide = b->d_guide.as<int32_t>();
@@ -845,7 +830,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       ra.z_fail_status = z_fail;
       ra.active = g_list;
       ra.n_active = g_len;
-      ra.refine_rounds = (int)b->gr_rounds;
+      ra.refine_rounds = (int)b->want.rescue_rounds;
       ra.rounds = g_rounds;
       ra.converged = g_conv;
       HIP_TRY(a, dynk::launch_band_reads(1, ra, resc_groups, a->stream));
@@ -865,33 +850,25 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       mg.code = g_code;
       mg.rounds = g_rounds;
       mg.converged = g_conv;
-      mg.single = b->gr_rounds <= 1 ? 1 : 0;
+      mg.single = b->want.rescue_rounds <= 1 ? 1 : 0;
       HIP_TRY(a, dynk::launch_rescue_merge(mg, a->stream));
       // a rescued read reports its margins against the window it was aligned in, every other read against the diagonal (above)
       if (b->bm_ready)
-        dynk::launch_guided_band_margin(q.descs, nr_all, b->max_T, q.st, q.tb, b->d_guide.as<int32_t>(), (int)b->gr_hw, dm, a->stream, g_code);
+        dynk::launch_guided_band_margin(q.descs, nr_all, b->max_T, q.st, q.tb, b->d_guide.as<int32_t>(), (int)b->want.rescue_hw, dm, a->stream, g_code);
     }
     b->gr_ready = true;
   }
   dynk::EventCols evc{};
-  b->ev_ready = false;
-  if (calc && b->ev_want) {
-    // [mean | stdev | median] x capacity; rows of reads that fail keep the zeros
-    HIP_TRY(a, b->d_ev.ensure(std::max<uint64_t>(24, b->capacity * 24)));
-    if (b->capacity) HIP_TRY(a, hipMemsetAsync(b->d_ev.p, 0, b->capacity * 24, a->stream));
-    double* e = b->d_ev.as<double>();
+  if (int rc = output_prepare(b, OUT_LEVELS, calc ? output_wanted(b->want, OUT_LEVELS) : 0, a->stream)) return rc;
+  if (b->out[OUT_LEVELS].ready) {  // [mean | stdev | median] x capacity
+    double* e = b->out[OUT_LEVELS].d.as<double>();
     evc = dynk::EventCols{q.sig, e, e + b->capacity, e + 2 * b->capacity};
-    b->ev_ready = true;
   }
   dynk::ScoreCols scc{};
-  b->sc_ready = false;
-  if (calc && b->sc_want) {
-    // [median_delta | mad_delta | homogeneity | scratch] x capacity; rows of reads that fail keep the zeros
-    HIP_TRY(a, b->d_sc.ensure(std::max<uint64_t>(32, b->capacity * 32)));
-    if (b->capacity) HIP_TRY(a, hipMemsetAsync(b->d_sc.p, 0, b->capacity * 32, a->stream));
-    double* e = b->d_sc.as<double>();
-    scc = dynk::ScoreCols{q.sig, e, e + b->capacity, e + 2 * b->capacity, e + 3 * b->capacity, b->sc_want};
-    b->sc_ready = true;
+  if (int rc = output_prepare(b, OUT_SCORES, calc ? output_wanted(b->want, OUT_SCORES) : 0, a->stream)) return rc;
+  if (b->out[OUT_SCORES].ready) {  // [median_delta | mad_delta | homogeneity | scratch] x capacity
+    double* e = b->out[OUT_SCORES].d.as<double>();
+    scc = dynk::ScoreCols{q.sig, e, e + b->capacity, e + 2 * b->capacity, e + 3 * b->capacity, b->want.segment_scores};
   }
   if (calc) {
     // the per-k-mer summary (once per job, after the last pass: the signal of a rescaling job is its last pass's)
@@ -938,7 +915,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
 std::vector<dynk::KmerSummary> kmer_summary_args(const dyn_batch* b) {
   std::vector<dynk::KmerSummary> out;
   const dyn_aligner* a = b->a;
-  if (!b->ks_want || !a->d_ksum.p) return out;
+  if (!b->want.kmer_summary || !a->d_ksum.p) return out;
   unsigned long long* acc = a->d_ksum.as<unsigned long long>();
   dynk::KmerSummary ks{b->d_sig.as<double>(), b->d_kmers.as<int32_t>(), acc, acc + 6 * a->model.num_kmers,
                        (uint32_t)a->model.num_kmers, 0u, (uint32_t)b->n};
@@ -954,9 +931,30 @@ std::vector<dynk::KmerSummary> kmer_summary_args(const dyn_batch* b) {
   return out;
 }
 
+int output_ensure(dyn_batch* b, Output k, int ready) {
+  OutputBuf& o = b->out[k];
+  o.ready = 0;
+  if (!ready) return DYN_OK;
+  const uint64_t bytes = (uint64_t)ready * OUTPUTS[k].row_bytes * b->capacity + (k == OUT_SAMPLES ? b->n * 4 : 0);
+  HIP_TRY(b->a, o.d.ensure(std::max<uint64_t>(32, bytes)));
+  o.ready = ready;
+  return DYN_OK;
+}
+
+int output_zero(dyn_batch* b, Output k, hipStream_t s) {
+  const uint64_t bytes = (uint64_t)b->out[k].ready * OUTPUTS[k].row_bytes * b->capacity + (k == OUT_SAMPLES ? b->n * 4 : 0);
+  if (b->out[k].ready && bytes) HIP_TRY(b->a, hipMemsetAsync(b->out[k].d.p, 0, bytes, s));
+  return DYN_OK;
+}
+
+int output_prepare(dyn_batch* b, Output k, int ready, hipStream_t s) {
+  if (int rc = output_ensure(b, k, ready)) return rc;
+  return output_zero(b, k, s);
+}
+
 int band_margin_prepare(dyn_batch* b, bool calc) {
   b->bm_ready = false;
-  if (!calc || !b->bm_want) return DYN_OK;
+  if (!calc || !b->want.band_margin) return DYN_OK;
   HIP_TRY(b->a, b->d_bm.ensure(std::max<uint64_t>(12, b->n * 12)));
   b->bm_ready = true;
   return DYN_OK;

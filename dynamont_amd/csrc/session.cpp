@@ -185,7 +185,7 @@ bool session_candidate(const dyn_batch* b) {
   // a launch of its own, for which an open session is quiesced.
   // A ticket under the guide rescue (dyn_aligner_set_guide_rescue) is a classic launch too -- an INTERIM: its
   // rescue stage is a guided kernel, and a guided kernel beside resident waves is what did not make progress before.
-  return a->sess_enabled.load() && !a->host_only && !a->ntk && b->async && b->job == DynJob::AlignFull && b->rs_want == 0 && b->bc_want == 0 && b->bi_want == 0 && b->ps_want == 0 && b->ag_want == 0 && b->gr_hw == 0 &&
+  return a->sess_enabled.load() && !a->host_only && !a->ntk && b->async && b->job == DynJob::AlignFull && b->want.rescale_iters == 0 && b->want.border_confidence == 0 && b->want.border_interval == 0 && b->want.merges() &&
          (a->sess_open_hint.load() || b->n >= SESSION_MIN_READS);
 }
 
@@ -379,10 +379,9 @@ int session_publish(dyn_batch* b) {
   HIP_TRY(a, b->d_segrow.ensure(std::max<uint64_t>(4, b->capacity * 4)));
   HIP_TRY(a, b->d_medhi.ensure(std::max<uint64_t>(8, b->capacity * 8)));
   HIP_TRY(a, b->d_medlo.ensure(std::max<uint64_t>(8, b->capacity * 8)));
-  b->ev_ready = b->ev_want;  // the columns are filled by session_finish_enqueue, behind the per-segment kernels
-  if (b->ev_want) HIP_TRY(a, b->d_ev.ensure(std::max<uint64_t>(24, b->capacity * 24)));
-  b->sc_ready = b->sc_want != 0;
-  if (b->sc_want) HIP_TRY(a, b->d_sc.ensure(std::max<uint64_t>(32, b->capacity * 32)));
+  // (the columns are zeroed and filled by session_finish_enqueue, behind the per-segment kernels)
+  for (Output k : {OUT_LEVELS, OUT_SCORES})
+    if (int rc = output_ensure(b, k, output_wanted(b->want, k))) return rc;
   if (int rc = band_margin_prepare(b, true)) return rc;  // filled by session_finish_enqueue as well
   ReadState* st = b->h_state.as<ReadState>();
   for (uint64_t i = 0; i < b->n; ++i) {
@@ -539,16 +538,16 @@ int session_finish_enqueue(dyn_batch* b, hipStream_t s) {
   dynk::TraceBuffers tb{b->d_pp.as<double>(), b->d_pathn.as<uint32_t>(), b->d_segrow.as<uint32_t>(), b->d_medhi.as<double>(),
                         b->d_medlo.as<double>()};
   dynk::EventCols evc{};
-  if (b->ev_ready) {
-    if (b->capacity) HIP_TRY(a, hipMemsetAsync(b->d_ev.p, 0, b->capacity * 24, s));
-    double* e = b->d_ev.as<double>();
+  for (Output k : {OUT_LEVELS, OUT_SCORES})
+    if (int rc = output_zero(b, k, s)) return rc;
+  if (b->out[OUT_LEVELS].ready) {
+    double* e = b->out[OUT_LEVELS].d.as<double>();
     evc = dynk::EventCols{b->d_sig.as<double>(), e, e + b->capacity, e + 2 * b->capacity};
   }
   dynk::ScoreCols scc{};
-  if (b->sc_ready) {
-    if (b->capacity) HIP_TRY(a, hipMemsetAsync(b->d_sc.p, 0, b->capacity * 32, s));
-    double* e = b->d_sc.as<double>();
-    scc = dynk::ScoreCols{b->d_sig.as<double>(), e, e + b->capacity, e + 2 * b->capacity, e + 3 * b->capacity, b->sc_want};
+  if (b->out[OUT_SCORES].ready) {
+    double* e = b->out[OUT_SCORES].d.as<double>();
+    scc = dynk::ScoreCols{b->d_sig.as<double>(), e, e + b->capacity, e + 2 * b->capacity, e + 3 * b->capacity, b->want.segment_scores};
   }
   const std::vector<dynk::KmerSummary> ks = kmer_summary_args(b);
   const std::vector<dynk::BandMargin> bm = band_margin_args(b);

@@ -432,9 +432,9 @@ def _report_band(aligner, rescue=None):
 
 def _rescue_codes(t):
     """--guide-rescue: the per-read codes of a COMPLETED ticket (None for a ticket submitted without the switch)"""
-    if not getattr(t, "_rescued", False):
+    if not t._wants.rescue:
         return None
-    t.result._fetch_rescue(t._L, t._h, t._al, True)
+    t.result._fetch_one(t._L, t._h, t._al, "rescue", True)
     return t.result.rescue
 
 
