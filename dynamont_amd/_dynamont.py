@@ -118,6 +118,9 @@ class AlignBatchResult:
         # per-border credible intervals (Aligner.set_border_interval): border_lo / border_hi uint32 [cap], border_mean / border_sd
         # float64 [cap], indexed like the segment columns; None when off
         self.border_lo = self.border_hi = self.border_mean = self.border_sd = None
+        # posterior-weighted per-base sums (Aligner.set_soft_levels): soft_weight / soft_sum / soft_sumsq float64 [cap], indexed
+        # like the segment columns; None when off
+        self.soft_weight = self.soft_sum = self.soft_sumsq = None
         # band-margin diagnostics (Aligner.set_band_margin): uint32 [n] each, None when off; band_used (uint32 [n]): the band
         # every read's rows come from, only with Aligner.set_band_retry
         self.band_margin_low = self.band_margin_high = self.band_edge_rows = None
@@ -202,6 +205,9 @@ class AlignBatchResult:
         if self.border_lo is not None:  # only when requested (Aligner.set_border_interval)
             for key in ("border_lo", "border_hi", "border_mean", "border_sd"):
                 d[key] = getattr(self, key)[a:b].copy()
+        if self.soft_weight is not None:  # only when requested (Aligner.set_soft_levels)
+            d["soft_dwell"], d["soft_mean"], d["soft_stdv"] = soft_level_columns(self.soft_weight[a:b], self.soft_sum[a:b],
+                                                                                 self.soft_sumsq[a:b])
         if self.rescale_shift is not None:  # only when requested (Aligner.set_rescale)
             d["rescale_shift"] = float(self.rescale_shift[i])
             d["rescale_scale"] = float(self.rescale_scale[i])
@@ -215,6 +221,18 @@ class AlignBatchResult:
         return d
 
 
+def soft_level_columns(weight, total, sumsq):
+    """(soft_dwell, soft_mean, soft_stdv) of the three posterior-weighted sums: the weight itself,
+    ``sum / weight`` and ``sqrt(max(sumsq / weight - mean^2, 1e-12))`` (the reference's M-step clamp); NaN mean and stdv where the
+    weight is 0."""
+    w = np.array(weight, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.asarray(total, dtype=np.float64) / w
+        var = np.asarray(sumsq, dtype=np.float64) / w - mean * mean
+        stdv = np.sqrt(np.where(var < 1e-12, 1e-12, var))
+    return w, mean, stdv
+
+
 class JobWants(NamedTuple):
     """What ONE align job / ticket took of the aligner's opt-in switches at its submission (``Aligner._job_wants``). All off: a
     Z-only or a train job, a batch never aligned."""
@@ -226,6 +244,7 @@ class JobWants(NamedTuple):
     intervals: bool = False  # set_border_interval
     margins: bool = False    # set_band_margin (tickets report margins; they are never retried)
     rescue: bool = False     # set_guide_rescue
+    soft: bool | None = None  # set_soft_levels (off is None, like the field behind it: both stand behind the positional fields)
     auto_guide: tuple | None = None  # set_auto_guide, tickets only: (alignments per read, the ticket's sample offsets)
 
 
@@ -245,6 +264,8 @@ _OPTIONAL = {
     "samples": ((("sample_starts", _U32, "Kcap"), ("sample_dead", _U32, "n")), N.DynSampleOut, "dyn_batch_fetch_samples"),
     "intervals": ((("border_lo", _U32, "cap"), ("border_hi", _U32, "cap"), ("border_mean", _F64, "cap"), ("border_sd", _F64, "cap")),
                   N.DynBorderIntervalOut, "dyn_batch_fetch_intervals"),
+    "soft": ((("soft_weight", _F64, "cap"), ("soft_sum", _F64, "cap"), ("soft_sumsq", _F64, "cap")),
+             N.DynSoftLevelOut, "dyn_batch_fetch_soft_levels"),
     "margins": ((("band_margin_low", _U32, "n"), ("band_margin_high", _U32, "n"), ("band_edge_rows", _U32, "n")),
                 N.DynBandMarginOut, "dyn_batch_fetch_band_margin"),
     "rescue": ((("rescue", np.uint8, "n"), ("guide_rounds", _U32, "n"), ("guide_converged", _U32, "n")),
@@ -275,16 +296,16 @@ def format_csv(aligner: "Aligner", res: AlignBatchResult, sequences: Sequence[st
     L = N.lib()
     # the optional columns the result carries, in the order the rows hold them: the signal levels (Aligner.set_event_stats), the
     # segment scores (set_segment_scores), the border confidence (set_border_confidence), the posterior samples
-    # (set_posterior_samples), the credible intervals (set_border_interval)
-    ev, sc, bd, sm, bi = (C.byref(res._out_struct(name)) if getattr(res, _OPTIONAL[name][0][0][0]) is not None else None
-                          for name in ("levels", "scores", "borders", "samples", "intervals"))
-    cap = int(L.dyn_format_csv_bound_intervals(aligner._h, n, C.byref(res._c), ev, sc, bd, sm, bi, rid, sid))
+    # (set_posterior_samples), the credible intervals (set_border_interval), the soft levels (set_soft_levels)
+    ev, sc, bd, sm, bi, sl = (C.byref(res._out_struct(name)) if getattr(res, _OPTIONAL[name][0][0][0]) is not None else None
+                              for name in ("levels", "scores", "borders", "samples", "intervals", "soft"))
+    cap = int(L.dyn_format_csv_bound_soft(aligner._h, n, C.byref(res._c), ev, sc, bd, sm, bi, sl, rid, sid))
     # one grow-only buffer per handle: first-touch page faults of a fresh 350 MB buffer cost ~100x
     # the formatting itself (15 ms per 1 024-read batch with warm pages)
     buf = getattr(aligner, "_csv_buf", None)
     if buf is None or buf.size < cap:
         buf = aligner._csv_buf = np.empty(max(cap, 1), dtype=np.uint8)
-    rc = L.dyn_format_csv_intervals(aligner._h, n, C.byref(res._c), ev, sc, bd, sm, bi, seqs, _ptr(seq_off, N.c_u64_p), rid, sid,
+    rc = L.dyn_format_csv_soft(aligner._h, n, C.byref(res._c), ev, sc, bd, sm, bi, sl, seqs, _ptr(seq_off, N.c_u64_p), rid, sid,
                           so.ctypes.data_as(C.POINTER(C.c_int64)), li.ctypes.data_as(C.POINTER(C.c_int64)),
                           int(threads), buf.ctypes.data, cap, _ptr(begin, N.c_u64_p), _ptr(end, N.c_u64_p))
     if rc != N.DYN_OK:
@@ -491,6 +512,7 @@ class Batch:
     fetch_borders = _fetch_into("dyn_batch_fetch_borders")            # N.DynBorderOut
     fetch_samples = _fetch_into("dyn_batch_fetch_samples")            # N.DynSampleOut
     fetch_intervals = _fetch_into("dyn_batch_fetch_intervals")        # N.DynBorderIntervalOut
+    fetch_soft_levels = _fetch_into("dyn_batch_fetch_soft_levels")    # N.DynSoftLevelOut
     fetch_band_margin = _fetch_into("dyn_batch_fetch_band_margin")    # N.DynBandMarginOut
     fetch_rescale = _fetch_into("dyn_batch_fetch_rescale")            # N.DynRescaleOut
 
@@ -588,6 +610,7 @@ class AsyncBatch:
     fetch_borders = Batch.fetch_borders
     fetch_samples = Batch.fetch_samples
     fetch_intervals = Batch.fetch_intervals
+    fetch_soft_levels = Batch.fetch_soft_levels
     fetch_band_margin = Batch.fetch_band_margin
 
     def timing(self) -> dict:
@@ -693,6 +716,7 @@ class Aligner:
     _border_confidence = 0  # set_border_confidence
     _posterior_samples = (0, 0)  # set_posterior_samples: (count, seed)
     _border_interval = 0.0  # set_border_interval: the mass
+    _soft_levels = False  # set_soft_levels
     _band_margin = False  # set_band_margin
     _auto_guide = (0, 8)  # set_auto_guide: (half_width, refine)
     _band_retry = None  # set_band_retry: (min_margin, max_band, factor)
@@ -842,6 +866,20 @@ class Aligner:
             _raise(rc, self.last_error())
         self._border_interval = float(mass)
 
+    def set_soft_levels(self, on: bool) -> None:
+        """dyn_aligner_set_soft_levels: align(calc_probabilities=True) jobs submitted while it is on also compute, on the GPU from
+        every read's own lattice, the posterior-weighted per-base sums: ``AlignBatchResult.soft_weight``
+        (the expected dwell of the base, in samples), ``.soft_sum`` and ``.soft_sumsq`` (float64 ``[cap]``: the signal and its
+        square under the same weights -- additive over reads and positions, and summed per k-mer the read's share of ``train()``'s
+        ``weight`` / ``sum`` / ``sumsq``); ``read(i)`` gains ``soft_dwell``, ``soft_mean`` and ``soft_stdv``. Off by default. A job
+        started with ``set_border_confidence``, ``set_posterior_samples``, ``set_border_interval``, ``set_auto_guide`` or
+        ``set_guide_rescue`` on as well, or on a guided batch, is refused (ValueError); with ``set_rescale`` the values are the
+        last pass's, over the last pass's signal. ``MultiAligner`` has no such switch."""
+        rc = self._L.dyn_aligner_set_soft_levels(self._h, int(bool(on)))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        self._soft_levels = bool(on)
+
     def set_posterior_samples(self, count: int, seed: int = 0) -> None:
         """dyn_aligner_set_posterior_samples: align(calc_probabilities=True) jobs submitted while ``count`` (0 .. 64) > 0 also
         draw ``count`` complete alignments of every read from the posterior distribution over alignments, on the GPU from the
@@ -893,13 +931,14 @@ class Aligner:
 
     def _job_wants(self, calc_probabilities: bool, sig_off=None) -> JobWants:
         """What an align job submitted NOW takes of the switches. ``sig_off``: the sample offsets of a TICKET (the auto-guide switch
-        concerns tickets alone). The Z-only job takes nothing; modes ntk / resquiggle have no samples, intervals, rescue or guide."""
+        concerns tickets alone). The Z-only job takes nothing; modes ntk / resquiggle have no samples, intervals, soft levels, rescue
+        or guide."""
         if not calc_probabilities:
             return JobWants()
         plain = self._ctor[2] not in ("ntk", "resquiggle")
         return JobWants(levels=bool(self._event_stats), rescale=self._rescale > 0, scores=self._segment_scores > 0,
                         borders=self._border_confidence > 0, samples=self._posterior_samples[0] if plain else 0,
-                        intervals=plain and self._border_interval > 0, margins=bool(self._band_margin),
+                        intervals=plain and self._border_interval > 0, soft=(plain and self._soft_levels) or None, margins=bool(self._band_margin),
                         rescue=plain and self._guide_rescue[1] > 0,
                         auto_guide=(self._auto_guide[1], sig_off) if plain and sig_off is not None and self._auto_guide[0] > 0 else None)
 
@@ -975,13 +1014,14 @@ class Aligner:
         al.set_segment_scores(self._segment_scores)
         al.set_border_confidence(self._border_confidence)
         al.set_border_interval(self._border_interval)
+        al.set_soft_levels(self._soft_levels)
         al.set_band_margin(True)
         return al
 
     # per-row and per-read columns a retried read's entries are spliced into (those that are on)
     _ROW_COLUMNS = ("sequence_positions", "signal_positions", "probabilities", "states", "level_mean", "level_stdv", "level_median",
                     "median_delta", "mad_delta", "homogeneity", "border_probability", "border_window_probability",
-                    "border_lo", "border_hi", "border_mean", "border_sd")
+                    "border_lo", "border_hi", "border_mean", "border_sd", "soft_weight", "soft_sum", "soft_sumsq")
     _READ_COLUMNS = ("Z", "rescale_shift", "rescale_scale", "rescale_iters", "band_margin_low", "band_margin_high", "band_edge_rows")
 
     def _retry_bands(self, res: AlignBatchResult, signals: Sequence, sequences: Sequence[str]) -> None:

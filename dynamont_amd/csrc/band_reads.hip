@@ -53,6 +53,7 @@
 
 #include "border_kernels.hpp"
 #include "interval_kernels.hpp"
+#include "soft_level_kernels.hpp"
 #include "sample_kernels.hpp"
 #include "dp_math_strict.hpp"
 
@@ -535,6 +536,39 @@ __global__ __launch_bounds__(256) void k_band_reads_interval(const BandArgs a) {
   }
 }
 
+// ... and with the soft-level phase (soft_level_kernels.hpp) behind every read, a kernel of its own likewise: one thread per
+// column walks that column's row interval through BorderCellWide / SampleLpeWide
+__global__ __launch_bounds__(256) void k_band_reads_soft(const BandArgs a) {
+  constexpr int THREADS = 256, CPT = 16;
+  using Window = DiagonalWindow;
+  extern __shared__ __attribute__((aligned(16))) char g_lds[];
+  char* lds = Window::lds(g_lds);
+  const int stride = Window::row_stride(a);
+  uint64_t* s_exp = reinterpret_cast<uint64_t*>(lds);
+  double* s_rows = reinterpret_cast<double*>(lds + dynmath::STRICT_EXP_WORDS * 8);
+  int* s_ctl = reinterpret_cast<int*>(s_rows + 4 * stride);  // [0] next read, [1] s_bad
+  for (int i = threadIdx.x; i < dynmath::STRICT_EXP_WORDS; i += THREADS) s_exp[i] = a.exp_tab[i];
+  char* arena = a.arena + (size_t)blockIdx.x * a.arena_bytes;
+  for (;;) {
+    __syncthreads();
+    if (threadIdx.x == 0) s_ctl[0] = (int)atomicAdd(a.head, 1u);
+    __syncthreads();
+    const int k = s_ctl[0];
+    if (k >= a.n_reads) break;
+    const ReadDesc rd = a.descs[k];
+    const size_t cells = (size_t)rd.T * (size_t)(2 * Window(rd, a).bw + 3);
+    double* bE = reinterpret_cast<double*>(arena);
+    double* bM = bE + cells;
+    float* lp = reinterpret_cast<float*>(bM + cells);
+    uint8_t* bit = reinterpret_cast<uint8_t*>(lp + 2 * cells);
+    band_read<Window, THREADS, CPT, true, false>(rd, a, bE, bM, lp, bit, s_rows, stride, s_exp, s_ctl + 1);
+    if (__hip_atomic_load(&a.st[rd.read].status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) {
+      const BorderBand band{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio};
+      soft_levels_read_columns(BorderCellWide{band, lp}, SampleLpeWide{band, lp}, band, rd, a.sig + rd.sig_off, a.soft, (int)threadIdx.x, THREADS);
+    }
+  }
+}
+
 uint64_t band_arena_bytes(uint64_t T, uint64_t bw, int job) {
   if (job == 0) return 0;
   const uint64_t cells = T * (2 * bw + 3);
@@ -590,7 +624,9 @@ hipError_t launch_band_reads(int job, const BandArgs& a, int n_groups, hipStream
   if (job == 2 && !(a.tr.col_w && a.tr.col_s1 && a.tr.col_s2 && a.tr.trans)) return hipErrorInvalidValue;
   if (job != 0 && !a.arena) return hipErrorInvalidValue;
   if (a.border_window > 0 && (a.guide || job != 1 || !a.border_p || !a.border_window_p)) return hipErrorInvalidValue;
-  if (job == 1 && a.sample.count != 0 && (a.sample.count < 0 || a.guide || a.active || job != 1 || a.sample.count > PS_MAX_SAMPLES || !a.sample.start))
+  const bool soft = job == 1 && a.soft.tag == SOFT_TAG;  // dyn_aligner_set_soft_levels
+  if (soft && (a.guide || a.active || a.border_window > 0 || !a.soft.weight || a.soft.zero != 0)) return hipErrorInvalidValue;
+  if (!soft && job == 1 && a.sample.count != 0 && (a.sample.count < 0 || a.guide || a.active || job != 1 || a.sample.count > PS_MAX_SAMPLES || !a.sample.start))
     return hipErrorInvalidValue;
   const bool interval = job == 1 && a.sample.count == 0 && a.interval.tail > 0.0;  // dyn_aligner_set_border_interval
   if (interval && (a.guide || a.active || a.border_window > 0 || !a.interval.mean || !(a.interval.tail < 0.5))) return hipErrorInvalidValue;
@@ -605,6 +641,10 @@ hipError_t launch_band_reads(int job, const BandArgs& a, int n_groups, hipStream
     }
     if (interval) {
       hipLaunchKernelGGL(k_band_reads_interval, dim3(n_groups), dim3(256), 0, s, a);
+      return hipGetLastError();
+    }
+    if (soft) {
+      hipLaunchKernelGGL(k_band_reads_soft, dim3(n_groups), dim3(256), 0, s, a);
       return hipGetLastError();
     }
     if (a.border_window > 0) return launch_kernel<DiagonalWindow, 256, 16, true, false, true>(a, n_groups, 0, s);

@@ -36,6 +36,7 @@ struct BandArgs {
     TrainBuffers tr;       // job 2 only: the read's column sums at col_* + ReadDesc::par_off, trans[2 * read]
     SampleOut sample;      // job 1 only, diagonal window, with or without a border window: posterior path samples, count > 0 when asked for
     IntervalOut interval;  // job 1 only, diagonal window, no border window: credible intervals, tail > 0 (and sample.count == 0) when asked for
+    SoftOut soft;          // job 1 only, diagonal window, no border window: posterior-weighted per-base sums, tag == SOFT_TAG when asked for
   };
   char* arena;             // n_groups arenas of arena_bytes: the lattice of the read a workgroup is working on (jobs 1 and 2)
   uint64_t arena_bytes;    // >= band_arena_bytes of the largest read
@@ -72,7 +73,8 @@ int band_groups_per_cu(bool guided, int bw, int job);
 // raising the dynamic-LDS limit (guided rows above 48 KiB) or the launch reported. hipErrorInvalidValue for a refining launch
 // (BandArgs::refine_rounds > 1) without a guide, with a job other than 1, with a border window or without rounds / converged,
 // for posterior samples (BandArgs::sample.count > 0) with a guide, a job other than 1 or without their arrays, and for credible
-// intervals (BandArgs::interval.tail > 0) with a guide, a border window or without their buffer.
+// intervals (BandArgs::interval.tail > 0) with a guide, a border window or without their buffer, and likewise for the soft levels
+// (BandArgs::soft.tag == SOFT_TAG).
 hipError_t launch_band_reads(int job, const BandArgs& a, int n_groups, hipStream_t s);
 
 }  // namespace dynk

@@ -101,6 +101,7 @@ struct Args {
   const dyn_border_out* bd;  // nullptr: no border-confidence columns
   const dyn_sample_out* sm;  // nullptr: no posterior-sample column
   const dyn_border_interval_out* bi;  // nullptr: no border-interval columns
+  const dyn_soft_level_out* sl;  // nullptr: no soft-level columns
   const char* seqs;
   const uint64_t* seq_offsets;
   const char* const* readids;
@@ -118,6 +119,24 @@ constexpr uint64_t kRowBound = 3 * 20 + 1 + 32 + 1 + 48 + 2 + 9 + 1;
 constexpr uint64_t kEventSmallBound = 1 + 16 + 1 + 6;
 constexpr uint64_t kEventValueBound = 1 + 309 + 1 + 6;
 inline uint64_t event_value_bound(double x) { return std::fabs(x) < 1e15 ? kEventSmallBound : kEventValueBound; }
+
+// the soft-level columns of output row s (dyn_soft_level_out): dwell, mean, stdv derived from the three sums
+struct SoftRow {
+  double dwell, mean, stdv;
+};
+inline SoftRow soft_row(const dyn_soft_level_out* sl, uint64_t s) {
+  const double w = sl->weight[s], m = sl->sum[s] / w;
+  const double v = sl->sumsq[s] / w - m * m;
+  return SoftRow{w, m, std::sqrt(v < 1e-12 ? 1e-12 : v)};  // (a NaN stays one)
+}
+// put_prob6<true>, with a NaN of either sign as "nan" (Python's f"{x:.6f}")
+inline char* put_soft(char* p, double x) {
+  if (std::isnan(x)) {
+    std::memcpy(p, "nan", 3);
+    return p + 3;
+  }
+  return put_prob6<true>(p, x);
+}
 
 uint64_t read_bound(const Args& a, uint64_t i) {
   if (a.res->status[i] != DYN_READ_OK) return 0;
@@ -148,6 +167,14 @@ uint64_t read_bound(const Args& a, uint64_t i) {
     for (uint64_t s = o; s < o + n; ++s)
       // (the mean is written with the read's offset added, an int64: 20 integer digits at most below 1e15 + 2^63)
       b += (std::fabs(a.bi->border_mean[s]) < 1e15 ? kEventSmallBound + 4 : kEventValueBound) + event_value_bound(a.bi->border_sd[s]);
+  }
+  if (a.sl) {
+    const uint64_t o = a.res->seg_offsets[i];
+    b += 3 * n;  // the commas
+    for (uint64_t s = o; s < o + n; ++s) {
+      const SoftRow r = soft_row(a.sl, s);
+      b += event_value_bound(r.dwell) + event_value_bound(r.mean) + event_value_bound(r.stdv);  // (a NaN takes the long bound)
+    }
   }
   return b;
 }
@@ -225,6 +252,15 @@ char* format_read(const Args& a, uint64_t i, char* p) {
       *p++ = ',';
       p = put_prob6<true>(p, a.bi->border_sd[o + s]);
     }
+    if (a.sl) {
+      const SoftRow r = soft_row(a.sl, o + s);
+      *p++ = ',';
+      p = put_soft(p, r.dwell);
+      *p++ = ',';
+      p = put_soft(p, r.mean);
+      *p++ = ',';
+      p = put_soft(p, r.stdv);
+    }
     *p++ = '\n';
   }
   return p;
@@ -265,12 +301,21 @@ extern "C" uint64_t dyn_format_csv_bound_intervals(const dyn_aligner* a, uint64_
                                                    const dyn_event_out* ev, const dyn_score_out* sc, const dyn_border_out* bd,
                                                    const dyn_sample_out* sm, const dyn_border_interval_out* bi,
                                                    const char* const* readids, const char* const* signalids) {
+  return dyn_format_csv_bound_soft(a, n_reads, res, ev, sc, bd, sm, bi, nullptr, readids, signalids);
+}
+
+extern "C" uint64_t dyn_format_csv_bound_soft(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
+                                              const dyn_event_out* ev, const dyn_score_out* sc, const dyn_border_out* bd,
+                                              const dyn_sample_out* sm, const dyn_border_interval_out* bi,
+                                              const dyn_soft_level_out* sl, const char* const* readids,
+                                              const char* const* signalids) {
+  if (sl && (!sl->weight || !sl->sum || !sl->sumsq)) return 0;
   if (bi && (!bi->border_lo || !bi->border_hi || !bi->border_mean || !bi->border_sd)) return 0;
   if (!a || !res || (ev && (!ev->mean || !ev->stdev || !ev->median)) ||
       (sc && (!sc->median_delta || !sc->mad_delta || !sc->homogeneity)) ||
       (bd && (!bd->border_probability || !bd->border_window_probability)) || (sm && !sm->sample_start))
     return 0;
-  Args args{0, 0, res, ev, sc, bd, sm, bi, nullptr, nullptr, readids, signalids, nullptr, nullptr};
+  Args args{0, 0, res, ev, sc, bd, sm, bi, sl, nullptr, nullptr, readids, signalids, nullptr, nullptr};
   uint64_t total = 0;
   for (uint64_t i = 0; i < n_reads; ++i) total += read_bound(args, i);
   return total;
@@ -328,6 +373,17 @@ extern "C" int dyn_format_csv_intervals(const dyn_aligner* a, uint64_t n_reads, 
                                         const uint64_t* seq_offsets, const char* const* readids, const char* const* signalids,
                                         const int64_t* sig_offsets, const int64_t* last_index, int threads, char* out,
                                         uint64_t out_cap, uint64_t* row_begin, uint64_t* row_end) {
+  return dyn_format_csv_soft(a, n_reads, res, ev, sc, bd, sm, bi, nullptr, seqs, seq_offsets, readids, signalids, sig_offsets, last_index,
+                             threads, out, out_cap, row_begin, row_end);
+}
+
+extern "C" int dyn_format_csv_soft(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                                   const dyn_score_out* sc, const dyn_border_out* bd, const dyn_sample_out* sm,
+                                   const dyn_border_interval_out* bi, const dyn_soft_level_out* sl, const char* seqs,
+                                   const uint64_t* seq_offsets, const char* const* readids, const char* const* signalids,
+                                   const int64_t* sig_offsets, const int64_t* last_index, int threads, char* out,
+                                   uint64_t out_cap, uint64_t* row_begin, uint64_t* row_end) {
+  if (sl && (!sl->weight || !sl->sum || !sl->sumsq)) return DYN_ERR_INVALID_ARGUMENT;
   if (bi && (!bi->border_lo || !bi->border_hi || !bi->border_mean || !bi->border_sd)) return DYN_ERR_INVALID_ARGUMENT;
   if (sm && !sm->sample_start) return DYN_ERR_INVALID_ARGUMENT;
   if (!a || !res || !res->status || !res->n_segments || !res->seg_offsets || !res->sequence_positions ||
@@ -338,7 +394,7 @@ extern "C" int dyn_format_csv_intervals(const dyn_aligner* a, uint64_t n_reads, 
   dyn_info info;
   dyn_aligner_info(a, &info);
   if (info.kmer_size > 31) return DYN_ERR_INVALID_ARGUMENT;
-  Args args{info.kmer_size, info.rna, res, ev, sc, bd, sm, bi, seqs, seq_offsets, readids, signalids, sig_offsets, last_index};
+  Args args{info.kmer_size, info.rna, res, ev, sc, bd, sm, bi, sl, seqs, seq_offsets, readids, signalids, sig_offsets, last_index};
   // every read formats straight into its own worst-case slot of the caller's buffer: no allocation,
   // no shared cache lines between threads
   uint64_t pos = 0;

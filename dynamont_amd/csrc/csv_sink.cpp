@@ -46,6 +46,7 @@ const char kHeaderScores[] = ",median_delta,mad_delta,homogeneity";
 const char kHeaderBorders[] = ",border_probability,border_window_probability";
 const char kHeaderSamples[] = ",sample_starts";
 const char kHeaderIntervals[] = ",border_lo,border_hi,border_mean,border_sd";
+const char kHeaderSoft[] = ",soft_dwell,soft_mean,soft_stdv";
 
 struct Blob {  // the formatted rows of one batch; freed when its last job has been compressed
   std::unique_ptr<char[]> data;
@@ -115,6 +116,8 @@ struct dyn_csv_sink {
   std::vector<uint32_t> sm_cols;              // [K][capacity] the batch's sample starts, then [n] its dead counts (dyn_batch_fetch_samples)
   bool intervals = false;                     // DYN_CSV_BORDER_INTERVAL
   std::vector<double> bi_cols;                // [2][capacity] f64 mean / sd, then [2][capacity] u32 lo / hi (dyn_batch_fetch_intervals)
+  bool soft = false;                          // DYN_CSV_SOFT_LEVELS
+  std::vector<double> sl_cols;                // [3][capacity] the batch's weight / sum / sumsq (dyn_batch_fetch_soft_levels)
   std::thread t_sink, t_writer;
   std::vector<std::thread> t_comp;
   std::vector<std::shared_ptr<Blob>> spare;  // recycled row buffers (first-touch page faults cost more than formatting)
@@ -315,12 +318,19 @@ struct dyn_csv_sink {
           return dyn_batch_fetch_intervals(it.ticket, &bi);
         }, "batch border intervals: "))
       return;
+    dyn_soft_level_out sl{};
+    if (soft && !fetch(sl_cols, 3 * cap, [&] {
+          sl = dyn_soft_level_out{sl_cols.data(), sl_cols.data() + cap, sl_cols.data() + 2 * cap, cap};
+          return dyn_batch_fetch_soft_levels(it.ticket, &sl);
+        }, "batch soft levels: "))
+      return;
     const dyn_event_out* evp = events ? &ev : nullptr;
     const dyn_score_out* scp = scores ? &sc : nullptr;
     const dyn_border_out* bdp = borders ? &bd : nullptr;
     const dyn_sample_out* smp = samples ? &sm : nullptr;
     const dyn_border_interval_out* bip = intervals ? &bi : nullptr;
-    const uint64_t bound = dyn_format_csv_bound_intervals(it.a, it.n, it.res, evp, scp, bdp, smp, bip, it.readids, it.signalids);
+    const dyn_soft_level_out* slp = soft ? &sl : nullptr;
+    const uint64_t bound = dyn_format_csv_bound_soft(it.a, it.n, it.res, evp, scp, bdp, smp, bip, slp, it.readids, it.signalids);
     std::shared_ptr<Blob> blob;
     {
       std::lock_guard<std::mutex> lk(m);
@@ -338,7 +348,7 @@ struct dyn_csv_sink {
       if (spare.size() < 4) spare.push_back(blob);
     }
     const double c2 = now_ms();
-    const int frc = dyn_format_csv_intervals(it.a, it.n, it.res, evp, scp, bdp, smp, bip, it.seqs, it.seq_offsets, it.readids, it.signalids, it.sig_offsets,
+    const int frc = dyn_format_csv_soft(it.a, it.n, it.res, evp, scp, bdp, smp, bip, slp, it.seqs, it.seq_offsets, it.readids, it.signalids, it.sig_offsets,
                                           last_index.data(), std::min(threads, 8), blob->data.get(), blob->cap, begin.data(), end.data());
     if (frc != DYN_OK) {
       std::lock_guard<std::mutex> lk(m);
@@ -386,6 +396,7 @@ struct dyn_csv_sink {
       if (borders) text.insert(text.size() - 1, kHeaderBorders);
       if (samples) text.insert(text.size() - 1, kHeaderSamples);
       if (intervals) text.insert(text.size() - 1, kHeaderIntervals);
+      if (soft) text.insert(text.size() - 1, kHeaderSoft);
       const size_t len = text.size();
       hdr->cap = len + 1;
       hdr->data.reset(new char[hdr->cap]);
@@ -445,7 +456,7 @@ int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int 
   };
   if (!csv_zst_path || !errors_path || !out) return DYN_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  if (flags & ~(DYN_CSV_EVENT_STATS | DYN_CSV_SEGMENT_SCORES | DYN_CSV_BORDER_CONFIDENCE | DYN_CSV_POSTERIOR_SAMPLES | DYN_CSV_BORDER_INTERVAL)) {
+  if (flags & ~(DYN_CSV_EVENT_STATS | DYN_CSV_SEGMENT_SCORES | DYN_CSV_BORDER_CONFIDENCE | DYN_CSV_POSTERIOR_SAMPLES | DYN_CSV_BORDER_INTERVAL | DYN_CSV_SOFT_LEVELS)) {
     put("dyn_csv_sink_open_ex: unknown flags");
     return DYN_ERR_INVALID_ARGUMENT;
   }
@@ -471,6 +482,7 @@ int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int 
   s->borders = (flags & DYN_CSV_BORDER_CONFIDENCE) != 0;
   s->samples = (flags & DYN_CSV_POSTERIOR_SAMPLES) != 0;
   s->intervals = (flags & DYN_CSV_BORDER_INTERVAL) != 0;
+  s->soft = (flags & DYN_CSV_SOFT_LEVELS) != 0;
   dyn_csv_sink* p = s.release();
   for (int t = 0; t < p->threads; ++t) p->t_comp.emplace_back([p] { p->compress_loop(); });
   p->t_writer = std::thread([p] { p->writer_loop(); });
@@ -495,7 +507,8 @@ int dyn_csv_sink_submit_bases(dyn_csv_sink* s, dyn_aligner* a, dyn_batch* ticket
                                                {s->scores, DYN_CSV_SEGMENT_SCORES},
                                                {s->borders, DYN_CSV_BORDER_CONFIDENCE},
                                                {s->samples, DYN_CSV_POSTERIOR_SAMPLES},
-                                               {s->intervals, DYN_CSV_BORDER_INTERVAL}};
+                                               {s->intervals, DYN_CSV_BORDER_INTERVAL},
+                                               {s->soft, DYN_CSV_SOFT_LEVELS}};
   for (const auto& w : written)
     if (w.first)
       if (int rc = dyneng::batch_check_output(ticket, w.second)) return rc;  // the message is the handle's (dyn_aligner_last_error)

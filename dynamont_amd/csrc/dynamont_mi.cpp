@@ -585,6 +585,12 @@ int dyn_aligner_set_border_interval(dyn_aligner* a, double mass) {
   return DYN_OK;
 }
 
+int dyn_aligner_set_soft_levels(dyn_aligner* a, int on) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  a->opt.soft_levels = on != 0;
+  return DYN_OK;
+}
+
 int dyn_aligner_set_posterior_samples(dyn_aligner* a, int count, uint64_t seed) {
   if (!a) return DYN_ERR_INVALID_ARGUMENT;
   auto fail = [&](const std::string& msg) {
@@ -1166,14 +1172,14 @@ namespace dyneng {
 namespace {
 // the switches the rules below speak of: the setter, and how a refusal names the switch when it is the OTHER one
 // (SW_GUIDE: no handle switch -- the batch carries a guide of its own, dyn_batch_set_guide / dyn_batch_auto_guide)
-enum Sw { SW_RESCALE, SW_CONFIDENCE, SW_INTERVAL, SW_SAMPLES, SW_AUTO_GUIDE, SW_RESCUE, SW_GUIDE };
+enum Sw { SW_RESCALE, SW_CONFIDENCE, SW_INTERVAL, SW_SAMPLES, SW_AUTO_GUIDE, SW_RESCUE, SW_GUIDE, SW_SOFT };
 struct SwText {
   const char *setter, *on;
 };
 const SwText SW_TEXT[] = {{"dyn_aligner_set_rescale", "(a, iters > 0)"},        {"dyn_aligner_set_border_confidence", "(a, window > 0)"},
                           {"dyn_aligner_set_border_interval", "(a, mass > 0)"}, {"dyn_aligner_set_posterior_samples", "(a, count > 0)"},
                           {"dyn_aligner_set_auto_guide", "(a, half_width > 0)"}, {"dyn_aligner_set_guide_rescue", "(a, half_width > 0)"},
-                          {nullptr, nullptr}};
+                          {nullptr, nullptr},                                    {"dyn_aligner_set_soft_levels", "(a, 1)"}};
 // (switch, what it does not combine with), in the order a job is checked: the first rule it violates is the one its refusal names.
 //   guide rescue: the three re-align or read the lattice of every read -- the rescue's second alignment has no place in their
 //     order; and a guided batch is not rescued
@@ -1182,25 +1188,29 @@ const SwText SW_TEXT[] = {{"dyn_aligner_set_rescale", "(a, iters > 0)"},        
 //     the switches that re-align a read or align it inside a guide window have no such lattice to offer
 //   border interval: one lattice phase runs per launch for now (an INTERIM), and the switches that align a read
 //     inside a guide window have no diagonal lattice to offer
+//   soft levels: refused where the border interval is, for the same reasons, and together with the border interval itself
 const struct {
   Sw sw, other;
 } RULES[] = {{SW_RESCUE, SW_RESCALE},     {SW_RESCUE, SW_CONFIDENCE},  {SW_RESCUE, SW_AUTO_GUIDE},   {SW_RESCUE, SW_GUIDE},
              {SW_AUTO_GUIDE, SW_RESCALE}, {SW_AUTO_GUIDE, SW_CONFIDENCE},
              {SW_SAMPLES, SW_GUIDE},      {SW_SAMPLES, SW_RESCALE},    {SW_SAMPLES, SW_AUTO_GUIDE},  {SW_SAMPLES, SW_RESCUE},
              {SW_INTERVAL, SW_GUIDE},     {SW_INTERVAL, SW_CONFIDENCE}, {SW_INTERVAL, SW_SAMPLES},   {SW_INTERVAL, SW_AUTO_GUIDE},
-             {SW_INTERVAL, SW_RESCUE}};
+             {SW_INTERVAL, SW_RESCUE},
+             {SW_SOFT, SW_GUIDE},         {SW_SOFT, SW_CONFIDENCE},     {SW_SOFT, SW_SAMPLES},       {SW_SOFT, SW_AUTO_GUIDE},
+             {SW_SOFT, SW_RESCUE},        {SW_SOFT, SW_INTERVAL}};
 }  // namespace
 
 int resolve_job_options(dyn_aligner* a, DynJob job, bool ticket, bool guided, const char* api, JobOptions* out) {
   JobOptions w = a->opt;
-  if (job != DynJob::AlignFull || a->ntk) {  // the four that concern align jobs with probabilities alone; the Z-only and the train job ignore them
+  if (job != DynJob::AlignFull || a->ntk) {  // the five that concern align jobs with probabilities alone; the Z-only and the train job ignore them
     w.rescue_hw = 0;
     w.auto_guide_hw = 0;
     w.posterior_samples = 0;
     w.border_interval = 0.0;
+    w.soft_levels = false;
   }
   const bool on[] = {w.rescale_iters > 0, w.border_confidence > 0, w.border_interval > 0, w.posterior_samples > 0,
-                     w.auto_guide_hw > 0, w.rescue_hw > 0,         guided};
+                     w.auto_guide_hw > 0, w.rescue_hw > 0,         guided,                  w.soft_levels};
   for (const auto& r : RULES) {
     if (!on[r.sw] || !on[r.other] || (r.sw == SW_AUTO_GUIDE && !ticket)) continue;
     const SwText &x = SW_TEXT[r.sw], &y = SW_TEXT[r.other];
@@ -1523,6 +1533,8 @@ const OutputDesc OUTPUTS[OUT_COUNT] = {
      "the border confidence (DYN_CSV_BORDER_CONFIDENCE)"},
     {24, "dyn_batch_fetch_intervals", "dyn_border_interval_out", "dyn_aligner_set_border_interval(a, mass > 0)", DYN_CSV_BORDER_INTERVAL,
      "the border intervals (DYN_CSV_BORDER_INTERVAL)"},
+    {24, "dyn_batch_fetch_soft_levels", "dyn_soft_level_out", "dyn_aligner_set_soft_levels(a, 1)", DYN_CSV_SOFT_LEVELS,
+     "the soft levels (DYN_CSV_SOFT_LEVELS)"},
     {4, "dyn_batch_fetch_samples", "dyn_sample_out", "dyn_aligner_set_posterior_samples(a, count > 0)", DYN_CSV_POSTERIOR_SAMPLES,
      "the posterior samples (DYN_CSV_POSTERIOR_SAMPLES)"},
 };
@@ -1533,6 +1545,7 @@ int output_wanted(const JobOptions& w, Output k) {
     case OUT_SCORES: return w.segment_scores ? 1 : 0;
     case OUT_BORDERS: return w.border_confidence ? 1 : 0;
     case OUT_INTERVALS: return w.border_interval > 0 ? 1 : 0;
+    case OUT_SOFT: return w.soft_levels ? 1 : 0;
     default: return w.posterior_samples;
   }
 }
@@ -1624,6 +1637,19 @@ int dyn_batch_fetch_intervals(dyn_batch* b, dyn_border_interval_out* out) {
   HIP_TRY(a, copy_out(a, out->border_sd, e + f.src->capacity + f.seg0, b->capacity * 8));
   HIP_TRY(a, copy_out(a, out->border_lo, q + f.seg0, b->capacity * 4));
   HIP_TRY(a, copy_out(a, out->border_hi, q + f.src->capacity + f.seg0, b->capacity * 4));
+  return DYN_OK;
+}
+
+int dyn_batch_fetch_soft_levels(dyn_batch* b, dyn_soft_level_out* out) {
+  if (!b || !out || !out->weight || !out->sum || !out->sumsq) return DYN_ERR_INVALID_ARGUMENT;
+  dyn_aligner* a = b->a;
+  FetchSrc f;
+  const int rc = fetch_prologue(b, OUT_SOFT, out->capacity, &f);
+  if (rc != DYN_OK || !b->capacity) return rc;
+  const double* e = f.src->out[OUT_SOFT].d.as<double>() + f.seg0;
+  HIP_TRY(a, copy_out(a, out->weight, e, b->capacity * 8));
+  HIP_TRY(a, copy_out(a, out->sum, e + f.src->capacity, b->capacity * 8));
+  HIP_TRY(a, copy_out(a, out->sumsq, e + 2 * f.src->capacity, b->capacity * 8));
   return DYN_OK;
 }
 

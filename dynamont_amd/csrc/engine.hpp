@@ -140,12 +140,13 @@ struct JobOptions {
   int segment_scores = 0;       // dyn_aligner_set_segment_scores (window, 0 = off)
   int border_confidence = 0;    // dyn_aligner_set_border_confidence (window, 0 = off)
   double border_interval = 0;   // dyn_aligner_set_border_interval (mass, 0 = off)
+  bool soft_levels = false;     // dyn_aligner_set_soft_levels
   int posterior_samples = 0;    // dyn_aligner_set_posterior_samples (count, 0 = off)
   uint64_t sample_seed = 0;     // ... and its seed
   uint32_t auto_guide_hw = 0, auto_guide_rounds = 8;               // dyn_aligner_set_auto_guide (half width, 0 = off; alignments per read)
   uint32_t rescue_margin = 0, rescue_hw = 0, rescue_rounds = 8;    // dyn_aligner_set_guide_rescue (minimum margin; half width, 0 = off; alignments)
   // May tickets x and y share ONE launch (Pipeline::merge)? Three kinds of fields:
-  //   launch-wide: event_stats, rescale_iters, segment_scores, border_confidence, border_interval -- one value per launch, so the
+  //   launch-wide: event_stats, rescale_iters, segment_scores, border_confidence, border_interval, soft_levels -- one value per launch, so the
   //                members must agree; the launch's batch takes them from its first member
   //   per-ticket:  kmer_summary, band_margin -- not compared: the launch's batch lists the read ranges of the members that asked
   //   alone:       posterior_samples (the read's index in its OWN ticket keys the random stream), auto_guide_hw (a guide of its own
@@ -153,7 +154,7 @@ struct JobOptions {
   bool merges() const { return posterior_samples == 0 && auto_guide_hw == 0 && rescue_hw == 0; }
   bool same_launch(const JobOptions& y) const {
     return event_stats == y.event_stats && rescale_iters == y.rescale_iters && segment_scores == y.segment_scores &&
-           border_confidence == y.border_confidence && border_interval == y.border_interval;
+           border_confidence == y.border_confidence && border_interval == y.border_interval && soft_levels == y.soft_levels;
   }
   // the launch-wide part alone: what the batch of a merged launch runs under
   JobOptions launch_wide() const {
@@ -163,16 +164,18 @@ struct JobOptions {
     g.segment_scores = segment_scores;
     g.border_confidence = border_confidence;
     g.border_interval = border_interval;
+    g.soft_levels = soft_levels;
     return g;
   }
 };
 
 // ---- the per-segment outputs a job may add to its rows (one fetcher, one out-struct and one CSV flag each) ---------------------
-enum Output { OUT_LEVELS, OUT_SCORES, OUT_BORDERS, OUT_INTERVALS, OUT_SAMPLES, OUT_COUNT };
+enum Output { OUT_LEVELS, OUT_SCORES, OUT_BORDERS, OUT_INTERVALS, OUT_SOFT, OUT_SAMPLES, OUT_COUNT };
 struct OutputBuf {
   DevBuf d;       // OUT_LEVELS [3][capacity] f64 mean / stdev / median (event_stats.hip); OUT_SCORES [4][capacity] f64 median_delta /
                   // mad_delta / homogeneity / scratch (segment_scores.hip); OUT_BORDERS [2][capacity] f64 (border_kernels.hpp);
-                  // OUT_INTERVALS [2][capacity] f64 mean / sd, then [2][capacity] u32 lo / hi (interval_kernels.hpp); OUT_SAMPLES
+                  // OUT_INTERVALS [2][capacity] f64 mean / sd, then [2][capacity] u32 lo / hi (interval_kernels.hpp); OUT_SOFT [3][capacity] f64
+                  // weight / sum / sumsq (soft_level_kernels.hpp); OUT_SAMPLES
                   // [count][capacity] u32 sample starts, then [n] u32 dead samples (sample_kernels.hpp)
   int ready = 0;  // the last job computed the columns into d (OUT_SAMPLES: the count it sampled)
 };
@@ -459,8 +462,8 @@ std::vector<dynk::BandMargin> band_margin_args(const dyn_batch* b);
 // bm_ready and the room for the margins of an align(calc = 1) job of this batch / ticket
 int band_margin_prepare(dyn_batch* b, bool calc);
 // What a job of kind `job` submitted NOW through `api` ("dyn_batch_align", "dyn_batch_align_async": `ticket`) takes of the handle's
-// switches: the four that concern align(calc = 1) jobs outside modes ntk / resquiggle alone are masked (guide rescue, auto-guide
-// -- tickets only --, posterior samples, border interval), and a combination the rule table (dynamont_mi.cpp) or a guided batch
+// switches: the five that concern align(calc = 1) jobs outside modes ntk / resquiggle alone are masked (guide rescue, auto-guide
+// -- tickets only --, posterior samples, border interval, soft levels), and a combination the rule table (dynamont_mi.cpp) or a guided batch
 // forbids is refused with its text in last_error. No HIP call, no lock but err_mu: the same answer with and without a device.
 int resolve_job_options(dyn_aligner* a, DynJob job, bool ticket, bool guided, const char* api, JobOptions* out);
 // what the job's switches ask of output k: 0 = nothing, else what OutputBuf::ready becomes (1; OUT_SAMPLES: the count)

@@ -617,6 +617,10 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   // zeros), written by the read queue / the banded-lattice kernel of the LAST pass behind every read
   if (int rc = output_prepare(b, OUT_INTERVALS, calc ? output_wanted(b->want, OUT_INTERVALS) : 0, a->stream)) return rc;
   const bool bi_on = b->out[OUT_INTERVALS].ready != 0;
+  // soft levels: [weight | sum | sumsq] f64 x capacity in one buffer, zeroed here (rows of reads that fail keep the zeros), written
+  // by the read queue / the banded-lattice kernel of the LAST pass behind every read
+  if (int rc = output_prepare(b, OUT_SOFT, calc ? output_wanted(b->want, OUT_SOFT) : 0, a->stream)) return rc;
+  const bool sl_on = b->out[OUT_SOFT].ready != 0;
   // posterior path samples: [count][capacity] segment starts, then the per-read count of dead samples, zeroed here (rows of reads
   // that fail keep the zeros), written by the read queue / the banded-lattice kernel behind every read. (The callers refuse the
   // switches that would make this more than one pass.)
@@ -646,6 +650,10 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     }
     if (bi_on && pass + 1 == n_pass) {  // (the callers refuse the border confidence and the samples beside it)
       q.interval = dynk::IntervalOut{b->out[OUT_INTERVALS].d.as<double>(), b->capacity, (1.0 - b->want.border_interval) / 2, 0};
+      q.lpe_dense = 1;  // the phase reads whole columns of LPE (the kernel variant that carries it stores densely anyway)
+    }
+    if (sl_on && pass + 1 == n_pass) {  // (the callers refuse the other three lattice phases beside it)
+      q.soft = dynk::SoftOut{b->out[OUT_SOFT].d.as<double>(), b->capacity, 0, dynk::SOFT_TAG};
       q.lpe_dense = 1;  // the phase reads whole columns of LPE (the kernel variant that carries it stores densely anyway)
     }
     if (pass == 0) HIP_TRY(a, hipEventRecord(ev[0], a->stream));
@@ -679,7 +687,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
       ba.guide = b->guided ? b->d_guide.as<int32_t>() : nullptr;  // null: the diagonal window
       ba.st = q.st;
       ba.tb = q.tb;
-      ba.tr = q.tr;  // (an align job: the posterior samples or the credible intervals, which share the place)
+      ba.tr = q.tr;  // (an align job: the posterior samples, the credible intervals or the soft levels, which share the place)
       ba.head = arena_buf.as<uint32_t>();
       ba.arena = arena_buf.as<char>() + 256;
       ba.arena_bytes = wide_arena;

@@ -53,6 +53,7 @@
 #include "dp_cell.hpp"
 #include "dp_math_strict.hpp"
 #include "interval_kernels.hpp"
+#include "soft_level_kernels.hpp"
 #include "sample_kernels.hpp"
 #include "segment_kernels.hpp"
 #include "preprocess_kernels.hpp"
@@ -1532,17 +1533,20 @@ __global__ void k_pool_init(PagePool pool, uint32_t first_free, uint32_t n_stati
 // JOBX: the job, plus JOB_BORDER for the launches that carry the border-confidence phase (border_kernels.hpp) behind every
 // read. The phase is a bit of the job number and not a template parameter of its own, so that the instantiations without
 // it keep the names (and the code) they have always had. JOB_SAMPLE likewise: the posterior-sampling phase (sample_kernels.hpp),
-// and JOB_INTERVAL: the credible-interval phase (interval_kernels.hpp), which runs alone.
+// and JOB_INTERVAL: the credible-interval phase (interval_kernels.hpp), which runs alone, as does JOB_SOFT: the soft-level phase
+// (soft_level_kernels.hpp).
 template <int JOBX, bool MIXED>
 __global__ DYN_ONE_WAVE_PER_SIMD void k_read_queue(const QueueArgs q, const ReadDesc* __restrict__ descs,
                                                    const double* __restrict__ sig, const Emis* __restrict__ par,
                                                    const SoftplusNode* __restrict__ sp_tab) {
-  constexpr int JOB = JOBX & ~(JOB_BORDER | JOB_SAMPLE | JOB_INTERVAL);
+  constexpr int JOB = JOBX & ~(JOB_BORDER | JOB_SAMPLE | JOB_INTERVAL | JOB_SOFT);
   constexpr bool BORDER = (JOBX & JOB_BORDER) != 0;
   constexpr bool SAMPLE = (JOBX & JOB_SAMPLE) != 0;
   constexpr bool INTERVAL = (JOBX & JOB_INTERVAL) != 0;
-  static_assert(!(BORDER || SAMPLE || INTERVAL) || JOB == JOB_ALIGN || JOB == JOB_ALIGN_INPLACE, "borders and samples exist for align(calc=true) only");
+  constexpr bool SOFT = (JOBX & JOB_SOFT) != 0;
+  static_assert(!(BORDER || SAMPLE || INTERVAL || SOFT) || JOB == JOB_ALIGN || JOB == JOB_ALIGN_INPLACE, "borders and samples exist for align(calc=true) only");
   static_assert(!INTERVAL || !(BORDER || SAMPLE), "one lattice phase per launch");
+  static_assert(!SOFT || !(BORDER || SAMPLE || INTERVAL), "one lattice phase per launch");
   constexpr bool LATTICE = JOB != JOB_Z;
   // + 2^(i/128) as plain doubles (exp_table128_vec) + glibc's table of the strict exp (dp_math_strict.hpp)
   constexpr int TAB_NODES = SP_NODES + dynmath::EXP128_NODES + dynmath::STRICT_EXP_WORDS / 2;
@@ -1564,9 +1568,9 @@ __global__ DYN_ONE_WAVE_PER_SIMD void k_read_queue(const QueueArgs q, const Read
   lds_u64_t* sb = (lds_u64_t*)&s_ring[wave][0][0];  // traceback staging: the ring is idle by then
 
   WaveStats ws;
-  // the border-confidence phase reads whole windows of LPE, a sampled path any cell of the band, the interval phase whole
-  // columns: every cell is stored then
-  const float lpe_floor = (BORDER || SAMPLE || INTERVAL || q.lpe_dense) ? -INFINITY : q.lpe_floor;
+  // the border-confidence phase reads whole windows of LPE, a sampled path any cell of the band, the interval and the soft-level
+  // phase whole columns: every cell is stored then
+  const float lpe_floor = (BORDER || SAMPLE || INTERVAL || SOFT || q.lpe_dense) ? -INFINITY : q.lpe_floor;
   const uint64_t t_start = __builtin_amdgcn_s_memtime();
   uint32_t* ctl = q.pool.ctl;
   uint32_t have = 0;  // pages in this wave's table
@@ -1666,6 +1670,28 @@ __global__ DYN_ONE_WAVE_PER_SIMD void k_read_queue(const QueueArgs q, const Read
         }
       }
       ws.cyc_t += __builtin_amdgcn_s_memtime() - t7;
+    }
+    if constexpr (SOFT) {
+      // as the interval phase: one sweep of the whole wave over the read's rows, every lane at the band slots the sweeps gave it;
+      // a cell's posterior is the sum of its M and its E share
+      const uint64_t t8 = __builtin_amdgcn_s_memtime();
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      const ReadState* rs = q.st + rd.read;
+      if (__builtin_amdgcn_readfirstlane((int)ctl_load(reinterpret_cast<const uint32_t*>(&rs->status))) == 0) {
+        const BorderBand band{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio};
+        auto row = [&w](int t) { return pool_row(w, t); };
+        if constexpr (JOB == JOB_ALIGN) {
+          const double Zb = __hip_atomic_load(&rs->Zb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const BorderCellSeparate<decltype(row)> lpm{band, q.pool.lpe, q.pool.ws, sig + rd.sig_off, par + rd.par_off, Zb, q.m1, row};
+          const SampleLpeSeparate<decltype(row)> lpe{band, q.pool.lpe, row};
+          soft_levels_read_wave(lpm, lpe, band, rd, sig + rd.sig_off, q.soft, w.lane);
+        } else {
+          const BorderCellInplace<decltype(row)> lpm{band, reinterpret_cast<const float*>(q.pool.ws), row};
+          const SampleLpeInplace<decltype(row)> lpe{band, reinterpret_cast<const float*>(q.pool.ws), row};
+          soft_levels_read_wave(lpm, lpe, band, rd, sig + rd.sig_off, q.soft, w.lane);
+        }
+      }
+      ws.cyc_t += __builtin_amdgcn_s_memtime() - t8;
     }
   }
   // leaving: while a claimed read still lacks its pages, somebody may be waiting for these
@@ -1945,6 +1971,18 @@ void launch_read_queue(QueueJob job, bool with_strict, const QueueArgs& q, int n
   if (q.n_reads <= 0) return;
   const int groups = std::min((q.n_reads + DYN_WAVES_PER_GROUP - 1) / DYN_WAVES_PER_GROUP, std::max(1, n_cus));
   const dim3 grid(groups), block(64 * DYN_WAVES_PER_GROUP);
+  if (q.soft.tag == SOFT_TAG && (job == JOB_ALIGN || job == JOB_ALIGN_INPLACE)) {  // dyn_aligner_set_soft_levels
+#define DYN_SOFT_LAUNCH(J, M) hipLaunchKernelGGL((k_read_queue<J | JOB_SOFT, M>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab)
+    if (job == JOB_ALIGN) {
+      if (with_strict) DYN_SOFT_LAUNCH(JOB_ALIGN, true);
+      else DYN_SOFT_LAUNCH(JOB_ALIGN, false);
+    } else {
+      if (with_strict) DYN_SOFT_LAUNCH(JOB_ALIGN_INPLACE, true);
+      else DYN_SOFT_LAUNCH(JOB_ALIGN_INPLACE, false);
+    }
+#undef DYN_SOFT_LAUNCH
+    return;
+  }
   if (q.sample.count == 0 && q.interval.tail > 0.0 && (job == JOB_ALIGN || job == JOB_ALIGN_INPLACE)) {  // dyn_aligner_set_border_interval
 #define DYN_INTERVAL_LAUNCH(J, M) hipLaunchKernelGGL((k_read_queue<J | JOB_INTERVAL, M>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab)
     if (job == JOB_ALIGN) {

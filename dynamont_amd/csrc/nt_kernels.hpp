@@ -111,6 +111,8 @@ constexpr int JOB_BORDER = 8;  // a bit on top of JOB_ALIGN / JOB_ALIGN_INPLACE 
                                // carries the border-confidence phase (border_kernels.hpp)
 constexpr int JOB_INTERVAL = 32;  // likewise: the launch carries the credible-interval phase (interval_kernels.hpp); never together
                                   // with the other two
+constexpr int JOB_SOFT = 64;      // likewise: the launch carries the soft-level phase (soft_level_kernels.hpp); never together with
+                                  // any of the other three
 constexpr int JOB_SAMPLE = 16; // likewise: the launch carries the posterior-sampling phase (sample_kernels.hpp), behind the border
                                // phase when both bits are set
 
@@ -136,6 +138,21 @@ struct IntervalOut {
 };
 static_assert(offsetof(IntervalOut, none) == offsetof(SampleOut, count), "an interval launch reads as a launch without samples");
 
+// posterior-weighted per-base sums (dyn_aligner_set_soft_levels; soft_level_kernels.hpp): the three columns of a launch, in ONE
+// buffer of 24 bytes per output row:
+//   double weight[capacity] | double sum[capacity] | double sumsq[capacity]                         (zeroed by the caller)
+// It shares the same place. `zero` lies on SampleOut::seed / IntervalOut::tail and stays 0 (no interval launch), `tag` lies on
+// SampleOut::count / IntervalOut::none and is SOFT_TAG, a value neither of the others ever holds (a sample count is 0 .. 64).
+struct SoftOut {
+  double* weight;
+  uint64_t capacity;
+  uint64_t zero;  // = IntervalOut::tail: 0.0
+  int tag;        // = SampleOut::count: SOFT_TAG when asked for
+};
+constexpr int SOFT_TAG = -1;
+static_assert(offsetof(SoftOut, tag) == offsetof(SampleOut, count) && offsetof(SoftOut, zero) == offsetof(IntervalOut, tail),
+              "a soft-level launch reads as one without samples and without intervals");
+
 struct QueueArgs {
   const ReadDesc* descs;   // in processing order
   int n_reads;
@@ -151,6 +168,9 @@ struct QueueArgs {
     TrainBuffers tr;    // JOB_TRAIN / JOB_TRAIN_ZCHECK
     SampleOut sample;   // JOB_ALIGN / JOB_ALIGN_INPLACE: posterior path samples, count > 0 when asked for
     IntervalOut interval;  // JOB_ALIGN / JOB_ALIGN_INPLACE: per-border credible intervals, tail > 0 (and sample.count == 0) when asked for
+    SoftOut soft;       // JOB_ALIGN / JOB_ALIGN_INPLACE: posterior-weighted per-base sums, tag == SOFT_TAG when asked for
+    // Which member an align launch carries is read from ONE word, sample.count (= interval.none = soft.tag): > 0 the samples,
+    // SOFT_TAG the soft levels, 0 the intervals if interval.tail > 0 and else none of them.
   };
   double m1, e2;          // log transition probabilities (NT_aligner_api.cpp:84-86)
   const dynmath::SoftplusNode* sp_tab;
@@ -167,6 +187,7 @@ struct QueueArgs {
 };
 static_assert(sizeof(SampleOut) <= sizeof(TrainBuffers), "the samples take the train buffers' place in QueueArgs / BandArgs");
 static_assert(sizeof(IntervalOut) <= sizeof(TrainBuffers), "the intervals take the train buffers' place in QueueArgs / BandArgs");
+static_assert(sizeof(SoftOut) <= sizeof(TrainBuffers), "the soft levels take the train buffers' place in QueueArgs / BandArgs");
 
 // ---- the RESIDENT read queue (round 5) ---------------------------------------------------------------------------
 // k_read_queue drains ONE batch per launch: its waves finish up to one read apart, and the next launch -- queued on the same

@@ -185,7 +185,7 @@ bool session_candidate(const dyn_batch* b) {
   // a launch of its own, for which an open session is quiesced.
   // A ticket under the guide rescue (dyn_aligner_set_guide_rescue) is a classic launch too -- an INTERIM: its
   // rescue stage is a guided kernel, and a guided kernel beside resident waves is what did not make progress before.
-  return a->sess_enabled.load() && !a->host_only && !a->ntk && b->async && b->job == DynJob::AlignFull && b->want.rescale_iters == 0 && b->want.border_confidence == 0 && b->want.border_interval == 0 && b->want.merges() &&
+  return a->sess_enabled.load() && !a->host_only && !a->ntk && b->async && b->job == DynJob::AlignFull && b->want.rescale_iters == 0 && b->want.border_confidence == 0 && b->want.border_interval == 0 && !b->want.soft_levels && b->want.merges() &&
          (a->sess_open_hint.load() || b->n >= SESSION_MIN_READS);
 }
 

@@ -52,6 +52,8 @@ CSV_COLUMNS_BORDERS = b",border_probability,border_window_probability"
 CSV_COLUMNS_SAMPLES = b",sample_starts"
 # --border-interval MASS: ... and, after those, the credible interval and spread of the segment's start (Aligner.set_border_interval)
 CSV_COLUMNS_INTERVALS = b",border_lo,border_hi,border_mean,border_sd"
+# --soft-levels: ... and, after those, the posterior-weighted dwell, level and spread of the base (Aligner.set_soft_levels)
+CSV_COLUMNS_SOFT = b",soft_dwell,soft_mean,soft_stdv"
 POLYA = "AAAAAAAAA"
 
 MAX_SAMPLES_IN_FLIGHT = 512 << 20  # ~1 GB of pinned int16 staging + ~4 GB of float64 on the device, whatever --depth says
@@ -118,6 +120,12 @@ def parse(argv=None) -> Namespace:
                         "and the mean and standard deviation of that posterior, in the unit of the start column -- computed on the "
                         "GPU from the forward-backward lattice of the alignment. Not together with --border-confidence, "
                         "--posterior-samples, --guide-auto or --guide-rescue")
+    p.add_argument("--soft-levels", action="store_true",
+                   help="add soft_dwell, soft_mean, soft_stdv to every row (after every other optional column): the expected number "
+                        "of samples of the base and the mean and standard deviation of the normalised signal, weighted by the "
+                        "posterior that a sample belongs to the base instead of cut at the called borders -- computed on the GPU "
+                        "from the forward-backward lattice of the alignment. The library refuses it together with "
+                        "--border-confidence, --posterior-samples, --border-interval, --guide-auto or --guide-rescue")
     p.add_argument("--sample-seed", type=int, default=0, metavar="S", help="with --posterior-samples: the seed of the draws (default 0)")
     p.add_argument("--rescale-iters", type=int, default=0, choices=range(0, 9), metavar="N",
                    help="align every read N + 1 times (0 .. 8, default 0 = off), refitting the read's signal shift and scale "
@@ -672,6 +680,8 @@ class _NativePipeline:
             flags |= N.DYN_CSV_POSTERIOR_SAMPLES  # ... and the posterior samples (--posterior-samples)
         if aligner._border_interval:
             flags |= N.DYN_CSV_BORDER_INTERVAL  # ... and the credible intervals (--border-interval)
+        if aligner._soft_levels:
+            flags |= N.DYN_CSV_SOFT_LEVELS  # ... and the soft levels (--soft-levels)
         rc = self.L.dyn_csv_sink_open_ex(outfile.encode(), errfile.encode(), int(os.environ.get("DYN_SINK_LEVEL", level)), int(threads),
                                          int(first), int(last), flags, C.byref(h), err, 1024)
         if rc != N.DYN_OK:
@@ -893,7 +903,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             zstd_level: int = 3, event_stats: bool = False, rescale_iters: int = 0, kmer_summary: str = "",
             segment_scores: int = 0, border_confidence: int = 0, band_report: str = "", band: int = 400,
             guide_auto: int = 0, guide_rounds: int = 8, guide_rescue: int = 0, guide_rescue_margin: int = 1,
-            posterior_samples: int = 0, sample_seed: int = 0, border_interval: float = 0.0) -> None:
+            posterior_samples: int = 0, sample_seed: int = 0, border_interval: float = 0.0,
+            soft_levels: bool = False) -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
@@ -937,6 +948,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             header = header[:-1] + CSV_COLUMNS_SAMPLES + b"\n"
         if border_interval:
             header = header[:-1] + CSV_COLUMNS_INTERVALS + b"\n"
+        if soft_levels:
+            header = header[:-1] + CSV_COLUMNS_SOFT + b"\n"
         writer = threading.Thread(target=listener, args=(q, outfile, header), daemon=True)
         writer.start()
     sink = None if native else (q if comm is None else _Collector())
@@ -1024,6 +1037,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                 aligner.set_posterior_samples(posterior_samples, sample_seed)
             if border_interval:
                 aligner.set_border_interval(border_interval)
+            if soft_levels:
+                aligner.set_soft_levels(True)
             if kmer_summary:
                 aligner.set_kmer_summary(True)
             if band_report:
@@ -1187,7 +1202,7 @@ def main(argv=None) -> None:
             border_confidence=args.border_confidence, band_report=args.band_report, band=args.band,
             guide_auto=args.guide_auto, guide_rounds=args.guide_rounds, guide_rescue=args.guide_rescue,
             guide_rescue_margin=args.guide_rescue_margin, posterior_samples=args.posterior_samples, sample_seed=args.sample_seed,
-            border_interval=args.border_interval)
+            border_interval=args.border_interval, soft_levels=args.soft_levels)
     _stamp("segment() returned (aligner closed)")
     if argv is None and not int(__import__("os").environ.get("WORLD_SIZE", "1") or 1) > 1:
         # Invoked as the command (console script / python -m), single process, everything written and closed: leave without

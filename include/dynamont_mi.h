@@ -253,6 +253,33 @@ typedef struct dyn_border_interval_out {
   uint64_t capacity;    /* >= dyn_segment_capacity() */
 } dyn_border_interval_out;
 
+/* (added within ABI 10: a caller that must know looks the symbol up) Posterior-weighted per-base levels and expected dwell of an
+ * align(calc_probabilities = 1) job whose handle had dyn_aligner_set_soft_levels(a, 1) when the batch was submitted: what level
+ * the pore showed for every base and for how many samples, weighted by the lattice's own posteriors instead of cut at the called
+ * borders -- the per-base terms of dyn_batch_train's per-k-mer sums, additive over reads and reference positions.
+ * An ok read has signal x, T = len(x) + 1 lattice rows and N columns; sample x[t - 1] belongs to row t. Output row j is lattice
+ * column n = j + 1. LPM(t, n) and LPE(t, n) are the log-posteriors of the cell's M and E state, LPM exactly the value
+ * dyn_border_out is defined over and LPE its twin ((fE(t, n) + bE(t, n)) - Z); both are -inf outside the reference's band window
+ * of row t (computeBounds, NT_aligner_api.cpp:90-108) and in row 0.
+ *   pM = exp(LPM(t, n)), pE = exp(LPE(t, n))     (0 where the log is -inf)
+ *   g(t)      = pM + pE                           the posterior that sample t - 1 belongs to base n
+ *   weight[j] = sum over t = 1 .. T-1 of g(t)
+ *   sum[j]    = sum of g(t) * x[t - 1]
+ *   sumsq[j]  = sum of (g(t) * x[t - 1]) * x[t - 1]
+ * The grouping of sumsq is the reference's own (posterior * obs * obs in runTraining). Every sum is fp64, in ascending t, g formed
+ * first, one IEEE operation per step, no contraction. x is the signal the lattice was computed on: normalised, and with
+ * dyn_aligner_set_rescale the last pass's. Summed over the rows of equal k-mer the three columns are the read's share of
+ * dyn_train_out's weight / sum / sumsq. Derived values, as the CSV columns and the Python binding give them:
+ *   soft_dwell = weight;  soft_mean = sum / weight;  soft_stdv = sqrt(max(sumsq / weight - soft_mean^2, 1e-12))
+ * (the clamp is the reference's M-step clamp; with weight == 0 mean and stdv are NaN). The same bits on every run of the same
+ * batch in the same layout. Rows of failed reads are 0. */
+typedef struct dyn_soft_level_out {
+  double* weight;     /* [capacity] each, rows indexed like dyn_align_out's */
+  double* sum;
+  double* sumsq;
+  uint64_t capacity;  /* >= dyn_segment_capacity() */
+} dyn_soft_level_out;
+
 /* (ABI 10) Per-read signal rescaling of an align(calc_probabilities = 1) job whose handle had dyn_aligner_set_rescale(a, K)
  * with K > 0 when the batch was submitted. Read r is aligned K + 1 times. x0 = its preprocessed signal (what
  * dyn_batch_signals returns with the switch off); A_0 = 0.0, B_0 = 1.0; pass k = 0 .. K aligns x_k, x_0 = x0 and
@@ -520,6 +547,18 @@ int dyn_aligner_set_posterior_samples(dyn_aligner* a, int count, uint64_t seed);
  * A ticket submitted with mass > 0 takes one launch per batch (not the resident session) and merges only with tickets of the
  * same mass. Handles of mode ntk / resquiggle ignore the switch. */
 int dyn_aligner_set_border_interval(dyn_aligner* a, double mass);
+/* (added within ABI 10) align(calc_probabilities = 1) also computes the posterior-weighted per-base sums (dyn_soft_level_out) on
+ * the device behind every read's traceback, while its lattice is still in place, for every batch or ticket SUBMITTED while
+ * on != 0; 24 bytes of device memory per segment row for those batches only. Off (the default): nothing is allocated or changed,
+ * and every launch is the one it would have been. One lattice phase runs per launch for now: a job or ticket started while the
+ * switch is on is refused (DYN_ERR_INVALID_ARGUMENT + message) wherever dyn_aligner_set_border_interval is -- together with
+ * dyn_aligner_set_border_confidence(window > 0), dyn_aligner_set_posterior_samples(count > 0),
+ * dyn_aligner_set_auto_guide(half_width > 0), dyn_aligner_set_guide_rescue(half_width > 0) or a guided batch -- and together
+ * with dyn_aligner_set_border_interval(mass > 0) itself. It combines with dyn_aligner_set_rescale (the values are the last
+ * pass's, over the last pass's signal), the signal levels, the segment scores, the k-mer summary and the band margins, none of
+ * whose outputs it changes. A ticket submitted with the switch on takes one launch per batch (not the resident session) and
+ * merges only with tickets that carry it too. Handles of mode ntk / resquiggle ignore the switch. */
+int dyn_aligner_set_soft_levels(dyn_aligner* a, int on);
 /* (added within ABI 10: a caller that must know looks the symbol up) Per-k-mer level summary of a run. While it is on, every output row (segment) of every read with status 0 of an
  * align(calc_probabilities = 1) batch or ticket SUBMITTED on this handle is added, on the device behind the per-segment
  * kernels, to its k-mer's entry of an accumulator that lives on the handle: six u64 per k-mer code (48 bytes x num_kmers of
@@ -652,6 +691,21 @@ int dyn_format_csv_intervals(const dyn_aligner* a, uint64_t n_reads, const dyn_a
                              const int64_t* last_index, int threads, char* out, uint64_t out_cap, uint64_t* row_begin,
                              uint64_t* row_end);
 
+/* (added within ABI 10) The same with the soft levels of dyn_batch_fetch_soft_levels as well: after every other optional column
+ * each row gets ",{soft_dwell:.6f},{soft_mean:.6f},{soft_stdv:.6f}", derived from the three sums as dyn_soft_level_out says, the
+ * floats as Python's f"{x:.6f}" (a NaN as "nan"). ev, sc, bd, sm, bi and sl may each be NULL; sl == NULL:
+ * dyn_format_csv_intervals / dyn_format_csv_bound_intervals, byte for byte. */
+uint64_t dyn_format_csv_bound_soft(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                                   const dyn_score_out* sc, const dyn_border_out* bd, const dyn_sample_out* sm,
+                                   const dyn_border_interval_out* bi, const dyn_soft_level_out* sl, const char* const* readids,
+                                   const char* const* signalids);
+int dyn_format_csv_soft(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                        const dyn_score_out* sc, const dyn_border_out* bd, const dyn_sample_out* sm,
+                        const dyn_border_interval_out* bi, const dyn_soft_level_out* sl, const char* seqs,
+                        const uint64_t* seq_offsets, const char* const* readids, const char* const* signalids,
+                        const int64_t* sig_offsets, const int64_t* last_index, int threads, char* out, uint64_t out_cap,
+                        uint64_t* row_begin, uint64_t* row_end);
+
 /* Closes the gaps between the per-read ranges dyn_format_csv produced: all rows become one contiguous run at the
  * front of `out`, in read order; row_begin/row_end are updated. Returns the total byte count. */
 uint64_t dyn_csv_compact(char* out, uint64_t n_reads, uint64_t* row_begin, uint64_t* row_end);
@@ -711,6 +765,11 @@ int dyn_csv_sink_open_part(const char* csv_zst_path, const char* errors_path, in
  * (0x40, not 0x20: bits 0x4 and 0x20 stay unassigned, and a sink opened with either is refused as before; so is every bit
  * above 0x40.) */
 #define DYN_CSV_BORDER_INTERVAL 0x40u
+/* (added within ABI 10) DYN_CSV_SOFT_LEVELS: the header gains ",soft_dwell,soft_mean,soft_stdv" after every other optional
+ * column, every row the three fields of dyn_format_csv_soft; the sink fetches each ticket's sums after its wait, and a submit
+ * whose ticket was submitted with dyn_aligner_set_soft_levels off fails with DYN_ERR_INVALID_ARGUMENT. (0x200: bits 0x4, 0x20,
+ * 0x80 and 0x100 stay unassigned, and a sink opened with any of them is refused as before; so is every bit above 0x200.) */
+#define DYN_CSV_SOFT_LEVELS 0x200u
 int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int level, int threads, int first, int last,
                          uint32_t flags, dyn_csv_sink** out, char* err, uint64_t errcap);
 #define DYN_ZSTD_FRAME_END "\x01\x00\x00" /* an empty last block (raw, size 0): 3 bytes; the frames carry no checksum */
@@ -845,6 +904,11 @@ int dyn_batch_fetch_samples(dyn_batch* b, dyn_sample_out* out);
  * batch was submitted with dyn_aligner_set_border_interval off, or aligned with calc_probabilities = 0, or out->capacity is too
  * small. */
 int dyn_batch_fetch_intervals(dyn_batch* b, dyn_border_interval_out* out);
+/* (added within ABI 10) The posterior-weighted per-base sums of the batch's last align(calc_probabilities = 1) job (of a
+ * completed ticket, merged launch or not), copied on the handle's own non-blocking stream. DYN_ERR_INVALID_ARGUMENT (with a
+ * message) when the batch was submitted with dyn_aligner_set_soft_levels off, or aligned with calc_probabilities = 0, or
+ * out->capacity is too small. */
+int dyn_batch_fetch_soft_levels(dyn_batch* b, dyn_soft_level_out* out);
 /* (ABI 10) Copy the per-read transforms of the last dyn_batch_align (or of a completed ticket, merged launch or not) into
  * `out` (n >= the batch's read count). DYN_ERR_INVALID_ARGUMENT + message for a batch submitted with
  * dyn_aligner_set_rescale(a, 0), or aligned with calc_probabilities = 0. */
