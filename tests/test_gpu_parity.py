@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import any_band_cases as ab
 from conftest import GOLDEN, assert_matches_golden, golden, model_for
 from dynamont_amd import Aligner, synth
 from oracle.pyoracle import Oracle
@@ -925,7 +926,8 @@ def test_any_band_long_reads_equal_the_oracle_bit_for_bit(models, pore, band):
     borders, Z BITS (forward and backward are the reference's operation by operation), posteriors, the Z-only call and
     train() against the oracle at the same band -- among them reads that START with a structural tie (the polyA pad followed by
     A's), where the reference's choice rests on the last bits of its logPlus. Asynchronous tickets take the same path (no
-    resident session for them)."""
+    resident session for them). train()'s sums are held to rtol 1e-7 and, beside it, to the bar derived from the arithmetic
+    (tests/any_band_cases.py; measured: profiles/any_band/train_bar.txt)."""
     model = model_for(models, pore)
     _, mean, sd = synth.read_model_file(model)
     lengths = ((900, 2600) if "rna" in pore else (900, 1500)) if band < 4000 else (2500, 2600)   # (the oracle on the CPU is what takes the time)
@@ -941,6 +943,7 @@ def test_any_band_long_reads_equal_the_oracle_bit_for_bit(models, pore, band):
     assert t.timing()["launches"] == 1
     zonly = al.align_batch(sigs, seqs, False)
     tr = al.train_batch(sigs, seqs)
+    worst = np.zeros(3)
     for i, r in enumerate(reads):
         want = orc.align(r.signal, r.sequence, True)
         for got_res in (res, res_async):
@@ -958,6 +961,12 @@ def test_any_band_long_reads_equal_the_oracle_bit_for_bit(models, pore, band):
         codes = tr.em_code[a0:a0 + cnt]
         assert cnt > 100 and np.allclose(tr.em_weight[a0:a0 + cnt], wt["weight"][codes], rtol=1e-7, atol=1e-9)
         assert np.allclose(tr.em_sum[a0:a0 + cnt], wt["sum"][codes], rtol=1e-7, atol=1e-9)
+        # ... and, beside it, the bar derived from the arithmetic (tests/any_band_cases.py): (2 m + 12) u per k-mer, m its terms
+        assert np.array_equal(codes, np.flatnonzero(wt["weight"] > 0))
+        ratio = ab.check_derived_bar(codes, tr.em_weight[a0:a0 + cnt], tr.em_sum[a0:a0 + cnt], tr.em_sumsq[a0:a0 + cnt], wt,
+                                     orc.kmers(r.sequence), r.signal, f"{pore} band {band} read {i}")
+        worst = np.maximum(worst, ratio)
+    print(f"train, {pore}, band {band}: worst error / bar over {len(reads)} reads: weight {worst[0]:.4f} sum {worst[1]:.4f} sumsq {worst[2]:.4f}")
     t.close()
     al.close()
 
