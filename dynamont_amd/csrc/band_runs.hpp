@@ -55,4 +55,47 @@ DYN_BR_HD int run_first_row(int t, double ratio, double inv_ratio, int floor_row
   return first_row_reaching(band_mid(t, ratio), ratio, inv_ratio, floor_row, t);
 }
 
+// ---- runs of row ADDRESSES ---------------------------------------------------------------------------------------------
+// A lattice row lives in a page of 2^log_r rows (nt_kernels.hpp), so the address of row t + 1 is the address of row t plus
+// a constant for as long as the two share a page. The sweeps carry their row addresses as running values inside a run and
+// recompute them from the page table where a run starts, so a run must also end where a cursor would cross a page.
+
+// the first row of the page behind the one that holds row r
+DYN_BR_HD int next_page_row(int r, int log_r) { return ((r >> log_r) + 1) << log_r; }
+
+// Forward sweep, two cursors: the row t it writes and the row min(t + ahead, T) it fetches (ahead = 1 + the ring's depth;
+// rows past T repeat row T). One past the last row r >= t of [t, limit) such that rows t .. r share a page, rows
+// t + ahead .. r + ahead share a page or are all clamped, and t + ahead .. r + ahead lie on one side of the clamp
+// (all < T: the fetch address advances by a row per row; all >= T: it stands still).
+DYN_BR_HD int fwd_address_run_end(int t, int limit, int log_r, int ahead, int T) {
+  if (t >= limit) return limit;
+  int end = next_page_row(t, log_r);
+  const int d = t + ahead;
+  if (d < T) {
+    const int page_end = next_page_row(d, log_r) - ahead;  // > t
+    const int clamp = T - ahead;                           // > t: the first row whose fetch is row T
+    if (page_end < end) end = page_end;
+    if (clamp < end) end = clamp;
+  }
+  return end < limit ? end : limit;
+}
+
+// the fetch address of the forward sweep advances inside a run that starts at row t (else every row of it fetches row T)
+DYN_BR_HD bool fwd_fetch_advances(int t, int ahead, int T) { return t + ahead < T; }
+
+// Forward sweep: the end of the run that starts at row t -- where the band window moves (next_move_row looks at the rows
+// t + 1 .. : the window of row r + 1 differs from that of row r) or an address run ends, whichever comes first.
+DYN_BR_HD int fwd_run_end(int t, double ratio, double inv_ratio, int limit, int log_r, int ahead, int T) {
+  const int move = next_move_row(t + 1, ratio, inv_ratio, limit);
+  const int addr = fwd_address_run_end(t, limit, log_r, ahead, T);
+  return move < addr ? move : addr;
+}
+
+// Backward sweep (top-down, one cursor: the row t it writes). The lowest row q in [floor_row, t] with band_mid(q) ==
+// band_mid(t) that shares row t's page.
+DYN_BR_HD int bwd_run_first(int t, double ratio, double inv_ratio, int floor_row, int log_r) {
+  const int page_first = (t >> log_r) << log_r;
+  return run_first_row(t, ratio, inv_ratio, page_first > floor_row ? page_first : floor_row);
+}
+
 }  // namespace dynband

@@ -5,6 +5,7 @@
 #include "engine.hpp"
 
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -23,6 +24,17 @@
   } while (0)
 
 namespace dyneng {
+
+// Lattice pages hold 2^log_r rows, log_r >= 8 (and more where the longest read would not fit a wave's page table).
+// DYN_PAGE_LOG_ROWS=2..8 lowers that floor (read at every launch; tests: the sweeps' row cursors then cross a page every few
+// rows instead of every 256).
+inline int min_page_log_rows() {
+  if (const char* s = std::getenv("DYN_PAGE_LOG_ROWS")) {
+    const long v = std::strtol(s, nullptr, 10);
+    if (v >= 2 && v <= 8) return (int)v;
+  }
+  return 8;
+}
 
 // bytes of lattice pools that destroyed handles have parked on `device` (they are this process's to use)
 size_t parked_bytes(int device);

@@ -317,7 +317,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   // rows per page: the longest read must fit the waves' PT_MAX-entry page tables
   uint32_t max_T = 0;
   for (uint32_t i : order) max_T = std::max<uint32_t>(max_T, (uint32_t)(b->reads[i].S + 1));
-  int log_r = 8;
+  int log_r = dyneng::min_page_log_rows();
   while (((uint64_t)max_T + 1 + ((1ull << log_r) - 1)) >> log_r > (uint64_t)dynk::PT_MAX) ++log_r;
   const uint64_t page_rows = 1ull << log_r;
   auto pages_of = [&](uint64_t S) { return (uint32_t)((S + 2 + page_rows - 1) >> log_r); };  // rows 0 .. T = S+1

@@ -13,7 +13,8 @@
 //   * a lane GROUP (LPE_GROUP = 16 lanes) is live when any of its lanes is, and all lanes of a live group store: the three
 //     8-byte stores of a row then cover whole 128-byte runs and the 4-byte store a whole 64-byte one, never part of a sector
 //     (8-lane groups would halve the 4-byte store's run; tools/ubench/stream_pattern.hip measures both patterns);
-//   * the group mask is word CPL of the row's record (ROW_WORDS, nt_kernels.hpp), beside the CPL decision ballots.
+//   * every lane keeps its group's verdict as bit 7 of its byte of the row's record, above its CPL decision bits
+//     (decision_record.hpp, which also holds the readers' lpe_slot_stored).
 //
 // tests/device_math/lpe_liveness.hip runs both functions on crafted rows against a host restatement.
 #pragma once
@@ -21,6 +22,8 @@
 #include <cstdint>
 
 #include <hip/hip_runtime.h>
+
+#include "decision_record.hpp"
 
 namespace dynk {
 
@@ -41,20 +44,22 @@ __device__ __forceinline__ bool lpe_lane_live(const float (&f)[7], float floor) 
   return !(m < floor);
 }
 
-// The lanes of the groups that hold a live lane, as a wave-uniform mask. OR over each row of 16 lanes as a butterfly of four
+// Whether this lane's group holds a live lane, as 0 / 1 in every lane. OR over each row of 16 lanes as a butterfly of four
 // DPP steps (mirror the row, mirror its halves, swap neighbours, swap pairs): every lane of a row ends with the OR of all
-// sixteen, so the ballot IS the group mask and no scalar bit arithmetic follows.
-__device__ __forceinline__ uint64_t lpe_store_mask(bool lane_live) {
+// sixteen. It is bit 7 of the lane's byte of the row's record, and the seed of that byte's accumulator (decision_record.hpp).
+__device__ __forceinline__ uint32_t lpe_store_flag(bool lane_live) {
   static_assert(LPE_GROUP == 16, "one DPP row");
   uint32_t x = lane_live ? 1u : 0u;
   x |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x140, 0xf, 0xf, true);  // row_mirror:           i <-> 15 - i
   x |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x141, 0xf, 0xf, true);  // row_half_mirror:      i <-> 7 - i in each half
   x |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]:  i <-> i ^ 1
   x |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xf, 0xf, true);   // quad_perm [2,3,0,1]:  i <-> i ^ 2
-  return __ballot(x != 0);
+  return x;
 }
 
-// the lane of a row that holds band slot s (blocked layout: lane l owns slots l * 7 .. l * 7 + 6)
-__host__ __device__ inline bool lpe_slot_stored(uint64_t group_mask, int slot) { return (group_mask >> (slot / 7)) & 1ull; }
+// The lanes of the groups that hold a live lane, as a wave-uniform mask: the ballot of the flag IS the group mask (the exec
+// mask of the row's LPE stores) and no scalar bit arithmetic follows.
+__device__ __forceinline__ uint64_t lpe_store_mask(uint32_t flag) { return __ballot(flag != 0); }
+__device__ __forceinline__ uint64_t lpe_store_mask(bool lane_live) { return lpe_store_mask(lpe_store_flag(lane_live)); }
 
 }  // namespace dynk

@@ -86,7 +86,7 @@ using dynmath::SP_NODES;
 namespace {
 
 typedef __attribute__((address_space(3))) uint32_t lds_u32_t;
-typedef __attribute__((address_space(3))) uint64_t lds_u64_t;
+typedef __attribute__((address_space(3))) uint8_t lds_u8_t;
 
 __device__ __forceinline__ int pmod(int a) {
   int r = a % P;
@@ -119,45 +119,6 @@ __device__ __forceinline__ void store_row_f64(double* __restrict__ row, int lane
   if (NT) __builtin_nontemporal_store(x[6], row + 384 + lane);
   else row[384 + lane] = x[6];
 }
-
-// ---- out-of-band lanes (experiment DYN_SKIP_OOB) -------------------------------------------------
-// A row holds P = 448 slots for the 2 bw + 1 <= 401 cells of the band: the other >= 47 slots -- 6.7 lanes of the blocked
-// layout, more than half the wave for reads shorter than the band is wide -- carry "no k-mer" cells whose values nobody
-// needs. The lanes that hold NOTHING of a window of the slot ring skip their row stores and their part of the ring DMA.
-// lanes_of_window: the lanes that hold at least one slot of the lattice columns [c0, c0 + len).
-__device__ __forceinline__ uint64_t lanes_of_window(int c0, int len) {
-  const int s0 = pmod(c0);
-  const int l0 = s0 / CPL;
-  const int n = (s0 + len - 1) / CPL - l0 + 1;   // lanes touched (slots s and s - P share a lane: P = 64 CPL)
-  if (n >= 64) return ~0ull;
-  const uint64_t m = (1ull << n) - 1ull;
-  return l0 ? ((m << l0) | (m >> (64 - l0))) : m;
-}
-// a wave-uniform 64-bit value the compiler holds in vector registers (everything derived from band_mid is): into scalar ones
-__device__ __forceinline__ uint64_t uniform_u64(uint64_t v) {
-  const uint32_t lo32 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-  const uint32_t hi32 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
-  return ((uint64_t)hi32 << 32) | lo32;
-}
-// the half-wave instruction of a row (register 6 of lanes 2l, 2l + 1 comes from lane l < 32): lane l takes part when either does
-__device__ __forceinline__ uint64_t half_mask_of(uint64_t live) {
-  uint64_t x = (live | (live >> 1)) & 0x5555555555555555ull;
-  x = (x | (x >> 1)) & 0x3333333333333333ull;
-  x = (x | (x >> 2)) & 0x0f0f0f0f0f0f0f0full;
-  x = (x | (x >> 4)) & 0x00ff00ff00ff00ffull;
-  x = (x | (x >> 8)) & 0x0000ffff0000ffffull;
-  x = (x | (x >> 16)) & 0x00000000ffffffffull;
-  return x;
-}
-#ifdef DYN_SKIP_OOB
-constexpr bool SKIP_OOB = true;
-#else
-constexpr bool SKIP_OOB = false;
-#endif
-// Rows are fetched RING_D + 1 rows ahead of the row that decides the forward sweep's mask, and the band moves at most one
-// column per row: the backward sweep stores the lanes of the band widened by OOB_SLACK columns on either side, the forward
-// sweep fetches those of [lo, lo + W + OOB_SLACK) -- always inside what was stored, always containing the fetched row's band.
-constexpr int OOB_SLACK = 5;
 
 // size_t(t * RATIO): one IEEE fp64 multiply, then truncation (NT_aligner_api.cpp:100); band_runs.hpp
 using dynband::band_mid;
@@ -293,21 +254,6 @@ __device__ __forceinline__ void ring_dma_row(const double* row_lane_ptr, unsigne
       : "memory");
 }
 
-// the same for the lanes of `live` only (`half` = half_mask_of(live)); the others' ring slots keep what they held
-__device__ __forceinline__ void ring_dma_row_masked(const double* row_lane_ptr, unsigned lds_slot_addr, uint64_t live, uint64_t half) {
-  asm volatile(
-      "s_mov_b32 m0, %1\n\t"
-      "s_mov_b64 exec, %2\n\t"
-      "global_load_lds_dwordx4 %0, off" DYN_DMA_MOD "\n\t"
-      "global_load_lds_dwordx4 %0, off offset:1024" DYN_DMA_MOD "\n\t"
-      "global_load_lds_dwordx4 %0, off offset:2048" DYN_DMA_MOD "\n\t"
-      "s_mov_b64 exec, %3\n\t"
-      "global_load_lds_dwordx4 %0, off offset:3072" DYN_DMA_MOD "\n\t"
-      "s_mov_b64 exec, -1\n\t"
-      ::"v"(row_lane_ptr), "s"(__builtin_amdgcn_readfirstlane(lds_slot_addr)), "s"(live), "s"(half)
-      : "memory");
-}
-
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -363,9 +309,9 @@ __device__ __forceinline__ double backward_sweep(const ReadDesc& rd, const WaveC
   bool bad_sample = false;
   int lo = band_mid(T - 1, ratio) - bw;
   const double inv_ratio = 1.0 / ratio;  // seeds the run-length prediction only (band_runs.hpp)
-  // DYN_SKIP_OOB: the lanes whose row stores count (align jobs: the forward sweep fetches exactly these or fewer)
-  constexpr bool MASKED = SKIP_OOB && STORE && ARITH != ARITH_FOLDED;
-  uint64_t store_mask = MASKED ? uniform_u64(lanes_of_window(lo - OOB_SLACK, W + 2 * OOB_SLACK)) : ~0ull;
+  // The address of the row about to be stored, carried from row to row inside a run: a run never crosses a page
+  // (band_runs.hpp, bwd_run_first), so the row below lies P slots below, and the page table is consulted once per run.
+  double* __restrict__ row_out = out;
   const int n_init = lo + bw;  // band column bw+1 of row T-1 (NT_aligner_api.cpp:170)
   int n[CPL];
   double bE[CPL], bM[CPL], bE2[CPL], bM2[CPL], e[CPL];
@@ -437,10 +383,9 @@ __device__ __forceinline__ double backward_sweep(const ReadDesc& rd, const WaveC
         }
       }
       lo = new_lo;
-      if constexpr (MASKED) store_mask = uniform_u64(lanes_of_window(lo - OOB_SLACK, W + 2 * OOB_SLACK));
     };
     auto row = [&](int t, const double (&bE_in)[CPL], const double (&bM_in)[CPL], double (&bE_out)[CPL], double (&bM_out)[CPL]) {
-      const int i = t - base;
+      const int i = t - base;  // (t serves the sample lookup only: the row's address runs)
       // e[] = e(t+1, n) was computed during the previous row's table lookups (software pipeline)
       double Y[CPL], Yr[CPL], x1[CPL], x2[CPL];
 #pragma unroll
@@ -466,7 +411,6 @@ __device__ __forceinline__ double backward_sweep(const ReadDesc& rd, const WaveC
       if constexpr (ARITH == ARITH_FOLDED) dynmath::log_plus_finish3<CPL>(L, bE_out);  // train(): no decision hangs on it
       else if constexpr (ARITH == ARITH_STRICT) log_plus_finish_certified(L, bE_out, strict_tab(s_tab), nfb);
       else log_plus_finish<CPL>(L, bE_out);
-      const size_t rt = STORE ? (size_t)cur.at(w, t) * P : 0;
       // streamed once, read back by the forward sweep ~100 MB later: non-temporal (-2 %)
       if constexpr (STORE && ARITH == ARITH_FOLDED) {
         // train(): what its forward sweep (the posterior chain) needs of row t is ln P(stay | E(t,n)) = the stay operand
@@ -475,17 +419,14 @@ __device__ __forceinline__ double backward_sweep(const ReadDesc& rd, const WaveC
         double ls[CPL];
 #pragma unroll
         for (int j = 0; j < CPL; ++j) ls[j] = x2[j] - bE_out[j];
-        store_row_f64<true>(out + rt, lane, ls);
+        store_row_f64<true>(row_out, lane, ls);
       } else if (STORE) {
-        if constexpr (MASKED) {
-          if (__builtin_amdgcn_inverse_ballot_w64(store_mask)) store_row_f64<true>(out + rt, lane, bE_out);
-        } else {
-          store_row_f64<true>(out + rt, lane, bE_out);
-        }
+        store_row_f64<true>(row_out, lane, bE_out);
       }
+      if (STORE) row_out -= P;
     };
-    // The block's rows in RUNS, top-down: maximal spans of rows t with band_mid(t) - bw == lo, the hand-over in front of a
-    // run's first row and no window test inside a run (see forward_sweep).
+    // The block's rows in RUNS, top-down: maximal spans of rows t of one page with band_mid(t) - bw == lo, the hand-over and
+    // the page lookup in front of a run's first row and neither a window nor a page test inside a run (see forward_sweep).
     int t = thi;
     const int tlo = base + ilo;  // the block's lowest row
 #pragma unroll 1
@@ -493,7 +434,8 @@ __device__ __forceinline__ double backward_sweep(const ReadDesc& rd, const WaveC
       const int new_lo = band_mid(t, ratio) - bw;
       if (new_lo != lo) hand_over(new_lo);
       // the run's lowest row (band_runs.hpp: predicted with one multiply, confirmed with band_mid itself)
-      const int tq = __builtin_amdgcn_readfirstlane(dynband::run_first_row(t, ratio, inv_ratio, tlo));
+      const int tq = __builtin_amdgcn_readfirstlane(dynband::bwd_run_first(t, ratio, inv_ratio, tlo, STORE ? w.log_r : 30));
+      if (STORE) row_out = out + (size_t)cur.at(w, t) * P;
 #pragma unroll 1
       for (; t - 1 >= tq; t -= 2) {
         row(t, bE, bM, bE2, bM2);
@@ -548,7 +490,7 @@ template <bool POST, bool INPLACE, bool STRICT>
 __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCtx& w,
                                                 const double* __restrict__ sig, const Emis* __restrict__ par,
                                                 const double* __restrict__ ws_rd, float* __restrict__ lp_out,
-                                                uint64_t* __restrict__ bits, double Z, double m1, double e2,
+                                                uint8_t* __restrict__ rec, double Z, double m1, double e2,
                                                 const SoftplusNode* s_tab, unsigned ring_base, float lpe_floor,
                                                 int strict_rows = 0, uint32_t* fallbacks = nullptr) {
   // lpe_floor (wave-uniform; separate layout only): the float LPE of a 16-lane group is stored only in rows where one of its
@@ -576,7 +518,6 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
   // the load pointer hipcc orders every prefetch behind the previous row's stores (s_waitcnt vmcnt(0)
   // at the top of each row = 43 % of the wave's lifetime spent waiting).
   const double* __restrict__ lat = ws_rd;
-  float* __restrict__ lat_lp = lp_out;
   RowCursor cur_dma, cur_out;
 
   // Band edges without per-row masks. Lower edge: the slot of a column that leaves the band is
@@ -586,27 +527,16 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
   // no select in the row loop. Both hand-overs happen in the rare block that looks one row ahead.
   int lo = band_mid(1, ratio) - bw;  // band of row 1 (column 0 of row 0 is inside: band_mid(1) <= 1 <= bw)
   const double inv_ratio = 1.0 / ratio;  // seeds the run-length prediction only (band_runs.hpp)
-  // DYN_SKIP_OOB: lanes whose part of a row is fetched (rows up to RING_D + 1 ahead) / whose posteriors of a row are stored
-  // (the row's band, whichever side of the hand-over `lo` is on when the stores are issued)
-  constexpr bool MASKED = SKIP_OOB && POST;
-  uint64_t dma_mask = ~0ull, dma_half = 0xffffffffull, out_mask = ~0ull;
-  auto set_masks = [&]() {
-    if constexpr (MASKED) {
-      dma_mask = uniform_u64(lanes_of_window(lo, W + OOB_SLACK));
-      dma_half = half_mask_of(dma_mask);
-      out_mask = uniform_u64(lanes_of_window(lo - 1, W + 1));
-    }
-  };
-  set_masks();
-  if constexpr (MASKED) {
-    // lanes that fetch nothing of a row read what their ring slots held before: that must be a harmless number (-inf here;
-    // later, values of rows they did fetch), never the ballot words the previous read's traceback staged in this ring
-    // (a NaN pattern in a slot outside the band would travel into its in-band neighbour through the Viterbi values)
-    auto* ringp = (__attribute__((address_space(3))) double*)(size_t)ring_base;
-#pragma unroll
-    for (int k = 0; k < RING_D * P / 64; ++k) ringp[k * 64 + lane] = NEG_INF;
-    wave_lds_sync_local();
-  }
+  // Row addresses that RUN (separate from the arithmetic: all wave-uniform but the fetch pointer, which carries the lane's
+  // 16 bytes). A run of rows never crosses a page of either cursor -- the row t being written, the row min(t + 1 + RING_D, T)
+  // being fetched -- nor the clamp (band_runs.hpp, fwd_run_end): inside it the next row's addresses are this row's plus a
+  // constant, and the page table, the modulo of the ring slot and the multiply by the row size are paid once per run.
+  constexpr int AHEAD = 1 + RING_D;
+  unsigned ring_off = (2 % RING_D) * ROW_BYTES;  // ring slot of row t + 1 (row r lives in slot r % RING_D): a counter that wraps
+  const double* __restrict__ dma_row = ws_rd;    // this lane's part of the row about to be fetched
+  int dma_step = 0;                              // slots the fetch advances per row: P, or 0 once it repeats row T
+  float* __restrict__ lp_row = lp_out;           // row t of the posteriors
+  uint8_t* __restrict__ rec_row = rec;           // row t's record (decision_record.hpp)
   int n[CPL];
   // The loop-carried values of a row. The row loop is unrolled by two and ping-pongs between two of these:
   // with one set, "new" values are computed while the "old" ones are still live and hipcc closes every
@@ -665,8 +595,7 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
   const double* __restrict__ dma_src = ws_rd + lane * 2;
   if (POST) {  // rows past T repeat the all -inf row T (backward sweep): RING_D rows are always in flight
     for (int r = 2; r <= RING_D + 1; ++r) {
-      if constexpr (MASKED) ring_dma_row_masked(dma_src + (size_t)cur_dma.at(w, min(r, T)) * P, ring_base + (r % RING_D) * ROW_BYTES, dma_mask, dma_half);
-      else ring_dma_row(dma_src + (size_t)cur_dma.at(w, min(r, T)) * P, ring_base + (r % RING_D) * ROW_BYTES);
+      ring_dma_row(dma_src + (size_t)cur_dma.at(w, min(r, T)) * P, ring_base + (r % RING_D) * ROW_BYTES);
     }
   }
 
@@ -687,7 +616,6 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
       if (n[j] == lo + W) set_p(j, entering, strict_tag);  // first band row of this column is t+1
     }
     lo = next_lo;
-    set_masks();
   };
 
   // one lattice row: reads the state `in` (row t-1), writes `out` (row t)
@@ -700,11 +628,11 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
       // -inf row T, so that the same number of memory operations is in flight in every row and
       // one hand-counted s_waitcnt serves the whole loop, tail included)
       wait_vmcnt<RING_WAIT>();
-      ring_read_row(ring_base + ((t + 1) % RING_D) * ROW_BYTES, lane, out.b);
-      if constexpr (MASKED)
-        ring_dma_row_masked(dma_src + (size_t)cur_dma.at(w, min(t + 1 + RING_D, T)) * P, ring_base + ((t + 1) % RING_D) * ROW_BYTES, dma_mask, dma_half);
-      else
-        ring_dma_row(dma_src + (size_t)cur_dma.at(w, min(t + 1 + RING_D, T)) * P, ring_base + ((t + 1) % RING_D) * ROW_BYTES);
+      const unsigned slot_addr = ring_base + ring_off;
+      ring_read_row(slot_addr, lane, out.b);
+      ring_dma_row(dma_row, slot_addr);
+      dma_row += dma_step;
+      ring_off = ring_off == (RING_D - 1) * ROW_BYTES ? 0u : ring_off + ROW_BYTES;
     }
     from_left(in.fE, fEl);
     if (POST) from_left(in.vE, vEl);
@@ -729,22 +657,23 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
     }
     if (POST) {
       double LPM[CPL], LPE[CPL], alt[CPL];
-      uint64_t bj[CPL];
 #pragma unroll
       for (int j = 0; j < CPL; ++j) LPM[j] = (out.fM[j] + (out.b[j] + out.e[j])) - Z;  // bM(t,n) = bE(t+1,n) + e(t+1,n)
 #pragma unroll
       for (int j = 0; j < CPL; ++j) LPE[j] = (out.fE[j] + in.b[j]) - Z;
-      // The row's record has one more word, kept by lane CPL: the lanes whose float LPE this row stores (separate layout:
-      // the groups that hold a cell a reader can tell from -inf, whole groups so that no store covers part of a sector;
-      // in-place layout: every lane, and its traceback does not look). A ballot like the others: same asm block below.
+      // The row's record is one byte per lane (decision_record.hpp): bit 7 says that this lane's float LPE cells are stored in
+      // this row (separate layout: the groups that hold a cell a reader can tell from -inf, whole groups so that no store
+      // covers part of a sector; in-place layout: every lane, and its traceback does not look), bits 0 .. CPL-1 are the
+      // decisions of its cells. The flag seeds the byte's accumulator; its ballot is the exec mask of the LPE stores.
       // Taken here, ahead of the Viterbi arithmetic: its dependent chain of lane exchanges then has fp64 work to hide behind.
       float f[CPL];
       uint64_t stored = ~0ull;
+      uint32_t acc = 1u;
       if constexpr (!INPLACE) {
 #pragma unroll
         for (int j = 0; j < CPL; ++j) f[j] = (float)LPE[j];
-        stored = lpe_store_mask(lpe_lane_live(f, lpe_floor));
-        if constexpr (MASKED) stored &= out_mask;
+        acc = lpe_store_flag(lpe_lane_live(f, lpe_floor));
+        stored = lpe_store_mask(acc);
       }
 #pragma unroll
       for (int j = 0; j < CPL; ++j) out.vM[j] = vEl[j] + LPM[j];
@@ -752,32 +681,24 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
       for (int j = 0; j < CPL; ++j) out.vE[j] = max_f64(in.vM[j], in.vE[j]) + LPE[j];
 #pragma unroll
       for (int j = 0; j < CPL; ++j) alt[j] = in.vM[j] + LPE[j];
+      // one compare and one add-with-carry per cell, in the lane's own register: acc = 2 acc + decision, highest cell first,
+      // so that cell j ends in bit j and the flag in bit 7. No ballot leaves its lane (the layout [word j][bit = lane] cost
+      // sixteen v_writelane behind an s_nop per row).
+      // Written out: from `(acc + acc) + (a == b)` hipcc makes a select per cell and a shift and a three-way OR per two
+      // cells (20 instructions per row instead of 14). The carry-in of v_addc is an ordinary VALU operand: the hardware
+      // interlocks it against the v_cmp in front of it, as in every 64-bit add the compiler emits (v_add_co, v_addc_co back
+      // to back) -- the read-after-VALU-write hazards that need wait states are those of v_readlane / v_writelane lane
+      // selects, v_div_fmas and memory instructions reading an SGPR, and none of them is here. Not volatile, one block per
+      // cell: the scheduler places them between the fp64 work like any other instruction.
 #pragma unroll
-      for (int j = 0; j < CPL; ++j) bj[j] = __ballot(out.vE[j] == alt[j]);
-      // lane j keeps ballot j: two v_writelane per word (a select chain costs twice as much). All 14
-      // sit in ONE asm block behind an s_nop: the ballots are SGPR pairs written by v_cmp (VALU), and
-      // a v_writelane that reads such an SGPR too soon after the v_cmp picks up stale data -- the
-      // compiler's hazard recogniser does not look inside inline asm (observed: a build that happened
-      // to schedule v_cmp two instructions ahead of the v_writelane produced garbage decision bits).
-      unsigned wlo, whi;
-      static_assert(CPL == 7, "one v_writelane pair per cell register");
-#define DYN_WL(J, LO, HI) "v_writelane_b32 %0, %" #LO ", " #J "\n\tv_writelane_b32 %1, %" #HI ", " #J "\n\t"
-      asm("s_nop 4\n\t"
-          DYN_WL(0, 2, 3) DYN_WL(1, 4, 5) DYN_WL(2, 6, 7) DYN_WL(3, 8, 9) DYN_WL(4, 10, 11) DYN_WL(5, 12, 13) DYN_WL(6, 14, 15) DYN_WL(7, 16, 17)
-          : "=&v"(wlo), "=&v"(whi)
-          : "s"((unsigned)bj[0]), "s"((unsigned)(bj[0] >> 32)), "s"((unsigned)bj[1]), "s"((unsigned)(bj[1] >> 32)),
-            "s"((unsigned)bj[2]), "s"((unsigned)(bj[2] >> 32)), "s"((unsigned)bj[3]), "s"((unsigned)(bj[3] >> 32)),
-            "s"((unsigned)bj[4]), "s"((unsigned)(bj[4] >> 32)), "s"((unsigned)bj[5]), "s"((unsigned)(bj[5] >> 32)),
-            "s"((unsigned)bj[6]), "s"((unsigned)(bj[6] >> 32)), "s"((unsigned)stored), "s"((unsigned)(stored >> 32)));
-#undef DYN_WL
-      const uint64_t mybits = ((uint64_t)whi << 32) | wlo;
-      const uint32_t prow = cur_out.at(w, t);
-      const size_t rt = (size_t)prow * P;
+      for (int j = CPL - 1; j >= 0; --j)
+        asm("v_cmp_eq_f64 vcc, %1, %2\n\t"
+            "v_addc_co_u32 %0, vcc, %3, %3, vcc"
+            : "=v"(acc)
+            : "v"(out.vE[j]), "v"(alt[j]), "v"(acc)
+            : "vcc");
       // read again only by the traceback, one cell per row: non-temporal; same pairing as the bE rows
-      const bool out_live = (MASKED && INPLACE) ? __builtin_amdgcn_inverse_ballot_w64(out_mask) : true;
-      if (!out_live) {
-        // (DYN_SKIP_OOB: nothing of this lane lies in the row's band)
-      } else if (INPLACE) {
+      if constexpr (INPLACE) {
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
           dyn_f4 v4;
@@ -785,25 +706,21 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
           v4.y = (float)LPE[2 * q];
           v4.z = (float)LPM[2 * q + 1];
           v4.w = (float)LPE[2 * q + 1];
-          __builtin_nontemporal_store(v4, reinterpret_cast<dyn_f4*>(&lat_lp[2 * (rt + q * 128 + lane * 2)]));
+          __builtin_nontemporal_store(v4, reinterpret_cast<dyn_f4*>(&lp_row[2 * (q * 128 + lane * 2)]));
         }
         dyn_f2 v2;
         v2.x = (float)LPM[6];
         v2.y = (float)LPE[6];
-        __builtin_nontemporal_store(v2, reinterpret_cast<dyn_f2*>(&lat_lp[2 * (rt + 384 + lane)]));
-      }
-      if constexpr (INPLACE) {
-        if (lane < ROW_WORDS) bits[(size_t)prow * ROW_WORDS + lane] = mybits;
+        __builtin_nontemporal_store(v2, reinterpret_cast<dyn_f2*>(&lp_row[2 * (384 + lane)]));
+        lp_row += 2 * P;
       } else {
-        // The four LPE stores under exec = stored, the record under exec = lanes 0 .. ROW_WORDS-1, then every lane again
-        // (all 64 are active here, as ring_dma_row assumes): three scalar moves. Written as two divergent branches the
-        // same stores cost a save, a branch and a restore of exec each -- and a wave pays for every instruction.
+        // The four LPE stores under exec = stored, then every lane again (all 64 are active here, as ring_dma_row assumes):
+        // two scalar moves. Written as a divergent branch the same stores cost a save, a branch and a restore of exec -- and
+        // a wave pays for every instruction.
         // Same addresses as store_row_f64's: (f0,f1) (f2,f3) (f4,f5) at 8 bytes per lane in runs of 512, f6 at 4 behind them.
-        static_assert(ROW_WORDS == 8 && CPL == 7, "exec = 0xff; three pairs and a single");
+        static_assert(CPL == 7, "three pairs and a single");
         dyn_f2 p0, p1, p2;
         p0.x = f[0], p0.y = f[1], p1.x = f[2], p1.y = f[3], p2.x = f[4], p2.y = f[5];
-        float* const lp_row = lat_lp + rt;
-        uint64_t* const rec_row = bits + (size_t)prow * ROW_WORDS;
         const int off8 = lane * 8, off4 = lane * 4;
         const float f6 = f[6];
         asm volatile(
@@ -812,12 +729,15 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
             "global_store_dwordx2 %1, %4, %7 offset:512 nt\n\t"
             "global_store_dwordx2 %1, %5, %7 offset:1024 nt\n\t"
             "global_store_dword %2, %6, %7 offset:1536 nt\n\t"
-            "s_mov_b64 exec, 0xff\n\t"
-            "global_store_dwordx2 %1, %8, %9\n\t"
             "s_mov_b64 exec, -1\n\t"
-            :: "s"(stored), "v"(off8), "v"(off4), "v"(p0), "v"(p1), "v"(p2), "v"(f6), "s"(lp_row), "v"(mybits), "s"(rec_row)
+            :: "s"(stored), "v"(off8), "v"(off4), "v"(p0), "v"(p1), "v"(p2), "v"(f6), "s"(lp_row)
             : "memory");
+        lp_row += P;
       }
+      // the record: 64 contiguous bytes, one per lane, every lane active
+      static_assert(dynrec::REC_BYTES == ROW_WORDS * 8 && dynrec::REC_CPL == CPL, "a row's record fills its place in the pool");
+      rec_row[lane] = (uint8_t)acc;
+      rec_row += dynrec::REC_BYTES;
     }
   };
 
@@ -830,16 +750,27 @@ __device__ __forceinline__ double forward_sweep(const ReadDesc& rd, const WaveCt
     // DMA ring in every row (+7 % on the sweep). A use here pins the wait to once per 64 rows.
     asm volatile("" ::"v"(xs));
     const int tend = tb + min(64, T - tb);  // one past the block's last row
-    // The block's rows in RUNS: maximal spans of rows t with band_mid(t + 1) - bw == lo. The hand-over sits in front of a
-    // run's first row and the rows of a run are instantiated without a window test: with the test inside the pair loop
-    // hipcc copied all 21 emission parameters on its fall-through, in every row (21 of a row's 24 v_mov_b64).
+    // The block's rows in RUNS: maximal spans of rows t with band_mid(t + 1) - bw == lo whose two row cursors stay in their
+    // pages. The hand-over sits in front of a run's first row and the rows of a run are instantiated without a window test:
+    // with the test inside the pair loop hipcc copied all 21 emission parameters on its fall-through, in every row (21 of a
+    // row's 24 v_mov_b64). The row addresses are looked up here, once per run, and run from there (see ring_off above).
     int t = tb;
 #pragma unroll 1
     while (t < tend) {
       const int next_lo = band_mid(t + 1, ratio) - bw;
       if (next_lo != lo) hand_over(strict_tag, next_lo);
       // the next run's first row (band_runs.hpp: predicted with one multiply, confirmed with band_mid itself)
-      const int te = __builtin_amdgcn_readfirstlane(dynband::next_move_row(t + 1, ratio, inv_ratio, tend));
+      int te;
+      if constexpr (POST) {
+        te = __builtin_amdgcn_readfirstlane(dynband::fwd_run_end(t, ratio, inv_ratio, tend, w.log_r, AHEAD, T));
+        const uint32_t prow = cur_out.at(w, t);
+        lp_row = lp_out + (size_t)prow * (INPLACE ? 2 * P : P);
+        rec_row = rec + (size_t)prow * dynrec::REC_BYTES;
+        dma_row = dma_src + (size_t)cur_dma.at(w, min(t + AHEAD, T)) * P;
+        dma_step = dynband::fwd_fetch_advances(t, AHEAD, T) ? P : 0;
+      } else {
+        te = __builtin_amdgcn_readfirstlane(dynband::next_move_row(t + 1, ratio, inv_ratio, tend));
+      }
 #pragma unroll 1
       for (; t + 1 < te; t += 2) {
         row(strict_tag, t, readlane_f64(xs, t - tb), sa, sb);
@@ -887,12 +818,17 @@ __device__ __forceinline__ bool z_ok(const ReadDesc& rd, double Zf, double Zb) {
 // decision bits. Each lattice row 1..T-1 holds exactly one path cell, so the walk is recorded
 // as pathn[row] (column, bit31 = state M) and pp[row] = exp(LP of that cell); a segment is the
 // run of rows that share a column, its M cell is the lowest row (segrow).
-// 64 rows of bits are staged in LDS per step so the serial walk pays LDS, not HBM, latency.
+// The records of 64 rows are staged in LDS per step so the serial walk pays LDS, not HBM, latency.
 // Returns true when the walk ended in (0, 0).
 // ---------------------------------------------------------------------------------------------
+// A staged row's record (decision_record.hpp: 64 bytes, byte = lane of the sweep) starts every TB_STAGE_STRIDE bytes: in a
+// step of the walk lane i reads ONE byte of row i, the same byte index in all 64, and 17 dwords from row to row put the 32
+// lanes of a half-wave on 32 different banks (a stride of 64 bytes would put them on two).
+constexpr int TB_STAGE_STRIDE = dynrec::REC_BYTES + 4;
+static_assert(64 * TB_STAGE_STRIDE <= RING_D * ROW_BYTES, "the staged block fits the wave's idle ring");
 __device__ __forceinline__ bool traceback(const ReadDesc& rd, const WaveCtx& w, const float* __restrict__ lp,
-                                          const uint64_t* __restrict__ bits, TraceBuffers tb, bool inplace,
-                                          lds_u64_t* sb) {
+                                          const uint8_t* __restrict__ rec, TraceBuffers tb, bool inplace,
+                                          lds_u8_t* sb) {
   const int lane = w.lane;
   const int T = (int)rd.T, N = (int)rd.N;
   // separate layout: float LPE rows [.][P]; in-place layout: (float LPM, float LPE) in the 8-byte bE slots
@@ -908,26 +844,28 @@ __device__ __forceinline__ bool traceback(const ReadDesc& rd, const WaveCtx& w, 
   int t = T - 1, n = N - 1;
   int slot = n % P;
   int stM = 0;  // the cell at row t is an M cell (carried across blocks)
-#ifndef DYN_EXP_TB_SERIAL
   // The blocks follow each other at a fixed stride (a block is left at its lowest row, whatever the path does inside), so
   // the next block's decision bits are fetched while this one is walked, and a block's path posteriors -- one dependent
   // load per row -- are finished one block later: the walk pays neither HBM latency.
-  uint64_t nb[CPL];          // the bits of the block about to be walked (row base + lane)
-  uint64_t nstored = 0;      // ... and the lanes of that row whose float LPE the forward sweep stored
+  constexpr int REC_DWORDS = dynrec::REC_BYTES / 4;
+  uint32_t nb[REC_DWORDS];   // the record of this lane's row (base + lane) of the block about to be walked
   uint32_t nprow = 0;
   auto fetch = [&](int base_) {
     const int row_ = base_ + lane;
     nprow = 0;
 #pragma unroll
-    for (int j = 0; j < CPL; ++j) nb[j] = 0;
-    nstored = 0;
+    for (int k = 0; k < REC_DWORDS; ++k) nb[k] = 0;
     if (row_ >= 1) {
       nprow = pool_row(w, row_);
+      const uint4* __restrict__ r4 = reinterpret_cast<const uint4*>(rec + (size_t)nprow * dynrec::REC_BYTES);
 #pragma unroll
-      for (int j = 0; j < CPL; ++j) nb[j] = bits[(size_t)nprow * ROW_WORDS + j];
-      nstored = bits[(size_t)nprow * ROW_WORDS + CPL];
+      for (int k = 0; k < REC_DWORDS / 4; ++k) {
+        const uint4 v = r4[k];
+        nb[4 * k] = v.x, nb[4 * k + 1] = v.y, nb[4 * k + 2] = v.z, nb[4 * k + 3] = v.w;
+      }
     }
   };
+  lds_u8_t* const my_rec = sb + lane * TB_STAGE_STRIDE;  // this lane's row of the staged block
   int pend_row = 0, pend_n = 0, pend_st = -1;   // this lane's path cell of the previous block, its posterior in flight
   float pend_lp = 0.0f;
   auto finish = [&]() {
@@ -944,9 +882,8 @@ __device__ __forceinline__ bool traceback(const ReadDesc& rd, const WaveCtx& w, 
     const int base = t - 63;
     const int row = base + lane;
     const uint32_t prow = nprow;
-    const uint64_t stored = nstored;
 #pragma unroll
-    for (int j = 0; j < CPL; ++j) sb[lane * CPL + j] = nb[j];
+    for (int k = 0; k < REC_DWORDS; ++k) reinterpret_cast<lds_u32_t*>(my_rec)[k] = nb[k];
     wave_lds_sync_local();
     if (base > 1) fetch(base - 64);   // (base <= 1: this is the last block)
     int my_n = 0, my_st = -1;
@@ -974,9 +911,9 @@ __device__ __forceinline__ bool traceback(const ReadDesc& rd, const WaveCtx& w, 
         continue;
       }
       // state E in column n at row t: every lane tests its own row's decision bit of this column
-      const uint64_t wd = sb[lane * CPL + sj];                       // ballot word of cell index j = slot % CPL
+      const uint32_t by = my_rec[sq];                                 // the byte of the sweep's lane slot / CPL, in this lane's row
       const uint64_t upto = (2ull << tl) - 1ull;                      // lanes 0 .. tl (tl = 63: the shift leaves 0, minus 1: all)
-      const uint64_t m = __ballot((wd >> sq) & 1) & upto & in_block;  // bit of lane slot / CPL; rows block_lo .. t
+      const uint64_t m = __ballot(dynrec::rec_decision(by, sj)) & upto & in_block;  // cell index slot % CPL; rows block_lo .. t
       if (m) {
         // the path turns at the highest such row r: rows r .. t are E cells of column n, the M cell lies one row below,
         // then E in column n-1 -- taken in the same step when that M cell lies in this block
@@ -1018,7 +955,7 @@ __device__ __forceinline__ bool traceback(const ReadDesc& rd, const WaveCtx& w, 
       // a cell the sweep did not store lies below the floor: exp() of it is exactly 0.0, as exp(-inf) is (lpe_liveness.hpp);
       // what the array holds there is another read's
       if (inplace) pend_lp = lp[2 * cell + (my_st ? 0 : 1)];
-      else if (my_st == 0) pend_lp = lpe_slot_stored(stored, my_n % P) ? lp[cell] : -INFINITY;
+      else if (my_st == 0) pend_lp = dynrec::rec_stored(my_rec[(my_n % P) / CPL]) ? lp[cell] : -INFINITY;  // lpe_slot_stored on the staged copy
       pend_row = row;
       pend_n = my_n;
       pend_st = my_st;
@@ -1026,64 +963,6 @@ __device__ __forceinline__ bool traceback(const ReadDesc& rd, const WaveCtx& w, 
     wave_lds_sync_local();
   }
   finish();
-#else
-  while (t > 0 && n > 0) {
-    const int base = t - 63;
-    const int row = base + lane;
-    uint32_t prow = 0;
-    uint64_t stored = 0;
-    if (row >= 1) {
-      prow = pool_row(w, row);
-#pragma unroll
-      for (int j = 0; j < CPL; ++j) sb[lane * CPL + j] = bits[(size_t)prow * ROW_WORDS + j];
-      stored = bits[(size_t)prow * ROW_WORDS + CPL];
-    }
-    wave_lds_sync();
-    int my_n = 0, my_slot = 0, my_st = -1;
-    const int block_lo = base < 1 ? 1 : base;  // lowest row of this block that exists
-    while (t >= block_lo && n > 0) {
-      if (stM) {  // M(t,n): segment start; continue with E(t-1, n-1)
-        if (row == t) {
-          my_n = n;
-          my_slot = slot;
-          my_st = 1;
-        }
-        --n;
-        slot = slot ? slot - 1 : P - 1;
-        stM = 0;
-        --t;
-        continue;
-      }
-      // state E in column n at row t: every lane tests its own row for this column
-      const uint64_t wd = sb[lane * CPL + (slot % CPL)];  // ballot word of cell index j = slot % CPL
-      const bool bit = (row >= block_lo) && (row <= t) && ((wd >> (slot / CPL)) & 1);  // lane = slot / CPL
-      const uint64_t m = __ballot(bit);
-      const int r = m ? base + (63 - __builtin_clzll(m)) : block_lo - 1;  // highest turning row, or none
-      const int e_lo = m ? r : block_lo;  // rows e_lo..t are E cells of column n
-      if (row >= e_lo && row <= t) {
-        my_n = n;
-        my_slot = slot;
-        my_st = 0;
-      }
-      if (m) {
-        t = r - 1;  // M cell of column n (may lie in the next block: stM carries over)
-        stM = 1;
-      } else {
-        t = block_lo - 1;
-      }
-    }
-    if (my_st >= 0) {
-      // E cell of the path: the forward sweep stored its log-posterior. M cells (segment starts, ~1 row in
-      // 10) get theirs from mpost, one lane per segment, instead of ~6 dependent loads in this walk.
-      const size_t cell = (size_t)prow * P + row_pos(my_slot);
-      if (inplace) pp[row] = exp((double)lp[2 * cell + (my_st ? 0 : 1)]);
-      else if (my_st == 0) pp[row] = exp((double)(lpe_slot_stored(stored, my_slot) ? lp[cell] : -INFINITY));
-      pathn[row] = (uint32_t)my_n | (my_st ? 0x80000000u : 0u);
-      if (my_st) segrow[my_n - 1] = (uint32_t)row;
-    }
-    wave_lds_sync();
-  }
-#endif
   return t == 0 && n == 0;
 }
 
@@ -1099,7 +978,7 @@ __device__ __forceinline__ bool traceback(const ReadDesc& rd, const WaveCtx& w, 
 // -inf in its place gives the same exp() = 0.0 (lpe_liveness.hpp).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void mpost(const ReadDesc& rd, const WaveCtx& w, const double* __restrict__ bE,
-                                      const float* __restrict__ lp, const uint64_t* __restrict__ bits, const double* __restrict__ sig,
+                                      const float* __restrict__ lp, const uint8_t* __restrict__ rec, const double* __restrict__ sig,
                                       const Emis* __restrict__ par, TraceBuffers tb, double Zb, double m1) {
   const int T = (int)rd.T, N = (int)rd.N;
   const double* __restrict__ sg = sig + rd.sig_off;
@@ -1112,7 +991,7 @@ __device__ __forceinline__ void mpost(const ReadDesc& rd, const WaveCtx& w, cons
     } else {
       const uint32_t prow = pool_row(w, row - 1);
       const size_t pcell = (size_t)prow * P + row_pos(pslot);
-      const double lpe = lpe_slot_stored(bits[(size_t)prow * ROW_WORDS + CPL], pslot) ? (double)lp[pcell] : NEG_INF;
+      const double lpe = lpe_slot_stored(rec + (size_t)prow * dynrec::REC_BYTES, pslot) ? (double)lp[pcell] : NEG_INF;
       fE_prev = (lpe - bE[pcell]) + Zb;
     }
     const Emis em = par[rd.par_off + n - 1];
@@ -1409,7 +1288,7 @@ struct WaveStats {
 template <int JOB, bool MIXED>
 __device__ __forceinline__ void run_read(const ReadDesc& rd, const WaveCtx& w, const PagePool& pool, const ReadIO& io,
                                          const double* __restrict__ sig, const Emis* __restrict__ par,
-                                         const SoftplusNode* s_tab, unsigned ring_base, lds_u64_t* sb, WaveStats& ws, uint64_t t1) {
+                                         const SoftplusNode* s_tab, unsigned ring_base, lds_u8_t* sb, WaveStats& ws, uint64_t t1) {
   constexpr bool LATTICE = JOB != JOB_Z;
   // READ_STRICT: every row bit for bit. READ_STRICT_START: the backward sweep and the first rd.strict_rows rows of the
   // forward sweep -- every decision up to that row is then the reference's own (see forward_sweep), which is what a
@@ -1426,9 +1305,9 @@ __device__ __forceinline__ void run_read(const ReadDesc& rd, const WaveCtx& w, c
     t2 = __builtin_amdgcn_s_memtime();
     ws.rows_cert += (uint64_t)rd.T + (uint64_t)min((int)rd.T, strict_rows);
     if (JOB == JOB_ALIGN_INPLACE)
-      Zf = forward_sweep<true, true, MIXED>(rd, w, sig, par, pool.ws, reinterpret_cast<float*>(pool.ws), pool.bits, Zb, io.m1, io.e2, s_tab, ring_base, io.lpe_floor, strict_rows, &ws.n_fallback);
+      Zf = forward_sweep<true, true, MIXED>(rd, w, sig, par, pool.ws, reinterpret_cast<float*>(pool.ws), reinterpret_cast<uint8_t*>(pool.bits), Zb, io.m1, io.e2, s_tab, ring_base, io.lpe_floor, strict_rows, &ws.n_fallback);
     else
-      Zf = forward_sweep<true, false, MIXED>(rd, w, sig, par, pool.ws, pool.lpe, pool.bits, Zb, io.m1, io.e2, s_tab, ring_base, io.lpe_floor, strict_rows, &ws.n_fallback);
+      Zf = forward_sweep<true, false, MIXED>(rd, w, sig, par, pool.ws, pool.lpe, reinterpret_cast<uint8_t*>(pool.bits), Zb, io.m1, io.e2, s_tab, ring_base, io.lpe_floor, strict_rows, &ws.n_fallback);
   } else {
     if constexpr (JOB == JOB_TRAIN || JOB == JOB_TRAIN_ZCHECK) {
       // backward sweep in the log domain (the emission's constant folded), then the posterior chain
@@ -1446,9 +1325,9 @@ __device__ __forceinline__ void run_read(const ReadDesc& rd, const WaveCtx& w, c
       Zb = backward_sweep<LATTICE, JOB == JOB_Z ? ARITH_FOLDED : ARITH_DEFAULT>(rd, w, sig, par, pool.ws, io.m1, io.e2, s_tab);
       t2 = __builtin_amdgcn_s_memtime();
       if (JOB == JOB_ALIGN) {
-        Zf = forward_sweep<true, false, false>(rd, w, sig, par, pool.ws, pool.lpe, pool.bits, Zb, io.m1, io.e2, s_tab, ring_base, io.lpe_floor);
+        Zf = forward_sweep<true, false, false>(rd, w, sig, par, pool.ws, pool.lpe, reinterpret_cast<uint8_t*>(pool.bits), Zb, io.m1, io.e2, s_tab, ring_base, io.lpe_floor);
       } else if (JOB == JOB_ALIGN_INPLACE) {
-        Zf = forward_sweep<true, true, false>(rd, w, sig, par, pool.ws, reinterpret_cast<float*>(pool.ws), pool.bits, Zb, io.m1, io.e2, s_tab, ring_base, io.lpe_floor);
+        Zf = forward_sweep<true, true, false>(rd, w, sig, par, pool.ws, reinterpret_cast<float*>(pool.ws), reinterpret_cast<uint8_t*>(pool.bits), Zb, io.m1, io.e2, s_tab, ring_base, io.lpe_floor);
       } else {
         Zf = forward_sweep<false, false, false>(rd, w, sig, par, nullptr, nullptr, nullptr, 0.0, io.m1, io.e2, s_tab, ring_base, 0.0f);
       }
@@ -1466,7 +1345,7 @@ __device__ __forceinline__ void run_read(const ReadDesc& rd, const WaveCtx& w, c
   uint32_t n_seg = 0;
   if ((JOB == JOB_ALIGN || JOB == JOB_ALIGN_INPLACE) && status == 0) {
     const float* lp = JOB == JOB_ALIGN ? pool.lpe : reinterpret_cast<const float*>(pool.ws);
-    const bool complete = traceback(rd, w, lp, pool.bits, io.tb, JOB == JOB_ALIGN_INPLACE, sb);
+    const bool complete = traceback(rd, w, lp, reinterpret_cast<uint8_t*>(pool.bits), io.tb, JOB == JOB_ALIGN_INPLACE, sb);
 #ifdef DYN_EXP_TRACE_SPLIT  // development: the statistics slots of the certified sweeps carry traceback / mpost cycles instead
     const uint64_t t4 = __builtin_amdgcn_s_memtime();
     ws.cyc_bs += t4 - t3;
@@ -1475,7 +1354,7 @@ __device__ __forceinline__ void run_read(const ReadDesc& rd, const WaveCtx& w, c
       if (JOB == JOB_ALIGN) {
         // segrow was written by other lanes of this wave through global memory
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        mpost(rd, w, pool.ws, pool.lpe, pool.bits, sig, par, io.tb, Zb, io.m1);
+        mpost(rd, w, pool.ws, pool.lpe, reinterpret_cast<uint8_t*>(pool.bits), sig, par, io.tb, Zb, io.m1);
       }
 #ifdef DYN_EXP_TRACE_SPLIT
       ws.cyc_fs += __builtin_amdgcn_s_memtime() - t4;
@@ -1565,7 +1444,7 @@ __global__ DYN_ONE_WAVE_PER_SIMD void k_read_queue(const QueueArgs q, const Read
   w.pt = (lds_u32_t*)&s_pt[wave][0];
   w.log_r = q.pool.log_rows;
   const unsigned ring_base = (unsigned)(size_t)(__attribute__((address_space(3))) double*)&s_ring[wave][0][0];
-  lds_u64_t* sb = (lds_u64_t*)&s_ring[wave][0][0];  // traceback staging: the ring is idle by then
+  lds_u8_t* sb = (lds_u8_t*)&s_ring[wave][0][0];  // traceback staging: the ring is idle by then
 
   WaveStats ws;
   // the border-confidence phase reads whole windows of LPE, a sampled path any cell of the band, the interval and the soft-level
@@ -1766,7 +1645,7 @@ __global__ DYN_ONE_WAVE_PER_SIMD void k_session(const SessionArgs sa, const char
   w.pt = (lds_u32_t*)&s_pt[wave][0];
   w.log_r = sa.pool.log_rows;
   const unsigned ring_base = (unsigned)(size_t)(__attribute__((address_space(3))) double*)&s_ring[wave][0][0];
-  lds_u64_t* sb = (lds_u64_t*)&s_ring[wave][0][0];
+  lds_u8_t* sb = (lds_u8_t*)&s_ring[wave][0][0];
   // this wave's arena, for the whole session (PAGED: pages come and go through the free list)
   if (!PAGED)
     for (uint32_t k = w.lane; k < sa.arena_pages; k += 64) w.pt[k] = slot * sa.arena_pages + k;

@@ -21,8 +21,9 @@ using dynmath::Emis;
 constexpr int CPL = 7;                       // cells per lane
 constexpr int P = 64 * CPL;                  // 448 slots per row
 constexpr int MAX_HALF_BAND = (P - 2) / 2;   // 2*bw+1 <= P-1  ->  bw <= 223 (band <= 447)
-// 64-bit words of a row's record in PagePool::bits: the CPL decision ballots, then the lane mask of the float LPE cells the
-// forward sweep stored (lpe_liveness.hpp; in-place layout: every lane). 64 bytes per row.
+// 64-bit words of a row's record in PagePool::bits: 64 bytes per row, one BYTE per lane of the forward sweep -- the lane's CPL
+// decision bits and, in bit 7, whether its float LPE cells of the row were stored (decision_record.hpp, lpe_liveness.hpp;
+// in-place layout: set in every lane).
 constexpr int ROW_WORDS = CPL + 1;
 
 // The lattice of a read lives in PAGES of 2^log_rows rows taken from a pool that all reads of a
@@ -88,7 +89,7 @@ struct TrainBuffers {
 struct PagePool {
   double* ws;           // [n_pages][rows_per_page][P]   backward-E (8 B per slot); in place: (float LPM, float LPE)
   float* lpe;           // [n_pages][rows_per_page][P]   float LPE per slot (separate layout) or nullptr
-  uint64_t* bits;       // [n_pages][rows_per_page][ROW_WORDS] decision ballots, then the mask of the lanes whose LPE was stored
+  uint64_t* bits;       // [n_pages][rows_per_page][ROW_WORDS] the rows' records: a byte per lane, its decision bits and "LPE stored"
   uint32_t* free_list;  // stack of free page numbers
   // ctl (32-bit words): [0] lock of the free-page stack, [1] queue head (next read), [2] free pages on the
   // stack, [3] abort (a wave gave up waiting: the queue drains, the host reports the launch as failed),

@@ -26,7 +26,7 @@ namespace {
 
 // workgroups of a session = CUs it occupies (dyn_aligner_set_session_mode leaves the others free)
 int session_wgs(const dyn_aligner* a) { return std::max(1, a->sess_cus); }
-// bytes of one lattice row in the pool (separate LPE layout): bE 8 B + float LPE 4 B per slot + the decision ballots
+// bytes of one lattice row in the pool (separate LPE layout): bE 8 B + float LPE 4 B per slot + the row's 64-byte record
 constexpr uint64_t SESSION_ROW_BYTES = (uint64_t)dynk::P * 12 + dynk::ROW_WORDS * 8;
 
 uint32_t session_pages_of(uint64_t S, int log_r) { return (uint32_t)((S + 2 + (1ull << log_r) - 1) >> log_r); }
@@ -220,7 +220,7 @@ int session_quiesce(dyn_aligner* a) {
 // of the same kind should fit as well) stays within a wave's PT_MAX-entry page table.
 static void session_geometry(uint64_t max_S, int* log_r, uint32_t* arena_pages) {
   const uint64_t cap_S = max_S + max_S / 8 + 64;
-  int lr = 8;
+  int lr = dyneng::min_page_log_rows();
   while (session_pages_of(cap_S, lr) > (uint32_t)dynk::PT_MAX) ++lr;
   *log_r = lr;
   *arena_pages = session_pages_of(cap_S, lr);
