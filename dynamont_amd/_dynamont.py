@@ -389,10 +389,11 @@ class Batch:
 
     _wants = JobWants()  # of the last align(): a batch never aligned has nothing optional to fetch
 
-    def __init__(self, aligner: "Aligner", signals, sig_offsets, seqs: bytes, seq_offsets, raw=None):
+    def __init__(self, aligner: "Aligner", signals, sig_offsets, seqs: bytes, seq_offsets, raw=None, site_ids=None):
         """raw = None: ``signals`` are normalised float64 samples. raw = dict(shift, scale, window,
         n_sigmas, f32): ``signals`` are RAW float32 / int16 / float64 samples and the preprocessing of
-        segment.py:146-153 runs on the device (dyn_batch_create_raw)."""
+        segment.py:146-153 runs on the device (dyn_batch_create_raw). ``site_ids``: the batch's per-base site ids, packed like
+        ``seqs`` (``Aligner.set_site_summary``); kept alive here."""
         self._al = aligner
         self._L = N.lib()
         self.n = len(sig_offsets) - 1
@@ -402,6 +403,7 @@ class Batch:
         h = C.c_void_p()
         if raw is None:
             sig = np.ascontiguousarray(signals, dtype=np.float64)
+            self._site_ids = aligner._stage_site_ids(site_ids)
             rc = self._L.dyn_batch_create(aligner._h, self.n, _ptr(sig, N.c_double_p), _ptr(self._sig_off, N.c_u64_p),
                                           seqs, _ptr(self._seq_off, N.c_u64_p), C.byref(h))
         else:
@@ -411,6 +413,7 @@ class Batch:
                 raise ValueError(f"raw signal dtype {sig.dtype} is not float32, int16 or float64")
             shift = np.ascontiguousarray(raw["shift"], dtype=np.float64)
             scale = np.ascontiguousarray(raw["scale"], dtype=np.float64)
+            self._site_ids = aligner._stage_site_ids(site_ids)
             rc = self._L.dyn_batch_create_raw(aligner._h, self.n, sig.ctypes.data, code, _ptr(self._sig_off, N.c_u64_p),
                                               _ptr(shift, N.c_double_p), _ptr(scale, N.c_double_p),
                                               int(raw.get("window", 3)), float(raw.get("n_sigmas", 3.0)),
@@ -694,6 +697,17 @@ def int128_of_limbs(lo, hi) -> np.ndarray:
     return out
 
 
+SITE_SUMMARY_TOTALS = ("reads_ok", "rows_added", "samples_added", "rows_without_site", "rows_skipped")
+
+
+def site_summary_from_limbs(cols, totals) -> dict:
+    """the dict Aligner.site_summary() returns, from the seven uint64 arrays and the five totals of the C interface"""
+    cols = [np.ascontiguousarray(c, dtype=np.uint64) for c in cols]
+    t = [int(x) for x in np.asarray(totals, dtype=np.uint64).tolist()]
+    return {"n_rows": cols[0], "n_samples": cols[1], "dwell_sq": cols[2], "M1": int128_of_limbs(cols[3], cols[4]),
+            "M2": int128_of_limbs(cols[5], cols[6]), "limbs": cols, "totals": dict(zip(SITE_SUMMARY_TOTALS, t))}
+
+
 def kmer_summary_from_limbs(cols, totals) -> dict:
     """the dict Aligner.kmer_summary() returns, from the six uint64 arrays and the four totals of the C interface"""
     cols = [np.ascontiguousarray(c, dtype=np.uint64) for c in cols]
@@ -722,6 +736,8 @@ class Aligner:
     _band_retry = None  # set_band_retry: (min_margin, max_band, factor)
     _guide_rescue = (0, 0, 8)  # set_guide_rescue: (min_margin, half_width, refine)
     _kmer_summary = False  # set_kmer_summary
+    _site_summary = 0  # set_site_summary: num_sites while on
+    _site_table = 0  # ... and the size of the handle's table (it outlives the switch)
     _strict = 1  # set_strict
     _model_override = None  # set_model: (mean, stdev)
 
@@ -962,6 +978,60 @@ class Aligner:
             _raise(rc, self.last_error())
         self._kmer_summary = bool(on)
 
+    def set_site_summary(self, num_sites: int) -> None:
+        """dyn_aligner_set_site_summary: while ``num_sites`` > 0, every output row of every ok read of the
+        align(calc_probabilities=True) jobs submitted on this aligner WITH ``site_ids=`` is added to its site's entry of a
+        per-site table kept on the GPU as exact integers, 56 bytes per site: coverage, dwell and the
+        sums of the reads' event means and of their squares. ``site_ids``: one uint32 per base of every sequence, in aligner
+        orientation, packed like the sequences (``dynamont_amd.sites`` builds them from a mapping); ``DYN_SITE_NONE`` = no site.
+        ``site_summary()`` fetches the table, ``reset_site_summary()`` zeroes it; 0 turns the switch off and keeps the table;
+        another size waits for the tickets in flight and starts a new table. Like ``set_kmer_summary`` it is not combined
+        with ``set_band_retry``: the retried reads would be summed twice (ValueError)."""
+        num_sites = int(num_sites)
+        if num_sites < 0:
+            raise ValueError("set_site_summary: num_sites must be >= 0")
+        if num_sites and self._band_retry:
+            raise ValueError("set_site_summary with set_band_retry: the retried reads would be summed twice")
+        rc = self._L.dyn_aligner_set_site_summary(self._h, num_sites)
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        self._site_summary = num_sites
+        if num_sites:
+            self._site_table = num_sites
+
+    def _stage_site_ids(self, site_ids):
+        """dyn_aligner_stage_site_ids for the batch-creating call that follows at once; returns the array to keep alive"""
+        if site_ids is None:
+            return None
+        ids = np.ascontiguousarray(site_ids, dtype=np.uint32)
+        if ids.ndim != 1:
+            raise ValueError("site_ids must be a one-dimensional uint32 array, one id per base")
+        rc = self._L.dyn_aligner_stage_site_ids(self._h, _ptr(ids, N.c_u32_p), ids.size)
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        return ids
+
+    def reset_site_summary(self) -> None:
+        rc = self._L.dyn_aligner_site_summary_reset(self._h)
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+
+    def site_summary(self, lo: int = 0, hi: int | None = None) -> dict:
+        """dyn_aligner_site_summary_fetch: the sites [lo, hi) (default: all) of the table after every job that has completed.
+        ``n_rows`` (coverage), ``n_samples``, ``dwell_sq``: uint64 arrays; ``M1``, ``M2``: object arrays of Python ints (the
+        signed 128-bit sums of rint(m * 2**40) and rint(m * m * 2**40) over the rows' event means m); ``limbs``: the seven raw
+        uint64 arrays as fetched; ``totals``: reads_ok, rows_added, samples_added, rows_without_site, rows_skipped. Fetch when
+        the pipeline is dry."""
+        lo = int(lo)
+        hi = self._site_table if hi is None else int(hi)
+        n = max(0, hi - lo)
+        cols = [np.zeros(n, dtype=np.uint64) for _ in range(7)]
+        totals = np.zeros(5, dtype=np.uint64)
+        rc = self._L.dyn_aligner_site_summary_fetch(self._h, lo, hi, *[_ptr(c, N.c_u64_p) for c in cols], _ptr(totals, N.c_u64_p))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        return site_summary_from_limbs(cols, totals)
+
     def set_band_margin(self, on: bool) -> None:
         """dyn_aligner_set_band_margin: align(calc_probabilities=True) jobs submitted while on also report, per read, how
         close the called path came to a real edge of its band: ``AlignBatchResult.band_margin_low``
@@ -981,7 +1051,7 @@ class Aligner:
         first result in place, and ``band_used`` (uint32 [n]) records the band each read's rows come from. A read whose
         retry fails keeps its last good result. Implies ``set_band_margin(True)``; ``min_margin = 0`` turns the retry off
         (the margins stay on). ``align_async`` tickets report margins but are never retried. Not together with
-        ``set_kmer_summary(True)``: the retried reads would be summed twice (ValueError)."""
+        ``set_kmer_summary(True)`` or ``set_site_summary(num_sites > 0)``: the retried reads would be summed twice (ValueError)."""
         min_margin, max_band, factor = int(min_margin), int(max_band), int(factor)
         if min_margin < 0 or factor < 2 or max_band < 1:
             raise ValueError("set_band_retry: min_margin >= 0, factor >= 2 and max_band >= 1 are required")
@@ -992,6 +1062,8 @@ class Aligner:
             raise ValueError("set_band_retry with set_guide_rescue: both re-align the reads a margin flags; choose one")
         if self._kmer_summary:
             raise ValueError("set_band_retry with set_kmer_summary: the retried reads would be summed twice")
+        if self._site_summary:
+            raise ValueError("set_band_retry with set_site_summary: the retried reads would be summed twice")
         if self._posterior_samples[0] > 0:
             raise ValueError("set_band_retry with set_posterior_samples: a retried read's samples would come from another handle, "
                              "keyed by another index")
@@ -1118,9 +1190,10 @@ class Aligner:
         return status, msgs, out
 
     # -- batch API ------------------------------------------------------------------------------
-    def batch(self, signals: Sequence, sequences: Sequence[str]) -> Batch:
+    def batch(self, signals: Sequence, sequences: Sequence[str], site_ids=None) -> Batch:
+        """``site_ids``: the batch's per-base uint32 site ids, packed like the sequences (``set_site_summary``)"""
         sig, sig_off, seqs, seq_off = _pack(signals, sequences)
-        return Batch(self, sig, sig_off, seqs, seq_off)
+        return Batch(self, sig, sig_off, seqs, seq_off, site_ids=site_ids)
 
     def batch_packed(self, signals, sig_offsets, seqs: bytes, seq_offsets) -> Batch:
         return Batch(self, signals, sig_offsets, seqs, seq_offsets)
@@ -1141,10 +1214,11 @@ class Aligner:
                      raw=dict(shift=shift, scale=scale, window=window, n_sigmas=n_sigmas, f32=f32))
 
     def align_async(self, signals, sig_offsets, seqs: bytes, seq_offsets, calc_probabilities: bool = True,
-                    out: AlignBatchResult | None = None) -> AsyncBatch:
+                    out: AlignBatchResult | None = None, site_ids=None) -> AsyncBatch:
         """dyn_batch_align_async on packed inputs (``synth.pack_reads`` layout): returns at once; the batch's
         validation, H2D, kernels, D2H and unpacking overlap with those of the batches submitted around it.
-        ``out``: result object of an EARLIER, completed batch to refill."""
+        ``out``: result object of an EARLIER, completed batch to refill. ``site_ids``: the ticket's per-base uint32 site ids,
+        packed like ``seqs`` (``set_site_summary``); the ticket keeps the array alive."""
         sig = np.ascontiguousarray(signals, dtype=np.float64)
         sig_off = np.ascontiguousarray(sig_offsets, dtype=np.uint64)
         seq_off = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
@@ -1153,12 +1227,13 @@ class Aligner:
         if out is None or out.n != n or out.cap < cap:
             out = AlignBatchResult(n, cap + cap // 8)
         h = C.c_void_p()
+        ids = self._stage_site_ids(site_ids)
         rc = self._L.dyn_batch_align_async(self._h, n, _ptr(sig, N.c_double_p), _ptr(sig_off, N.c_u64_p), seqs,
                                            _ptr(seq_off, N.c_u64_p), int(bool(calc_probabilities)), C.byref(out._c),
                                            C.byref(h))
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
-        return AsyncBatch(self, h, out, (sig, sig_off, seqs, seq_off), wants=self._job_wants(calc_probabilities, sig_off))
+        return AsyncBatch(self, h, out, (sig, sig_off, seqs, seq_off, ids), wants=self._job_wants(calc_probabilities, sig_off))
 
     def _raw_args(self, raw, shift, scale, calibration=None):
         scattered = isinstance(raw, (list, tuple))
@@ -1186,7 +1261,7 @@ class Aligner:
 
     def align_raw_async(self, raw, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 3,
                         n_sigmas: float = 3.0, f32: bool = False, calc_probabilities: bool = True,
-                        out: AlignBatchResult | None = None, calibration=None) -> AsyncBatch:
+                        out: AlignBatchResult | None = None, calibration=None, site_ids=None) -> AsyncBatch:
         """dyn_batch_align_raw_async: ``raw`` = the concatenated RAW [start:end) slices of the batch (float32 pA,
         int16 ADC or float64), or a LIST of per-read arrays (gathered by the library's helper threads, no copy here); normalisation + Hampel filter (segment.py:146-153) run on the device as the first
         stage of the asynchronous pipeline. ``calibration`` = (offset[n], scale[n]) with int16 ``raw``: the samples are
@@ -1200,6 +1275,7 @@ class Aligner:
         if out is None or out.n != n or out.cap < cap:
             out = AlignBatchResult(n, cap + cap // 8)
         h = C.c_void_p()
+        ids = self._stage_site_ids(site_ids)
         rc = self._L.dyn_batch_align_raw_async(self._h, n, raw.ctypes.data, code, _ptr(raw_off, N.c_u64_p),
                                                _ptr(cal[0], N.c_float_p) if code & 0xff == 3 else None,
                                                _ptr(cal[1], N.c_float_p) if code & 0xff == 3 else None, _ptr(shift, N.c_double_p), _ptr(scale, N.c_double_p), int(window),
@@ -1207,12 +1283,12 @@ class Aligner:
                                                int(bool(calc_probabilities)), C.byref(out._c), C.byref(h))
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
-        return AsyncBatch(self, h, out, (raw, raw_off, shift, scale, seqs, seq_off, cal),
+        return AsyncBatch(self, h, out, (raw, raw_off, shift, scale, seqs, seq_off, cal, ids),
                           wants=self._job_wants(calc_probabilities, raw_off))
 
     def align_vbz_async(self, chunks, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 3,
                         n_sigmas: float = 3.0, f32: bool = False, calc_probabilities: bool = True,
-                        out: AlignBatchResult | None = None, calibration=None) -> AsyncBatch:
+                        out: AlignBatchResult | None = None, calibration=None, site_ids=None) -> AsyncBatch:
         """dyn_batch_align_vbz_async: the batch's signal as POD5 chunks that are still VBZ-compressed. ``chunks`` =
         (ptrs uint64[c], nbytes uint64[c], samples uint32[c], read_chunk_offsets uint64[n+1], slice_start uint64[n]);
         ``raw_offsets`` = prefix sums of the slice lengths. The library's helper threads decode straight into the pinned
@@ -1231,6 +1307,7 @@ class Aligner:
         if out is None or out.n != n or out.cap < cap:
             out = AlignBatchResult(n, cap + cap // 8)
         h = C.c_void_p()
+        ids = self._stage_site_ids(site_ids)
         rc = self._L.dyn_batch_align_vbz_async(self._h, n, ptrs.ctypes.data, _ptr(nbytes, N.c_u64_p),
                                                samples.ctypes.data_as(C.POINTER(C.c_uint32)), _ptr(read_off, N.c_u64_p),
                                                _ptr(skip, N.c_u64_p), _ptr(raw_off, N.c_u64_p),
@@ -1241,7 +1318,7 @@ class Aligner:
                                                C.byref(out._c), C.byref(h))
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
-        return AsyncBatch(self, h, out, (ptrs, nbytes, samples, read_off, skip, raw_off, shift, scale, seqs, seq_off, cal),
+        return AsyncBatch(self, h, out, (ptrs, nbytes, samples, read_off, skip, raw_off, shift, scale, seqs, seq_off, cal, ids),
                           wants=self._job_wants(calc_probabilities, raw_off))
 
     def train_raw_async(self, raw, raw_offsets, shift, scale, seqs: bytes, seq_offsets, window: int = 7,
@@ -1287,8 +1364,9 @@ class Aligner:
             _raise(rc, self.last_error())
         return AsyncBatch(self, h, out, (sig, sig_off, seqs, seq_off), wants=JobWants())
 
-    def align_batch(self, signals: Sequence, sequences: Sequence[str], calc_probabilities: bool = True) -> AlignBatchResult:
-        with self.batch(signals, sequences) as b:
+    def align_batch(self, signals: Sequence, sequences: Sequence[str], calc_probabilities: bool = True,
+                    site_ids=None) -> AlignBatchResult:
+        with self.batch(signals, sequences, site_ids=site_ids) as b:
             b.align(calc_probabilities)
             res = b.fetch()
         if self._band_retry and calc_probabilities and res.band_margin_low is not None:
@@ -1503,6 +1581,12 @@ class MultiAligner:
 
     def last_error(self) -> str:
         return (self._L.dyn_multi_last_error(self._h) or b"").decode(errors="replace")
+
+    def set_site_summary(self, num_sites: int) -> None:
+        """Not supported: the per-site table lives on ONE device's handle and the reads of a batch are cut over the devices.
+        Use one ``Aligner`` per device and add the tables (they are integers)."""
+        raise NotImplementedError("MultiAligner has no per-site summary (Aligner.set_site_summary): use one Aligner per device "
+                                  "and add their tables")
 
     def _cap(self, seq_off) -> int:
         return int(self._L.dyn_segment_capacity(self._L.dyn_multi_handle(self._h, 0), len(seq_off) - 1, _ptr(seq_off, N.c_u64_p)))

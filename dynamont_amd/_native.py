@@ -14,8 +14,8 @@ CSRC = os.path.join(HERE, "csrc")
 # DYN_LIB_PATH: another build of the SAME sources (tools/sanitize: the host side under ASan / UBSan / TSan on the CPU)
 LIB_PATH = os.environ.get("DYN_LIB_PATH") or os.path.join(HERE, "libdynamont_mi.so")
 SOURCES = ["dynamont_mi.cpp", "buffers.cpp", "launch.cpp", "session.cpp", "async_engine.cpp", "pore_model.cpp", "csv_format.cpp", "csv_sink.cpp", "vbz_decode.cpp", "bam_reader.cpp", "rccl_comm.cpp", "model_format.cpp",
-           "nt_kernels.hip", "pool_stats.hip", "band_reads.hip", "event_stats.hip", "rescale.hip", "kmer_summary.hip", "segment_scores.hip", "band_margin.hip", "guided_band.hip", "auto_guide.hip", "guide_rescue.hip"]
-HEADERS = ["engine.hpp", "engine_internal.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "dp_cell.hpp", "segment_kernels.hpp", "preprocess_kernels.hpp", "kmer_summary_kernels.hpp", "segment_score_kernels.hpp", "border_kernels.hpp", "interval_kernels.hpp", "soft_level_kernels.hpp", "sample_kernels.hpp", "band_margin_kernels.hpp", "band_reads.hpp", "guided_band_kernels.hpp", "auto_guide_kernels.hpp", "guide_rescue_kernels.hpp", "band_runs.hpp", "lpe_liveness.hpp", "decision_record.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
+           "nt_kernels.hip", "pool_stats.hip", "band_reads.hip", "event_stats.hip", "rescale.hip", "kmer_summary.hip", "site_summary.hip", "segment_scores.hip", "band_margin.hip", "guided_band.hip", "auto_guide.hip", "guide_rescue.hip"]
+HEADERS = ["engine.hpp", "engine_internal.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "dp_cell.hpp", "segment_kernels.hpp", "preprocess_kernels.hpp", "kmer_summary_kernels.hpp", "site_summary_kernels.hpp", "exact_sum_kernels.hpp", "segment_score_kernels.hpp", "border_kernels.hpp", "interval_kernels.hpp", "soft_level_kernels.hpp", "sample_kernels.hpp", "band_margin_kernels.hpp", "band_reads.hpp", "guided_band_kernels.hpp", "auto_guide_kernels.hpp", "guide_rescue_kernels.hpp", "band_runs.hpp", "lpe_liveness.hpp", "decision_record.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
 
 DYN_DEVICE_HOST_ONLY = -2
 DYN_CSV_EVENT_STATS = 0x1  # dyn_csv_sink_open_ex flag
@@ -30,6 +30,7 @@ DYN_CSV_SOFT_LEVELS = 0x200  # dyn_csv_sink_open_ex flag (bits 0x4, 0x20, 0x80 a
 DYN_POSTERIOR_SAMPLES_MAX = 64
 DYN_SAMPLE_DEAD = 0xFFFFFFFF  # dyn_sample_out: every entry of a dead sample
 DYN_BAND_MARGIN_NONE = 0xFFFFFFFF  # dyn_band_margin_out: the edge was never a real one
+DYN_SITE_NONE = 0xFFFFFFFF  # dyn_aligner_stage_site_ids: this base has no site
 DYN_OK, DYN_ERR_INVALID_ARGUMENT, DYN_ERR_RUNTIME, DYN_ERR_DEVICE, DYN_ERR_OUT_OF_MEMORY = range(5)
 
 c_double_p = C.POINTER(C.c_double)
@@ -108,6 +109,12 @@ class DynJobBatch(C.Structure):
                 ("file_id", C.POINTER(C.c_uint32)), ("bases", C.POINTER(C.c_uint32))]
 
 
+class DynJobAlignment(C.Structure):
+    """dyn_job_alignment: the mapping columns of the batch dyn_bam_next returned last (owned by the reader)"""
+    _fields_ = [("n", C.c_uint64), ("flag", C.POINTER(C.c_uint32)), ("ref_id", C.POINTER(C.c_int32)), ("pos", C.POINTER(C.c_int32)),
+                ("cigar", C.POINTER(C.c_uint32)), ("cigar_off", C.POINTER(C.c_uint64))]
+
+
 class DynTiming(C.Structure):
     _fields_ = [("ms_total", C.c_double), ("ms_dp", C.c_double), ("ms_backward", C.c_double), ("ms_forward", C.c_double),
                 ("ms_trace", C.c_double), ("wave_wait_share", C.c_double), ("wave_occupancy", C.c_double),
@@ -154,6 +161,11 @@ SIGNATURES = {
     "dyn_aligner_set_band_margin": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_aligner_kmer_summary_fetch": (C.c_int, [C.c_void_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p]),
     "dyn_aligner_kmer_summary_reset": (C.c_int, [C.c_void_p]),
+    "dyn_aligner_set_site_summary": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "dyn_aligner_stage_site_ids": (C.c_int, [C.c_void_p, c_u32_p, C.c_uint64]),
+    "dyn_aligner_site_summary_fetch": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p,
+                                                 c_u64_p, c_u64_p]),
+    "dyn_aligner_site_summary_reset": (C.c_int, [C.c_void_p]),
     "dyn_tie_rows": (C.c_uint32, [C.c_void_p, c_i32_p, C.c_uint64, C.c_uint64]),
     "dyn_aligner_last_error": (C.c_char_p, [C.c_void_p]),
     "dyn_read_strerror": (C.c_int, [C.c_int, C.c_char, C.c_char_p, C.c_uint64]),
@@ -229,6 +241,8 @@ SIGNATURES = {
     "dyn_bam_next": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, C.c_uint32, C.c_uint32, C.POINTER(DynJobBatch),
                                C.c_char_p, C.c_uint64]),
     "dyn_bam_skipped": (C.c_uint64, [C.c_void_p]),
+    "dyn_bam_references": (C.c_int, [C.c_void_p, c_u64_p, C.POINTER(C.c_void_p), C.POINTER(c_u64_p), C.POINTER(c_u32_p)]),
+    "dyn_bam_alignment": (C.c_int, [C.c_void_p, C.POINTER(DynJobAlignment)]),
     "dyn_bam_close": (None, [C.c_void_p]),
     "dyn_batch_create": (C.c_int, [C.c_void_p, C.c_uint64, c_double_p, c_u64_p, C.c_char_p, c_u64_p,
                                    C.POINTER(C.c_void_p)]),

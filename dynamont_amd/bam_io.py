@@ -112,9 +112,12 @@ def iter_bam(path: str):
 
 def _parse_bam_record(path: str, data: bytes):
     pos, end = 0, len(data)
-    (_ref, _p, l_read_name, _mapq, _bin, n_cigar, _flag, l_seq, _nref, _npos, _tlen) = struct.unpack_from("<iiBBHHHiiii", data, pos)
+    (ref, p, l_read_name, _mapq, _bin, n_cigar, flag, l_seq, _nref, _npos, _tlen) = struct.unpack_from("<iiBBHHHiiii", data, pos)
     q = pos + 32
     name = data[q:q + l_read_name - 1].decode()
+    if 32 + l_read_name + 4 * n_cigar > end:
+        raise ValueError(f"{path}: malformed BAM record")
+    cigar = np.frombuffer(data, dtype="<u4", count=n_cigar, offset=q + l_read_name)
     q += l_read_name + 4 * n_cigar
     nb = (l_seq + 1) // 2
     # two bases per byte, high nibble first: hexlify spells the nibbles out as hex digits, translate maps those to bases
@@ -145,7 +148,29 @@ def _parse_bam_record(path: str, data: bytes):
             q += 5 + _TAG_SIZE[sub] * cnt
         else:
             raise ValueError(f"{path}: unknown BAM tag type {typ!r}")
-    return BasecallRecord(name, seq, tags)
+    rec = BasecallRecord(name, seq, tags)
+    # the mapping, for callers that key results by reference position (dynamont_amd.sites): BAM's words of len << 4 | op
+    rec.ref, rec.pos, rec.flag, rec.cigar = ref, p, flag, cigar
+    return rec
+
+
+def bam_references(path: str):
+    """(names, lengths) of the reference sequences in a BAM header; two empty lists for an unaligned BAM"""
+    st = _Stream(path)
+    try:
+        head = st.take(8)
+        if head[:4] != b"BAM\x01":
+            raise ValueError(f"{path}: not a BAM file")
+        st.take(struct.unpack_from("<i", head, 4)[0])
+        n_ref, = struct.unpack("<i", st.take(4))
+        names, lengths = [], []
+        for _ in range(n_ref):
+            l_name, = struct.unpack("<i", st.take(4))
+            names.append(st.take(l_name).rstrip(b"\0").decode())
+            lengths.append(struct.unpack("<i", st.take(4))[0])
+        return names, lengths
+    finally:
+        st.close()
 
 
 def _sam_tag_text(tag, value):
@@ -175,17 +200,24 @@ def _bgzf_block(payload: bytes) -> bytes:
     return header + body + struct.pack("<II", zlib.crc32(payload) & 0xFFFFFFFF, len(payload))
 
 
-def write_bam(path: str, records) -> None:
-    """Minimal uBAM writer (tests / synthetic datasets): floats as 'f' (single precision, as dorado
+def write_bam(path: str, records, references=None) -> None:
+    """Minimal BAM writer (tests / synthetic datasets): floats as 'f' (single precision, as dorado
     writes sm/sd/qs), ints as 'i', NumPy arrays as 'B' arrays of their own element type (an int8 array is dorado's
-    move table, mv:B:c), strings as 'Z'."""
+    move table, mv:B:c), strings as 'Z'. Records are (name, sequence, tags): unaligned (flag 4); or (name, sequence, tags,
+    (flag, ref_id, pos, cigar words)) with ``references`` = [(name, length), ..] in the header: a mapped BAM."""
     enc_lut = np.full(256, 15, dtype=np.uint8)  # anything outside the 16 IUPAC codes is stored as N
     for i, c in enumerate(_SEQ_DECODE):
         enc_lut[ord(c)] = i
     out = bytearray(b"BAM\x01")
     text = b"@HD\tVN:1.6\tSO:unknown\n"
-    out += struct.pack("<i", len(text)) + text + struct.pack("<i", 0)
-    for name, seq, tags in records:
+    refs = list(references or [])
+    text += b"".join(b"@SQ\tSN:%s\tLN:%d\n" % (n.encode(), ln) for n, ln in refs)
+    out += struct.pack("<i", len(text)) + text + struct.pack("<i", len(refs))
+    for n, ln in refs:
+        out += struct.pack("<i", len(n) + 1) + n.encode() + b"\0" + struct.pack("<i", ln)
+    for name, seq, tags, *mapping in records:
+        flag, ref_id, pos, cigar = mapping[0] if mapping else (4, -1, -1, ())
+        cigar = np.asarray(cigar, dtype="<u4")
         nm = name.encode() + b"\0"
         codes = enc_lut[np.frombuffer(seq.upper().encode("latin-1"), dtype=np.uint8)]
         if len(codes) % 2:
@@ -202,7 +234,8 @@ def write_bam(path: str, records) -> None:
                 tagb += k.encode() + b"B" + sub.encode() + struct.pack("<i", v.size) + np.ascontiguousarray(v).tobytes()
             else:
                 tagb += k.encode() + b"Z" + str(v).encode() + b"\0"
-        body = struct.pack("<iiBBHHHiiii", -1, -1, len(nm), 0, 4680, 0, 4, len(seq), -1, -1, 0) + nm + packed + b"\xff" * len(seq) + bytes(tagb)
+        body = struct.pack("<iiBBHHHiiii", ref_id, pos, len(nm), 0, 4680, len(cigar), flag, len(seq), -1, -1, 0) + nm + cigar.tobytes() + packed + \
+            b"\xff" * len(seq) + bytes(tagb)
         out += struct.pack("<i", len(body)) + body
     with open(path, "wb") as w:
         data = bytes(out)
@@ -223,7 +256,7 @@ class JobBatch:
     sequence lengths."""
 
     __slots__ = ("n", "names", "name_off", "sids", "sid_off", "uuid", "uuid_ok", "seqs", "seq_off", "shift", "scale",
-                 "start", "end", "files", "file_id", "bases")
+                 "start", "end", "files", "file_id", "bases", "site_ids")  # site_ids: per read, set by whoever keys the reads (--site-summary)
 
     def name(self, i: int) -> str:
         return self.names[int(self.name_off[i]):int(self.name_off[i + 1]) - 1].tobytes().decode()
@@ -256,6 +289,9 @@ class JobBatch:
         out.uuid, out.uuid_ok = self.uuid[keep], self.uuid_ok[keep]
         out.shift, out.scale, out.start, out.end = self.shift[keep], self.scale[keep], self.start[keep], self.end[keep]
         out.files, out.file_id, out.bases = self.files, self.file_id[keep], self.bases[keep]
+        ids = getattr(self, "site_ids", None)
+        if ids is not None:
+            out.site_ids = [ids[int(i)] for i in keep]
         return out
 
 
@@ -318,6 +354,33 @@ class NativeBamJobs:
         out.file_id = arr(b.file_id, n, np.uint32)
         out.bases = arr(b.bases, n, np.uint32)
         return out
+
+    def references(self):
+        """dyn_bam_references: (names, lengths uint32[n_ref]) of the header's reference sequences; n_ref = 0 for an unaligned BAM"""
+        C, N = self._C, self._N
+        n, names, off, lens = C.c_uint64(), C.c_void_p(), N.c_u64_p(), N.c_u32_p()
+        rc = self._L.dyn_bam_references(self._h, C.byref(n), C.byref(names), C.byref(off), C.byref(lens))
+        if rc != N.DYN_OK:
+            raise ValueError("dyn_bam_references failed")
+        k = int(n.value)
+        if k == 0:
+            return [], np.zeros(0, dtype=np.uint32)
+        raw = C.string_at(names, int(off[k]))
+        return [x.decode() for x in raw.split(b"\0")[:k]], np.array(lens[:k], dtype=np.uint32)
+
+    def alignment(self) -> dict:
+        """dyn_bam_alignment: the mapping of the batch ``next`` returned last, in its order -- ``flag`` (uint32), ``ref_id``,
+        ``pos`` (int32, 0-based, -1 = unmapped), ``cigar`` (BAM's words of len << 4 | op, back to back, stored orientation) and
+        ``cigar_off`` (uint64 [n + 1]); copies"""
+        C, N = self._C, self._N
+        a = N.DynJobAlignment()
+        rc = self._L.dyn_bam_alignment(self._h, C.byref(a))
+        if rc != N.DYN_OK:
+            raise ValueError("dyn_bam_alignment failed")
+        n = int(a.n)
+        off = np.array(a.cigar_off[:n + 1], dtype=np.uint64)
+        return {"flag": np.array(a.flag[:n], dtype=np.uint32), "ref_id": np.array(a.ref_id[:n], dtype=np.int32),
+                "pos": np.array(a.pos[:n], dtype=np.int32), "cigar": np.array(a.cigar[:int(off[-1])], dtype=np.uint32), "cigar_off": off}
 
     def close(self) -> None:
         if self._h:

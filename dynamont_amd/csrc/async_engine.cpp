@@ -206,6 +206,18 @@ std::shared_ptr<BatchGroup> Pipeline::merge(const std::vector<dyn_batch*>& ticke
     }
     grp->seqs.append(t->in_seqs + t->in_seq_offsets[0], t->in_seq_offsets[t->n] - t->in_seq_offsets[0]);
   }
+  // the members' site ids, concatenated exactly as their sequences are (DYN_SITE_NONE for a member that staged none): only when a
+  // member that asked for the per-site summary staged any
+  bool any_sites = false;
+  for (dyn_batch* t : tickets) any_sites |= t->want.site_summary && t->in_site_ids && t->n;
+  if (any_sites) {
+    grp->site_ids.reserve(grp->seqs.size());
+    for (dyn_batch* t : tickets) {
+      const uint64_t len = t->n ? t->in_seq_offsets[t->n] - t->in_seq_offsets[0] : 0;
+      if (t->in_site_ids) grp->site_ids.insert(grp->site_ids.end(), t->in_site_ids, t->in_site_ids + len);
+      else grp->site_ids.insert(grp->site_ids.end(), len, (uint32_t)DYN_SITE_NONE);
+    }
+  }
   dyn_batch* g = new dyn_batch();
   g->a = a;
   attach_cache(g);
@@ -223,7 +235,16 @@ std::shared_ptr<BatchGroup> Pipeline::merge(const std::vector<dyn_batch*>& ticke
     if (!t->n) continue;
     if (t->want.kmer_summary) add_range(g->ks_ranges, t);
     if (t->want.band_margin) add_range(g->bm_ranges, t);
+    if (any_sites && t->want.site_summary && t->in_site_ids) {
+      add_range(g->ss_ranges, t);
+      if (!g->ss_table) {  // (the setter waits for the jobs in flight before it replaces the table: the members saw one table)
+        g->ss_table = t->ss_table;
+        g->ss_num_sites = t->ss_num_sites;
+      }
+    }
   }
+  g->want.site_summary = !g->ss_ranges.empty();
+  if (any_sites) g->in_site_ids = grp->site_ids.data();
   g->want.kmer_summary = !g->ks_ranges.empty();
   g->want.band_margin = !g->bm_ranges.empty();
   g->in_sig_offsets = grp->sig_offsets.data();
@@ -370,7 +391,8 @@ void Pipeline::close_idle_session() {
 int Pipeline::front_stage(dyn_batch* b) {
   const uint64_t n = b->n;
   const double t0 = now_ms();
-  int rc = host_prepare(b, a->model, true, n, b->in_sig_offsets, b->in_seqs, b->in_seq_offsets, &helpers);
+  int rc = host_prepare(b, a->model, true, n, b->in_sig_offsets, b->in_seqs, b->in_seq_offsets, &helpers,
+                        (b->want.site_summary && b->job == DynJob::AlignFull) ? b->in_site_ids : nullptr);
   const double t1 = now_ms();
   if (rc != DYN_OK) {
     b->error = last_error_of(a);
@@ -491,6 +513,8 @@ int Pipeline::front_stage(dyn_batch* b) {
   }
   if (b->total_cols)
     P_TRY(b, hipMemcpyAsync(b->d_kmers.p, b->h_kmers.p, b->total_cols * 4, hipMemcpyHostToDevice, a->s_in));
+  if (b->total_cols && b->has_sites)
+    P_TRY(b, hipMemcpyAsync(b->d_sites.p, b->h_sites.p, b->total_cols * 4, hipMemcpyHostToDevice, a->s_in));
   P_TRY(b, hipEventRecord(b->ev_in, a->s_in));
   const double t4 = now_ms();
   // The resident read queue (engine.hpp: Session)? Then the ticket's small kernels run on the copy-in stream, behind its
@@ -744,7 +768,20 @@ namespace {
 int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const uint64_t* sig_offsets,
                   const char* seqs, const uint64_t* seq_offsets, DynJob job, dyn_align_out* oa,
                   dyn_train_out* ot, double* pooled, dyn_batch** ticket, const RawSource* rs = nullptr) {
-  if (!a || !ticket || !sig_offsets || !seq_offsets || (n_reads && ((!signals && !rs) || !seqs))) return DYN_ERR_INVALID_ARGUMENT;
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  // the ids dyn_aligner_stage_site_ids left are this call's, whatever becomes of it
+  const uint32_t* site_ids = nullptr;
+  unsigned long long* ss_table = nullptr;
+  uint64_t ss_num_sites = 0;
+  int staged_rc = DYN_OK;
+  {
+    std::lock_guard<std::mutex> lk(a->mu);
+    staged_rc = take_staged_sites(a, "dyn_batch_align_async", n_reads, seq_offsets, &site_ids);
+    ss_table = a->d_site.as<unsigned long long>();  // the table as it stands at this submission
+    ss_num_sites = a->num_sites;
+  }
+  if (!ticket || !sig_offsets || !seq_offsets || (n_reads && ((!signals && !rs) || !seqs))) return DYN_ERR_INVALID_ARGUMENT;
+  if (staged_rc != DYN_OK) return staged_rc;
   RawSource rs_local;
   if (rs) {  // DYN_RAW_SCATTERED: `raw` is a table of n_reads pointers
     rs_local = *rs;
@@ -790,6 +827,9 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
   b->async = true;
   b->job = job;
   b->want = want;
+  b->in_site_ids = site_ids;
+  b->ss_table = ss_table;
+  b->ss_num_sites = ss_num_sites;
   b->in_signals = signals;
   if (rs) {
     b->has_raw = true;

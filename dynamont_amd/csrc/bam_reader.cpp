@@ -84,6 +84,13 @@ struct dyn_bam_reader {
   std::vector<uint8_t> sid16, sid_ok;
   std::unordered_map<std::string, uint32_t> file_ids;
   std::string tmp;
+  // the header's reference sequences, and the mapping columns of the last batch (dyn_bam_references, dyn_bam_alignment)
+  std::string ref_names;
+  std::vector<uint64_t> ref_name_off{0};
+  std::vector<uint32_t> ref_len;
+  std::vector<uint32_t> a_flag, a_cigar;
+  std::vector<int32_t> a_ref, a_pos;
+  std::vector<uint64_t> a_cigar_off{0};
 
   ~dyn_bam_reader() {
     for (auto& f : ahead) f.wait();
@@ -253,6 +260,11 @@ struct dyn_bam_reader {
         if (err.empty()) err = path + ": truncated BAM header";
         return false;
       }
+      const char* rname = reinterpret_cast<const char*>(buf.data() + bpos + 4);
+      ref_names.append(rname, strnlen(rname, l_name));
+      ref_names.push_back('\0');
+      ref_name_off.push_back(ref_names.size());
+      ref_len.push_back(le32(buf.data() + bpos + 4 + l_name));
       bpos += 8 + l_name;
     }
     header_done = true;
@@ -389,6 +401,8 @@ static int bam_next_impl(dyn_bam_reader* r, uint64_t max_reads, uint32_t flags, 
   r->name_off.assign(1, 0); r->seq_off.assign(1, 0); r->sid_off.assign(1, 0); r->file_off.assign(1, 0);
   r->sm.clear(); r->sd.clear(); r->start.clear(); r->end.clear(); r->file_id.clear(); r->bases.clear(); r->sid16.clear(); r->sid_ok.clear();
   r->file_ids.clear();
+  r->a_flag.clear(); r->a_ref.clear(); r->a_pos.clear(); r->a_cigar.clear();
+  r->a_cigar_off.assign(1, 0);
   uint64_t n = 0;
   std::string e;
   while (n < max_reads) {
@@ -514,6 +528,12 @@ static int bam_next_impl(dyn_bam_reader* r, uint64_t max_reads, uint32_t flags, 
     r->start.push_back(t.sp + t.ts);
     r->end.push_back(t.sp + t.ns);
     r->bases.push_back((uint32_t)l_seq);
+    // the mapping, as the record holds it (the CIGAR's 4 * n_cigar bytes lie inside the record: checked above)
+    r->a_flag.push_back(le16(d + 14));
+    r->a_ref.push_back((int32_t)le32(d));
+    r->a_pos.push_back((int32_t)le32(d + 4));
+    for (size_t c = 0; c < n_cigar; ++c) r->a_cigar.push_back(le32(d + 32 + l_read_name + 4 * c));
+    r->a_cigar_off.push_back(r->a_cigar.size());
     // sequence: two bases per byte, high nibble first (a 256-entry table of base pairs); RNA: reversed, the pad in front
     // unless the read brings it
     r->tmp.resize(2 * nb + 2);
@@ -553,6 +573,26 @@ static int bam_next_impl(dyn_bam_reader* r, uint64_t max_reads, uint32_t flags, 
   out->seqs_bytes = r->seqs.size();
   out->signal_ids_bytes = r->sids.size();
   out->files_bytes = r->files.size();
+  return DYN_OK;
+}
+
+int dyn_bam_references(dyn_bam_reader* r, uint64_t* n_ref, const char** names, const uint64_t** name_off, const uint32_t** lengths) {
+  if (!r || !n_ref) return DYN_ERR_INVALID_ARGUMENT;
+  *n_ref = r->ref_len.size();
+  if (names) *names = r->ref_names.data();
+  if (name_off) *name_off = r->ref_name_off.data();
+  if (lengths) *lengths = r->ref_len.data();
+  return DYN_OK;
+}
+
+int dyn_bam_alignment(dyn_bam_reader* r, dyn_job_alignment* out) {
+  if (!r || !out) return DYN_ERR_INVALID_ARGUMENT;
+  out->n = r->a_flag.size();
+  out->flag = r->a_flag.data();
+  out->ref_id = r->a_ref.data();
+  out->pos = r->a_pos.data();
+  out->cigar = r->a_cigar.data();
+  out->cigar_off = r->a_cigar_off.data();
   return DYN_OK;
 }
 

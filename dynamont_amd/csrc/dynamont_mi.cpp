@@ -58,13 +58,13 @@ hipError_t copy_out(dyn_aligner* a, void* dst, const void* src, size_t bytes) {
 namespace dyneng {
 void attach_cache(dyn_batch* b) {
   dyneng::BufCache* c = &b->a->cache;
-  for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
+  for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_sites, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
                     &b->d_pathn, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
                     &b->d_resc_st, &b->d_resc_pp, &b->d_resc_pathn, &b->d_resc_segrow})
     d->cache = c;
   for (OutputBuf& o : b->out) o.d.cache = c;
-  for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref, &b->h_resc}) h->cache = c;
+  for (PinnedBuf* h : {&b->h_kmers, &b->h_sites, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref, &b->h_resc}) h->cache = c;
 }
 
 int need_device(dyn_aligner* a) {
@@ -86,7 +86,7 @@ int need_device(dyn_aligner* a) {
 // Every read that passes validateInput gets its slice of the flat k-mer array up front; a read that
 // then fails in sequenceToKmers ("Invalid nucleotide") simply leaves its slice unused.
 int host_prepare(dyn_batch* b, const PoreModel& m, bool pinned, uint64_t n, const uint64_t* sig_offsets,
-                 const char* seqs, const uint64_t* seq_offsets, HelperPool* pool) {
+                 const char* seqs, const uint64_t* seq_offsets, HelperPool* pool, const uint32_t* site_ids) {
   b->n = n;
   b->reads.assign(n, HostRead());
   b->n_wide = 0;
@@ -130,6 +130,23 @@ int host_prepare(dyn_batch* b, const PoreModel& m, bool pinned, uint64_t n, cons
     b->h_kmers.bytes = 0;  // marks "malloc'ed": freed by the caller of host_prepare
     if (!b->h_kmers.p) return DYN_ERR_OUT_OF_MEMORY;
   }
+  // the site id of every output row beside its k-mer code: row j of a read is the row whose sequence_pos is j + k / 2
+  // (segment_kernels.hpp), so it takes the id of that base. ids[0] belongs to the batch's first character (seq_offsets[0]).
+  b->has_sites = pinned && site_ids != nullptr;
+  if (b->has_sites) {
+    if (b->h_sites.ensure(std::max<uint64_t>(4, flat * 4)) != hipSuccess) {
+      (void)hipGetLastError();
+      if (b->a) b->a->last_error = "out of pinned host memory for the site ids";
+      return DYN_ERR_OUT_OF_MEMORY;
+    }
+    uint32_t* hs = b->h_sites.as<uint32_t>();
+    const uint64_t half = (uint64_t)m.k / 2;
+    for (uint64_t i = 0; i < n; ++i) {
+      const HostRead& r = b->reads[i];
+      if (r.status != DYN_READ_OK) continue;
+      std::memcpy(hs + r.flat_off, site_ids + (seq_offsets[i] - seq_offsets[0]) + half, r.kc * sizeof(uint32_t));
+    }
+  }
   int32_t* km = b->h_kmers.as<int32_t>();
   auto encode_range = [&](uint64_t lo, uint64_t hi) {
     for (uint64_t i = lo; i < hi; ++i) {
@@ -161,6 +178,7 @@ static int alloc_batch_buffers_once(dyn_batch* b, uint64_t total_sig) {
   dyn_aligner* a = b->a;
   HIP_TRY(a, b->d_sig.ensure(std::max<uint64_t>(8, total_sig * 8)));
   HIP_TRY(a, b->d_kmers.ensure(std::max<uint64_t>(4, b->total_cols * 4)));
+  if (b->has_sites) HIP_TRY(a, b->d_sites.ensure(std::max<uint64_t>(4, b->total_cols * 4)));
   HIP_TRY(a, b->d_par.ensure(std::max<uint64_t>(sizeof(Emis), b->total_cols * sizeof(Emis))));
   HIP_TRY(a, b->d_state.ensure(std::max<uint64_t>(sizeof(ReadState), b->n * sizeof(ReadState))));
   HIP_TRY(a, b->d_rows.ensure(std::max<uint64_t>(sizeof(SegRow), b->capacity * sizeof(SegRow))));
@@ -431,6 +449,7 @@ void dyn_aligner_destroy(dyn_aligner* a) {
     a->d_model.release();
     a->d_sptab.release();
     a->d_ksum.release();
+    a->d_site.release();
     park_pool_buffer(a->device, 0, a->ws);
     park_pool_buffer(a->device, 1, a->lpe);
     park_pool_buffer(a->device, 2, a->bits);
@@ -719,9 +738,149 @@ int dyn_aligner_kmer_summary_reset(dyn_aligner* a) {
   return DYN_OK;
 }
 
+// ---- the per-site level summary (site_summary_kernels.hpp) -------------------------------------------------------------------
+int dyn_aligner_set_site_summary(dyn_aligner* a, uint64_t num_sites) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  auto fail = [&](const std::string& msg) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = "dyn_aligner_set_site_summary: " + msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  };
+  if (a->ntk) return fail("modes ntk / resquiggle have no align(calc_probabilities = 1) job to summarise");
+  if (num_sites >= (uint64_t)DYN_SITE_NONE) return fail("num_sites " + std::to_string(num_sites) + " is not below DYN_SITE_NONE (4294967295)");
+  Pipeline* pipe = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (int rc = need_device(a)) return rc;
+    if (num_sites == 0) {  // off: the table stays for the fetch
+      a->opt.site_summary = false;
+      return DYN_OK;
+    }
+    if (num_sites == a->num_sites && a->d_site.p) {
+      a->opt.site_summary = true;
+      return DYN_OK;
+    }
+    // off before the lock is dropped: a ticket another thread submits while this call drains takes no part in the summary, so
+    // none can add to the table that is about to be freed
+    a->opt.site_summary = false;
+    pipe = a->pipe.get();
+  }
+  // another size: the jobs in flight hold the old table's address (snapshot at their submission) -- they finish first
+  if (pipe) pipe->drain();
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = session_quiesce(a)) return rc;  // (hipFree waits for the whole device: no resident wave may be waiting for tickets)
+  HIP_TRY(a, hipStreamSynchronize(a->stream));
+  HIP_TRY(a, hipStreamSynchronize(a->s_out));
+  a->opt.site_summary = false;
+  a->d_site.release();
+  a->num_sites = 0;
+  const uint64_t bytes = ((uint64_t)dynk::SS_FIELDS * num_sites + (uint64_t)dynk::SS_TOTALS) * sizeof(uint64_t);
+  if (a->mem_budget && bytes > a->mem_budget) {
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = "dyn_aligner_set_site_summary: the table of " + std::to_string(num_sites) + " sites (" + std::to_string(bytes) +
+                    " bytes) does not fit dyn_aligner_set_mem_budget's " + std::to_string(a->mem_budget) + " bytes";
+    return DYN_ERR_OUT_OF_MEMORY;
+  }
+  const hipError_t e = a->d_site.ensure(bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = "dyn_aligner_set_site_summary: no device memory for the table of " + std::to_string(num_sites) + " sites (" +
+                    std::to_string(bytes) + " bytes): " + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? DYN_ERR_OUT_OF_MEMORY : DYN_ERR_DEVICE;
+  }
+  HIP_TRY(a, hipMemsetAsync(a->d_site.p, 0, bytes, a->s_get));
+  HIP_TRY(a, hipStreamSynchronize(a->s_get));
+  a->num_sites = num_sites;
+  a->opt.site_summary = true;
+  return DYN_OK;
+}
+
+int dyn_aligner_stage_site_ids(dyn_aligner* a, const uint32_t* site_ids, uint64_t count) {
+  if (!a || (count && !site_ids)) return DYN_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(a->mu);
+  a->staged_sites = site_ids;
+  a->staged_count = count;
+  a->sites_staged = true;
+  return DYN_OK;
+}
+
+namespace {
+// every kernel that adds to the table runs on the compute stream (one launch per batch) or on the copy-out stream (tickets of a
+// resident session): the table of the jobs that have completed is behind both
+int site_summary_quiet(dyn_aligner* a, const char* who) {
+  if (int rc = need_device(a)) return rc;
+  if (!a->d_site.p) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = std::string(who) + ": dyn_aligner_set_site_summary(a, num_sites > 0) was never called on this handle";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  HIP_TRY(a, hipStreamSynchronize(a->stream));
+  HIP_TRY(a, hipStreamSynchronize(a->s_out));
+  return DYN_OK;
+}
+}  // namespace
+
+int dyn_aligner_site_summary_fetch(dyn_aligner* a, uint64_t lo, uint64_t hi, uint64_t* n_rows, uint64_t* n_samples,
+                                   uint64_t* dwell_sq, uint64_t* m1_lo, uint64_t* m1_hi, uint64_t* m2_lo, uint64_t* m2_hi,
+                                   uint64_t totals[5]) {
+  if (!a || !totals) return DYN_ERR_INVALID_ARGUMENT;
+  uint64_t* cols[7] = {n_rows, n_samples, dwell_sq, m1_lo, m1_hi, m2_lo, m2_hi};
+  if (lo < hi)
+    for (uint64_t* c : cols)
+      if (!c) return DYN_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = site_summary_quiet(a, "dyn_aligner_site_summary_fetch")) return rc;
+  if (lo > hi || hi > a->num_sites) {
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = "dyn_aligner_site_summary_fetch: [" + std::to_string(lo) + ", " + std::to_string(hi) + ") is not a range of the table's " +
+                    std::to_string(a->num_sites) + " sites";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  const uint64_t F = (uint64_t)dynk::SS_FIELDS, step = 1ull << 20;  // 56 MB of staging at a time
+  std::vector<uint64_t> h(F * std::min(step, hi - lo) + 1);
+  const uint64_t* table = a->d_site.as<uint64_t>();
+  for (uint64_t s0 = lo; s0 < hi; s0 += step) {
+    const uint64_t cnt = std::min(step, hi - s0);
+    HIP_TRY(a, copy_out(a, h.data(), table + F * s0, F * cnt * sizeof(uint64_t)));
+    for (uint64_t c = 0; c < cnt; ++c)
+      for (uint64_t f = 0; f < F; ++f) cols[f][s0 - lo + c] = h[F * c + f];
+  }
+  HIP_TRY(a, copy_out(a, totals, table + F * a->num_sites, (uint64_t)dynk::SS_TOTALS * sizeof(uint64_t)));
+  return DYN_OK;
+}
+
+int dyn_aligner_site_summary_reset(dyn_aligner* a) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = site_summary_quiet(a, "dyn_aligner_site_summary_reset")) return rc;
+  HIP_TRY(a, hipMemsetAsync(a->d_site.p, 0, ((uint64_t)dynk::SS_FIELDS * a->num_sites + (uint64_t)dynk::SS_TOTALS) * sizeof(uint64_t), a->s_get));
+  HIP_TRY(a, hipStreamSynchronize(a->s_get));
+  return DYN_OK;
+}
+
 }  // extern "C"
 
 namespace dyneng {
+
+int take_staged_sites(dyn_aligner* a, const char* api, uint64_t n_reads, const uint64_t* seq_offsets, const uint32_t** ids) {
+  *ids = nullptr;
+  if (!a->sites_staged) return DYN_OK;
+  const uint32_t* p = a->staged_sites;
+  const uint64_t count = a->staged_count;
+  a->sites_staged = false;
+  a->staged_sites = nullptr;
+  a->staged_count = 0;
+  const uint64_t span = (n_reads && seq_offsets) ? seq_offsets[n_reads] - seq_offsets[0] : 0;
+  if (count != span) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = std::string(api) + ": dyn_aligner_stage_site_ids staged " + std::to_string(count) + " ids, the batch's sequences hold " +
+                    std::to_string(span) + " characters";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  *ids = p;
+  return DYN_OK;
+}
 
 // Which reads need the reference's arithmetic bit for bit, and for how many forward rows (dyn_aligner_set_strict, mode 1).
 // A STRUCTURAL TIE: two neighbouring lattice columns with the same emission parameters (equal k-mers -- the polyA pad
@@ -843,9 +1002,14 @@ namespace {
 int create_impl(dyn_aligner* a, uint64_t n_reads, const double* signals, const RawSource* rs,
                 const uint64_t* sig_offsets, const char* seqs, const uint64_t* seq_offsets,
                 dyn_batch** out) {
-  if (!a || !out) return DYN_ERR_INVALID_ARGUMENT;
-  *out = nullptr;
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lk(a->mu);
+  // the ids dyn_aligner_stage_site_ids left are this call's, whatever becomes of it
+  const uint32_t* site_ids = nullptr;
+  const int src = take_staged_sites(a, "dyn_batch_create", n_reads, seq_offsets, &site_ids);
+  if (!out) return DYN_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  if (src != DYN_OK) return src;
   if (a->host_only) {
     // A handle without a device gets the read table alone (validateInput + sequenceToKmers in plain memory): what the host-side
     // checks of a batch need (dyn_batch_set_guide). Every job and every getter of such a batch reports the missing device.
@@ -874,7 +1038,7 @@ int create_impl(dyn_aligner* a, uint64_t n_reads, const double* signals, const R
     dyn_batch_destroy(b);
     return code;
   };
-  rc = host_prepare(b, a->model, true, n_reads, sig_offsets, seqs, seq_offsets, nullptr);
+  rc = host_prepare(b, a->model, true, n_reads, sig_offsets, seqs, seq_offsets, nullptr, site_ids);
   if (rc != DYN_OK) return cleanup(rc);
   const double t_prepared = now_ms();
 #define B_TRY(expr)                                                                        \
@@ -920,6 +1084,7 @@ int create_impl(dyn_aligner* a, uint64_t n_reads, const double* signals, const R
   }
   if (b->total_cols) {
     B_TRY(hipMemcpyAsync(b->d_kmers.p, b->h_kmers.p, b->total_cols * 4, hipMemcpyHostToDevice, a->stream));
+    if (b->has_sites) B_TRY(hipMemcpyAsync(b->d_sites.p, b->h_sites.p, b->total_cols * 4, hipMemcpyHostToDevice, a->stream));
     dynk::launch_prep_params(b->d_kmers.as<int32_t>(), a->d_model.as<Emis>(), b->d_par.as<Emis>(), b->total_cols, (uint32_t)a->model.num_kmers, a->stream);
     B_TRY(hipGetLastError());
   }
@@ -988,13 +1153,13 @@ void dyn_batch_destroy(dyn_batch* b) {
     std::free(b->h_kmers.p);
     b->h_kmers.p = nullptr;
   }
-  for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
+  for (DevBuf* d : {&b->d_sig, &b->d_kmers, &b->d_sites, &b->d_par, &b->d_state, &b->d_rows, &b->d_segrow, &b->d_medhi,
                     &b->d_medlo, &b->d_descs, &b->d_colw, &b->d_cols1, &b->d_cols2, &b->d_trans, &b->d_pooled, &b->d_poolwork, &b->d_pooltemp, &b->d_pp,
                     &b->d_pathn, &b->d_bm, &b->d_sig0, &b->d_rs, &b->d_norm, &b->d_meta, &b->d_tctl, &b->d_arena, &b->d_guide, &b->d_gref, &b->d_resc,
                     &b->d_resc_st, &b->d_resc_pp, &b->d_resc_pathn, &b->d_resc_segrow})
     d->release();
   for (OutputBuf& o : b->out) o.d.release();
-  for (PinnedBuf* h : {&b->h_kmers, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref, &b->h_resc}) h->release();
+  for (PinnedBuf* h : {&b->h_kmers, &b->h_sites, &b->h_descs, &b->h_state, &b->h_rows, &b->h_stats, &b->h_sig, &b->h_gdescs, &b->h_gref, &b->h_resc}) h->release();
   for (hipEvent_t e : b->events) (void)hipEventDestroy(e);
   for (hipEvent_t e : {b->ev_in, b->ev_done, b->ev_out})
     if (e) (void)hipEventDestroy(e);
@@ -1276,6 +1441,8 @@ int run_job_sync(dyn_batch* b, DynJob job, bool guided_train = false) {
     int rc = need_device(a);
     if (rc != DYN_OK) return rc;
     b->want = want;
+    b->ss_table = a->d_site.as<unsigned long long>();  // the table as it stands at this submission
+    b->ss_num_sites = a->num_sites;
     rc = enqueue_job(b, job);
     if (rc != DYN_OK) {
       (void)hipStreamSynchronize(a->stream);

@@ -136,6 +136,7 @@ struct JobOptions {
   bool event_stats = false;     // dyn_aligner_set_event_stats
   int rescale_iters = 0;        // dyn_aligner_set_rescale (0 .. 8)
   bool kmer_summary = false;    // dyn_aligner_set_kmer_summary
+  bool site_summary = false;    // dyn_aligner_set_site_summary (num_sites > 0)
   bool band_margin = false;     // dyn_aligner_set_band_margin
   int segment_scores = 0;       // dyn_aligner_set_segment_scores (window, 0 = off)
   int border_confidence = 0;    // dyn_aligner_set_border_confidence (window, 0 = off)
@@ -148,7 +149,7 @@ struct JobOptions {
   // May tickets x and y share ONE launch (Pipeline::merge)? Three kinds of fields:
   //   launch-wide: event_stats, rescale_iters, segment_scores, border_confidence, border_interval, soft_levels -- one value per launch, so the
   //                members must agree; the launch's batch takes them from its first member
-  //   per-ticket:  kmer_summary, band_margin -- not compared: the launch's batch lists the read ranges of the members that asked
+  //   per-ticket:  kmer_summary, site_summary, band_margin -- not compared: the launch's batch lists the read ranges of the members that asked
   //   alone:       posterior_samples (the read's index in its OWN ticket keys the random stream), auto_guide_hw (a guide of its own
   //                and the banded-lattice kernel), rescue_hw (its list of reads to re-align is its own) -- such a ticket never merges
   bool merges() const { return posterior_samples == 0 && auto_guide_hw == 0 && rescue_hw == 0; }
@@ -216,6 +217,14 @@ struct dyn_aligner {
   dyneng::DevBuf band_arena;
   dyneng::DevBuf d_ksum;      // [6 num_kmers + 4] u64: the per-k-mer accumulator and its totals (kmer_summary_kernels.hpp),
                               // allocated and zeroed by the first dyn_aligner_set_kmer_summary(a, 1)
+  // the per-site table (site_summary_kernels.hpp): [7 num_sites + 5] u64, allocated and zeroed by dyn_aligner_set_site_summary(a,
+  // num_sites > 0), kept until the setter names another size; a job snapshots pointer and size at its submission
+  dyneng::DevBuf d_site;
+  uint64_t num_sites = 0;
+  // dyn_aligner_stage_site_ids: the caller's ids for the NEXT batch-creating call on this handle (consumed by it, whatever its outcome)
+  const uint32_t* staged_sites = nullptr;
+  uint64_t staged_count = 0;
+  bool sites_staged = false;
   bool ntk = false;     // created with mode "resquiggle" / "ntk"
   std::string last_error;
   // grow-only lattice workspace pool, reused across batches (only ever touched by work on `stream`,
@@ -247,6 +256,11 @@ struct dyn_aligner {
 };
 
 namespace dyneng {
+// what dyn_aligner_set_mem_budget leaves once the per-site table is taken off (0: no budget was set)
+inline uint64_t mem_budget_left(const dyn_aligner* a) {
+  if (!a->mem_budget) return 0;
+  return a->mem_budget > a->d_site.bytes ? a->mem_budget - a->d_site.bytes : 1;
+}
 // what a session is launched with (session_choose, session.cpp)
 struct SessionGeom {
   bool ok = false;
@@ -298,6 +312,8 @@ struct dyn_batch {
   uint64_t n = 0;
   std::vector<HostRead> reads;
   dyneng::PinnedBuf h_kmers;   // flat int32 codes, ok reads only
+  dyneng::PinnedBuf h_sites;   // flat uint32 site ids of the output rows, ok reads only (row j of a read: the id of base j + k / 2);
+                               // filled by host_prepare when the batch has ids (has_sites)
   uint64_t capacity = 0;       // sum of kc over ALL reads with L >= k (segment rows)
   uint64_t total_cols = 0;     // sum of kc over ok reads
   uint32_t max_T = 0, max_N = 0;
@@ -318,6 +334,15 @@ struct dyn_batch {
   // per-k-mer summary and band-margin diagnostics (want.kmer_summary, want.band_margin): a merged launch's batch lists the read
   // ranges of the members that asked (JobOptions::same_launch does not look at the two switches)
   std::vector<std::pair<uint32_t, uint32_t>> ks_ranges, bm_ranges;
+  // per-site summary (want.site_summary): the caller's per-base ids, packed like the sequences (nullptr: none staged -- the job
+  // adds nothing), the per-row ids on the device, the handle's table as it stood at submission, and for a merged launch the read
+  // ranges of the members that asked AND staged ids
+  const uint32_t* in_site_ids = nullptr;
+  bool has_sites = false;
+  dyneng::DevBuf d_sites;
+  unsigned long long* ss_table = nullptr;
+  uint64_t ss_num_sites = 0;
+  std::vector<std::pair<uint32_t, uint32_t>> ss_ranges;
   dyneng::DevBuf d_bm;                         // [3][n] uint32 low / high / edge_rows (band_margin_kernels.hpp), when asked for
   bool bm_ready = false;                       // the last job computed the margins into d_bm
   dyneng::PinnedBuf h_descs, h_state, h_rows;  // h_state/h_rows: D2H targets of the asynchronous path
@@ -413,6 +438,7 @@ struct BatchGroup {
   std::vector<double> shift, scale;
   std::vector<float> cal_offset, cal_scale;
   std::string seqs;
+  std::vector<uint32_t> site_ids;       // the members' per-base ids, concatenated like seqs (DYN_SITE_NONE for members without)
   ~BatchGroup();
 };
 
@@ -430,8 +456,13 @@ void park_masked_stream(int device, hipStream_t s);
 void attach_cache(dyn_batch* b);
 // validateInput + sequenceToKmers of every read; fills b->reads / b->h_kmers / capacity / max_T / max_N
 // (pinned: k-mer codes go to pinned memory for an asynchronous H2D; false = plain malloc, no HIP call)
+// site_ids: the caller's per-base site ids, packed like seqs (pinned batches only): b->h_sites gets the per-row ids beside the codes
 int host_prepare(dyn_batch* b, const dynhost::PoreModel& m, bool pinned, uint64_t n_reads,
-                 const uint64_t* sig_offsets, const char* seqs, const uint64_t* seq_offsets, HelperPool* pool);
+                 const uint64_t* sig_offsets, const char* seqs, const uint64_t* seq_offsets, HelperPool* pool,
+                 const uint32_t* site_ids = nullptr);
+// what dyn_aligner_stage_site_ids left for the batch-creating call `api` whose sequences span seq_offsets[0 .. n]: consumed here
+// whatever the outcome. *ids = nullptr: nothing was staged. DYN_ERR_INVALID_ARGUMENT (text in last_error): the count differs.
+int take_staged_sites(dyn_aligner* a, const char* api, uint64_t n_reads, const uint64_t* seq_offsets, const uint32_t** ids);
 // allocate the per-batch device buffers (from the handle's cache)
 int alloc_batch_buffers(dyn_batch* b, uint64_t total_sig);
 // enqueue every kernel of `job` on the handle's compute stream without synchronising the host
@@ -457,6 +488,11 @@ int session_recover(dyn_batch* b, bool* republished);
 // what launch_segments and launch_kmer_summary get for this batch's align(calc = 1) job: one entry per range of reads whose
 // ticket asked for the summary (empty: none did)
 std::vector<dynk::KmerSummary> kmer_summary_args(const dyn_batch* b);
+// the same for the per-site summary (empty: none asked, or none of those that asked staged ids)
+std::vector<dynk::SiteSummary> site_summary_args(const dyn_batch* b);
+// launch_site_summary for every entry of site_summary_args, behind the per-segment kernels on `s`
+void enqueue_site_summary(const dyn_batch* b, const dynk::ReadDesc* descs, int n_reads, uint32_t max_N, const dynk::ReadState* st,
+                          const dynk::TraceBuffers& tb, hipStream_t s);
 // the same for the band margins (b->d_bm must hold 3 * n uint32: band_margin_prepare)
 std::vector<dynk::BandMargin> band_margin_args(const dyn_batch* b);
 // bm_ready and the room for the margins of an align(calc = 1) job of this batch / ticket

@@ -17,75 +17,24 @@
 //   k_ksum_short  one thread per OUTPUT row (not per lattice row): block (read, chunk of 256 rows)
 //   k_ksum_long   one 256-thread block per read that has a longer segment: lanes sum chunks in parallel, lane 0 adds the
 //                 chunk sums in order (the chunk loop wraps beyond 256 chunks, segments above 16 384 samples)
+// The chunked sums, the double -> 128-bit conversion and the 128-bit add are exact_sum_kernels.hpp (shared with the per-site
+// summary, site_summary_kernels.hpp).
 // Footprint: 256 threads, 4 KB of static LDS (k_ksum_long), no scratch -- they run beside a resident workgroup.
 #pragma once
 
+#include "exact_sum_kernels.hpp"
 #include "nt_kernels.hpp"
 
 namespace dynk {
 
 constexpr int KS_SHORT_MAX = 256;
-constexpr int KS_CHUNK = 64;
+constexpr int KS_CHUNK = XS_CHUNK;
 constexpr int KS_FIELDS = 6;  // per k-mer: n_segments, n_samples, q1_lo, q1_hi, q2_lo, q2_hi
 constexpr int KS_TOTALS = 4;  // reads_ok, segments, samples, skipped_segments
-
-__device__ __forceinline__ void ks_chunked_sums(const double* __restrict__ x, int L, double& s1, double& s2) {
-  double a1 = 0.0, a2 = 0.0;
-  for (int c0 = 0; c0 < L; c0 += KS_CHUNK) {
-    const int c1 = min(c0 + KS_CHUNK, L);
-    double v = x[c0];
-    double c1s = v, c2s = __dmul_rn(v, v);
-    for (int j = c0 + 1; j < c1; ++j) {
-      v = x[j];
-      c1s = __dadd_rn(c1s, v);
-      c2s = __dadd_rn(c2s, __dmul_rn(v, v));
-    }
-    a1 = c0 == 0 ? c1s : __dadd_rn(a1, c1s);
-    a2 = c0 == 0 ? c2s : __dadd_rn(a2, c2s);
-  }
-  s1 = a1;
-  s2 = a2;
-}
 
 // does the definition keep the segment? (NaN fails the first comparison)
 __device__ __forceinline__ bool ks_kept(double s1, double s2) {
   return s2 < 18446744073709551616.0 && s2 >= 0.0 && fabs(s1) <= 1.7976931348623157e308;
-}
-
-// an integer-valued double of magnitude below 2^116 as a 128-bit two's complement integer: the significand shifted by the
-// exponent (__double2ll_rn covers |v| < 2^63 only; q2 reaches 2^104)
-__device__ __forceinline__ void ks_to_i128(double v, unsigned long long& lo, unsigned long long& hi) {
-  const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
-  const int e = (int)((bits >> 52) & 0x7ffu);
-  lo = 0;
-  hi = 0;
-  if (e == 0) return;  // +-0 (an integer-valued double is never denormal)
-  const unsigned long long m = (bits & 0x000fffffffffffffull) | 0x0010000000000000ull;
-  const int sh = e - 1075;  // v = m * 2^sh
-  if (sh < 0) {
-    lo = m >> (-sh);  // |v| >= 1: sh >= -52, and the bits shifted out are zero
-  } else if (sh == 0) {
-    lo = m;
-  } else if (sh < 64) {
-    lo = m << sh;
-    hi = m >> (64 - sh);
-  } else {
-    hi = m << (sh - 64);  // sh <= 63 + 52 for every value the definition keeps
-  }
-  if (bits >> 63) {
-    lo = ~lo + 1ull;
-    hi = ~hi + (lo == 0 ? 1ull : 0ull);
-  }
-}
-
-// cell += (hi:lo) mod 2^128: the low limb first, the carry from the value it replaced
-__device__ __forceinline__ void ks_add128(unsigned long long* cell, unsigned long long lo, unsigned long long hi) {
-  unsigned long long up = hi;
-  if (lo) {
-    const unsigned long long old = atomicAdd(cell, lo);
-    up += (old + lo < old) ? 1ull : 0ull;
-  }
-  if (up) atomicAdd(cell + 1, up);
 }
 
 // one segment into its k-mer's cell; returns false when the definition skips it
@@ -95,16 +44,11 @@ __device__ __forceinline__ bool ks_accumulate(const KmerSummary& ks, int32_t cod
   atomicAdd(cell, 1ull);
   atomicAdd(cell + 1, (unsigned long long)L);
   unsigned long long lo, hi;
-  ks_to_i128(rint(__dmul_rn(s1, 1099511627776.0)), lo, hi);
-  ks_add128(cell + 2, lo, hi);
-  ks_to_i128(rint(__dmul_rn(s2, 1099511627776.0)), lo, hi);
-  ks_add128(cell + 4, lo, hi);
+  xs_to_i128(rint(__dmul_rn(s1, 1099511627776.0)), lo, hi);
+  xs_add128(cell + 2, lo, hi);
+  xs_to_i128(rint(__dmul_rn(s2, 1099511627776.0)), lo, hi);
+  xs_add128(cell + 4, lo, hi);
   return true;
-}
-
-__device__ __forceinline__ unsigned long long ks_wave_sum(unsigned long long v) {
-  for (int d = warpSize >> 1; d > 0; d >>= 1) v += __shfl_down(v, d);
-  return v;
 }
 
 __device__ __forceinline__ bool ks_read_wanted(const KmerSummary& ks, const ReadDesc& rd, const ReadState* __restrict__ st) {
@@ -130,7 +74,7 @@ __global__ __launch_bounds__(256) void k_ksum_short(const ReadDesc* __restrict__
     if (L >= 1 && L <= KS_SHORT_MAX && a >= 1 && b <= T) {
       if ((uint32_t)code < ks.num_kmers) {
         double s1, s2;
-        ks_chunked_sums(ks.sig + rd.sig_off + (a - 1), L, s1, s2);  // sample row - 1
+        xs_chunked_sums(ks.sig + rd.sig_off + (a - 1), L, s1, s2);  // sample row - 1
         if (ks_accumulate(ks, code, L, s1, s2)) {
           n_kept = 1;
           n_samp = (unsigned long long)L;
@@ -142,9 +86,9 @@ __global__ __launch_bounds__(256) void k_ksum_short(const ReadDesc* __restrict__
       }
     }
   }
-  n_kept = ks_wave_sum(n_kept);
-  n_samp = ks_wave_sum(n_samp);
-  n_skip = ks_wave_sum(n_skip);
+  n_kept = xs_wave_sum(n_kept);
+  n_samp = xs_wave_sum(n_samp);
+  n_skip = xs_wave_sum(n_skip);
   if ((threadIdx.x & (warpSize - 1)) == 0) {
     if (n_kept) atomicAdd(ks.totals + 1, n_kept);
     if (n_samp) atomicAdd(ks.totals + 2, n_samp);
@@ -179,7 +123,7 @@ __global__ __launch_bounds__(256) void k_ksum_long(const ReadDesc* __restrict__ 
       const int c = c0 + tid;
       if (c < n_chunks) {
         double p1, p2;
-        ks_chunked_sums(xs + c * KS_CHUNK, min(KS_CHUNK, L - c * KS_CHUNK), p1, p2);
+        xs_chunked_sums(xs + c * KS_CHUNK, min(KS_CHUNK, L - c * KS_CHUNK), p1, p2);
         s_p1[tid] = p1;
         s_p2[tid] = p2;
       }

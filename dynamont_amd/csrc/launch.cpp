@@ -303,7 +303,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
   }
 
   // HBM budget for the page pool
-  uint64_t budget = a->mem_budget;
+  uint64_t budget = mem_budget_left(a);
   if (lattice) {
     size_t free_b = 0, total_b = 0;
     HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
@@ -484,7 +484,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     size_t free_b = 0, total_b = 0;
     HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
     uint64_t room = (uint64_t)((double)(free_b + arena_buf.bytes + parked_bytes(a->device)) * 0.8);
-    if (b->guided && a->mem_budget && room > a->mem_budget) room = a->mem_budget;
+    if (b->guided && a->mem_budget && room > mem_budget_left(a)) room = mem_budget_left(a);
     size_t wr = 0;
     for (uint32_t i : wide) {
       const HostRead& r = b->reads[i];
@@ -545,7 +545,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     size_t free_b = 0, total_b = 0;
     HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
     uint64_t room = (uint64_t)((double)(free_b + resc_arena_buf.bytes + parked_bytes(a->device)) * 0.8);
-    if (a->mem_budget && room > a->mem_budget) room = a->mem_budget;
+    if (a->mem_budget && room > mem_budget_left(a)) room = mem_budget_left(a);
     for (size_t k = 0; k < n_all; ++k)
       if (descs[k].T > resc_T_fit && dynk::band_arena_bytes(descs[k].T, b->want.rescue_hw, 1) <= room) resc_T_fit = descs[k].T;
     if (resc_T_fit) {
@@ -887,6 +887,8 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     dynk::launch_segments(q.descs, nr_all, rows_total, max_N, q.st, q.tb, b->d_rows.as<SegRow>(), m.k, a->stream, evc,
                           ks.empty() ? dynk::KmerSummary{} : ks[0], scc, (bm.empty() || b->guided || rescue) ? dynk::BandMargin{} : bm[0]);
     for (size_t k = 1; k < ks.size(); ++k) dynk::launch_kmer_summary(q.descs, nr_all, max_N, q.st, q.tb, ks[k], a->stream);
+    // the per-site summary (likewise once: the last pass's signal, the borders the rescue left)
+    enqueue_site_summary(b, q.descs, nr_all, max_N, q.st, q.tb, a->stream);
     // (under the guide rescue the margins were taken above, in front of the selection: such a job is never a merged launch)
     for (size_t k = b->guided ? 0 : 1; k < bm.size() && !rescue; ++k) {
       if (b->guided) dynk::launch_guided_band_margin(q.descs, nr_all, b->max_T, q.st, q.tb, b->d_guide.as<int32_t>(), (int)b->guide_hw, bm[k], a->stream);
@@ -937,6 +939,28 @@ std::vector<dynk::KmerSummary> kmer_summary_args(const dyn_batch* b) {
     }
   }
   return out;
+}
+
+std::vector<dynk::SiteSummary> site_summary_args(const dyn_batch* b) {
+  std::vector<dynk::SiteSummary> out;
+  if (!b->want.site_summary || !b->ss_table || !b->ss_num_sites || !b->has_sites || !b->d_sites.p) return out;
+  dynk::SiteSummary ss{b->d_sig.as<double>(), b->d_sites.as<uint32_t>(), b->ss_table, b->ss_table + (uint64_t)dynk::SS_FIELDS * b->ss_num_sites,
+                       (uint32_t)b->ss_num_sites, 0u, (uint32_t)b->n};
+  if (b->ss_ranges.empty()) {  // (a merged launch has ids only when a member that asked staged some: its ranges are never empty)
+    out.push_back(ss);
+  } else {
+    for (const auto& r : b->ss_ranges) {
+      ss.read_lo = r.first;
+      ss.read_hi = r.second;
+      out.push_back(ss);
+    }
+  }
+  return out;
+}
+
+void enqueue_site_summary(const dyn_batch* b, const dynk::ReadDesc* descs, int n_reads, uint32_t max_N, const dynk::ReadState* st,
+                          const dynk::TraceBuffers& tb, hipStream_t s) {
+  for (const dynk::SiteSummary& ss : site_summary_args(b)) dynk::launch_site_summary(descs, n_reads, max_N, st, tb, ss, s);
 }
 
 int output_ensure(dyn_batch* b, Output k, int ready) {

@@ -298,6 +298,20 @@ struct KmerSummary {
 };
 void launch_kmer_summary(const ReadDesc* descs, int n_reads, uint32_t max_N, const ReadState* st, const TraceBuffers& tb,
                          const KmerSummary& ks, hipStream_t s);
+// per-site level summary of a run (site_summary.hip, dyn_aligner_set_site_summary); acc == nullptr: not asked for
+constexpr int SS_FIELDS = 7;  // per site: n_rows, n_samples, dwell_sq, m1_lo, m1_hi, m2_lo, m2_hi
+constexpr int SS_TOTALS = 5;  // reads_ok, rows_added, samples_added, rows_without_site, rows_skipped
+struct SiteSummary {
+  const double* sig;          // the signal the read queue aligned (ReadDesc::sig_off counts from here)
+  const uint32_t* sites;      // site id of every output row (ReadDesc::par_off counts from here): row j <-> entry j
+  unsigned long long* acc;    // the handle's table: [num_sites][7] n_rows, n_samples, dwell_sq, m1 lo / hi, m2 lo / hi
+  unsigned long long* totals; // [5] reads_ok, rows_added, samples_added, rows_without_site, rows_skipped
+  uint32_t num_sites;
+  uint32_t read_lo, read_hi;  // the reads [read_lo, read_hi) (ReadDesc::read) contribute: the members of a merged launch
+                              // that asked and staged ids
+};
+void launch_site_summary(const ReadDesc* descs, int n_reads, uint32_t max_N, const ReadState* st, const TraceBuffers& tb,
+                         const SiteSummary& ss, hipStream_t s);
 // per-border segment quality scores (segment_scores.hip, dyn_aligner_set_segment_scores): columns indexed like the output
 // rows, zeroed by the caller; median_delta == nullptr: not asked for
 struct ScoreCols {

@@ -236,7 +236,7 @@ static int session_choose(dyn_aligner* a, const dyn_batch* b, const SessionNeed&
   HIP_TRY(a, hipMemGetInfo(&free_b, &total_b));
   const uint64_t pool = a->ws.bytes + a->lpe.bytes + a->bits.bytes + parked_bytes(a->device);
   uint64_t budget = (uint64_t)((double)(free_b + pool) * 0.90);
-  if (a->mem_budget && a->mem_budget < budget) budget = a->mem_budget;
+  if (a->mem_budget && mem_budget_left(a) < budget) budget = mem_budget_left(a);
   const uint64_t page_rows = 1ull << g->log_r, max_pages = 0xfffffff0ull >> g->log_r;  // pool rows are 32-bit
   const uint64_t want = n_waves * g->arena_pages * (page_rows * SESSION_ROW_BYTES);
   if (want <= budget && n_waves * g->arena_pages <= max_pages) {
@@ -558,6 +558,7 @@ int session_finish_enqueue(dyn_batch* b, hipStream_t s) {
     dynk::launch_kmer_summary(b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_max_N, b->d_state.as<ReadState>(), tb, ks[k], s);
   for (size_t k = 1; k < bm.size(); ++k)
     dynk::launch_band_margin(b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_max_N, b->d_state.as<ReadState>(), tb, bm[k], s);
+  enqueue_site_summary(b, b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_max_N, b->d_state.as<ReadState>(), tb, s);
   HIP_TRY(a, hipGetLastError());
   HIP_TRY(a, hipEventRecord(ev[2], s));
   HIP_TRY(a, hipMemcpyAsync(b->h_stats.p, b->d_tctl.p, dynk::SESSION_TCTL_WORDS * 4, hipMemcpyDeviceToHost, s));

@@ -11,6 +11,7 @@ aligner batches of reads (``--batch-reads``), while a writer thread streams the 
 """
 from __future__ import annotations
 
+import os
 import queue as queue_mod
 import sys
 import threading
@@ -132,6 +133,10 @@ def parse(argv=None) -> Namespace:
                         "on the GPU between the passes: a least-squares fit of the segment levels on the model levels. "
                         "The rows are those of the last pass (with --event-stats, its levels). The CSV columns are unchanged; "
                         "the per-read shift and scale are not written anywhere")
+    p.add_argument("--site-summary", default="", metavar="FILE",
+                   help="per reference position across reads (the basecalls must be a MAPPED .bam): coverage, dwell and level "
+                        "mean / sd of the reads' event means, summed on the GPU as exact integers, written as a TSV of the sites "
+                        "with coverage > 0 in reference order (INTEGRATION.md section 3). One process only")
     p.add_argument("--kmer-summary", default="", metavar="PATH",
                    help="also write a per-k-mer summary of the run to PATH: a TSV in the model file's k-mer order with the "
                         "level (mean, stdev of the normalised signal) and dwell the run's segments showed per k-mer beside the "
@@ -289,10 +294,38 @@ def _native_bam(basecalls: str) -> bool:
     return basecalls.endswith(".bam") and os.environ.get("DYN_PY_BAM", "0") != "1"
 
 
-def job_batches(basecalls: str, minQual: float, batch_reads: int, is_rna: bool, rank: int = 0, world: int = 1):
+def batch_site_ids(jb, aln: dict, offsets, is_rna: bool) -> tuple:
+    """--site-summary: (per-read uint32 ids in aligner orientation, reads left without ids) of one JobBatch from its mapping
+    (NativeBamJobs.alignment()). A read gets no ids -- DYN_SITE_NONE throughout -- when it is unmapped, secondary or
+    supplementary, on the reverse strand (the stored sequence is then the reverse complement, which the pipeline aligns as it
+    stands), carries its CIGAR in a CG tag (the record holds the kSmN placeholder), or has a CIGAR that does not cover it."""
+    from dynamont_amd.sites import DYN_SITE_NONE, site_ids_from_cigar, to_aligner_orientation
+    out, without = [], 0
+    seq_len = np.diff(jb.seq_off.astype(np.int64))
+    for i in range(jb.n):
+        flag, ref, l_seq = int(aln["flag"][i]), int(aln["ref_id"][i]), int(jb.bases[i])
+        words = aln["cigar"][int(aln["cigar_off"][i]):int(aln["cigar_off"][i + 1])]
+        ids = None
+        placeholder = len(words) == 2 and int(words[0]) == (l_seq << 4 | 4) and int(words[1]) & 0xF == 3
+        if not flag & (0x4 | 0x10 | 0x100 | 0x800) and 0 <= ref < len(offsets) - 1 and len(words) and not placeholder:
+            try:
+                ids = to_aligner_orientation(site_ids_from_cigar(int(aln["pos"][i]), words, l_seq, int(offsets[ref])), is_rna,
+                                             int(seq_len[i]) - l_seq)
+            except ValueError:
+                ids = None
+        if ids is None:
+            without += 1
+            ids = np.full(int(seq_len[i]), DYN_SITE_NONE, dtype=np.uint32)
+        out.append(ids)
+    return out, without
+
+
+def job_batches(basecalls: str, minQual: float, batch_reads: int, is_rna: bool, rank: int = 0, world: int = 1, site_offsets=None,
+                site_counts=None):
     """generate_jobs a batch at a time, as columns (bam_io.JobBatch): the quality filter, the rank's share
     (index % world == rank) and -- ``is_rna`` -- the workers' sequence orientation (segment.py:149-153) are applied by the
-    native reader."""
+    native reader. ``site_offsets`` (--site-summary: sites.contig_offsets of the header's references): every batch carries
+    ``site_ids``, and ``site_counts`` [reads, reads left without ids] is added to."""
     from dynamont_amd.bam_io import NativeBamJobs
     reader = NativeBamJobs(basecalls, rna=is_rna, pad=POLYA, min_qual=minQual or 0.0, rank=rank, world=world)
     try:
@@ -300,6 +333,11 @@ def job_batches(basecalls: str, minQual: float, batch_reads: int, is_rna: bool, 
             jb = reader.next(batch_reads)
             if jb is None:
                 break
+            if site_offsets is not None:
+                jb.site_ids, without = batch_site_ids(jb, reader.alignment(), site_offsets, is_rna)
+                if site_counts is not None:
+                    site_counts[0] += jb.n
+                    site_counts[1] += without
             yield jb
         print(f"Skipped reads due to low quality: {reader.skipped}", file=sys.stderr)
     finally:
@@ -748,9 +786,11 @@ class _NativePipeline:
             out = self.free.pop() if self.free else None
             if self.raw:
                 cal = ([p[3][0] for p in g], [p[3][1] for p in g]) if g[0][3] is not None else None
+                # --site-summary: every pending tuple then carries its read's ids as a sixth element (all of them or none)
+                ids = np.concatenate([p[5] for p in g]) if all(len(p) > 5 and p[5] is not None for p in g) else None
                 submit_raw = self.aligner.align_vbz_async if isinstance(sig, tuple) else self.aligner.align_raw_async
                 t = submit_raw(sig, sig_off, [p[2][1] for p in g], [p[2][2] for p in g], seqs, seq_off,
-                               window=3, n_sigmas=3.0, f32=False, calc_probabilities=True, out=out, calibration=cal)
+                               window=3, n_sigmas=3.0, f32=False, calc_probabilities=True, out=out, calibration=cal, site_ids=ids)
             else:
                 t = self.aligner.align_async(sig, sig_off, seqs, seq_off, True, out=out)
             res = t.result
@@ -806,8 +846,10 @@ class _NativePipeline:
         self._room_for(int(raw_off[-1]))
         n = jb.n
         out = self.free.pop() if self.free else None
+        ids = getattr(jb, "site_ids", None)  # --site-summary: the batch's per-read ids, packed like its sequences
         t = self.aligner.align_vbz_async(chunks, raw_off, jb.shift, jb.scale, jb.seqs, jb.seq_off, window=3, n_sigmas=3.0, f32=False,
-                                         calc_probabilities=True, out=out, calibration=(cal_o, cal_s) if calibrated.all() else None)
+                                         calc_probabilities=True, out=out, calibration=(cal_o, cal_s) if calibrated.all() else None,
+                                         site_ids=np.concatenate(ids) if ids else None)
         res = t.result
         rid = (jb.names.ctypes.data + jb.name_off[:-1]).astype(np.uint64)  # char* of every NUL-terminated name
         sid = (jb.sids.ctypes.data + jb.sid_off[:-1]).astype(np.uint64)
@@ -904,7 +946,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             segment_scores: int = 0, border_confidence: int = 0, band_report: str = "", band: int = 400,
             guide_auto: int = 0, guide_rounds: int = 8, guide_rescue: int = 0, guide_rescue_margin: int = 1,
             posterior_samples: int = 0, sample_seed: int = 0, border_interval: float = 0.0,
-            soft_levels: bool = False) -> None:
+            soft_levels: bool = False, site_summary: str = "") -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
@@ -922,6 +964,22 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
     if border_interval and (not 0.01 <= border_interval <= 0.999 or border_confidence or posterior_samples or guide_auto or guide_rescue):
         raise ValueError("--border-interval must be 0 or 0.01 .. 0.999 and is not combined with --border-confidence, "
                          "--posterior-samples, --guide-auto or --guide-rescue")
+    site_refs = None
+    if site_summary:
+        # refused before anything is started: what the per-site table cannot do yet, and a BAM that is not mapped
+        from dynamont_amd.bam_io import bam_references
+        from dynamont_amd.sites import DYN_SITE_NONE, contig_offsets
+        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+            raise ValueError("--site-summary runs in one process: merging the per-site tables of several ranks is not built yet")
+        if host_preprocess or ZSTD_PARALLEL_FRAMES or not _native_bam(basecalls):
+            raise ValueError("--site-summary needs the basecalls as a mapped .bam read by the native reader (not with "
+                             "--host-preprocess, --parallel-zstd-frames or DYN_PY_BAM=1)")
+        names, lengths = bam_references(basecalls)
+        if not names:
+            raise ValueError(f"--site-summary: the header of {basecalls} has no reference sequences (an unaligned BAM); map the reads first")
+        site_refs = (names, contig_offsets(lengths))
+        if int(site_refs[1][-1]) >= DYN_SITE_NONE or int(site_refs[1][-1]) == 0:
+            raise ValueError(f"--site-summary: the references hold {int(site_refs[1][-1])} positions; the table takes 1 .. 4294967294")
     from dynamont_amd import parallel
     comm, local_rank = parallel.init_from_env()
     rank, world = (comm.rank, comm.world) if comm else (0, 1)
@@ -990,6 +1048,21 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
         write_kmer_summary(kmer_summary, merge_kmer_summaries(parts), model_path, mean, stdev, aligner.rna)
         print(f"k-mer summary written: {kmer_summary}", file=sys.stderr, flush=True)
 
+    site_counts = [0, 0]  # --site-summary: reads handed to the aligner, reads of those left without ids
+
+    def write_sites(aligner):
+        # --site-summary, with the pipeline dry: the sites with coverage, a window of the table at a time
+        if not site_summary:
+            return
+        from dynamont_amd.segmentation.utils import write_site_summary
+        num_sites = int(site_refs[1][-1])
+        written = write_site_summary(site_summary, aligner.site_summary, num_sites, *site_refs)
+        t = aligner.site_summary(0, 0)["totals"]
+        print(f"site summary written: {site_summary}: {written} sites with coverage; reads_ok {t['reads_ok']}, rows_added {t['rows_added']}, "
+              f"samples_added {t['samples_added']}, rows_without_site {t['rows_without_site']}, rows_skipped {t['rows_skipped']}; "
+              f"reads left without ids (unmapped, secondary / supplementary, reverse strand, CIGAR in a CG tag or not covering the read): "
+              f"{site_counts[1]} of {site_counts[0]}", file=sys.stderr, flush=True)
+
     def write_band_report(lines):
         # --band-report, with the pipeline dry: every rank's lines travel to rank 0 (one more gather), which sorts and writes
         # them -- the same bytes for any number of ranks
@@ -1041,6 +1114,11 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                 aligner.set_soft_levels(True)
             if kmer_summary:
                 aligner.set_kmer_summary(True)
+            if site_summary:
+                try:
+                    aligner.set_site_summary(int(site_refs[1][-1]))
+                except MemoryError as error:
+                    raise MemoryError(f"--site-summary: the table of {int(site_refs[1][-1])} sites (56 bytes each) does not fit: {error}") from None
             if band_report:
                 aligner.set_band_margin(True)
             if guide_auto:
@@ -1048,7 +1126,6 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             if guide_rescue:
                 aligner.set_guide_rescue(guide_rescue_margin, guide_rescue, guide_rounds)
             if native:
-                import os
                 import tempfile
                 part, part_err = outfile, None
                 if rank != 0:  # a part of the frame, in local scratch space; its bytes travel to rank 0 at the end
@@ -1069,7 +1146,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                 if not host_preprocess and _native_bam(basecalls):
                     # BAM basecalls: the jobs arrive as columns (this rank's share of them); raw files that can point at their
                     # compressed chunks (.pod5, VBZ) are served without a Python object per read, any other reader read by read
-                    for jb in job_batches(basecalls, minq, batch_reads, is_rna, rank, world):
+                    for jb in job_batches(basecalls, minq, batch_reads, is_rna, rank, world,
+                                          site_offsets=site_refs[1] if site_summary else None, site_counts=site_counts):
                         prepared = prepare_job_columns(jb, data_path, sink.put)
                         if prepared is not None:
                             pipe.submit_columns(*prepared)
@@ -1083,7 +1161,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                             except Exception as error:  # noqa: BLE001  (segment.py:178-187)
                                 sink.put(f"error: worker, {error}\tN: {int(jb.bases[i])}\tRid: {job[6]}\tSid: {job[7]}")
                                 continue
-                            pending.append((signal, read, job, cal, int(jb.bases[i])))
+                            pending.append((signal, read, job, cal, int(jb.bases[i]), jb.site_ids[i] if site_summary else None))
                         pipe.submit(pending)
                 else:
                     pending = []
@@ -1111,6 +1189,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                 if comm is not None:
                     _gather_parts(comm, parallel, outfile, part, part_err)
                 write_summary(aligner)
+                write_sites(aligner)
                 write_band_report(band_lines)
                 parallel.remove_scratch()
                 print("Done with segmentation.", file=sys.stderr, flush=True)
@@ -1202,7 +1281,7 @@ def main(argv=None) -> None:
             border_confidence=args.border_confidence, band_report=args.band_report, band=args.band,
             guide_auto=args.guide_auto, guide_rounds=args.guide_rounds, guide_rescue=args.guide_rescue,
             guide_rescue_margin=args.guide_rescue_margin, posterior_samples=args.posterior_samples, sample_seed=args.sample_seed,
-            border_interval=args.border_interval, soft_levels=args.soft_levels)
+            border_interval=args.border_interval, soft_levels=args.soft_levels, site_summary=args.site_summary)
     _stamp("segment() returned (aligner closed)")
     if argv is None and not int(__import__("os").environ.get("WORLD_SIZE", "1") or 1) > 1:
         # Invoked as the command (console script / python -m), single process, everything written and closed: leave without

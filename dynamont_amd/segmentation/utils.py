@@ -289,3 +289,50 @@ def write_kmer_summary(path: str, summary: dict, model_file: str, model_mean, mo
             c = code_of_kmer(name, rna)
             w.write(f"{name}\t{cols[0][c]!r}\t{cols[1][c]!r}\t{nseg[c]}\t{nsamp[c]}\t{cols[2][c]!r}\t{cols[3][c]!r}\t{cols[4][c]!r}\n")
     return t
+
+
+# ---- per-site level summary (Aligner.set_site_summary, dynamont-resquiggle --site-summary) -------------------------------------
+SITE_SUMMARY_HEADER = "contig\tposition\tcoverage\tn_samples\tdwell_mean\tdwell_sd\tlevel_mean\tlevel_sd\n"
+
+
+def site_summary_row(n_rows: int, n_samples: int, dwell_sq: int, M1: int, M2: int):
+    """(dwell_mean, dwell_sd, level_mean, level_sd) of one site with coverage ``n_rows`` > 0, from the table's Python ints
+    (INTEGRATION.md section 3). Every quantity is formed exactly, as a fraction, and rounded to a double once; the two standard
+    deviations are the square roots of those doubles: level_mean = M1 / (n 2^40), level variance = M2 / (n 2^40) - (M1 / (n 2^40))^2,
+    dwell_mean = n_samples / n, dwell variance = dwell_sq / n - (n_samples / n)^2, negative variances taken as 0."""
+    from fractions import Fraction
+    import math
+    n = int(n_rows)
+    lm = Fraction(int(M1), n << 40)
+    lv = max(Fraction(0), Fraction(int(M2), n << 40) - lm * lm)
+    dm = Fraction(int(n_samples), n)
+    dv = max(Fraction(0), Fraction(int(dwell_sq), n) - dm * dm)
+    return float(dm), math.sqrt(float(dv)), float(lm), math.sqrt(float(lv))
+
+
+def site_summary_lines(summary: dict, lo: int, ref_names, offsets) -> list:
+    """the TSV lines (no header) of the sites with coverage > 0 of one window ``summary`` = Aligner.site_summary(lo, hi), in
+    reference order; ``offsets`` = sites.contig_offsets(reference lengths), positions 1-based"""
+    out = []
+    offs = np.asarray(offsets, dtype=np.int64)
+    for i in np.flatnonzero(summary["n_rows"]).tolist():
+        site = lo + i
+        c = int(np.searchsorted(offs, site, side="right")) - 1
+        dm, dsd, lm, lsd = site_summary_row(summary["n_rows"][i], summary["n_samples"][i], summary["dwell_sq"][i], summary["M1"][i],
+                                            summary["M2"][i])
+        out.append("%s\t%d\t%d\t%d\t%r\t%r\t%r\t%r\n" % (ref_names[c], site - int(offs[c]) + 1, int(summary["n_rows"][i]),
+                                                         int(summary["n_samples"][i]), dm, dsd, lm, lsd))
+    return out
+
+
+def write_site_summary(path: str, fetch, num_sites: int, ref_names, offsets, window: int = 1 << 20) -> int:
+    """--site-summary FILE: the header and one line per site with coverage > 0, in reference order. ``fetch(lo, hi)`` returns a
+    window of the table (Aligner.site_summary): a genome-sized table is never on the host at once. Returns the sites written."""
+    written = 0
+    with open(path, "w") as f:
+        f.write(SITE_SUMMARY_HEADER)
+        for lo in range(0, int(num_sites), window):
+            lines = site_summary_lines(fetch(lo, min(lo + window, int(num_sites))), lo, ref_names, offsets)
+            f.writelines(lines)
+            written += len(lines)
+    return written

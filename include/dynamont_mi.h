@@ -579,6 +579,44 @@ int dyn_aligner_kmer_summary_fetch(dyn_aligner* a, uint64_t* n_segments, uint64_
                                    uint64_t* q2_lo, uint64_t* q2_hi, uint64_t totals[4]);
 /* Zeroes the accumulator and the totals (same conditions as the fetch). */
 int dyn_aligner_kmer_summary_reset(dyn_aligner* a);
+/* (added within ABI 10: a caller that must know looks the symbol up) Per-site level summary of a run, keyed by caller-supplied
+ * site ids. A SITE ID is a uint32 the caller supplies per BASE of every sequence, in aligner
+ * orientation, packed exactly like `seqs` (ids[0] belongs to the character at seq_offsets[0]; one id per character, for RNA
+ * the pad included); DYN_SITE_NONE = "this base has no site". Output row j of a read -- the row whose sequence_pos is
+ * j + kmer_size / 2 -- belongs to site ids[j + kmer_size / 2]. While the switch is on, every output row of every read with
+ * status 0 of an align(calc_probabilities = 1) batch or ticket SUBMITTED on this handle WITH STAGED IDS is added, on the device
+ * behind the per-segment kernels, to its site's entry of a table that lives on the handle: seven u64 per site (56 bytes x
+ * num_sites of device memory), as EXACT INTEGERS --
+ *   n_rows, n_samples, dwell_sq   rows (one per read and row: the coverage), sum of their sample counts L, sum of L * L mod 2^64
+ *   M1 = sum m1, M2 = sum m2      signed 128-bit two's complement, two u64 limbs each; per row m = S1 / L (dyn_event_out's
+ *                                 level_mean, bit for bit), m1 = rint(m * 2^40), m2 = rint((m * m) * 2^40)
+ * so the table is the same bits whatever the launch path, the merging of tickets or the order of the device's atomics. The unit
+ * is the read's event mean, one observation per read and site. A row whose id is DYN_SITE_NONE is left out and counted in
+ * rows_without_site; one with id >= num_sites, a non-finite m or m * m >= 2^64 is left out and counted in rows_skipped.
+ * num_sites = 0 turns the switch off (the table stays and can be fetched); num_sites > 0 (below DYN_SITE_NONE) turns it on, and
+ * allocates and zeroes the table when the handle has none of that size: a call with ANOTHER size first waits for every job in
+ * flight on the handle, then frees the old table. The table counts against dyn_aligner_set_mem_budget (a table larger than the
+ * budget: DYN_ERR_OUT_OF_MEMORY) and against what the lattice pool may take. A job counts once per time it runs; a rescaling
+ * job counts once, with its last pass's signal; under the guide rescue the summary runs once, behind the rescue. A job with the
+ * switch on and nothing staged adds nothing. Default off: nothing is allocated, launched or changed. DYN_ERR_INVALID_ARGUMENT
+ * for a handle of mode "ntk" / "resquiggle" or num_sites >= DYN_SITE_NONE, DYN_ERR_DEVICE for a handle without a device,
+ * DYN_ERR_OUT_OF_MEMORY when the table does not fit. */
+#define DYN_SITE_NONE 0xFFFFFFFFu
+int dyn_aligner_set_site_summary(dyn_aligner* a, uint64_t num_sites);
+/* The site ids of the NEXT batch-creating call on this handle: dyn_batch_create[_raw], dyn_align_batch or
+ * dyn_batch_align[_raw|_vbz]_async (dyn_train_batch and the train tickets consume and ignore them, as a Z-only job does). That
+ * call consumes them whether it succeeds or not. `count` must equal that call's seq_offsets[n] - seq_offsets[0], otherwise that
+ * call fails with DYN_ERR_INVALID_ARGUMENT. Nothing is copied here: the array must stay valid as long as `seqs` must (a
+ * synchronous call: until it returns; a ticket: until dyn_batch_wait has returned). Staging again replaces what was staged. */
+int dyn_aligner_stage_site_ids(dyn_aligner* a, const uint32_t* site_ids, uint64_t count);
+/* The columns of the sites [lo, hi) of the table as it stands after every job that has COMPLETED (the conditions of
+ * dyn_aligner_kmer_summary_fetch); arrays of hi - lo. totals: reads_ok (ok reads of the jobs that added), rows_added,
+ * samples_added, rows_without_site, rows_skipped. DYN_ERR_INVALID_ARGUMENT when the handle has no table or hi > num_sites. */
+int dyn_aligner_site_summary_fetch(dyn_aligner* a, uint64_t lo, uint64_t hi, uint64_t* n_rows, uint64_t* n_samples,
+                                   uint64_t* dwell_sq, uint64_t* m1_lo, uint64_t* m1_hi, uint64_t* m2_lo, uint64_t* m2_hi,
+                                   uint64_t totals[5]);
+/* Zeroes the table and the totals (same conditions as the fetch). */
+int dyn_aligner_site_summary_reset(dyn_aligner* a);
 /* The rule of mode 1 for one read, given its k-mer codes (dyn_validate_batch) and signal length: 0 = no structural tie;
  * otherwise the number of forward rows that run in the strict arithmetic (UINT32_MAX: all of them). Host only. */
 uint32_t dyn_tie_rows(const dyn_aligner* a, const int32_t* kmers, uint64_t n_kmers, uint64_t signal_len);
@@ -850,6 +888,24 @@ int dyn_bam_open(const char* path, int threads, const char* rna_pad, dyn_bam_rea
 int dyn_bam_next(dyn_bam_reader* r, uint64_t max_reads, uint32_t flags, double min_qual, uint32_t rank, uint32_t world,
                  dyn_job_batch* out, char* err, uint64_t errcap);
 uint64_t dyn_bam_skipped(const dyn_bam_reader* r);
+/* (added within ABI 10: a caller that must know looks the symbol up) The mapping of a MAPPED BAM, for callers that key their
+ * results by reference position (dyn_aligner_stage_site_ids; dynamont_amd/sites.py). dyn_bam_references: the header's reference
+ * sequences -- n_ref of them (0: an unaligned BAM), their names NUL-terminated back to back with name_off[i] = start of name i
+ * (n_ref + 1 entries), their lengths. dyn_bam_alignment: per read of the batch dyn_bam_next returned LAST, in that batch's
+ * order -- the record's flag, ref_id and 0-based pos (-1: unmapped), and its CIGAR as BAM stores it (words of len << 4 | op, op
+ * 0 .. 8 = MIDNSHP=X) back to back with cigar_off[i] = first word of read i (n + 1 entries). The CIGAR is as the RECORD holds
+ * it, in stored orientation (a record that carries its real CIGAR in a CG tag shows the kSmN placeholder here). dyn_job_batch
+ * itself does not change. The arrays belong to the reader and stay valid until its next dyn_bam_next. */
+typedef struct dyn_job_alignment {
+  uint64_t n;
+  const uint32_t* flag;
+  const int32_t* ref_id;
+  const int32_t* pos;
+  const uint32_t* cigar;
+  const uint64_t* cigar_off;
+} dyn_job_alignment;
+int dyn_bam_references(dyn_bam_reader* r, uint64_t* n_ref, const char** names, const uint64_t** name_off, const uint32_t** lengths);
+int dyn_bam_alignment(dyn_bam_reader* r, dyn_job_alignment* out);
 void dyn_bam_close(dyn_bam_reader* r);
 
 /* ---- staged form: inputs resident in HBM before the timed region (bench.py, pipelining) ---- */
