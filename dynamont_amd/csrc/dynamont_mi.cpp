@@ -15,6 +15,7 @@
 // There is NO CPU compute path here: without a bound GPU every compute entry point fails with
 // DYN_ERR_DEVICE.
 #include "engine_internal.hpp"
+#include "launch_plan.hpp"
 #include "dp_math_strict.hpp"
 #include "auto_guide_kernels.hpp"
 
@@ -23,8 +24,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <numeric>
-#include <queue>
 #include <stdexcept>
 
 using dynhost::PoreModel;
@@ -1295,35 +1294,24 @@ int enqueue_auto_guide(dyn_batch* b, uint32_t half_width) {
   std::vector<uint32_t> order;
   for (uint64_t i = 0; i < b->n; ++i)
     if (b->reads[i].status == DYN_READ_OK) order.push_back((uint32_t)i);
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return b->reads[x].S > b->reads[y].S; });  // longest first
+  dynplan::length_order(order, [&](uint32_t i) { return b->reads[i].S; });
   if (!order.empty()) {
     // pinned and the batch's own: the copy below may still be pending when this returns
     HIP_TRY(a, b->h_gdescs.ensure(order.size() * sizeof(ReadDesc)));
     ReadDesc* descs = b->h_gdescs.as<ReadDesc>();
+    // full descriptors, as every launch's: k_auto_guide reads T, N, sig_off and par_off alone (auto_guide.hip; AutoGuideArgs in
+    // auto_guide_kernels.hpp says so), so bw, ratio and path_off -- zero here before -- change nothing it computes
+    uint64_t rows_total = 0;
     for (size_t k = 0; k < order.size(); ++k) {
       const HostRead& r = b->reads[order[k]];
-      ReadDesc d{};
-      d.T = (uint32_t)(r.S + 1);
-      d.N = (uint32_t)(r.kc + 1);
-      d.read = order[k];
-      d.sig_off = r.sig_off;
-      d.par_off = r.flat_off;
-      d.seg_off = r.seg_off;
-      d.first_page = dynk::NO_PAGE;
-      descs[k] = d;
+      descs[k] = dynplan::make_desc<ReadDesc>(order[k], r.S, r.kc, a->model.half_band, r.sig_off, r.flat_off, r.seg_off, rows_total, 0);
+      rows_total += descs[k].T;
     }
     HIP_TRY(a, b->d_descs.ensure(order.size() * sizeof(ReadDesc)));  // (enqueue_job's table holds these reads at the most: it does not grow the buffer)
     HIP_TRY(a, hipMemcpyAsync(b->d_descs.p, descs, order.size() * sizeof(ReadDesc), hipMemcpyHostToDevice, a->stream));
-    dynk::AutoGuideArgs ag{};
-    ag.descs = b->d_descs.as<ReadDesc>();
-    ag.n_reads = (int)order.size();
-    ag.bw = (int)half_width;
-    ag.sig = b->d_sig.as<double>();
-    ag.par = b->d_par.as<Emis>();
-    ag.guide = b->d_guide.as<int32_t>();
-    ag.head = reinterpret_cast<uint32_t*>(b->d_guide.as<char>() + head_off);
-    ag.m1 = a->model.log_m1;
-    ag.e2 = a->model.log_e2;
+    // descs, n_reads, bw | sig, par | guide, head | m1, e2
+    const dynk::AutoGuideArgs ag{b->d_descs.as<ReadDesc>(), (int)order.size(), (int)half_width, b->d_sig.as<double>(), b->d_par.as<Emis>(), b->d_guide.as<int32_t>(),
+                                 reinterpret_cast<uint32_t*>(b->d_guide.as<char>() + head_off), a->model.log_m1, a->model.log_e2};
     const int groups = (int)std::min<uint64_t>(order.size(), (uint64_t)a->n_cus * (uint64_t)dynk::auto_guide_groups_per_cu((int)half_width));
     HIP_TRY(a, dynk::launch_auto_guide(ag, groups, a->stream));
   }

@@ -444,6 +444,10 @@ struct BatchGroup {
 
 }  // namespace dyneng
 
+namespace dynk {
+struct BandArgs;  // band_reads.hpp
+}
+
 namespace dyneng {
 
 // ---- shared between the engine's translation units (dynamont_mi.cpp, launch.cpp, session.cpp, async_engine.cpp) ----
@@ -490,11 +494,30 @@ int session_recover(dyn_batch* b, bool* republished);
 std::vector<dynk::KmerSummary> kmer_summary_args(const dyn_batch* b);
 // the same for the per-site summary (empty: none asked, or none of those that asked staged ids)
 std::vector<dynk::SiteSummary> site_summary_args(const dyn_batch* b);
-// launch_site_summary for every entry of site_summary_args, behind the per-segment kernels on `s`
-void enqueue_site_summary(const dyn_batch* b, const dynk::ReadDesc* descs, int n_reads, uint32_t max_N, const dynk::ReadState* st,
-                          const dynk::TraceBuffers& tb, hipStream_t s);
 // the same for the band margins (b->d_bm must hold 3 * n uint32: band_margin_prepare)
 std::vector<dynk::BandMargin> band_margin_args(const dyn_batch* b);
+// ---- the launch path's shared steps (launch.cpp; the host-only rules behind them: launch_plan.hpp) ----
+// the batch's pinned initial per-read state: the host-side status (ntk: DYN_READ_NTK_MISMATCH for every ok read), everything else 0
+dynk::ReadState* init_read_state(dyn_batch* b, bool ntk);
+// bytes the lattice arenas in `buf` may take: 0.8 of what is free, what `buf` holds and what is parked, within the budget if asked
+int arena_room(dyn_aligner* a, const DevBuf& buf, bool cap_by_budget, uint64_t* room);
+// `buf` holds `want` bytes afterwards: parked pools are given back first when memory is tight, and the compute stream is waited
+// for when the buffer that grows is the handle's (the ticket before may still be working in it)
+int grow_arena(dyn_aligner* a, DevBuf& buf, uint64_t want);
+// launch_band_reads' arguments as far as the queue's `q` and the arenas in arena_buf (256-byte head, then arena_bytes per
+// workgroup) decide them: descs, sig, par, st, tb, head, arena, exp_tab, m1, e2, z_fail_status
+dynk::BandArgs band_args_common(const dyn_batch* b, const dynk::QueueArgs& q, int z_fail, const DevBuf& arena_buf, uint64_t arena_bytes);
+// which band margins the rider tail takes: the diagonal's (the first range rides in launch_segments), a guided batch's against its
+// guide window, or none -- the guide rescue's stage has taken them
+enum class Margins { Diagonal, Guided, Taken };
+// launch_segments with the level / score columns, the per-k-mer and per-site summaries and the margins of an align(calc = 1) job or
+// ticket on `s`; the caller has prepared (and zeroed) OUT_LEVELS / OUT_SCORES and the margins' room
+void enqueue_riders(dyn_batch* b, const dynk::ReadDesc* descs, int n, uint64_t rows_total, uint32_t max_N, const dynk::ReadState* st,
+                    const dynk::TraceBuffers& tb, hipStream_t s, Margins margins);
+// what the batch remembers of the job just enqueued: tm (with reads_ok / reads_strict filled in), the strict flags, n_chunks,
+// aligned / trained / last_calc
+void record_job(dyn_batch* b, dyn_timing tm, DynJob job, bool calc, uint64_t reads_ok, uint64_t n_strict, const std::vector<uint32_t>& strict_rows,
+                uint32_t n_chunks);
 // bm_ready and the room for the margins of an align(calc = 1) job of this batch / ticket
 int band_margin_prepare(dyn_batch* b, bool calc);
 // What a job of kind `job` submitted NOW through `api` ("dyn_batch_align", "dyn_batch_align_async": `ticket`) takes of the handle's

@@ -4,18 +4,16 @@
 // noted. Reference counterpart: none -- the reference keeps one Aligner per forked worker busy with one read at a time
 // (src/dynamont/segmentation/segment.py:296-325); this is what keeps 1 024 waves busy across batches.
 #include "engine_internal.hpp"
+#include "launch_plan.hpp"
 #include "dp_math_strict.hpp"
 
 #include <algorithm>
-#include <chrono>
-#include <cmath>
 #include <cstdio>
 #include <cstring>
 
 using dynhost::PoreModel;
 using dynk::ReadDesc;
 using dynk::ReadState;
-using dynk::SegRow;
 using dynmath::Emis;
 using namespace dyneng;
 
@@ -26,10 +24,9 @@ namespace {
 
 // workgroups of a session = CUs it occupies (dyn_aligner_set_session_mode leaves the others free)
 int session_wgs(const dyn_aligner* a) { return std::max(1, a->sess_cus); }
-// bytes of one lattice row in the pool (separate LPE layout): bE 8 B + float LPE 4 B per slot + the row's 64-byte record
-constexpr uint64_t SESSION_ROW_BYTES = (uint64_t)dynk::P * 12 + dynk::ROW_WORDS * 8;
-
-uint32_t session_pages_of(uint64_t S, int log_r) { return (uint32_t)((S + 2 + (1ull << log_r) - 1) >> log_r); }
+// an arena for every wave is sized for the separate LPE layout
+constexpr uint64_t SESSION_ROW_BYTES = dynplan::row_sep;
+using dynplan::pages_of;
 
 struct SessionNeed {
   uint64_t n_ok = 0;
@@ -221,9 +218,9 @@ int session_quiesce(dyn_aligner* a) {
 static void session_geometry(uint64_t max_S, int* log_r, uint32_t* arena_pages) {
   const uint64_t cap_S = max_S + max_S / 8 + 64;
   int lr = dyneng::min_page_log_rows();
-  while (session_pages_of(cap_S, lr) > (uint32_t)dynk::PT_MAX) ++lr;
+  while (pages_of(cap_S, lr) > (uint32_t)dynk::PT_MAX) ++lr;
   *log_r = lr;
-  *arena_pages = session_pages_of(cap_S, lr);
+  *arena_pages = pages_of(cap_S, lr);
 }
 
 // The geometry of a session that could take the ticket: an arena for every wave if the memory budget allows (layout 0),
@@ -250,19 +247,10 @@ static int session_choose(dyn_aligner* a, const dyn_batch* b, const SessionNeed&
   std::vector<uint32_t> pg;
   pg.reserve(need.n_ok);
   for (uint64_t i = 0; i < b->n; ++i)
-    if (b->reads[i].status == DYN_READ_OK) pg.push_back(session_pages_of(b->reads[i].S, g->log_r));
-  const size_t top = std::min<size_t>(n_waves, pg.size());
-  std::partial_sort(pg.begin(), pg.begin() + top, pg.end(), std::greater<uint32_t>());
-  uint64_t wanted = 0;
-  for (size_t k = 0; k < top; ++k) wanted += pg[k];
-  wanted = std::max<uint64_t>(wanted, 1);
-  // separate float LPE: the forward sweep is 17 % faster, 12 instead of 8 bytes per band slot (enqueue_job's rule)
-  const uint64_t row_sep = (uint64_t)dynk::P * 12 + dynk::ROW_WORDS * 8, row_inp = (uint64_t)dynk::P * 8 + dynk::ROW_WORDS * 8;
-  const double c_sep = std::min(1.0, (double)budget / ((double)wanted * page_rows * row_sep + 1.0));
-  const double c_inp = std::min(1.0, (double)budget / ((double)wanted * page_rows * row_inp + 1.0));
-  bool separate = !(c_sep < 1.0 && c_inp * 0.92 > c_sep);
-  if (const char* f = std::getenv("DYN_FORCE_LAYOUT")) separate = std::string(f) != "inplace";
-  const uint64_t page_bytes = page_rows * (separate ? row_sep : row_inp);
+    if (b->reads[i].status == DYN_READ_OK) pg.push_back(pages_of(b->reads[i].S, g->log_r));
+  const uint64_t wanted = std::max<uint64_t>(dynplan::pages_wanted(pg, n_waves), 1);
+  const bool separate = dynplan::choose_lpe_layout(budget, wanted, page_rows);
+  const uint64_t page_bytes = page_rows * (separate ? dynplan::row_sep : dynplan::row_inp);
   // later tickets of the stream are served from the same pool: everything the budget gives, up to an arena per wave
   const uint64_t n_pages = std::min<uint64_t>({budget / page_bytes, n_waves * g->arena_pages, max_pages});
   if (n_pages < g->arena_pages) return DYN_OK;  // the longest read alone does not fit: the classic launch gives it its status
@@ -274,7 +262,7 @@ static int session_choose(dyn_aligner* a, const dyn_batch* b, const SessionNeed&
 
 static bool session_fits(const dyn_aligner* a, const Session& ss, const SessionNeed& need) {
   const uint32_t cap = ss.layout == 0 ? ss.arena_pages : std::min<uint32_t>((uint32_t)dynk::PT_MAX, ss.n_pages);
-  return session_pages_of(need.max_S, ss.log_r) <= cap && ss.published < SESSION_RING && (uint64_t)ss.next_base + need.n_ok < 0x7fffffffull &&
+  return pages_of(need.max_S, ss.log_r) <= cap && ss.published < SESSION_RING && (uint64_t)ss.next_base + need.n_ok < 0x7fffffffull &&
          (ss.mixed || a->strict_mode == 0);
 }
 
@@ -308,36 +296,26 @@ int session_publish(dyn_batch* b) {
   dyn_aligner* a = b->a;
   const PoreModel& m = a->model;
   Session& ss = a->sess;
-  // strict reads and the queue order: as enqueue_job
+  // strict reads (always, where enqueue_job computes them for calc alone: a ticket is an align(calc = 1) job) and the cost order
   const int32_t* km = b->kmers();
   std::vector<uint32_t> strict_rows(b->n, 0), order;
-  uint64_t n_strict = 0, max_S = 0;
+  uint64_t n_strict = 0;
   for (uint64_t i = 0; i < b->n; ++i) {
     const HostRead& r = b->reads[i];
     if (r.status != DYN_READ_OK) continue;
     if (a->strict_mode == 2) strict_rows[i] = 0xffffffffu;
     else if (a->strict_mode == 1) strict_rows[i] = tie_rows(a->model, km + r.flat_off, r.kc, r.S);
     n_strict += strict_rows[i] != 0;
-    max_S = std::max(max_S, r.S);
     order.push_back((uint32_t)i);
   }
-  auto cost_rows = [&](uint32_t i) -> uint64_t {
-    const uint64_t T = b->reads[i].S + 1;
-    if (!strict_rows[i]) return T;
-    const uint64_t fr = std::min<uint64_t>(T, strict_rows[i]);
-    return (T * 100 + T * 12 + fr * 24) / 100;
-  };
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cost_rows(x) > cost_rows(y); });
+  auto S_of = [&](uint32_t i) { return b->reads[i].S; };
+  dynplan::cost_order(order, S_of, strict_rows.data());
   const size_t n_ok = order.size();
 
   if (!ss.open) {
-    SessionNeed need;
-    need.n_ok = n_ok;
-    need.max_S = max_S;
     SessionGeom g = b->sess_geom;  // session_plan's (the open session it may have counted on has been closed since: its own)
-    if (!g.ok) {
-      if (int rc = session_choose(a, b, need, &g)) return rc;
-    }
+    if (!g.ok)
+      if (int rc = session_choose(a, b, session_need(b), &g)) return rc;
     if (!g.ok) {
       a->last_error = "session_publish: no session geometry for a ticket session_plan had accepted";
       return DYN_ERR_RUNTIME;
@@ -349,12 +327,12 @@ int session_publish(dyn_batch* b) {
     // waves that claim them would wait while the short reads behind them could run: the reads are dealt out in SPREAD order
     // (spread_order; the planned order of a page-starved LAUNCH, plan_queue, assumes waves that all start empty-handed and
     // a launch that must end on short reads -- measured here as well, DYN_SESSION_PLANNED: 465 against 507 Msamp/s).
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return b->reads[x].S > b->reads[y].S; });
+    dynplan::length_order(order, S_of);
     std::vector<uint32_t> need(n_ok);
     std::vector<uint64_t> rows(n_ok);
     for (size_t k = 0; k < n_ok; ++k) {
-      need[k] = session_pages_of(b->reads[order[k]].S, ss.log_r);
-      rows[k] = cost_rows(order[k]);
+      need[k] = pages_of(b->reads[order[k]].S, ss.log_r);
+      rows[k] = dynplan::cost_rows(S_of(order[k]) + 1, strict_rows[order[k]]);
     }
     if (std::getenv("DYN_SESSION_PLANNED")) {
       plan_queue(order, need, rows, ss.n_waves, ss.n_pages);
@@ -383,13 +361,7 @@ int session_publish(dyn_batch* b) {
   for (Output k : {OUT_LEVELS, OUT_SCORES})
     if (int rc = output_ensure(b, k, output_wanted(b->want, k))) return rc;
   if (int rc = band_margin_prepare(b, true)) return rc;  // filled by session_finish_enqueue as well
-  ReadState* st = b->h_state.as<ReadState>();
-  for (uint64_t i = 0; i < b->n; ++i) {
-    st[i].Zb = 0.0;
-    st[i].Zf = 0.0;
-    st[i].status = b->reads[i].status;
-    st[i].n_segments = 0;
-  }
+  const ReadState* st = init_read_state(b, false);  // (session_candidate: not a handle in mode ntk)
   HIP_TRY(a, hipMemcpyAsync(b->d_state.p, st, b->n * sizeof(ReadState), hipMemcpyHostToDevice, a->s_in));
   HIP_TRY(a, b->h_descs.ensure(std::max<size_t>(sizeof(ReadDesc), n_ok * sizeof(ReadDesc))));
   ReadDesc* descs = b->h_descs.as<ReadDesc>();
@@ -398,21 +370,9 @@ int session_publish(dyn_batch* b) {
   uint32_t max_N = 0;
   for (size_t k = 0; k < n_ok; ++k) {
     const uint32_t i = order[k];
-    const HostRead& r = b->reads[i];
-    ReadDesc d{};
-    d.T = (uint32_t)(r.S + 1);
-    d.N = (uint32_t)(r.kc + 1);
-    d.bw = (uint32_t)std::min<uint64_t>(m.half_band, d.N / 2);
-    d.read = i;
-    d.ratio = (double)d.N / (double)d.T;
-    d.sig_off = r.sig_off;
-    d.par_off = r.flat_off;
-    d.seg_off = r.seg_off;
-    d.path_off = rows_total;
-    d.n_pages = session_pages_of(r.S, ss.log_r);
-    d.first_page = dynk::NO_PAGE;  // the wave's own arena
-    d.flags = !strict_rows[i] ? 0u : strict_rows[i] == 0xffffffffu ? dynk::READ_STRICT : dynk::READ_STRICT_START;
-    d.strict_rows = strict_rows[i];
+    const HostRead& r = b->reads[i];  // (first_page stays NO_PAGE: the wave's own arena)
+    ReadDesc d = dynplan::make_desc<ReadDesc>(i, r.S, r.kc, m.half_band, r.sig_off, r.flat_off, r.seg_off, rows_total, strict_rows[i]);
+    d.n_pages = pages_of(r.S, ss.log_r);
     rows_total += d.T;
     max_N = std::max(max_N, d.N);
     descs[k] = d;
@@ -467,8 +427,6 @@ int session_publish(dyn_batch* b) {
   // events[0]: the ticket's counter has been cleared and its record published. Until then d_tctl holds what the buffer's last
   // ticket left there (its full count, often the same number of reads): wait_resident must not read it earlier.
   HIP_TRY(a, hipEventRecord(b->events[0], a->s_in));
-  tm.reads_ok = n_ok;
-  tm.reads_strict = (uint32_t)n_strict;
   tm.launch_share = 0.0;
   tm.launches = 0;
   tm.lp_inplace = ss.layout == 2 ? 1 : 0;
@@ -476,13 +434,7 @@ int session_publish(dyn_batch* b) {
   tm.page_rows = 1u << ss.log_r;
   tm.n_static = 0;
   tm.n_waves = ss.n_waves;
-  b->strict_flag.assign(b->n, 0);
-  for (uint64_t i = 0; i < b->n; ++i) b->strict_flag[i] = strict_rows[i] != 0;
-  b->timing = tm;
-  b->n_chunks = 1;
-  b->aligned = true;
-  b->trained = false;
-  b->last_calc = 1;
+  record_job(b, tm, DynJob::AlignFull, true, n_ok, n_strict, strict_rows, 1);
   b->in_session = true;
   b->sess_reads = (uint32_t)n_ok;
   b->sess_waves = ss.n_waves;
@@ -537,28 +489,10 @@ int session_finish_enqueue(dyn_batch* b, hipStream_t s) {
   HIP_TRY(a, hipEventRecord(ev[1], s));
   dynk::TraceBuffers tb{b->d_pp.as<double>(), b->d_pathn.as<uint32_t>(), b->d_segrow.as<uint32_t>(), b->d_medhi.as<double>(),
                         b->d_medlo.as<double>()};
-  dynk::EventCols evc{};
   for (Output k : {OUT_LEVELS, OUT_SCORES})
     if (int rc = output_zero(b, k, s)) return rc;
-  if (b->out[OUT_LEVELS].ready) {
-    double* e = b->out[OUT_LEVELS].d.as<double>();
-    evc = dynk::EventCols{b->d_sig.as<double>(), e, e + b->capacity, e + 2 * b->capacity};
-  }
-  dynk::ScoreCols scc{};
-  if (b->out[OUT_SCORES].ready) {
-    double* e = b->out[OUT_SCORES].d.as<double>();
-    scc = dynk::ScoreCols{b->d_sig.as<double>(), e, e + b->capacity, e + 2 * b->capacity, e + 3 * b->capacity, b->want.segment_scores};
-  }
-  const std::vector<dynk::KmerSummary> ks = kmer_summary_args(b);
-  const std::vector<dynk::BandMargin> bm = band_margin_args(b);
-  dynk::launch_segments(b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_rows_total, b->sess_max_N, b->d_state.as<ReadState>(), tb,
-                        b->d_rows.as<SegRow>(), a->model.k, s, evc, ks.empty() ? dynk::KmerSummary{} : ks[0], scc,
-                        bm.empty() ? dynk::BandMargin{} : bm[0]);
-  for (size_t k = 1; k < ks.size(); ++k)
-    dynk::launch_kmer_summary(b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_max_N, b->d_state.as<ReadState>(), tb, ks[k], s);
-  for (size_t k = 1; k < bm.size(); ++k)
-    dynk::launch_band_margin(b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_max_N, b->d_state.as<ReadState>(), tb, bm[k], s);
-  enqueue_site_summary(b, b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_max_N, b->d_state.as<ReadState>(), tb, s);
+  enqueue_riders(b, b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_rows_total, b->sess_max_N, b->d_state.as<ReadState>(), tb, s,
+                 Margins::Diagonal);
   HIP_TRY(a, hipGetLastError());
   HIP_TRY(a, hipEventRecord(ev[2], s));
   HIP_TRY(a, hipMemcpyAsync(b->h_stats.p, b->d_tctl.p, dynk::SESSION_TCTL_WORDS * 4, hipMemcpyDeviceToHost, s));
@@ -591,35 +525,31 @@ int session_collect_timing(dyn_batch* b) {
 
 }  // namespace dyneng
 
+// the statistics of a session are complete once its kernel has left
+static int quiesce_for_stats(dyn_aligner* a) {
+  if (a->host_only || !a->s_session) return DYN_OK;
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = need_device(a)) return rc;
+  return session_quiesce(a);
+}
+
 extern "C" int dyn_aligner_session_stats(dyn_aligner* a, dyn_session_stats* out) {
   if (!a || !out) return DYN_ERR_INVALID_ARGUMENT;
-  if (!a->host_only && a->s_session) {
-    std::lock_guard<std::mutex> lk(a->mu);
-    if (int rc = need_device(a)) return rc;
-    if (int rc = session_quiesce(a)) return rc;
-  }
+  if (int rc = quiesce_for_stats(a)) return rc;
   *out = a->sess_total;
   return DYN_OK;
 }
 
 extern "C" int dyn_aligner_session_page_wait(dyn_aligner* a, uint64_t* wave_cycles_waiting_for_pages) {
   if (!a || !wave_cycles_waiting_for_pages) return DYN_ERR_INVALID_ARGUMENT;
-  if (!a->host_only && a->s_session) {
-    std::lock_guard<std::mutex> lk(a->mu);
-    if (int rc = need_device(a)) return rc;
-    if (int rc = session_quiesce(a)) return rc;
-  }
+  if (int rc = quiesce_for_stats(a)) return rc;
   *wave_cycles_waiting_for_pages = a->sess_page_wait_cycles;
   return DYN_OK;
 }
 
 extern "C" int dyn_aligner_session_idle_split(dyn_aligner* a, uint64_t out4[4]) {
   if (!a || !out4) return DYN_ERR_INVALID_ARGUMENT;
-  if (!a->host_only && a->s_session) {
-    std::lock_guard<std::mutex> lk(a->mu);
-    if (int rc = need_device(a)) return rc;
-    if (int rc = session_quiesce(a)) return rc;
-  }
+  if (int rc = quiesce_for_stats(a)) return rc;
   for (int k = 0; k < 4; ++k) out4[k] = a->sess_idle_split[k];
   return DYN_OK;
 }
