@@ -738,6 +738,7 @@ class Aligner:
     _kmer_summary = False  # set_kmer_summary
     _site_summary = 0  # set_site_summary: num_sites while on
     _site_table = 0  # ... and the size of the handle's table (it outlives the switch)
+    _site_histogram = None  # set_site_histogram: (bins, lo, hi) of the handle's counters (they outlive the switch too)
     _strict = 1  # set_strict
     _model_override = None  # set_model: (mean, stdev)
 
@@ -997,6 +998,8 @@ class Aligner:
             _raise(rc, self.last_error())
         self._site_summary = num_sites
         if num_sites:
+            if num_sites != self._site_table:
+                self._site_histogram = None  # another size releases the histograms: set_site_histogram again
             self._site_table = num_sites
 
     def _stage_site_ids(self, site_ids):
@@ -1031,6 +1034,62 @@ class Aligner:
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
         return site_summary_from_limbs(cols, totals)
+
+    def set_site_histogram(self, bins: int, lo: float = 0.0, hi: float = 0.0) -> None:
+        """dyn_aligner_set_site_histogram: beside the per-site table (``set_site_summary(num_sites > 0)`` first), a histogram of
+        the reads' event means with ``bins`` (2 .. 254) equal bins over [``lo``, ``hi``) plus an under and an over counter, and
+        a log2 histogram of the dwell (16 bins), per site, as exact uint32 counters filled in the same pass (INTEGRATION.md
+        section 3). ``site_histogram()`` fetches them, ``site_quantiles()`` reduces them to quantiles on the GPU,
+        ``reset_site_summary()`` zeroes them with the table. ``bins = 0`` stops the counting and keeps the counters; other
+        parameters wait for the tickets in flight and start zeroed counters; ``set_site_summary`` with another size releases
+        them."""
+        bins = int(bins)
+        rc = self._L.dyn_aligner_set_site_histogram(self._h, bins, float(lo), float(hi))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        if bins:
+            self._site_histogram = (bins, float(lo), float(hi))
+
+    def _site_window(self, lo, hi):
+        lo = int(lo)
+        hi = self._site_table if hi is None else int(hi)
+        return lo, hi, max(0, hi - lo)
+
+    def site_histogram(self, lo: int = 0, hi: int | None = None) -> dict:
+        """dyn_aligner_site_histogram_fetch: the counters of the sites [lo, hi) (default: all). ``level``: uint32 [n, bins + 2]
+        (column 0 under, 1 .. bins the bins, bins + 1 over); ``dwell``: uint32 [n, 16] (bin d: 2**d <= L < 2**(d + 1), the last
+        one open); ``edges``: float64 [bins + 1], the nominal bin edges lo + i * (hi - lo) / bins; ``bins``, ``lo``, ``hi``."""
+        lo, hi, n = self._site_window(lo, hi)
+        bins, h_lo, h_hi = self._site_histogram or (0, 0.0, 0.0)
+        level = np.zeros((n, bins + 2), dtype=np.uint32)
+        dwell = np.zeros((n, 16), dtype=np.uint32)
+        rc = self._L.dyn_aligner_site_histogram_fetch(self._h, lo, hi, _ptr(level, N.c_u32_p), _ptr(dwell, N.c_u32_p))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        edges = h_lo + np.arange(bins + 1, dtype=np.float64) * ((h_hi - h_lo) / bins)
+        return {"level": level, "dwell": dwell, "edges": edges, "bins": bins, "lo": h_lo, "hi": h_hi}
+
+    def site_quantiles(self, probs, lo: int = 0, hi: int | None = None) -> dict:
+        """dyn_aligner_site_quantiles: per site of [lo, hi) (default: all) and per probability of ``probs`` (1 .. 8 values in
+        [0, 1]) the rank k = min(max(ceil(q n), 1), n) among the site's n event means, the level counter ``bin`` that holds the
+        k-th smallest, the count ``below`` that counter and the count ``in_bin`` -- found on the GPU; the histograms stay there.
+        ``n``: uint32 [n_sites]; ``rank``, ``bin``, ``below``, ``in_bin``: uint32 [n_sites, n_probs]; ``level``: float64
+        [n_sites, n_probs], the value interpolated inside the bin (``segmentation.utils.site_quantile_levels``: -inf / +inf for
+        the under / over counter, NaN for a site without rows); ``probs``."""
+        from dynamont_amd.segmentation.utils import site_quantile_levels
+        q = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        if not 1 <= q.size <= 8 or not ((q >= 0.0) & (q <= 1.0)).all():
+            raise ValueError("site_quantiles: 1 .. 8 probabilities in [0, 1]")
+        lo, hi, n = self._site_window(lo, hi)
+        cnt = np.zeros(n, dtype=np.uint32)
+        cols = [np.zeros((n, q.size), dtype=np.uint32) for _ in range(4)]
+        rc = self._L.dyn_aligner_site_quantiles(self._h, lo, hi, _ptr(q, N.c_double_p), q.size, _ptr(cnt, N.c_u32_p),
+                                                *[_ptr(c, N.c_u32_p) for c in cols])
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        bins, h_lo, h_hi = self._site_histogram
+        return {"n": cnt, "rank": cols[0], "bin": cols[1], "below": cols[2], "in_bin": cols[3], "probs": q,
+                "level": site_quantile_levels(cols[0], cols[1], cols[2], cols[3], bins, h_lo, h_hi)}
 
     def set_band_margin(self, on: bool) -> None:
         """dyn_aligner_set_band_margin: align(calc_probabilities=True) jobs submitted while on also report, per read, how
@@ -1586,6 +1645,12 @@ class MultiAligner:
         """Not supported: the per-site table lives on ONE device's handle and the reads of a batch are cut over the devices.
         Use one ``Aligner`` per device and add the tables (they are integers)."""
         raise NotImplementedError("MultiAligner has no per-site summary (Aligner.set_site_summary): use one Aligner per device "
+                                  "and add their tables")
+
+    def set_site_histogram(self, bins: int, lo: float = 0.0, hi: float = 0.0) -> None:
+        """Not supported, as ``set_site_summary`` is not: the histograms live beside ONE device's table. Use one ``Aligner`` per
+        device and add the counters (they are integers)."""
+        raise NotImplementedError("MultiAligner has no per-site histograms (Aligner.set_site_histogram): use one Aligner per device "
                                   "and add their tables")
 
     def _cap(self, seq_off) -> int:

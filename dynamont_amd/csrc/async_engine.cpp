@@ -241,9 +241,17 @@ std::shared_ptr<BatchGroup> Pipeline::merge(const std::vector<dyn_batch*>& ticke
         g->ss_table = t->ss_table;
         g->ss_num_sites = t->ss_num_sites;
       }
+      // (likewise one set of histograms: the setter drains before it changes their parameters)
+      if (t->want.site_histogram && t->ss_hist.p) {
+        add_range(g->sh_ranges, t);
+        g->ss_hist = t->ss_hist;
+      } else {
+        add_range(g->ss_plain_ranges, t);
+      }
     }
   }
   g->want.site_summary = !g->ss_ranges.empty();
+  g->want.site_histogram = !g->sh_ranges.empty();
   if (any_sites) g->in_site_ids = grp->site_ids.data();
   g->want.kmer_summary = !g->ks_ranges.empty();
   g->want.band_margin = !g->bm_ranges.empty();
@@ -773,12 +781,14 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
   const uint32_t* site_ids = nullptr;
   unsigned long long* ss_table = nullptr;
   uint64_t ss_num_sites = 0;
+  SiteHist ss_hist;
   int staged_rc = DYN_OK;
   {
     std::lock_guard<std::mutex> lk(a->mu);
     staged_rc = take_staged_sites(a, "dyn_batch_align_async", n_reads, seq_offsets, &site_ids);
     ss_table = a->d_site.as<unsigned long long>();  // the table as it stands at this submission
     ss_num_sites = a->num_sites;
+    ss_hist = site_hist_now(a);
   }
   if (!ticket || !sig_offsets || !seq_offsets || (n_reads && ((!signals && !rs) || !seqs))) return DYN_ERR_INVALID_ARGUMENT;
   if (staged_rc != DYN_OK) return staged_rc;
@@ -830,6 +840,7 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
   b->in_site_ids = site_ids;
   b->ss_table = ss_table;
   b->ss_num_sites = ss_num_sites;
+  b->ss_hist = ss_hist;
   b->in_signals = signals;
   if (rs) {
     b->has_raw = true;

@@ -449,6 +449,8 @@ void dyn_aligner_destroy(dyn_aligner* a) {
     a->d_sptab.release();
     a->d_ksum.release();
     a->d_site.release();
+    a->d_shist.release();
+    a->d_squant.release();
     park_pool_buffer(a->device, 0, a->ws);
     park_pool_buffer(a->device, 1, a->lpe);
     park_pool_buffer(a->device, 2, a->bits);
@@ -773,6 +775,10 @@ int dyn_aligner_set_site_summary(dyn_aligner* a, uint64_t num_sites) {
   a->opt.site_summary = false;
   a->d_site.release();
   a->num_sites = 0;
+  // the histograms were the old table's: released and off, the caller sets them again (dyn_aligner_set_site_histogram)
+  a->opt.site_histogram = false;
+  a->d_shist.release();
+  a->sh_bins = 0;
   const uint64_t bytes = ((uint64_t)dynk::SS_FIELDS * num_sites + (uint64_t)dynk::SS_TOTALS) * sizeof(uint64_t);
   if (a->mem_budget && bytes > a->mem_budget) {
     std::lock_guard<std::mutex> elk(a->err_mu);
@@ -854,7 +860,147 @@ int dyn_aligner_site_summary_reset(dyn_aligner* a) {
   std::lock_guard<std::mutex> lk(a->mu);
   if (int rc = site_summary_quiet(a, "dyn_aligner_site_summary_reset")) return rc;
   HIP_TRY(a, hipMemsetAsync(a->d_site.p, 0, ((uint64_t)dynk::SS_FIELDS * a->num_sites + (uint64_t)dynk::SS_TOTALS) * sizeof(uint64_t), a->s_get));
+  if (a->d_shist.p && a->sh_bins)
+    HIP_TRY(a, hipMemsetAsync(a->d_shist.p, 0, a->num_sites * site_hist_width(a->sh_bins) * sizeof(uint32_t), a->s_get));
   HIP_TRY(a, hipStreamSynchronize(a->s_get));
+  return DYN_OK;
+}
+
+// ---- the per-site histograms beside the table (site_summary_kernels.hpp) -------------------------------------------------------
+int dyn_aligner_set_site_histogram(dyn_aligner* a, int bins, double lo, double hi) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  auto fail = [&](const std::string& msg) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = "dyn_aligner_set_site_histogram: " + msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  };
+  if (bins == 0) {  // off: the counters stay for the fetch
+    std::lock_guard<std::mutex> lk(a->mu);
+    a->opt.site_histogram = false;
+    return DYN_OK;
+  }
+  // refused before the device is looked at: the same text on a handle without one
+  if (bins < 2 || bins > dynk::SH_BINS_MAX) return fail("bins " + std::to_string(bins) + " is not 0 (off) or 2 .. 254");
+  if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) return fail("lo and hi must be finite with lo < hi");
+  const double inv_w = (double)bins / (hi - lo);  // one IEEE subtraction, one IEEE division
+  if (!std::isfinite(inv_w) || !(inv_w > 0.0)) return fail("hi - lo must be a finite width with a finite bins / (hi - lo)");
+  Pipeline* pipe = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (!a->d_site.p) return fail("dyn_aligner_set_site_summary(a, num_sites > 0) was never called on this handle");
+    if (int rc = need_device(a)) return rc;
+    if (a->d_shist.p && a->sh_bins == (uint32_t)bins && a->sh_lo == lo && a->sh_hi == hi) {
+      a->opt.site_histogram = true;
+      return DYN_OK;
+    }
+    // off before the lock is dropped, as the table's setter does it: no ticket submitted while this call drains counts
+    a->opt.site_histogram = false;
+    pipe = a->pipe.get();
+  }
+  // other parameters: the jobs in flight hold the old counters' address and parameters -- they finish first
+  if (pipe) pipe->drain();
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = session_quiesce(a)) return rc;
+  HIP_TRY(a, hipStreamSynchronize(a->stream));
+  HIP_TRY(a, hipStreamSynchronize(a->s_out));
+  a->opt.site_histogram = false;
+  a->d_shist.release();
+  a->sh_bins = 0;
+  if (!a->d_site.p || !a->num_sites) return fail("dyn_aligner_set_site_summary(a, num_sites > 0) was never called on this handle");
+  const uint64_t bytes = a->num_sites * site_hist_width((uint32_t)bins) * sizeof(uint32_t);
+  if (a->mem_budget && bytes > mem_budget_left(a)) {
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = "dyn_aligner_set_site_histogram: the histograms of " + std::to_string(a->num_sites) + " sites (" + std::to_string(bytes) +
+                    " bytes) do not fit dyn_aligner_set_mem_budget's " + std::to_string(a->mem_budget) + " bytes";
+    return DYN_ERR_OUT_OF_MEMORY;
+  }
+  const hipError_t e = a->d_shist.ensure(bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = "dyn_aligner_set_site_histogram: no device memory for the histograms of " + std::to_string(a->num_sites) + " sites (" +
+                    std::to_string(bytes) + " bytes): " + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? DYN_ERR_OUT_OF_MEMORY : DYN_ERR_DEVICE;
+  }
+  HIP_TRY(a, hipMemsetAsync(a->d_shist.p, 0, bytes, a->s_get));
+  HIP_TRY(a, hipStreamSynchronize(a->s_get));
+  a->sh_bins = (uint32_t)bins;
+  a->sh_lo = lo;
+  a->sh_hi = hi;
+  a->sh_inv_w = inv_w;
+  a->opt.site_histogram = true;
+  return DYN_OK;
+}
+
+namespace {
+// the conditions of site_summary_quiet, and histograms to read; [lo, hi) must be a range of the table
+int site_histogram_quiet(dyn_aligner* a, const char* who, uint64_t lo, uint64_t hi) {
+  if (int rc = site_summary_quiet(a, who)) return rc;
+  std::string msg;
+  if (!a->d_shist.p || !a->sh_bins) msg = ": dyn_aligner_set_site_histogram(a, bins > 0, lo, hi) was never called on this handle";
+  else if (lo > hi || hi > a->num_sites)
+    msg = ": [" + std::to_string(lo) + ", " + std::to_string(hi) + ") is not a range of the table's " + std::to_string(a->num_sites) + " sites";
+  if (msg.empty()) return DYN_OK;
+  std::lock_guard<std::mutex> elk(a->err_mu);
+  a->last_error = who + msg;
+  return DYN_ERR_INVALID_ARGUMENT;
+}
+}  // namespace
+
+int dyn_aligner_site_histogram_fetch(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi, uint32_t* level, uint32_t* dwell) {
+  if (!a || (site_lo < site_hi && (!level || !dwell))) return DYN_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = site_histogram_quiet(a, "dyn_aligner_site_histogram_fetch", site_lo, site_hi)) return rc;
+  const uint64_t B = (uint64_t)a->sh_bins + 2, D = (uint64_t)dynk::SH_DWELL_BINS, H = B + D, step = 1ull << 20;
+  std::vector<uint32_t> h(H * std::min(step, site_hi - site_lo) + 1);
+  const uint32_t* hist = a->d_shist.as<uint32_t>();
+  for (uint64_t s0 = site_lo; s0 < site_hi; s0 += step) {
+    const uint64_t cnt = std::min(step, site_hi - s0);
+    HIP_TRY(a, copy_out(a, h.data(), hist + H * s0, H * cnt * sizeof(uint32_t)));
+    for (uint64_t c = 0; c < cnt; ++c) {
+      std::memcpy(level + B * (s0 - site_lo + c), h.data() + H * c, B * sizeof(uint32_t));
+      std::memcpy(dwell + D * (s0 - site_lo + c), h.data() + H * c + B, D * sizeof(uint32_t));
+    }
+  }
+  return DYN_OK;
+}
+
+int dyn_aligner_site_quantiles(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi, const double* probs, int n_probs, uint32_t* n,
+                               uint32_t* rank, uint32_t* bin, uint32_t* below, uint32_t* in_bin) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  auto fail = [&](const std::string& msg) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = "dyn_aligner_site_quantiles: " + msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  };
+  if (!probs || n_probs < 1 || n_probs > dynk::SQ_PROBS_MAX) return fail("n_probs " + std::to_string(n_probs) + " is not 1 .. 8");
+  for (int q = 0; q < n_probs; ++q)
+    if (!(probs[q] >= 0.0 && probs[q] <= 1.0)) return fail("probs[" + std::to_string(q) + "] is not in [0, 1]");
+  if (site_lo < site_hi && (!n || !rank || !bin || !below || !in_bin)) return DYN_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = site_histogram_quiet(a, "dyn_aligner_site_quantiles", site_lo, site_hi)) return rc;
+  if (site_lo == site_hi) return DYN_OK;
+  const uint64_t H = site_hist_width(a->sh_bins), P = (uint64_t)n_probs, step = 1ull << 20;
+  const uint64_t most = std::min(step, site_hi - site_lo);
+  HIP_TRY(a, a->d_squant.ensure((1 + 4 * P) * most * sizeof(uint32_t)));
+  std::vector<uint32_t> h((1 + 4 * P) * most);
+  dynk::SiteQuantiles sq{};
+  sq.bins = a->sh_bins;
+  sq.n_probs = n_probs;
+  for (int q = 0; q < n_probs; ++q) sq.probs[q] = probs[q];
+  sq.out = a->d_squant.as<uint32_t>();
+  for (uint64_t s0 = site_lo; s0 < site_hi; s0 += step) {
+    const uint64_t cnt = std::min(step, site_hi - s0);
+    sq.hist = a->d_shist.as<unsigned int>() + H * s0;
+    sq.count = (uint32_t)cnt;
+    dynk::launch_site_quantiles(sq, a->s_get);
+    HIP_TRY(a, hipGetLastError());
+    HIP_TRY(a, copy_out(a, h.data(), sq.out, (1 + 4 * P) * cnt * sizeof(uint32_t)));  // (behind the kernel on the same stream)
+    const uint64_t o = s0 - site_lo;
+    std::memcpy(n + o, h.data(), cnt * sizeof(uint32_t));
+    uint32_t* cols[4] = {rank, bin, below, in_bin};
+    for (int f = 0; f < 4; ++f) std::memcpy(cols[f] + o * P, h.data() + cnt + (uint64_t)f * cnt * P, cnt * P * sizeof(uint32_t));
+  }
   return DYN_OK;
 }
 
@@ -1431,6 +1577,7 @@ int run_job_sync(dyn_batch* b, DynJob job, bool guided_train = false) {
     b->want = want;
     b->ss_table = a->d_site.as<unsigned long long>();  // the table as it stands at this submission
     b->ss_num_sites = a->num_sites;
+    b->ss_hist = site_hist_now(a);
     rc = enqueue_job(b, job);
     if (rc != DYN_OK) {
       (void)hipStreamSynchronize(a->stream);

@@ -137,6 +137,7 @@ struct JobOptions {
   int rescale_iters = 0;        // dyn_aligner_set_rescale (0 .. 8)
   bool kmer_summary = false;    // dyn_aligner_set_kmer_summary
   bool site_summary = false;    // dyn_aligner_set_site_summary (num_sites > 0)
+  bool site_histogram = false;  // dyn_aligner_set_site_histogram (bins > 0); counts only where site_summary does
   bool band_margin = false;     // dyn_aligner_set_band_margin
   int segment_scores = 0;       // dyn_aligner_set_segment_scores (window, 0 = off)
   int border_confidence = 0;    // dyn_aligner_set_border_confidence (window, 0 = off)
@@ -149,7 +150,7 @@ struct JobOptions {
   // May tickets x and y share ONE launch (Pipeline::merge)? Three kinds of fields:
   //   launch-wide: event_stats, rescale_iters, segment_scores, border_confidence, border_interval, soft_levels -- one value per launch, so the
   //                members must agree; the launch's batch takes them from its first member
-  //   per-ticket:  kmer_summary, site_summary, band_margin -- not compared: the launch's batch lists the read ranges of the members that asked
+  //   per-ticket:  kmer_summary, site_summary, site_histogram, band_margin -- not compared: the launch's batch lists the read ranges of the members that asked
   //   alone:       posterior_samples (the read's index in its OWN ticket keys the random stream), auto_guide_hw (a guide of its own
   //                and the banded-lattice kernel), rescue_hw (its list of reads to re-align is its own) -- such a ticket never merges
   bool merges() const { return posterior_samples == 0 && auto_guide_hw == 0 && rescue_hw == 0; }
@@ -168,6 +169,13 @@ struct JobOptions {
     g.soft_levels = soft_levels;
     return g;
   }
+};
+
+// the per-site histograms as a job sees them (dyn_aligner_set_site_histogram): taken at its submission, beside the table's address
+struct SiteHist {
+  unsigned int* p = nullptr;  // [num_sites][bins + 2 + 16] uint32; nullptr: off
+  uint32_t bins = 0;
+  double lo = 0.0, inv_w = 0.0;
 };
 
 // ---- the per-segment outputs a job may add to its rows (one fetcher, one out-struct and one CSV flag each) ---------------------
@@ -221,6 +229,12 @@ struct dyn_aligner {
   // num_sites > 0), kept until the setter names another size; a job snapshots pointer and size at its submission
   dyneng::DevBuf d_site;
   uint64_t num_sites = 0;
+  // the per-site histograms beside it: [num_sites][sh_bins + 2 + 16] u32, allocated and zeroed by dyn_aligner_set_site_histogram(a,
+  // bins > 0, lo, hi), kept (bins = 0 only stops the counting) until that setter names other parameters or the table another size
+  dyneng::DevBuf d_shist;
+  uint32_t sh_bins = 0;
+  double sh_lo = 0.0, sh_hi = 0.0, sh_inv_w = 0.0;
+  dyneng::DevBuf d_squant;    // staging of dyn_aligner_site_quantiles: one window's output
   // dyn_aligner_stage_site_ids: the caller's ids for the NEXT batch-creating call on this handle (consumed by it, whatever its outcome)
   const uint32_t* staged_sites = nullptr;
   uint64_t staged_count = 0;
@@ -256,10 +270,24 @@ struct dyn_aligner {
 };
 
 namespace dyneng {
-// what dyn_aligner_set_mem_budget leaves once the per-site table is taken off (0: no budget was set)
+// what dyn_aligner_set_mem_budget leaves once the per-site table and its histograms are taken off (0: no budget was set)
 inline uint64_t mem_budget_left(const dyn_aligner* a) {
   if (!a->mem_budget) return 0;
-  return a->mem_budget > a->d_site.bytes ? a->mem_budget - a->d_site.bytes : 1;
+  const uint64_t taken = a->d_site.bytes + a->d_shist.bytes;
+  return a->mem_budget > taken ? a->mem_budget - taken : 1;
+}
+// uint32 counters per site: under, the level bins, over, the dwell bins
+inline uint64_t site_hist_width(uint32_t bins) { return (uint64_t)bins + 2 + (uint64_t)dynk::SH_DWELL_BINS; }
+// the histograms a job submitted now counts into (nothing while the switch is off)
+inline SiteHist site_hist_now(const dyn_aligner* a) {
+  SiteHist h;
+  if (a->opt.site_histogram && a->d_shist.p && a->sh_bins) {
+    h.p = a->d_shist.as<unsigned int>();
+    h.bins = a->sh_bins;
+    h.lo = a->sh_lo;
+    h.inv_w = a->sh_inv_w;
+  }
+  return h;
 }
 // what a session is launched with (session_choose, session.cpp)
 struct SessionGeom {
@@ -343,6 +371,10 @@ struct dyn_batch {
   unsigned long long* ss_table = nullptr;
   uint64_t ss_num_sites = 0;
   std::vector<std::pair<uint32_t, uint32_t>> ss_ranges;
+  // the per-site histograms as they stood at submission (p == nullptr: off). A merged launch splits ss_ranges into the members
+  // submitted with the histograms on (sh_ranges) and the others (ss_plain_ranges)
+  dyneng::SiteHist ss_hist;
+  std::vector<std::pair<uint32_t, uint32_t>> sh_ranges, ss_plain_ranges;
   dyneng::DevBuf d_bm;                         // [3][n] uint32 low / high / edge_rows (band_margin_kernels.hpp), when asked for
   bool bm_ready = false;                       // the last job computed the margins into d_bm
   dyneng::PinnedBuf h_descs, h_state, h_rows;  // h_state/h_rows: D2H targets of the asynchronous path

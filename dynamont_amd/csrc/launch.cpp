@@ -294,7 +294,17 @@ std::vector<dynk::SiteSummary> site_summary_args(const dyn_batch* b) {
   if (!b->want.site_summary || !b->ss_table || !b->ss_num_sites || !b->has_sites || !b->d_sites.p) return {};
   // (a merged launch has ids only when a member that asked staged some: its ranges are never empty)
   unsigned long long* totals = b->ss_table + (uint64_t)dynk::SS_FIELDS * b->ss_num_sites;
-  return over_ranges(dynk::SiteSummary{b->d_sig.as<double>(), b->d_sites.as<uint32_t>(), b->ss_table, totals, (uint32_t)b->ss_num_sites, 0u, (uint32_t)b->n}, b->ss_ranges);
+  dynk::SiteSummary ss{b->d_sig.as<double>(), b->d_sites.as<uint32_t>(), b->ss_table, totals, (uint32_t)b->ss_num_sites, 0u, (uint32_t)b->n};
+  if (!b->want.site_histogram || !b->ss_hist.p) return over_ranges(ss, b->ss_ranges);
+  // the histograms: a merged launch's members submitted with them on (sh_ranges) count, the others (ss_plain_ranges) add to the table alone
+  std::vector<dynk::SiteSummary> out;
+  if (!b->ss_plain_ranges.empty()) out = over_ranges(ss, b->ss_plain_ranges);
+  ss.hist = b->ss_hist.p;
+  ss.bins = b->ss_hist.bins;
+  ss.hist_lo = b->ss_hist.lo;
+  ss.inv_w = b->ss_hist.inv_w;
+  for (const dynk::SiteSummary& x : over_ranges(ss, b->sh_ranges)) out.push_back(x);
+  return out;
 }
 
 std::vector<dynk::BandMargin> band_margin_args(const dyn_batch* b) {

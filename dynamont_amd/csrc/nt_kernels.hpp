@@ -309,9 +309,29 @@ struct SiteSummary {
   uint32_t num_sites;
   uint32_t read_lo, read_hi;  // the reads [read_lo, read_hi) (ReadDesc::read) contribute: the members of a merged launch
                               // that asked and staged ids
+  // the per-site histograms (dyn_aligner_set_site_histogram); hist == nullptr: off. An aggregate initialiser that stops at
+  // read_hi leaves them zero.
+  unsigned int* hist;         // [num_sites][bins + 2 + 16] under, level bins 1 .. bins, over, dwell bins 0 .. 15
+  uint32_t bins;
+  double hist_lo, inv_w;      // level bin of m: u = (m - hist_lo) * inv_w, inv_w = bins / (hi - lo)
 };
 void launch_site_summary(const ReadDesc* descs, int n_reads, uint32_t max_N, const ReadState* st, const TraceBuffers& tb,
                          const SiteSummary& ss, hipStream_t s);
+constexpr int SH_DWELL_BINS = 16;
+constexpr int SH_BINS_MAX = 254;
+constexpr int SQ_PROBS_MAX = 8;
+constexpr uint32_t SQ_NO_BIN = 0xFFFFFFFFu;
+// quantiles of a window of the per-site level histograms (k_site_quantiles, site_summary_kernels.hpp). out: uint32
+// [count] n, then rank, bin, below, in_bin as [count][n_probs] each
+struct SiteQuantiles {
+  const unsigned int* hist;   // the first site's counters; a site's bins + 2 + 16 counters are contiguous
+  uint32_t bins;
+  uint32_t count;             // sites of the window
+  int n_probs;                // 1 .. 8
+  double probs[SQ_PROBS_MAX];
+  uint32_t* out;
+};
+void launch_site_quantiles(const SiteQuantiles& sq, hipStream_t s);
 // per-border segment quality scores (segment_scores.hip, dyn_aligner_set_segment_scores): columns indexed like the output
 // rows, zeroed by the caller; median_delta == nullptr: not asked for
 struct ScoreCols {

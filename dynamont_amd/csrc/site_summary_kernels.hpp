@@ -21,6 +21,13 @@
 //   k_ssum_long   one 256-thread block per read that has a longer row: lanes sum chunks in parallel, lane 0 adds the chunk
 //                 sums in order (the chunk loop wraps beyond 256 chunks, rows above 16 384 samples)
 // Footprint: 256 threads, 2 KB of static LDS (k_ssum_long), no scratch -- they run beside a resident workgroup.
+//
+// The per-site histograms (dyn_aligner_set_site_histogram, ss.hist != nullptr): every row the table adds also counts into two
+// uint32 counters of its site's H = bins + 2 + 16 contiguous ones, [under, level bin 1 .. bins, over, dwell bin 0 .. 15]:
+//   level  u = __dmul_rn(__dsub_rn(m, lo), inv_w); u < 0: 0; u >= bins: bins + 1; otherwise 1 + (int)u
+//   dwell  min(31 - clz(L), 15)
+// with 32-bit device-scope atomics: exact while a site has fewer than 2^32 rows. k_site_quantiles reduces a window of the level
+// histograms to ranks and bins on the device (site_quantile_kernels.hpp).
 #pragma once
 
 #include "exact_sum_kernels.hpp"
@@ -45,6 +52,13 @@ __device__ __forceinline__ bool ss_accumulate(const SiteSummary& ss, uint32_t id
   xs_add128(cell + 3, lo, hi);
   xs_to_i128(rint(__dmul_rn(mm, XS_SCALE)), lo, hi);
   xs_add128(cell + 5, lo, hi);
+  if (ss.hist) {
+    unsigned int* h = ss.hist + (uint64_t)id * (ss.bins + 2u + (uint32_t)SH_DWELL_BINS);
+    const double u = __dmul_rn(__dsub_rn(m, ss.hist_lo), ss.inv_w);  // m is finite here, inv_w finite and > 0: u is no NaN
+    const uint32_t lb = u < 0.0 ? 0u : (u >= (double)ss.bins ? ss.bins + 1u : 1u + (uint32_t)(int)u);
+    atomicAdd(h + lb, 1u);
+    atomicAdd(h + ss.bins + 2u + (uint32_t)min(31 - __clz(L), SH_DWELL_BINS - 1), 1u);
+  }
   return true;
 }
 

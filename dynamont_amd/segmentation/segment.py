@@ -137,6 +137,11 @@ def parse(argv=None) -> Namespace:
                    help="per reference position across reads (the basecalls must be a MAPPED .bam): coverage, dwell and level "
                         "mean / sd of the reads' event means, summed on the GPU as exact integers, written as a TSV of the sites "
                         "with coverage > 0 in reference order (INTEGRATION.md section 3). One process only")
+    p.add_argument("--site-histogram", default="", metavar="BINS[:LO:HI]",
+                   help="with --site-summary FILE: also count, per reference position, a histogram of the reads' event means with "
+                        "BINS (2 .. 254) bins over [LO, HI) and one of their dwell on the GPU, and add the columns level_q25, "
+                        "level_median and level_q75 to FILE, found from the histograms on the GPU. Without LO:HI the range is "
+                        "the model's lowest and highest k-mer level widened by four of its largest standard deviations")
     p.add_argument("--kmer-summary", default="", metavar="PATH",
                    help="also write a per-k-mer summary of the run to PATH: a TSV in the model file's k-mer order with the "
                         "level (mean, stdev of the normalised signal) and dwell the run's segments showed per k-mer beside the "
@@ -946,7 +951,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             segment_scores: int = 0, border_confidence: int = 0, band_report: str = "", band: int = 400,
             guide_auto: int = 0, guide_rounds: int = 8, guide_rescue: int = 0, guide_rescue_margin: int = 1,
             posterior_samples: int = 0, sample_seed: int = 0, border_interval: float = 0.0,
-            soft_levels: bool = False, site_summary: str = "") -> None:
+            soft_levels: bool = False, site_summary: str = "", site_histogram: str = "") -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
@@ -964,6 +969,12 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
     if border_interval and (not 0.01 <= border_interval <= 0.999 or border_confidence or posterior_samples or guide_auto or guide_rescue):
         raise ValueError("--border-interval must be 0 or 0.01 .. 0.999 and is not combined with --border-confidence, "
                          "--posterior-samples, --guide-auto or --guide-rescue")
+    site_hist = None
+    if site_histogram:
+        from dynamont_amd.segmentation.utils import parse_site_histogram
+        if not site_summary:
+            raise ValueError("--site-histogram counts beside the per-site table: it needs --site-summary FILE")
+        site_hist = parse_site_histogram(site_histogram)
     site_refs = None
     if site_summary:
         # refused before anything is started: what the per-site table cannot do yet, and a BAM that is not mapped
@@ -1054,9 +1065,11 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
         # --site-summary, with the pipeline dry: the sites with coverage, a window of the table at a time
         if not site_summary:
             return
-        from dynamont_amd.segmentation.utils import write_site_summary
+        from dynamont_amd.segmentation.utils import SITE_QUANTILE_PROBS, write_site_summary
         num_sites = int(site_refs[1][-1])
-        written = write_site_summary(site_summary, aligner.site_summary, num_sites, *site_refs)
+        # --site-histogram: the three quantile columns, reduced on the GPU window by window beside the table's window
+        quantiles = (lambda lo, hi: aligner.site_quantiles(SITE_QUANTILE_PROBS, lo, hi)) if site_hist else None
+        written = write_site_summary(site_summary, aligner.site_summary, num_sites, *site_refs, quantiles=quantiles)
         t = aligner.site_summary(0, 0)["totals"]
         print(f"site summary written: {site_summary}: {written} sites with coverage; reads_ok {t['reads_ok']}, rows_added {t['rows_added']}, "
               f"samples_added {t['samples_added']}, rows_without_site {t['rows_without_site']}, rows_skipped {t['rows_skipped']}; "
@@ -1119,6 +1132,17 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                     aligner.set_site_summary(int(site_refs[1][-1]))
                 except MemoryError as error:
                     raise MemoryError(f"--site-summary: the table of {int(site_refs[1][-1])} sites (56 bytes each) does not fit: {error}") from None
+                if site_hist:
+                    from dynamont_amd.segmentation.utils import site_histogram_range
+                    bins, h_lo, h_hi = site_hist
+                    if h_lo is None:
+                        h_lo, h_hi = site_histogram_range(*aligner.model_table())
+                    try:
+                        aligner.set_site_histogram(bins, h_lo, h_hi)
+                    except MemoryError as error:
+                        raise MemoryError(f"--site-histogram: the counters of {int(site_refs[1][-1])} sites ({4 * (bins + 18)} bytes each) "
+                                          f"do not fit: {error}") from None
+                    print(f"site histogram: {bins} bins over [{h_lo!r}, {h_hi!r})", file=sys.stderr, flush=True)
             if band_report:
                 aligner.set_band_margin(True)
             if guide_auto:
@@ -1281,7 +1305,8 @@ def main(argv=None) -> None:
             border_confidence=args.border_confidence, band_report=args.band_report, band=args.band,
             guide_auto=args.guide_auto, guide_rounds=args.guide_rounds, guide_rescue=args.guide_rescue,
             guide_rescue_margin=args.guide_rescue_margin, posterior_samples=args.posterior_samples, sample_seed=args.sample_seed,
-            border_interval=args.border_interval, soft_levels=args.soft_levels, site_summary=args.site_summary)
+            border_interval=args.border_interval, soft_levels=args.soft_levels, site_summary=args.site_summary,
+            site_histogram=args.site_histogram)
     _stamp("segment() returned (aligner closed)")
     if argv is None and not int(__import__("os").environ.get("WORLD_SIZE", "1") or 1) > 1:
         # Invoked as the command (console script / python -m), single process, everything written and closed: leave without

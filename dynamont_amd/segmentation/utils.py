@@ -325,14 +325,69 @@ def site_summary_lines(summary: dict, lo: int, ref_names, offsets) -> list:
     return out
 
 
-def write_site_summary(path: str, fetch, num_sites: int, ref_names, offsets, window: int = 1 << 20) -> int:
+def write_site_summary(path: str, fetch, num_sites: int, ref_names, offsets, window: int = 1 << 20, quantiles=None) -> int:
     """--site-summary FILE: the header and one line per site with coverage > 0, in reference order. ``fetch(lo, hi)`` returns a
-    window of the table (Aligner.site_summary): a genome-sized table is never on the host at once. Returns the sites written."""
+    window of the table (Aligner.site_summary): a genome-sized table is never on the host at once. ``quantiles(lo, hi)``
+    (--site-histogram: Aligner.site_quantiles of SITE_QUANTILE_PROBS over the same window) adds the three columns of
+    SITE_QUANTILE_HEADER to every line. Returns the sites written."""
     written = 0
     with open(path, "w") as f:
-        f.write(SITE_SUMMARY_HEADER)
+        f.write(SITE_SUMMARY_HEADER if quantiles is None else SITE_SUMMARY_HEADER[:-1] + "\t" + SITE_QUANTILE_HEADER + "\n")
         for lo in range(0, int(num_sites), window):
-            lines = site_summary_lines(fetch(lo, min(lo + window, int(num_sites))), lo, ref_names, offsets)
+            hi = min(lo + window, int(num_sites))
+            summary = fetch(lo, hi)
+            lines = site_summary_lines(summary, lo, ref_names, offsets)
+            if quantiles is not None:
+                level = quantiles(lo, hi)["level"]
+                covered = np.flatnonzero(summary["n_rows"]).tolist()
+                lines = [line[:-1] + "".join("\t%r" % float(v) for v in level[i]) + "\n" for line, i in zip(lines, covered)]
             f.writelines(lines)
             written += len(lines)
     return written
+
+
+# ---- per-site histograms and quantiles (Aligner.set_site_histogram, dynamont-resquiggle --site-histogram) ----------------------
+SITE_QUANTILE_PROBS = (0.25, 0.5, 0.75)
+SITE_QUANTILE_HEADER = "level_q25\tlevel_median\tlevel_q75"
+
+
+def site_quantile_levels(rank, bin, below, in_bin, bins: int, lo: float, hi: float) -> np.ndarray:
+    """The level of every (site, probability) from what dyn_aligner_site_quantiles returns: the rank's
+    place inside its bin, interpolated over the bin's width w = (hi - lo) / bins,
+        lo + ((bin - 1) + (rank - below - 0.5) / in_bin) * w      for an interior bin 1 .. bins,
+    -inf for the under counter (bin 0), +inf for the over counter (bin bins + 1), NaN for a site without rows (bin 0xFFFFFFFF).
+    float64, the shape of ``bin``."""
+    b = np.asarray(bin, dtype=np.int64)
+    r, bl, ib = (np.asarray(v, dtype=np.float64) for v in (rank, below, in_bin))
+    w = (float(hi) - float(lo)) / int(bins)
+    out = np.full(b.shape, np.nan, dtype=np.float64)
+    inner = (b >= 1) & (b <= int(bins))
+    out[inner] = float(lo) + ((b[inner] - 1) + (r[inner] - bl[inner] - 0.5) / ib[inner]) * w
+    out[b == 0] = -np.inf
+    out[b == int(bins) + 1] = np.inf
+    return out
+
+
+def parse_site_histogram(text: str):
+    """--site-histogram BINS[:LO:HI] -> (bins, lo, hi), lo = hi = None when the range is left to the model table
+    (site_histogram_range). ValueError for anything else."""
+    parts = str(text).split(":")
+    try:
+        if len(parts) not in (1, 3):
+            raise ValueError
+        bins = int(parts[0])
+        lo, hi = (float(parts[1]), float(parts[2])) if len(parts) == 3 else (None, None)
+    except ValueError:
+        raise ValueError(f"--site-histogram {text!r}: expected BINS or BINS:LO:HI (an integer and two numbers)") from None
+    if not 2 <= bins <= 254:
+        raise ValueError(f"--site-histogram {text!r}: BINS must be 2 .. 254")
+    if lo is not None and not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError(f"--site-histogram {text!r}: LO and HI must be finite with LO < HI")
+    return bins, lo, hi
+
+
+def site_histogram_range(level_mean, level_stdv):
+    """the default range of --site-histogram, from the model table (Aligner.model_table()): four of the widest k-mer's standard
+    deviations beyond the lowest and the highest k-mer level"""
+    mean, sd = np.asarray(level_mean, dtype=np.float64), np.asarray(level_stdv, dtype=np.float64)
+    return float(mean.min() - 4.0 * sd.max()), float(mean.max() + 4.0 * sd.max())

@@ -615,8 +615,41 @@ int dyn_aligner_stage_site_ids(dyn_aligner* a, const uint32_t* site_ids, uint64_
 int dyn_aligner_site_summary_fetch(dyn_aligner* a, uint64_t lo, uint64_t hi, uint64_t* n_rows, uint64_t* n_samples,
                                    uint64_t* dwell_sq, uint64_t* m1_lo, uint64_t* m1_hi, uint64_t* m2_lo, uint64_t* m2_hi,
                                    uint64_t totals[5]);
-/* Zeroes the table and the totals (same conditions as the fetch). */
+/* Zeroes the table and the totals (same conditions as the fetch), and the per-site histograms when the handle has any. */
 int dyn_aligner_site_summary_reset(dyn_aligner* a);
+/* (added within ABI 10: a caller that must know looks the symbol up) Per-site level and dwell HISTOGRAMS beside the table
+ * (INTEGRATION.md section 3): what a median, a quantile, a Kolmogorov-Smirnov test or a mixture fit per site needs and two
+ * moments cannot give. `bins` in 2 .. 254 and finite lo < hi turn them on; the handle must have a table
+ * (dyn_aligner_set_site_summary(a, num_sites > 0) first). Per site H = bins + 2 + 16 uint32 counters, contiguous:
+ *   [under, level bin 1 .. bins, over, dwell bin 0 .. 15]           (num_sites * H * 4 bytes of device memory)
+ * Every row the table ADDS (id < num_sites, a finite m with m * m < 2^64, an ok read of a job with staged ids) counts once in a
+ * level counter and once in a dwell counter, in the same pass over the signal; rows counted in rows_without_site or rows_skipped
+ * touch none, so per site both groups sum to n_rows. With inv_w = (double)bins / (hi - lo), formed once on the host:
+ *   level   u = (m - lo) * inv_w, one IEEE subtraction and one IEEE product of the table's m (dyn_event_out's level_mean, bit
+ *           for bit); u < 0: counter 0 (under); u >= bins: counter bins + 1 (over); otherwise counter 1 + (int)u
+ *   dwell   min(31 - clz(L), 15) of the row's L samples: 1, 2-3, 4-7, ... 2^15 and above
+ * The counters are exact integers (32-bit device-scope atomic adds) while a site has fewer than 2^32 rows -- the defined domain --
+ * and the same bits whatever the launch path, the merging of tickets or the order of the atomics. bins = 0 stops the counting and
+ * keeps the counters fetchable. A call that changes (bins, lo, hi) first waits for every job in flight, then starts zeroed
+ * counters. dyn_aligner_set_site_summary with ANOTHER num_sites releases the histograms and turns them off (set them again);
+ * num_sites = 0 stops both from growing. The counters count against dyn_aligner_set_mem_budget as the table does.
+ * DYN_ERR_INVALID_ARGUMENT for bins outside 0, 2 .. 254, bounds that are not finite with lo < hi (or whose bins / (hi - lo) is
+ * not finite), or a handle without a table; DYN_ERR_OUT_OF_MEMORY when the counters do not fit. */
+int dyn_aligner_set_site_histogram(dyn_aligner* a, int bins, double lo, double hi);
+/* The counters of the sites [site_lo, site_hi) after every job that has COMPLETED (the conditions of
+ * dyn_aligner_site_summary_fetch): level [n][bins + 2] and dwell [n][16], n = site_hi - site_lo. */
+int dyn_aligner_site_histogram_fetch(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi, uint32_t* level, uint32_t* dwell);
+/* Quantiles of the level histograms of the sites [site_lo, site_hi), reduced on the device (the histograms themselves never
+ * cross to the host). n_probs in 1 .. 8, every probs[q] in [0, 1]. Per site, over its B = bins + 2 level counters:
+ *   n[site]   their sum
+ *   rank      k = min(max((uint32)ceil(q * n), 1), n)      (q * n: one IEEE product)
+ *   bin       the smallest counter index whose inclusive prefix sum is >= k (0: under, bins + 1: over)
+ *   below     the prefix sum in front of that counter;  in_bin: that counter's value
+ * rank, bin, below and in_bin are [n_sites][n_probs]. A site with n = 0 has bin = 0xFFFFFFFF and rank = below = in_bin = 0. The
+ * k-th smallest event mean of the site lies in `bin`; interpolated inside it, it is
+ * lo + ((bin - 1) + (rank - below - 0.5) / in_bin) * (hi - lo) / bins. */
+int dyn_aligner_site_quantiles(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi, const double* probs, int n_probs, uint32_t* n,
+                               uint32_t* rank, uint32_t* bin, uint32_t* below, uint32_t* in_bin);
 /* The rule of mode 1 for one read, given its k-mer codes (dyn_validate_batch) and signal length: 0 = no structural tie;
  * otherwise the number of forward rows that run in the strict arithmetic (UINT32_MAX: all of them). Host only. */
 uint32_t dyn_tie_rows(const dyn_aligner* a, const int32_t* kmers, uint64_t n_kmers, uint64_t signal_len);
