@@ -697,6 +697,15 @@ def int128_of_limbs(lo, hi) -> np.ndarray:
     return out
 
 
+def limbs_of_int128(values):
+    """the inverse of int128_of_limbs: (lo, hi) uint64 arrays of the 128-bit two's complement of Python ints"""
+    v = np.empty(len(values), dtype=object)
+    v[:] = [int(x) for x in values]
+    if not len(v):
+        return np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint64)
+    return (v & 0xFFFFFFFFFFFFFFFF).astype(np.uint64), ((v >> 64) & 0xFFFFFFFFFFFFFFFF).astype(np.uint64)
+
+
 SITE_SUMMARY_TOTALS = ("reads_ok", "rows_added", "samples_added", "rows_without_site", "rows_skipped")
 
 
@@ -1090,6 +1099,75 @@ class Aligner:
         bins, h_lo, h_hi = self._site_histogram
         return {"n": cnt, "rank": cols[0], "bin": cols[1], "below": cols[2], "in_bin": cols[3], "probs": q,
                 "level": site_quantile_levels(cols[0], cols[1], cols[2], cols[3], bins, h_lo, h_hi)}
+
+    def site_summary_add(self, lo: int, summary: dict, histogram: dict | None = None) -> None:
+        """dyn_aligner_site_summary_add: adds a table shaped like ``site_summary()``'s -- ``n_rows``, ``n_samples``, ``dwell_sq``,
+        ``M1`` / ``M2`` as Python ints, ``totals`` optional -- into the sites [lo, lo + len(n_rows)) of the device table, and the
+        counters of ``histogram`` (shaped like ``site_histogram()``'s) into the histograms, all as exact integers (INTEGRATION.md
+        section 3): a table saved by an earlier run back onto the device, or two runs' tables into one. ValueError when
+        ``histogram["edges"]`` are not bit-equal to the handle's."""
+        lo = int(lo)
+        cols = [np.ascontiguousarray(summary[k], dtype=np.uint64).reshape(-1) for k in ("n_rows", "n_samples", "dwell_sq")]
+        n = cols[0].size
+        for k in ("M1", "M2"):
+            cols.extend(limbs_of_int128(summary[k]))
+        if any(c.size != n for c in cols):
+            raise ValueError("site_summary_add: the columns of the summary differ in length")
+        totals = None
+        if summary.get("totals") is not None:
+            t = summary["totals"]
+            totals = np.array([int(t[k]) for k in SITE_SUMMARY_TOTALS] if isinstance(t, dict) else [int(x) for x in t], dtype=np.uint64)
+            if totals.size != 5:
+                raise ValueError("site_summary_add: five totals")
+        level = dwell = None
+        if histogram is not None:
+            bins, h_lo, h_hi = self._site_histogram or (0, 0.0, 0.0)
+            mine = h_lo + np.arange(bins + 1, dtype=np.float64) * ((h_hi - h_lo) / bins) if bins else np.zeros(0)
+            edges = np.ascontiguousarray(histogram["edges"], dtype=np.float64)
+            if bins and (edges.shape != mine.shape or edges.tobytes() != mine.tobytes()):
+                raise ValueError("site_summary_add: the histogram's edges are not the handle's (set_site_histogram%r)" % ((bins, h_lo, h_hi),))
+            level = np.ascontiguousarray(histogram["level"], dtype=np.uint32)
+            dwell = np.ascontiguousarray(histogram["dwell"], dtype=np.uint32)
+            if bins and (level.shape != (n, bins + 2) or dwell.shape != (n, 16)):
+                raise ValueError("site_summary_add: level must be [n, bins + 2] and dwell [n, 16] for the summary's n sites")
+        rc = self._L.dyn_aligner_site_summary_add(self._h, lo, lo + n, *[_ptr(c, N.c_u64_p) for c in cols],
+                                                  None if totals is None else _ptr(totals, N.c_u64_p),
+                                                  None if level is None else _ptr(level, N.c_u32_p),
+                                                  None if dwell is None else _ptr(dwell, N.c_u32_p))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+
+    def site_compare(self, lo: int = 0, hi: int | None = None, other_lo: int | None = None) -> dict:
+        """dyn_aligner_site_compare: the sites [lo, hi) (default: the first half of the table) against the sites starting at
+        ``other_lo`` (default ``num_sites // 2 + lo``: the second sample of a table of 2 N sites whose ids were offset by N), pair
+        by pair on the GPU; the histograms stay there. ``n_a``, ``n_b``, ``level_at``, ``dwell_at``: uint32; ``level_num``,
+        ``dwell_num``: uint64; ``level_side``, ``dwell_side``: int32. ``level_d`` / ``dwell_d``:
+        float64, the binned Kolmogorov-Smirnov statistic num / (n_a * n_b), NaN where either side is empty; ``level_edge``:
+        the level at the upper edge of counter ``level_at`` (``lo_h + level_at * w``; +inf for the over counter, NaN where
+        ``level_at`` is 0xFFFFFFFF)."""
+        half = self._site_table // 2
+        lo = int(lo)
+        hi = half if hi is None else int(hi)
+        other_lo = half + lo if other_lo is None else int(other_lo)
+        n = max(0, hi - lo)
+        u32 = [np.zeros(n, dtype=np.uint32) for _ in range(4)]
+        u64 = [np.zeros(n, dtype=np.uint64) for _ in range(2)]
+        i32 = [np.zeros(n, dtype=np.int32) for _ in range(2)]
+        rc = self._L.dyn_aligner_site_compare(self._h, lo, hi, other_lo, _ptr(u32[0], N.c_u32_p), _ptr(u32[1], N.c_u32_p),
+                                              _ptr(u64[0], N.c_u64_p), _ptr(u32[2], N.c_u32_p), _ptr(i32[0], N.c_i32_p),
+                                              _ptr(u64[1], N.c_u64_p), _ptr(u32[3], N.c_u32_p), _ptr(i32[1], N.c_i32_p))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        bins, h_lo, h_hi = self._site_histogram
+        den = u32[0].astype(np.float64) * u32[1].astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            level_d = np.where(den > 0, u64[0].astype(np.float64) / den, np.nan)
+            dwell_d = np.where(den > 0, u64[1].astype(np.float64) / den, np.nan)
+        at = u32[2].astype(np.float64)
+        edge = h_lo + at * ((h_hi - h_lo) / bins)
+        edge = np.where(u32[2] == 0xFFFFFFFF, np.nan, np.where(u32[2] == bins + 1, np.inf, edge))
+        return {"n_a": u32[0], "n_b": u32[1], "level_num": u64[0], "level_at": u32[2], "level_side": i32[0], "dwell_num": u64[1],
+                "dwell_at": u32[3], "dwell_side": i32[1], "level_d": level_d, "dwell_d": dwell_d, "level_edge": edge}
 
     def set_band_margin(self, on: bool) -> None:
         """dyn_aligner_set_band_margin: align(calc_probabilities=True) jobs submitted while on also report, per read, how
@@ -1651,6 +1729,16 @@ class MultiAligner:
         """Not supported, as ``set_site_summary`` is not: the histograms live beside ONE device's table. Use one ``Aligner`` per
         device and add the counters (they are integers)."""
         raise NotImplementedError("MultiAligner has no per-site histograms (Aligner.set_site_histogram): use one Aligner per device "
+                                  "and add their tables")
+
+    def site_summary_add(self, lo: int, summary: dict, histogram: dict | None = None) -> None:
+        """Not supported, as ``set_site_summary`` is not."""
+        raise NotImplementedError("MultiAligner has no per-site summary (Aligner.site_summary_add): use one Aligner per device "
+                                  "and add their tables")
+
+    def site_compare(self, lo: int = 0, hi: int | None = None, other_lo: int | None = None) -> dict:
+        """Not supported, as ``set_site_histogram`` is not."""
+        raise NotImplementedError("MultiAligner has no per-site histograms (Aligner.site_compare): use one Aligner per device "
                                   "and add their tables")
 
     def _cap(self, seq_off) -> int:

@@ -451,6 +451,8 @@ void dyn_aligner_destroy(dyn_aligner* a) {
     a->d_site.release();
     a->d_shist.release();
     a->d_squant.release();
+    a->d_scomp.release();
+    a->d_sadd.release();
     park_pool_buffer(a->device, 0, a->ws);
     park_pool_buffer(a->device, 1, a->lpe);
     park_pool_buffer(a->device, 2, a->bits);
@@ -1000,6 +1002,111 @@ int dyn_aligner_site_quantiles(dyn_aligner* a, uint64_t site_lo, uint64_t site_h
     std::memcpy(n + o, h.data(), cnt * sizeof(uint32_t));
     uint32_t* cols[4] = {rank, bin, below, in_bin};
     for (int f = 0; f < 4; ++f) std::memcpy(cols[f] + o * P, h.data() + cnt + (uint64_t)f * cnt * P, cnt * P * sizeof(uint32_t));
+  }
+  return DYN_OK;
+}
+
+// ---- two samples in one table: the exact add of host columns and the comparison of two windows (site_compare_kernels.hpp) ----
+int dyn_aligner_site_summary_add(dyn_aligner* a, uint64_t lo, uint64_t hi, const uint64_t* n_rows, const uint64_t* n_samples,
+                                 const uint64_t* dwell_sq, const uint64_t* m1_lo, const uint64_t* m1_hi, const uint64_t* m2_lo,
+                                 const uint64_t* m2_hi, const uint64_t totals[5], const uint32_t* level, const uint32_t* dwell) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  const char* who = "dyn_aligner_site_summary_add";
+  auto fail = [&](const std::string& msg) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = std::string(who) + ": " + msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  };
+  // refused before the device is looked at: the same text on a handle without one
+  if ((level == nullptr) != (dwell == nullptr)) return fail("level and dwell counters are given together or not at all");
+  const uint64_t* cols[7] = {n_rows, n_samples, dwell_sq, m1_lo, m1_hi, m2_lo, m2_hi};
+  if (lo < hi)
+    for (const uint64_t* c : cols)
+      if (!c) return DYN_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (level) {
+    if (int rc = site_histogram_quiet(a, who, lo, hi)) return rc;
+  } else {
+    if (int rc = site_summary_quiet(a, who)) return rc;
+    if (lo > hi || hi > a->num_sites)
+      return fail("[" + std::to_string(lo) + ", " + std::to_string(hi) + ") is not a range of the table's " + std::to_string(a->num_sites) + " sites");
+  }
+  if (lo == hi) return DYN_OK;  // an empty window touches nothing, the totals included
+  const uint64_t F = (uint64_t)dynk::SS_FIELDS, step = 1ull << 20;
+  const uint64_t B = (uint64_t)a->sh_bins + 2, D = (uint64_t)dynk::SH_DWELL_BINS, H = level ? B + D : 0;
+  const uint64_t most = std::min(step, hi - lo);
+  HIP_TRY(a, a->d_sadd.ensure(most * (F * sizeof(uint64_t) + H * sizeof(uint32_t))));
+  std::vector<uint64_t> hc(F * most);
+  std::vector<uint32_t> hh(H * most);
+  dynk::SiteAdd sa{};
+  sa.totals = a->d_site.as<unsigned long long>() + F * a->num_sites;
+  sa.cols = a->d_sadd.as<unsigned long long>();
+  sa.width = (uint32_t)H;
+  for (uint64_t s0 = lo; s0 < hi; s0 += step) {
+    const uint64_t cnt = std::min(step, hi - s0), o = s0 - lo;
+    for (uint64_t c = 0; c < cnt; ++c)
+      for (uint64_t f = 0; f < F; ++f) hc[F * c + f] = cols[f][o + c];
+    HIP_TRY(a, hipMemcpyAsync(a->d_sadd.p, hc.data(), F * cnt * sizeof(uint64_t), hipMemcpyHostToDevice, a->s_get));
+    sa.acc = a->d_site.as<unsigned long long>() + F * s0;
+    sa.count = (uint32_t)cnt;
+    if (level) {
+      for (uint64_t c = 0; c < cnt; ++c) {
+        std::memcpy(hh.data() + H * c, level + B * (o + c), B * sizeof(uint32_t));
+        std::memcpy(hh.data() + H * c + B, dwell + D * (o + c), D * sizeof(uint32_t));
+      }
+      unsigned int* staged = reinterpret_cast<unsigned int*>(a->d_sadd.as<unsigned long long>() + F * cnt);
+      HIP_TRY(a, hipMemcpyAsync(staged, hh.data(), H * cnt * sizeof(uint32_t), hipMemcpyHostToDevice, a->s_get));
+      sa.hist = a->d_shist.as<unsigned int>() + H * s0;
+      sa.counters = staged;
+    }
+    sa.add_totals = (totals && s0 == lo) ? 1 : 0;  // the caller's totals once, with the first window
+    for (int f = 0; f < dynk::SS_TOTALS; ++f) sa.totals_in[f] = sa.add_totals ? totals[f] : 0ull;
+    dynk::launch_site_add(sa, a->s_get);
+    HIP_TRY(a, hipGetLastError());
+    HIP_TRY(a, hipStreamSynchronize(a->s_get));  // (the host vectors are filled again for the next window)
+  }
+  return DYN_OK;
+}
+
+int dyn_aligner_site_compare(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi, uint64_t other_lo, uint32_t* n_a, uint32_t* n_b,
+                             uint64_t* level_num, uint32_t* level_at, int32_t* level_side, uint64_t* dwell_num, uint32_t* dwell_at,
+                             int32_t* dwell_side) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  if (site_lo < site_hi && (!n_a || !n_b || !level_num || !level_at || !level_side || !dwell_num || !dwell_at || !dwell_side))
+    return DYN_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = site_histogram_quiet(a, "dyn_aligner_site_compare", site_lo, site_hi)) return rc;
+  const uint64_t n = site_hi - site_lo;
+  if (other_lo > a->num_sites || n > a->num_sites - other_lo) {
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = "dyn_aligner_site_compare: the other window [" + std::to_string(other_lo) + ", " + std::to_string(other_lo) + " + " +
+                    std::to_string(n) + ") does not end inside the table's " + std::to_string(a->num_sites) + " sites";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  if (n == 0) return DYN_OK;
+  const uint64_t H = site_hist_width(a->sh_bins), step = 1ull << 20, most = std::min(step, n);
+  HIP_TRY(a, a->d_scomp.ensure((uint64_t)dynk::SC_PAIR_BYTES * most));
+  std::vector<uint64_t> h((uint64_t)dynk::SC_PAIR_BYTES / 8 * most);
+  dynk::SiteCompare sc{};
+  sc.bins = a->sh_bins;
+  sc.out = a->d_scomp.as<unsigned long long>();
+  for (uint64_t o = 0; o < n; o += step) {
+    const uint64_t cnt = std::min(step, n - o);
+    sc.hist_a = a->d_shist.as<unsigned int>() + H * (site_lo + o);
+    sc.hist_b = a->d_shist.as<unsigned int>() + H * (other_lo + o);
+    sc.count = (uint32_t)cnt;
+    dynk::launch_site_compare(sc, a->s_get);
+    HIP_TRY(a, hipGetLastError());
+    HIP_TRY(a, copy_out(a, h.data(), sc.out, (uint64_t)dynk::SC_PAIR_BYTES * cnt));  // (behind the kernel on the same stream)
+    std::memcpy(level_num + o, h.data(), cnt * sizeof(uint64_t));
+    std::memcpy(dwell_num + o, h.data() + cnt, cnt * sizeof(uint64_t));
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(h.data() + 2 * cnt);
+    std::memcpy(n_a + o, w, cnt * sizeof(uint32_t));
+    std::memcpy(n_b + o, w + cnt, cnt * sizeof(uint32_t));
+    std::memcpy(level_at + o, w + 2 * cnt, cnt * sizeof(uint32_t));
+    std::memcpy(dwell_at + o, w + 3 * cnt, cnt * sizeof(uint32_t));
+    std::memcpy(level_side + o, w + 4 * cnt, cnt * sizeof(int32_t));
+    std::memcpy(dwell_side + o, w + 5 * cnt, cnt * sizeof(int32_t));
   }
   return DYN_OK;
 }

@@ -332,6 +332,32 @@ struct SiteQuantiles {
   uint32_t* out;
 };
 void launch_site_quantiles(const SiteQuantiles& sq, hipStream_t s);
+constexpr uint32_t SC_NO_AT = 0xFFFFFFFFu;
+constexpr int SC_PAIR_BYTES = 2 * 8 + 6 * 4;
+// two windows of the per-site histograms compared pair by pair (k_site_compare, site_compare_kernels.hpp). out, SC_PAIR_BYTES per
+// pair: uint64 [count] level_num, dwell_num, then uint32 [count] n_a, n_b, level_at, dwell_at, level_side, dwell_side (the sides
+// as int32 bits)
+struct SiteCompare {
+  const unsigned int* hist_a; // the first site's counters of either window; a site's bins + 2 + 16 counters are contiguous
+  const unsigned int* hist_b;
+  uint32_t bins;
+  uint32_t count;             // pairs of the window
+  unsigned long long* out;
+};
+void launch_site_compare(const SiteCompare& sc, hipStream_t s);
+// host columns added into a window of the table and, optionally, of the counters (k_site_add, site_compare_kernels.hpp)
+struct SiteAdd {
+  unsigned long long* acc;          // the window's first cell of the table: [count][7]
+  unsigned long long* totals;       // the table's [5] totals
+  const unsigned long long* cols;   // staged [count][7], the table's own field order
+  unsigned int* hist;               // the window's first counter, [count][width]; nullptr: the table alone
+  const unsigned int* counters;     // staged [count][width]
+  uint32_t count;
+  uint32_t width;                   // bins + 2 + 16
+  int add_totals;                   // 0: totals_in is not added
+  unsigned long long totals_in[SS_TOTALS];
+};
+void launch_site_add(const SiteAdd& sa, hipStream_t s);
 // per-border segment quality scores (segment_scores.hip, dyn_aligner_set_segment_scores): columns indexed like the output
 // rows, zeroed by the caller; median_delta == nullptr: not asked for
 struct ScoreCols {

@@ -1,6 +1,7 @@
 // site_summary.hip -- per-site level summary of a run (dyn_aligner_set_site_summary): coverage, dwell and the sums of the
 // reads' event means per caller-supplied site id, accumulated on the handle as exact integers while the switch is on. The
 // kernels and the definition are in site_summary_kernels.hpp (shared with tests/device_math/site_summary.hip).
+#include "site_compare_kernels.hpp"
 #include "site_quantile_kernels.hpp"
 #include "site_summary_kernels.hpp"
 
@@ -13,5 +14,11 @@ void launch_site_summary(const ReadDesc* descs, int n_reads, uint32_t max_N, con
 
 // dyn_aligner_site_quantiles: one window of the level histograms into its staging buffer
 void launch_site_quantiles(const SiteQuantiles& sq, hipStream_t s) { launch_site_quantiles_kernel(sq, s); }
+
+// dyn_aligner_site_compare: one window of site pairs into its staging buffer
+void launch_site_compare(const SiteCompare& sc, hipStream_t s) { launch_site_compare_kernel(sc, s); }
+
+// dyn_aligner_site_summary_add: one staged window into the table and its counters
+void launch_site_add(const SiteAdd& sa, hipStream_t s) { launch_site_add_kernel(sa, s); }
 
 }  // namespace dynk

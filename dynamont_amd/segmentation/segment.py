@@ -142,6 +142,15 @@ def parse(argv=None) -> Namespace:
                         "BINS (2 .. 254) bins over [LO, HI) and one of their dwell on the GPU, and add the columns level_q25, "
                         "level_median and level_q75 to FILE, found from the histograms on the GPU. Without LO:HI the range is "
                         "the model's lowest and highest k-mer level widened by four of its largest standard deviations")
+    p.add_argument("--site-table-out", default="", metavar="TABLE.npz",
+                   help="with --site-summary FILE: also save the run's per-site table (and, with --site-histogram, its histograms) "
+                        "as exact integers once the pipeline is dry: the covered sites as sparse columns in an .npz, for a later "
+                        "run's --site-control")
+    p.add_argument("--site-control", default="", metavar="TABLE.npz",
+                   help="with --site-summary FILE and --site-histogram: compare the run, per reference position, against the table a "
+                        "control run saved with --site-table-out (the same references, the same histogram bins and range, bit for "
+                        "bit). FILE gains control_coverage, ks_d, ks_p, ks_level, ks_side, dwell_ks_d, welch_t and welch_df: a "
+                        "binned Kolmogorov-Smirnov statistic found on the GPU from both histograms, and Welch's t from both tables")
     p.add_argument("--kmer-summary", default="", metavar="PATH",
                    help="also write a per-k-mer summary of the run to PATH: a TSV in the model file's k-mer order with the "
                         "level (mean, stdev of the normalised signal) and dwell the run's segments showed per k-mer beside the "
@@ -951,7 +960,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             segment_scores: int = 0, border_confidence: int = 0, band_report: str = "", band: int = 400,
             guide_auto: int = 0, guide_rounds: int = 8, guide_rescue: int = 0, guide_rescue_margin: int = 1,
             posterior_samples: int = 0, sample_seed: int = 0, border_interval: float = 0.0,
-            soft_levels: bool = False, site_summary: str = "", site_histogram: str = "") -> None:
+            soft_levels: bool = False, site_summary: str = "", site_histogram: str = "", site_table_out: str = "",
+            site_control: str = "") -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
@@ -975,7 +985,13 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
         if not site_summary:
             raise ValueError("--site-histogram counts beside the per-site table: it needs --site-summary FILE")
         site_hist = parse_site_histogram(site_histogram)
+    if site_table_out and not site_summary:
+        raise ValueError("--site-table-out saves the per-site table: it needs --site-summary FILE")
+    if site_control and not (site_summary and site_hist):
+        raise ValueError("--site-control compares the per-site histograms of the run and the control: it needs --site-summary FILE and "
+                         "--site-histogram BINS[:LO:HI]")
     site_refs = None
+    control_table = None
     if site_summary:
         # refused before anything is started: what the per-site table cannot do yet, and a BAM that is not mapped
         from dynamont_amd.bam_io import bam_references
@@ -991,6 +1007,13 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
         site_refs = (names, contig_offsets(lengths))
         if int(site_refs[1][-1]) >= DYN_SITE_NONE or int(site_refs[1][-1]) == 0:
             raise ValueError(f"--site-summary: the references hold {int(site_refs[1][-1])} positions; the table takes 1 .. 4294967294")
+        if site_control:
+            # refused before anything is started: a control of other references, without histograms or of other bins
+            from dynamont_amd.segmentation.utils import check_site_control, load_site_table
+            control_table = load_site_table(site_control)
+            check_site_control(control_table, site_control, names, lengths, site_hist)
+            if 2 * int(site_refs[1][-1]) >= DYN_SITE_NONE:
+                raise ValueError(f"--site-control: the run and the control take 2 x {int(site_refs[1][-1])} sites; the table takes up to 4294967294")
     from dynamont_amd import parallel
     comm, local_rank = parallel.init_from_env()
     rank, world = (comm.rank, comm.world) if comm else (0, 1)
@@ -1069,7 +1092,18 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
         num_sites = int(site_refs[1][-1])
         # --site-histogram: the three quantile columns, reduced on the GPU window by window beside the table's window
         quantiles = (lambda lo, hi: aligner.site_quantiles(SITE_QUANTILE_PROBS, lo, hi)) if site_hist else None
-        written = write_site_summary(site_summary, aligner.site_summary, num_sites, *site_refs, quantiles=quantiles)
+        control = None
+        if control_table is not None:
+            # --site-control: the control sits in [N, 2N); compared on the GPU window by window beside the table's window
+            from dynamont_amd.segmentation.utils import site_control_columns
+            control = lambda lo, hi, run: site_control_columns(aligner.site_compare(lo, hi, num_sites + lo), run,  # noqa: E731
+                                                               aligner.site_summary(num_sites + lo, num_sites + hi))
+        written = write_site_summary(site_summary, aligner.site_summary, num_sites, *site_refs, quantiles=quantiles, control=control)
+        if site_table_out:
+            from dynamont_amd.bam_io import bam_references
+            from dynamont_amd.segmentation.utils import save_site_table
+            saved = save_site_table(site_table_out, aligner, *bam_references(basecalls), lo=0, hi=num_sites)   # the run's half only
+            print(f"site table written: {site_table_out}: {saved} sites with coverage", file=sys.stderr, flush=True)
         t = aligner.site_summary(0, 0)["totals"]
         print(f"site summary written: {site_summary}: {written} sites with coverage; reads_ok {t['reads_ok']}, rows_added {t['rows_added']}, "
               f"samples_added {t['samples_added']}, rows_without_site {t['rows_without_site']}, rows_skipped {t['rows_skipped']}; "
@@ -1129,7 +1163,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                 aligner.set_kmer_summary(True)
             if site_summary:
                 try:
-                    aligner.set_site_summary(int(site_refs[1][-1]))
+                    aligner.set_site_summary(int(site_refs[1][-1]) * (2 if control_table is not None else 1))  # --site-control: [N, 2N)
                 except MemoryError as error:
                     raise MemoryError(f"--site-summary: the table of {int(site_refs[1][-1])} sites (56 bytes each) does not fit: {error}") from None
                 if site_hist:
@@ -1143,6 +1177,12 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                         raise MemoryError(f"--site-histogram: the counters of {int(site_refs[1][-1])} sites ({4 * (bins + 18)} bytes each) "
                                           f"do not fit: {error}") from None
                     print(f"site histogram: {bins} bins over [{h_lo!r}, {h_hi!r})", file=sys.stderr, flush=True)
+                    if control_table is not None:
+                        # before the first batch: the control into [N, 2N). (A range left to the model table is known only now.)
+                        from dynamont_amd.segmentation.utils import check_site_control, load_site_control
+                        check_site_control(control_table, site_control, site_refs[0], control_table["ref_lengths"], (bins, h_lo, h_hi))
+                        added = load_site_control(aligner, control_table, int(site_refs[1][-1]))
+                        print(f"site control: {site_control}: {added} sites with coverage loaded", file=sys.stderr, flush=True)
             if band_report:
                 aligner.set_band_margin(True)
             if guide_auto:
@@ -1305,7 +1345,8 @@ def main(argv=None) -> None:
             border_confidence=args.border_confidence, band_report=args.band_report, band=args.band,
             guide_auto=args.guide_auto, guide_rounds=args.guide_rounds, guide_rescue=args.guide_rescue,
             guide_rescue_margin=args.guide_rescue_margin, posterior_samples=args.posterior_samples, sample_seed=args.sample_seed,
-            border_interval=args.border_interval, soft_levels=args.soft_levels, site_summary=args.site_summary,
+            border_interval=args.border_interval, soft_levels=args.soft_levels, site_summary=args.site_summary, site_table_out=args.site_table_out,
+            site_control=args.site_control,
             site_histogram=args.site_histogram)
     _stamp("segment() returned (aligner closed)")
     if argv is None and not int(__import__("os").environ.get("WORLD_SIZE", "1") or 1) > 1:

@@ -325,14 +325,17 @@ def site_summary_lines(summary: dict, lo: int, ref_names, offsets) -> list:
     return out
 
 
-def write_site_summary(path: str, fetch, num_sites: int, ref_names, offsets, window: int = 1 << 20, quantiles=None) -> int:
+def write_site_summary(path: str, fetch, num_sites: int, ref_names, offsets, window: int = 1 << 20, quantiles=None, control=None) -> int:
     """--site-summary FILE: the header and one line per site with coverage > 0, in reference order. ``fetch(lo, hi)`` returns a
     window of the table (Aligner.site_summary): a genome-sized table is never on the host at once. ``quantiles(lo, hi)``
     (--site-histogram: Aligner.site_quantiles of SITE_QUANTILE_PROBS over the same window) adds the three columns of
-    SITE_QUANTILE_HEADER to every line. Returns the sites written."""
+    SITE_QUANTILE_HEADER to every line. ``control(lo, hi)`` (--site-control: ``site_control_columns`` over the same window) returns
+    one string per site of the window, the eight columns of SITE_CONTROL_HEADER, added to every line behind the others. Sites are
+    written when the RUN has coverage. Returns the sites written."""
     written = 0
     with open(path, "w") as f:
-        f.write(SITE_SUMMARY_HEADER if quantiles is None else SITE_SUMMARY_HEADER[:-1] + "\t" + SITE_QUANTILE_HEADER + "\n")
+        header = SITE_SUMMARY_HEADER if quantiles is None else SITE_SUMMARY_HEADER[:-1] + "\t" + SITE_QUANTILE_HEADER + "\n"
+        f.write(header if control is None else header[:-1] + "\t" + SITE_CONTROL_HEADER + "\n")
         for lo in range(0, int(num_sites), window):
             hi = min(lo + window, int(num_sites))
             summary = fetch(lo, hi)
@@ -341,6 +344,9 @@ def write_site_summary(path: str, fetch, num_sites: int, ref_names, offsets, win
                 level = quantiles(lo, hi)["level"]
                 covered = np.flatnonzero(summary["n_rows"]).tolist()
                 lines = [line[:-1] + "".join("\t%r" % float(v) for v in level[i]) + "\n" for line, i in zip(lines, covered)]
+            if control is not None:
+                extra = control(lo, hi, summary)
+                lines = [line[:-1] + "\t" + extra[i] + "\n" for line, i in zip(lines, np.flatnonzero(summary["n_rows"]).tolist())]
             f.writelines(lines)
             written += len(lines)
     return written
@@ -391,3 +397,194 @@ def site_histogram_range(level_mean, level_stdv):
     deviations beyond the lowest and the highest k-mer level"""
     mean, sd = np.asarray(level_mean, dtype=np.float64), np.asarray(level_stdv, dtype=np.float64)
     return float(mean.min() - 4.0 * sd.max()), float(mean.max() + 4.0 * sd.max())
+
+
+# ---- two samples per site (Aligner.site_compare / site_summary_add, dynamont-resquiggle --site-table-out / --site-control) -----
+SITE_CONTROL_HEADER = "control_coverage\tks_d\tks_p\tks_level\tks_side\tdwell_ks_d\twelch_t\twelch_df"
+SITE_TABLE_VERSION = 1
+SITE_TABLE_LIMBS = ("n_rows", "n_samples", "dwell_sq", "m1_lo", "m1_hi", "m2_lo", "m2_hi")
+
+
+def site_welch(row_a, row_b):
+    """Welch's t and its degrees of freedom (Welch-Satterthwaite) between the event means of two sites, from two rows of table
+    integers ``(n_rows, M1, M2)`` (Python ints). Means and UNBIASED variances are formed exactly, as
+    fractions: mean = M1 / (n 2^40), var = (M2 / 2^40 - n mean^2) / (n - 1), negative variances taken as 0. t^2 and df are exact
+    fractions rounded to a double once; t is the square root of that double with the sign of mean_a - mean_b. (nan, nan) when
+    either side has fewer than 2 rows or the standard error is 0."""
+    from fractions import Fraction
+    import math
+    (na, m1a, m2a), (nb, m1b, m2b) = [(int(r[0]), int(r[1]), int(r[2])) for r in (row_a, row_b)]
+    if na < 2 or nb < 2:
+        return math.nan, math.nan
+    sides = []
+    for n, m1, m2 in ((na, m1a, m2a), (nb, m1b, m2b)):
+        mean = Fraction(m1, n << 40)
+        var = max(Fraction(0), (Fraction(m2, 1 << 40) - n * mean * mean) / (n - 1))
+        sides.append((mean, var / n, n))
+    (ma, sa, _), (mb, sb, _) = sides
+    se2 = sa + sb
+    if se2 == 0:
+        return math.nan, math.nan
+    diff = ma - mb
+    t = math.sqrt(float(diff * diff / se2))
+    df = float(se2 * se2 / (sa * sa / (na - 1) + sb * sb / (nb - 1)))
+    return (-t if diff < 0 else t), df
+
+
+def ks_two_sample_p(d: float, n_a: int, n_b: int) -> float:
+    """The asymptotic Kolmogorov tail of a two-sample statistic ``d``: ne = n_a n_b / (n_a + n_b),
+    lam = (sqrt(ne) + 0.12 + 0.11 / sqrt(ne)) * d, p = 2 sum_{j >= 1} (-1)^(j - 1) exp(-2 j^2 lam^2), summed until a term is below
+    1e-16 and clipped to [0, 1]. On BINNED data (``Aligner.site_compare``'s level_d, which never exceeds the distance over the raw
+    event means) it is conservative: the p it gives is never below the one the raw samples would give. NaN for a NaN ``d`` or an
+    empty side."""
+    import math
+    if not (n_a > 0 and n_b > 0) or d != d:
+        return math.nan
+    ne = float(n_a) * float(n_b) / (float(n_a) + float(n_b))
+    lam = (math.sqrt(ne) + 0.12 + 0.11 / math.sqrt(ne)) * float(d)
+    if lam <= 0.0:
+        return 1.0
+    if lam < 0.04:     # the series needs 1 / lam terms and its sum is 1 here to within exp(-pi^2 / (8 lam^2)) < 1e-300
+        return 1.0
+    total, j = 0.0, 1
+    while True:
+        term = math.exp(-2.0 * j * j * lam * lam)
+        total += term if j & 1 else -term
+        if term < 1e-16:
+            break
+        j += 1
+    return min(1.0, max(0.0, 2.0 * total))
+
+
+def save_site_table(path: str, aligner, ref_names, ref_lengths, lo: int = 0, hi=None, window: int = 1 << 20) -> int:
+    """The covered sites of the window [lo, hi) (default: one sample, the references' total length) of ``aligner``'s per-site table
+    as an .npz (numpy only): ``site`` uint64 (relative to ``lo``), the seven limb columns, ``level`` / ``dwell`` counters when the
+    handle has histograms, ``hist_spec`` = (bins, lo, hi) with the bounds as float64 BITS (uint64; bins 0 = no histograms),
+    ``ref_names``, ``ref_lengths``, ``totals`` and ``version``. Fetched window by window: nothing genome-sized is on the host at
+    once. Returns the sites saved."""
+    lengths = np.asarray(ref_lengths, dtype=np.uint64)
+    hi = int(lo) + int(lengths.sum()) if hi is None else int(hi)
+    spec = getattr(aligner, "_site_histogram", None)
+    sites, limbs, level, dwell = [], [[] for _ in SITE_TABLE_LIMBS], [], []
+    totals = None
+    for w0 in range(int(lo), hi, int(window)):
+        w1 = min(w0 + int(window), hi)
+        t = aligner.site_summary(w0, w1)
+        totals = t["totals"]
+        idx = np.flatnonzero(t["n_rows"])
+        sites.append((idx + (w0 - int(lo))).astype(np.uint64))
+        for f in range(7):
+            limbs[f].append(np.asarray(t["limbs"][f], dtype=np.uint64)[idx])
+        if spec:
+            h = aligner.site_histogram(w0, w1)
+            level.append(h["level"][idx])
+            dwell.append(h["dwell"][idx])
+    if totals is None:
+        totals = aligner.site_summary(int(lo), int(lo))["totals"]
+    from dynamont_amd._dynamont import SITE_SUMMARY_TOTALS
+    cat = lambda parts, dtype, shape: np.concatenate(parts) if parts else np.zeros(shape, dtype=dtype)  # noqa: E731
+    out = {"version": np.array([SITE_TABLE_VERSION], dtype=np.uint32), "num_sites": np.array([hi - int(lo)], dtype=np.uint64),
+           "site": cat(sites, np.uint64, 0), "ref_names": np.array([str(n) for n in ref_names], dtype=np.str_), "ref_lengths": lengths,
+           "totals": np.array([int(totals[k]) for k in SITE_SUMMARY_TOTALS], dtype=np.uint64)}
+    for name, parts in zip(SITE_TABLE_LIMBS, limbs):
+        out[name] = cat(parts, np.uint64, 0)
+    if spec:
+        bins = int(spec[0])
+        out["hist_spec"] = np.concatenate([np.array([bins], dtype=np.uint64), np.array(spec[1:], dtype=np.float64).view(np.uint64)])
+        out["level"] = cat(level, np.uint32, (0, bins + 2))
+        out["dwell"] = cat(dwell, np.uint32, (0, 16))
+    else:
+        out["hist_spec"] = np.zeros(3, dtype=np.uint64)
+    with open(path, "wb") as f:          # (a file object: np.savez appends no extension to the name the caller chose)
+        np.savez(f, **out)
+    return int(out["site"].size)
+
+
+def load_site_table(path: str) -> dict:
+    """What ``save_site_table`` wrote, as a dict: ``site`` uint64, ``limbs`` (the seven uint64 columns), ``M1`` / ``M2`` (object
+    arrays of Python ints), ``level`` / ``dwell`` (None without histograms), ``hist_spec`` = (bins, lo, hi) with float bounds or
+    None, ``hist_bits`` (the three uint64 as stored), ``ref_names`` (list of str), ``ref_lengths`` (uint64), ``num_sites``,
+    ``totals`` (dict) and ``version``. ValueError for another format version."""
+    from dynamont_amd._dynamont import SITE_SUMMARY_TOTALS, int128_of_limbs
+    with np.load(path, allow_pickle=False) as z:
+        version = int(z["version"][0])
+        if version != SITE_TABLE_VERSION:
+            raise ValueError(f"{path}: site table format version {version}, this build reads version {SITE_TABLE_VERSION}")
+        limbs = [np.ascontiguousarray(z[k], dtype=np.uint64) for k in SITE_TABLE_LIMBS]
+        bits = np.asarray(z["hist_spec"], dtype=np.uint64)
+        has = int(bits[0]) > 0
+        lo, hi = bits[1:].view(np.float64).tolist()
+        return {"version": version, "num_sites": int(z["num_sites"][0]), "site": np.asarray(z["site"], dtype=np.uint64), "limbs": limbs,
+                "n_rows": limbs[0], "n_samples": limbs[1], "dwell_sq": limbs[2], "M1": int128_of_limbs(limbs[3], limbs[4]),
+                "M2": int128_of_limbs(limbs[5], limbs[6]), "level": np.asarray(z["level"], dtype=np.uint32) if has else None,
+                "dwell": np.asarray(z["dwell"], dtype=np.uint32) if has else None, "hist_spec": (int(bits[0]), lo, hi) if has else None,
+                "hist_bits": bits.copy(), "ref_names": [str(n) for n in z["ref_names"].tolist()],
+                "ref_lengths": np.asarray(z["ref_lengths"], dtype=np.uint64),
+                "totals": dict(zip(SITE_SUMMARY_TOTALS, [int(v) for v in z["totals"].tolist()]))}
+
+
+def check_site_control(table: dict, path: str, ref_names, ref_lengths, hist_spec) -> None:
+    """--site-control: refuses, each with its own message, a saved table whose references differ from the BAM header's in name or
+    length, one without histograms, and one whose hist_spec is not bit-equal to the run's ``hist_spec`` = (bins, lo, hi); a bound
+    of None (the range left to the model table) is compared once the run knows it."""
+    names, lengths = [str(n) for n in ref_names], [int(v) for v in ref_lengths]
+    if table["ref_names"] != names:
+        raise ValueError(f"--site-control {path}: its reference names differ from the BAM header's")
+    if [int(v) for v in table["ref_lengths"].tolist()] != lengths:
+        raise ValueError(f"--site-control {path}: its reference lengths differ from the BAM header's")
+    if table["hist_spec"] is None:
+        raise ValueError(f"--site-control {path}: the file holds no histograms (it was saved by a run without --site-histogram)")
+    bins, lo, hi = hist_spec
+    mine = [int(bins)] + [None if v is None else int(np.array([v], dtype=np.float64).view(np.uint64)[0]) for v in (lo, hi)]
+    theirs = [int(v) for v in table["hist_bits"].tolist()]
+    if any(m is not None and m != t for m, t in zip(mine, theirs)):
+        raise ValueError(f"--site-control {path}: its histograms ({table['hist_spec'][0]} bins over [{table['hist_spec'][1]!r}, "
+                         f"{table['hist_spec'][2]!r})) are not the run's ({bins} bins over [{lo!r}, {hi!r})), bit for bit")
+
+
+def load_site_control(aligner, table: dict, offset: int, window: int = 1 << 20) -> int:
+    """adds a loaded table (``load_site_table``) into the sites [offset, offset + num_sites) of ``aligner``'s table and histograms
+    (``Aligner.site_summary_add``), a window of sites at a time; its totals are NOT added: the handle's totals stay the run's own.
+    Returns the covered sites added."""
+    site = table["site"].astype(np.int64)
+    bins = table["hist_spec"][0] if table["hist_spec"] else 0
+    spec = getattr(aligner, "_site_histogram", None)
+    edges = spec[1] + np.arange(spec[0] + 1, dtype=np.float64) * ((spec[2] - spec[1]) / spec[0]) if spec else None
+    for w0 in range(0, int(table["num_sites"]), int(window)):
+        w1 = min(w0 + int(window), int(table["num_sites"]))
+        a, b = np.searchsorted(site, [w0, w1])
+        if a == b:
+            continue
+        rel = site[a:b] - w0
+        cols = {}
+        for k in ("n_rows", "n_samples", "dwell_sq"):
+            cols[k] = np.zeros(w1 - w0, dtype=np.uint64)
+            cols[k][rel] = table[k][a:b]
+        for k in ("M1", "M2"):
+            cols[k] = np.zeros(w1 - w0, dtype=object)
+            cols[k][rel] = table[k][a:b]
+        hist = None
+        if bins:
+            hist = {"level": np.zeros((w1 - w0, bins + 2), dtype=np.uint32), "dwell": np.zeros((w1 - w0, 16), dtype=np.uint32), "edges": edges}
+            hist["level"][rel] = table["level"][a:b]
+            hist["dwell"][rel] = table["dwell"][a:b]
+        aligner.site_summary_add(int(offset) + w0, cols, hist)
+    return int(site.size)
+
+
+def site_control_columns(compare: dict, run: dict, control: dict) -> list:
+    """the eight columns of SITE_CONTROL_HEADER for every site of one window, as strings: ``compare`` = Aligner.site_compare(lo, hi,
+    N + lo) (A the run, B the control), ``run`` / ``control`` = Aligner.site_summary of [lo, hi) and [N + lo, N + hi). ks_d =
+    level_d, ks_p = ks_two_sample_p of it, ks_level = level_edge, ks_side = level_side, dwell_ks_d = dwell_d, welch_t / welch_df =
+    site_welch of the two rows (floats as ``repr``)."""
+    out = []
+    for i in range(len(compare["n_a"])):
+        n_a, n_b = int(compare["n_a"][i]), int(compare["n_b"][i])
+        if n_a == 0:
+            out.append("")      # not written: the run has no coverage here
+            continue
+        d = float(compare["level_d"][i])
+        t, df = site_welch((run["n_rows"][i], run["M1"][i], run["M2"][i]), (control["n_rows"][i], control["M1"][i], control["M2"][i]))
+        out.append("%d\t%r\t%r\t%r\t%d\t%r\t%r\t%r" % (n_b, d, ks_two_sample_p(d, n_a, n_b), float(compare["level_edge"][i]),
+                                                         int(compare["level_side"][i]), float(compare["dwell_d"][i]), t, df))
+    return out

@@ -650,6 +650,44 @@ int dyn_aligner_site_histogram_fetch(dyn_aligner* a, uint64_t site_lo, uint64_t 
  * lo + ((bin - 1) + (rank - below - 0.5) / in_bin) * (hi - lo) / bins. */
 int dyn_aligner_site_quantiles(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi, const double* probs, int n_probs, uint32_t* n,
                                uint32_t* rank, uint32_t* bin, uint32_t* below, uint32_t* in_bin);
+/* (added within ABI 10: a caller that must know looks the symbol up) TWO SAMPLES IN ONE TABLE. A
+ * second sample is mapped with ids alone: sample c's site s gets the id c * N + s in a table of 2 N sites; nothing else about the
+ * accumulation changes. The table and the counters are exact integers, so merging tables is addition:
+ * dyn_aligner_site_summary_add adds host columns -- a table saved by another run, for instance -- into the sites [lo, hi) of the
+ * device table: n_rows, n_samples and dwell_sq mod 2^64, M1 and M2 as 128-bit two's complement (the low limb's carry goes into
+ * the high limb, mod 2^128), and, when `level` [n][bins + 2] and `dwell` [n][16] are given (both or neither), every counter mod
+ * 2^32; `totals` (may be NULL: adds none) is added to the table's five totals. The adds are the filling kernels' own device-scope
+ * atomics: a job still in flight loses no update. The conditions and error texts of dyn_aligner_site_summary_fetch /
+ * dyn_aligner_site_histogram_fetch; counters given on a handle without histograms, or one given without the other:
+ * DYN_ERR_INVALID_ARGUMENT. An empty window is DYN_OK and touches nothing. */
+int dyn_aligner_site_summary_add(dyn_aligner* a, uint64_t lo, uint64_t hi,
+    const uint64_t* n_rows, const uint64_t* n_samples, const uint64_t* dwell_sq,
+    const uint64_t* m1_lo, const uint64_t* m1_hi, const uint64_t* m2_lo, const uint64_t* m2_hi,
+    const uint64_t totals[5],           /* may be NULL: adds none */
+    const uint32_t* level, const uint32_t* dwell);   /* both NULL: the table alone; else [n][bins+2] and [n][16] */
+/* Compares the sites [site_lo, site_hi) with the sites starting at other_lo, pair by pair, on the device: the histograms never
+ * cross to the host. Pair i: A = site_lo + i, B = other_lo + i; a[e], b[e] their Bc = bins + 2 level counters, PA[e], PB[e] the
+ * inclusive prefix sums (uint32: fewer than 2^32 rows per site is the defined domain), nA = PA[Bc - 1], nB = PB[Bc - 1]. Per counter
+ *   x[e] = (uint64)PA[e] * nB,  y[e] = (uint64)PB[e] * nA,  d[e] = x[e] > y[e] ? x[e] - y[e] : y[e] - x[e]
+ * (the product of two uint32 cannot overflow a uint64), and per pair
+ *   level_num    max_e d[e]
+ *   level_at     the SMALLEST e with d[e] == level_num
+ *   level_side   +1 if x[at] > y[at] (A's distribution function is ahead: A's levels are lower), -1 if x[at] < y[at], 0 when
+ *                level_num == 0
+ *   nA == 0 or nB == 0: level_num = 0, level_at = 0xFFFFFFFF, level_side = 0
+ * and the same three over the 16 dwell counters with the dwell counters' own totals: dwell_num, dwell_at, dwell_side.
+ * n_a = nA, n_b = nB. All arrays of site_hi - site_lo. The binned Kolmogorov-Smirnov statistic is D = level_num / (nA * nB); the
+ * host forms it as (double)level_num / ((double)nA * (double)nB): three roundings -- level_num to double (exact below 2^53), the
+ * product nA * nB (exact below 2^53), the quotient; NaN where either side is empty. D is the distance between the two
+ * distribution functions evaluated AT THE BIN EDGES ONLY: it never exceeds the distance over the raw event means, and falls
+ * short of it by at most max_e max(a[e] / nA, b[e] / nB) -- at a point inside bin e one distribution function has grown by at most
+ * its bin share since the edge. Choose the bins accordingly. Every output is an integer; integer adds, products and maxima do
+ * not depend on order, so the comparison is the same bits on every launch path. The two windows may lie anywhere in the table, in
+ * either order, and may overlap. The conditions and error texts of dyn_aligner_site_quantiles; other_lo + (site_hi - site_lo) >
+ * num_sites: DYN_ERR_INVALID_ARGUMENT with a text of its own. An empty window is DYN_OK and touches nothing. */
+int dyn_aligner_site_compare(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi, uint64_t other_lo,
+    uint32_t* n_a, uint32_t* n_b, uint64_t* level_num, uint32_t* level_at, int32_t* level_side,
+    uint64_t* dwell_num, uint32_t* dwell_at, int32_t* dwell_side);
 /* The rule of mode 1 for one read, given its k-mer codes (dyn_validate_batch) and signal length: 0 = no structural tie;
  * otherwise the number of forward rows that run in the strict arithmetic (UINT32_MAX: all of them). Host only. */
 uint32_t dyn_tie_rows(const dyn_aligner* a, const int32_t* kmers, uint64_t n_kmers, uint64_t signal_len);
