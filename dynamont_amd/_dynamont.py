@@ -1169,6 +1169,40 @@ class Aligner:
         return {"n_a": u32[0], "n_b": u32[1], "level_num": u64[0], "level_at": u32[2], "level_side": i32[0], "dwell_num": u64[1],
                 "dwell_at": u32[3], "dwell_side": i32[1], "level_d": level_d, "dwell_d": dwell_d, "level_edge": edge}
 
+    def site_mixture(self, lo: int = 0, hi: int | None = None, other_lo: int | None = None, max_iters: int = 128, tol: float = 1e-3,
+                     min_n: int = 8) -> dict:
+        """dyn_aligner_site_mixture: per site of [lo, hi) (default: all) a mixture of two Gaussians fitted by EM on the GPU to the
+        site's level counters -- pooled with those of the site ``other_lo + i`` when ``other_lo`` is given (a run in [0, N) and its
+        control in [N, 2 N): ``site_mixture(0, N, N)``) -- and each side's rows split between the two components; the histograms
+        stay on the device. Component 1 is the one with the higher level. From the device, float64:
+        ``pi1`` (its weight), ``mu0``, ``mu1``, ``var0``, ``var1``, ``r_a``, ``r_b`` (the expected number of A's / B's in-range rows
+        in component 1); uint32: ``n_a``, ``n_b`` (in-range rows), ``out_a``, ``out_b`` (under + over), ``iters``, ``status`` (0
+        converged, 1 no fit: fewer than ``min_n`` rows or no spread, the floats are NaN; 2 ``max_iters`` reached; 3 a component
+        collapsed). Formed on the host: ``sd0``, ``sd1``; ``share_a`` = r_a / n_a and ``share_b`` = r_b / n_b (NaN where the count
+        is 0): the modified share of either sample; ``separation`` = (mu1 - mu0) / sqrt(0.5 * (var0 + var1))."""
+        lo = int(lo)
+        hi = self._site_table if hi is None else int(hi)
+        n = max(0, hi - lo)
+        max_iters, min_n = int(max_iters), int(min_n)
+        if not (0 <= max_iters <= 0xFFFFFFFF and 0 <= min_n <= 0xFFFFFFFF):
+            raise ValueError("site_mixture: max_iters and min_n must be non-negative 32-bit integers")
+        if other_lo is not None and not 0 <= int(other_lo) < 0xFFFFFFFFFFFFFFFF:
+            raise ValueError("site_mixture: other_lo must be a site of the table or None")
+        f64 = [np.zeros(n, dtype=np.float64) for _ in range(7)]
+        u32 = [np.zeros(n, dtype=np.uint32) for _ in range(6)]
+        rc = self._L.dyn_aligner_site_mixture(self._h, lo, hi, 0xFFFFFFFFFFFFFFFF if other_lo is None else int(other_lo), max_iters,
+                                              float(tol), min_n, *[_ptr(c, N.c_double_p) for c in f64], *[_ptr(c, N.c_u32_p) for c in u32])
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        out = dict(zip(("pi1", "mu0", "mu1", "var0", "var1", "r_a", "r_b"), f64))
+        out.update(zip(("n_a", "n_b", "out_a", "out_b", "iters", "status"), u32))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["sd0"], out["sd1"] = np.sqrt(out["var0"]), np.sqrt(out["var1"])
+            out["share_a"] = np.where(out["n_a"] > 0, out["r_a"] / out["n_a"].astype(np.float64), np.nan)
+            out["share_b"] = np.where(out["n_b"] > 0, out["r_b"] / out["n_b"].astype(np.float64), np.nan)
+            out["separation"] = (out["mu1"] - out["mu0"]) / np.sqrt(0.5 * (out["var0"] + out["var1"]))
+        return out
+
     def set_band_margin(self, on: bool) -> None:
         """dyn_aligner_set_band_margin: align(calc_probabilities=True) jobs submitted while on also report, per read, how
         close the called path came to a real edge of its band: ``AlignBatchResult.band_margin_low``
@@ -1739,6 +1773,12 @@ class MultiAligner:
     def site_compare(self, lo: int = 0, hi: int | None = None, other_lo: int | None = None) -> dict:
         """Not supported, as ``set_site_histogram`` is not."""
         raise NotImplementedError("MultiAligner has no per-site histograms (Aligner.site_compare): use one Aligner per device "
+                                  "and add their tables")
+
+    def site_mixture(self, lo: int = 0, hi: int | None = None, other_lo: int | None = None, max_iters: int = 128, tol: float = 1e-3,
+                     min_n: int = 8) -> dict:
+        """Not supported, as ``set_site_histogram`` is not."""
+        raise NotImplementedError("MultiAligner has no per-site histograms (Aligner.site_mixture): use one Aligner per device "
                                   "and add their tables")
 
     def _cap(self, seq_off) -> int:

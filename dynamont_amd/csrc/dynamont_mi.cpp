@@ -452,6 +452,7 @@ void dyn_aligner_destroy(dyn_aligner* a) {
     a->d_shist.release();
     a->d_squant.release();
     a->d_scomp.release();
+    a->d_smix.release();
     a->d_sadd.release();
     park_pool_buffer(a->device, 0, a->ws);
     park_pool_buffer(a->device, 1, a->lpe);
@@ -1107,6 +1108,65 @@ int dyn_aligner_site_compare(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi,
     std::memcpy(dwell_at + o, w + 3 * cnt, cnt * sizeof(uint32_t));
     std::memcpy(level_side + o, w + 4 * cnt, cnt * sizeof(int32_t));
     std::memcpy(dwell_side + o, w + 5 * cnt, cnt * sizeof(int32_t));
+  }
+  return DYN_OK;
+}
+
+// ---- a two-component mixture per site pair, fitted on the device from the level counters (site_mixture_kernels.hpp) ----
+int dyn_aligner_site_mixture(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi, uint64_t other_lo, uint32_t max_iters, double tol,
+                             uint32_t min_n, double* pi1, double* mu0, double* mu1, double* var0, double* var1, double* r_a, double* r_b,
+                             uint32_t* n_a, uint32_t* n_b, uint32_t* out_a, uint32_t* out_b, uint32_t* iters, uint32_t* status) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  auto fail = [&](const std::string& msg) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = "dyn_aligner_site_mixture: " + msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  };
+  // refused before the device is looked at: the same text on a handle without one
+  if (max_iters < 1 || max_iters > dynk::SM_MAX_ITERS) return fail("max_iters " + std::to_string(max_iters) + " is not 1 .. 1024");
+  if (!std::isfinite(tol) || !(tol >= 0.0)) return fail("tol must be finite and >= 0");
+  if (min_n < 2) return fail("min_n " + std::to_string(min_n) + " is not >= 2");
+  double* dcols[7] = {pi1, mu0, mu1, var0, var1, r_a, r_b};
+  uint32_t* ucols[6] = {n_a, n_b, out_a, out_b, iters, status};
+  if (site_lo < site_hi) {
+    for (double* c : dcols)
+      if (!c) return DYN_ERR_INVALID_ARGUMENT;
+    for (uint32_t* c : ucols)
+      if (!c) return DYN_ERR_INVALID_ARGUMENT;
+  }
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = site_histogram_quiet(a, "dyn_aligner_site_mixture", site_lo, site_hi)) return rc;
+  const uint64_t n = site_hi - site_lo;
+  const bool one = other_lo == UINT64_MAX;
+  if (!one && (other_lo > a->num_sites || n > a->num_sites - other_lo))
+    return fail("the other window [" + std::to_string(other_lo) + ", " + std::to_string(other_lo) + " + " + std::to_string(n) +
+                ") does not end inside the table's " + std::to_string(a->num_sites) + " sites");
+  if (n == 0) return DYN_OK;
+  const uint64_t H = site_hist_width(a->sh_bins), step = 1ull << 20, most = std::min(step, n);
+  HIP_TRY(a, a->d_smix.ensure((uint64_t)dynk::SM_PAIR_BYTES * most));
+  std::vector<double> h((uint64_t)dynk::SM_PAIR_BYTES / 8 * most);
+  dynk::SiteMixture sm{};
+  sm.exp_tab = reinterpret_cast<const uint64_t*>(a->d_sptab.as<dynmath::SoftplusNode>() + dynmath::SP_NODES + dynmath::EXP128_NODES);
+  sm.bins = a->sh_bins;
+  sm.max_iters = max_iters;
+  sm.min_n = min_n;
+  sm.lo = a->sh_lo;
+  sm.w = (a->sh_hi - a->sh_lo) / (double)a->sh_bins;  // one IEEE subtraction, one IEEE division
+  sm.vfloor = (sm.w * sm.w) / 12.0;
+  sm.tol_mu = tol * sm.w;
+  sm.tol_pi = tol;
+  sm.out = a->d_smix.as<double>();
+  for (uint64_t o = 0; o < n; o += step) {
+    const uint64_t cnt = std::min(step, n - o);
+    sm.hist_a = a->d_shist.as<unsigned int>() + H * (site_lo + o);
+    sm.hist_b = one ? nullptr : a->d_shist.as<unsigned int>() + H * (other_lo + o);
+    sm.count = (uint32_t)cnt;
+    dynk::launch_site_mixture(sm, a->s_get);
+    HIP_TRY(a, hipGetLastError());
+    HIP_TRY(a, copy_out(a, h.data(), sm.out, (uint64_t)dynk::SM_PAIR_BYTES * cnt));  // (behind the kernel on the same stream)
+    for (int f = 0; f < 7; ++f) std::memcpy(dcols[f] + o, h.data() + (uint64_t)f * cnt, cnt * sizeof(double));
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(h.data() + 7 * cnt);
+    for (int f = 0; f < 6; ++f) std::memcpy(ucols[f] + o, w + (uint64_t)f * cnt, cnt * sizeof(uint32_t));
   }
   return DYN_OK;
 }

@@ -236,6 +236,7 @@ struct dyn_aligner {
   double sh_lo = 0.0, sh_hi = 0.0, sh_inv_w = 0.0;
   dyneng::DevBuf d_squant;    // staging of dyn_aligner_site_quantiles: one window's output
   dyneng::DevBuf d_scomp;     // staging of dyn_aligner_site_compare: one window's output
+  dyneng::DevBuf d_smix;      // staging of dyn_aligner_site_mixture: one window's output
   dyneng::DevBuf d_sadd;      // staging of dyn_aligner_site_summary_add: one window's columns and counters
   // dyn_aligner_stage_site_ids: the caller's ids for the NEXT batch-creating call on this handle (consumed by it, whatever its outcome)
   const uint32_t* staged_sites = nullptr;

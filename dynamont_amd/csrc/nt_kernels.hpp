@@ -345,6 +345,25 @@ struct SiteCompare {
   unsigned long long* out;
 };
 void launch_site_compare(const SiteCompare& sc, hipStream_t s);
+constexpr int SM_PAIR_BYTES = 7 * 8 + 6 * 4;
+constexpr uint32_t SM_MAX_ITERS = 1024;
+// a two-component mixture fitted to the level counters of every pair of two windows (k_site_mixture, site_mixture_kernels.hpp).
+// out, SM_PAIR_BYTES per pair: float64 [count] pi1, mu0, mu1, var0, var1, r_a, r_b, then uint32 [count] n_a, n_b, out_a, out_b,
+// iters, status
+struct SiteMixture {
+  const unsigned int* hist_a; // the first site's counters of either window; a site's bins + 2 + 16 counters are contiguous
+  const unsigned int* hist_b; // nullptr: the single-sample form
+  const uint64_t* exp_tab;    // dynmath::strict_exp_table on the device
+  uint32_t bins;
+  uint32_t count;             // pairs of the window
+  uint32_t max_iters;         // 1 .. SM_MAX_ITERS
+  uint32_t min_n;
+  double lo, w;               // the histograms' lower bound and bin width (hi - lo) / bins
+  double vfloor;              // (w * w) / 12
+  double tol_mu, tol_pi;      // tol * w, tol
+  double* out;
+};
+void launch_site_mixture(const SiteMixture& sm, hipStream_t s);
 // host columns added into a window of the table and, optionally, of the counters (k_site_add, site_compare_kernels.hpp)
 struct SiteAdd {
   unsigned long long* acc;          // the window's first cell of the table: [count][7]

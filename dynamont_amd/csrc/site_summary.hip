@@ -2,6 +2,7 @@
 // reads' event means per caller-supplied site id, accumulated on the handle as exact integers while the switch is on. The
 // kernels and the definition are in site_summary_kernels.hpp (shared with tests/device_math/site_summary.hip).
 #include "site_compare_kernels.hpp"
+#include "site_mixture_kernels.hpp"
 #include "site_quantile_kernels.hpp"
 #include "site_summary_kernels.hpp"
 
@@ -17,6 +18,9 @@ void launch_site_quantiles(const SiteQuantiles& sq, hipStream_t s) { launch_site
 
 // dyn_aligner_site_compare: one window of site pairs into its staging buffer
 void launch_site_compare(const SiteCompare& sc, hipStream_t s) { launch_site_compare_kernel(sc, s); }
+
+// dyn_aligner_site_mixture: one window of site pairs into its staging buffer
+void launch_site_mixture(const SiteMixture& sm, hipStream_t s) { launch_site_mixture_kernel(sm, s); }
 
 // dyn_aligner_site_summary_add: one staged window into the table and its counters
 void launch_site_add(const SiteAdd& sa, hipStream_t s) { launch_site_add_kernel(sa, s); }

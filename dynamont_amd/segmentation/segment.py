@@ -151,6 +151,12 @@ def parse(argv=None) -> Namespace:
                         "control run saved with --site-table-out (the same references, the same histogram bins and range, bit for "
                         "bit). FILE gains control_coverage, ks_d, ks_p, ks_level, ks_side, dwell_ks_d, welch_t and welch_df: a "
                         "binned Kolmogorov-Smirnov statistic found on the GPU from both histograms, and Welch's t from both tables")
+    p.add_argument("--site-mixture", type=int, nargs="?", const=128, default=0, metavar="MAX_ITERS",
+                   help="with --site-summary FILE and --site-histogram: fit, per reference position, a mixture of two Gaussians to "
+                        "the level histogram by EM on the GPU (at most MAX_ITERS rounds, 1 .. 1024, default 128). FILE gains mix_share "
+                        "(the share of the run's rows in the upper component), mix_mu0, mix_mu1, mix_sd0, mix_sd1, mix_iters and "
+                        "mix_status; with --site-control the run and the control are pooled for the fit and mix_control_share, "
+                        "mix_delta, mix_lor and mix_p compare their shares")
     p.add_argument("--kmer-summary", default="", metavar="PATH",
                    help="also write a per-k-mer summary of the run to PATH: a TSV in the model file's k-mer order with the "
                         "level (mean, stdev of the normalised signal) and dwell the run's segments showed per k-mer beside the "
@@ -961,7 +967,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             guide_auto: int = 0, guide_rounds: int = 8, guide_rescue: int = 0, guide_rescue_margin: int = 1,
             posterior_samples: int = 0, sample_seed: int = 0, border_interval: float = 0.0,
             soft_levels: bool = False, site_summary: str = "", site_histogram: str = "", site_table_out: str = "",
-            site_control: str = "") -> None:
+            site_control: str = "", site_mixture: int = 0) -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
@@ -990,6 +996,11 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
     if site_control and not (site_summary and site_hist):
         raise ValueError("--site-control compares the per-site histograms of the run and the control: it needs --site-summary FILE and "
                          "--site-histogram BINS[:LO:HI]")
+    if site_mixture and not (site_summary and site_hist):
+        raise ValueError("--site-mixture fits the per-site histograms of the run: it needs --site-summary FILE and "
+                         "--site-histogram BINS[:LO:HI]")
+    if site_mixture and not 1 <= site_mixture <= 1024:
+        raise ValueError(f"--site-mixture {site_mixture}: MAX_ITERS must be 1 .. 1024")
     site_refs = None
     control_table = None
     if site_summary:
@@ -1098,7 +1109,15 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             from dynamont_amd.segmentation.utils import site_control_columns
             control = lambda lo, hi, run: site_control_columns(aligner.site_compare(lo, hi, num_sites + lo), run,  # noqa: E731
                                                                aligner.site_summary(num_sites + lo, num_sites + hi))
-        written = write_site_summary(site_summary, aligner.site_summary, num_sites, *site_refs, quantiles=quantiles, control=control)
+        mixture = None
+        if site_mixture:
+            # --site-mixture: fitted on the GPU window by window beside the table's window; with a control, pooled with [N, 2N)
+            from dynamont_amd.segmentation.utils import site_mixture_columns
+            pooled = control_table is not None
+            mixture = lambda lo, hi: site_mixture_columns(aligner.site_mixture(lo, hi, num_sites + lo if pooled else None,  # noqa: E731
+                                                                               max_iters=site_mixture), pooled)
+        written = write_site_summary(site_summary, aligner.site_summary, num_sites, *site_refs, quantiles=quantiles, control=control,
+                                     mixture=mixture)
         if site_table_out:
             from dynamont_amd.bam_io import bam_references
             from dynamont_amd.segmentation.utils import save_site_table
@@ -1346,7 +1365,7 @@ def main(argv=None) -> None:
             guide_auto=args.guide_auto, guide_rounds=args.guide_rounds, guide_rescue=args.guide_rescue,
             guide_rescue_margin=args.guide_rescue_margin, posterior_samples=args.posterior_samples, sample_seed=args.sample_seed,
             border_interval=args.border_interval, soft_levels=args.soft_levels, site_summary=args.site_summary, site_table_out=args.site_table_out,
-            site_control=args.site_control,
+            site_control=args.site_control, site_mixture=args.site_mixture,
             site_histogram=args.site_histogram)
     _stamp("segment() returned (aligner closed)")
     if argv is None and not int(__import__("os").environ.get("WORLD_SIZE", "1") or 1) > 1:

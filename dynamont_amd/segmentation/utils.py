@@ -325,17 +325,23 @@ def site_summary_lines(summary: dict, lo: int, ref_names, offsets) -> list:
     return out
 
 
-def write_site_summary(path: str, fetch, num_sites: int, ref_names, offsets, window: int = 1 << 20, quantiles=None, control=None) -> int:
+def write_site_summary(path: str, fetch, num_sites: int, ref_names, offsets, window: int = 1 << 20, quantiles=None, control=None,
+                       mixture=None) -> int:
     """--site-summary FILE: the header and one line per site with coverage > 0, in reference order. ``fetch(lo, hi)`` returns a
     window of the table (Aligner.site_summary): a genome-sized table is never on the host at once. ``quantiles(lo, hi)``
     (--site-histogram: Aligner.site_quantiles of SITE_QUANTILE_PROBS over the same window) adds the three columns of
     SITE_QUANTILE_HEADER to every line. ``control(lo, hi)`` (--site-control: ``site_control_columns`` over the same window) returns
-    one string per site of the window, the eight columns of SITE_CONTROL_HEADER, added to every line behind the others. Sites are
-    written when the RUN has coverage. Returns the sites written."""
+    one string per site of the window, the eight columns of SITE_CONTROL_HEADER, added to every line behind the others.
+    ``mixture(lo, hi)`` (--site-mixture: ``site_mixture_columns`` over the same window) returns one string per site of the window,
+    the columns of SITE_MIXTURE_HEADER -- with a control, of SITE_MIXTURE_CONTROL_HEADER too -- added last. Sites are written when
+    the RUN has coverage. Returns the sites written."""
     written = 0
     with open(path, "w") as f:
         header = SITE_SUMMARY_HEADER if quantiles is None else SITE_SUMMARY_HEADER[:-1] + "\t" + SITE_QUANTILE_HEADER + "\n"
-        f.write(header if control is None else header[:-1] + "\t" + SITE_CONTROL_HEADER + "\n")
+        header = header if control is None else header[:-1] + "\t" + SITE_CONTROL_HEADER + "\n"
+        if mixture is not None:
+            header = header[:-1] + "\t" + SITE_MIXTURE_HEADER + ("" if control is None else "\t" + SITE_MIXTURE_CONTROL_HEADER) + "\n"
+        f.write(header)
         for lo in range(0, int(num_sites), window):
             hi = min(lo + window, int(num_sites))
             summary = fetch(lo, hi)
@@ -346,6 +352,9 @@ def write_site_summary(path: str, fetch, num_sites: int, ref_names, offsets, win
                 lines = [line[:-1] + "".join("\t%r" % float(v) for v in level[i]) + "\n" for line, i in zip(lines, covered)]
             if control is not None:
                 extra = control(lo, hi, summary)
+                lines = [line[:-1] + "\t" + extra[i] + "\n" for line, i in zip(lines, np.flatnonzero(summary["n_rows"]).tolist())]
+            if mixture is not None:
+                extra = mixture(lo, hi)
                 lines = [line[:-1] + "\t" + extra[i] + "\n" for line, i in zip(lines, np.flatnonzero(summary["n_rows"]).tolist())]
             f.writelines(lines)
             written += len(lines)
@@ -587,4 +596,47 @@ def site_control_columns(compare: dict, run: dict, control: dict) -> list:
         t, df = site_welch((run["n_rows"][i], run["M1"][i], run["M2"][i]), (control["n_rows"][i], control["M1"][i], control["M2"][i]))
         out.append("%d\t%r\t%r\t%r\t%d\t%r\t%r\t%r" % (n_b, d, ks_two_sample_p(d, n_a, n_b), float(compare["level_edge"][i]),
                                                          int(compare["level_side"][i]), float(compare["dwell_d"][i]), t, df))
+    return out
+
+
+# ---- a two-component mixture per site (Aligner.site_mixture, dynamont-resquiggle --site-mixture) ---------------------------------
+SITE_MIXTURE_HEADER = "mix_share\tmix_mu0\tmix_mu1\tmix_sd0\tmix_sd1\tmix_iters\tmix_status"
+SITE_MIXTURE_CONTROL_HEADER = "mix_control_share\tmix_delta\tmix_lor\tmix_p"
+
+
+def site_mixture_test(r_a: float, n_a: int, r_b: float, n_b: int):
+    """(log odds ratio, p) of the soft 2 x 2 table [[r_a, n_a - r_a], [r_b, n_b - r_b]] -- the expected rows of either sample in the
+    upper and in the lower component. The log odds ratio adds 0.5 to each cell (Haldane-Anscombe). p is the upper tail of
+    Pearson's chi-square of the table as it stands, chi2 = n (r_a (n_b - r_b) - r_b (n_a - r_a))^2 / (n_a n_b k1 k0) with k1 = r_a +
+    r_b, k0 = n - k1, one degree of freedom: erfc(sqrt(chi2 / 2)); 1.0 where a margin is 0. The cells are expectations, not counts:
+    p is a screening figure. (nan, nan) for a NaN cell."""
+    import math
+    r_a, r_b, n_a, n_b = float(r_a), float(r_b), float(n_a), float(n_b)
+    if r_a != r_a or r_b != r_b:
+        return math.nan, math.nan
+    c_a, c_b = max(n_a - r_a, 0.0), max(n_b - r_b, 0.0)
+    lor = math.log(((r_a + 0.5) * (c_b + 0.5)) / ((c_a + 0.5) * (r_b + 0.5)))
+    k1, k0 = r_a + r_b, c_a + c_b
+    margins = n_a * n_b * k1 * k0
+    if not margins > 0.0:
+        return lor, 1.0
+    det = r_a * c_b - r_b * c_a
+    chi2 = (n_a + n_b) * det * det / margins
+    return lor, math.erfc(math.sqrt(chi2 / 2.0))
+
+
+def site_mixture_columns(mix: dict, control: bool = False) -> list:
+    """the columns of SITE_MIXTURE_HEADER for every site of one window, as strings (floats as ``repr``): ``mix`` =
+    Aligner.site_mixture(lo, hi) of the run alone, or, with ``control``, Aligner.site_mixture(lo, hi, N + lo) (A the run, B the
+    control, pooled), which adds the columns of SITE_MIXTURE_CONTROL_HEADER: mix_share = share_a, mix_control_share = share_b,
+    mix_delta their difference, mix_lor / mix_p = site_mixture_test of the soft table. A site without a fit (status 1) prints nan."""
+    out = []
+    for i in range(len(mix["status"])):
+        line = "%r\t%r\t%r\t%r\t%r\t%d\t%d" % (float(mix["share_a"][i]), float(mix["mu0"][i]), float(mix["mu1"][i]), float(mix["sd0"][i]),
+                                                float(mix["sd1"][i]), int(mix["iters"][i]), int(mix["status"][i]))
+        if control:
+            sa, sb = float(mix["share_a"][i]), float(mix["share_b"][i])
+            lor, p = site_mixture_test(mix["r_a"][i], mix["n_a"][i], mix["r_b"][i], mix["n_b"][i])
+            line += "\t%r\t%r\t%r\t%r" % (sb, sa - sb, lor, p)
+        out.append(line)
     return out

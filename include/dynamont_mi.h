@@ -688,6 +688,40 @@ int dyn_aligner_site_summary_add(dyn_aligner* a, uint64_t lo, uint64_t hi,
 int dyn_aligner_site_compare(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi, uint64_t other_lo,
     uint32_t* n_a, uint32_t* n_b, uint64_t* level_num, uint32_t* level_at, int32_t* level_side,
     uint64_t* dwell_num, uint32_t* dwell_at, int32_t* dwell_side);
+/* Fits, per pair of the sites [site_lo, site_hi) and the sites starting at other_lo (UINT64_MAX: no second sample, all of B's
+ * counters count as 0), a mixture of two Gaussians to the POOLED level counters by EM on the device, and splits each side's rows
+ * between the two components: the histograms never cross to the host. Pair i: A = site_lo + i, B = other_lo + i; a[e], b[e] their
+ * Bc = bins + 2 level counters (e = 0 under, e = Bc - 1 over; the dwell counters are not used). Every floating-point operation is
+ * one IEEE fp64 operation in the order written; exp is the library's strict exp (every argument is <= 0).
+ *   w = (hi - lo) / bins, vfloor = (w * w) / 12, tol_mu = tol * w, tol_pi = tol       (formed on the host)
+ *   x[e] = lo + ((double)e - 0.5) * w                                                 (the bin centres)
+ *   c[e] = (double)a[e] + (double)b[e] for 1 <= e <= bins, c[0] = c[Bc - 1] = 0       (exact; under and over take no part)
+ *   n_a, n_b: the sums of the in-range counters of each side; out_a, out_b: under + over (uint32, mod 2^32)
+ *   gsum(t): G = min(64, the power of two >= Bc, at least 4). Partial l = 0 .. G - 1 starts at +0.0 and adds t[r * G + l] in rising
+ *            r (an index >= Bc adds 0.0); then for m = 1, 2, 4, .. < G every partial l adds partial l ^ m (all at once). The one
+ *            summation order of the whole fit.
+ *   start:   n = gsum(c); status 1 (no fit) if n < min_n. m = gsum(c * x) / n, v = gsum(c * ((x - m) * (x - m))) / n; status 1 if
+ *            not v > vfloor. sd = sqrt(v), mu = (m - sd, m + sd), var = (v, v), pi = (0.5, 0.5).
+ *   E-step:  A_k = pi_k / sqrt(var_k); per counter d_k = x - mu_k, q_k = -0.5 * ((d_k * d_k) / var_k), qm = q_1 > q_0 ? q_1 : q_0,
+ *            p_k = A_k * exp(q_k - qm), s = p_0 + p_1, g_k = p_k / s. (One exponential is exactly 1: s > 0, no logarithm anywhere.)
+ *   M-step, round it = 1 .. max_iters: t_k = c * g_k, N_k = gsum(t_k). N_0 < 1 or N_1 < 1: a component has collapsed, status 3, the
+ *            parameters stay those before this round, iters = it - 1. Otherwise mu'_k = gsum(t_k * x) / N_k,
+ *            var'_k = max(gsum(t_k * ((x - mu'_k) * (x - mu'_k))) / N_k, vfloor), pi'_k = N_k / (N_0 + N_1); they are adopted,
+ *            iters = it, and the fit stops with status 0 when max_k |mu'_k - mu_k| <= tol_mu and |pi'_1 - pi_1| <= tol_pi.
+ *            max_iters rounds without that: status 2.
+ *   shares:  one more E-step with the FINAL parameters; r_a = gsum((double)a * g_1), r_b = gsum((double)b * g_1), under and over
+ *            excluded: the expected number of each side's rows in component 1.
+ *   labels:  component 1 is the one with the larger final mean: if mu_0 > mu_1 the two are exchanged in every output, the g of
+ *            the shares included (equal means: nothing is exchanged).
+ * Outputs, arrays of site_hi - site_lo: pi1, mu0, mu1, var0, var1, r_a, r_b; n_a, n_b, out_a, out_b, iters, status. Status 1: the
+ * seven doubles are NaN and iters = 0. Defined domain: counters whose pooled in-range sum is below 2^53. 1 <= max_iters <= 1024,
+ * tol finite and >= 0, min_n >= 2, else DYN_ERR_INVALID_ARGUMENT with a text of their own (suggested: 128, 1e-3, 8). The two
+ * windows may lie anywhere in the table, in either order, and may overlap. The conditions and error texts of
+ * dyn_aligner_site_compare. An empty window is DYN_OK and touches nothing. */
+int dyn_aligner_site_mixture(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi, uint64_t other_lo /* UINT64_MAX: one sample */,
+    uint32_t max_iters, double tol, uint32_t min_n,
+    double* pi1, double* mu0, double* mu1, double* var0, double* var1, double* r_a, double* r_b,
+    uint32_t* n_a, uint32_t* n_b, uint32_t* out_a, uint32_t* out_b, uint32_t* iters, uint32_t* status);
 /* The rule of mode 1 for one read, given its k-mer codes (dyn_validate_batch) and signal length: 0 = no structural tie;
  * otherwise the number of forward rows that run in the strict arithmetic (UINT32_MAX: all of them). Host only. */
 uint32_t dyn_tie_rows(const dyn_aligner* a, const int32_t* kmers, uint64_t n_kmers, uint64_t signal_len);
