@@ -746,6 +746,7 @@ class Aligner:
     _guide_rescue = (0, 0, 8)  # set_guide_rescue: (min_margin, half_width, refine)
     _kmer_summary = False  # set_kmer_summary
     _site_summary = 0  # set_site_summary: num_sites while on
+    _site_capacity = 0  # set_site_summary(capacity=): rows of the sparse table, 0 while the table is dense
     _site_table = 0  # ... and the size of the handle's table (it outlives the switch)
     _site_histogram = None  # set_site_histogram: (bins, lo, hi) of the handle's counters (they outlive the switch too)
     _strict = 1  # set_strict
@@ -988,7 +989,7 @@ class Aligner:
             _raise(rc, self.last_error())
         self._kmer_summary = bool(on)
 
-    def set_site_summary(self, num_sites: int) -> None:
+    def set_site_summary(self, num_sites: int, capacity: int | None = None) -> None:
         """dyn_aligner_set_site_summary: while ``num_sites`` > 0, every output row of every ok read of the
         align(calc_probabilities=True) jobs submitted on this aligner WITH ``site_ids=`` is added to its site's entry of a
         per-site table kept on the GPU as exact integers, 56 bytes per site: coverage, dwell and the
@@ -996,20 +997,65 @@ class Aligner:
         orientation, packed like the sequences (``dynamont_amd.sites`` builds them from a mapping); ``DYN_SITE_NONE`` = no site.
         ``site_summary()`` fetches the table, ``reset_site_summary()`` zeroes it; 0 turns the switch off and keeps the table;
         another size waits for the tickets in flight and starts a new table. Like ``set_kmer_summary`` it is not combined
-        with ``set_band_retry``: the retried reads would be summed twice (ValueError)."""
+        with ``set_band_retry``: the retried reads would be summed twice (ValueError).
+
+        ``capacity`` (dyn_aligner_set_site_summary_sparse): a SPARSE table of ``capacity`` rows behind a hash map on the GPU from
+        site id to row, 60 bytes per row; ``num_sites`` then only bounds the ids (anything below 4 294 967 295). Every call
+        keeps its meaning in id space and, while ``site_map()["rows_dropped"]`` is 0, returns what a dense table returns. A
+        row whose id finds no bucket in a full map is dropped as a whole site; choose ``capacity`` well above the sites a run
+        touches. Another capacity, or the other mode, is another size."""
         num_sites = int(num_sites)
         if num_sites < 0:
             raise ValueError("set_site_summary: num_sites must be >= 0")
+        if capacity is not None and int(capacity) < 1:
+            raise ValueError("set_site_summary: capacity must be None (a dense table) or >= 1")
+        capacity = 0 if capacity is None else int(capacity)
         if num_sites and self._band_retry:
             raise ValueError("set_site_summary with set_band_retry: the retried reads would be summed twice")
-        rc = self._L.dyn_aligner_set_site_summary(self._h, num_sites)
+        if capacity:
+            rc = self._L.dyn_aligner_set_site_summary_sparse(self._h, num_sites, capacity)
+        else:
+            rc = self._L.dyn_aligner_set_site_summary(self._h, num_sites)
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
         self._site_summary = num_sites
         if num_sites:
-            if num_sites != self._site_table:
+            if (num_sites, capacity) != (self._site_table, self._site_capacity):
                 self._site_histogram = None  # another size releases the histograms: set_site_histogram again
             self._site_table = num_sites
+            self._site_capacity = capacity
+
+    def site_map(self) -> dict:
+        """dyn_aligner_site_map_stats: ``capacity``, ``n_keys``, ``rows_dropped`` (job rows whose id found no bucket; they also
+        count in the totals' rows_skipped) and ``sites_dropped`` (the same for ``site_summary_add``) of a sparse table."""
+        out = np.zeros(4, dtype=np.uint64)
+        rc = self._L.dyn_aligner_site_map_stats(self._h, _ptr(out, N.c_u64_p))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        return {"capacity": int(out[0]), "n_keys": int(out[1]), "rows_dropped": int(out[2]), "sites_dropped": int(out[3])}
+
+    def site_map_keys(self, lo: int = 0, hi: int | None = None) -> np.ndarray:
+        """dyn_aligner_site_map_keys: the uint32 keys of the buckets [lo, hi) (default: all) of a sparse table's map;
+        0xFFFFFFFF is an empty bucket. For diagnostics."""
+        lo = int(lo)
+        hi = self._site_capacity if hi is None else int(hi)
+        keys = np.zeros(max(0, hi - lo), dtype=np.uint32)
+        rc = self._L.dyn_aligner_site_map_keys(self._h, lo, hi, _ptr(keys, N.c_u32_p))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        return keys
+
+    def site_map_windows(self, shift: int = 20) -> np.ndarray:
+        """dyn_aligner_site_map_windows: the ascending uint64 indices w of the id windows [w << shift, (w + 1) << shift) that hold
+        a key of a sparse table, found on the GPU."""
+        shift = int(shift)
+        count = np.zeros(1, dtype=np.uint64)
+        cap = max(1, ((max(self._site_table, 1) - 1) >> shift) + 1) if 0 <= shift <= 31 else 1
+        wins = np.zeros(min(cap, 1 << 22), dtype=np.uint64)
+        rc = self._L.dyn_aligner_site_map_windows(self._h, shift, _ptr(wins, N.c_u64_p), wins.size, _ptr(count, N.c_u64_p))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        return wins[: int(count[0])].copy()
 
     def _stage_site_ids(self, site_ids):
         """dyn_aligner_stage_site_ids for the batch-creating call that follows at once; returns the array to keep alive"""
@@ -1753,9 +1799,9 @@ class MultiAligner:
     def last_error(self) -> str:
         return (self._L.dyn_multi_last_error(self._h) or b"").decode(errors="replace")
 
-    def set_site_summary(self, num_sites: int) -> None:
-        """Not supported: the per-site table lives on ONE device's handle and the reads of a batch are cut over the devices.
-        Use one ``Aligner`` per device and add the tables (they are integers)."""
+    def set_site_summary(self, num_sites: int, capacity: int | None = None) -> None:
+        """Not supported, dense or sparse (``capacity=``): the per-site table lives on ONE device's handle and the reads of a
+        batch are cut over the devices. Use one ``Aligner`` per device and add the tables (they are integers)."""
         raise NotImplementedError("MultiAligner has no per-site summary (Aligner.set_site_summary): use one Aligner per device "
                                   "and add their tables")
 

@@ -240,6 +240,7 @@ std::shared_ptr<BatchGroup> Pipeline::merge(const std::vector<dyn_batch*>& ticke
       if (!g->ss_table) {  // (the setter waits for the jobs in flight before it replaces the table: the members saw one table)
         g->ss_table = t->ss_table;
         g->ss_num_sites = t->ss_num_sites;
+        g->ss_map = t->ss_map;
       }
       // (likewise one set of histograms: the setter drains before it changes their parameters)
       if (t->want.site_histogram && t->ss_hist.p) {
@@ -782,6 +783,7 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
   unsigned long long* ss_table = nullptr;
   uint64_t ss_num_sites = 0;
   SiteHist ss_hist;
+  SiteMap ss_map;
   int staged_rc = DYN_OK;
   {
     std::lock_guard<std::mutex> lk(a->mu);
@@ -789,6 +791,7 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
     ss_table = a->d_site.as<unsigned long long>();  // the table as it stands at this submission
     ss_num_sites = a->num_sites;
     ss_hist = site_hist_now(a);
+    ss_map = site_map_now(a);
   }
   if (!ticket || !sig_offsets || !seq_offsets || (n_reads && ((!signals && !rs) || !seqs))) return DYN_ERR_INVALID_ARGUMENT;
   if (staged_rc != DYN_OK) return staged_rc;
@@ -841,6 +844,7 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
   b->ss_table = ss_table;
   b->ss_num_sites = ss_num_sites;
   b->ss_hist = ss_hist;
+  b->ss_map = ss_map;
   b->in_signals = signals;
   if (rs) {
     b->has_raw = true;

@@ -454,6 +454,8 @@ void dyn_aligner_destroy(dyn_aligner* a) {
     a->d_scomp.release();
     a->d_smix.release();
     a->d_sadd.release();
+    a->d_smap.release();
+    a->d_sgath.release();
     park_pool_buffer(a->device, 0, a->ws);
     park_pool_buffer(a->device, 1, a->lpe);
     park_pool_buffer(a->device, 2, a->bits);
@@ -743,15 +745,20 @@ int dyn_aligner_kmer_summary_reset(dyn_aligner* a) {
 }
 
 // ---- the per-site level summary (site_summary_kernels.hpp) -------------------------------------------------------------------
-int dyn_aligner_set_site_summary(dyn_aligner* a, uint64_t num_sites) {
+namespace {
+// both setters of the table: capacity == 0 is the dense table of num_sites rows, capacity > 0 the sparse one of capacity rows
+// behind a map (site_map.hpp) whose ids stay below num_sites
+int set_site_table(dyn_aligner* a, uint64_t num_sites, uint64_t capacity, const char* who) {
   if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  const bool sparse = capacity > 0;
   auto fail = [&](const std::string& msg) {
     std::lock_guard<std::mutex> lk(a->err_mu);
-    a->last_error = "dyn_aligner_set_site_summary: " + msg;
+    a->last_error = std::string(who) + ": " + msg;
     return DYN_ERR_INVALID_ARGUMENT;
   };
   if (a->ntk) return fail("modes ntk / resquiggle have no align(calc_probabilities = 1) job to summarise");
   if (num_sites >= (uint64_t)DYN_SITE_NONE) return fail("num_sites " + std::to_string(num_sites) + " is not below DYN_SITE_NONE (4294967295)");
+  if (capacity >= (uint64_t)DYN_SITE_NONE) return fail("capacity " + std::to_string(capacity) + " is not below 4294967295");
   Pipeline* pipe = nullptr;
   {
     std::lock_guard<std::mutex> lk(a->mu);
@@ -760,7 +767,7 @@ int dyn_aligner_set_site_summary(dyn_aligner* a, uint64_t num_sites) {
       a->opt.site_summary = false;
       return DYN_OK;
     }
-    if (num_sites == a->num_sites && a->d_site.p) {
+    if (num_sites == a->num_sites && capacity == a->site_capacity && a->d_site.p) {
       a->opt.site_summary = true;
       return DYN_OK;
     }
@@ -769,7 +776,7 @@ int dyn_aligner_set_site_summary(dyn_aligner* a, uint64_t num_sites) {
     a->opt.site_summary = false;
     pipe = a->pipe.get();
   }
-  // another size: the jobs in flight hold the old table's address (snapshot at their submission) -- they finish first
+  // another size or mode: the jobs in flight hold the old table's address (snapshot at their submission) -- they finish first
   if (pipe) pipe->drain();
   std::lock_guard<std::mutex> lk(a->mu);
   if (int rc = session_quiesce(a)) return rc;  // (hipFree waits for the whole device: no resident wave may be waiting for tickets)
@@ -777,31 +784,55 @@ int dyn_aligner_set_site_summary(dyn_aligner* a, uint64_t num_sites) {
   HIP_TRY(a, hipStreamSynchronize(a->s_out));
   a->opt.site_summary = false;
   a->d_site.release();
+  a->d_smap.release();
+  a->d_sgath.release();
   a->num_sites = 0;
+  a->site_capacity = 0;
   // the histograms were the old table's: released and off, the caller sets them again (dyn_aligner_set_site_histogram)
   a->opt.site_histogram = false;
   a->d_shist.release();
   a->sh_bins = 0;
-  const uint64_t bytes = ((uint64_t)dynk::SS_FIELDS * num_sites + (uint64_t)dynk::SS_TOTALS) * sizeof(uint64_t);
+  const uint64_t rows = sparse ? capacity : num_sites;
+  const uint64_t key_bytes = sparse ? capacity * sizeof(uint32_t) : 0;
+  const uint64_t table_bytes = ((uint64_t)dynk::SS_FIELDS * rows + (uint64_t)dynk::SS_TOTALS + (sparse ? (uint64_t)dynk::SM_STATS : 0)) * sizeof(uint64_t);
+  const uint64_t bytes = table_bytes + key_bytes;
+  const std::string what = sparse ? "the sparse table of " + std::to_string(capacity) + " rows (" + std::to_string(bytes) + " bytes)"
+                                  : "the table of " + std::to_string(num_sites) + " sites (" + std::to_string(bytes) + " bytes)";
   if (a->mem_budget && bytes > a->mem_budget) {
     std::lock_guard<std::mutex> elk(a->err_mu);
-    a->last_error = "dyn_aligner_set_site_summary: the table of " + std::to_string(num_sites) + " sites (" + std::to_string(bytes) +
-                    " bytes) does not fit dyn_aligner_set_mem_budget's " + std::to_string(a->mem_budget) + " bytes";
+    a->last_error = std::string(who) + ": " + what + " does not fit dyn_aligner_set_mem_budget's " + std::to_string(a->mem_budget) + " bytes";
     return DYN_ERR_OUT_OF_MEMORY;
   }
-  const hipError_t e = a->d_site.ensure(bytes);
+  hipError_t e = a->d_site.ensure(table_bytes);
+  if (e == hipSuccess && sparse) e = a->d_smap.ensure(key_bytes);
   if (e != hipSuccess) {
     (void)hipGetLastError();
+    a->d_site.release();
+    a->d_smap.release();
     std::lock_guard<std::mutex> elk(a->err_mu);
-    a->last_error = "dyn_aligner_set_site_summary: no device memory for the table of " + std::to_string(num_sites) + " sites (" +
-                    std::to_string(bytes) + " bytes): " + hipGetErrorString(e);
+    a->last_error = std::string(who) + ": no device memory for " + what + ": " + hipGetErrorString(e);
     return e == hipErrorOutOfMemory ? DYN_ERR_OUT_OF_MEMORY : DYN_ERR_DEVICE;
   }
-  HIP_TRY(a, hipMemsetAsync(a->d_site.p, 0, bytes, a->s_get));
+  HIP_TRY(a, hipMemsetAsync(a->d_site.p, 0, table_bytes, a->s_get));
+  if (sparse) HIP_TRY(a, hipMemsetAsync(a->d_smap.p, 0xFF, key_bytes, a->s_get));
   HIP_TRY(a, hipStreamSynchronize(a->s_get));
   a->num_sites = num_sites;
+  a->site_capacity = capacity;
   a->opt.site_summary = true;
   return DYN_OK;
+}
+}  // namespace
+
+int dyn_aligner_set_site_summary(dyn_aligner* a, uint64_t num_sites) { return set_site_table(a, num_sites, 0, "dyn_aligner_set_site_summary"); }
+
+int dyn_aligner_set_site_summary_sparse(dyn_aligner* a, uint64_t num_sites, uint64_t capacity) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  if (num_sites && !capacity) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = "dyn_aligner_set_site_summary_sparse: capacity 0 is no table (dyn_aligner_set_site_summary sets a dense one)";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  return set_site_table(a, num_sites, num_sites ? capacity : 0, "dyn_aligner_set_site_summary_sparse");
 }
 
 int dyn_aligner_stage_site_ids(dyn_aligner* a, const uint32_t* site_ids, uint64_t count) {
@@ -827,7 +858,115 @@ int site_summary_quiet(dyn_aligner* a, const char* who) {
   HIP_TRY(a, hipStreamSynchronize(a->s_out));
   return DYN_OK;
 }
+
+// the table's words: the cells, the totals and, behind a sparse table, the map's statistics
+uint64_t site_table_words(const dyn_aligner* a) {
+  return (uint64_t)dynk::SS_FIELDS * site_rows(a) + (uint64_t)dynk::SS_TOTALS + (a->site_capacity ? (uint64_t)dynk::SM_STATS : 0);
+}
+
+// A window of a sparse table as the dense calls see one. The ids [lo, lo + cnt) are gathered on s_get into slot `slot` of the
+// `slots` (1, or 2 where a call reads two windows at once) of the scratch d_sgath, each sized for `most` sites of what the call
+// asks for -- every gather of one call asks for the same: *table points at [cnt][7] u64, *hist at [cnt][bins + 2 + 16] uint32.
+// The scratch grows on first use and counts against the memory budget (mem_budget_left). The window kernels and copies behind
+// the gather on s_get read the scratch.
+int site_gather_window(dyn_aligner* a, uint64_t lo, uint64_t cnt, uint64_t most, int slot, int slots, const uint64_t** table,
+                       const unsigned int** hist) {
+  const uint64_t F = (uint64_t)dynk::SS_FIELDS, H = (hist && a->d_shist.p && a->sh_bins) ? site_hist_width(a->sh_bins) : 0;
+  const uint64_t table_bytes = table ? most * F * sizeof(uint64_t) : 0;
+  const uint64_t slot_bytes = (table_bytes + most * H * sizeof(uint32_t) + 7) / 8 * 8;  // (rounded up: every slot starts 8-byte aligned)
+  HIP_TRY(a, a->d_sgath.ensure((uint64_t)slots * slot_bytes));
+  char* base = a->d_sgath.as<char>() + (uint64_t)slot * slot_bytes;
+  dynk::SiteGather sg{};
+  sg.keys = a->d_smap.as<uint32_t>();
+  sg.capacity = (uint32_t)a->site_capacity;
+  sg.acc = a->d_site.as<unsigned long long>();
+  sg.lo = (uint32_t)lo;
+  sg.count = (uint32_t)cnt;
+  if (table) {
+    sg.out_acc = reinterpret_cast<unsigned long long*>(base);
+    *table = reinterpret_cast<const uint64_t*>(base);
+  }
+  if (hist) {
+    sg.hist = a->d_shist.as<unsigned int>();
+    sg.width = (uint32_t)H;
+    sg.out_hist = reinterpret_cast<unsigned int*>(base + table_bytes);
+    *hist = sg.out_hist;
+  }
+  dynk::launch_site_gather(sg, a->s_get);
+  HIP_TRY(a, hipGetLastError());
+  return DYN_OK;
+}
+
+// the conditions of the calls that read the map: a sparse table, completed jobs
+int site_map_quiet(dyn_aligner* a, const char* who) {
+  if (int rc = site_summary_quiet(a, who)) return rc;
+  if (!a->site_capacity || !a->d_smap.p) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = std::string(who) + ": the per-site table of this handle is dense (dyn_aligner_set_site_summary_sparse sets a sparse one)";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  return DYN_OK;
+}
 }  // namespace
+
+int dyn_aligner_site_map_stats(dyn_aligner* a, uint64_t out[4]) {
+  if (!a || !out) return DYN_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = site_map_quiet(a, "dyn_aligner_site_map_stats")) return rc;
+  out[0] = a->site_capacity;
+  const uint64_t* stats = a->d_site.as<uint64_t>() + (uint64_t)dynk::SS_FIELDS * a->site_capacity + (uint64_t)dynk::SS_TOTALS;
+  HIP_TRY(a, copy_out(a, out + 1, stats, (uint64_t)dynk::SM_STATS * sizeof(uint64_t)));
+  return DYN_OK;
+}
+
+int dyn_aligner_site_map_keys(dyn_aligner* a, uint64_t bucket_lo, uint64_t bucket_hi, uint32_t* keys) {
+  if (!a || (bucket_lo < bucket_hi && !keys)) return DYN_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = site_map_quiet(a, "dyn_aligner_site_map_keys")) return rc;
+  if (bucket_lo > bucket_hi || bucket_hi > a->site_capacity) {
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = "dyn_aligner_site_map_keys: [" + std::to_string(bucket_lo) + ", " + std::to_string(bucket_hi) + ") is not a range of the map's " +
+                    std::to_string(a->site_capacity) + " buckets";
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
+  if (bucket_lo == bucket_hi) return DYN_OK;
+  HIP_TRY(a, copy_out(a, keys, a->d_smap.as<uint32_t>() + bucket_lo, (bucket_hi - bucket_lo) * sizeof(uint32_t)));
+  return DYN_OK;
+}
+
+int dyn_aligner_site_map_windows(dyn_aligner* a, int shift, uint64_t* windows, uint64_t cap, uint64_t* count) {
+  if (!a || !count || (cap && !windows)) return DYN_ERR_INVALID_ARGUMENT;
+  const char* who = "dyn_aligner_site_map_windows";
+  auto fail = [&](const std::string& msg) {
+    std::lock_guard<std::mutex> lk(a->err_mu);
+    a->last_error = std::string(who) + ": " + msg;
+    return DYN_ERR_INVALID_ARGUMENT;
+  };
+  if (shift < 0 || shift > 31) return fail("shift " + std::to_string(shift) + " is not 0 .. 31");
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = site_map_quiet(a, who)) return rc;
+  const uint64_t n_win = ((a->num_sites - 1) >> shift) + 1;  // (a table has num_sites >= 1)
+  if (n_win > (1ull << 22))
+    return fail("shift " + std::to_string(shift) + " cuts the " + std::to_string(a->num_sites) + " ids into " + std::to_string(n_win) +
+                " windows, more than 4194304");
+  const uint64_t words = (n_win + 31) / 32;
+  HIP_TRY(a, a->d_squant.ensure(words * sizeof(uint32_t)));  // (the quantiles' staging: every window call runs under a->mu on s_get)
+  HIP_TRY(a, hipMemsetAsync(a->d_squant.p, 0, words * sizeof(uint32_t), a->s_get));
+  dynk::SiteWindows sw{a->d_smap.as<uint32_t>(), (uint32_t)a->site_capacity, shift, a->d_squant.as<unsigned int>()};
+  dynk::launch_site_map_windows(sw, a->s_get);
+  HIP_TRY(a, hipGetLastError());
+  std::vector<uint32_t> h(words);
+  HIP_TRY(a, copy_out(a, h.data(), sw.bitmap, words * sizeof(uint32_t)));
+  uint64_t n = 0;
+  for (uint64_t w = 0; w < n_win; ++w)
+    if (h[w >> 5] >> (w & 31) & 1u) {
+      if (n < cap) windows[n] = w;
+      ++n;
+    }
+  *count = n;
+  if (n > cap) return fail(std::to_string(n) + " windows are occupied, the caller's array holds " + std::to_string(cap));
+  return DYN_OK;
+}
 
 int dyn_aligner_site_summary_fetch(dyn_aligner* a, uint64_t lo, uint64_t hi, uint64_t* n_rows, uint64_t* n_samples,
                                    uint64_t* dwell_sq, uint64_t* m1_lo, uint64_t* m1_hi, uint64_t* m2_lo, uint64_t* m2_hi,
@@ -850,11 +989,14 @@ int dyn_aligner_site_summary_fetch(dyn_aligner* a, uint64_t lo, uint64_t hi, uin
   const uint64_t* table = a->d_site.as<uint64_t>();
   for (uint64_t s0 = lo; s0 < hi; s0 += step) {
     const uint64_t cnt = std::min(step, hi - s0);
-    HIP_TRY(a, copy_out(a, h.data(), table + F * s0, F * cnt * sizeof(uint64_t)));
+    const uint64_t* src = table + F * s0;
+    if (a->site_capacity)  // sparse: the window's ids looked up, their cells gathered (an absent id: zeros)
+      if (int rc = site_gather_window(a, s0, cnt, std::min(step, hi - lo), 0, 1, &src, nullptr)) return rc;
+    HIP_TRY(a, copy_out(a, h.data(), src, F * cnt * sizeof(uint64_t)));
     for (uint64_t c = 0; c < cnt; ++c)
       for (uint64_t f = 0; f < F; ++f) cols[f][s0 - lo + c] = h[F * c + f];
   }
-  HIP_TRY(a, copy_out(a, totals, table + F * a->num_sites, (uint64_t)dynk::SS_TOTALS * sizeof(uint64_t)));
+  HIP_TRY(a, copy_out(a, totals, table + F * site_rows(a), (uint64_t)dynk::SS_TOTALS * sizeof(uint64_t)));
   return DYN_OK;
 }
 
@@ -862,9 +1004,10 @@ int dyn_aligner_site_summary_reset(dyn_aligner* a) {
   if (!a) return DYN_ERR_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lk(a->mu);
   if (int rc = site_summary_quiet(a, "dyn_aligner_site_summary_reset")) return rc;
-  HIP_TRY(a, hipMemsetAsync(a->d_site.p, 0, ((uint64_t)dynk::SS_FIELDS * a->num_sites + (uint64_t)dynk::SS_TOTALS) * sizeof(uint64_t), a->s_get));
+  HIP_TRY(a, hipMemsetAsync(a->d_site.p, 0, site_table_words(a) * sizeof(uint64_t), a->s_get));  // (the map's statistics with it)
+  if (a->site_capacity) HIP_TRY(a, hipMemsetAsync(a->d_smap.p, 0xFF, a->site_capacity * sizeof(uint32_t), a->s_get));  // no key left
   if (a->d_shist.p && a->sh_bins)
-    HIP_TRY(a, hipMemsetAsync(a->d_shist.p, 0, a->num_sites * site_hist_width(a->sh_bins) * sizeof(uint32_t), a->s_get));
+    HIP_TRY(a, hipMemsetAsync(a->d_shist.p, 0, site_rows(a) * site_hist_width(a->sh_bins) * sizeof(uint32_t), a->s_get));
   HIP_TRY(a, hipStreamSynchronize(a->s_get));
   return DYN_OK;
 }
@@ -910,10 +1053,10 @@ int dyn_aligner_set_site_histogram(dyn_aligner* a, int bins, double lo, double h
   a->d_shist.release();
   a->sh_bins = 0;
   if (!a->d_site.p || !a->num_sites) return fail("dyn_aligner_set_site_summary(a, num_sites > 0) was never called on this handle");
-  const uint64_t bytes = a->num_sites * site_hist_width((uint32_t)bins) * sizeof(uint32_t);
+  const uint64_t bytes = site_rows(a) * site_hist_width((uint32_t)bins) * sizeof(uint32_t);  // (a sparse table: capacity rows)
   if (a->mem_budget && bytes > mem_budget_left(a)) {
     std::lock_guard<std::mutex> elk(a->err_mu);
-    a->last_error = "dyn_aligner_set_site_histogram: the histograms of " + std::to_string(a->num_sites) + " sites (" + std::to_string(bytes) +
+    a->last_error = "dyn_aligner_set_site_histogram: the histograms of " + std::to_string(site_rows(a)) + (a->site_capacity ? " rows (" : " sites (") + std::to_string(bytes) +
                     " bytes) do not fit dyn_aligner_set_mem_budget's " + std::to_string(a->mem_budget) + " bytes";
     return DYN_ERR_OUT_OF_MEMORY;
   }
@@ -921,7 +1064,7 @@ int dyn_aligner_set_site_histogram(dyn_aligner* a, int bins, double lo, double h
   if (e != hipSuccess) {
     (void)hipGetLastError();
     std::lock_guard<std::mutex> elk(a->err_mu);
-    a->last_error = "dyn_aligner_set_site_histogram: no device memory for the histograms of " + std::to_string(a->num_sites) + " sites (" +
+    a->last_error = "dyn_aligner_set_site_histogram: no device memory for the histograms of " + std::to_string(site_rows(a)) + (a->site_capacity ? " rows (" : " sites (") +
                     std::to_string(bytes) + " bytes): " + hipGetErrorString(e);
     return e == hipErrorOutOfMemory ? DYN_ERR_OUT_OF_MEMORY : DYN_ERR_DEVICE;
   }
@@ -959,7 +1102,10 @@ int dyn_aligner_site_histogram_fetch(dyn_aligner* a, uint64_t site_lo, uint64_t 
   const uint32_t* hist = a->d_shist.as<uint32_t>();
   for (uint64_t s0 = site_lo; s0 < site_hi; s0 += step) {
     const uint64_t cnt = std::min(step, site_hi - s0);
-    HIP_TRY(a, copy_out(a, h.data(), hist + H * s0, H * cnt * sizeof(uint32_t)));
+    const unsigned int* src = hist + H * s0;
+    if (a->site_capacity)
+      if (int rc = site_gather_window(a, s0, cnt, std::min(step, site_hi - site_lo), 0, 1, nullptr, &src)) return rc;
+    HIP_TRY(a, copy_out(a, h.data(), src, H * cnt * sizeof(uint32_t)));
     for (uint64_t c = 0; c < cnt; ++c) {
       std::memcpy(level + B * (s0 - site_lo + c), h.data() + H * c, B * sizeof(uint32_t));
       std::memcpy(dwell + D * (s0 - site_lo + c), h.data() + H * c + B, D * sizeof(uint32_t));
@@ -995,6 +1141,8 @@ int dyn_aligner_site_quantiles(dyn_aligner* a, uint64_t site_lo, uint64_t site_h
   for (uint64_t s0 = site_lo; s0 < site_hi; s0 += step) {
     const uint64_t cnt = std::min(step, site_hi - s0);
     sq.hist = a->d_shist.as<unsigned int>() + H * s0;
+    if (a->site_capacity)
+      if (int rc = site_gather_window(a, s0, cnt, most, 0, 1, nullptr, &sq.hist)) return rc;
     sq.count = (uint32_t)cnt;
     dynk::launch_site_quantiles(sq, a->s_get);
     HIP_TRY(a, hipGetLastError());
@@ -1040,9 +1188,22 @@ int dyn_aligner_site_summary_add(dyn_aligner* a, uint64_t lo, uint64_t hi, const
   std::vector<uint64_t> hc(F * most);
   std::vector<uint32_t> hh(H * most);
   dynk::SiteAdd sa{};
-  sa.totals = a->d_site.as<unsigned long long>() + F * a->num_sites;
+  sa.totals = a->d_site.as<unsigned long long>() + F * site_rows(a);
   sa.cols = a->d_sadd.as<unsigned long long>();
   sa.width = (uint32_t)H;
+  // sparse: the same staging, scattered into the rows of the window's ids (site_map_kernels.hpp)
+  dynk::SiteScatter ssc{};
+  uint64_t dropped_before = 0;
+  if (a->site_capacity) {
+    ssc.keys = a->d_smap.as<uint32_t>();
+    ssc.capacity = (uint32_t)a->site_capacity;
+    ssc.stats = sa.totals + dynk::SS_TOTALS;
+    ssc.acc = a->d_site.as<unsigned long long>();
+    ssc.totals = sa.totals;
+    ssc.cols = sa.cols;
+    ssc.width = (uint32_t)H;
+    HIP_TRY(a, copy_out(a, &dropped_before, ssc.stats + dynk::SM_SITES_DROPPED, sizeof(uint64_t)));
+  }
   for (uint64_t s0 = lo; s0 < hi; s0 += step) {
     const uint64_t cnt = std::min(step, hi - s0), o = s0 - lo;
     for (uint64_t c = 0; c < cnt; ++c)
@@ -1062,9 +1223,29 @@ int dyn_aligner_site_summary_add(dyn_aligner* a, uint64_t lo, uint64_t hi, const
     }
     sa.add_totals = (totals && s0 == lo) ? 1 : 0;  // the caller's totals once, with the first window
     for (int f = 0; f < dynk::SS_TOTALS; ++f) sa.totals_in[f] = sa.add_totals ? totals[f] : 0ull;
-    dynk::launch_site_add(sa, a->s_get);
+    if (a->site_capacity) {
+      ssc.hist = level ? a->d_shist.as<unsigned int>() : nullptr;
+      ssc.counters = sa.counters;
+      ssc.lo = (uint32_t)s0;
+      ssc.count = (uint32_t)cnt;
+      ssc.add_totals = sa.add_totals;
+      for (int f = 0; f < dynk::SS_TOTALS; ++f) ssc.totals_in[f] = sa.totals_in[f];
+      dynk::launch_site_scatter_add(ssc, a->s_get);
+    } else {
+      dynk::launch_site_add(sa, a->s_get);
+    }
     HIP_TRY(a, hipGetLastError());
     HIP_TRY(a, hipStreamSynchronize(a->s_get));  // (the host vectors are filled again for the next window)
+  }
+  if (a->site_capacity) {
+    uint64_t dropped = 0;
+    HIP_TRY(a, copy_out(a, &dropped, ssc.stats + dynk::SM_SITES_DROPPED, sizeof(uint64_t)));
+    if (dropped > dropped_before) {
+      std::lock_guard<std::mutex> elk(a->err_mu);
+      a->last_error = std::string(who) + ": " + std::to_string(dropped - dropped_before) + " sites found no bucket in the map of " +
+                      std::to_string(a->site_capacity) + " rows and were dropped; the other sites were added";
+      return DYN_ERR_OUT_OF_MEMORY;
+    }
   }
   return DYN_OK;
 }
@@ -1095,6 +1276,10 @@ int dyn_aligner_site_compare(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi,
     const uint64_t cnt = std::min(step, n - o);
     sc.hist_a = a->d_shist.as<unsigned int>() + H * (site_lo + o);
     sc.hist_b = a->d_shist.as<unsigned int>() + H * (other_lo + o);
+    if (a->site_capacity) {  // sparse: either window gathered into a scratch of its own
+      if (int rc = site_gather_window(a, site_lo + o, cnt, most, 0, 2, nullptr, &sc.hist_a)) return rc;
+      if (int rc = site_gather_window(a, other_lo + o, cnt, most, 1, 2, nullptr, &sc.hist_b)) return rc;
+    }
     sc.count = (uint32_t)cnt;
     dynk::launch_site_compare(sc, a->s_get);
     HIP_TRY(a, hipGetLastError());
@@ -1160,6 +1345,11 @@ int dyn_aligner_site_mixture(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi,
     const uint64_t cnt = std::min(step, n - o);
     sm.hist_a = a->d_shist.as<unsigned int>() + H * (site_lo + o);
     sm.hist_b = one ? nullptr : a->d_shist.as<unsigned int>() + H * (other_lo + o);
+    if (a->site_capacity) {
+      if (int rc = site_gather_window(a, site_lo + o, cnt, most, 0, one ? 1 : 2, nullptr, &sm.hist_a)) return rc;
+      if (!one)
+        if (int rc = site_gather_window(a, other_lo + o, cnt, most, 1, 2, nullptr, &sm.hist_b)) return rc;
+    }
     sm.count = (uint32_t)cnt;
     dynk::launch_site_mixture(sm, a->s_get);
     HIP_TRY(a, hipGetLastError());
@@ -1745,6 +1935,7 @@ int run_job_sync(dyn_batch* b, DynJob job, bool guided_train = false) {
     b->ss_table = a->d_site.as<unsigned long long>();  // the table as it stands at this submission
     b->ss_num_sites = a->num_sites;
     b->ss_hist = site_hist_now(a);
+    b->ss_map = site_map_now(a);
     rc = enqueue_job(b, job);
     if (rc != DYN_OK) {
       (void)hipStreamSynchronize(a->stream);

@@ -177,6 +177,11 @@ struct SiteHist {
   uint32_t bins = 0;
   double lo = 0.0, inv_w = 0.0;
 };
+// the map of a sparse table as a job sees it (dyn_aligner_set_site_summary_sparse): taken at its submission likewise
+struct SiteMap {
+  uint32_t* keys = nullptr;  // [capacity]; nullptr: the table is dense
+  uint64_t capacity = 0;
+};
 
 // ---- the per-segment outputs a job may add to its rows (one fetcher, one out-struct and one CSV flag each) ---------------------
 enum Output { OUT_LEVELS, OUT_SCORES, OUT_BORDERS, OUT_INTERVALS, OUT_SOFT, OUT_SAMPLES, OUT_COUNT };
@@ -229,6 +234,12 @@ struct dyn_aligner {
   // num_sites > 0), kept until the setter names another size; a job snapshots pointer and size at its submission
   dyneng::DevBuf d_site;
   uint64_t num_sites = 0;
+  // the sparse mode (dyn_aligner_set_site_summary_sparse, site_map.hpp): site_capacity > 0, d_smap the [site_capacity] uint32 keys,
+  // d_site [7 site_capacity + 5 + 3] u64 (the map's three statistics behind the totals), the histograms site_capacity rows; num_sites
+  // stays the bound of the ids. d_sgath: the dense scratch the window calls gather into (one or two windows of what the call reads)
+  dyneng::DevBuf d_smap;
+  uint64_t site_capacity = 0;
+  dyneng::DevBuf d_sgath;
   // the per-site histograms beside it: [num_sites][sh_bins + 2 + 16] u32, allocated and zeroed by dyn_aligner_set_site_histogram(a,
   // bins > 0, lo, hi), kept (bins = 0 only stops the counting) until that setter names other parameters or the table another size
   dyneng::DevBuf d_shist;
@@ -273,11 +284,21 @@ struct dyn_aligner {
 };
 
 namespace dyneng {
-// what dyn_aligner_set_mem_budget leaves once the per-site table and its histograms are taken off (0: no budget was set)
+// what dyn_aligner_set_mem_budget leaves once the per-site table, its histograms, a sparse table's map and gather scratch are taken off (0: no budget was set)
 inline uint64_t mem_budget_left(const dyn_aligner* a) {
   if (!a->mem_budget) return 0;
-  const uint64_t taken = a->d_site.bytes + a->d_shist.bytes;
+  const uint64_t taken = a->d_site.bytes + a->d_shist.bytes + a->d_smap.bytes + a->d_sgath.bytes;
   return a->mem_budget > taken ? a->mem_budget - taken : 1;
+}
+// rows of the per-site table and of its histograms: the capacity of a sparse table, the id space of a dense one
+inline uint64_t site_rows(const dyn_aligner* a) { return a->site_capacity ? a->site_capacity : a->num_sites; }
+inline SiteMap site_map_now(const dyn_aligner* a) {
+  SiteMap m;
+  if (a->site_capacity && a->d_smap.p) {
+    m.keys = a->d_smap.as<uint32_t>();
+    m.capacity = a->site_capacity;
+  }
+  return m;
 }
 // uint32 counters per site: under, the level bins, over, the dwell bins
 inline uint64_t site_hist_width(uint32_t bins) { return (uint64_t)bins + 2 + (uint64_t)dynk::SH_DWELL_BINS; }
@@ -373,6 +394,7 @@ struct dyn_batch {
   dyneng::DevBuf d_sites;
   unsigned long long* ss_table = nullptr;
   uint64_t ss_num_sites = 0;
+  dyneng::SiteMap ss_map;  // the map of a sparse table as it stood at submission (keys == nullptr: dense)
   std::vector<std::pair<uint32_t, uint32_t>> ss_ranges;
   // the per-site histograms as they stood at submission (p == nullptr: off). A merged launch splits ss_ranges into the members
   // submitted with the histograms on (sh_ranges) and the others (ss_plain_ranges)

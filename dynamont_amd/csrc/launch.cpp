@@ -293,8 +293,15 @@ std::vector<dynk::KmerSummary> kmer_summary_args(const dyn_batch* b) {
 std::vector<dynk::SiteSummary> site_summary_args(const dyn_batch* b) {
   if (!b->want.site_summary || !b->ss_table || !b->ss_num_sites || !b->has_sites || !b->d_sites.p) return {};
   // (a merged launch has ids only when a member that asked staged some: its ranges are never empty)
-  unsigned long long* totals = b->ss_table + (uint64_t)dynk::SS_FIELDS * b->ss_num_sites;
+  // (a sparse table has ss_map.capacity rows, the totals behind them and the map's statistics behind the totals)
+  const uint64_t rows = b->ss_map.keys ? b->ss_map.capacity : b->ss_num_sites;
+  unsigned long long* totals = b->ss_table + (uint64_t)dynk::SS_FIELDS * rows;
   dynk::SiteSummary ss{b->d_sig.as<double>(), b->d_sites.as<uint32_t>(), b->ss_table, totals, (uint32_t)b->ss_num_sites, 0u, (uint32_t)b->n};
+  if (b->ss_map.keys) {
+    ss.map_keys = b->ss_map.keys;
+    ss.capacity = (uint32_t)b->ss_map.capacity;
+    ss.map_stats = totals + dynk::SS_TOTALS;
+  }
   if (!b->want.site_histogram || !b->ss_hist.p) return over_ranges(ss, b->ss_ranges);
   // the histograms: a merged launch's members submitted with them on (sh_ranges) count, the others (ss_plain_ranges) add to the table alone
   std::vector<dynk::SiteSummary> out;

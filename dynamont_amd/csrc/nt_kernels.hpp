@@ -301,6 +301,8 @@ void launch_kmer_summary(const ReadDesc* descs, int n_reads, uint32_t max_N, con
 // per-site level summary of a run (site_summary.hip, dyn_aligner_set_site_summary); acc == nullptr: not asked for
 constexpr int SS_FIELDS = 7;  // per site: n_rows, n_samples, dwell_sq, m1_lo, m1_hi, m2_lo, m2_hi
 constexpr int SS_TOTALS = 5;  // reads_ok, rows_added, samples_added, rows_without_site, rows_skipped
+constexpr int SM_STATS = 3;   // of a sparse table's map (site_map.hpp), behind the totals: n_keys, rows_dropped, sites_dropped
+constexpr int SM_N_KEYS = 0, SM_ROWS_DROPPED = 1, SM_SITES_DROPPED = 2;
 struct SiteSummary {
   const double* sig;          // the signal the read queue aligned (ReadDesc::sig_off counts from here)
   const uint32_t* sites;      // site id of every output row (ReadDesc::par_off counts from here): row j <-> entry j
@@ -314,6 +316,12 @@ struct SiteSummary {
   unsigned int* hist;         // [num_sites][bins + 2 + 16] under, level bins 1 .. bins, over, dwell bins 0 .. 15
   uint32_t bins;
   double hist_lo, inv_w;      // level bin of m: u = (m - hist_lo) * inv_w, inv_w = bins / (hi - lo)
+  // the sparse mode (dyn_aligner_set_site_summary_sparse, site_map.hpp); map_keys == nullptr: dense, the id is the row. Sparse:
+  // acc and hist have `capacity` rows and a row's bucket is looked up (or taken) as it is added; num_sites still bounds the ids.
+  // An aggregate initialiser that stops earlier leaves them zero.
+  uint32_t* map_keys;         // [capacity], 0xFFFFFFFF: empty
+  uint32_t capacity;
+  unsigned long long* map_stats;  // [3] n_keys, rows_dropped, sites_dropped
 };
 void launch_site_summary(const ReadDesc* descs, int n_reads, uint32_t max_N, const ReadState* st, const TraceBuffers& tb,
                          const SiteSummary& ss, hipStream_t s);
@@ -377,6 +385,44 @@ struct SiteAdd {
   unsigned long long totals_in[SS_TOTALS];
 };
 void launch_site_add(const SiteAdd& sa, hipStream_t s);
+// the window calls of a sparse table (site_map_kernels.hpp). k_site_gather: the ids [lo, lo + count) looked up, their cells copied
+// into a dense scratch table (and scratch counters when hist is set); an absent id gets zeros
+struct SiteGather {
+  const uint32_t* keys;             // [capacity]
+  uint32_t capacity;
+  const unsigned long long* acc;    // the table: [capacity][7]
+  const unsigned int* hist;         // [capacity][width]; nullptr: the table alone
+  uint32_t width;                   // bins + 2 + 16
+  uint32_t lo, count;               // the window of ids
+  unsigned long long* out_acc;      // [count][7]; nullptr: the counters alone
+  unsigned int* out_hist;           // [count][width]
+};
+void launch_site_gather(const SiteGather& sg, hipStream_t s);
+// k_site_scatter_add: the add of SiteAdd into the rows of the ids [lo, lo + count); a site with any non-zero word is looked up or
+// inserted, an all-zero site inserts nothing, a site without a bucket counts in stats[sites_dropped]
+struct SiteScatter {
+  uint32_t* keys;
+  uint32_t capacity;
+  unsigned long long* stats;        // [3] n_keys, rows_dropped, sites_dropped
+  unsigned long long* acc;          // the table: [capacity][7]
+  unsigned long long* totals;       // the table's [5] totals
+  unsigned int* hist;               // [capacity][width]; nullptr: the table alone
+  const unsigned long long* cols;   // staged [count][7]
+  const unsigned int* counters;     // staged [count][width]
+  uint32_t width;
+  uint32_t lo, count;
+  int add_totals;
+  unsigned long long totals_in[SS_TOTALS];
+};
+void launch_site_scatter_add(const SiteScatter& sc, hipStream_t s);
+// k_site_map_windows: every occupied bucket sets bit (key >> shift) of bitmap
+struct SiteWindows {
+  const uint32_t* keys;
+  uint32_t capacity;
+  int shift;
+  unsigned int* bitmap;             // [ceil(((num_sites - 1) >> shift) + 1, 32)] uint32, zeroed by the caller
+};
+void launch_site_map_windows(const SiteWindows& sw, hipStream_t s);
 // per-border segment quality scores (segment_scores.hip, dyn_aligner_set_segment_scores): columns indexed like the output
 // rows, zeroed by the caller; median_delta == nullptr: not asked for
 struct ScoreCols {

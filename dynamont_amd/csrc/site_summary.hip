@@ -2,6 +2,7 @@
 // reads' event means per caller-supplied site id, accumulated on the handle as exact integers while the switch is on. The
 // kernels and the definition are in site_summary_kernels.hpp (shared with tests/device_math/site_summary.hip).
 #include "site_compare_kernels.hpp"
+#include "site_map_kernels.hpp"
 #include "site_mixture_kernels.hpp"
 #include "site_quantile_kernels.hpp"
 #include "site_summary_kernels.hpp"
@@ -24,5 +25,11 @@ void launch_site_mixture(const SiteMixture& sm, hipStream_t s) { launch_site_mix
 
 // dyn_aligner_site_summary_add: one staged window into the table and its counters
 void launch_site_add(const SiteAdd& sa, hipStream_t s) { launch_site_add_kernel(sa, s); }
+
+// the window calls of a sparse table: one window of ids gathered into a dense scratch, one staged window scattered into the
+// rows of its ids, the bitmap of the occupied id windows
+void launch_site_gather(const SiteGather& sg, hipStream_t s) { launch_site_gather_kernel(sg, s); }
+void launch_site_scatter_add(const SiteScatter& sc, hipStream_t s) { launch_site_scatter_add_kernel(sc, s); }
+void launch_site_map_windows(const SiteWindows& sw, hipStream_t s) { launch_site_map_windows_kernel(sw, s); }
 
 }  // namespace dynk

@@ -28,10 +28,15 @@
 //   dwell  min(31 - clz(L), 15)
 // with 32-bit device-scope atomics: exact while a site has fewer than 2^32 rows. k_site_quantiles reduces a window of the level
 // histograms to ranks and bins on the device (site_quantile_kernels.hpp).
+//
+// The sparse mode (dyn_aligner_set_site_summary_sparse, ss.map_keys != nullptr): acc and hist have ss.capacity rows, and a row
+// that passed every check above looks its id up in the map (site_map.hpp), inserting it when it is new; the bucket is the row.
+// A row whose id finds no bucket in its probe window is dropped: counted in map_stats[rows_dropped] and in rows_skipped.
 #pragma once
 
 #include "exact_sum_kernels.hpp"
 #include "nt_kernels.hpp"
+#include "site_map.hpp"
 
 namespace dynk {
 
@@ -43,6 +48,14 @@ __device__ __forceinline__ bool ss_accumulate(const SiteSummary& ss, uint32_t id
   const double m = __ddiv_rn(s1, (double)L);
   const double mm = __dmul_rn(m, m);
   if (!(mm < XS_TWO64)) return false;  // NaN and +-inf fail the comparison too
+  if (ss.map_keys) {  // sparse: the row of the id, taken now when the id is new; a row left out above never inserts a key
+    const uint32_t row = sm_find_or_insert(ss.map_keys, ss.capacity, ss.map_stats, id);
+    if (row == SM_NO_ROW) {  // dropped: counted here and, by the caller, in rows_skipped
+      atomicAdd(ss.map_stats + SM_ROWS_DROPPED, 1ull);
+      return false;
+    }
+    id = row;
+  }
   unsigned long long* cell = ss.acc + (uint64_t)id * SS_FIELDS;
   atomicAdd(cell, 1ull);
   atomicAdd(cell + 1, (unsigned long long)L);

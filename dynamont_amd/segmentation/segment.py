@@ -137,6 +137,14 @@ def parse(argv=None) -> Namespace:
                    help="per reference position across reads (the basecalls must be a MAPPED .bam): coverage, dwell and level "
                         "mean / sd of the reads' event means, summed on the GPU as exact integers, written as a TSV of the sites "
                         "with coverage > 0 in reference order (INTEGRATION.md section 3). One process only")
+    p.add_argument("--site-capacity", type=int, default=0, metavar="ROWS",
+                   help="with --site-summary FILE: keep the per-site table SPARSE, ROWS rows behind a hash map on the GPU from "
+                        "reference position to row (60 bytes per row, plus the histograms' per row), instead of one row per "
+                        "reference position: for genomes and transcriptomes whose dense table does not fit. Choose ROWS at least "
+                        "twice the positions the reads cover. A position that finds no row in a full map is left out of FILE as a "
+                        "whole (every position in FILE is complete); the run then says so and ends with exit status 3. With "
+                        "--site-control the rows hold the control's positions too: a control that does not fit ends the run with a "
+                        "MemoryError before any read is aligned")
     p.add_argument("--site-histogram", default="", metavar="BINS[:LO:HI]",
                    help="with --site-summary FILE: also count, per reference position, a histogram of the reads' event means with "
                         "BINS (2 .. 254) bins over [LO, HI) and one of their dwell on the GPU, and add the columns level_q25, "
@@ -967,7 +975,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             guide_auto: int = 0, guide_rounds: int = 8, guide_rescue: int = 0, guide_rescue_margin: int = 1,
             posterior_samples: int = 0, sample_seed: int = 0, border_interval: float = 0.0,
             soft_levels: bool = False, site_summary: str = "", site_histogram: str = "", site_table_out: str = "",
-            site_control: str = "", site_mixture: int = 0) -> None:
+            site_control: str = "", site_mixture: int = 0, site_capacity: int = 0) -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
@@ -1001,6 +1009,11 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                          "--site-histogram BINS[:LO:HI]")
     if site_mixture and not 1 <= site_mixture <= 1024:
         raise ValueError(f"--site-mixture {site_mixture}: MAX_ITERS must be 1 .. 1024")
+    if site_capacity and not site_summary:
+        raise ValueError("--site-capacity sizes the sparse per-site table: it needs --site-summary FILE")
+    if site_capacity and not 1 <= site_capacity <= 4294967294:
+        raise ValueError(f"--site-capacity {site_capacity}: ROWS must be 1 .. 4294967294")
+    LAST_RUN.pop("site_rows_dropped", None)
     site_refs = None
     control_table = None
     if site_summary:
@@ -1024,7 +1037,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             control_table = load_site_table(site_control)
             check_site_control(control_table, site_control, names, lengths, site_hist)
             if 2 * int(site_refs[1][-1]) >= DYN_SITE_NONE:
-                raise ValueError(f"--site-control: the run and the control take 2 x {int(site_refs[1][-1])} sites; the table takes up to 4294967294")
+                raise ValueError(f"--site-control: the run and the control take 2 x {int(site_refs[1][-1])} sites; the table takes up to 4294967294"
+                                 + (" with --site-capacity too: the site ids are 32-bit" if site_capacity else ""))
     from dynamont_amd import parallel
     comm, local_rank = parallel.init_from_env()
     rank, world = (comm.rank, comm.world) if comm else (0, 1)
@@ -1116,18 +1130,29 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             pooled = control_table is not None
             mixture = lambda lo, hi: site_mixture_columns(aligner.site_mixture(lo, hi, num_sites + lo if pooled else None,  # noqa: E731
                                                                                max_iters=site_mixture), pooled)
+        # --site-capacity: only the 2^20-id windows that hold a key are gathered (a genome-wide id space has thousands of empty ones)
+        windows = aligner.site_map_windows(20).tolist() if site_capacity else None
         written = write_site_summary(site_summary, aligner.site_summary, num_sites, *site_refs, quantiles=quantiles, control=control,
-                                     mixture=mixture)
+                                     mixture=mixture, windows=windows)
         if site_table_out:
             from dynamont_amd.bam_io import bam_references
             from dynamont_amd.segmentation.utils import save_site_table
-            saved = save_site_table(site_table_out, aligner, *bam_references(basecalls), lo=0, hi=num_sites)   # the run's half only
+            saved = save_site_table(site_table_out, aligner, *bam_references(basecalls), lo=0, hi=num_sites, windows=windows)   # the run's half only
             print(f"site table written: {site_table_out}: {saved} sites with coverage", file=sys.stderr, flush=True)
         t = aligner.site_summary(0, 0)["totals"]
+        sparse = ""
+        if site_capacity:
+            m = aligner.site_map()
+            sparse = f"; sparse table: {m['n_keys']} of {m['capacity']} rows taken, rows_dropped {m['rows_dropped']}"
+            LAST_RUN["site_rows_dropped"] = m["rows_dropped"]
         print(f"site summary written: {site_summary}: {written} sites with coverage; reads_ok {t['reads_ok']}, rows_added {t['rows_added']}, "
               f"samples_added {t['samples_added']}, rows_without_site {t['rows_without_site']}, rows_skipped {t['rows_skipped']}; "
               f"reads left without ids (unmapped, secondary / supplementary, reverse strand, CIGAR in a CG tag or not covering the read): "
-              f"{site_counts[1]} of {site_counts[0]}", file=sys.stderr, flush=True)
+              f"{site_counts[1]} of {site_counts[0]}{sparse}", file=sys.stderr, flush=True)
+        if site_capacity and m["rows_dropped"]:
+            print(f"site summary INCOMPLETE: {m['rows_dropped']} rows of positions that found no row in the full table of {m['capacity']} "
+                  f"(rows_skipped counts them too) were dropped; every position in {site_summary} is complete, positions are missing. "
+                  f"Run again with a larger --site-capacity (exit status 3)", file=sys.stderr, flush=True)
 
     def write_band_report(lines):
         # --band-report, with the pipeline dry: every rank's lines travel to rank 0 (one more gather), which sorts and writes
@@ -1182,8 +1207,11 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                 aligner.set_kmer_summary(True)
             if site_summary:
                 try:
-                    aligner.set_site_summary(int(site_refs[1][-1]) * (2 if control_table is not None else 1))  # --site-control: [N, 2N)
+                    aligner.set_site_summary(int(site_refs[1][-1]) * (2 if control_table is not None else 1),  # --site-control: [N, 2N)
+                                             capacity=site_capacity or None)
                 except MemoryError as error:
+                    if site_capacity:
+                        raise MemoryError(f"--site-capacity: the sparse table of {site_capacity} rows (60 bytes each) does not fit: {error}") from None
                     raise MemoryError(f"--site-summary: the table of {int(site_refs[1][-1])} sites (56 bytes each) does not fit: {error}") from None
                 if site_hist:
                     from dynamont_amd.segmentation.utils import site_histogram_range
@@ -1193,6 +1221,9 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                     try:
                         aligner.set_site_histogram(bins, h_lo, h_hi)
                     except MemoryError as error:
+                        if site_capacity:
+                            raise MemoryError(f"--site-histogram: the counters of {site_capacity} rows ({4 * (bins + 18)} bytes each) "
+                                              f"do not fit: {error}") from None
                         raise MemoryError(f"--site-histogram: the counters of {int(site_refs[1][-1])} sites ({4 * (bins + 18)} bytes each) "
                                           f"do not fit: {error}") from None
                     print(f"site histogram: {bins} bins over [{h_lo!r}, {h_hi!r})", file=sys.stderr, flush=True)
@@ -1200,7 +1231,15 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                         # before the first batch: the control into [N, 2N). (A range left to the model table is known only now.)
                         from dynamont_amd.segmentation.utils import check_site_control, load_site_control
                         check_site_control(control_table, site_control, site_refs[0], control_table["ref_lengths"], (bins, h_lo, h_hi))
-                        added = load_site_control(aligner, control_table, int(site_refs[1][-1]))
+                        try:
+                            added = load_site_control(aligner, control_table, int(site_refs[1][-1]))
+                        except MemoryError as error:
+                            if not site_capacity:
+                                raise
+                            # a control that is only partly in the table would be compared as if it were whole: the run ends here,
+                            # before any read is aligned and before the TSV exists
+                            raise MemoryError(f"--site-capacity {site_capacity}: the control {site_control} does not fit the sparse table "
+                                              f"beside the run ({error}); run again with a larger --site-capacity") from None
                         print(f"site control: {site_control}: {added} sites with coverage loaded", file=sys.stderr, flush=True)
             if band_report:
                 aligner.set_band_margin(True)
@@ -1366,8 +1405,10 @@ def main(argv=None) -> None:
             guide_rescue_margin=args.guide_rescue_margin, posterior_samples=args.posterior_samples, sample_seed=args.sample_seed,
             border_interval=args.border_interval, soft_levels=args.soft_levels, site_summary=args.site_summary, site_table_out=args.site_table_out,
             site_control=args.site_control, site_mixture=args.site_mixture,
-            site_histogram=args.site_histogram)
+            site_histogram=args.site_histogram, site_capacity=args.site_capacity)
     _stamp("segment() returned (aligner closed)")
+    # --site-capacity: rows were dropped from a full table -- everything is written, the status says that sites are missing
+    status = 3 if LAST_RUN.get("site_rows_dropped") else 0
     if argv is None and not int(__import__("os").environ.get("WORLD_SIZE", "1") or 1) > 1:
         # Invoked as the command (console script / python -m), single process, everything written and closed: leave without
         # the interpreter's and the HIP runtime's orderly teardown (0.3 s in which ~130 GB of device memory are handed back
@@ -1375,7 +1416,9 @@ def main(argv=None) -> None:
         import os
         sys.stdout.flush()
         sys.stderr.flush()
-        os._exit(0)
+        os._exit(status)
+    if status:
+        sys.exit(status)
 
 
 if __name__ == "__main__":

@@ -326,7 +326,7 @@ def site_summary_lines(summary: dict, lo: int, ref_names, offsets) -> list:
 
 
 def write_site_summary(path: str, fetch, num_sites: int, ref_names, offsets, window: int = 1 << 20, quantiles=None, control=None,
-                       mixture=None) -> int:
+                       mixture=None, windows=None) -> int:
     """--site-summary FILE: the header and one line per site with coverage > 0, in reference order. ``fetch(lo, hi)`` returns a
     window of the table (Aligner.site_summary): a genome-sized table is never on the host at once. ``quantiles(lo, hi)``
     (--site-histogram: Aligner.site_quantiles of SITE_QUANTILE_PROBS over the same window) adds the three columns of
@@ -334,15 +334,18 @@ def write_site_summary(path: str, fetch, num_sites: int, ref_names, offsets, win
     one string per site of the window, the eight columns of SITE_CONTROL_HEADER, added to every line behind the others.
     ``mixture(lo, hi)`` (--site-mixture: ``site_mixture_columns`` over the same window) returns one string per site of the window,
     the columns of SITE_MIXTURE_HEADER -- with a control, of SITE_MIXTURE_CONTROL_HEADER too -- added last. Sites are written when
-    the RUN has coverage. Returns the sites written."""
+    the RUN has coverage. ``windows`` (a sparse table: Aligner.site_map_windows at log2(window)): the indices w of the windows
+    [w * window, (w + 1) * window) that hold a site, the only ones walked then -- the default walks them all; the lines are the
+    same, a window without a site has none. Returns the sites written."""
     written = 0
+    starts = range(0, int(num_sites), window) if windows is None else [int(w) * window for w in sorted(windows) if int(w) * window < int(num_sites)]
     with open(path, "w") as f:
         header = SITE_SUMMARY_HEADER if quantiles is None else SITE_SUMMARY_HEADER[:-1] + "\t" + SITE_QUANTILE_HEADER + "\n"
         header = header if control is None else header[:-1] + "\t" + SITE_CONTROL_HEADER + "\n"
         if mixture is not None:
             header = header[:-1] + "\t" + SITE_MIXTURE_HEADER + ("" if control is None else "\t" + SITE_MIXTURE_CONTROL_HEADER) + "\n"
         f.write(header)
-        for lo in range(0, int(num_sites), window):
+        for lo in starts:
             hi = min(lo + window, int(num_sites))
             summary = fetch(lo, hi)
             lines = site_summary_lines(summary, lo, ref_names, offsets)
@@ -465,19 +468,24 @@ def ks_two_sample_p(d: float, n_a: int, n_b: int) -> float:
     return min(1.0, max(0.0, 2.0 * total))
 
 
-def save_site_table(path: str, aligner, ref_names, ref_lengths, lo: int = 0, hi=None, window: int = 1 << 20) -> int:
+def save_site_table(path: str, aligner, ref_names, ref_lengths, lo: int = 0, hi=None, window: int = 1 << 20, windows=None) -> int:
     """The covered sites of the window [lo, hi) (default: one sample, the references' total length) of ``aligner``'s per-site table
     as an .npz (numpy only): ``site`` uint64 (relative to ``lo``), the seven limb columns, ``level`` / ``dwell`` counters when the
     handle has histograms, ``hist_spec`` = (bins, lo, hi) with the bounds as float64 BITS (uint64; bins 0 = no histograms),
     ``ref_names``, ``ref_lengths``, ``totals`` and ``version``. Fetched window by window: nothing genome-sized is on the host at
-    once. Returns the sites saved."""
+    once. ``windows`` (a sparse table: Aligner.site_map_windows at log2(window)): the indices w of the id windows [w * window,
+    (w + 1) * window) that hold a site, the only ones fetched then; the file is the same. Returns the sites saved."""
     lengths = np.asarray(ref_lengths, dtype=np.uint64)
     hi = int(lo) + int(lengths.sum()) if hi is None else int(hi)
+    if windows is None:
+        spans = [(w0, min(w0 + int(window), hi)) for w0 in range(int(lo), hi, int(window))]
+    else:
+        spans = [(max(int(lo), int(w) * int(window)), min(hi, (int(w) + 1) * int(window))) for w in sorted(windows)]
+        spans = [(w0, w1) for w0, w1 in spans if w0 < w1]
     spec = getattr(aligner, "_site_histogram", None)
     sites, limbs, level, dwell = [], [[] for _ in SITE_TABLE_LIMBS], [], []
     totals = None
-    for w0 in range(int(lo), hi, int(window)):
-        w1 = min(w0 + int(window), hi)
+    for w0, w1 in spans:
         t = aligner.site_summary(w0, w1)
         totals = t["totals"]
         idx = np.flatnonzero(t["n_rows"])

@@ -722,6 +722,31 @@ int dyn_aligner_site_mixture(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi,
     uint32_t max_iters, double tol, uint32_t min_n,
     double* pi1, double* mu0, double* mu1, double* var0, double* var1, double* r_a, double* r_b,
     uint32_t* n_a, uint32_t* n_b, uint32_t* out_a, uint32_t* out_b, uint32_t* iters, uint32_t* status);
+/* The SPARSE mode of the per-site table: the table, and the histograms beside it, have `capacity` rows
+ * and the handle keeps a hash map on the GPU from site id to row (uint32 keys[capacity], 0xFFFFFFFF = DYN_SITE_NONE = empty; the
+ * bucket is the row; linear probing over at most min(capacity, 128) buckets). A row is taken by the first job row, or the first
+ * dyn_aligner_site_summary_add site, that names the id; nothing is ever deleted, so an id is in the map with ALL of its rows or
+ * absent with all of them dropped. num_sites stays the bound of the ids and of every window call and may be anything below
+ * DYN_SITE_NONE whatever the memory; the memory is capacity * (4 + 56) bytes plus 4 * (bins + 2 + 16) per row of histograms. Every
+ * call that reads or adds a window of sites keeps its meaning in id space: an absent id reads as zeros, and while nothing was
+ * dropped a sparse handle returns the bits a dense one returns. A job row whose id finds no bucket is counted in rows_dropped AND
+ * in the totals' rows_skipped. dyn_aligner_site_summary_add inserts the ids of the sites that have any non-zero word; when sites
+ * found no bucket it returns DYN_ERR_OUT_OF_MEMORY with a text that gives their number (sites_dropped) -- the other sites were
+ * added. Everything dyn_aligner_set_site_summary says applies: num_sites = 0 is the switch off, the same (num_sites, capacity)
+ * again the switch on with nothing zeroed; another size, another capacity or the other mode waits for the jobs in flight, releases
+ * table, map and histograms and starts anew; the memory budget text gives rows and bytes. dyn_aligner_site_summary_reset also
+ * empties the map and zeroes its statistics. capacity = 0 with num_sites > 0: DYN_ERR_INVALID_ARGUMENT. A full map is not
+ * resized: reset, or set a larger one. */
+int dyn_aligner_set_site_summary_sparse(dyn_aligner* a, uint64_t num_sites, uint64_t capacity);
+/* out: capacity, n_keys, rows_dropped, sites_dropped. The conditions of dyn_aligner_site_summary_fetch (completed jobs); on a dense
+ * handle DYN_ERR_INVALID_ARGUMENT with a text that says so -- as for the two calls below. */
+int dyn_aligner_site_map_stats(dyn_aligner* a, uint64_t out[4]);
+/* The keys of the buckets [bucket_lo, bucket_hi) (0xFFFFFFFF: empty), for diagnostics and tests. */
+int dyn_aligner_site_map_keys(dyn_aligner* a, uint64_t bucket_lo, uint64_t bucket_hi, uint32_t* keys);
+/* The id windows [w << shift, (w + 1) << shift) that hold a key, ascending, found on the GPU: *count of them, the first
+ * min(*count, cap) written to windows; more than cap is DYN_ERR_INVALID_ARGUMENT (call again with *count). 0 <= shift <= 31 and
+ * at most 2^22 windows in the id space. A caller walks the table window by window without gathering the empty ones. */
+int dyn_aligner_site_map_windows(dyn_aligner* a, int shift, uint64_t* windows, uint64_t cap, uint64_t* count);
 /* The rule of mode 1 for one read, given its k-mer codes (dyn_validate_batch) and signal length: 0 = no structural tie;
  * otherwise the number of forward rows that run in the strict arithmetic (UINT32_MAX: all of them). Host only. */
 uint32_t dyn_tie_rows(const dyn_aligner* a, const int32_t* kmers, uint64_t n_kmers, uint64_t signal_len);

@@ -46,6 +46,9 @@ void launch_site_quantiles(const SiteQuantiles&, hipStream_t) { no_device("launc
 void launch_site_compare(const SiteCompare&, hipStream_t) { no_device("launch_site_compare"); }
 void launch_site_add(const SiteAdd&, hipStream_t) { no_device("launch_site_add"); }
 void launch_site_mixture(const SiteMixture&, hipStream_t) { no_device("launch_site_mixture"); }
+void launch_site_gather(const SiteGather&, hipStream_t) { no_device("launch_site_gather"); }
+void launch_site_scatter_add(const SiteScatter&, hipStream_t) { no_device("launch_site_scatter_add"); }
+void launch_site_map_windows(const SiteWindows&, hipStream_t) { no_device("launch_site_map_windows"); }
 void launch_rescale_init(RescaleState*, uint64_t, hipStream_t) { no_device("launch_rescale_init"); }
 void launch_rescale_pass(const ReadDesc*, int, uint32_t, const ReadState*, const TraceBuffers&, const double*, double*, const Emis*, double*,
                          RescaleState*, hipStream_t) {
