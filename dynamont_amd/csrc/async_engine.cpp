@@ -788,10 +788,10 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
   {
     std::lock_guard<std::mutex> lk(a->mu);
     staged_rc = take_staged_sites(a, "dyn_batch_align_async", n_reads, seq_offsets, &site_ids);
-    ss_table = a->d_site.as<unsigned long long>();  // the table as it stands at this submission
-    ss_num_sites = a->num_sites;
-    ss_hist = site_hist_now(a);
-    ss_map = site_map_now(a);
+    ss_table = a->site.table.as<unsigned long long>();  // the table as it stands at this submission
+    ss_num_sites = a->site.num_sites;
+    ss_hist = a->site.hist_now(a->opt.site_histogram);
+    ss_map = a->site.map_now();
   }
   if (!ticket || !sig_offsets || !seq_offsets || (n_reads && ((!signals && !rs) || !seqs))) return DYN_ERR_INVALID_ARGUMENT;
   if (staged_rc != DYN_OK) return staged_rc;

@@ -1,6 +1,6 @@
 // dynamont_mi.cpp -- C-ABI entry points (include/dynamont_mi.h): handles, validation + k-mer coding per read, the staged and
 // one-shot batch calls, result marshalling. The launches themselves: launch.cpp (one per batch), session.cpp (the resident read
-// queue); buffers: buffers.cpp; the asynchronous pipeline: async_engine.cpp.
+// queue); buffers: buffers.cpp; the asynchronous pipeline: async_engine.cpp; the per-site table's calls: site_table.cpp.
 //
 // Reference driver being replaced: NTAligner::align / NTAligner::train
 // (src/cpp/NT_aligner_api.cpp:230-312, 567-639) and the pybind marshalling around them
@@ -41,15 +41,6 @@ void copy_msg(char* buf, uint64_t cap, const std::string& s) {
   const size_t n = std::min<size_t>(cap - 1, s.size());
   std::memcpy(buf, s.data(), n);
   buf[n] = 0;
-}
-
-// A getter's copy off the device: on the handle's own non-blocking stream and waited for there. The data is complete when a
-// getter may be called (the synchronous job calls return after the compute stream has passed the batch, dyn_batch_wait after
-// the copy-out stream has); a null-stream hipMemcpy would ALSO wait for the resident session kernel that later tickets keep
-// open (the session stream is not a non-blocking one) and serialise a caller's stream of batches.
-hipError_t copy_out(dyn_aligner* a, void* dst, const void* src, size_t bytes) {
-  hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, a->s_get);
-  return e != hipSuccess ? e : hipStreamSynchronize(a->s_get);
 }
 
 }  // namespace
@@ -448,14 +439,7 @@ void dyn_aligner_destroy(dyn_aligner* a) {
     a->d_model.release();
     a->d_sptab.release();
     a->d_ksum.release();
-    a->d_site.release();
-    a->d_shist.release();
-    a->d_squant.release();
-    a->d_scomp.release();
-    a->d_smix.release();
-    a->d_sadd.release();
-    a->d_smap.release();
-    a->d_sgath.release();
+    a->site.release();
     park_pool_buffer(a->device, 0, a->ws);
     park_pool_buffer(a->device, 1, a->lpe);
     park_pool_buffer(a->device, 2, a->bits);
@@ -744,645 +728,9 @@ int dyn_aligner_kmer_summary_reset(dyn_aligner* a) {
   return DYN_OK;
 }
 
-// ---- the per-site level summary (site_summary_kernels.hpp) -------------------------------------------------------------------
-namespace {
-// both setters of the table: capacity == 0 is the dense table of num_sites rows, capacity > 0 the sparse one of capacity rows
-// behind a map (site_map.hpp) whose ids stay below num_sites
-int set_site_table(dyn_aligner* a, uint64_t num_sites, uint64_t capacity, const char* who) {
-  if (!a) return DYN_ERR_INVALID_ARGUMENT;
-  const bool sparse = capacity > 0;
-  auto fail = [&](const std::string& msg) {
-    std::lock_guard<std::mutex> lk(a->err_mu);
-    a->last_error = std::string(who) + ": " + msg;
-    return DYN_ERR_INVALID_ARGUMENT;
-  };
-  if (a->ntk) return fail("modes ntk / resquiggle have no align(calc_probabilities = 1) job to summarise");
-  if (num_sites >= (uint64_t)DYN_SITE_NONE) return fail("num_sites " + std::to_string(num_sites) + " is not below DYN_SITE_NONE (4294967295)");
-  if (capacity >= (uint64_t)DYN_SITE_NONE) return fail("capacity " + std::to_string(capacity) + " is not below 4294967295");
-  Pipeline* pipe = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(a->mu);
-    if (int rc = need_device(a)) return rc;
-    if (num_sites == 0) {  // off: the table stays for the fetch
-      a->opt.site_summary = false;
-      return DYN_OK;
-    }
-    if (num_sites == a->num_sites && capacity == a->site_capacity && a->d_site.p) {
-      a->opt.site_summary = true;
-      return DYN_OK;
-    }
-    // off before the lock is dropped: a ticket another thread submits while this call drains takes no part in the summary, so
-    // none can add to the table that is about to be freed
-    a->opt.site_summary = false;
-    pipe = a->pipe.get();
-  }
-  // another size or mode: the jobs in flight hold the old table's address (snapshot at their submission) -- they finish first
-  if (pipe) pipe->drain();
-  std::lock_guard<std::mutex> lk(a->mu);
-  if (int rc = session_quiesce(a)) return rc;  // (hipFree waits for the whole device: no resident wave may be waiting for tickets)
-  HIP_TRY(a, hipStreamSynchronize(a->stream));
-  HIP_TRY(a, hipStreamSynchronize(a->s_out));
-  a->opt.site_summary = false;
-  a->d_site.release();
-  a->d_smap.release();
-  a->d_sgath.release();
-  a->num_sites = 0;
-  a->site_capacity = 0;
-  // the histograms were the old table's: released and off, the caller sets them again (dyn_aligner_set_site_histogram)
-  a->opt.site_histogram = false;
-  a->d_shist.release();
-  a->sh_bins = 0;
-  const uint64_t rows = sparse ? capacity : num_sites;
-  const uint64_t key_bytes = sparse ? capacity * sizeof(uint32_t) : 0;
-  const uint64_t table_bytes = ((uint64_t)dynk::SS_FIELDS * rows + (uint64_t)dynk::SS_TOTALS + (sparse ? (uint64_t)dynk::SM_STATS : 0)) * sizeof(uint64_t);
-  const uint64_t bytes = table_bytes + key_bytes;
-  const std::string what = sparse ? "the sparse table of " + std::to_string(capacity) + " rows (" + std::to_string(bytes) + " bytes)"
-                                  : "the table of " + std::to_string(num_sites) + " sites (" + std::to_string(bytes) + " bytes)";
-  if (a->mem_budget && bytes > a->mem_budget) {
-    std::lock_guard<std::mutex> elk(a->err_mu);
-    a->last_error = std::string(who) + ": " + what + " does not fit dyn_aligner_set_mem_budget's " + std::to_string(a->mem_budget) + " bytes";
-    return DYN_ERR_OUT_OF_MEMORY;
-  }
-  hipError_t e = a->d_site.ensure(table_bytes);
-  if (e == hipSuccess && sparse) e = a->d_smap.ensure(key_bytes);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    a->d_site.release();
-    a->d_smap.release();
-    std::lock_guard<std::mutex> elk(a->err_mu);
-    a->last_error = std::string(who) + ": no device memory for " + what + ": " + hipGetErrorString(e);
-    return e == hipErrorOutOfMemory ? DYN_ERR_OUT_OF_MEMORY : DYN_ERR_DEVICE;
-  }
-  HIP_TRY(a, hipMemsetAsync(a->d_site.p, 0, table_bytes, a->s_get));
-  if (sparse) HIP_TRY(a, hipMemsetAsync(a->d_smap.p, 0xFF, key_bytes, a->s_get));
-  HIP_TRY(a, hipStreamSynchronize(a->s_get));
-  a->num_sites = num_sites;
-  a->site_capacity = capacity;
-  a->opt.site_summary = true;
-  return DYN_OK;
-}
-}  // namespace
-
-int dyn_aligner_set_site_summary(dyn_aligner* a, uint64_t num_sites) { return set_site_table(a, num_sites, 0, "dyn_aligner_set_site_summary"); }
-
-int dyn_aligner_set_site_summary_sparse(dyn_aligner* a, uint64_t num_sites, uint64_t capacity) {
-  if (!a) return DYN_ERR_INVALID_ARGUMENT;
-  if (num_sites && !capacity) {
-    std::lock_guard<std::mutex> lk(a->err_mu);
-    a->last_error = "dyn_aligner_set_site_summary_sparse: capacity 0 is no table (dyn_aligner_set_site_summary sets a dense one)";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  return set_site_table(a, num_sites, num_sites ? capacity : 0, "dyn_aligner_set_site_summary_sparse");
-}
-
-int dyn_aligner_stage_site_ids(dyn_aligner* a, const uint32_t* site_ids, uint64_t count) {
-  if (!a || (count && !site_ids)) return DYN_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> lk(a->mu);
-  a->staged_sites = site_ids;
-  a->staged_count = count;
-  a->sites_staged = true;
-  return DYN_OK;
-}
-
-namespace {
-// every kernel that adds to the table runs on the compute stream (one launch per batch) or on the copy-out stream (tickets of a
-// resident session): the table of the jobs that have completed is behind both
-int site_summary_quiet(dyn_aligner* a, const char* who) {
-  if (int rc = need_device(a)) return rc;
-  if (!a->d_site.p) {
-    std::lock_guard<std::mutex> lk(a->err_mu);
-    a->last_error = std::string(who) + ": dyn_aligner_set_site_summary(a, num_sites > 0) was never called on this handle";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  HIP_TRY(a, hipStreamSynchronize(a->stream));
-  HIP_TRY(a, hipStreamSynchronize(a->s_out));
-  return DYN_OK;
-}
-
-// the table's words: the cells, the totals and, behind a sparse table, the map's statistics
-uint64_t site_table_words(const dyn_aligner* a) {
-  return (uint64_t)dynk::SS_FIELDS * site_rows(a) + (uint64_t)dynk::SS_TOTALS + (a->site_capacity ? (uint64_t)dynk::SM_STATS : 0);
-}
-
-// A window of a sparse table as the dense calls see one. The ids [lo, lo + cnt) are gathered on s_get into slot `slot` of the
-// `slots` (1, or 2 where a call reads two windows at once) of the scratch d_sgath, each sized for `most` sites of what the call
-// asks for -- every gather of one call asks for the same: *table points at [cnt][7] u64, *hist at [cnt][bins + 2 + 16] uint32.
-// The scratch grows on first use and counts against the memory budget (mem_budget_left). The window kernels and copies behind
-// the gather on s_get read the scratch.
-int site_gather_window(dyn_aligner* a, uint64_t lo, uint64_t cnt, uint64_t most, int slot, int slots, const uint64_t** table,
-                       const unsigned int** hist) {
-  const uint64_t F = (uint64_t)dynk::SS_FIELDS, H = (hist && a->d_shist.p && a->sh_bins) ? site_hist_width(a->sh_bins) : 0;
-  const uint64_t table_bytes = table ? most * F * sizeof(uint64_t) : 0;
-  const uint64_t slot_bytes = (table_bytes + most * H * sizeof(uint32_t) + 7) / 8 * 8;  // (rounded up: every slot starts 8-byte aligned)
-  HIP_TRY(a, a->d_sgath.ensure((uint64_t)slots * slot_bytes));
-  char* base = a->d_sgath.as<char>() + (uint64_t)slot * slot_bytes;
-  dynk::SiteGather sg{};
-  sg.keys = a->d_smap.as<uint32_t>();
-  sg.capacity = (uint32_t)a->site_capacity;
-  sg.acc = a->d_site.as<unsigned long long>();
-  sg.lo = (uint32_t)lo;
-  sg.count = (uint32_t)cnt;
-  if (table) {
-    sg.out_acc = reinterpret_cast<unsigned long long*>(base);
-    *table = reinterpret_cast<const uint64_t*>(base);
-  }
-  if (hist) {
-    sg.hist = a->d_shist.as<unsigned int>();
-    sg.width = (uint32_t)H;
-    sg.out_hist = reinterpret_cast<unsigned int*>(base + table_bytes);
-    *hist = sg.out_hist;
-  }
-  dynk::launch_site_gather(sg, a->s_get);
-  HIP_TRY(a, hipGetLastError());
-  return DYN_OK;
-}
-
-// the conditions of the calls that read the map: a sparse table, completed jobs
-int site_map_quiet(dyn_aligner* a, const char* who) {
-  if (int rc = site_summary_quiet(a, who)) return rc;
-  if (!a->site_capacity || !a->d_smap.p) {
-    std::lock_guard<std::mutex> lk(a->err_mu);
-    a->last_error = std::string(who) + ": the per-site table of this handle is dense (dyn_aligner_set_site_summary_sparse sets a sparse one)";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  return DYN_OK;
-}
-}  // namespace
-
-int dyn_aligner_site_map_stats(dyn_aligner* a, uint64_t out[4]) {
-  if (!a || !out) return DYN_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> lk(a->mu);
-  if (int rc = site_map_quiet(a, "dyn_aligner_site_map_stats")) return rc;
-  out[0] = a->site_capacity;
-  const uint64_t* stats = a->d_site.as<uint64_t>() + (uint64_t)dynk::SS_FIELDS * a->site_capacity + (uint64_t)dynk::SS_TOTALS;
-  HIP_TRY(a, copy_out(a, out + 1, stats, (uint64_t)dynk::SM_STATS * sizeof(uint64_t)));
-  return DYN_OK;
-}
-
-int dyn_aligner_site_map_keys(dyn_aligner* a, uint64_t bucket_lo, uint64_t bucket_hi, uint32_t* keys) {
-  if (!a || (bucket_lo < bucket_hi && !keys)) return DYN_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> lk(a->mu);
-  if (int rc = site_map_quiet(a, "dyn_aligner_site_map_keys")) return rc;
-  if (bucket_lo > bucket_hi || bucket_hi > a->site_capacity) {
-    std::lock_guard<std::mutex> elk(a->err_mu);
-    a->last_error = "dyn_aligner_site_map_keys: [" + std::to_string(bucket_lo) + ", " + std::to_string(bucket_hi) + ") is not a range of the map's " +
-                    std::to_string(a->site_capacity) + " buckets";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  if (bucket_lo == bucket_hi) return DYN_OK;
-  HIP_TRY(a, copy_out(a, keys, a->d_smap.as<uint32_t>() + bucket_lo, (bucket_hi - bucket_lo) * sizeof(uint32_t)));
-  return DYN_OK;
-}
-
-int dyn_aligner_site_map_windows(dyn_aligner* a, int shift, uint64_t* windows, uint64_t cap, uint64_t* count) {
-  if (!a || !count || (cap && !windows)) return DYN_ERR_INVALID_ARGUMENT;
-  const char* who = "dyn_aligner_site_map_windows";
-  auto fail = [&](const std::string& msg) {
-    std::lock_guard<std::mutex> lk(a->err_mu);
-    a->last_error = std::string(who) + ": " + msg;
-    return DYN_ERR_INVALID_ARGUMENT;
-  };
-  if (shift < 0 || shift > 31) return fail("shift " + std::to_string(shift) + " is not 0 .. 31");
-  std::lock_guard<std::mutex> lk(a->mu);
-  if (int rc = site_map_quiet(a, who)) return rc;
-  const uint64_t n_win = ((a->num_sites - 1) >> shift) + 1;  // (a table has num_sites >= 1)
-  if (n_win > (1ull << 22))
-    return fail("shift " + std::to_string(shift) + " cuts the " + std::to_string(a->num_sites) + " ids into " + std::to_string(n_win) +
-                " windows, more than 4194304");
-  const uint64_t words = (n_win + 31) / 32;
-  HIP_TRY(a, a->d_squant.ensure(words * sizeof(uint32_t)));  // (the quantiles' staging: every window call runs under a->mu on s_get)
-  HIP_TRY(a, hipMemsetAsync(a->d_squant.p, 0, words * sizeof(uint32_t), a->s_get));
-  dynk::SiteWindows sw{a->d_smap.as<uint32_t>(), (uint32_t)a->site_capacity, shift, a->d_squant.as<unsigned int>()};
-  dynk::launch_site_map_windows(sw, a->s_get);
-  HIP_TRY(a, hipGetLastError());
-  std::vector<uint32_t> h(words);
-  HIP_TRY(a, copy_out(a, h.data(), sw.bitmap, words * sizeof(uint32_t)));
-  uint64_t n = 0;
-  for (uint64_t w = 0; w < n_win; ++w)
-    if (h[w >> 5] >> (w & 31) & 1u) {
-      if (n < cap) windows[n] = w;
-      ++n;
-    }
-  *count = n;
-  if (n > cap) return fail(std::to_string(n) + " windows are occupied, the caller's array holds " + std::to_string(cap));
-  return DYN_OK;
-}
-
-int dyn_aligner_site_summary_fetch(dyn_aligner* a, uint64_t lo, uint64_t hi, uint64_t* n_rows, uint64_t* n_samples,
-                                   uint64_t* dwell_sq, uint64_t* m1_lo, uint64_t* m1_hi, uint64_t* m2_lo, uint64_t* m2_hi,
-                                   uint64_t totals[5]) {
-  if (!a || !totals) return DYN_ERR_INVALID_ARGUMENT;
-  uint64_t* cols[7] = {n_rows, n_samples, dwell_sq, m1_lo, m1_hi, m2_lo, m2_hi};
-  if (lo < hi)
-    for (uint64_t* c : cols)
-      if (!c) return DYN_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> lk(a->mu);
-  if (int rc = site_summary_quiet(a, "dyn_aligner_site_summary_fetch")) return rc;
-  if (lo > hi || hi > a->num_sites) {
-    std::lock_guard<std::mutex> elk(a->err_mu);
-    a->last_error = "dyn_aligner_site_summary_fetch: [" + std::to_string(lo) + ", " + std::to_string(hi) + ") is not a range of the table's " +
-                    std::to_string(a->num_sites) + " sites";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  const uint64_t F = (uint64_t)dynk::SS_FIELDS, step = 1ull << 20;  // 56 MB of staging at a time
-  std::vector<uint64_t> h(F * std::min(step, hi - lo) + 1);
-  const uint64_t* table = a->d_site.as<uint64_t>();
-  for (uint64_t s0 = lo; s0 < hi; s0 += step) {
-    const uint64_t cnt = std::min(step, hi - s0);
-    const uint64_t* src = table + F * s0;
-    if (a->site_capacity)  // sparse: the window's ids looked up, their cells gathered (an absent id: zeros)
-      if (int rc = site_gather_window(a, s0, cnt, std::min(step, hi - lo), 0, 1, &src, nullptr)) return rc;
-    HIP_TRY(a, copy_out(a, h.data(), src, F * cnt * sizeof(uint64_t)));
-    for (uint64_t c = 0; c < cnt; ++c)
-      for (uint64_t f = 0; f < F; ++f) cols[f][s0 - lo + c] = h[F * c + f];
-  }
-  HIP_TRY(a, copy_out(a, totals, table + F * site_rows(a), (uint64_t)dynk::SS_TOTALS * sizeof(uint64_t)));
-  return DYN_OK;
-}
-
-int dyn_aligner_site_summary_reset(dyn_aligner* a) {
-  if (!a) return DYN_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> lk(a->mu);
-  if (int rc = site_summary_quiet(a, "dyn_aligner_site_summary_reset")) return rc;
-  HIP_TRY(a, hipMemsetAsync(a->d_site.p, 0, site_table_words(a) * sizeof(uint64_t), a->s_get));  // (the map's statistics with it)
-  if (a->site_capacity) HIP_TRY(a, hipMemsetAsync(a->d_smap.p, 0xFF, a->site_capacity * sizeof(uint32_t), a->s_get));  // no key left
-  if (a->d_shist.p && a->sh_bins)
-    HIP_TRY(a, hipMemsetAsync(a->d_shist.p, 0, site_rows(a) * site_hist_width(a->sh_bins) * sizeof(uint32_t), a->s_get));
-  HIP_TRY(a, hipStreamSynchronize(a->s_get));
-  return DYN_OK;
-}
-
-// ---- the per-site histograms beside the table (site_summary_kernels.hpp) -------------------------------------------------------
-int dyn_aligner_set_site_histogram(dyn_aligner* a, int bins, double lo, double hi) {
-  if (!a) return DYN_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    std::lock_guard<std::mutex> lk(a->err_mu);
-    a->last_error = "dyn_aligner_set_site_histogram: " + msg;
-    return DYN_ERR_INVALID_ARGUMENT;
-  };
-  if (bins == 0) {  // off: the counters stay for the fetch
-    std::lock_guard<std::mutex> lk(a->mu);
-    a->opt.site_histogram = false;
-    return DYN_OK;
-  }
-  // refused before the device is looked at: the same text on a handle without one
-  if (bins < 2 || bins > dynk::SH_BINS_MAX) return fail("bins " + std::to_string(bins) + " is not 0 (off) or 2 .. 254");
-  if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) return fail("lo and hi must be finite with lo < hi");
-  const double inv_w = (double)bins / (hi - lo);  // one IEEE subtraction, one IEEE division
-  if (!std::isfinite(inv_w) || !(inv_w > 0.0)) return fail("hi - lo must be a finite width with a finite bins / (hi - lo)");
-  Pipeline* pipe = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(a->mu);
-    if (!a->d_site.p) return fail("dyn_aligner_set_site_summary(a, num_sites > 0) was never called on this handle");
-    if (int rc = need_device(a)) return rc;
-    if (a->d_shist.p && a->sh_bins == (uint32_t)bins && a->sh_lo == lo && a->sh_hi == hi) {
-      a->opt.site_histogram = true;
-      return DYN_OK;
-    }
-    // off before the lock is dropped, as the table's setter does it: no ticket submitted while this call drains counts
-    a->opt.site_histogram = false;
-    pipe = a->pipe.get();
-  }
-  // other parameters: the jobs in flight hold the old counters' address and parameters -- they finish first
-  if (pipe) pipe->drain();
-  std::lock_guard<std::mutex> lk(a->mu);
-  if (int rc = session_quiesce(a)) return rc;
-  HIP_TRY(a, hipStreamSynchronize(a->stream));
-  HIP_TRY(a, hipStreamSynchronize(a->s_out));
-  a->opt.site_histogram = false;
-  a->d_shist.release();
-  a->sh_bins = 0;
-  if (!a->d_site.p || !a->num_sites) return fail("dyn_aligner_set_site_summary(a, num_sites > 0) was never called on this handle");
-  const uint64_t bytes = site_rows(a) * site_hist_width((uint32_t)bins) * sizeof(uint32_t);  // (a sparse table: capacity rows)
-  if (a->mem_budget && bytes > mem_budget_left(a)) {
-    std::lock_guard<std::mutex> elk(a->err_mu);
-    a->last_error = "dyn_aligner_set_site_histogram: the histograms of " + std::to_string(site_rows(a)) + (a->site_capacity ? " rows (" : " sites (") + std::to_string(bytes) +
-                    " bytes) do not fit dyn_aligner_set_mem_budget's " + std::to_string(a->mem_budget) + " bytes";
-    return DYN_ERR_OUT_OF_MEMORY;
-  }
-  const hipError_t e = a->d_shist.ensure(bytes);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    std::lock_guard<std::mutex> elk(a->err_mu);
-    a->last_error = "dyn_aligner_set_site_histogram: no device memory for the histograms of " + std::to_string(site_rows(a)) + (a->site_capacity ? " rows (" : " sites (") +
-                    std::to_string(bytes) + " bytes): " + hipGetErrorString(e);
-    return e == hipErrorOutOfMemory ? DYN_ERR_OUT_OF_MEMORY : DYN_ERR_DEVICE;
-  }
-  HIP_TRY(a, hipMemsetAsync(a->d_shist.p, 0, bytes, a->s_get));
-  HIP_TRY(a, hipStreamSynchronize(a->s_get));
-  a->sh_bins = (uint32_t)bins;
-  a->sh_lo = lo;
-  a->sh_hi = hi;
-  a->sh_inv_w = inv_w;
-  a->opt.site_histogram = true;
-  return DYN_OK;
-}
-
-namespace {
-// the conditions of site_summary_quiet, and histograms to read; [lo, hi) must be a range of the table
-int site_histogram_quiet(dyn_aligner* a, const char* who, uint64_t lo, uint64_t hi) {
-  if (int rc = site_summary_quiet(a, who)) return rc;
-  std::string msg;
-  if (!a->d_shist.p || !a->sh_bins) msg = ": dyn_aligner_set_site_histogram(a, bins > 0, lo, hi) was never called on this handle";
-  else if (lo > hi || hi > a->num_sites)
-    msg = ": [" + std::to_string(lo) + ", " + std::to_string(hi) + ") is not a range of the table's " + std::to_string(a->num_sites) + " sites";
-  if (msg.empty()) return DYN_OK;
-  std::lock_guard<std::mutex> elk(a->err_mu);
-  a->last_error = who + msg;
-  return DYN_ERR_INVALID_ARGUMENT;
-}
-}  // namespace
-
-int dyn_aligner_site_histogram_fetch(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi, uint32_t* level, uint32_t* dwell) {
-  if (!a || (site_lo < site_hi && (!level || !dwell))) return DYN_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> lk(a->mu);
-  if (int rc = site_histogram_quiet(a, "dyn_aligner_site_histogram_fetch", site_lo, site_hi)) return rc;
-  const uint64_t B = (uint64_t)a->sh_bins + 2, D = (uint64_t)dynk::SH_DWELL_BINS, H = B + D, step = 1ull << 20;
-  std::vector<uint32_t> h(H * std::min(step, site_hi - site_lo) + 1);
-  const uint32_t* hist = a->d_shist.as<uint32_t>();
-  for (uint64_t s0 = site_lo; s0 < site_hi; s0 += step) {
-    const uint64_t cnt = std::min(step, site_hi - s0);
-    const unsigned int* src = hist + H * s0;
-    if (a->site_capacity)
-      if (int rc = site_gather_window(a, s0, cnt, std::min(step, site_hi - site_lo), 0, 1, nullptr, &src)) return rc;
-    HIP_TRY(a, copy_out(a, h.data(), src, H * cnt * sizeof(uint32_t)));
-    for (uint64_t c = 0; c < cnt; ++c) {
-      std::memcpy(level + B * (s0 - site_lo + c), h.data() + H * c, B * sizeof(uint32_t));
-      std::memcpy(dwell + D * (s0 - site_lo + c), h.data() + H * c + B, D * sizeof(uint32_t));
-    }
-  }
-  return DYN_OK;
-}
-
-int dyn_aligner_site_quantiles(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi, const double* probs, int n_probs, uint32_t* n,
-                               uint32_t* rank, uint32_t* bin, uint32_t* below, uint32_t* in_bin) {
-  if (!a) return DYN_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    std::lock_guard<std::mutex> lk(a->err_mu);
-    a->last_error = "dyn_aligner_site_quantiles: " + msg;
-    return DYN_ERR_INVALID_ARGUMENT;
-  };
-  if (!probs || n_probs < 1 || n_probs > dynk::SQ_PROBS_MAX) return fail("n_probs " + std::to_string(n_probs) + " is not 1 .. 8");
-  for (int q = 0; q < n_probs; ++q)
-    if (!(probs[q] >= 0.0 && probs[q] <= 1.0)) return fail("probs[" + std::to_string(q) + "] is not in [0, 1]");
-  if (site_lo < site_hi && (!n || !rank || !bin || !below || !in_bin)) return DYN_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> lk(a->mu);
-  if (int rc = site_histogram_quiet(a, "dyn_aligner_site_quantiles", site_lo, site_hi)) return rc;
-  if (site_lo == site_hi) return DYN_OK;
-  const uint64_t H = site_hist_width(a->sh_bins), P = (uint64_t)n_probs, step = 1ull << 20;
-  const uint64_t most = std::min(step, site_hi - site_lo);
-  HIP_TRY(a, a->d_squant.ensure((1 + 4 * P) * most * sizeof(uint32_t)));
-  std::vector<uint32_t> h((1 + 4 * P) * most);
-  dynk::SiteQuantiles sq{};
-  sq.bins = a->sh_bins;
-  sq.n_probs = n_probs;
-  for (int q = 0; q < n_probs; ++q) sq.probs[q] = probs[q];
-  sq.out = a->d_squant.as<uint32_t>();
-  for (uint64_t s0 = site_lo; s0 < site_hi; s0 += step) {
-    const uint64_t cnt = std::min(step, site_hi - s0);
-    sq.hist = a->d_shist.as<unsigned int>() + H * s0;
-    if (a->site_capacity)
-      if (int rc = site_gather_window(a, s0, cnt, most, 0, 1, nullptr, &sq.hist)) return rc;
-    sq.count = (uint32_t)cnt;
-    dynk::launch_site_quantiles(sq, a->s_get);
-    HIP_TRY(a, hipGetLastError());
-    HIP_TRY(a, copy_out(a, h.data(), sq.out, (1 + 4 * P) * cnt * sizeof(uint32_t)));  // (behind the kernel on the same stream)
-    const uint64_t o = s0 - site_lo;
-    std::memcpy(n + o, h.data(), cnt * sizeof(uint32_t));
-    uint32_t* cols[4] = {rank, bin, below, in_bin};
-    for (int f = 0; f < 4; ++f) std::memcpy(cols[f] + o * P, h.data() + cnt + (uint64_t)f * cnt * P, cnt * P * sizeof(uint32_t));
-  }
-  return DYN_OK;
-}
-
-// ---- two samples in one table: the exact add of host columns and the comparison of two windows (site_compare_kernels.hpp) ----
-int dyn_aligner_site_summary_add(dyn_aligner* a, uint64_t lo, uint64_t hi, const uint64_t* n_rows, const uint64_t* n_samples,
-                                 const uint64_t* dwell_sq, const uint64_t* m1_lo, const uint64_t* m1_hi, const uint64_t* m2_lo,
-                                 const uint64_t* m2_hi, const uint64_t totals[5], const uint32_t* level, const uint32_t* dwell) {
-  if (!a) return DYN_ERR_INVALID_ARGUMENT;
-  const char* who = "dyn_aligner_site_summary_add";
-  auto fail = [&](const std::string& msg) {
-    std::lock_guard<std::mutex> lk(a->err_mu);
-    a->last_error = std::string(who) + ": " + msg;
-    return DYN_ERR_INVALID_ARGUMENT;
-  };
-  // refused before the device is looked at: the same text on a handle without one
-  if ((level == nullptr) != (dwell == nullptr)) return fail("level and dwell counters are given together or not at all");
-  const uint64_t* cols[7] = {n_rows, n_samples, dwell_sq, m1_lo, m1_hi, m2_lo, m2_hi};
-  if (lo < hi)
-    for (const uint64_t* c : cols)
-      if (!c) return DYN_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> lk(a->mu);
-  if (level) {
-    if (int rc = site_histogram_quiet(a, who, lo, hi)) return rc;
-  } else {
-    if (int rc = site_summary_quiet(a, who)) return rc;
-    if (lo > hi || hi > a->num_sites)
-      return fail("[" + std::to_string(lo) + ", " + std::to_string(hi) + ") is not a range of the table's " + std::to_string(a->num_sites) + " sites");
-  }
-  if (lo == hi) return DYN_OK;  // an empty window touches nothing, the totals included
-  const uint64_t F = (uint64_t)dynk::SS_FIELDS, step = 1ull << 20;
-  const uint64_t B = (uint64_t)a->sh_bins + 2, D = (uint64_t)dynk::SH_DWELL_BINS, H = level ? B + D : 0;
-  const uint64_t most = std::min(step, hi - lo);
-  HIP_TRY(a, a->d_sadd.ensure(most * (F * sizeof(uint64_t) + H * sizeof(uint32_t))));
-  std::vector<uint64_t> hc(F * most);
-  std::vector<uint32_t> hh(H * most);
-  dynk::SiteAdd sa{};
-  sa.totals = a->d_site.as<unsigned long long>() + F * site_rows(a);
-  sa.cols = a->d_sadd.as<unsigned long long>();
-  sa.width = (uint32_t)H;
-  // sparse: the same staging, scattered into the rows of the window's ids (site_map_kernels.hpp)
-  dynk::SiteScatter ssc{};
-  uint64_t dropped_before = 0;
-  if (a->site_capacity) {
-    ssc.keys = a->d_smap.as<uint32_t>();
-    ssc.capacity = (uint32_t)a->site_capacity;
-    ssc.stats = sa.totals + dynk::SS_TOTALS;
-    ssc.acc = a->d_site.as<unsigned long long>();
-    ssc.totals = sa.totals;
-    ssc.cols = sa.cols;
-    ssc.width = (uint32_t)H;
-    HIP_TRY(a, copy_out(a, &dropped_before, ssc.stats + dynk::SM_SITES_DROPPED, sizeof(uint64_t)));
-  }
-  for (uint64_t s0 = lo; s0 < hi; s0 += step) {
-    const uint64_t cnt = std::min(step, hi - s0), o = s0 - lo;
-    for (uint64_t c = 0; c < cnt; ++c)
-      for (uint64_t f = 0; f < F; ++f) hc[F * c + f] = cols[f][o + c];
-    HIP_TRY(a, hipMemcpyAsync(a->d_sadd.p, hc.data(), F * cnt * sizeof(uint64_t), hipMemcpyHostToDevice, a->s_get));
-    sa.acc = a->d_site.as<unsigned long long>() + F * s0;
-    sa.count = (uint32_t)cnt;
-    if (level) {
-      for (uint64_t c = 0; c < cnt; ++c) {
-        std::memcpy(hh.data() + H * c, level + B * (o + c), B * sizeof(uint32_t));
-        std::memcpy(hh.data() + H * c + B, dwell + D * (o + c), D * sizeof(uint32_t));
-      }
-      unsigned int* staged = reinterpret_cast<unsigned int*>(a->d_sadd.as<unsigned long long>() + F * cnt);
-      HIP_TRY(a, hipMemcpyAsync(staged, hh.data(), H * cnt * sizeof(uint32_t), hipMemcpyHostToDevice, a->s_get));
-      sa.hist = a->d_shist.as<unsigned int>() + H * s0;
-      sa.counters = staged;
-    }
-    sa.add_totals = (totals && s0 == lo) ? 1 : 0;  // the caller's totals once, with the first window
-    for (int f = 0; f < dynk::SS_TOTALS; ++f) sa.totals_in[f] = sa.add_totals ? totals[f] : 0ull;
-    if (a->site_capacity) {
-      ssc.hist = level ? a->d_shist.as<unsigned int>() : nullptr;
-      ssc.counters = sa.counters;
-      ssc.lo = (uint32_t)s0;
-      ssc.count = (uint32_t)cnt;
-      ssc.add_totals = sa.add_totals;
-      for (int f = 0; f < dynk::SS_TOTALS; ++f) ssc.totals_in[f] = sa.totals_in[f];
-      dynk::launch_site_scatter_add(ssc, a->s_get);
-    } else {
-      dynk::launch_site_add(sa, a->s_get);
-    }
-    HIP_TRY(a, hipGetLastError());
-    HIP_TRY(a, hipStreamSynchronize(a->s_get));  // (the host vectors are filled again for the next window)
-  }
-  if (a->site_capacity) {
-    uint64_t dropped = 0;
-    HIP_TRY(a, copy_out(a, &dropped, ssc.stats + dynk::SM_SITES_DROPPED, sizeof(uint64_t)));
-    if (dropped > dropped_before) {
-      std::lock_guard<std::mutex> elk(a->err_mu);
-      a->last_error = std::string(who) + ": " + std::to_string(dropped - dropped_before) + " sites found no bucket in the map of " +
-                      std::to_string(a->site_capacity) + " rows and were dropped; the other sites were added";
-      return DYN_ERR_OUT_OF_MEMORY;
-    }
-  }
-  return DYN_OK;
-}
-
-int dyn_aligner_site_compare(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi, uint64_t other_lo, uint32_t* n_a, uint32_t* n_b,
-                             uint64_t* level_num, uint32_t* level_at, int32_t* level_side, uint64_t* dwell_num, uint32_t* dwell_at,
-                             int32_t* dwell_side) {
-  if (!a) return DYN_ERR_INVALID_ARGUMENT;
-  if (site_lo < site_hi && (!n_a || !n_b || !level_num || !level_at || !level_side || !dwell_num || !dwell_at || !dwell_side))
-    return DYN_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> lk(a->mu);
-  if (int rc = site_histogram_quiet(a, "dyn_aligner_site_compare", site_lo, site_hi)) return rc;
-  const uint64_t n = site_hi - site_lo;
-  if (other_lo > a->num_sites || n > a->num_sites - other_lo) {
-    std::lock_guard<std::mutex> elk(a->err_mu);
-    a->last_error = "dyn_aligner_site_compare: the other window [" + std::to_string(other_lo) + ", " + std::to_string(other_lo) + " + " +
-                    std::to_string(n) + ") does not end inside the table's " + std::to_string(a->num_sites) + " sites";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  if (n == 0) return DYN_OK;
-  const uint64_t H = site_hist_width(a->sh_bins), step = 1ull << 20, most = std::min(step, n);
-  HIP_TRY(a, a->d_scomp.ensure((uint64_t)dynk::SC_PAIR_BYTES * most));
-  std::vector<uint64_t> h((uint64_t)dynk::SC_PAIR_BYTES / 8 * most);
-  dynk::SiteCompare sc{};
-  sc.bins = a->sh_bins;
-  sc.out = a->d_scomp.as<unsigned long long>();
-  for (uint64_t o = 0; o < n; o += step) {
-    const uint64_t cnt = std::min(step, n - o);
-    sc.hist_a = a->d_shist.as<unsigned int>() + H * (site_lo + o);
-    sc.hist_b = a->d_shist.as<unsigned int>() + H * (other_lo + o);
-    if (a->site_capacity) {  // sparse: either window gathered into a scratch of its own
-      if (int rc = site_gather_window(a, site_lo + o, cnt, most, 0, 2, nullptr, &sc.hist_a)) return rc;
-      if (int rc = site_gather_window(a, other_lo + o, cnt, most, 1, 2, nullptr, &sc.hist_b)) return rc;
-    }
-    sc.count = (uint32_t)cnt;
-    dynk::launch_site_compare(sc, a->s_get);
-    HIP_TRY(a, hipGetLastError());
-    HIP_TRY(a, copy_out(a, h.data(), sc.out, (uint64_t)dynk::SC_PAIR_BYTES * cnt));  // (behind the kernel on the same stream)
-    std::memcpy(level_num + o, h.data(), cnt * sizeof(uint64_t));
-    std::memcpy(dwell_num + o, h.data() + cnt, cnt * sizeof(uint64_t));
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(h.data() + 2 * cnt);
-    std::memcpy(n_a + o, w, cnt * sizeof(uint32_t));
-    std::memcpy(n_b + o, w + cnt, cnt * sizeof(uint32_t));
-    std::memcpy(level_at + o, w + 2 * cnt, cnt * sizeof(uint32_t));
-    std::memcpy(dwell_at + o, w + 3 * cnt, cnt * sizeof(uint32_t));
-    std::memcpy(level_side + o, w + 4 * cnt, cnt * sizeof(int32_t));
-    std::memcpy(dwell_side + o, w + 5 * cnt, cnt * sizeof(int32_t));
-  }
-  return DYN_OK;
-}
-
-// ---- a two-component mixture per site pair, fitted on the device from the level counters (site_mixture_kernels.hpp) ----
-int dyn_aligner_site_mixture(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi, uint64_t other_lo, uint32_t max_iters, double tol,
-                             uint32_t min_n, double* pi1, double* mu0, double* mu1, double* var0, double* var1, double* r_a, double* r_b,
-                             uint32_t* n_a, uint32_t* n_b, uint32_t* out_a, uint32_t* out_b, uint32_t* iters, uint32_t* status) {
-  if (!a) return DYN_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    std::lock_guard<std::mutex> lk(a->err_mu);
-    a->last_error = "dyn_aligner_site_mixture: " + msg;
-    return DYN_ERR_INVALID_ARGUMENT;
-  };
-  // refused before the device is looked at: the same text on a handle without one
-  if (max_iters < 1 || max_iters > dynk::SM_MAX_ITERS) return fail("max_iters " + std::to_string(max_iters) + " is not 1 .. 1024");
-  if (!std::isfinite(tol) || !(tol >= 0.0)) return fail("tol must be finite and >= 0");
-  if (min_n < 2) return fail("min_n " + std::to_string(min_n) + " is not >= 2");
-  double* dcols[7] = {pi1, mu0, mu1, var0, var1, r_a, r_b};
-  uint32_t* ucols[6] = {n_a, n_b, out_a, out_b, iters, status};
-  if (site_lo < site_hi) {
-    for (double* c : dcols)
-      if (!c) return DYN_ERR_INVALID_ARGUMENT;
-    for (uint32_t* c : ucols)
-      if (!c) return DYN_ERR_INVALID_ARGUMENT;
-  }
-  std::lock_guard<std::mutex> lk(a->mu);
-  if (int rc = site_histogram_quiet(a, "dyn_aligner_site_mixture", site_lo, site_hi)) return rc;
-  const uint64_t n = site_hi - site_lo;
-  const bool one = other_lo == UINT64_MAX;
-  if (!one && (other_lo > a->num_sites || n > a->num_sites - other_lo))
-    return fail("the other window [" + std::to_string(other_lo) + ", " + std::to_string(other_lo) + " + " + std::to_string(n) +
-                ") does not end inside the table's " + std::to_string(a->num_sites) + " sites");
-  if (n == 0) return DYN_OK;
-  const uint64_t H = site_hist_width(a->sh_bins), step = 1ull << 20, most = std::min(step, n);
-  HIP_TRY(a, a->d_smix.ensure((uint64_t)dynk::SM_PAIR_BYTES * most));
-  std::vector<double> h((uint64_t)dynk::SM_PAIR_BYTES / 8 * most);
-  dynk::SiteMixture sm{};
-  sm.exp_tab = reinterpret_cast<const uint64_t*>(a->d_sptab.as<dynmath::SoftplusNode>() + dynmath::SP_NODES + dynmath::EXP128_NODES);
-  sm.bins = a->sh_bins;
-  sm.max_iters = max_iters;
-  sm.min_n = min_n;
-  sm.lo = a->sh_lo;
-  sm.w = (a->sh_hi - a->sh_lo) / (double)a->sh_bins;  // one IEEE subtraction, one IEEE division
-  sm.vfloor = (sm.w * sm.w) / 12.0;
-  sm.tol_mu = tol * sm.w;
-  sm.tol_pi = tol;
-  sm.out = a->d_smix.as<double>();
-  for (uint64_t o = 0; o < n; o += step) {
-    const uint64_t cnt = std::min(step, n - o);
-    sm.hist_a = a->d_shist.as<unsigned int>() + H * (site_lo + o);
-    sm.hist_b = one ? nullptr : a->d_shist.as<unsigned int>() + H * (other_lo + o);
-    if (a->site_capacity) {
-      if (int rc = site_gather_window(a, site_lo + o, cnt, most, 0, one ? 1 : 2, nullptr, &sm.hist_a)) return rc;
-      if (!one)
-        if (int rc = site_gather_window(a, other_lo + o, cnt, most, 1, 2, nullptr, &sm.hist_b)) return rc;
-    }
-    sm.count = (uint32_t)cnt;
-    dynk::launch_site_mixture(sm, a->s_get);
-    HIP_TRY(a, hipGetLastError());
-    HIP_TRY(a, copy_out(a, h.data(), sm.out, (uint64_t)dynk::SM_PAIR_BYTES * cnt));  // (behind the kernel on the same stream)
-    for (int f = 0; f < 7; ++f) std::memcpy(dcols[f] + o, h.data() + (uint64_t)f * cnt, cnt * sizeof(double));
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(h.data() + 7 * cnt);
-    for (int f = 0; f < 6; ++f) std::memcpy(ucols[f] + o, w + (uint64_t)f * cnt, cnt * sizeof(uint32_t));
-  }
-  return DYN_OK;
-}
-
 }  // extern "C"
 
 namespace dyneng {
-
-int take_staged_sites(dyn_aligner* a, const char* api, uint64_t n_reads, const uint64_t* seq_offsets, const uint32_t** ids) {
-  *ids = nullptr;
-  if (!a->sites_staged) return DYN_OK;
-  const uint32_t* p = a->staged_sites;
-  const uint64_t count = a->staged_count;
-  a->sites_staged = false;
-  a->staged_sites = nullptr;
-  a->staged_count = 0;
-  const uint64_t span = (n_reads && seq_offsets) ? seq_offsets[n_reads] - seq_offsets[0] : 0;
-  if (count != span) {
-    std::lock_guard<std::mutex> lk(a->err_mu);
-    a->last_error = std::string(api) + ": dyn_aligner_stage_site_ids staged " + std::to_string(count) + " ids, the batch's sequences hold " +
-                    std::to_string(span) + " characters";
-    return DYN_ERR_INVALID_ARGUMENT;
-  }
-  *ids = p;
-  return DYN_OK;
-}
 
 // Which reads need the reference's arithmetic bit for bit, and for how many forward rows (dyn_aligner_set_strict, mode 1).
 // A STRUCTURAL TIE: two neighbouring lattice columns with the same emission parameters (equal k-mers -- the polyA pad
@@ -1506,7 +854,7 @@ int create_impl(dyn_aligner* a, uint64_t n_reads, const double* signals, const R
                 dyn_batch** out) {
   if (!a) return DYN_ERR_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lk(a->mu);
-  // the ids dyn_aligner_stage_site_ids left are this call's, whatever becomes of it
+  // the staged site ids (take_staged_sites) are this call's, whatever becomes of it
   const uint32_t* site_ids = nullptr;
   const int src = take_staged_sites(a, "dyn_batch_create", n_reads, seq_offsets, &site_ids);
   if (!out) return DYN_ERR_INVALID_ARGUMENT;
@@ -1932,10 +1280,10 @@ int run_job_sync(dyn_batch* b, DynJob job, bool guided_train = false) {
     int rc = need_device(a);
     if (rc != DYN_OK) return rc;
     b->want = want;
-    b->ss_table = a->d_site.as<unsigned long long>();  // the table as it stands at this submission
-    b->ss_num_sites = a->num_sites;
-    b->ss_hist = site_hist_now(a);
-    b->ss_map = site_map_now(a);
+    b->ss_table = a->site.table.as<unsigned long long>();  // the table as it stands at this submission
+    b->ss_num_sites = a->site.num_sites;
+    b->ss_hist = a->site.hist_now(a->opt.site_histogram);
+    b->ss_map = a->site.map_now();
     rc = enqueue_job(b, job);
     if (rc != DYN_OK) {
       (void)hipStreamSynchronize(a->stream);

@@ -183,6 +183,90 @@ struct SiteMap {
   uint64_t capacity = 0;
 };
 
+// ---- the per-site table of a handle and everything kept beside it (dyn_aligner::site; the calls: site_table.cpp) ---------------
+struct SiteTable {
+  // the table (site_summary_kernels.hpp): [7 rows() + 5] u64, allocated and zeroed by dyn_aligner_set_site_summary(a, num_sites > 0),
+  // kept until the setter names another size; a job snapshots pointer and size at its submission
+  DevBuf table;
+  uint64_t num_sites = 0;
+  // the sparse mode (dyn_aligner_set_site_summary_sparse, site_map.hpp): capacity > 0, keys the [capacity] uint32 keys of the map,
+  // table [7 capacity + 5 + 3] u64 (the map's three statistics behind the totals), the histograms capacity rows; num_sites stays
+  // the bound of the ids. gather: the dense scratch the window calls gather into (one or two windows of what the call reads)
+  DevBuf keys;
+  uint64_t capacity = 0;
+  DevBuf gather;
+  // the per-site histograms beside the table: [rows()][bins + 2 + 16] u32, allocated and zeroed by dyn_aligner_set_site_histogram(a,
+  // bins > 0, lo, hi), kept (bins = 0 only stops the counting) until that setter names other parameters or the table another size
+  DevBuf hist;
+  uint32_t bins = 0;
+  double lo = 0.0, hi = 0.0, inv_w = 0.0;
+  // one window's staging per call, each a buffer of its own: growing a buffer of the handle's is hipFree + hipMalloc, and hipFree
+  // waits for the whole device -- calls of different sizes must not free one another's staging under an open resident session
+  DevBuf quant;  // dyn_aligner_site_quantiles: one window's output
+  DevBuf comp;   // dyn_aligner_site_compare: one window's output
+  DevBuf mix;    // dyn_aligner_site_mixture: one window's output
+  DevBuf add;    // dyn_aligner_site_summary_add: one window's columns and counters
+  // dyn_aligner_stage_site_ids: the caller's ids for the NEXT batch-creating call on this handle (consumed by it, whatever its outcome)
+  const uint32_t* staged_ids = nullptr;
+  uint64_t staged_count = 0;
+  bool staged = false;
+
+  bool sparse() const { return capacity != 0; }
+  // rows of the table and of its histograms: the capacity of a sparse table, the id space of a dense one
+  uint64_t rows() const { return capacity ? capacity : num_sites; }
+  // the table's words: the cells, the totals and, behind a sparse table, the map's statistics
+  static uint64_t words(uint64_t rows, bool sparse) {
+    return (uint64_t)dynk::SS_FIELDS * rows + (uint64_t)dynk::SS_TOTALS + (sparse ? (uint64_t)dynk::SM_STATS : 0);
+  }
+  uint64_t words() const { return words(rows(), sparse()); }
+  unsigned long long* totals() const { return table.as<unsigned long long>() + (uint64_t)dynk::SS_FIELDS * rows(); }
+  // uint32 counters per site: under, the level bins, over, the dwell bins
+  static uint64_t hist_width(uint32_t bins) { return (uint64_t)bins + 2 + (uint64_t)dynk::SH_DWELL_BINS; }
+  uint64_t hist_width() const { return hist_width(bins); }
+  bool has_hist() const { return hist.p && bins; }
+  // the histograms a job submitted now counts into (nothing while the switch is off)
+  SiteHist hist_now(bool on) const {
+    SiteHist h;
+    if (on && has_hist()) {
+      h.p = hist.as<unsigned int>();
+      h.bins = bins;
+      h.lo = lo;
+      h.inv_w = inv_w;
+    }
+    return h;
+  }
+  SiteMap map_now() const {
+    SiteMap m;
+    if (capacity && keys.p) {
+      m.keys = keys.as<uint32_t>();
+      m.capacity = capacity;
+    }
+    return m;
+  }
+  // what dyn_aligner_set_mem_budget counts against the table: itself, its histograms, a sparse table's map and gather scratch
+  uint64_t held_bytes() const { return table.bytes + hist.bytes + keys.bytes + gather.bytes; }
+  // the occupancy bitmap of dyn_aligner_site_map_windows lives in the quantiles' staging: every window call runs under the
+  // handle's lock on s_get, so no two of them use it at once
+  DevBuf& window_bitmap() { return quant; }
+  void release_hist() {
+    hist.release();
+    bins = 0;
+  }
+  // the table, its map and scratch and its histograms (the setter, before another size; the staging stays)
+  void release_table() {
+    table.release();
+    keys.release();
+    gather.release();
+    num_sites = 0;
+    capacity = 0;
+    release_hist();
+  }
+  void release() {
+    release_table();
+    for (DevBuf* d : {&quant, &comp, &mix, &add}) d->release();
+  }
+};
+
 // ---- the per-segment outputs a job may add to its rows (one fetcher, one out-struct and one CSV flag each) ---------------------
 enum Output { OUT_LEVELS, OUT_SCORES, OUT_BORDERS, OUT_INTERVALS, OUT_SOFT, OUT_SAMPLES, OUT_COUNT };
 struct OutputBuf {
@@ -230,29 +314,7 @@ struct dyn_aligner {
   dyneng::DevBuf band_arena;
   dyneng::DevBuf d_ksum;      // [6 num_kmers + 4] u64: the per-k-mer accumulator and its totals (kmer_summary_kernels.hpp),
                               // allocated and zeroed by the first dyn_aligner_set_kmer_summary(a, 1)
-  // the per-site table (site_summary_kernels.hpp): [7 num_sites + 5] u64, allocated and zeroed by dyn_aligner_set_site_summary(a,
-  // num_sites > 0), kept until the setter names another size; a job snapshots pointer and size at its submission
-  dyneng::DevBuf d_site;
-  uint64_t num_sites = 0;
-  // the sparse mode (dyn_aligner_set_site_summary_sparse, site_map.hpp): site_capacity > 0, d_smap the [site_capacity] uint32 keys,
-  // d_site [7 site_capacity + 5 + 3] u64 (the map's three statistics behind the totals), the histograms site_capacity rows; num_sites
-  // stays the bound of the ids. d_sgath: the dense scratch the window calls gather into (one or two windows of what the call reads)
-  dyneng::DevBuf d_smap;
-  uint64_t site_capacity = 0;
-  dyneng::DevBuf d_sgath;
-  // the per-site histograms beside it: [num_sites][sh_bins + 2 + 16] u32, allocated and zeroed by dyn_aligner_set_site_histogram(a,
-  // bins > 0, lo, hi), kept (bins = 0 only stops the counting) until that setter names other parameters or the table another size
-  dyneng::DevBuf d_shist;
-  uint32_t sh_bins = 0;
-  double sh_lo = 0.0, sh_hi = 0.0, sh_inv_w = 0.0;
-  dyneng::DevBuf d_squant;    // staging of dyn_aligner_site_quantiles: one window's output
-  dyneng::DevBuf d_scomp;     // staging of dyn_aligner_site_compare: one window's output
-  dyneng::DevBuf d_smix;      // staging of dyn_aligner_site_mixture: one window's output
-  dyneng::DevBuf d_sadd;      // staging of dyn_aligner_site_summary_add: one window's columns and counters
-  // dyn_aligner_stage_site_ids: the caller's ids for the NEXT batch-creating call on this handle (consumed by it, whatever its outcome)
-  const uint32_t* staged_sites = nullptr;
-  uint64_t staged_count = 0;
-  bool sites_staged = false;
+  dyneng::SiteTable site;  // the per-site table, its map, histograms, staging and staged ids (site_table.cpp)
   bool ntk = false;     // created with mode "resquiggle" / "ntk"
   std::string last_error;
   // grow-only lattice workspace pool, reused across batches (only ever touched by work on `stream`,
@@ -284,34 +346,11 @@ struct dyn_aligner {
 };
 
 namespace dyneng {
-// what dyn_aligner_set_mem_budget leaves once the per-site table, its histograms, a sparse table's map and gather scratch are taken off (0: no budget was set)
+// what dyn_aligner_set_mem_budget leaves once the per-site table and what it holds beside it are taken off (0: no budget was set)
 inline uint64_t mem_budget_left(const dyn_aligner* a) {
   if (!a->mem_budget) return 0;
-  const uint64_t taken = a->d_site.bytes + a->d_shist.bytes + a->d_smap.bytes + a->d_sgath.bytes;
+  const uint64_t taken = a->site.held_bytes();
   return a->mem_budget > taken ? a->mem_budget - taken : 1;
-}
-// rows of the per-site table and of its histograms: the capacity of a sparse table, the id space of a dense one
-inline uint64_t site_rows(const dyn_aligner* a) { return a->site_capacity ? a->site_capacity : a->num_sites; }
-inline SiteMap site_map_now(const dyn_aligner* a) {
-  SiteMap m;
-  if (a->site_capacity && a->d_smap.p) {
-    m.keys = a->d_smap.as<uint32_t>();
-    m.capacity = a->site_capacity;
-  }
-  return m;
-}
-// uint32 counters per site: under, the level bins, over, the dwell bins
-inline uint64_t site_hist_width(uint32_t bins) { return (uint64_t)bins + 2 + (uint64_t)dynk::SH_DWELL_BINS; }
-// the histograms a job submitted now counts into (nothing while the switch is off)
-inline SiteHist site_hist_now(const dyn_aligner* a) {
-  SiteHist h;
-  if (a->opt.site_histogram && a->d_shist.p && a->sh_bins) {
-    h.p = a->d_shist.as<unsigned int>();
-    h.bins = a->sh_bins;
-    h.lo = a->sh_lo;
-    h.inv_w = a->sh_inv_w;
-  }
-  return h;
 }
 // what a session is launched with (session_choose, session.cpp)
 struct SessionGeom {
@@ -507,7 +546,7 @@ struct BandArgs;  // band_reads.hpp
 
 namespace dyneng {
 
-// ---- shared between the engine's translation units (dynamont_mi.cpp, launch.cpp, session.cpp, async_engine.cpp) ----
+// ---- shared between the engine's translation units (dynamont_mi.cpp, site_table.cpp, launch.cpp, session.cpp, async_engine.cpp) ----
 int need_device(dyn_aligner* a);
 // CU-masked streams (every CU enabled: a hardware queue of their own) are parked per device and reused, never destroyed
 // (dynamont_mi.cpp); nullptr when the runtime provides none. The session stream and a dyn_comm's stream come from here.

@@ -1,5 +1,5 @@
 // engine_internal.hpp -- what the translation units of the host engine share beyond engine.hpp (dynamont_mi.cpp: the C ABI,
-// buffers, classic launches; session.cpp: the resident read queue's host side).
+// buffers, classic launches; site_table.cpp: the per-site table's calls; session.cpp: the resident read queue's host side).
 #pragma once
 
 #include "engine.hpp"
@@ -24,6 +24,15 @@
   } while (0)
 
 namespace dyneng {
+
+// A getter's copy off the device: on the handle's own non-blocking stream and waited for there. The data is complete when a
+// getter may be called (the synchronous job calls return after the compute stream has passed the batch, dyn_batch_wait after
+// the copy-out stream has); a null-stream hipMemcpy would ALSO wait for the resident session kernel that later tickets keep
+// open (the session stream is not a non-blocking one) and serialise a caller's stream of batches.
+inline hipError_t copy_out(dyn_aligner* a, void* dst, const void* src, size_t bytes) {
+  hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, a->s_get);
+  return e != hipSuccess ? e : hipStreamSynchronize(a->s_get);
+}
 
 // Lattice pages hold 2^log_r rows, log_r >= 8 (and more where the longest read would not fit a wave's page table).
 // DYN_PAGE_LOG_ROWS=2..8 lowers that floor (read at every launch; tests: the sweeps' row cursors then cross a page every few

@@ -147,6 +147,11 @@ def test_the_kmer_summary_still_includes_the_shared_helpers():
     assert "site_summary.hip" in N.SOURCES and "exact_sum_kernels.hpp" in N.HEADERS and "site_summary_kernels.hpp" in N.HEADERS
 
 
+def test_the_table_host_unit_is_built():
+    """the host half of every per-site call lives in a translation unit of its own"""
+    assert "site_table.cpp" in N.SOURCES
+
+
 @pytest.fixture(scope="module")
 def batch():
     return ssc.build_batch()
