@@ -57,6 +57,8 @@
 #include "sample_kernels.hpp"
 #include "dp_math_strict.hpp"
 
+#include <utility>
+
 namespace dynk {
 
 using dynmath::NEG_INF;
@@ -387,9 +389,11 @@ __device__ void band_read(const ReadDesc& rd, const BandArgs& a, double* __restr
 }  // namespace
 
 // one workgroup takes reads off a queue until it is empty; its lattice arena (jobs 1 and 2) holds one read at a time.
-// BORDER: the border-confidence phase (border_kernels.hpp) behind every read, as a kernel of its own: the launches without the
-// phase are the ones they have always been. The read's lattice is still in the arena when band_read returns (its closing
-// barrier has made the state and segrow that thread 0 wrote visible to the workgroup).
+// PHASES: the lattice phases (lattice_phase.hpp) behind every read, diagonal window and align with probabilities only. The
+// read's lattice is still in the arena when band_read returns (its closing barrier has made the lattice, the state and the
+// segrow that thread 0 wrote visible to the workgroup), and the barrier at the head of the loop keeps the arena until every
+// thread is done with it. Border confidence: all threads; posterior samples: the first wave, a lane per sample; credible
+// intervals and soft levels: a thread per column walks that column's row interval.
 // REFINE (LiveGuideWindow, align with probabilities): the workgroup that holds a read refines its guide, behind every band_read
 // what k_guide_refine (guided_band.hip) does for the read between two launches of the round scheme, rule for rule: the
 // alignment is counted; a failed read is finished; the called path g'[s] = pathn[s + 1] (0 before the first border) is compared
@@ -397,8 +401,11 @@ __device__ void band_read(const ReadDesc& rd, const BandArgs& a, double* __restr
 // read is aligned again in the same arena. Only then does the workgroup take the next read: a launch lasts as long as its
 // reads' alignments, not as refine_rounds times its longest read. With BandArgs::active the launch takes the listed descriptors
 // only (the guide rescue); a self-guided ticket passes none.
-template <class Window, int THREADS, int CPT, bool CALC, bool TRAIN, bool BORDER, bool REFINE = false>
+template <class Window, int THREADS, int CPT, bool CALC, bool TRAIN, int PHASES, bool REFINE = false>
 __global__ __launch_bounds__(THREADS) void k_band_reads(const BandArgs a) {
+  static_assert(PHASES == 0 || (Window::DIAGONAL && CALC && !TRAIN && !REFINE), "lattice phases: diagonal window, align with probabilities");
+  static_assert((PHASES & ~LATTICE_PHASE_BITS) == 0 && (!(PHASES & (JOB_INTERVAL | JOB_SOFT)) || PHASES == JOB_INTERVAL || PHASES == JOB_SOFT),
+                "the credible intervals and the soft levels run alone");
   extern __shared__ __attribute__((aligned(16))) char g_lds[];
   char* lds = Window::lds(g_lds);
   const int stride = Window::row_stride(a);
@@ -414,9 +421,12 @@ __global__ __launch_bounds__(THREADS) void k_band_reads(const BandArgs a) {
     const int k = s_ctl[0];
     // a refinement round (launch_guide_refine) or the guide rescue (launch_rescue_select) hands over the list of the reads to
     // align and its length on the device; an empty list ends the workgroup at this first queue read
-    const bool listed = a.active != nullptr;
+    // LISTS: launch_band_reads refuses a list beside the samples, the intervals and the soft levels, and those kernels hold no
+    // branch for it
+    constexpr bool LISTS = (PHASES & (JOB_SAMPLE | JOB_INTERVAL | JOB_SOFT)) == 0;
+    const bool listed = LISTS && a.active != nullptr;
     if (k >= (listed ? (int)*a.n_active : a.n_reads)) break;
-    const ReadDesc rd = a.descs[listed ? a.active[k] : (uint32_t)k];
+    const ReadDesc rd = LISTS ? a.descs[listed ? a.active[k] : (uint32_t)k] : a.descs[k];
     const size_t cells = (size_t)rd.T * (size_t)(2 * Window(rd, a).bw + 3);
     double* bE = reinterpret_cast<double*>(arena);
     double* bM = bE + cells;
@@ -454,117 +464,18 @@ __global__ __launch_bounds__(THREADS) void k_band_reads(const BandArgs a) {
     } else {
       band_read<Window, THREADS, CPT, CALC, TRAIN>(rd, a, bE, bM, lp, bit, s_rows, stride, s_exp, s_ctl + 1);
     }
-    if constexpr (BORDER) {
+    if constexpr (PHASES != 0) {
       if (__hip_atomic_load(&a.st[rd.read].status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) {
-        const BorderCellWide cell{BorderBand{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio}, lp};
-        border_confidence_read(cell, rd, a.tb.segrow, a.border_p, a.border_window_p, a.border_window, (int)threadIdx.x, THREADS);
+        const BorderBand band{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio};
+        const BorderCellWide lpm{band, lp};
+        [[maybe_unused]] const SampleLpeWide lpe{band, lp};
+        const int tid = (int)threadIdx.x;
+        if constexpr ((PHASES & JOB_BORDER) != 0) border_confidence_read(lpm, rd, a.tb.segrow, a.border_p, a.border_window_p, a.border_window, tid, THREADS);
+        if constexpr ((PHASES & JOB_SAMPLE) != 0)
+          if (tid < 64) posterior_samples_read(lpm, lpe, rd, a.sample, tid);
+        if constexpr ((PHASES & JOB_INTERVAL) != 0) border_interval_read_columns(lpm, band, rd, a.tb.segrow, a.interval, tid, THREADS);
+        if constexpr ((PHASES & JOB_SOFT) != 0) soft_levels_read_columns(lpm, lpe, band, rd, a.sig + rd.sig_off, a.soft, tid, THREADS);
       }
-    }
-  }
-}
-
-// k_band_reads<DiagonalWindow, 256, 16, true, false, BORDER> with the posterior-sampling phase (sample_kernels.hpp) behind every
-// read (and behind the border phase), as a kernel of its own: the launches without it keep their names and their code. The
-// workgroup's first wave walks the samples, one lane each; band_read's closing barrier has made the lattice and the state
-// visible to it, and the barrier at the head of the loop keeps the arena until the walk is done.
-template <bool BORDER>
-__global__ __launch_bounds__(256) void k_band_reads_sample(const BandArgs a) {
-  constexpr int THREADS = 256, CPT = 16;
-  using Window = DiagonalWindow;
-  extern __shared__ __attribute__((aligned(16))) char g_lds[];
-  char* lds = Window::lds(g_lds);
-  const int stride = Window::row_stride(a);
-  uint64_t* s_exp = reinterpret_cast<uint64_t*>(lds);
-  double* s_rows = reinterpret_cast<double*>(lds + dynmath::STRICT_EXP_WORDS * 8);
-  int* s_ctl = reinterpret_cast<int*>(s_rows + 4 * stride);  // [0] next read, [1] s_bad
-  for (int i = threadIdx.x; i < dynmath::STRICT_EXP_WORDS; i += THREADS) s_exp[i] = a.exp_tab[i];
-  char* arena = a.arena + (size_t)blockIdx.x * a.arena_bytes;
-  for (;;) {
-    __syncthreads();
-    if (threadIdx.x == 0) s_ctl[0] = (int)atomicAdd(a.head, 1u);
-    __syncthreads();
-    const int k = s_ctl[0];
-    if (k >= a.n_reads) break;
-    const ReadDesc rd = a.descs[k];
-    const size_t cells = (size_t)rd.T * (size_t)(2 * Window(rd, a).bw + 3);
-    double* bE = reinterpret_cast<double*>(arena);
-    double* bM = bE + cells;
-    float* lp = reinterpret_cast<float*>(bM + cells);
-    uint8_t* bit = reinterpret_cast<uint8_t*>(lp + 2 * cells);
-    band_read<Window, THREADS, CPT, true, false>(rd, a, bE, bM, lp, bit, s_rows, stride, s_exp, s_ctl + 1);
-    if (__hip_atomic_load(&a.st[rd.read].status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) {
-      const BorderBand band{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio};
-      const BorderCellWide cell{band, lp};
-      if constexpr (BORDER)
-        border_confidence_read(cell, rd, a.tb.segrow, a.border_p, a.border_window_p, a.border_window, (int)threadIdx.x, THREADS);
-      if (threadIdx.x < 64) posterior_samples_read(cell, SampleLpeWide{band, lp}, rd, a.sample, (int)threadIdx.x);
-    }
-  }
-}
-
-// k_band_reads<DiagonalWindow, 256, 16, true, false> with the credible-interval phase (interval_kernels.hpp) behind every read, as
-// a kernel of its own for the same reason. One thread per column walks that column's row interval; band_read's closing barrier
-// has made the lattice, the state and segrow visible, and the barrier at the head of the loop keeps the arena until all are done.
-__global__ __launch_bounds__(256) void k_band_reads_interval(const BandArgs a) {
-  constexpr int THREADS = 256, CPT = 16;
-  using Window = DiagonalWindow;
-  extern __shared__ __attribute__((aligned(16))) char g_lds[];
-  char* lds = Window::lds(g_lds);
-  const int stride = Window::row_stride(a);
-  uint64_t* s_exp = reinterpret_cast<uint64_t*>(lds);
-  double* s_rows = reinterpret_cast<double*>(lds + dynmath::STRICT_EXP_WORDS * 8);
-  int* s_ctl = reinterpret_cast<int*>(s_rows + 4 * stride);  // [0] next read, [1] s_bad
-  for (int i = threadIdx.x; i < dynmath::STRICT_EXP_WORDS; i += THREADS) s_exp[i] = a.exp_tab[i];
-  char* arena = a.arena + (size_t)blockIdx.x * a.arena_bytes;
-  for (;;) {
-    __syncthreads();
-    if (threadIdx.x == 0) s_ctl[0] = (int)atomicAdd(a.head, 1u);
-    __syncthreads();
-    const int k = s_ctl[0];
-    if (k >= a.n_reads) break;
-    const ReadDesc rd = a.descs[k];
-    const size_t cells = (size_t)rd.T * (size_t)(2 * Window(rd, a).bw + 3);
-    double* bE = reinterpret_cast<double*>(arena);
-    double* bM = bE + cells;
-    float* lp = reinterpret_cast<float*>(bM + cells);
-    uint8_t* bit = reinterpret_cast<uint8_t*>(lp + 2 * cells);
-    band_read<Window, THREADS, CPT, true, false>(rd, a, bE, bM, lp, bit, s_rows, stride, s_exp, s_ctl + 1);
-    if (__hip_atomic_load(&a.st[rd.read].status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) {
-      const BorderBand band{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio};
-      border_interval_read_columns(BorderCellWide{band, lp}, band, rd, a.tb.segrow, a.interval, (int)threadIdx.x, THREADS);
-    }
-  }
-}
-
-// ... and with the soft-level phase (soft_level_kernels.hpp) behind every read, a kernel of its own likewise: one thread per
-// column walks that column's row interval through BorderCellWide / SampleLpeWide
-__global__ __launch_bounds__(256) void k_band_reads_soft(const BandArgs a) {
-  constexpr int THREADS = 256, CPT = 16;
-  using Window = DiagonalWindow;
-  extern __shared__ __attribute__((aligned(16))) char g_lds[];
-  char* lds = Window::lds(g_lds);
-  const int stride = Window::row_stride(a);
-  uint64_t* s_exp = reinterpret_cast<uint64_t*>(lds);
-  double* s_rows = reinterpret_cast<double*>(lds + dynmath::STRICT_EXP_WORDS * 8);
-  int* s_ctl = reinterpret_cast<int*>(s_rows + 4 * stride);  // [0] next read, [1] s_bad
-  for (int i = threadIdx.x; i < dynmath::STRICT_EXP_WORDS; i += THREADS) s_exp[i] = a.exp_tab[i];
-  char* arena = a.arena + (size_t)blockIdx.x * a.arena_bytes;
-  for (;;) {
-    __syncthreads();
-    if (threadIdx.x == 0) s_ctl[0] = (int)atomicAdd(a.head, 1u);
-    __syncthreads();
-    const int k = s_ctl[0];
-    if (k >= a.n_reads) break;
-    const ReadDesc rd = a.descs[k];
-    const size_t cells = (size_t)rd.T * (size_t)(2 * Window(rd, a).bw + 3);
-    double* bE = reinterpret_cast<double*>(arena);
-    double* bM = bE + cells;
-    float* lp = reinterpret_cast<float*>(bM + cells);
-    uint8_t* bit = reinterpret_cast<uint8_t*>(lp + 2 * cells);
-    band_read<Window, THREADS, CPT, true, false>(rd, a, bE, bM, lp, bit, s_rows, stride, s_exp, s_ctl + 1);
-    if (__hip_atomic_load(&a.st[rd.read].status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) {
-      const BorderBand band{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio};
-      soft_levels_read_columns(BorderCellWide{band, lp}, SampleLpeWide{band, lp}, band, rd, a.sig + rd.sig_off, a.soft, (int)threadIdx.x, THREADS);
     }
   }
 }
@@ -593,13 +504,13 @@ size_t lds_bytes(int bw, int job) {  // the train job keeps the two forward rows
   return (size_t)dynmath::STRICT_EXP_WORDS * 8 + (job == 2 ? 2 : 4) * (size_t)guided_row_stride(2 * bw + 3) * 8 + 16;
 }
 
-template <class Window, int THREADS, int CPT, bool CALC, bool TRAIN, bool BORDER = false, bool REFINE = false>
+template <class Window, int THREADS, int CPT, bool CALC, bool TRAIN, int PHASES = 0, bool REFINE = false>
 hipError_t launch_kernel(const BandArgs& a, int n_groups, size_t lds, hipStream_t s) {
   if (lds > 48 * 1024) {  // (a wide guided window: the request exceeds the default dynamic-LDS limit; diagonal launches ask for none)
-    const void* fn = reinterpret_cast<const void*>(&k_band_reads<Window, THREADS, CPT, CALC, TRAIN, BORDER, REFINE>);
+    const void* fn = reinterpret_cast<const void*>(&k_band_reads<Window, THREADS, CPT, CALC, TRAIN, PHASES, REFINE>);
     if (const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
   }
-  hipLaunchKernelGGL((k_band_reads<Window, THREADS, CPT, CALC, TRAIN, BORDER, REFINE>), dim3(n_groups), dim3(THREADS), lds, s, a);
+  hipLaunchKernelGGL((k_band_reads<Window, THREADS, CPT, CALC, TRAIN, PHASES, REFINE>), dim3(n_groups), dim3(THREADS), lds, s, a);
   return hipGetLastError();
 }
 template <class Window, int THREADS, int CPT>
@@ -607,6 +518,13 @@ hipError_t launch_shape(int job, const BandArgs& a, int n_groups, size_t lds, hi
   if (job == 2) return launch_kernel<Window, THREADS, CPT, false, true>(a, n_groups, lds, s);
   if (job == 1) return launch_kernel<Window, THREADS, CPT, true, false>(a, n_groups, lds, s);
   return launch_kernel<Window, THREADS, CPT, false, false>(a, n_groups, lds, s);
+}
+// the diagonal launch of align with probabilities: one kernel for every set of lattice phases on lattice_phase.hpp's list
+template <size_t... I>
+hipError_t launch_diagonal_phases(int phases, const BandArgs& a, int n_groups, hipStream_t s, std::index_sequence<I...>) {
+  hipError_t e = hipErrorInvalidValue;
+  ((phases == LATTICE_PHASE_SETS[I] ? void(e = launch_kernel<DiagonalWindow, 256, 16, true, false, LATTICE_PHASE_SETS[I]>(a, n_groups, 0, s)) : void()), ...);
+  return e;
 }
 }  // namespace
 
@@ -624,38 +542,27 @@ hipError_t launch_band_reads(int job, const BandArgs& a, int n_groups, hipStream
   if (job == 2 && !(a.tr.col_w && a.tr.col_s1 && a.tr.col_s2 && a.tr.trans)) return hipErrorInvalidValue;
   if (job != 0 && !a.arena) return hipErrorInvalidValue;
   if (a.border_window > 0 && (a.guide || job != 1 || !a.border_p || !a.border_window_p)) return hipErrorInvalidValue;
-  const bool soft = job == 1 && a.soft.tag == SOFT_TAG;  // dyn_aligner_set_soft_levels
+  const int phases = lattice_phases(job == 1, a.sample.count, a.interval.tail, a.border_window);
+  const bool soft = phases == JOB_SOFT;  // dyn_aligner_set_soft_levels
   if (soft && (a.guide || a.active || a.border_window > 0 || !a.soft.weight || a.soft.zero != 0)) return hipErrorInvalidValue;
   if (!soft && job == 1 && a.sample.count != 0 && (a.sample.count < 0 || a.guide || a.active || job != 1 || a.sample.count > PS_MAX_SAMPLES || !a.sample.start))
     return hipErrorInvalidValue;
-  const bool interval = job == 1 && a.sample.count == 0 && a.interval.tail > 0.0;  // dyn_aligner_set_border_interval
+  const bool interval = phases == JOB_INTERVAL;  // dyn_aligner_set_border_interval
   if (interval && (a.guide || a.active || a.border_window > 0 || !a.interval.mean || !(a.interval.tail < 0.5))) return hipErrorInvalidValue;
   const bool refine = a.refine_rounds > 1;  // every read refined inside this launch
   if (refine && (!a.guide || job != 1 || a.border_window > 0 || !a.rounds || !a.converged)) return hipErrorInvalidValue;
   if (const hipError_t e = hipMemsetAsync(a.head, 0, 4, s)) return e;
   if (!a.guide) {
-    if (job == 1 && a.sample.count > 0) {  // (static LDS, as every diagonal launch)
-      if (a.border_window > 0) hipLaunchKernelGGL(k_band_reads_sample<true>, dim3(n_groups), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL(k_band_reads_sample<false>, dim3(n_groups), dim3(256), 0, s, a);
-      return hipGetLastError();
-    }
-    if (interval) {
-      hipLaunchKernelGGL(k_band_reads_interval, dim3(n_groups), dim3(256), 0, s, a);
-      return hipGetLastError();
-    }
-    if (soft) {
-      hipLaunchKernelGGL(k_band_reads_soft, dim3(n_groups), dim3(256), 0, s, a);
-      return hipGetLastError();
-    }
-    if (a.border_window > 0) return launch_kernel<DiagonalWindow, 256, 16, true, false, true>(a, n_groups, 0, s);
-    return launch_shape<DiagonalWindow, 256, 16>(job, a, n_groups, 0, s);  // (static LDS)
+    // (static LDS, as every diagonal launch)
+    if (job == 1) return launch_diagonal_phases(phases, a, n_groups, s, std::make_index_sequence<N_LATTICE_PHASE_SETS>{});
+    return launch_shape<DiagonalWindow, 256, 16>(job, a, n_groups, 0, s);
   }
   const size_t lds = lds_bytes(a.bw, job);
   const Shape& sh = shape_of(a.bw);
   if (refine) {
-    if (sh.cpt == 1) return launch_kernel<LiveGuideWindow, 64, 1, true, false, false, true>(a, n_groups, lds, s);
-    if (sh.threads == 64) return launch_kernel<LiveGuideWindow, 64, 4, true, false, false, true>(a, n_groups, lds, s);
-    return launch_kernel<LiveGuideWindow, 256, 16, true, false, false, true>(a, n_groups, lds, s);
+    if (sh.cpt == 1) return launch_kernel<LiveGuideWindow, 64, 1, true, false, 0, true>(a, n_groups, lds, s);
+    if (sh.threads == 64) return launch_kernel<LiveGuideWindow, 64, 4, true, false, 0, true>(a, n_groups, lds, s);
+    return launch_kernel<LiveGuideWindow, 256, 16, true, false, 0, true>(a, n_groups, lds, s);
   }
   if (sh.cpt == 1) return launch_shape<GuideWindow, 64, 1>(job, a, n_groups, lds, s);
   if (sh.threads == 64) return launch_shape<GuideWindow, 64, 4>(job, a, n_groups, lds, s);

@@ -74,7 +74,7 @@ int band_groups_per_cu(bool guided, int bw, int job);
 // (BandArgs::refine_rounds > 1) without a guide, with a job other than 1, with a border window or without rounds / converged,
 // for posterior samples (BandArgs::sample.count > 0) with a guide, a job other than 1 or without their arrays, and for credible
 // intervals (BandArgs::interval.tail > 0) with a guide, a border window or without their buffer, and likewise for the soft levels
-// (BandArgs::soft.tag == SOFT_TAG).
+// (BandArgs::soft.tag == SOFT_TAG). Which lattice phases a launch carries: lattice_phases() (lattice_phase.hpp), as for the read queue.
 hipError_t launch_band_reads(int job, const BandArgs& a, int n_groups, hipStream_t s);
 
 }  // namespace dynk

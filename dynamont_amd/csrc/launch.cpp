@@ -855,7 +855,7 @@ int run_pass(dyn_batch* b, const LaunchPlan& L, dynk::QueueArgs& q, int pass) {
   if (last && b->out[OUT_SOFT].ready) q.soft = dynk::SoftOut{b->out[OUT_SOFT].d.as<double>(), b->capacity, 0, dynk::SOFT_TAG};
   if (last && (b->out[OUT_BORDERS].ready || b->out[OUT_INTERVALS].ready || b->out[OUT_SOFT].ready)) q.lpe_dense = 1;
   if (pass == 0) HIP_TRY(a, hipEventRecord(ev[0], a->stream));
-  dynk::launch_read_queue(L.qjob, L.n_strict != 0, q, a->n_cus, a->stream);
+  HIP_TRY(a, dynk::launch_read_queue(L.qjob, L.n_strict != 0, q, a->n_cus, a->stream));
   if (last) HIP_TRY(a, hipEventRecord(ev[1], a->stream));
   // the statistics leave the control words before the next pass's or batch's k_pool_init resets them (same stream)
   HIP_TRY(a, hipMemcpyAsync(b->h_stats.as<uint32_t>() + (size_t)pass * dynk::QUEUE_CTL_WORDS, L.pool.ctl, dynk::QUEUE_CTL_WORDS * 4,

@@ -47,6 +47,8 @@
 #include "lpe_liveness.hpp"
 
 #include <algorithm>
+#include <array>
+#include <utility>
 
 #include "band_runs.hpp"
 #include "border_kernels.hpp"
@@ -1265,6 +1267,10 @@ __device__ __forceinline__ bool pages_take(const PagePool& pool, const WaveCtx& 
   return ok;
 }
 
+// the table both read queues stage into LDS: the softplus nodes + 2^(i/128) as plain doubles (exp_table128_vec) + glibc's table
+// of the strict exp (dp_math_strict.hpp)
+constexpr int TAB_NODES = SP_NODES + dynmath::EXP128_NODES + dynmath::STRICT_EXP_WORDS / 2;
+
 // ---- one read's whole pipeline (the body both read queues share) -----------------------------------------
 // What a read touches beside the lattice pool: the arrays of its batch (classic launch: the launch's; resident queue: its
 // ticket's) and the model's transition constants.
@@ -1375,6 +1381,33 @@ __device__ __forceinline__ void run_read(const ReadDesc& rd, const WaveCtx& w, c
   ws.cyc_t += __builtin_amdgcn_s_memtime() - t3;
 }
 
+// The hook of a lattice phase (lattice_phase.hpp) behind run_read: the read's lattice is still in this wave's pages. A read
+// that did not fail gets body(lpm, lpe, band): the accessors of the float log-posteriors in the job's layout -- JOB_ALIGN:
+// LPM recomputed from the backward lattice and the state's Zb, LPE apart; JOB_ALIGN_INPLACE: both in place -- and the band
+// they index. A body that needs no lpe costs nothing: the accessor is a handful of scalars. The cycles count as traceback.
+template <int JOB, class Body>
+__device__ __forceinline__ void lattice_phase(const QueueArgs& q, const ReadDesc& rd, const WaveCtx& w, const double* __restrict__ sig,
+                                              const Emis* __restrict__ par, WaveStats& ws, Body body) {
+  static_assert(JOB == JOB_ALIGN || JOB == JOB_ALIGN_INPLACE, "lattice phases exist for align(calc=true) only");
+  const uint64_t t0 = __builtin_amdgcn_s_memtime();
+  // the read's state and segrow were written by lanes of this wave through global memory
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  const ReadState* rs = q.st + rd.read;
+  if (__builtin_amdgcn_readfirstlane((int)ctl_load(reinterpret_cast<const uint32_t*>(&rs->status))) == 0) {
+    const BorderBand band{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio};
+    auto row = [&w](int t) { return pool_row(w, t); };
+    if constexpr (JOB == JOB_ALIGN) {
+      const double Zb = __hip_atomic_load(&rs->Zb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      body(BorderCellSeparate<decltype(row)>{band, q.pool.lpe, q.pool.ws, sig + rd.sig_off, par + rd.par_off, Zb, q.m1, row},
+           SampleLpeSeparate<decltype(row)>{band, q.pool.lpe, row}, band);
+    } else {
+      body(BorderCellInplace<decltype(row)>{band, reinterpret_cast<const float*>(q.pool.ws), row},
+           SampleLpeInplace<decltype(row)>{band, reinterpret_cast<const float*>(q.pool.ws), row}, band);
+    }
+  }
+  ws.cyc_t += __builtin_amdgcn_s_memtime() - t0;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -1409,16 +1442,14 @@ __global__ void k_pool_init(PagePool pool, uint32_t first_free, uint32_t n_stati
 // guarded by s_waitcnt vmcnt(0) -- which drains the forward sweep's DMA ring every ~13 rows.
 // MIXED: the launch holds reads flagged READ_STRICT; such a read takes the sweeps instantiated with the bit-for-bit
 // arithmetic (dp_math_strict.hpp). The default launches (MIXED = false) do not contain that code at all.
-// JOBX: the job, plus JOB_BORDER for the launches that carry the border-confidence phase (border_kernels.hpp) behind every
-// read. The phase is a bit of the job number and not a template parameter of its own, so that the instantiations without
-// it keep the names (and the code) they have always had. JOB_SAMPLE likewise: the posterior-sampling phase (sample_kernels.hpp),
-// and JOB_INTERVAL: the credible-interval phase (interval_kernels.hpp), which runs alone, as does JOB_SOFT: the soft-level phase
-// (soft_level_kernels.hpp).
+// JOBX: the job, plus the bits of the lattice phases the launch carries behind every read (lattice_phase.hpp; the hook:
+// lattice_phase above). They are bits of the job number and not a template parameter of their own: the instantiations keep
+// the names the tools and the committed profiles know them by. READ_QUEUE_VARIANTS lists the instantiations that exist.
 template <int JOBX, bool MIXED>
 __global__ DYN_ONE_WAVE_PER_SIMD void k_read_queue(const QueueArgs q, const ReadDesc* __restrict__ descs,
                                                    const double* __restrict__ sig, const Emis* __restrict__ par,
                                                    const SoftplusNode* __restrict__ sp_tab) {
-  constexpr int JOB = JOBX & ~(JOB_BORDER | JOB_SAMPLE | JOB_INTERVAL | JOB_SOFT);
+  constexpr int JOB = JOBX & ~LATTICE_PHASE_BITS;
   constexpr bool BORDER = (JOBX & JOB_BORDER) != 0;
   constexpr bool SAMPLE = (JOBX & JOB_SAMPLE) != 0;
   constexpr bool INTERVAL = (JOBX & JOB_INTERVAL) != 0;
@@ -1427,8 +1458,6 @@ __global__ DYN_ONE_WAVE_PER_SIMD void k_read_queue(const QueueArgs q, const Read
   static_assert(!INTERVAL || !(BORDER || SAMPLE), "one lattice phase per launch");
   static_assert(!SOFT || !(BORDER || SAMPLE || INTERVAL), "one lattice phase per launch");
   constexpr bool LATTICE = JOB != JOB_Z;
-  // + 2^(i/128) as plain doubles (exp_table128_vec) + glibc's table of the strict exp (dp_math_strict.hpp)
-  constexpr int TAB_NODES = SP_NODES + dynmath::EXP128_NODES + dynmath::STRICT_EXP_WORDS / 2;
   __shared__ __attribute__((aligned(16))) SoftplusNode s_tab[TAB_NODES];
   __shared__ __attribute__((aligned(16))) double s_ring[DYN_WAVES_PER_GROUP][RING_D][P];
   __shared__ uint32_t s_pt[DYN_WAVES_PER_GROUP][PT_MAX];
@@ -1489,89 +1518,23 @@ __global__ DYN_ONE_WAVE_PER_SIMD void k_read_queue(const QueueArgs q, const Read
     const uint64_t t1 = __builtin_amdgcn_s_memtime();
     ws.cyc_w += t1 - t0;
     run_read<JOB, MIXED>(rd, w, q.pool, ReadIO{q.st, q.tb, q.tr, q.m1, q.e2, q.z_fail_status, lpe_floor}, sig, par, s_tab, ring_base, sb, ws, t1);
-    if constexpr (BORDER) {
-      // the read's lattice is still in this wave's pages; its state and segrow were written by lanes of this wave
-      const uint64_t t5 = __builtin_amdgcn_s_memtime();
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      const ReadState* rs = q.st + rd.read;
-      if (__builtin_amdgcn_readfirstlane((int)ctl_load(reinterpret_cast<const uint32_t*>(&rs->status))) == 0) {
-        const BorderBand band{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio};
-        auto row = [&w](int t) { return pool_row(w, t); };
-        if constexpr (JOB == JOB_ALIGN) {
-          const double Zb = __hip_atomic_load(&rs->Zb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const BorderCellSeparate<decltype(row)> cell{band, q.pool.lpe, q.pool.ws, sig + rd.sig_off, par + rd.par_off, Zb, q.m1, row};
-          border_confidence_read(cell, rd, q.tb.segrow, q.border_p, q.border_window_p, q.border_window, w.lane, 64);
-        } else {
-          const BorderCellInplace<decltype(row)> cell{band, reinterpret_cast<const float*>(q.pool.ws), row};
-          border_confidence_read(cell, rd, q.tb.segrow, q.border_p, q.border_window_p, q.border_window, w.lane, 64);
-        }
-      }
-      ws.cyc_t += __builtin_amdgcn_s_memtime() - t5;
-    }
-    if constexpr (SAMPLE) {
-      // as above: the lattice is still in this wave's pages, the read's state was written by lanes of this wave. One lane per
-      // sample; the phase writes nothing the border phase or anything behind it in this launch reads
-      const uint64_t t6 = __builtin_amdgcn_s_memtime();
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      const ReadState* rs = q.st + rd.read;
-      if (__builtin_amdgcn_readfirstlane((int)ctl_load(reinterpret_cast<const uint32_t*>(&rs->status))) == 0) {
-        const BorderBand band{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio};
-        auto row = [&w](int t) { return pool_row(w, t); };
-        if constexpr (JOB == JOB_ALIGN) {
-          const double Zb = __hip_atomic_load(&rs->Zb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const BorderCellSeparate<decltype(row)> lpm{band, q.pool.lpe, q.pool.ws, sig + rd.sig_off, par + rd.par_off, Zb, q.m1, row};
-          const SampleLpeSeparate<decltype(row)> lpe{band, q.pool.lpe, row};
-          posterior_samples_read(lpm, lpe, rd, q.sample, w.lane);
-        } else {
-          const BorderCellInplace<decltype(row)> lpm{band, reinterpret_cast<const float*>(q.pool.ws), row};
-          const SampleLpeInplace<decltype(row)> lpe{band, reinterpret_cast<const float*>(q.pool.ws), row};
-          posterior_samples_read(lpm, lpe, rd, q.sample, w.lane);
-        }
-      }
-      ws.cyc_t += __builtin_amdgcn_s_memtime() - t6;
-    }
-    if constexpr (INTERVAL) {
-      // as the border phase: the lattice is still in this wave's pages, state and segrow were written by lanes of this wave. The
-      // whole wave sweeps the read's rows once, every lane at the band slots the sweeps gave it
-      const uint64_t t7 = __builtin_amdgcn_s_memtime();
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      const ReadState* rs = q.st + rd.read;
-      if (__builtin_amdgcn_readfirstlane((int)ctl_load(reinterpret_cast<const uint32_t*>(&rs->status))) == 0) {
-        const BorderBand band{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio};
-        auto row = [&w](int t) { return pool_row(w, t); };
-        if constexpr (JOB == JOB_ALIGN) {
-          const double Zb = __hip_atomic_load(&rs->Zb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const BorderCellSeparate<decltype(row)> cell{band, q.pool.lpe, q.pool.ws, sig + rd.sig_off, par + rd.par_off, Zb, q.m1, row};
-          border_interval_read_wave(cell, band, rd, q.tb.segrow, q.interval, w.lane);
-        } else {
-          const BorderCellInplace<decltype(row)> cell{band, reinterpret_cast<const float*>(q.pool.ws), row};
-          border_interval_read_wave(cell, band, rd, q.tb.segrow, q.interval, w.lane);
-        }
-      }
-      ws.cyc_t += __builtin_amdgcn_s_memtime() - t7;
-    }
-    if constexpr (SOFT) {
-      // as the interval phase: one sweep of the whole wave over the read's rows, every lane at the band slots the sweeps gave it;
-      // a cell's posterior is the sum of its M and its E share
-      const uint64_t t8 = __builtin_amdgcn_s_memtime();
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      const ReadState* rs = q.st + rd.read;
-      if (__builtin_amdgcn_readfirstlane((int)ctl_load(reinterpret_cast<const uint32_t*>(&rs->status))) == 0) {
-        const BorderBand band{(int)rd.T, (int)rd.N, (int)rd.bw, rd.ratio};
-        auto row = [&w](int t) { return pool_row(w, t); };
-        if constexpr (JOB == JOB_ALIGN) {
-          const double Zb = __hip_atomic_load(&rs->Zb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const BorderCellSeparate<decltype(row)> lpm{band, q.pool.lpe, q.pool.ws, sig + rd.sig_off, par + rd.par_off, Zb, q.m1, row};
-          const SampleLpeSeparate<decltype(row)> lpe{band, q.pool.lpe, row};
-          soft_levels_read_wave(lpm, lpe, band, rd, sig + rd.sig_off, q.soft, w.lane);
-        } else {
-          const BorderCellInplace<decltype(row)> lpm{band, reinterpret_cast<const float*>(q.pool.ws), row};
-          const SampleLpeInplace<decltype(row)> lpe{band, reinterpret_cast<const float*>(q.pool.ws), row};
-          soft_levels_read_wave(lpm, lpe, band, rd, sig + rd.sig_off, q.soft, w.lane);
-        }
-      }
-      ws.cyc_t += __builtin_amdgcn_s_memtime() - t8;
-    }
+    // the lattice phases, border before sample, each behind a fence of its own (lattice_phase)
+    if constexpr (BORDER)
+      lattice_phase<JOB>(q, rd, w, sig, par, ws, [&](const auto& lpm, const auto&, const BorderBand&) {
+        border_confidence_read(lpm, rd, q.tb.segrow, q.border_p, q.border_window_p, q.border_window, w.lane, 64);
+      });
+    if constexpr (SAMPLE)  // one lane per sample; the phase writes nothing the border phase or anything behind it in this launch reads
+      lattice_phase<JOB>(q, rd, w, sig, par, ws, [&](const auto& lpm, const auto& lpe, const BorderBand&) {
+        posterior_samples_read(lpm, lpe, rd, q.sample, w.lane);
+      });
+    if constexpr (INTERVAL)  // the whole wave sweeps the read's rows once, every lane at the band slots the sweeps gave it
+      lattice_phase<JOB>(q, rd, w, sig, par, ws, [&](const auto& lpm, const auto&, const BorderBand& band) {
+        border_interval_read_wave(lpm, band, rd, q.tb.segrow, q.interval, w.lane);
+      });
+    if constexpr (SOFT)  // as the interval phase; a cell's posterior is the sum of its M and its E share
+      lattice_phase<JOB>(q, rd, w, sig, par, ws, [&](const auto& lpm, const auto& lpe, const BorderBand& band) {
+        soft_levels_read_wave(lpm, lpe, band, rd, sig + rd.sig_off, q.soft, w.lane);
+      });
   }
   // leaving: while a claimed read still lacks its pages, somebody may be waiting for these
   if (LATTICE && have && (uint32_t)__builtin_amdgcn_readfirstlane((int)ctl_load(&ctl[CTL_PROVISIONED])) < (uint32_t)q.n_reads)
@@ -1632,7 +1595,6 @@ __global__ DYN_ONE_WAVE_PER_SIMD void k_session(const SessionArgs sa, const char
                                                 const SoftplusNode* __restrict__ sp_tab) {
   constexpr int JOB = LAYOUT == 2 ? JOB_ALIGN_INPLACE : JOB_ALIGN;
   constexpr bool PAGED = LAYOUT != 0;
-  constexpr int TAB_NODES = SP_NODES + dynmath::EXP128_NODES + dynmath::STRICT_EXP_WORDS / 2;
   __shared__ __attribute__((aligned(16))) SoftplusNode s_tab[TAB_NODES];
   __shared__ __attribute__((aligned(16))) double s_ring[DYN_WAVES_PER_GROUP][RING_D][P];
   __shared__ uint32_t s_pt[DYN_WAVES_PER_GROUP][PT_MAX];
@@ -1846,78 +1808,44 @@ void launch_pool_init(const PagePool& pool, uint32_t first_free, int n_static, h
   hipLaunchKernelGGL(k_pool_init, dim3((n + 255) / 256), dim3(256), 0, s, pool, first_free, (uint32_t)n_static);
 }
 
-void launch_read_queue(QueueJob job, bool with_strict, const QueueArgs& q, int n_cus, hipStream_t s) {
-  if (q.n_reads <= 0) return;
+namespace {
+
+// The instantiations of k_read_queue, all of them: the jobs without posteriors as they are, the two align jobs with every set
+// of lattice phases (lattice_phase.hpp), each without and with the certified sweeps. Nothing else instantiates the kernel.
+struct ReadQueueVariant {
+  int jobx;
+  bool mixed;
+  void (*kernel)(QueueArgs, const ReadDesc*, const double*, const Emis*, const SoftplusNode*);
+};
+template <int JOBX, bool MIXED>
+constexpr ReadQueueVariant read_queue_variant{JOBX, MIXED, &k_read_queue<JOBX, MIXED>};
+template <size_t... I>
+constexpr std::array<ReadQueueVariant, 3 + 4 * sizeof...(I)> read_queue_variants(std::index_sequence<I...>) {
+  return {{read_queue_variant<JOB_Z, false>, read_queue_variant<JOB_TRAIN, false>, read_queue_variant<JOB_TRAIN_ZCHECK, false>,
+           read_queue_variant<JOB_ALIGN | LATTICE_PHASE_SETS[I], false>..., read_queue_variant<JOB_ALIGN | LATTICE_PHASE_SETS[I], true>...,
+           read_queue_variant<JOB_ALIGN_INPLACE | LATTICE_PHASE_SETS[I], false>...,
+           read_queue_variant<JOB_ALIGN_INPLACE | LATTICE_PHASE_SETS[I], true>...}};
+}
+constexpr auto READ_QUEUE_VARIANTS = read_queue_variants(std::make_index_sequence<N_LATTICE_PHASE_SETS>{});
+
+// ... and of k_session, [with the certified sweeps][layout]
+using SessionKernel = void (*)(SessionArgs, const char*, char*, const SoftplusNode*);
+constexpr SessionKernel SESSION_KERNELS[2][3] = {{&k_session<false, 0>, &k_session<false, 1>, &k_session<false, 2>},
+                                                 {&k_session<true, 0>, &k_session<true, 1>, &k_session<true, 2>}};
+
+}  // namespace
+
+hipError_t launch_read_queue(QueueJob job, bool with_strict, const QueueArgs& q, int n_cus, hipStream_t s) {
+  if (q.n_reads <= 0) return hipSuccess;
   const int groups = std::min((q.n_reads + DYN_WAVES_PER_GROUP - 1) / DYN_WAVES_PER_GROUP, std::max(1, n_cus));
   const dim3 grid(groups), block(64 * DYN_WAVES_PER_GROUP);
-  if (q.soft.tag == SOFT_TAG && (job == JOB_ALIGN || job == JOB_ALIGN_INPLACE)) {  // dyn_aligner_set_soft_levels
-#define DYN_SOFT_LAUNCH(J, M) hipLaunchKernelGGL((k_read_queue<J | JOB_SOFT, M>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab)
-    if (job == JOB_ALIGN) {
-      if (with_strict) DYN_SOFT_LAUNCH(JOB_ALIGN, true);
-      else DYN_SOFT_LAUNCH(JOB_ALIGN, false);
-    } else {
-      if (with_strict) DYN_SOFT_LAUNCH(JOB_ALIGN_INPLACE, true);
-      else DYN_SOFT_LAUNCH(JOB_ALIGN_INPLACE, false);
+  const int jobx = job | lattice_phases(job == JOB_ALIGN || job == JOB_ALIGN_INPLACE, q.sample.count, q.interval.tail, q.border_window);
+  for (const ReadQueueVariant& v : READ_QUEUE_VARIANTS)
+    if (v.jobx == jobx && v.mixed == with_strict) {
+      hipLaunchKernelGGL(v.kernel, grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab);
+      return hipGetLastError();
     }
-#undef DYN_SOFT_LAUNCH
-    return;
-  }
-  if (q.sample.count == 0 && q.interval.tail > 0.0 && (job == JOB_ALIGN || job == JOB_ALIGN_INPLACE)) {  // dyn_aligner_set_border_interval
-#define DYN_INTERVAL_LAUNCH(J, M) hipLaunchKernelGGL((k_read_queue<J | JOB_INTERVAL, M>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab)
-    if (job == JOB_ALIGN) {
-      if (with_strict) DYN_INTERVAL_LAUNCH(JOB_ALIGN, true);
-      else DYN_INTERVAL_LAUNCH(JOB_ALIGN, false);
-    } else {
-      if (with_strict) DYN_INTERVAL_LAUNCH(JOB_ALIGN_INPLACE, true);
-      else DYN_INTERVAL_LAUNCH(JOB_ALIGN_INPLACE, false);
-    }
-#undef DYN_INTERVAL_LAUNCH
-    return;
-  }
-  if (q.sample.count > 0 && (job == JOB_ALIGN || job == JOB_ALIGN_INPLACE)) {  // dyn_aligner_set_posterior_samples
-#define DYN_SAMPLE_LAUNCH(J, M) hipLaunchKernelGGL((k_read_queue<J | JOB_SAMPLE, M>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab)
-    if (q.border_window > 0) {  // ... behind the border-confidence phase
-      if (job == JOB_ALIGN) {
-        if (with_strict) DYN_SAMPLE_LAUNCH(JOB_ALIGN | JOB_BORDER, true);
-        else DYN_SAMPLE_LAUNCH(JOB_ALIGN | JOB_BORDER, false);
-      } else {
-        if (with_strict) DYN_SAMPLE_LAUNCH(JOB_ALIGN_INPLACE | JOB_BORDER, true);
-        else DYN_SAMPLE_LAUNCH(JOB_ALIGN_INPLACE | JOB_BORDER, false);
-      }
-    } else if (job == JOB_ALIGN) {
-      if (with_strict) DYN_SAMPLE_LAUNCH(JOB_ALIGN, true);
-      else DYN_SAMPLE_LAUNCH(JOB_ALIGN, false);
-    } else {
-      if (with_strict) DYN_SAMPLE_LAUNCH(JOB_ALIGN_INPLACE, true);
-      else DYN_SAMPLE_LAUNCH(JOB_ALIGN_INPLACE, false);
-    }
-#undef DYN_SAMPLE_LAUNCH
-    return;
-  }
-  if (q.border_window > 0 && (job == JOB_ALIGN || job == JOB_ALIGN_INPLACE)) {  // dyn_aligner_set_border_confidence
-#define DYN_BORDER_LAUNCH(J, M) hipLaunchKernelGGL((k_read_queue<J | JOB_BORDER, M>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab)
-    if (job == JOB_ALIGN) {
-      if (with_strict) DYN_BORDER_LAUNCH(JOB_ALIGN, true);
-      else DYN_BORDER_LAUNCH(JOB_ALIGN, false);
-    } else {
-      if (with_strict) DYN_BORDER_LAUNCH(JOB_ALIGN_INPLACE, true);
-      else DYN_BORDER_LAUNCH(JOB_ALIGN_INPLACE, false);
-    }
-#undef DYN_BORDER_LAUNCH
-    return;
-  }
-  if (with_strict) {  // only jobs with integer outputs have strict reads
-    if (job == JOB_ALIGN) hipLaunchKernelGGL((k_read_queue<JOB_ALIGN, true>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab);
-    else hipLaunchKernelGGL((k_read_queue<JOB_ALIGN_INPLACE, true>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab);
-    return;
-  }
-  switch (job) {
-    case JOB_Z: hipLaunchKernelGGL((k_read_queue<JOB_Z, false>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab); break;
-    case JOB_ALIGN: hipLaunchKernelGGL((k_read_queue<JOB_ALIGN, false>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab); break;
-    case JOB_ALIGN_INPLACE: hipLaunchKernelGGL((k_read_queue<JOB_ALIGN_INPLACE, false>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab); break;
-    case JOB_TRAIN: hipLaunchKernelGGL((k_read_queue<JOB_TRAIN, false>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab); break;
-    case JOB_TRAIN_ZCHECK: hipLaunchKernelGGL((k_read_queue<JOB_TRAIN_ZCHECK, false>), grid, block, 0, s, q, q.descs, q.sig, q.par, q.sp_tab); break;
-  }
+  return hipErrorInvalidValue;  // only jobs with integer outputs, the two align jobs, have strict reads
 }
 
 void launch_session(bool with_strict, int layout, const SessionArgs& a, const void* in_base, void* out_base, const dynmath::SoftplusNode* sp_tab,
@@ -1925,17 +1853,8 @@ void launch_session(bool with_strict, int layout, const SessionArgs& a, const vo
   const dim3 grid(std::max(1, n_cus)), block(64 * DYN_WAVES_PER_GROUP);
   const char* in = static_cast<const char*>(in_base);
   char* out = static_cast<char*>(out_base);
-#define DYN_SESSION_LAUNCH(M, L) hipLaunchKernelGGL((k_session<M, L>), grid, block, 0, s, a, in, out, sp_tab)
-  if (with_strict) {
-    if (layout == 0) DYN_SESSION_LAUNCH(true, 0);
-    else if (layout == 1) DYN_SESSION_LAUNCH(true, 1);
-    else DYN_SESSION_LAUNCH(true, 2);
-  } else {
-    if (layout == 0) DYN_SESSION_LAUNCH(false, 0);
-    else if (layout == 1) DYN_SESSION_LAUNCH(false, 1);
-    else DYN_SESSION_LAUNCH(false, 2);
-  }
-#undef DYN_SESSION_LAUNCH
+  const int l = layout == 0 || layout == 1 ? layout : 2;  // (any other value is the in-place layout, as it has always been)
+  hipLaunchKernelGGL(SESSION_KERNELS[with_strict][l], grid, block, 0, s, a, in, out, sp_tab);
 }
 
 void launch_session_publish(SessionTicket* ring, uint32_t* ctl, const SessionTicket& tk, uint32_t index, uint32_t ring_size, hipStream_t s) {

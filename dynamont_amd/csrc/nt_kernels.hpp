@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dp_math.hpp"
+#include "lattice_phase.hpp"
 
 namespace dynk {
 
@@ -108,14 +109,9 @@ constexpr int QUEUE_STATS = 8;        // first stats word (as uint32 index)
 constexpr int QUEUE_N_STATS = 10;
 
 enum QueueJob { JOB_Z = 0, JOB_ALIGN = 1, JOB_ALIGN_INPLACE = 2, JOB_TRAIN = 3, JOB_TRAIN_ZCHECK = 4 };
-constexpr int JOB_BORDER = 8;  // a bit on top of JOB_ALIGN / JOB_ALIGN_INPLACE in k_read_queue's template argument: the launch
-                               // carries the border-confidence phase (border_kernels.hpp)
-constexpr int JOB_INTERVAL = 32;  // likewise: the launch carries the credible-interval phase (interval_kernels.hpp); never together
-                                  // with the other two
-constexpr int JOB_SOFT = 64;      // likewise: the launch carries the soft-level phase (soft_level_kernels.hpp); never together with
-                                  // any of the other three
-constexpr int JOB_SAMPLE = 16; // likewise: the launch carries the posterior-sampling phase (sample_kernels.hpp), behind the border
-                               // phase when both bits are set
+// On top of JOB_ALIGN / JOB_ALIGN_INPLACE, k_read_queue's template argument carries the launch's lattice phases: the bits JOB_BORDER,
+// JOB_SAMPLE, JOB_INTERVAL and JOB_SOFT, and lattice_phases(), the one place that decides which of them a launch carries
+// (lattice_phase.hpp).
 
 // posterior path samples (dyn_aligner_set_posterior_samples; sample_kernels.hpp). count == 0: not asked for (and the launch is
 // the one it has always been). The per-read counts of dead samples live behind the planes: start + count * capacity, one per
@@ -129,8 +125,8 @@ struct SampleOut {
 
 // per-border credible intervals (dyn_aligner_set_border_interval; interval_kernels.hpp): the four columns of a launch, in ONE buffer of 24 bytes per output row:
 //   double mean[capacity] | double sd[capacity] | uint32 lo[capacity] | uint32 hi[capacity]       (zeroed by the caller)
-// tail == 0: not asked for. It shares the train buffers' / the samples' place in QueueArgs and BandArgs (nt_kernels.hpp): `none`
-// lies on SampleOut::count and stays 0, which is how a launch tells the two apart.
+// tail == 0: not asked for. It shares the train buffers' / the samples' place in QueueArgs and BandArgs: `none` lies on
+// SampleOut::count and stays 0, which is how lattice_phases() tells the two apart.
 struct IntervalOut {
   double* mean;
   uint64_t capacity;
@@ -143,14 +139,13 @@ static_assert(offsetof(IntervalOut, none) == offsetof(SampleOut, count), "an int
 // buffer of 24 bytes per output row:
 //   double weight[capacity] | double sum[capacity] | double sumsq[capacity]                         (zeroed by the caller)
 // It shares the same place. `zero` lies on SampleOut::seed / IntervalOut::tail and stays 0 (no interval launch), `tag` lies on
-// SampleOut::count / IntervalOut::none and is SOFT_TAG, a value neither of the others ever holds (a sample count is 0 .. 64).
+// SampleOut::count / IntervalOut::none and is SOFT_TAG (lattice_phase.hpp), a value neither of the others ever holds.
 struct SoftOut {
   double* weight;
   uint64_t capacity;
   uint64_t zero;  // = IntervalOut::tail: 0.0
   int tag;        // = SampleOut::count: SOFT_TAG when asked for
 };
-constexpr int SOFT_TAG = -1;
 static_assert(offsetof(SoftOut, tag) == offsetof(SampleOut, count) && offsetof(SoftOut, zero) == offsetof(IntervalOut, tail),
               "a soft-level launch reads as one without samples and without intervals");
 
@@ -170,8 +165,8 @@ struct QueueArgs {
     SampleOut sample;   // JOB_ALIGN / JOB_ALIGN_INPLACE: posterior path samples, count > 0 when asked for
     IntervalOut interval;  // JOB_ALIGN / JOB_ALIGN_INPLACE: per-border credible intervals, tail > 0 (and sample.count == 0) when asked for
     SoftOut soft;       // JOB_ALIGN / JOB_ALIGN_INPLACE: posterior-weighted per-base sums, tag == SOFT_TAG when asked for
-    // Which member an align launch carries is read from ONE word, sample.count (= interval.none = soft.tag): > 0 the samples,
-    // SOFT_TAG the soft levels, 0 the intervals if interval.tail > 0 and else none of them.
+    // Which member an align launch carries is read from ONE word, sample.count (= interval.none = soft.tag), and
+    // interval.tail, by lattice_phases() (lattice_phase.hpp) and by nobody else.
   };
   double m1, e2;          // log transition probabilities (NT_aligner_api.cpp:84-86)
   const dynmath::SoftplusNode* sp_tab;
@@ -276,7 +271,9 @@ void launch_pool_init(const PagePool& pool, uint32_t first_free, int n_static, h
 // n_cus: compute units of the device (one 4-wave workgroup per CU).
 // with_strict: the launch holds reads flagged READ_STRICT (JOB_ALIGN / JOB_ALIGN_INPLACE only): the kernel variant
 // that carries both arithmetic flavours and branches per read
-void launch_read_queue(QueueJob job, bool with_strict, const QueueArgs& q, int n_cus, hipStream_t s);
+// Returns what the launch reported. hipErrorInvalidValue, and no launch: no kernel exists for the job with its phases and
+// with_strict (a strict launch of a job other than the two align jobs)
+hipError_t launch_read_queue(QueueJob job, bool with_strict, const QueueArgs& q, int n_cus, hipStream_t s);
 // per-segment signal levels (event_stats.hip): columns indexed like the output rows; mean == nullptr: not asked for
 struct EventCols {
   const double* sig;  // the signal the read queue aligned (ReadDesc::sig_off counts from here)

@@ -1,6 +1,6 @@
 """Shared by tests/test_any_band_host.py, tests/test_gpu_any_band.py and tests/test_gpu_parity.py (no GPU, no library): the read
-sets that put the diagonal any-band kernel (k_band_reads<DiagonalWindow, 256, 16, ..> of band_reads.hip and its four rider
-copies) on REUSED workgroups with reads of MIXED width, and the bar a wide-band train() result is held to against
+sets that put the diagonal any-band kernel (k_band_reads<DiagonalWindow, 256, 16, ..> of band_reads.hip, with and without
+lattice phases) on REUSED workgroups with reads of MIXED width, and the bar a wide-band train() result is held to against
 ``Oracle.train(.., dense=False)``.
 
 Read sets (``read_sets``). Model syn5, pore dna_r9 (k = 5, no polyA pad: N = k-mer count + 1 = bases - 3, as launch.cpp forms it),

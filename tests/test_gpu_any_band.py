@@ -1,6 +1,6 @@
-"""GPU (-m gpu): the diagonal any-band kernel (k_band_reads<DiagonalWindow, 256, 16, ..> of band_reads.hip and the four copies of
-its queue loop: k_band_reads_sample<BORDER>, k_band_reads_interval, k_band_reads_soft) on REUSED workgroups and reads of MIXED
-width. A handle created under DYN_QUEUE_CUS=2 launches two workgroups for the 14 wide reads of tests/any_band_cases.py (B = 451,
+"""GPU (-m gpu): the diagonal any-band kernel (k_band_reads<DiagonalWindow, 256, 16, ..> of band_reads.hip, without a lattice
+phase and with each of the five sets of them a launch may carry: PHASES of lattice_phase.hpp) on REUSED workgroups and reads of
+MIXED width. A handle created under DYN_QUEUE_CUS=2 launches two workgroups for the 14 wide reads of tests/any_band_cases.py (B = 451,
 511, 513, 767, 769, 1 003; dwell 2 and 10; a structural tie; a NaN sample), so at least 12 reads run on a workgroup that has
 just finished another read of another B -- what a workgroup carries over (four LDS rows initialised only up to the new B, the
 arena in the previous read's layout, s_bad of a read that failed, the train job's running sums) must not reach the next read.
@@ -220,7 +220,7 @@ def test_train_on_two_workgroups_under_the_derived_bar_and_bit_for_bit(runs, bat
     same_bits(tr, again, TRAIN, f"train {order}: a second run on two workgroups")
 
 
-# ---- f. the riders: four copies of the queue loop and the BORDER instantiation -----------------------------------------------------
+# ---- f. the riders: the five instantiations of the kernel that carry lattice phases ------------------------------------------------
 RIDERS = {
     "border_confidence": (lambda al: al.set_border_confidence(8), ("border_probability", "border_window_probability"), "descending"),
     "samples": (lambda al: al.set_posterior_samples(4, 20261020), ("sample_starts", "sample_dead"), "ascending"),

@@ -117,6 +117,8 @@ def test_default_layout(models, sets, want, name, W):
     assert tm["lp_inplace"] == 0 and tm["launches"] == 1
     if name == "rna002":
         assert tm["reads_strict"] == len(reads)                     # every read carries the tie: the launch with both flavours
+    else:
+        assert tm["reads_strict"] == 0
     if name == "rna002" and W == 2:
         for _, bwp, _ in yard:
             assert bwp.min() <= 0.3 and bwp.max() >= 1.0 - bcc.TOL
@@ -185,6 +187,10 @@ def test_inplace_layout_and_page_starved_pool(models, sets, want, monkeypatch, n
     if path == "inplace":
         monkeypatch.delenv("DYN_FORCE_LAYOUT")
         assert tm["lp_inplace"] == 1
+        if name == "rna002":
+            assert tm["reads_strict"] == len(reads)                 # in place AND both flavours: k_read_queue<JOB_ALIGN_INPLACE | JOB_BORDER, true>
+        if name == "dna_r9":
+            assert tm["reads_strict"] == 0                          # ... and the plain in-place launch
     else:
         print(f"{name} page-starved: pool_pages {tm['pool_pages']}, page_rows {tm['page_rows']}, n_static {tm['n_static']} of {len(reads)}")
     check(res, yard, f"{name} W={W} {path}")

@@ -142,9 +142,33 @@ def test_inplace_layout_and_page_starved_pool(models, sets, yards, monkeypatch, 
     if path == "inplace":
         monkeypatch.delenv("DYN_FORCE_LAYOUT")
         assert tm["lp_inplace"] == 1
+        if name.startswith("imperfect"):
+            assert tm["reads_strict"] == len(reads)                 # in place AND both flavours: k_read_queue<JOB_ALIGN_INPLACE | JOB_INTERVAL, true>
     else:
         print(f"{name} page-starved: pool_pages {tm['pool_pages']}, page_rows {tm['page_rows']}, n_static {tm['n_static']} of {len(reads)}")
     check(res, ys, 0.9, f"{name} {path}")
+    same_segments(res, off)
+
+
+# two of the six "plain" reads carry a tie by chance (dyn_tie_rows), so every batch above takes the launch with both arithmetic
+# flavours; these four carry none
+PLAIN_WITHOUT_A_TIE = (1, 2, 4, 5)
+
+
+@pytest.mark.parametrize("layout", ["separate", "inplace"])
+def test_launch_without_a_certified_read(models, sets, yards, monkeypatch, layout):
+    """k_read_queue<JOB_ALIGN | JOB_INTERVAL, false> and <JOB_ALIGN_INPLACE | JOB_INTERVAL, false>: a batch the tie rule flags no
+    read of, held as the batches above are"""
+    key, pore, band, reads = sets["plain"]
+    reads, ys = [reads[i] for i in PLAIN_WITHOUT_A_TIE], [yards("plain")[i] for i in PLAIN_WITHOUT_A_TIE]
+    if layout == "inplace":
+        monkeypatch.setenv("DYN_FORCE_LAYOUT", "inplace")
+    res, tm = run(models[key], pore, band, reads, 0.9)
+    off = run_off(models[key], pore, band, reads)
+    if layout == "inplace":
+        monkeypatch.delenv("DYN_FORCE_LAYOUT")
+    assert tm["lp_inplace"] == (1 if layout == "inplace" else 0) and tm["launches"] == 1 and tm["reads_strict"] == 0
+    check(res, ys, 0.9, f"plain without a tie, {layout}")
     same_segments(res, off)
 
 

@@ -123,6 +123,8 @@ def test_separate_layout(models, sets, want, name, K):
     assert tm["lp_inplace"] == 0 and tm["launches"] == 1
     if name == "rna002":
         assert tm["reads_strict"] == len(reads)
+    else:
+        assert tm["reads_strict"] == 0
     check(res, want(members_of(sets, name), K), K, f"{name} K={K}")
     d = res.read(1)
     a, m = int(res.seg_offsets[1]), int(res.n_segments[1])
@@ -167,6 +169,10 @@ def test_inplace_layout_and_page_starved_pool(models, sets, want, monkeypatch, n
     if path == "inplace":
         monkeypatch.delenv("DYN_FORCE_LAYOUT")
         assert tm["lp_inplace"] == 1
+        if name == "rna002":
+            assert tm["reads_strict"] == len(reads)                 # in place AND both flavours: k_read_queue<JOB_ALIGN_INPLACE | JOB_SAMPLE, true>
+        if name == "dna_r9":
+            assert tm["reads_strict"] == 0                          # ... and the plain in-place launch
     else:
         print(f"{name} page-starved: pool_pages {tm['pool_pages']}, page_rows {tm['page_rows']}, n_static {tm['n_static']} of {len(reads)}")
     check(res, want(members, 16), 16, f"{name} {path}")
@@ -212,9 +218,35 @@ def test_runs_seeds_and_tickets(models, sets, want):
 # ---- 7. together with the border confidence ------------------------------------------------------------------------------------
 def test_with_border_confidence_both_outputs_unchanged(models, sets):
     pore, band, reads = sets["rna002"]
-    both, _ = run(models["syn5"], pore, band, reads, 16, W=8)
+    both, tm = run(models["syn5"], pore, band, reads, 16, W=8)
+    assert tm["lp_inplace"] == 0 and tm["reads_strict"] == len(reads)      # k_read_queue<JOB_ALIGN | JOB_SAMPLE | JOB_BORDER, true>
     samples_only, _ = run(models["syn5"], pore, band, reads, 16)
     borders_only = run_off(models["syn5"], pore, band, reads, W=8)
+    same_segments(both, borders_only)
+    same_samples(both, samples_only)
+    m = int(both.seg_offsets[-1])
+    for c in ("border_probability", "border_window_probability"):
+        assert np.array_equal(getattr(both, c)[:m].view(np.uint64), getattr(borders_only, c)[:m].view(np.uint64)), c
+
+
+@pytest.mark.parametrize("name,layout", [("dna_r9", "separate"), ("rna002", "inplace"), ("dna_r9", "inplace")])
+def test_with_border_confidence_the_other_launches(models, sets, want, monkeypatch, name, layout):
+    """The three other launches that carry both phases: the separate layout's plain one, and the in-place layout's with the
+    certified sweeps (rna002: every read carries the tie) and without. The paths against the yardstick as in the in-place case
+    above, both outputs those of the launches that carry one phase, and the segments those of a launch that carries none."""
+    pore, band, reads = sets[name]
+    if layout == "inplace":
+        monkeypatch.setenv("DYN_FORCE_LAYOUT", "inplace")
+    both, tm = run(models["syn5"], pore, band, reads, 16, W=8)
+    samples_only, _ = run(models["syn5"], pore, band, reads, 16)
+    borders_only = run_off(models["syn5"], pore, band, reads, W=8)
+    off = run_off(models["syn5"], pore, band, reads)
+    if layout == "inplace":
+        monkeypatch.delenv("DYN_FORCE_LAYOUT")
+    assert tm["lp_inplace"] == (1 if layout == "inplace" else 0) and tm["launches"] == 1
+    assert tm["reads_strict"] == (len(reads) if name == "rna002" else 0)
+    check(both, want(members_of(sets, name), 16), 16, f"{name} {layout} behind the border phase")
+    same_segments(both, off)
     same_segments(both, borders_only)
     same_samples(both, samples_only)
     m = int(both.seg_offsets[-1])

@@ -132,8 +132,32 @@ def test_inplace_layout_and_page_starved_pool(models, sets, yards, monkeypatch, 
     if path == "inplace":
         monkeypatch.delenv("DYN_FORCE_LAYOUT")
         assert tm["lp_inplace"] == 1
+        if name.startswith("imperfect"):
+            assert tm["reads_strict"] == len(reads)                 # in place AND both flavours: k_read_queue<JOB_ALIGN_INPLACE | JOB_SOFT, true>
     check(res, yards(name), f"{name} {path}")
     same_bits(res, off, SEGMENTS, path)
+
+
+# two of the six "plain" reads carry a tie by chance (dyn_tie_rows), so every batch above takes the launch with both arithmetic
+# flavours; these four carry none
+PLAIN_WITHOUT_A_TIE = (1, 2, 4, 5)
+
+
+@pytest.mark.parametrize("layout", ["separate", "inplace"])
+def test_launch_without_a_certified_read(models, sets, yards, monkeypatch, layout):
+    """k_read_queue<JOB_ALIGN | JOB_SOFT, false> and <JOB_ALIGN_INPLACE | JOB_SOFT, false>: a batch the tie rule flags no read of,
+    held as the batches above are"""
+    key, pore, band, reads = sets["plain"]
+    reads, ys = [reads[i] for i in PLAIN_WITHOUT_A_TIE], [yards("plain")[i] for i in PLAIN_WITHOUT_A_TIE]
+    if layout == "inplace":
+        monkeypatch.setenv("DYN_FORCE_LAYOUT", "inplace")
+    res, tm = run(models[key], pore, band, reads)
+    off, _ = run(models[key], pore, band, reads, on=False)
+    if layout == "inplace":
+        monkeypatch.delenv("DYN_FORCE_LAYOUT")
+    assert tm["lp_inplace"] == (1 if layout == "inplace" else 0) and tm["launches"] == 1 and tm["reads_strict"] == 0
+    check(res, ys, f"plain without a tie, {layout}")
+    same_bits(res, off, SEGMENTS, layout)
 
 
 # ---- 5. the banded-lattice kernel ------------------------------------------------------------------------------------------------

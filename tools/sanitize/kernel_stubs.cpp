@@ -25,7 +25,7 @@ void launch_preprocess(const void*, int, int, const uint64_t*, const double*, co
 }
 void launch_prep_params(const int32_t*, const Emis*, Emis*, uint64_t, uint32_t, hipStream_t) { no_device("launch_prep_params"); }
 void launch_pool_init(const PagePool&, uint32_t, int, hipStream_t) { no_device("launch_pool_init"); }
-void launch_read_queue(QueueJob, bool, const QueueArgs&, int, hipStream_t) { no_device("launch_read_queue"); }
+hipError_t launch_read_queue(QueueJob, bool, const QueueArgs&, int, hipStream_t) { no_device("launch_read_queue"); }
 void launch_segments(const ReadDesc*, int, uint64_t, uint32_t, const ReadState*, TraceBuffers, SegRow*, int, hipStream_t, const EventCols&,
                      const KmerSummary&, const ScoreCols&, const BandMargin&) {
   no_device("launch_segments");
