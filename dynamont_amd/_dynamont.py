@@ -121,6 +121,8 @@ class AlignBatchResult:
         # posterior-weighted per-base sums (Aligner.set_soft_levels): soft_weight / soft_sum / soft_sumsq float64 [cap], indexed
         # like the segment columns; None when off
         self.soft_weight = self.soft_sum = self.soft_sumsq = None
+        # per-read site calls (Aligner.set_site_calls): float64 [cap] like the segment columns, NaN = no call; None when off
+        self.site_probability = self.site_z = None
         # band-margin diagnostics (Aligner.set_band_margin): uint32 [n] each, None when off; band_used (uint32 [n]): the band
         # every read's rows come from, only with Aligner.set_band_retry
         self.band_margin_low = self.band_margin_high = self.band_edge_rows = None
@@ -208,6 +210,9 @@ class AlignBatchResult:
         if self.soft_weight is not None:  # only when requested (Aligner.set_soft_levels)
             d["soft_dwell"], d["soft_mean"], d["soft_stdv"] = soft_level_columns(self.soft_weight[a:b], self.soft_sum[a:b],
                                                                                  self.soft_sumsq[a:b])
+        if self.site_probability is not None:  # only when requested (Aligner.set_site_calls)
+            d["site_probability"] = self.site_probability[a:b].copy()
+            d["site_z"] = self.site_z[a:b].copy()
         if self.rescale_shift is not None:  # only when requested (Aligner.set_rescale)
             d["rescale_shift"] = float(self.rescale_shift[i])
             d["rescale_scale"] = float(self.rescale_scale[i])
@@ -245,6 +250,7 @@ class JobWants(NamedTuple):
     margins: bool = False    # set_band_margin (tickets report margins; they are never retried)
     rescue: bool = False     # set_guide_rescue
     soft: bool | None = None  # set_soft_levels (off is None, like the field behind it: both stand behind the positional fields)
+    calls: bool | None = None  # set_site_calls (off is None, as for soft)
     auto_guide: tuple | None = None  # set_auto_guide, tickets only: (alignments per read, the ticket's sample offsets)
 
 
@@ -266,6 +272,7 @@ _OPTIONAL = {
                   N.DynBorderIntervalOut, "dyn_batch_fetch_intervals"),
     "soft": ((("soft_weight", _F64, "cap"), ("soft_sum", _F64, "cap"), ("soft_sumsq", _F64, "cap")),
              N.DynSoftLevelOut, "dyn_batch_fetch_soft_levels"),
+    "calls": ((("site_probability", _F64, "cap"), ("site_z", _F64, "cap")), N.DynSiteCallOut, "dyn_batch_fetch_site_calls"),
     "margins": ((("band_margin_low", _U32, "n"), ("band_margin_high", _U32, "n"), ("band_edge_rows", _U32, "n")),
                 N.DynBandMarginOut, "dyn_batch_fetch_band_margin"),
     "rescue": ((("rescue", np.uint8, "n"), ("guide_rounds", _U32, "n"), ("guide_converged", _U32, "n")),
@@ -296,16 +303,17 @@ def format_csv(aligner: "Aligner", res: AlignBatchResult, sequences: Sequence[st
     L = N.lib()
     # the optional columns the result carries, in the order the rows hold them: the signal levels (Aligner.set_event_stats), the
     # segment scores (set_segment_scores), the border confidence (set_border_confidence), the posterior samples
-    # (set_posterior_samples), the credible intervals (set_border_interval), the soft levels (set_soft_levels)
-    ev, sc, bd, sm, bi, sl = (C.byref(res._out_struct(name)) if getattr(res, _OPTIONAL[name][0][0][0]) is not None else None
-                              for name in ("levels", "scores", "borders", "samples", "intervals", "soft"))
-    cap = int(L.dyn_format_csv_bound_soft(aligner._h, n, C.byref(res._c), ev, sc, bd, sm, bi, sl, rid, sid))
+    # (set_posterior_samples), the credible intervals (set_border_interval), the soft levels (set_soft_levels), the site calls
+    # (set_site_calls)
+    ev, sc, bd, sm, bi, sl, ca = (C.byref(res._out_struct(name)) if getattr(res, _OPTIONAL[name][0][0][0]) is not None else None
+                                  for name in ("levels", "scores", "borders", "samples", "intervals", "soft", "calls"))
+    cap = int(L.dyn_format_csv_bound_calls(aligner._h, n, C.byref(res._c), ev, sc, bd, sm, bi, sl, ca, rid, sid))
     # one grow-only buffer per handle: first-touch page faults of a fresh 350 MB buffer cost ~100x
     # the formatting itself (15 ms per 1 024-read batch with warm pages)
     buf = getattr(aligner, "_csv_buf", None)
     if buf is None or buf.size < cap:
         buf = aligner._csv_buf = np.empty(max(cap, 1), dtype=np.uint8)
-    rc = L.dyn_format_csv_soft(aligner._h, n, C.byref(res._c), ev, sc, bd, sm, bi, sl, seqs, _ptr(seq_off, N.c_u64_p), rid, sid,
+    rc = L.dyn_format_csv_calls(aligner._h, n, C.byref(res._c), ev, sc, bd, sm, bi, sl, ca, seqs, _ptr(seq_off, N.c_u64_p), rid, sid,
                           so.ctypes.data_as(C.POINTER(C.c_int64)), li.ctypes.data_as(C.POINTER(C.c_int64)),
                           int(threads), buf.ctypes.data, cap, _ptr(begin, N.c_u64_p), _ptr(end, N.c_u64_p))
     if rc != N.DYN_OK:
@@ -516,6 +524,7 @@ class Batch:
     fetch_samples = _fetch_into("dyn_batch_fetch_samples")            # N.DynSampleOut
     fetch_intervals = _fetch_into("dyn_batch_fetch_intervals")        # N.DynBorderIntervalOut
     fetch_soft_levels = _fetch_into("dyn_batch_fetch_soft_levels")    # N.DynSoftLevelOut
+    fetch_site_calls = _fetch_into("dyn_batch_fetch_site_calls")      # N.DynSiteCallOut
     fetch_band_margin = _fetch_into("dyn_batch_fetch_band_margin")    # N.DynBandMarginOut
     fetch_rescale = _fetch_into("dyn_batch_fetch_rescale")            # N.DynRescaleOut
 
@@ -614,6 +623,7 @@ class AsyncBatch:
     fetch_samples = Batch.fetch_samples
     fetch_intervals = Batch.fetch_intervals
     fetch_soft_levels = Batch.fetch_soft_levels
+    fetch_site_calls = Batch.fetch_site_calls
     fetch_band_margin = Batch.fetch_band_margin
 
     def timing(self) -> dict:
@@ -707,6 +717,7 @@ def limbs_of_int128(values):
 
 
 SITE_SUMMARY_TOTALS = ("reads_ok", "rows_added", "samples_added", "rows_without_site", "rows_skipped")
+SITE_MODEL_COLUMNS = ("pi1", "mu0", "mu1", "var0", "var1")  # a row of the per-site model (Aligner.set_site_model)
 
 
 def site_summary_from_limbs(cols, totals) -> dict:
@@ -749,6 +760,7 @@ class Aligner:
     _site_capacity = 0  # set_site_summary(capacity=): rows of the sparse table, 0 while the table is dense
     _site_table = 0  # ... and the size of the handle's table (it outlives the switch)
     _site_histogram = None  # set_site_histogram: (bins, lo, hi) of the handle's counters (they outlive the switch too)
+    _site_calls = False  # set_site_calls
     _strict = 1  # set_strict
     _model_override = None  # set_model: (mean, stdev)
 
@@ -965,7 +977,8 @@ class Aligner:
         plain = self._ctor[2] not in ("ntk", "resquiggle")
         return JobWants(levels=bool(self._event_stats), rescale=self._rescale > 0, scores=self._segment_scores > 0,
                         borders=self._border_confidence > 0, samples=self._posterior_samples[0] if plain else 0,
-                        intervals=plain and self._border_interval > 0, soft=(plain and self._soft_levels) or None, margins=bool(self._band_margin),
+                        intervals=plain and self._border_interval > 0, soft=(plain and self._soft_levels) or None,
+                        calls=bool(self._site_calls) or None, margins=bool(self._band_margin),
                         rescue=plain and self._guide_rescue[1] > 0,
                         auto_guide=(self._auto_guide[1], sig_off) if plain and sig_off is not None and self._auto_guide[0] > 0 else None)
 
@@ -1248,6 +1261,57 @@ class Aligner:
             out["share_b"] = np.where(out["n_b"] > 0, out["r_b"] / out["n_b"].astype(np.float64), np.nan)
             out["separation"] = (out["mu1"] - out["mu0"]) / np.sqrt(0.5 * (out["var0"] + out["var1"]))
         return out
+
+    def set_site_model(self, lo: int, m: dict, accept=(0, 2)) -> dict:
+        """dyn_aligner_set_site_model: the dict ``site_mixture()`` returns as the per-site model of the sites [lo, lo + len) -- ``pi1``,
+        ``mu0``, ``mu1``, ``var0``, ``var1`` go to the device unchanged for the rows whose ``status`` is in ``accept`` (default:
+        converged, or ``max_iters`` reached); every other row is stored NOT SET (five zeros). A dict without ``status`` stores
+        every row as it is. The model lives beside the per-site table (``set_site_summary`` first), 40 bytes per table row
+        (INTEGRATION.md section 3). Returns ``{"stored": rows sent as set, "dropped": those of them whose id found no bucket in a
+        sparse table's map}``."""
+        cols = [np.array(m[k], dtype=np.float64).reshape(-1) for k in SITE_MODEL_COLUMNS]
+        n = cols[0].size
+        if any(c.size != n for c in cols):
+            raise ValueError("set_site_model: the columns of the model differ in length")
+        if m.get("status") is not None:
+            keep = np.isin(np.asarray(m["status"]).reshape(-1), list(accept))
+            if keep.size != n:
+                raise ValueError("set_site_model: status and the columns of the model differ in length")
+            for c in cols:
+                c[~keep] = 0.0
+        with np.errstate(invalid="ignore"):
+            stored = int(((cols[3] > 0) & np.isfinite(cols[1]) & np.isfinite(cols[3])).sum())
+        dropped = np.zeros(1, dtype=np.uint64)
+        rc = self._L.dyn_aligner_set_site_model(self._h, int(lo), n, *[_ptr(c, N.c_double_p) for c in cols], _ptr(dropped, N.c_u64_p))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        return {"stored": stored, "dropped": int(dropped[0])}
+
+    def site_model(self, lo: int = 0, hi: int | None = None) -> dict:
+        """dyn_aligner_site_model_fetch: the model rows of the sites [lo, hi) (default: all) as float64 arrays ``pi1``, ``mu0``,
+        ``mu1``, ``var0``, ``var1``; a row that is not set, and an id without a bucket in a sparse table, reads as zeros."""
+        lo, hi, n = self._site_window(lo, hi)
+        cols = [np.zeros(n, dtype=np.float64) for _ in SITE_MODEL_COLUMNS]
+        rc = self._L.dyn_aligner_site_model_fetch(self._h, lo, hi, *[_ptr(c, N.c_double_p) for c in cols])
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        return dict(zip(SITE_MODEL_COLUMNS, cols))
+
+    def reset_site_model(self) -> None:
+        rc = self._L.dyn_aligner_site_model_reset(self._h)
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+
+    def set_site_calls(self, on: bool) -> None:
+        """dyn_aligner_set_site_calls: align(calc_probabilities=True) jobs submitted while on also score every output row against
+        the per-site model (``set_site_model``) on the GPU: ``AlignBatchResult.site_z``, the row's event mean as a z-score under
+        the site's component 0, and ``site_probability``, the posterior probability of component 1 of the site's mixture
+        (INTEGRATION.md section 3); NaN where there is no call -- no id, no model row, a one-component row (``site_z`` alone).
+        Needs ``set_site_summary`` on and ``site_ids=`` with the job; jobs of any other kind are refused while it is on."""
+        rc = self._L.dyn_aligner_set_site_calls(self._h, 1 if on else 0)
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+        self._site_calls = bool(on)
 
     def set_band_margin(self, on: bool) -> None:
         """dyn_aligner_set_band_margin: align(calc_probabilities=True) jobs submitted while on also report, per read, how
@@ -1810,6 +1874,14 @@ class MultiAligner:
         device and add the counters (they are integers)."""
         raise NotImplementedError("MultiAligner has no per-site histograms (Aligner.set_site_histogram): use one Aligner per device "
                                   "and add their tables")
+
+    def set_site_model(self, lo: int, m: dict, accept=(0, 2)) -> dict:
+        """Not supported, as ``set_site_summary`` is not: the model lives beside ONE device's table."""
+        raise NotImplementedError("MultiAligner has no per-site model (Aligner.set_site_model): use one Aligner per device")
+
+    def set_site_calls(self, on: bool) -> None:
+        """Not supported, as ``set_site_summary`` is not."""
+        raise NotImplementedError("MultiAligner has no per-read site calls (Aligner.set_site_calls): use one Aligner per device")
 
     def site_summary_add(self, lo: int, summary: dict, histogram: dict | None = None) -> None:
         """Not supported, as ``set_site_summary`` is not."""

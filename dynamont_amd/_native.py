@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("DYN_LIB_PATH") or os.path.join(HERE, "libdynamont_mi.so")
 SOURCES = ["dynamont_mi.cpp", "site_table.cpp", "buffers.cpp", "launch.cpp", "session.cpp", "async_engine.cpp", "pore_model.cpp", "csv_format.cpp", "csv_sink.cpp", "vbz_decode.cpp", "bam_reader.cpp", "rccl_comm.cpp", "model_format.cpp",
            "nt_kernels.hip", "pool_stats.hip", "band_reads.hip", "event_stats.hip", "rescale.hip", "kmer_summary.hip", "site_summary.hip", "segment_scores.hip", "band_margin.hip", "guided_band.hip", "auto_guide.hip", "guide_rescue.hip"]
-HEADERS = ["engine.hpp", "engine_internal.hpp", "launch_plan.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "lattice_phase.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "dp_cell.hpp", "segment_kernels.hpp", "preprocess_kernels.hpp", "kmer_summary_kernels.hpp", "site_summary_kernels.hpp", "site_quantile_kernels.hpp", "site_compare_kernels.hpp", "site_mixture_kernels.hpp", "site_map.hpp", "site_map_kernels.hpp", "exact_sum_kernels.hpp", "segment_score_kernels.hpp", "border_kernels.hpp", "interval_kernels.hpp", "soft_level_kernels.hpp", "sample_kernels.hpp", "band_margin_kernels.hpp", "band_reads.hpp", "guided_band_kernels.hpp", "auto_guide_kernels.hpp", "guide_rescue_kernels.hpp", "band_runs.hpp", "lpe_liveness.hpp", "decision_record.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
+HEADERS = ["engine.hpp", "engine_internal.hpp", "launch_plan.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "lattice_phase.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "dp_cell.hpp", "segment_kernels.hpp", "preprocess_kernels.hpp", "kmer_summary_kernels.hpp", "site_summary_kernels.hpp", "site_quantile_kernels.hpp", "site_compare_kernels.hpp", "site_mixture_kernels.hpp", "site_call_kernels.hpp", "site_map.hpp", "site_map_kernels.hpp", "exact_sum_kernels.hpp", "segment_score_kernels.hpp", "border_kernels.hpp", "interval_kernels.hpp", "soft_level_kernels.hpp", "sample_kernels.hpp", "band_margin_kernels.hpp", "band_reads.hpp", "guided_band_kernels.hpp", "auto_guide_kernels.hpp", "guide_rescue_kernels.hpp", "band_runs.hpp", "lpe_liveness.hpp", "decision_record.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
 
 DYN_DEVICE_HOST_ONLY = -2
 DYN_CSV_EVENT_STATS = 0x1  # dyn_csv_sink_open_ex flag
@@ -27,6 +27,7 @@ DYN_CSV_POSTERIOR_SAMPLES = 0x10  # dyn_csv_sink_open_ex flag
 DYN_CSV_BORDER_INTERVAL = 0x40  # dyn_csv_sink_open_ex flag (bits 0x4 and 0x20 stay unassigned)
 DYN_BORDER_INTERVAL_MIN_MASS, DYN_BORDER_INTERVAL_MAX_MASS = 0.01, 0.999
 DYN_CSV_SOFT_LEVELS = 0x200  # dyn_csv_sink_open_ex flag (bits 0x4, 0x20, 0x80 and 0x100 stay unassigned)
+DYN_CSV_SITE_CALLS = 0x800  # dyn_csv_sink_open_ex flag (bits 0x4, 0x20, 0x80, 0x100 and 0x400 stay unassigned)
 DYN_POSTERIOR_SAMPLES_MAX = 64
 DYN_SAMPLE_DEAD = 0xFFFFFFFF  # dyn_sample_out: every entry of a dead sample
 DYN_BAND_MARGIN_NONE = 0xFFFFFFFF  # dyn_band_margin_out: the edge was never a real one
@@ -73,6 +74,10 @@ class DynBorderIntervalOut(C.Structure):
 
 class DynSoftLevelOut(C.Structure):
     _fields_ = [("weight", c_double_p), ("sum", c_double_p), ("sumsq", c_double_p), ("capacity", C.c_uint64)]
+
+
+class DynSiteCallOut(C.Structure):
+    _fields_ = [("site_probability", c_double_p), ("site_z", c_double_p), ("capacity", C.c_uint64)]
 
 
 class DynSampleOut(C.Structure):
@@ -177,6 +182,10 @@ SIGNATURES = {
                                            c_u32_p, c_i32_p]),
     "dyn_aligner_site_mixture": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_double, C.c_uint32] + [c_double_p] * 7 +
                                           [c_u32_p] * 6),
+    "dyn_aligner_set_site_model": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64] + [c_double_p] * 5 + [c_u64_p]),
+    "dyn_aligner_site_model_reset": (C.c_int, [C.c_void_p]),
+    "dyn_aligner_site_model_fetch": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64] + [c_double_p] * 5),
+    "dyn_aligner_set_site_calls": (C.c_int, [C.c_void_p, C.c_int]),
     "dyn_aligner_site_quantiles": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, c_double_p, C.c_int, c_u32_p, c_u32_p, c_u32_p, c_u32_p,
                                              c_u32_p]),
     "dyn_tie_rows": (C.c_uint32, [C.c_void_p, c_i32_p, C.c_uint64, C.c_uint64]),
@@ -236,6 +245,15 @@ SIGNATURES = {
                                       C.POINTER(DynBorderIntervalOut), C.POINTER(DynSoftLevelOut), C.c_char_p, c_u64_p,
                                       C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
                                       C.c_void_p, C.c_uint64, c_u64_p, c_u64_p]),
+    "dyn_format_csv_bound_calls": (C.c_uint64, [C.c_void_p, C.c_uint64, C.POINTER(DynAlignOut), C.POINTER(DynEventOut),
+                                                C.POINTER(DynScoreOut), C.POINTER(DynBorderOut), C.POINTER(DynSampleOut),
+                                                C.POINTER(DynBorderIntervalOut), C.POINTER(DynSoftLevelOut), C.POINTER(DynSiteCallOut),
+                                                C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]),
+    "dyn_format_csv_calls": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(DynAlignOut), C.POINTER(DynEventOut),
+                                       C.POINTER(DynScoreOut), C.POINTER(DynBorderOut), C.POINTER(DynSampleOut),
+                                       C.POINTER(DynBorderIntervalOut), C.POINTER(DynSoftLevelOut), C.POINTER(DynSiteCallOut), C.c_char_p, c_u64_p,
+                                       C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
+                                       C.c_void_p, C.c_uint64, c_u64_p, c_u64_p]),
     "dyn_csv_compact": (C.c_uint64, [C.c_void_p, C.c_uint64, c_u64_p, c_u64_p]),
     "dyn_csv_sink_open": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_uint64]),
     "dyn_csv_sink_open_part": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_uint64]),
@@ -272,6 +290,7 @@ SIGNATURES = {
     "dyn_batch_fetch_samples": (C.c_int, [C.c_void_p, C.POINTER(DynSampleOut)]),
     "dyn_batch_fetch_intervals": (C.c_int, [C.c_void_p, C.POINTER(DynBorderIntervalOut)]),
     "dyn_batch_fetch_soft_levels": (C.c_int, [C.c_void_p, C.POINTER(DynSoftLevelOut)]),
+    "dyn_batch_fetch_site_calls": (C.c_int, [C.c_void_p, C.POINTER(DynSiteCallOut)]),
     "dyn_batch_fetch_rescale": (C.c_int, [C.c_void_p, C.POINTER(DynRescaleOut)]),
     "dyn_batch_fetch_band_margin": (C.c_int, [C.c_void_p, C.POINTER(DynBandMarginOut)]),
     "dyn_batch_set_guide": (C.c_int, [C.c_void_p, c_i32_p, C.c_uint64, C.c_uint32]),

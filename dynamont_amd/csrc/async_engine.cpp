@@ -235,6 +235,15 @@ std::shared_ptr<BatchGroup> Pipeline::merge(const std::vector<dyn_batch*>& ticke
     if (!t->n) continue;
     if (t->want.kmer_summary) add_range(g->ks_ranges, t);
     if (t->want.band_margin) add_range(g->bm_ranges, t);
+    // the site calls are launch-wide (same_kind), the model each member scores against is its own snapshot; the table's bounds and
+    // map come with the first member (the setter waits for the jobs in flight before it replaces them: the members saw one table)
+    if (t->want.site_calls) {
+      g->sc_ranges.push_back(dyn_batch::SiteCallRange{(uint32_t)t->g_read0, (uint32_t)(t->g_read0 + t->n), t->ss_model});
+      if (!g->ss_num_sites) {
+        g->ss_num_sites = t->ss_num_sites;
+        g->ss_map = t->ss_map;
+      }
+    }
     if (any_sites && t->want.site_summary && t->in_site_ids) {
       add_range(g->ss_ranges, t);
       if (!g->ss_table) {  // (the setter waits for the jobs in flight before it replaces the table: the members saw one table)
@@ -784,6 +793,7 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
   uint64_t ss_num_sites = 0;
   SiteHist ss_hist;
   SiteMap ss_map;
+  const double* ss_model = nullptr;
   int staged_rc = DYN_OK;
   {
     std::lock_guard<std::mutex> lk(a->mu);
@@ -792,6 +802,7 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
     ss_num_sites = a->site.num_sites;
     ss_hist = a->site.hist_now(a->opt.site_histogram);
     ss_map = a->site.map_now();
+    ss_model = a->site.model.as<double>();
   }
   if (!ticket || !sig_offsets || !seq_offsets || (n_reads && ((!signals && !rs) || !seqs))) return DYN_ERR_INVALID_ARGUMENT;
   if (staged_rc != DYN_OK) return staged_rc;
@@ -845,6 +856,7 @@ int submit_common(dyn_aligner* a, uint64_t n_reads, const double* signals, const
   b->ss_num_sites = ss_num_sites;
   b->ss_hist = ss_hist;
   b->ss_map = ss_map;
+  b->ss_model = ss_model;
   b->in_signals = signals;
   if (rs) {
     b->has_raw = true;

@@ -102,6 +102,7 @@ struct Args {
   const dyn_sample_out* sm;  // nullptr: no posterior-sample column
   const dyn_border_interval_out* bi;  // nullptr: no border-interval columns
   const dyn_soft_level_out* sl;  // nullptr: no soft-level columns
+  const dyn_site_call_out* ca;   // nullptr: no site-call columns
   const char* seqs;
   const uint64_t* seq_offsets;
   const char* const* readids;
@@ -175,6 +176,11 @@ uint64_t read_bound(const Args& a, uint64_t i) {
       const SoftRow r = soft_row(a.sl, s);
       b += event_value_bound(r.dwell) + event_value_bound(r.mean) + event_value_bound(r.stdv);  // (a NaN takes the long bound)
     }
+  }
+  if (a.ca) {
+    const uint64_t o = a.res->seg_offsets[i];
+    b += 2 * n;  // the commas
+    for (uint64_t s = o; s < o + n; ++s) b += event_value_bound(a.ca->site_probability[s]) + event_value_bound(a.ca->site_z[s]);
   }
   return b;
 }
@@ -261,6 +267,12 @@ char* format_read(const Args& a, uint64_t i, char* p) {
       *p++ = ',';
       p = put_soft(p, r.stdv);
     }
+    if (a.ca) {  // (no call: "nan")
+      *p++ = ',';
+      p = put_soft(p, a.ca->site_probability[o + s]);
+      *p++ = ',';
+      p = put_soft(p, a.ca->site_z[o + s]);
+    }
     *p++ = '\n';
   }
   return p;
@@ -309,13 +321,22 @@ extern "C" uint64_t dyn_format_csv_bound_soft(const dyn_aligner* a, uint64_t n_r
                                               const dyn_sample_out* sm, const dyn_border_interval_out* bi,
                                               const dyn_soft_level_out* sl, const char* const* readids,
                                               const char* const* signalids) {
+  return dyn_format_csv_bound_calls(a, n_reads, res, ev, sc, bd, sm, bi, sl, nullptr, readids, signalids);
+}
+
+extern "C" uint64_t dyn_format_csv_bound_calls(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res,
+                                               const dyn_event_out* ev, const dyn_score_out* sc, const dyn_border_out* bd,
+                                               const dyn_sample_out* sm, const dyn_border_interval_out* bi,
+                                               const dyn_soft_level_out* sl, const dyn_site_call_out* ca,
+                                               const char* const* readids, const char* const* signalids) {
+  if (ca && (!ca->site_probability || !ca->site_z)) return 0;
   if (sl && (!sl->weight || !sl->sum || !sl->sumsq)) return 0;
   if (bi && (!bi->border_lo || !bi->border_hi || !bi->border_mean || !bi->border_sd)) return 0;
   if (!a || !res || (ev && (!ev->mean || !ev->stdev || !ev->median)) ||
       (sc && (!sc->median_delta || !sc->mad_delta || !sc->homogeneity)) ||
       (bd && (!bd->border_probability || !bd->border_window_probability)) || (sm && !sm->sample_start))
     return 0;
-  Args args{0, 0, res, ev, sc, bd, sm, bi, sl, nullptr, nullptr, readids, signalids, nullptr, nullptr};
+  Args args{0, 0, res, ev, sc, bd, sm, bi, sl, ca, nullptr, nullptr, readids, signalids, nullptr, nullptr};
   uint64_t total = 0;
   for (uint64_t i = 0; i < n_reads; ++i) total += read_bound(args, i);
   return total;
@@ -383,6 +404,17 @@ extern "C" int dyn_format_csv_soft(const dyn_aligner* a, uint64_t n_reads, const
                                    const uint64_t* seq_offsets, const char* const* readids, const char* const* signalids,
                                    const int64_t* sig_offsets, const int64_t* last_index, int threads, char* out,
                                    uint64_t out_cap, uint64_t* row_begin, uint64_t* row_end) {
+  return dyn_format_csv_calls(a, n_reads, res, ev, sc, bd, sm, bi, sl, nullptr, seqs, seq_offsets, readids, signalids, sig_offsets, last_index,
+                              threads, out, out_cap, row_begin, row_end);
+}
+
+extern "C" int dyn_format_csv_calls(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                                    const dyn_score_out* sc, const dyn_border_out* bd, const dyn_sample_out* sm,
+                                    const dyn_border_interval_out* bi, const dyn_soft_level_out* sl, const dyn_site_call_out* ca,
+                                    const char* seqs, const uint64_t* seq_offsets, const char* const* readids,
+                                    const char* const* signalids, const int64_t* sig_offsets, const int64_t* last_index, int threads,
+                                    char* out, uint64_t out_cap, uint64_t* row_begin, uint64_t* row_end) {
+  if (ca && (!ca->site_probability || !ca->site_z)) return DYN_ERR_INVALID_ARGUMENT;
   if (sl && (!sl->weight || !sl->sum || !sl->sumsq)) return DYN_ERR_INVALID_ARGUMENT;
   if (bi && (!bi->border_lo || !bi->border_hi || !bi->border_mean || !bi->border_sd)) return DYN_ERR_INVALID_ARGUMENT;
   if (sm && !sm->sample_start) return DYN_ERR_INVALID_ARGUMENT;
@@ -394,7 +426,7 @@ extern "C" int dyn_format_csv_soft(const dyn_aligner* a, uint64_t n_reads, const
   dyn_info info;
   dyn_aligner_info(a, &info);
   if (info.kmer_size > 31) return DYN_ERR_INVALID_ARGUMENT;
-  Args args{info.kmer_size, info.rna, res, ev, sc, bd, sm, bi, sl, seqs, seq_offsets, readids, signalids, sig_offsets, last_index};
+  Args args{info.kmer_size, info.rna, res, ev, sc, bd, sm, bi, sl, ca, seqs, seq_offsets, readids, signalids, sig_offsets, last_index};
   // every read formats straight into its own worst-case slot of the caller's buffer: no allocation,
   // no shared cache lines between threads
   uint64_t pos = 0;

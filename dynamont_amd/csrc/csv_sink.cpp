@@ -47,6 +47,7 @@ const char kHeaderBorders[] = ",border_probability,border_window_probability";
 const char kHeaderSamples[] = ",sample_starts";
 const char kHeaderIntervals[] = ",border_lo,border_hi,border_mean,border_sd";
 const char kHeaderSoft[] = ",soft_dwell,soft_mean,soft_stdv";
+const char kHeaderCalls[] = ",site_probability,site_z";
 
 struct Blob {  // the formatted rows of one batch; freed when its last job has been compressed
   std::unique_ptr<char[]> data;
@@ -118,6 +119,8 @@ struct dyn_csv_sink {
   std::vector<double> bi_cols;                // [2][capacity] f64 mean / sd, then [2][capacity] u32 lo / hi (dyn_batch_fetch_intervals)
   bool soft = false;                          // DYN_CSV_SOFT_LEVELS
   std::vector<double> sl_cols;                // [3][capacity] the batch's weight / sum / sumsq (dyn_batch_fetch_soft_levels)
+  bool calls = false;                         // DYN_CSV_SITE_CALLS
+  std::vector<double> ca_cols;                // [2][capacity] the batch's site_probability / site_z (dyn_batch_fetch_site_calls)
   std::thread t_sink, t_writer;
   std::vector<std::thread> t_comp;
   std::vector<std::shared_ptr<Blob>> spare;  // recycled row buffers (first-touch page faults cost more than formatting)
@@ -324,13 +327,20 @@ struct dyn_csv_sink {
           return dyn_batch_fetch_soft_levels(it.ticket, &sl);
         }, "batch soft levels: "))
       return;
+    dyn_site_call_out ca{};
+    if (calls && !fetch(ca_cols, 2 * cap, [&] {
+          ca = dyn_site_call_out{ca_cols.data(), ca_cols.data() + cap, cap};
+          return dyn_batch_fetch_site_calls(it.ticket, &ca);
+        }, "batch site calls: "))
+      return;
     const dyn_event_out* evp = events ? &ev : nullptr;
     const dyn_score_out* scp = scores ? &sc : nullptr;
     const dyn_border_out* bdp = borders ? &bd : nullptr;
     const dyn_sample_out* smp = samples ? &sm : nullptr;
     const dyn_border_interval_out* bip = intervals ? &bi : nullptr;
     const dyn_soft_level_out* slp = soft ? &sl : nullptr;
-    const uint64_t bound = dyn_format_csv_bound_soft(it.a, it.n, it.res, evp, scp, bdp, smp, bip, slp, it.readids, it.signalids);
+    const dyn_site_call_out* cap_ca = calls ? &ca : nullptr;
+    const uint64_t bound = dyn_format_csv_bound_calls(it.a, it.n, it.res, evp, scp, bdp, smp, bip, slp, cap_ca, it.readids, it.signalids);
     std::shared_ptr<Blob> blob;
     {
       std::lock_guard<std::mutex> lk(m);
@@ -348,7 +358,7 @@ struct dyn_csv_sink {
       if (spare.size() < 4) spare.push_back(blob);
     }
     const double c2 = now_ms();
-    const int frc = dyn_format_csv_soft(it.a, it.n, it.res, evp, scp, bdp, smp, bip, slp, it.seqs, it.seq_offsets, it.readids, it.signalids, it.sig_offsets,
+    const int frc = dyn_format_csv_calls(it.a, it.n, it.res, evp, scp, bdp, smp, bip, slp, cap_ca, it.seqs, it.seq_offsets, it.readids, it.signalids, it.sig_offsets,
                                           last_index.data(), std::min(threads, 8), blob->data.get(), blob->cap, begin.data(), end.data());
     if (frc != DYN_OK) {
       std::lock_guard<std::mutex> lk(m);
@@ -397,6 +407,7 @@ struct dyn_csv_sink {
       if (samples) text.insert(text.size() - 1, kHeaderSamples);
       if (intervals) text.insert(text.size() - 1, kHeaderIntervals);
       if (soft) text.insert(text.size() - 1, kHeaderSoft);
+      if (calls) text.insert(text.size() - 1, kHeaderCalls);
       const size_t len = text.size();
       hdr->cap = len + 1;
       hdr->data.reset(new char[hdr->cap]);
@@ -456,7 +467,7 @@ int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int 
   };
   if (!csv_zst_path || !errors_path || !out) return DYN_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  if (flags & ~(DYN_CSV_EVENT_STATS | DYN_CSV_SEGMENT_SCORES | DYN_CSV_BORDER_CONFIDENCE | DYN_CSV_POSTERIOR_SAMPLES | DYN_CSV_BORDER_INTERVAL | DYN_CSV_SOFT_LEVELS)) {
+  if (flags & ~(DYN_CSV_EVENT_STATS | DYN_CSV_SEGMENT_SCORES | DYN_CSV_BORDER_CONFIDENCE | DYN_CSV_POSTERIOR_SAMPLES | DYN_CSV_BORDER_INTERVAL | DYN_CSV_SOFT_LEVELS | DYN_CSV_SITE_CALLS)) {
     put("dyn_csv_sink_open_ex: unknown flags");
     return DYN_ERR_INVALID_ARGUMENT;
   }
@@ -483,6 +494,7 @@ int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int 
   s->samples = (flags & DYN_CSV_POSTERIOR_SAMPLES) != 0;
   s->intervals = (flags & DYN_CSV_BORDER_INTERVAL) != 0;
   s->soft = (flags & DYN_CSV_SOFT_LEVELS) != 0;
+  s->calls = (flags & DYN_CSV_SITE_CALLS) != 0;
   dyn_csv_sink* p = s.release();
   for (int t = 0; t < p->threads; ++t) p->t_comp.emplace_back([p] { p->compress_loop(); });
   p->t_writer = std::thread([p] { p->writer_loop(); });
@@ -508,7 +520,8 @@ int dyn_csv_sink_submit_bases(dyn_csv_sink* s, dyn_aligner* a, dyn_batch* ticket
                                                {s->borders, DYN_CSV_BORDER_CONFIDENCE},
                                                {s->samples, DYN_CSV_POSTERIOR_SAMPLES},
                                                {s->intervals, DYN_CSV_BORDER_INTERVAL},
-                                               {s->soft, DYN_CSV_SOFT_LEVELS}};
+                                               {s->soft, DYN_CSV_SOFT_LEVELS},
+                                               {s->calls, DYN_CSV_SITE_CALLS}};
   for (const auto& w : written)
     if (w.first)
       if (int rc = dyneng::batch_check_output(ticket, w.second)) return rc;  // the message is the handle's (dyn_aligner_last_error)

@@ -600,6 +600,12 @@ int dyn_aligner_set_soft_levels(dyn_aligner* a, int on) {
   return DYN_OK;
 }
 
+int dyn_aligner_set_site_calls(dyn_aligner* a, int on) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  a->opt.site_calls = on != 0;
+  return DYN_OK;
+}
+
 int dyn_aligner_set_posterior_samples(dyn_aligner* a, int count, uint64_t seed) {
   if (!a) return DYN_ERR_INVALID_ARGUMENT;
   auto fail = [&](const std::string& msg) {
@@ -1228,6 +1234,15 @@ int resolve_job_options(dyn_aligner* a, DynJob job, bool ticket, bool guided, co
     a->last_error = msg;
     return DYN_ERR_INVALID_ARGUMENT;
   }
+  // the site calls score the rows of an align(calc = 1) job against the model beside the per-site table: no other job has rows,
+  // and without the table's switch the job carries no ids
+  if (w.site_calls && (job != DynJob::AlignFull || !w.site_summary)) {
+    std::lock_guard<std::mutex> elk(a->err_mu);
+    a->last_error = std::string(api) + (job != DynJob::AlignFull
+                                            ? ": dyn_aligner_set_site_calls is on, which scores the rows of align(calc_probabilities = 1) jobs alone"
+                                            : ": dyn_aligner_set_site_calls is on, which needs dyn_aligner_set_site_summary(a, num_sites > 0)");
+    return DYN_ERR_INVALID_ARGUMENT;
+  }
   if (!ticket) w.auto_guide_hw = 0;  // (a synchronous batch makes its guide through dyn_batch_auto_guide)
   *out = w;
   return DYN_OK;
@@ -1284,6 +1299,7 @@ int run_job_sync(dyn_batch* b, DynJob job, bool guided_train = false) {
     b->ss_num_sites = a->site.num_sites;
     b->ss_hist = a->site.hist_now(a->opt.site_histogram);
     b->ss_map = a->site.map_now();
+    b->ss_model = a->site.model.as<double>();
     rc = enqueue_job(b, job);
     if (rc != DYN_OK) {
       (void)hipStreamSynchronize(a->stream);
@@ -1543,6 +1559,8 @@ const OutputDesc OUTPUTS[OUT_COUNT] = {
      "the border intervals (DYN_CSV_BORDER_INTERVAL)"},
     {24, "dyn_batch_fetch_soft_levels", "dyn_soft_level_out", "dyn_aligner_set_soft_levels(a, 1)", DYN_CSV_SOFT_LEVELS,
      "the soft levels (DYN_CSV_SOFT_LEVELS)"},
+    {16, "dyn_batch_fetch_site_calls", "dyn_site_call_out", "dyn_aligner_set_site_calls(a, 1)", DYN_CSV_SITE_CALLS,
+     "the site calls (DYN_CSV_SITE_CALLS)"},
     {4, "dyn_batch_fetch_samples", "dyn_sample_out", "dyn_aligner_set_posterior_samples(a, count > 0)", DYN_CSV_POSTERIOR_SAMPLES,
      "the posterior samples (DYN_CSV_POSTERIOR_SAMPLES)"},
 };
@@ -1554,6 +1572,7 @@ int output_wanted(const JobOptions& w, Output k) {
     case OUT_BORDERS: return w.border_confidence ? 1 : 0;
     case OUT_INTERVALS: return w.border_interval > 0 ? 1 : 0;
     case OUT_SOFT: return w.soft_levels ? 1 : 0;
+    case OUT_SITE_CALLS: return w.site_calls ? 1 : 0;
     default: return w.posterior_samples;
   }
 }
@@ -1658,6 +1677,18 @@ int dyn_batch_fetch_soft_levels(dyn_batch* b, dyn_soft_level_out* out) {
   HIP_TRY(a, copy_out(a, out->weight, e, b->capacity * 8));
   HIP_TRY(a, copy_out(a, out->sum, e + f.src->capacity, b->capacity * 8));
   HIP_TRY(a, copy_out(a, out->sumsq, e + 2 * f.src->capacity, b->capacity * 8));
+  return DYN_OK;
+}
+
+int dyn_batch_fetch_site_calls(dyn_batch* b, dyn_site_call_out* out) {
+  if (!b || !out || !out->site_probability || !out->site_z) return DYN_ERR_INVALID_ARGUMENT;
+  dyn_aligner* a = b->a;
+  FetchSrc f;
+  const int rc = fetch_prologue(b, OUT_SITE_CALLS, out->capacity, &f);
+  if (rc != DYN_OK || !b->capacity) return rc;
+  const double* e = f.src->out[OUT_SITE_CALLS].d.as<double>() + f.seg0;
+  HIP_TRY(a, copy_out(a, out->site_probability, e, b->capacity * 8));
+  HIP_TRY(a, copy_out(a, out->site_z, e + f.src->capacity, b->capacity * 8));
   return DYN_OK;
 }
 

@@ -143,20 +143,21 @@ struct JobOptions {
   int border_confidence = 0;    // dyn_aligner_set_border_confidence (window, 0 = off)
   double border_interval = 0;   // dyn_aligner_set_border_interval (mass, 0 = off)
   bool soft_levels = false;     // dyn_aligner_set_soft_levels
+  bool site_calls = false;      // dyn_aligner_set_site_calls; needs site_summary
   int posterior_samples = 0;    // dyn_aligner_set_posterior_samples (count, 0 = off)
   uint64_t sample_seed = 0;     // ... and its seed
   uint32_t auto_guide_hw = 0, auto_guide_rounds = 8;               // dyn_aligner_set_auto_guide (half width, 0 = off; alignments per read)
   uint32_t rescue_margin = 0, rescue_hw = 0, rescue_rounds = 8;    // dyn_aligner_set_guide_rescue (minimum margin; half width, 0 = off; alignments)
   // May tickets x and y share ONE launch (Pipeline::merge)? Three kinds of fields:
-  //   launch-wide: event_stats, rescale_iters, segment_scores, border_confidence, border_interval, soft_levels -- one value per launch, so the
-  //                members must agree; the launch's batch takes them from its first member
+  //   launch-wide: event_stats, rescale_iters, segment_scores, border_confidence, border_interval, soft_levels, site_calls -- one value per
+  //                launch, so the members must agree; the launch's batch takes them from its first member
   //   per-ticket:  kmer_summary, site_summary, site_histogram, band_margin -- not compared: the launch's batch lists the read ranges of the members that asked
   //   alone:       posterior_samples (the read's index in its OWN ticket keys the random stream), auto_guide_hw (a guide of its own
   //                and the banded-lattice kernel), rescue_hw (its list of reads to re-align is its own) -- such a ticket never merges
   bool merges() const { return posterior_samples == 0 && auto_guide_hw == 0 && rescue_hw == 0; }
   bool same_launch(const JobOptions& y) const {
     return event_stats == y.event_stats && rescale_iters == y.rescale_iters && segment_scores == y.segment_scores &&
-           border_confidence == y.border_confidence && border_interval == y.border_interval && soft_levels == y.soft_levels;
+           border_confidence == y.border_confidence && border_interval == y.border_interval && soft_levels == y.soft_levels && site_calls == y.site_calls;
   }
   // the launch-wide part alone: what the batch of a merged launch runs under
   JobOptions launch_wide() const {
@@ -167,6 +168,7 @@ struct JobOptions {
     g.border_confidence = border_confidence;
     g.border_interval = border_interval;
     g.soft_levels = soft_levels;
+    g.site_calls = site_calls;
     return g;
   }
 };
@@ -195,6 +197,10 @@ struct SiteTable {
   DevBuf keys;
   uint64_t capacity = 0;
   DevBuf gather;
+  // the per-site model beside the table (dyn_aligner_set_site_model, site_call_kernels.hpp): [rows()][5] f64 pi1, mu0, mu1, var0, var1,
+  // allocated and zeroed by the first upload, released with the table; a job snapshots the pointer at its submission. model_stage:
+  // one window's staged rows per call (and, behind them, the counter of a sparse upload's dropped rows)
+  DevBuf model, model_stage;
   // the per-site histograms beside the table: [rows()][bins + 2 + 16] u32, allocated and zeroed by dyn_aligner_set_site_histogram(a,
   // bins > 0, lo, hi), kept (bins = 0 only stops the counting) until that setter names other parameters or the table another size
   DevBuf hist;
@@ -244,7 +250,7 @@ struct SiteTable {
     return m;
   }
   // what dyn_aligner_set_mem_budget counts against the table: itself, its histograms, a sparse table's map and gather scratch
-  uint64_t held_bytes() const { return table.bytes + hist.bytes + keys.bytes + gather.bytes; }
+  uint64_t held_bytes() const { return table.bytes + hist.bytes + keys.bytes + gather.bytes + model.bytes; }
   // the occupancy bitmap of dyn_aligner_site_map_windows lives in the quantiles' staging: every window call runs under the
   // handle's lock on s_get, so no two of them use it at once
   DevBuf& window_bitmap() { return quant; }
@@ -257,23 +263,25 @@ struct SiteTable {
     table.release();
     keys.release();
     gather.release();
+    model.release();
     num_sites = 0;
     capacity = 0;
     release_hist();
   }
   void release() {
     release_table();
-    for (DevBuf* d : {&quant, &comp, &mix, &add}) d->release();
+    for (DevBuf* d : {&quant, &comp, &mix, &add, &model_stage}) d->release();
   }
 };
 
 // ---- the per-segment outputs a job may add to its rows (one fetcher, one out-struct and one CSV flag each) ---------------------
-enum Output { OUT_LEVELS, OUT_SCORES, OUT_BORDERS, OUT_INTERVALS, OUT_SOFT, OUT_SAMPLES, OUT_COUNT };
+enum Output { OUT_LEVELS, OUT_SCORES, OUT_BORDERS, OUT_INTERVALS, OUT_SOFT, OUT_SITE_CALLS, OUT_SAMPLES, OUT_COUNT };
 struct OutputBuf {
   DevBuf d;       // OUT_LEVELS [3][capacity] f64 mean / stdev / median (event_stats.hip); OUT_SCORES [4][capacity] f64 median_delta /
                   // mad_delta / homogeneity / scratch (segment_scores.hip); OUT_BORDERS [2][capacity] f64 (border_kernels.hpp);
                   // OUT_INTERVALS [2][capacity] f64 mean / sd, then [2][capacity] u32 lo / hi (interval_kernels.hpp); OUT_SOFT [3][capacity] f64
-                  // weight / sum / sumsq (soft_level_kernels.hpp); OUT_SAMPLES
+                  // weight / sum / sumsq (soft_level_kernels.hpp); OUT_SITE_CALLS [2][capacity] f64 site_probability / site_z
+                  // (site_call_kernels.hpp); OUT_SAMPLES
                   // [count][capacity] u32 sample starts, then [n] u32 dead samples (sample_kernels.hpp)
   int ready = 0;  // the last job computed the columns into d (OUT_SAMPLES: the count it sampled)
 };
@@ -434,6 +442,13 @@ struct dyn_batch {
   unsigned long long* ss_table = nullptr;
   uint64_t ss_num_sites = 0;
   dyneng::SiteMap ss_map;  // the map of a sparse table as it stood at submission (keys == nullptr: dense)
+  const double* ss_model = nullptr;  // the per-site model as it stood at submission (nullptr: none uploaded; want.site_calls reads it)
+  // the site calls of a merged launch (want.site_calls is launch-wide): every member's read range with the model IT snapshot
+  struct SiteCallRange {
+    uint32_t lo, hi;
+    const double* model;
+  };
+  std::vector<SiteCallRange> sc_ranges;
   std::vector<std::pair<uint32_t, uint32_t>> ss_ranges;
   // the per-site histograms as they stood at submission (p == nullptr: off). A merged launch splits ss_ranges into the members
   // submitted with the histograms on (sh_ranges) and the others (ss_plain_ranges)
@@ -590,6 +605,9 @@ int session_recover(dyn_batch* b, bool* republished);
 std::vector<dynk::KmerSummary> kmer_summary_args(const dyn_batch* b);
 // the same for the per-site summary (empty: none asked, or none of those that asked staged ids)
 std::vector<dynk::SiteSummary> site_summary_args(const dyn_batch* b);
+// the same for the site calls (b->out[OUT_SITE_CALLS] must be ready; empty: not asked for). A batch without ids, or a merged launch's
+// members without, get the NaN columns: one entry with sites == nullptr covers them
+std::vector<dynk::SiteCalls> site_call_args(const dyn_batch* b);
 // the same for the band margins (b->d_bm must hold 3 * n uint32: band_margin_prepare)
 std::vector<dynk::BandMargin> band_margin_args(const dyn_batch* b);
 // ---- the launch path's shared steps (launch.cpp; the host-only rules behind them: launch_plan.hpp) ----

@@ -314,6 +314,34 @@ std::vector<dynk::SiteSummary> site_summary_args(const dyn_batch* b) {
   return out;
 }
 
+std::vector<dynk::SiteCalls> site_call_args(const dyn_batch* b) {
+  if (!b->out[OUT_SITE_CALLS].ready || !b->n || !b->capacity) return {};
+  const dyn_aligner* a = b->a;
+  double* cols = b->out[OUT_SITE_CALLS].d.as<double>();  // [site_probability | site_z] x capacity
+  dynk::SiteCalls sc{};
+  sc.sig = b->d_sig.as<double>();
+  sc.sites = (b->has_sites && b->d_sites.p) ? b->d_sites.as<uint32_t>() : nullptr;  // no ids staged: every row the NaN
+  sc.model = b->ss_model;
+  sc.map_keys = b->ss_map.keys;
+  sc.capacity = (uint32_t)b->ss_map.capacity;
+  sc.num_sites = (uint32_t)b->ss_num_sites;
+  sc.read_lo = 0u;
+  sc.read_hi = (uint32_t)b->n;
+  sc.exp_tab = reinterpret_cast<const uint64_t*>(a->d_sptab.as<dynmath::SoftplusNode>() + dynmath::SP_NODES + dynmath::EXP128_NODES);
+  sc.prob = cols;
+  sc.z = cols + b->capacity;
+  if (b->sc_ranges.empty()) return {sc};
+  std::vector<dynk::SiteCalls> out;  // a merged launch: every member against the model it snapshot
+  for (const dyn_batch::SiteCallRange& r : b->sc_ranges) {
+    sc.read_lo = r.lo;
+    sc.read_hi = r.hi;
+    sc.model = r.model;
+    if (!out.empty() && out.back().model == r.model && out.back().read_hi == r.lo) out.back().read_hi = r.hi;
+    else out.push_back(sc);
+  }
+  return out;
+}
+
 std::vector<dynk::BandMargin> band_margin_args(const dyn_batch* b) {
   if (!b->bm_ready || !b->n) return {};
   uint32_t* m = b->d_bm.as<uint32_t>();
@@ -373,6 +401,8 @@ void enqueue_riders(dyn_batch* b, const ReadDesc* descs, int n, uint64_t rows_to
                         scc, (bm.empty() || margins != Margins::Diagonal) ? dynk::BandMargin{} : bm[0]);
   for (size_t k = 1; k < ks.size(); ++k) dynk::launch_kmer_summary(descs, n, max_N, st, tb, ks[k], s);
   for (const dynk::SiteSummary& ss : site_summary_args(b)) dynk::launch_site_summary(descs, n, max_N, st, tb, ss, s);
+  // (behind the summary: a sparse map's buckets are only looked up here, and the model's ids have theirs since the upload)
+  for (const dynk::SiteCalls& sc : site_call_args(b)) dynk::launch_site_calls(descs, n, max_N, st, tb, sc, s);
   if (margins == Margins::Diagonal)
     for (size_t k = 1; k < bm.size(); ++k) dynk::launch_band_margin(descs, n, max_N, st, tb, bm[k], s);
   if (margins == Margins::Guided)
@@ -1002,7 +1032,7 @@ int enqueue_job(dyn_batch* b, DynJob job) {
     if (int rc = run_rescue(b, L, q)) return rc;
     b->gr_ready = true;
   }
-  for (Output k : {OUT_LEVELS, OUT_SCORES})
+  for (Output k : {OUT_LEVELS, OUT_SCORES, OUT_SITE_CALLS})
     if (int rc = output_prepare(b, k, L.calc ? output_wanted(b->want, k) : 0, a->stream)) return rc;
   // (under the guide rescue the margins were taken by its stage, in front of the selection: such a job is never a merged launch;
   //  a guided batch's are taken against its own window)

@@ -420,6 +420,44 @@ struct SiteWindows {
   unsigned int* bitmap;             // [ceil(((num_sites - 1) >> shift) + 1, 32)] uint32, zeroed by the caller
 };
 void launch_site_map_windows(const SiteWindows& sw, hipStream_t s);
+// per-read site calls (site_call_kernels.hpp, dyn_aligner_set_site_calls): every output row scored against the per-site model of
+// dyn_aligner_set_site_model; prob == nullptr: not asked for
+constexpr int SC_MODEL_FIELDS = 5;  // per table row: pi1, mu0, mu1, var0, var1 (all zero: not set)
+struct SiteCalls {
+  const double* sig;          // the signal the read queue aligned (ReadDesc::sig_off counts from here)
+  const uint32_t* sites;      // site id of every output row (ReadDesc::par_off counts from here); nullptr: none staged, every row the NaN
+  const double* model;        // [num_sites][5], sparse [capacity][5]; nullptr: none uploaded, every row the NaN
+  const uint32_t* map_keys;   // the map of a sparse table (only ever read); nullptr: dense, the id is the row
+  uint32_t capacity;
+  uint32_t num_sites;
+  uint32_t read_lo, read_hi;  // the reads [read_lo, read_hi) (ReadDesc::read) are written
+  const uint64_t* exp_tab;    // dynmath::strict_exp_table on the device
+  double* prob;               // the two columns, indexed like the output rows (ReadDesc::seg_off + j)
+  double* z;
+};
+void launch_site_calls(const ReadDesc* descs, int n_reads, uint32_t max_N, const ReadState* st, const TraceBuffers& tb,
+                       const SiteCalls& sc, hipStream_t s);
+// k_site_model_scatter: a staged window of model rows into the rows of the ids [lo, lo + count) of a sparse table; a set row finds
+// or inserts its bucket (one without a bucket counts in *dropped), a row that is not set inserts nothing
+struct SiteModelScatter {
+  uint32_t* keys;
+  uint32_t capacity;
+  unsigned long long* stats;        // [3] n_keys, rows_dropped, sites_dropped (n_keys moves with an insert)
+  double* model;                    // [capacity][5]
+  const double* rows;               // staged [count][5]
+  uint32_t lo, count;
+  unsigned long long* dropped;      // one counter of this call
+};
+void launch_site_model_scatter(const SiteModelScatter& ms, hipStream_t s);
+// k_site_model_gather: the model rows of the ids [lo, lo + count) of a sparse table into a dense scratch; an absent id gets zeros
+struct SiteModelGather {
+  const uint32_t* keys;
+  uint32_t capacity;
+  const double* model;              // [capacity][5]
+  uint32_t lo, count;
+  double* out;                      // [count][5]
+};
+void launch_site_model_gather(const SiteModelGather& mg, hipStream_t s);
 // per-border segment quality scores (segment_scores.hip, dyn_aligner_set_segment_scores): columns indexed like the output
 // rows, zeroed by the caller; median_delta == nullptr: not asked for
 struct ScoreCols {

@@ -358,7 +358,7 @@ int session_publish(dyn_batch* b) {
   HIP_TRY(a, b->d_medhi.ensure(std::max<uint64_t>(8, b->capacity * 8)));
   HIP_TRY(a, b->d_medlo.ensure(std::max<uint64_t>(8, b->capacity * 8)));
   // (the columns are zeroed and filled by session_finish_enqueue, behind the per-segment kernels)
-  for (Output k : {OUT_LEVELS, OUT_SCORES})
+  for (Output k : {OUT_LEVELS, OUT_SCORES, OUT_SITE_CALLS})
     if (int rc = output_ensure(b, k, output_wanted(b->want, k))) return rc;
   if (int rc = band_margin_prepare(b, true)) return rc;  // filled by session_finish_enqueue as well
   const ReadState* st = init_read_state(b, false);  // (session_candidate: not a handle in mode ntk)
@@ -489,7 +489,7 @@ int session_finish_enqueue(dyn_batch* b, hipStream_t s) {
   HIP_TRY(a, hipEventRecord(ev[1], s));
   dynk::TraceBuffers tb{b->d_pp.as<double>(), b->d_pathn.as<uint32_t>(), b->d_segrow.as<uint32_t>(), b->d_medhi.as<double>(),
                         b->d_medlo.as<double>()};
-  for (Output k : {OUT_LEVELS, OUT_SCORES})
+  for (Output k : {OUT_LEVELS, OUT_SCORES, OUT_SITE_CALLS})
     if (int rc = output_zero(b, k, s)) return rc;
   enqueue_riders(b, b->d_descs.as<ReadDesc>(), (int)b->sess_reads, b->sess_rows_total, b->sess_max_N, b->d_state.as<ReadState>(), tb, s,
                  Margins::Diagonal);

@@ -1,6 +1,7 @@
 // site_summary.hip -- per-site level summary of a run (dyn_aligner_set_site_summary): coverage, dwell and the sums of the
 // reads' event means per caller-supplied site id, accumulated on the handle as exact integers while the switch is on. The
 // kernels and the definition are in site_summary_kernels.hpp (shared with tests/device_math/site_summary.hip).
+#include "site_call_kernels.hpp"
 #include "site_compare_kernels.hpp"
 #include "site_map_kernels.hpp"
 #include "site_mixture_kernels.hpp"
@@ -31,5 +32,14 @@ void launch_site_add(const SiteAdd& sa, hipStream_t s) { launch_site_add_kernel(
 void launch_site_gather(const SiteGather& sg, hipStream_t s) { launch_site_gather_kernel(sg, s); }
 void launch_site_scatter_add(const SiteScatter& sc, hipStream_t s) { launch_site_scatter_add_kernel(sc, s); }
 void launch_site_map_windows(const SiteWindows& sw, hipStream_t s) { launch_site_map_windows_kernel(sw, s); }
+
+// dyn_aligner_set_site_calls: the rows of the reads [read_lo, read_hi) scored against the per-site model (site_call_kernels.hpp),
+// and the model's two window calls on a sparse table
+void launch_site_calls(const ReadDesc* descs, int n_reads, uint32_t max_N, const ReadState* st, const TraceBuffers& tb,
+                       const SiteCalls& sc, hipStream_t s) {
+  launch_site_call_kernels(descs, n_reads, max_N, st, tb.segrow, sc, s);
+}
+void launch_site_model_scatter(const SiteModelScatter& ms, hipStream_t s) { launch_site_model_scatter_kernel(ms, s); }
+void launch_site_model_gather(const SiteModelGather& mg, hipStream_t s) { launch_site_model_gather_kernel(mg, s); }
 
 }  // namespace dynk

@@ -584,6 +584,95 @@ int dyn_aligner_site_mixture(dyn_aligner* a, uint64_t site_lo, uint64_t site_hi,
   return DYN_OK;
 }
 
+// ---- the per-site model beside the table and its window calls (site_call_kernels.hpp) ---------------------------------------------
+int dyn_aligner_set_site_model(dyn_aligner* a, uint64_t site_lo, uint64_t count, const double* pi1, const double* mu0, const double* mu1,
+                               const double* var0, const double* var1, uint64_t* dropped) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  const char* who = "dyn_aligner_set_site_model";
+  const double* cols[5] = {pi1, mu0, mu1, var0, var1};
+  if (count)
+    for (const double* c : cols)
+      if (!c) return DYN_ERR_INVALID_ARGUMENT;
+  if (dropped) *dropped = 0;
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = site_summary_quiet(a, who)) return rc;
+  SiteTable& t = a->site;
+  if (!a->opt.site_summary) return fail(a, who, "dyn_aligner_set_site_summary(a, num_sites > 0) is off on this handle");
+  if (site_lo > t.num_sites || count > t.num_sites - site_lo) return fail(a, who, no_range(a, site_lo, site_lo + count));
+  if (count == 0) return DYN_OK;
+  const uint64_t F = (uint64_t)dynk::SC_MODEL_FIELDS;
+  if (!t.model.p) {  // the first upload: one row per table row, zeroed -- no row is set
+    const uint64_t bytes = t.rows() * F * sizeof(double);
+    const std::string what = "the site model of " + std::to_string(t.rows()) + (t.sparse() ? " rows (" : " sites (") + std::to_string(bytes) + " bytes)";
+    if (int rc = alloc_zeroed(a, who, what, "does not fit", {{&t.model, bytes, 0}})) return rc;
+  }
+  const Windows win(site_lo, count);
+  HIP_TRY(a, t.model_stage.ensure(win.most * F * sizeof(double) + sizeof(uint64_t)));
+  unsigned long long* d_dropped = reinterpret_cast<unsigned long long*>(t.model_stage.as<double>() + win.most * F);
+  HIP_TRY(a, hipMemsetAsync(d_dropped, 0, sizeof(uint64_t), a->s_get));
+  std::vector<double> h(F * win.most);
+  for (auto [s0, cnt, o] : win) {
+    for (uint64_t c = 0; c < cnt; ++c)
+      for (uint64_t f = 0; f < F; ++f) h[F * c + f] = cols[f][o + c];
+    if (t.sparse()) {  // staged, then scattered into the rows of the window's ids
+      HIP_TRY(a, hipMemcpyAsync(t.model_stage.p, h.data(), F * cnt * sizeof(double), hipMemcpyHostToDevice, a->s_get));
+      dynk::SiteModelScatter ms{t.keys.as<uint32_t>(), (uint32_t)t.capacity, t.totals() + dynk::SS_TOTALS, t.model.as<double>(),
+                                t.model_stage.as<double>(), (uint32_t)s0, (uint32_t)cnt, d_dropped};
+      dynk::launch_site_model_scatter(ms, a->s_get);
+      HIP_TRY(a, hipGetLastError());
+    } else {
+      HIP_TRY(a, hipMemcpyAsync(t.model.as<double>() + F * s0, h.data(), F * cnt * sizeof(double), hipMemcpyHostToDevice, a->s_get));
+    }
+    HIP_TRY(a, hipStreamSynchronize(a->s_get));  // (the host vector is filled again for the next window)
+  }
+  if (t.sparse() && dropped) HIP_TRY(a, copy_out(a, dropped, d_dropped, sizeof(uint64_t)));
+  return DYN_OK;
+}
+
+int dyn_aligner_site_model_reset(dyn_aligner* a) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = site_summary_quiet(a, "dyn_aligner_site_model_reset")) return rc;
+  SiteTable& t = a->site;
+  if (!t.model.p) return DYN_OK;
+  HIP_TRY(a, hipMemsetAsync(t.model.p, 0, t.rows() * dynk::SC_MODEL_FIELDS * sizeof(double), a->s_get));  // (a sparse map keeps its keys)
+  HIP_TRY(a, hipStreamSynchronize(a->s_get));
+  return DYN_OK;
+}
+
+int dyn_aligner_site_model_fetch(dyn_aligner* a, uint64_t lo, uint64_t hi, double* pi1, double* mu0, double* mu1, double* var0, double* var1) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  double* cols[5] = {pi1, mu0, mu1, var0, var1};
+  if (lo < hi)
+    for (double* c : cols)
+      if (!c) return DYN_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = site_range_quiet(a, "dyn_aligner_site_model_fetch", lo, hi)) return rc;
+  SiteTable& t = a->site;
+  const uint64_t F = (uint64_t)dynk::SC_MODEL_FIELDS;
+  if (!t.model.p) {  // never uploaded: no row is set
+    for (double* c : cols)
+      if (lo < hi) std::fill(c, c + (hi - lo), 0.0);
+    return DYN_OK;
+  }
+  const Windows win(lo, hi - lo);
+  std::vector<double> h(F * win.most + 1);
+  if (t.sparse() && hi > lo) HIP_TRY(a, t.model_stage.ensure(win.most * F * sizeof(double) + sizeof(uint64_t)));
+  for (auto [s0, cnt, o] : win) {
+    const double* src = t.model.as<double>() + F * s0;
+    if (t.sparse()) {  // the window's ids looked up, their rows gathered -- an absent id: zeros
+      dynk::SiteModelGather mg{t.keys.as<uint32_t>(), (uint32_t)t.capacity, t.model.as<double>(), (uint32_t)s0, (uint32_t)cnt, t.model_stage.as<double>()};
+      dynk::launch_site_model_gather(mg, a->s_get);
+      HIP_TRY(a, hipGetLastError());
+      src = t.model_stage.as<double>();
+    }
+    HIP_TRY(a, copy_out(a, h.data(), src, F * cnt * sizeof(double)));  // (behind the kernel on the same stream)
+    for (uint64_t c = 0; c < cnt; ++c)
+      for (uint64_t f = 0; f < F; ++f) cols[f][o + c] = h[F * c + f];
+  }
+  return DYN_OK;
+}
+
 }  // extern "C"
 
 namespace dyneng {

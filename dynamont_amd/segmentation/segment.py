@@ -165,6 +165,16 @@ def parse(argv=None) -> Namespace:
                         "(the share of the run's rows in the upper component), mix_mu0, mix_mu1, mix_sd0, mix_sd1, mix_iters and "
                         "mix_status; with --site-control the run and the control are pooled for the fit and mix_control_share, "
                         "mix_delta, mix_lor and mix_p compare their shares")
+    p.add_argument("--site-model-out", default="", metavar="MODEL.npz",
+                   help="with --site-mixture: save the fitted per-site model (the positions whose fit converged or reached MAX_ITERS: "
+                        "pi1, mu0, mu1, var0, var1) with the BAM header's references and the histogram's bins and range, for a later "
+                        "run's --site-model")
+    p.add_argument("--site-model", default="", metavar="MODEL.npz",
+                   help="with --site-summary FILE: load a per-site model saved by --site-model-out onto the GPU before the first batch "
+                        "and score every row against its position's model there: every row of the output gains site_probability (the "
+                        "posterior probability of the upper component, given the row's level) and site_z (the level as a z-score under "
+                        "the lower component); nan where the position has no model or the read no mapping. Works with "
+                        "--site-capacity: model rows that find no row in the table are reported on stderr")
     p.add_argument("--kmer-summary", default="", metavar="PATH",
                    help="also write a per-k-mer summary of the run to PATH: a TSV in the model file's k-mer order with the "
                         "level (mean, stdev of the normalised signal) and dwell the run's segments showed per k-mer beside the "
@@ -748,6 +758,8 @@ class _NativePipeline:
             flags |= N.DYN_CSV_BORDER_INTERVAL  # ... and the credible intervals (--border-interval)
         if aligner._soft_levels:
             flags |= N.DYN_CSV_SOFT_LEVELS  # ... and the soft levels (--soft-levels)
+        if aligner._site_calls:
+            flags |= N.DYN_CSV_SITE_CALLS  # ... and the site calls (--site-model)
         rc = self.L.dyn_csv_sink_open_ex(outfile.encode(), errfile.encode(), int(os.environ.get("DYN_SINK_LEVEL", level)), int(threads),
                                          int(first), int(last), flags, C.byref(h), err, 1024)
         if rc != N.DYN_OK:
@@ -975,7 +987,7 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             guide_auto: int = 0, guide_rounds: int = 8, guide_rescue: int = 0, guide_rescue_margin: int = 1,
             posterior_samples: int = 0, sample_seed: int = 0, border_interval: float = 0.0,
             soft_levels: bool = False, site_summary: str = "", site_histogram: str = "", site_table_out: str = "",
-            site_control: str = "", site_mixture: int = 0, site_capacity: int = 0) -> None:
+            site_control: str = "", site_mixture: int = 0, site_capacity: int = 0, site_model_out: str = "", site_model: str = "") -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
@@ -1013,9 +1025,15 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
         raise ValueError("--site-capacity sizes the sparse per-site table: it needs --site-summary FILE")
     if site_capacity and not 1 <= site_capacity <= 4294967294:
         raise ValueError(f"--site-capacity {site_capacity}: ROWS must be 1 .. 4294967294")
+    if site_model_out and not site_mixture:
+        raise ValueError("--site-model-out saves the fitted per-site mixtures: it needs --site-mixture")
+    if site_model and not site_summary:
+        raise ValueError("--site-model scores every row against its position's model beside the per-site table: it needs --site-summary FILE")
     LAST_RUN.pop("site_rows_dropped", None)
+    LAST_RUN.pop("site_model_dropped", None)
     site_refs = None
     control_table = None
+    loaded_model = None
     if site_summary:
         # refused before anything is started: what the per-site table cannot do yet, and a BAM that is not mapped
         from dynamont_amd.bam_io import bam_references
@@ -1031,6 +1049,10 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
         site_refs = (names, contig_offsets(lengths))
         if int(site_refs[1][-1]) >= DYN_SITE_NONE or int(site_refs[1][-1]) == 0:
             raise ValueError(f"--site-summary: the references hold {int(site_refs[1][-1])} positions; the table takes 1 .. 4294967294")
+        if site_model:
+            # refused before anything is started: a model fitted over other references
+            from dynamont_amd.segmentation.utils import load_site_model
+            loaded_model = load_site_model(site_model, names, lengths)
         if site_control:
             # refused before anything is started: a control of other references, without histograms or of other bins
             from dynamont_amd.segmentation.utils import check_site_control, load_site_table
@@ -1134,6 +1156,24 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
         windows = aligner.site_map_windows(20).tolist() if site_capacity else None
         written = write_site_summary(site_summary, aligner.site_summary, num_sites, *site_refs, quantiles=quantiles, control=control,
                                      mixture=mixture, windows=windows)
+        if site_model_out:
+            # --site-model-out: the run's fit again, window by window, its accepted rows kept; the file is sparse
+            from dynamont_amd.bam_io import bam_references
+            from dynamont_amd.segmentation.utils import SITE_MODEL_COLUMNS, save_site_model
+            parts = {k: [] for k in SITE_MODEL_COLUMNS + ("site",)}
+            step = 1 << 20
+            spans = [(w0, min(w0 + step, num_sites)) for w0 in (range(0, num_sites, step) if windows is None else [w * step for w in sorted(windows)])
+                     if w0 < num_sites]
+            for w0, w1 in spans:
+                fit = aligner.site_mixture(w0, w1, num_sites + w0 if control_table is not None else None, max_iters=site_mixture)
+                keep = np.flatnonzero(np.isin(fit["status"], (0, 2)))
+                parts["site"].append((keep + w0).astype(np.uint64))
+                for k in SITE_MODEL_COLUMNS:
+                    parts[k].append(fit[k][keep])
+            cols = {k: (np.concatenate(v) if v else np.zeros(0, dtype=np.uint64 if k == "site" else np.float64)) for k, v in parts.items()}
+            cols["num_sites"] = num_sites
+            saved = save_site_model(site_model_out, cols, *bam_references(basecalls), histogram=aligner._site_histogram)
+            print(f"site model written: {site_model_out}: {saved} positions with a fitted model", file=sys.stderr, flush=True)
         if site_table_out:
             from dynamont_amd.bam_io import bam_references
             from dynamont_amd.segmentation.utils import save_site_table
@@ -1241,6 +1281,18 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                             raise MemoryError(f"--site-capacity {site_capacity}: the control {site_control} does not fit the sparse table "
                                               f"beside the run ({error}); run again with a larger --site-capacity") from None
                         print(f"site control: {site_control}: {added} sites with coverage loaded", file=sys.stderr, flush=True)
+            if loaded_model is not None:
+                # --site-model: onto the GPU before the first ticket, beside the table; every ticket from here on is scored
+                from dynamont_amd.segmentation.utils import upload_site_model
+                try:
+                    up = upload_site_model(aligner, loaded_model)
+                except MemoryError as error:
+                    raise MemoryError(f"--site-model: the model of {site_capacity or int(site_refs[1][-1])} rows (40 bytes each) does not fit: {error}") from None
+                aligner.set_site_calls(True)
+                LAST_RUN["site_model_dropped"] = up["dropped"]
+                print(f"site model: {site_model}: {up['stored']} positions loaded" +
+                      (f"; {up['dropped']} of them found no row in the sparse table of {site_capacity} rows and were dropped: their rows have no call"
+                       if up["dropped"] else ""), file=sys.stderr, flush=True)
             if band_report:
                 aligner.set_band_margin(True)
             if guide_auto:
@@ -1405,7 +1457,8 @@ def main(argv=None) -> None:
             guide_rescue_margin=args.guide_rescue_margin, posterior_samples=args.posterior_samples, sample_seed=args.sample_seed,
             border_interval=args.border_interval, soft_levels=args.soft_levels, site_summary=args.site_summary, site_table_out=args.site_table_out,
             site_control=args.site_control, site_mixture=args.site_mixture,
-            site_histogram=args.site_histogram, site_capacity=args.site_capacity)
+            site_histogram=args.site_histogram, site_capacity=args.site_capacity, site_model_out=args.site_model_out,
+            site_model=args.site_model)
     _stamp("segment() returned (aligner closed)")
     # --site-capacity: rows were dropped from a full table -- everything is written, the status says that sites are missing
     status = 3 if LAST_RUN.get("site_rows_dropped") else 0

@@ -559,6 +559,92 @@ def check_site_control(table: dict, path: str, ref_names, ref_lengths, hist_spec
                          f"{table['hist_spec'][2]!r})) are not the run's ({bins} bins over [{lo!r}, {hi!r})), bit for bit")
 
 
+SITE_MODEL_VERSION = 1
+SITE_MODEL_COLUMNS = ("pi1", "mu0", "mu1", "var0", "var1")
+
+
+def save_site_model(path: str, model: dict, ref_names, ref_lengths, histogram=None) -> int:
+    """The SET rows (var0 > 0, mu0 and var0 finite) of a per-site model -- the five float64 columns ``pi1``, ``mu0``, ``mu1``,
+    ``var0``, ``var1`` over the sites [0, n), as ``Aligner.site_model()`` returns them or ``Aligner.site_mixture()`` fitted them --
+    as a sparse .npz (numpy only): ``site`` uint64, the five columns, ``num_sites``, ``ref_names``, ``ref_lengths``, ``hist_spec`` =
+    (bins, lo, hi) of the histograms the model was fitted under with the bounds as float64 BITS (bins 0: not recorded) and
+    ``version``. A ``model`` that holds ``site`` (ascending uint64) and ``num_sites`` is taken as sparse already: its columns are
+    the rows of those sites (a genome-wide id space is never dense on the host). Returns the rows saved."""
+    cols = [np.ascontiguousarray(model[k], dtype=np.float64).reshape(-1) for k in SITE_MODEL_COLUMNS]
+    n = cols[0].size
+    if any(c.size != n for c in cols):
+        raise ValueError("save_site_model: the columns of the model differ in length")
+    site = np.arange(n, dtype=np.uint64) if model.get("site") is None else np.ascontiguousarray(model["site"], dtype=np.uint64).reshape(-1)
+    if site.size != n:
+        raise ValueError("save_site_model: the columns of the model differ in length")
+    with np.errstate(invalid="ignore"):
+        idx = np.flatnonzero((cols[3] > 0) & np.isfinite(cols[1]) & np.isfinite(cols[3]))
+    out = {"version": np.array([SITE_MODEL_VERSION], dtype=np.uint32),
+           "num_sites": np.array([n if model.get("site") is None else int(model["num_sites"])], dtype=np.uint64),
+           "site": site[idx], "ref_names": np.array([str(r) for r in ref_names], dtype=np.str_),
+           "ref_lengths": np.asarray(ref_lengths, dtype=np.uint64)}
+    for k, c in zip(SITE_MODEL_COLUMNS, cols):
+        out[k] = c[idx]
+    if histogram:
+        out["hist_spec"] = np.concatenate([np.array([int(histogram[0])], dtype=np.uint64), np.array(histogram[1:], dtype=np.float64).view(np.uint64)])
+    else:
+        out["hist_spec"] = np.zeros(3, dtype=np.uint64)
+    with open(path, "wb") as f:          # (a file object: np.savez appends no extension to the name the caller chose)
+        np.savez(f, **out)
+    return int(idx.size)
+
+
+def load_site_model(path: str, ref_names=None, ref_lengths=None) -> dict:
+    """What ``save_site_model`` wrote: ``site`` uint64 and the five float64 columns over the set rows, ``num_sites``, ``ref_names``,
+    ``ref_lengths``, ``histogram`` = (bins, lo, hi) or None, and ``dense(lo, hi)``: the five columns over the sites [lo, hi) with
+    zeros (not set) elsewhere -- what ``Aligner.set_site_model(lo, ...)`` takes. With ``ref_names`` / ``ref_lengths`` (the BAM
+    header's) a model fitted over other contigs is refused, as ``check_site_control`` refuses a control. ValueError for another
+    format version."""
+    with np.load(path, allow_pickle=False) as z:
+        version = int(z["version"][0])
+        if version != SITE_MODEL_VERSION:
+            raise ValueError(f"{path}: site model format version {version}, this build reads version {SITE_MODEL_VERSION}")
+        out = {"version": version, "num_sites": int(z["num_sites"][0]), "site": np.asarray(z["site"], dtype=np.uint64),
+               "ref_names": [str(r) for r in z["ref_names"].tolist()], "ref_lengths": np.asarray(z["ref_lengths"], dtype=np.uint64)}
+        for k in SITE_MODEL_COLUMNS:
+            out[k] = np.ascontiguousarray(z[k], dtype=np.float64)
+        spec = np.asarray(z["hist_spec"], dtype=np.uint64)
+    lo_b, hi_b = spec[1:].view(np.float64).tolist()
+    out["histogram"] = (int(spec[0]), lo_b, hi_b) if int(spec[0]) else None
+    if ref_names is not None:
+        if out["ref_names"] != [str(r) for r in ref_names] or \
+                [int(v) for v in out["ref_lengths"].tolist()] != [int(v) for v in (ref_lengths if ref_lengths is not None else [])]:
+            raise ValueError(f"--site-model {path}: the site model was fitted over other contigs than the BAM header's (names or lengths differ)")
+    site = out["site"].astype(np.int64)
+
+    def dense(lo: int, hi: int) -> dict:
+        a, b = np.searchsorted(site, [int(lo), int(hi)])
+        cols = {k: np.zeros(max(0, int(hi) - int(lo)), dtype=np.float64) for k in SITE_MODEL_COLUMNS}
+        for k in SITE_MODEL_COLUMNS:
+            cols[k][site[a:b] - int(lo)] = out[k][a:b]
+        return cols
+
+    out["dense"] = dense
+    return out
+
+
+def upload_site_model(aligner, model: dict, offset: int = 0, window: int = 1 << 20) -> dict:
+    """a loaded model (``load_site_model``) into the sites [offset, offset + num_sites) of ``aligner``'s model
+    (``Aligner.set_site_model``), a window of sites at a time and only the windows that hold a set row. Returns the summed
+    ``{"stored", "dropped"}``."""
+    total = {"stored": 0, "dropped": 0}
+    site = model["site"].astype(np.int64)
+    for w0 in range(0, int(model["num_sites"]), int(window)):
+        w1 = min(w0 + int(window), int(model["num_sites"]))
+        a, b = np.searchsorted(site, [w0, w1])
+        if a == b:
+            continue
+        got = aligner.set_site_model(int(offset) + w0, model["dense"](w0, w1), accept=None)
+        total["stored"] += got["stored"]
+        total["dropped"] += got["dropped"]
+    return total
+
+
 def load_site_control(aligner, table: dict, offset: int, window: int = 1 << 20) -> int:
     """adds a loaded table (``load_site_table``) into the sites [offset, offset + num_sites) of ``aligner``'s table and histograms
     (``Aligner.site_summary_add``), a window of sites at a time; its totals are NOT added: the handle's totals stay the run's own.

@@ -280,6 +280,25 @@ typedef struct dyn_soft_level_out {
   uint64_t capacity;  /* >= dyn_segment_capacity() */
 } dyn_soft_level_out;
 
+/* (added within ABI 10: a caller that must know looks the symbol up) Per-read site calls of an align(calc_probabilities = 1) job
+ * whose handle had dyn_aligner_set_site_calls(a, 1) when the batch was submitted: every output row scored against the per-site
+ * model of dyn_aligner_set_site_model. Row j of an ok read has the site id s of base j + kmer_size / 2
+ * (dyn_aligner_stage_site_ids) and the event mean m -- level_mean of dyn_event_out, bit for bit. With the model row (pi1, mu0,
+ * mu1, var0, var1) of s:
+ *   site_z           = (m - mu0) / sqrt(var0)
+ *   site_probability = p_1 / (p_0 + p_1), p_k = pi_k / sqrt(var_k) * exp(q_k - max(q_0, q_1)), q_k = -0.5 * ((m - mu_k)^2 / var_k),
+ *                      pi_0 = 1 - pi1: the E-step of dyn_aligner_site_mixture at x = m, one IEEE fp64 operation per operation,
+ *                      the library's strict exp (one evaluation; the other factor is exactly 1)
+ * Both are the NaN 0x7FF8000000000000 ("no call") when no ids were staged, no model was uploaded, s is DYN_SITE_NONE or >=
+ * num_sites, the row is one the per-site table would skip (m not finite or m * m >= 2^64), a sparse table has no bucket for s, or
+ * the model row is not set (var0 > 0, mu0 and var0 finite); site_probability also when the row is not two-component (0 < pi1 < 1,
+ * var1 > 0, mu1 and var1 finite). The same bits on every launch path. Rows of failed reads are 0. */
+typedef struct dyn_site_call_out {
+  double* site_probability; /* [capacity] each, rows indexed like dyn_align_out's */
+  double* site_z;
+  uint64_t capacity;        /* >= dyn_segment_capacity() */
+} dyn_site_call_out;
+
 /* (ABI 10) Per-read signal rescaling of an align(calc_probabilities = 1) job whose handle had dyn_aligner_set_rescale(a, K)
  * with K > 0 when the batch was submitted. Read r is aligned K + 1 times. x0 = its preprocessed signal (what
  * dyn_batch_signals returns with the switch off); A_0 = 0.0, B_0 = 1.0; pass k = 0 .. K aligns x_k, x_0 = x0 and
@@ -747,6 +766,27 @@ int dyn_aligner_site_map_keys(dyn_aligner* a, uint64_t bucket_lo, uint64_t bucke
  * min(*count, cap) written to windows; more than cap is DYN_ERR_INVALID_ARGUMENT (call again with *count). 0 <= shift <= 31 and
  * at most 2^22 windows in the id space. A caller walks the table window by window without gathering the empty ones. */
 int dyn_aligner_site_map_windows(dyn_aligner* a, int shift, uint64_t* windows, uint64_t cap, uint64_t* count);
+/* (added within ABI 10) The per-site MODEL of a handle, beside its per-site table: five doubles per table row -- pi1, mu0, mu1,
+ * var0, var1, the columns dyn_aligner_site_mixture returns --, 40 bytes per row (dense: per site; sparse: per bucket), allocated
+ * and zeroed by the first upload, counted in the memory budget, released with the table when dyn_aligner_set_site_summary[_sparse]
+ * names another size. A row is SET when var0 > 0 and mu0, var0 are finite (all zeros: not set).
+ * dyn_aligner_set_site_model uploads the rows of the sites [site_lo, site_lo + count), staged 2^20 rows at a time, after the jobs
+ * that have been enqueued (the quiescence of dyn_aligner_site_summary_add). Dense: a copy. Sparse: a set row finds or inserts the
+ * bucket of its id, a row that is not set inserts no key (and clears the row of an id that has one); *dropped (may be NULL) gets the
+ * number of set rows whose id found no bucket in its probe window -- they are not stored, the call is still DYN_OK.
+ * DYN_ERR_INVALID_ARGUMENT with a text: no table on this handle, or the window does not lie below num_sites. count = 0 touches
+ * nothing. dyn_aligner_site_model_reset zeroes the model (a handle that never uploaded one: DYN_OK). dyn_aligner_site_model_fetch
+ * reads the rows of [lo, hi) back (a handle without a model, or an id without a bucket: zeros). */
+int dyn_aligner_set_site_model(dyn_aligner* a, uint64_t site_lo, uint64_t count, const double* pi1, const double* mu0,
+                               const double* mu1, const double* var0, const double* var1, uint64_t* dropped);
+int dyn_aligner_site_model_reset(dyn_aligner* a);
+int dyn_aligner_site_model_fetch(dyn_aligner* a, uint64_t lo, uint64_t hi, double* pi1, double* mu0, double* mu1, double* var0,
+                                 double* var1);
+/* (added within ABI 10) align(calc_probabilities = 1) jobs submitted while on also score every output row against the per-site
+ * model (dyn_site_call_out, dyn_batch_fetch_site_calls). The model and the map are taken as they stand at the job's submission.
+ * A job submitted while on is refused with DYN_ERR_INVALID_ARGUMENT and a text when dyn_aligner_set_site_summary[_sparse] is not
+ * on, and when it is not an align(calc_probabilities = 1) job; a job that staged no ids gets NaN columns. */
+int dyn_aligner_set_site_calls(dyn_aligner* a, int on);
 /* The rule of mode 1 for one read, given its k-mer codes (dyn_validate_batch) and signal length: 0 = no structural tie;
  * otherwise the number of forward rows that run in the strict arithmetic (UINT32_MAX: all of them). Host only. */
 uint32_t dyn_tie_rows(const dyn_aligner* a, const int32_t* kmers, uint64_t n_kmers, uint64_t signal_len);
@@ -874,6 +914,20 @@ int dyn_format_csv_soft(const dyn_aligner* a, uint64_t n_reads, const dyn_align_
                         const int64_t* sig_offsets, const int64_t* last_index, int threads, char* out, uint64_t out_cap,
                         uint64_t* row_begin, uint64_t* row_end);
 
+/* (added within ABI 10) The same with the site calls of dyn_batch_fetch_site_calls as well: after every other optional column each
+ * row gets ",{site_probability:.6f},{site_z:.6f}", the floats as the level columns print theirs (a NaN as "nan", an infinity as "inf" / "-inf"). Every out-struct
+ * may be NULL; ca == NULL: dyn_format_csv_soft / dyn_format_csv_bound_soft, byte for byte. */
+uint64_t dyn_format_csv_bound_calls(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                                    const dyn_score_out* sc, const dyn_border_out* bd, const dyn_sample_out* sm,
+                                    const dyn_border_interval_out* bi, const dyn_soft_level_out* sl, const dyn_site_call_out* ca,
+                                    const char* const* readids, const char* const* signalids);
+int dyn_format_csv_calls(const dyn_aligner* a, uint64_t n_reads, const dyn_align_out* res, const dyn_event_out* ev,
+                         const dyn_score_out* sc, const dyn_border_out* bd, const dyn_sample_out* sm,
+                         const dyn_border_interval_out* bi, const dyn_soft_level_out* sl, const dyn_site_call_out* ca, const char* seqs,
+                         const uint64_t* seq_offsets, const char* const* readids, const char* const* signalids,
+                         const int64_t* sig_offsets, const int64_t* last_index, int threads, char* out, uint64_t out_cap,
+                         uint64_t* row_begin, uint64_t* row_end);
+
 /* Closes the gaps between the per-read ranges dyn_format_csv produced: all rows become one contiguous run at the
  * front of `out`, in read order; row_begin/row_end are updated. Returns the total byte count. */
 uint64_t dyn_csv_compact(char* out, uint64_t n_reads, uint64_t* row_begin, uint64_t* row_end);
@@ -938,6 +992,11 @@ int dyn_csv_sink_open_part(const char* csv_zst_path, const char* errors_path, in
  * whose ticket was submitted with dyn_aligner_set_soft_levels off fails with DYN_ERR_INVALID_ARGUMENT. (0x200: bits 0x4, 0x20,
  * 0x80 and 0x100 stay unassigned, and a sink opened with any of them is refused as before; so is every bit above 0x200.) */
 #define DYN_CSV_SOFT_LEVELS 0x200u
+/* (added within ABI 10) DYN_CSV_SITE_CALLS: the header gains ",site_probability,site_z" after every other optional column, every
+ * row the two fields of dyn_format_csv_calls; the sink fetches each ticket's calls after its wait, and a submit whose ticket was
+ * submitted with dyn_aligner_set_site_calls off fails with DYN_ERR_INVALID_ARGUMENT. (0x800: bits 0x4, 0x20, 0x80, 0x100 and 0x400
+ * stay unassigned, and a sink opened with any of them is refused as before; so is every bit above 0x800.) */
+#define DYN_CSV_SITE_CALLS 0x800u
 int dyn_csv_sink_open_ex(const char* csv_zst_path, const char* errors_path, int level, int threads, int first, int last,
                          uint32_t flags, dyn_csv_sink** out, char* err, uint64_t errcap);
 #define DYN_ZSTD_FRAME_END "\x01\x00\x00" /* an empty last block (raw, size 0): 3 bytes; the frames carry no checksum */
@@ -1095,6 +1154,10 @@ int dyn_batch_fetch_intervals(dyn_batch* b, dyn_border_interval_out* out);
  * message) when the batch was submitted with dyn_aligner_set_soft_levels off, or aligned with calc_probabilities = 0, or
  * out->capacity is too small. */
 int dyn_batch_fetch_soft_levels(dyn_batch* b, dyn_soft_level_out* out);
+/* (added within ABI 10) The site calls of the batch's last align(calc_probabilities = 1) job (of a completed ticket, merged launch
+ * or not), copied on the handle's own non-blocking stream. DYN_ERR_INVALID_ARGUMENT (with a message) when the batch was submitted
+ * with dyn_aligner_set_site_calls off, or aligned with calc_probabilities = 0, or out->capacity is too small. */
+int dyn_batch_fetch_site_calls(dyn_batch* b, dyn_site_call_out* out);
 /* (ABI 10) Copy the per-read transforms of the last dyn_batch_align (or of a completed ticket, merged launch or not) into
  * `out` (n >= the batch's read count). DYN_ERR_INVALID_ARGUMENT + message for a batch submitted with
  * dyn_aligner_set_rescale(a, 0), or aligned with calc_probabilities = 0. */
