@@ -1196,6 +1196,117 @@ class Aligner:
         if rc != N.DYN_OK:
             _raise(rc, self.last_error())
 
+    def site_table_pack(self, lo: int = 0, hi: int | None = None) -> dict:
+        """dyn_aligner_site_pack: the LIVE sites of [lo, hi) (default: all) -- those with any non-zero word in the table or, on a
+        handle with histograms, in their counters -- compacted on the GPU, so that only they cross to the host (INTEGRATION.md
+        section 3). ``site``: uint64, the ids relative to ``lo``, ascending (a dense and a sparse handle on the same reads return
+        equal arrays); ``limbs``, ``n_rows``, ``n_samples``, ``dwell_sq``, ``M1``, ``M2``: as ``site_summary()`` has them, one entry
+        per live site; with histograms ``level``, ``dwell``, ``edges``, ``bins`` as ``site_histogram()`` has them; ``totals``.
+        The rows of the table are walked 2^20 at a time: host memory is one window's records plus the result. Every window's
+        call first waits for the tickets in flight, so the records are the table behind every ticket submitted before; tickets
+        submitted from another thread WHILE it runs may show in the later windows and in ``totals`` (fetched last): pack when
+        the pipeline is dry."""
+        lo, hi, _ = self._site_window(lo, hi)
+        spec = self._site_histogram
+        B = spec[0] + 2 if spec else 0
+        rows = self._site_capacity or None
+        row_lo, row_hi = (0, rows) if rows else (lo, hi)
+        step = 1 << 20
+        cap = 1 << 12
+        count = np.zeros(1, dtype=np.uint64)
+        sites, cells, levels, dwells = [], [], [], []
+        r0 = row_lo
+        while True:
+            r1 = min(r0 + step, row_hi) if row_hi > r0 else r0
+            while True:
+                site = np.zeros(cap, dtype=np.uint32)
+                cell = np.zeros((cap, 7), dtype=np.uint64)
+                level = np.zeros((cap, B), dtype=np.uint32) if spec else None
+                dwell = np.zeros((cap, 16), dtype=np.uint32) if spec else None
+                rc = self._L.dyn_aligner_site_pack(self._h, r0, r1, lo, hi, cap, _ptr(site, N.c_u32_p), _ptr(cell, N.c_u64_p),
+                                                   None if level is None else _ptr(level, N.c_u32_p),
+                                                   None if dwell is None else _ptr(dwell, N.c_u32_p), _ptr(count, N.c_u64_p))
+                n = int(count[0])
+                if rc != N.DYN_OK and n > cap:  # the window holds more: nothing was copied, once more with room for them
+                    cap = n
+                    continue
+                if rc != N.DYN_OK:
+                    _raise(rc, self.last_error())
+                break
+            if n:
+                sites.append(site[:n].copy())
+                cells.append(cell[:n].copy())
+                if spec:
+                    levels.append(level[:n].copy())
+                    dwells.append(dwell[:n].copy())
+            r0 = r1
+            if r0 >= row_hi:
+                break
+        site = np.concatenate(sites) if sites else np.zeros(0, dtype=np.uint32)
+        cell = np.concatenate(cells) if cells else np.zeros((0, 7), dtype=np.uint64)
+        order = np.argsort(site, kind="stable") if rows else None  # (a sparse table: bucket order -> id order)
+        pick = (lambda v: v[order]) if order is not None else (lambda v: v)
+        cell = pick(cell)
+        out = site_summary_from_limbs([np.ascontiguousarray(cell[:, f]) for f in range(7)], list(self.site_summary(0, 0)["totals"].values()))
+        out["site"] = pick(site).astype(np.uint64) - np.uint64(lo)
+        if spec:
+            bins, h_lo, h_hi = spec
+            out["level"] = pick(np.concatenate(levels)) if levels else np.zeros((0, B), dtype=np.uint32)
+            out["dwell"] = pick(np.concatenate(dwells)) if dwells else np.zeros((0, 16), dtype=np.uint32)
+            out["edges"] = h_lo + np.arange(bins + 1, dtype=np.float64) * ((h_hi - h_lo) / bins)
+            out["bins"] = bins
+        return out
+
+    def site_summary_merge(self, packed: dict, offset: int = 0) -> None:
+        """dyn_aligner_site_summary_merge: adds what ``site_table_pack()`` returned -- of this handle or of another one, another
+        process's included -- into the table BY KEY: the record of ``site[i]`` into the site ``site[i] + offset``, as exact
+        integers, with its counters when ``packed`` has them, and ``packed["totals"]`` (when there) once. The same id may appear
+        any number of times (the records of several ranks concatenated). Checked like ``site_summary_add``: ValueError when
+        ``packed["edges"]`` are not bit-equal to the handle's or an id + offset is not below the table's sites; MemoryError,
+        with the count, when a sparse table had no bucket for some ids -- the others were added."""
+        offset = int(offset)
+        if offset < 0:
+            raise ValueError("site_summary_merge: offset must be >= 0")
+        ids = np.ascontiguousarray(packed["site"]).reshape(-1)
+        n = ids.size
+        if n and (ids.dtype.kind not in "ui" or int(ids.min()) < 0 or int(ids.max()) >= 0xFFFFFFFF):
+            raise ValueError("site_summary_merge: site must hold integer ids below 4294967295")
+        site = ids.astype(np.uint32)
+        if "limbs" in packed and packed["limbs"] is not None:
+            cols = [np.ascontiguousarray(c, dtype=np.uint64).reshape(-1) for c in packed["limbs"]]
+        else:
+            cols = [np.ascontiguousarray(packed[k], dtype=np.uint64).reshape(-1) for k in ("n_rows", "n_samples", "dwell_sq")]
+            for k in ("M1", "M2"):
+                cols.extend(limbs_of_int128(packed[k]))
+        if len(cols) != 7 or any(c.size != n for c in cols):
+            raise ValueError("site_summary_merge: seven columns of one entry per site")
+        cells = np.ascontiguousarray(np.stack(cols, axis=1)) if n else np.zeros((0, 7), dtype=np.uint64)
+        totals = None
+        if packed.get("totals") is not None:
+            t = packed["totals"]
+            totals = np.array([int(t[k]) for k in SITE_SUMMARY_TOTALS] if isinstance(t, dict) else [int(x) for x in t], dtype=np.uint64)
+            if totals.size != 5:
+                raise ValueError("site_summary_merge: five totals")
+        level = dwell = None
+        if packed.get("level") is not None or packed.get("dwell") is not None:
+            if packed.get("level") is None or packed.get("dwell") is None:
+                raise ValueError("site_summary_merge: level and dwell counters are given together or not at all")
+            bins, h_lo, h_hi = self._site_histogram or (0, 0.0, 0.0)
+            mine = h_lo + np.arange(bins + 1, dtype=np.float64) * ((h_hi - h_lo) / bins) if bins else np.zeros(0)
+            edges = np.ascontiguousarray(packed["edges"], dtype=np.float64)
+            if bins and (edges.shape != mine.shape or edges.tobytes() != mine.tobytes()):
+                raise ValueError("site_summary_merge: the histogram's edges are not the handle's (set_site_histogram%r)" % ((bins, h_lo, h_hi),))
+            level = np.ascontiguousarray(packed["level"], dtype=np.uint32)
+            dwell = np.ascontiguousarray(packed["dwell"], dtype=np.uint32)
+            if bins and (level.shape != (n, bins + 2) or dwell.shape != (n, 16)):
+                raise ValueError("site_summary_merge: level must be [n, bins + 2] and dwell [n, 16] for the n sites")
+        rc = self._L.dyn_aligner_site_summary_merge(self._h, n, _ptr(site, N.c_u32_p), offset, _ptr(cells, N.c_u64_p),
+                                                    None if totals is None else _ptr(totals, N.c_u64_p),
+                                                    None if level is None else _ptr(level, N.c_u32_p),
+                                                    None if dwell is None else _ptr(dwell, N.c_u32_p))
+        if rc != N.DYN_OK:
+            _raise(rc, self.last_error())
+
     def site_compare(self, lo: int = 0, hi: int | None = None, other_lo: int | None = None) -> dict:
         """dyn_aligner_site_compare: the sites [lo, hi) (default: the first half of the table) against the sites starting at
         ``other_lo`` (default ``num_sites // 2 + lo``: the second sample of a table of 2 N sites whose ids were offset by N), pair
@@ -1887,6 +1998,16 @@ class MultiAligner:
         """Not supported, as ``set_site_summary`` is not."""
         raise NotImplementedError("MultiAligner has no per-site summary (Aligner.site_summary_add): use one Aligner per device "
                                   "and add their tables")
+
+    def site_table_pack(self, lo: int = 0, hi: int | None = None) -> dict:
+        """Not supported, as ``set_site_summary`` is not: pack the table of each device's ``Aligner``."""
+        raise NotImplementedError("MultiAligner has no per-site summary (Aligner.site_table_pack): use one Aligner per device "
+                                  "and merge their packed tables (Aligner.site_summary_merge)")
+
+    def site_summary_merge(self, packed: dict, offset: int = 0) -> None:
+        """Not supported, as ``set_site_summary`` is not."""
+        raise NotImplementedError("MultiAligner has no per-site summary (Aligner.site_summary_merge): use one Aligner per device "
+                                  "and merge their packed tables")
 
     def site_compare(self, lo: int = 0, hi: int | None = None, other_lo: int | None = None) -> dict:
         """Not supported, as ``set_site_histogram`` is not."""

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("DYN_LIB_PATH") or os.path.join(HERE, "libdynamont_mi.so")
 SOURCES = ["dynamont_mi.cpp", "site_table.cpp", "buffers.cpp", "launch.cpp", "session.cpp", "async_engine.cpp", "pore_model.cpp", "csv_format.cpp", "csv_sink.cpp", "vbz_decode.cpp", "bam_reader.cpp", "rccl_comm.cpp", "model_format.cpp",
            "nt_kernels.hip", "pool_stats.hip", "band_reads.hip", "event_stats.hip", "rescale.hip", "kmer_summary.hip", "site_summary.hip", "segment_scores.hip", "band_margin.hip", "guided_band.hip", "auto_guide.hip", "guide_rescue.hip"]
-HEADERS = ["engine.hpp", "engine_internal.hpp", "launch_plan.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "lattice_phase.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "dp_cell.hpp", "segment_kernels.hpp", "preprocess_kernels.hpp", "kmer_summary_kernels.hpp", "site_summary_kernels.hpp", "site_quantile_kernels.hpp", "site_compare_kernels.hpp", "site_mixture_kernels.hpp", "site_call_kernels.hpp", "site_map.hpp", "site_map_kernels.hpp", "exact_sum_kernels.hpp", "segment_score_kernels.hpp", "border_kernels.hpp", "interval_kernels.hpp", "soft_level_kernels.hpp", "sample_kernels.hpp", "band_margin_kernels.hpp", "band_reads.hpp", "guided_band_kernels.hpp", "auto_guide_kernels.hpp", "guide_rescue_kernels.hpp", "band_runs.hpp", "lpe_liveness.hpp", "decision_record.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
+HEADERS = ["engine.hpp", "engine_internal.hpp", "launch_plan.hpp", "zstd_dl.hpp", "vbz_decode.hpp", "nt_kernels.hpp", "lattice_phase.hpp", "pore_model.hpp", "dp_math.hpp", "dp_math_strict.hpp", "dp_cell.hpp", "segment_kernels.hpp", "preprocess_kernels.hpp", "kmer_summary_kernels.hpp", "site_summary_kernels.hpp", "site_quantile_kernels.hpp", "site_compare_kernels.hpp", "site_mixture_kernels.hpp", "site_call_kernels.hpp", "site_map.hpp", "site_map_kernels.hpp", "site_pack_kernels.hpp", "exact_sum_kernels.hpp", "segment_score_kernels.hpp", "border_kernels.hpp", "interval_kernels.hpp", "soft_level_kernels.hpp", "sample_kernels.hpp", "band_margin_kernels.hpp", "band_reads.hpp", "guided_band_kernels.hpp", "auto_guide_kernels.hpp", "guide_rescue_kernels.hpp", "band_runs.hpp", "lpe_liveness.hpp", "decision_record.hpp", "strict_exp_table.inc", os.path.join("..", "..", "include", "dynamont_mi.h")]
 
 DYN_DEVICE_HOST_ONLY = -2
 DYN_CSV_EVENT_STATS = 0x1  # dyn_csv_sink_open_ex flag
@@ -178,6 +178,9 @@ SIGNATURES = {
     "dyn_aligner_set_site_histogram": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double]),
     "dyn_aligner_site_histogram_fetch": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, c_u32_p, c_u32_p]),
     "dyn_aligner_site_summary_add": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64] + [c_u64_p] * 8 + [c_u32_p, c_u32_p]),
+    "dyn_aligner_site_pack": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, c_u32_p, c_u64_p, c_u32_p, c_u32_p,
+                                        c_u64_p]),
+    "dyn_aligner_site_summary_merge": (C.c_int, [C.c_void_p, C.c_uint64, c_u32_p, C.c_uint64, c_u64_p, c_u64_p, c_u32_p, c_u32_p]),
     "dyn_aligner_site_compare": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, c_u32_p, c_u32_p, c_u64_p, c_u32_p, c_i32_p, c_u64_p,
                                            c_u32_p, c_i32_p]),
     "dyn_aligner_site_mixture": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_double, C.c_uint32] + [c_double_p] * 7 +

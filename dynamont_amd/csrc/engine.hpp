@@ -212,6 +212,9 @@ struct SiteTable {
   DevBuf comp;   // dyn_aligner_site_compare: one window's output
   DevBuf mix;    // dyn_aligner_site_mixture: one window's output
   DevBuf add;    // dyn_aligner_site_summary_add: one window's columns and counters
+  DevBuf pack;   // dyn_aligner_site_pack: one window's records (sized from the window's live count)
+  DevBuf pack_scan;  // ... and its live masks, offsets and total, which have to outlive the growing of `pack` between the passes
+  DevBuf merge;  // dyn_aligner_site_summary_merge: one chunk's staged records
   // dyn_aligner_stage_site_ids: the caller's ids for the NEXT batch-creating call on this handle (consumed by it, whatever its outcome)
   const uint32_t* staged_ids = nullptr;
   uint64_t staged_count = 0;
@@ -270,7 +273,7 @@ struct SiteTable {
   }
   void release() {
     release_table();
-    for (DevBuf* d : {&quant, &comp, &mix, &add, &model_stage}) d->release();
+    for (DevBuf* d : {&quant, &comp, &mix, &add, &model_stage, &pack, &pack_scan, &merge}) d->release();
   }
 };
 

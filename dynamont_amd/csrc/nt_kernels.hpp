@@ -420,6 +420,46 @@ struct SiteWindows {
   unsigned int* bitmap;             // [ceil(((num_sites - 1) >> shift) + 1, 32)] uint32, zeroed by the caller
 };
 void launch_site_map_windows(const SiteWindows& sw, hipStream_t s);
+// the table by content (site_pack_kernels.hpp). k_site_pack_*: the live rows of the table rows [row_lo, row_lo + count) -- an id
+// in [site_lo, site_hi), any cell word or counter non-zero -- as records in ascending row order: a count pass, a scan and a write
+constexpr int SPK_CHUNK_ROWS = 64;  // rows per live mask: the scratch of a window is sized from it
+struct SitePack {
+  const uint32_t* keys;             // [capacity], the row's id; nullptr: the table is dense, the row is the id
+  const unsigned long long* acc;    // the table: [rows][7]
+  const unsigned int* hist;         // [rows][width]; nullptr: the table alone
+  uint32_t width;                   // bins + 2 + 16
+  uint32_t row_lo, count;           // the window of rows, count <= 2^20
+  uint32_t site_lo, site_hi;        // the filter on the ids
+  unsigned long long* mask;         // scratch, [ceil(count / 64)]: the live rows of every chunk of 64
+  uint32_t* offset;                 // scratch, [ceil(count / 64)]: the live rows in front of every chunk
+  unsigned long long* total;        // [1]: the live rows of the window
+  uint64_t cap;                     // records the three arrays below hold (the write pass alone reads these four)
+  uint32_t* out_site;               // [cap]
+  unsigned long long* out_cells;    // [cap][7]
+  unsigned int* out_hist;           // [cap][width]
+};
+void launch_site_pack(const SitePack& sp, hipStream_t s);        // count and scan: *total
+void launch_site_pack_write(const SitePack& sp, hipStream_t s);  // the records, behind them on the same stream
+// k_site_merge: `count` records added into the rows of the ids site[i] + offset, duplicates allowed; what k_site_scatter_add adds
+// and counts, by key
+struct SiteMerge {
+  uint32_t* keys;                   // nullptr: the table is dense, the id is the row
+  uint32_t capacity;
+  unsigned long long* stats;        // [3] n_keys, rows_dropped, sites_dropped (sparse)
+  unsigned long long* acc;          // the table: [rows][7]
+  unsigned long long* totals;       // the table's [5] totals
+  unsigned int* hist;               // [rows][width]; nullptr: the table alone
+  const uint32_t* site;             // staged [count]
+  const unsigned long long* cells;  // staged [count][7]
+  const unsigned int* counters;     // staged [count][width]
+  uint32_t width;
+  uint32_t count;
+  uint64_t offset;                  // added to every id
+  uint64_t num_sites;               // the bound of id + offset
+  int add_totals;
+  unsigned long long totals_in[SS_TOTALS];
+};
+void launch_site_merge(const SiteMerge& sm, hipStream_t s);
 // per-read site calls (site_call_kernels.hpp, dyn_aligner_set_site_calls): every output row scored against the per-site model of
 // dyn_aligner_set_site_model; prob == nullptr: not asked for
 constexpr int SC_MODEL_FIELDS = 5;  // per table row: pi1, mu0, mu1, var0, var1 (all zero: not set)

@@ -8,6 +8,7 @@
 // looks the id up (the same addresses: one request), then lane f < 7 moves field f and the lanes stride over the counters.
 // Footprint: 256 threads, no LDS, no scratch.
 #pragma once
+#define DYNK_SITE_MAP_KERNELS_HPP 1  // (site_pack_kernels.hpp asks for this header in front of it)
 
 #include "exact_sum_kernels.hpp"
 #include "nt_kernels.hpp"

@@ -5,6 +5,7 @@
 #include "site_compare_kernels.hpp"
 #include "site_map_kernels.hpp"
 #include "site_mixture_kernels.hpp"
+#include "site_pack_kernels.hpp"
 #include "site_quantile_kernels.hpp"
 #include "site_summary_kernels.hpp"
 
@@ -32,6 +33,12 @@ void launch_site_add(const SiteAdd& sa, hipStream_t s) { launch_site_add_kernel(
 void launch_site_gather(const SiteGather& sg, hipStream_t s) { launch_site_gather_kernel(sg, s); }
 void launch_site_scatter_add(const SiteScatter& sc, hipStream_t s) { launch_site_scatter_add_kernel(sc, s); }
 void launch_site_map_windows(const SiteWindows& sw, hipStream_t s) { launch_site_map_windows_kernel(sw, s); }
+
+// dyn_aligner_site_pack / dyn_aligner_site_summary_merge: the live rows of a window of table rows as records (count and scan,
+// then the write), and records added into the table by key
+void launch_site_pack(const SitePack& sp, hipStream_t s) { launch_site_pack_kernels(sp, s); }
+void launch_site_pack_write(const SitePack& sp, hipStream_t s) { launch_site_pack_write_kernel(sp, s); }
+void launch_site_merge(const SiteMerge& sm, hipStream_t s) { launch_site_merge_kernel(sm, s); }
 
 // dyn_aligner_set_site_calls: the rows of the reads [read_lo, read_hi) scored against the per-site model (site_call_kernels.hpp),
 // and the model's two window calls on a sparse table

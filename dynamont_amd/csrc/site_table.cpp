@@ -1,7 +1,7 @@
 // site_table.cpp -- the per-site table of a handle (dyneng::SiteTable, engine.hpp: dyn_aligner::site) behind the C ABI: its two
 // setters, the staged ids, the map's getters and the window calls that read or add to a range of sites. The kernels:
 // site_summary_kernels.hpp (the table, its histograms, the quantiles), site_compare_kernels.hpp, site_mixture_kernels.hpp,
-// site_map_kernels.hpp (the sparse table); what a JOB adds to the table is launched with the job (launch.cpp).
+// site_map_kernels.hpp (the sparse table), site_pack_kernels.hpp (the table by content); what a JOB adds to the table is launched with the job (launch.cpp).
 //
 // A window call holds the handle's lock throughout and runs every copy and kernel on s_get. It walks its range in windows of
 // 2^20 sites (Windows), points its kernel's argument struct at each (table_window / hist_window: the table itself, or the gathered
@@ -483,6 +483,174 @@ int dyn_aligner_site_summary_add(dyn_aligner* a, uint64_t lo, uint64_t hi, const
     }
     HIP_TRY(a, hipGetLastError());
     HIP_TRY(a, hipStreamSynchronize(a->s_get));  // (the host vectors are filled again for the next window)
+  }
+  if (t.sparse()) HIP_TRY(a, copy_out(a, &dropped, dropped_at, sizeof(uint64_t)));
+  if (dropped > dropped_before)
+    return fail(a, who, std::to_string(dropped - dropped_before) + " sites found no bucket in the map of " + std::to_string(t.capacity) +
+                            " rows and were dropped; the other sites were added", DYN_ERR_OUT_OF_MEMORY);
+  return DYN_OK;
+}
+
+// ---- the table by content: the live rows as records, and records added by key (site_pack_kernels.hpp) -------------------------
+int dyn_aligner_site_pack(dyn_aligner* a, uint64_t row_lo, uint64_t row_hi, uint64_t site_lo, uint64_t site_hi, uint64_t cap, uint32_t* site,
+                          uint64_t* cells, uint32_t* level, uint32_t* dwell, uint64_t* count) {
+  if (!a || !count) return DYN_ERR_INVALID_ARGUMENT;
+  const char* who = "dyn_aligner_site_pack";
+  // refused before the device is looked at: the same text on a handle without one
+  if ((level == nullptr) != (dwell == nullptr)) return fail(a, who, "level and dwell counters are given together or not at all");
+  if (cap && (!site || !cells)) return DYN_ERR_INVALID_ARGUMENT;
+  *count = 0;
+  if (row_lo > row_hi) return fail(a, who, "[" + std::to_string(row_lo) + ", " + std::to_string(row_hi) + ") is not a range of rows");
+  if (site_lo > site_hi) return fail(a, who, "[" + std::to_string(site_lo) + ", " + std::to_string(site_hi) + ") is not a range of sites");
+  if (row_lo == row_hi || site_lo == site_hi) return DYN_OK;  // an empty range touches nothing: no lock, no stream, no device
+  // The table behind every ticket submitted before this call: the tickets in flight finish first (the setters' drain, with the
+  // lock dropped while it waits -- a ticket may still be in front of its launch, where waiting for the streams would not see it),
+  // then, under the lock again, both adding streams are waited for.
+  std::unique_lock<std::mutex> lk(a->mu);
+  if (Pipeline* pipe = a->pipe.get()) {
+    lk.unlock();
+    pipe->drain();
+    lk.lock();
+  }
+  if (int rc = level ? site_histogram_quiet(a, who, 0, 0) : site_summary_quiet(a, who)) return rc;
+  SiteTable& t = a->site;
+  // (the two bounds below are the table's own: they can only be looked at where there is a table)
+  if (!in_table(a, site_lo, site_hi)) return fail(a, who, no_range(a, site_lo, site_hi));
+  if (row_hi > t.rows())
+    return fail(a, who, "[" + std::to_string(row_lo) + ", " + std::to_string(row_hi) + ") is not a range of the table's " + std::to_string(t.rows()) + " rows");
+  const uint64_t F = (uint64_t)dynk::SS_FIELDS;
+  const uint64_t B = (uint64_t)t.bins + 2, D = (uint64_t)dynk::SH_DWELL_BINS, H = level ? B + D : 0;
+  const Windows win(row_lo, row_hi - row_lo);
+  // the scratch of the passes: the total, then a live mask and an offset per chunk of 64 rows
+  const uint64_t chunks = (win.most + dynk::SPK_CHUNK_ROWS - 1) / dynk::SPK_CHUNK_ROWS;
+  HIP_TRY(a, t.pack_scan.ensure(sizeof(uint64_t) * (1 + chunks) + sizeof(uint32_t) * chunks));
+  dynk::SitePack sp{};
+  sp.keys = t.sparse() ? t.keys.as<uint32_t>() : nullptr;
+  sp.acc = t.table.as<unsigned long long>();
+  sp.hist = level ? t.hist.as<unsigned int>() : nullptr;
+  sp.width = (uint32_t)H;
+  sp.site_lo = (uint32_t)site_lo;
+  sp.site_hi = (uint32_t)site_hi;
+  sp.total = t.pack_scan.as<unsigned long long>();
+  sp.mask = sp.total + 1;
+  sp.offset = reinterpret_cast<uint32_t*>(sp.mask + chunks);
+  auto count_window = [&](uint64_t r0, uint64_t cnt, uint64_t* live) -> int {
+    sp.row_lo = (uint32_t)r0;
+    sp.count = (uint32_t)cnt;
+    dynk::launch_site_pack(sp, a->s_get);
+    HIP_TRY(a, hipGetLastError());
+    HIP_TRY(a, copy_out(a, live, sp.total, sizeof(uint64_t)));  // (behind the two kernels on the same stream)
+    return DYN_OK;
+  };
+  // the count of every window first: a caller whose arrays are too small gets the count and nothing else
+  std::vector<uint64_t> live;
+  uint64_t n = 0, most = 0;
+  for (auto [r0, cnt, o] : win) {
+    uint64_t c = 0;
+    if (int rc = count_window(r0, cnt, &c)) return rc;
+    live.push_back(c);
+    n += c;
+    most = std::max(most, c);
+  }
+  *count = n;
+  if (n > cap) return fail(a, who, std::to_string(n) + " rows are live, the caller's arrays hold " + std::to_string(cap));
+  if (n == 0) return DYN_OK;
+  // the records of one window: cells, then counters, then ids (every section 4-byte aligned or better)
+  // (headroom: a caller that walks the table window by window meets a new maximum often, and growing is hipFree + hipMalloc)
+  HIP_TRY(a, t.pack.ensure(most * (F * sizeof(uint64_t) + H * sizeof(uint32_t) + sizeof(uint32_t)), 2.0));
+  sp.cap = most;
+  sp.out_cells = t.pack.as<unsigned long long>();
+  sp.out_hist = reinterpret_cast<unsigned int*>(sp.out_cells + F * most);
+  sp.out_site = sp.out_hist + H * most;
+  std::vector<uint32_t> hh(H * most);
+  uint64_t at = 0, w = 0;
+  for (auto [r0, cnt, o] : win) {
+    const uint64_t c = live[w++];
+    if (c == 0) continue;
+    if (live.size() > 1) {  // the scratch holds the last window's masks: this window's again
+      uint64_t again = 0;
+      if (int rc = count_window(r0, cnt, &again)) return rc;
+      if (again != c) return fail(a, who, "the table changed while it was packed (a job was submitted from another thread)", DYN_ERR_DEVICE);
+    }
+    sp.row_lo = (uint32_t)r0;
+    sp.count = (uint32_t)cnt;
+    dynk::launch_site_pack_write(sp, a->s_get);
+    HIP_TRY(a, hipGetLastError());
+    HIP_TRY(a, hipMemcpyAsync(site + at, sp.out_site, c * sizeof(uint32_t), hipMemcpyDeviceToHost, a->s_get));
+    if (level) HIP_TRY(a, hipMemcpyAsync(hh.data(), sp.out_hist, H * c * sizeof(uint32_t), hipMemcpyDeviceToHost, a->s_get));
+    HIP_TRY(a, copy_out(a, cells + F * at, sp.out_cells, F * c * sizeof(uint64_t)));
+    for (uint64_t i = 0; level && i < c; ++i) {
+      std::memcpy(level + B * (at + i), hh.data() + H * i, B * sizeof(uint32_t));
+      std::memcpy(dwell + D * (at + i), hh.data() + H * i + B, D * sizeof(uint32_t));
+    }
+    at += c;
+  }
+  return DYN_OK;
+}
+
+int dyn_aligner_site_summary_merge(dyn_aligner* a, uint64_t count, const uint32_t* site, uint64_t offset, const uint64_t* cells,
+                                   const uint64_t totals[5], const uint32_t* level, const uint32_t* dwell) {
+  if (!a) return DYN_ERR_INVALID_ARGUMENT;
+  const char* who = "dyn_aligner_site_summary_merge";
+  // refused before the device is looked at: the same text on a handle without one
+  if ((level == nullptr) != (dwell == nullptr)) return fail(a, who, "level and dwell counters are given together or not at all");
+  if (count && (!site || !cells)) return DYN_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (int rc = level ? site_histogram_quiet(a, who, 0, 0) : site_summary_quiet(a, who)) return rc;
+  if (count == 0 && !totals) return DYN_OK;  // nothing to add touches nothing
+  SiteTable& t = a->site;
+  for (uint64_t i = 0; i < count; ++i)  // refused before anything is added
+    if (offset >= t.num_sites || site[i] >= t.num_sites - offset)
+      return fail(a, who, "record " + std::to_string(i) + ": id " + std::to_string(site[i]) + " + offset " + std::to_string(offset) +
+                              " is not below the table's " + std::to_string(t.num_sites) + " sites");
+  const uint64_t F = (uint64_t)dynk::SS_FIELDS;
+  const uint64_t B = (uint64_t)t.bins + 2, D = (uint64_t)dynk::SH_DWELL_BINS, H = level ? B + D : 0;
+  const Windows win(0, count);  // (of records, not of ids)
+  if (count) HIP_TRY(a, t.merge.ensure(win.most * (F * sizeof(uint64_t) + H * sizeof(uint32_t) + sizeof(uint32_t))));
+  std::vector<uint32_t> hh(H * win.most);
+  dynk::SiteMerge sm{};
+  sm.keys = t.sparse() ? t.keys.as<uint32_t>() : nullptr;
+  sm.capacity = (uint32_t)t.capacity;
+  sm.totals = t.totals();
+  sm.stats = t.sparse() ? sm.totals + dynk::SS_TOTALS : nullptr;
+  sm.acc = t.table.as<unsigned long long>();
+  sm.hist = level ? t.hist.as<unsigned int>() : nullptr;
+  sm.width = (uint32_t)H;
+  sm.offset = offset;
+  sm.num_sites = t.num_sites;
+  unsigned long long* d_cells = t.merge.as<unsigned long long>();
+  unsigned int* d_counters = reinterpret_cast<unsigned int*>(d_cells + F * win.most);
+  uint32_t* d_site = d_counters + H * win.most;
+  sm.cells = d_cells;
+  sm.counters = d_counters;
+  sm.site = d_site;
+  const unsigned long long* dropped_at = sm.totals + dynk::SS_TOTALS + dynk::SM_SITES_DROPPED;
+  uint64_t dropped_before = 0, dropped = 0;
+  if (t.sparse()) HIP_TRY(a, copy_out(a, &dropped_before, dropped_at, sizeof(uint64_t)));
+  if (count == 0) {  // the totals alone (a rank that covered no site still counted its reads): one launch without records
+    sm.add_totals = 1;
+    for (int f = 0; f < dynk::SS_TOTALS; ++f) sm.totals_in[f] = totals[f];
+    dynk::launch_site_merge(sm, a->s_get);
+    HIP_TRY(a, hipGetLastError());
+    HIP_TRY(a, hipStreamSynchronize(a->s_get));
+    return DYN_OK;
+  }
+  for (auto [r0, cnt, o] : win) {
+    HIP_TRY(a, hipMemcpyAsync(d_cells, cells + F * r0, F * cnt * sizeof(uint64_t), hipMemcpyHostToDevice, a->s_get));
+    HIP_TRY(a, hipMemcpyAsync(d_site, site + r0, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, a->s_get));
+    if (level) {
+      for (uint64_t c = 0; c < cnt; ++c) {
+        std::memcpy(hh.data() + H * c, level + B * (r0 + c), B * sizeof(uint32_t));
+        std::memcpy(hh.data() + H * c + B, dwell + D * (r0 + c), D * sizeof(uint32_t));
+      }
+      HIP_TRY(a, hipMemcpyAsync(d_counters, hh.data(), H * cnt * sizeof(uint32_t), hipMemcpyHostToDevice, a->s_get));
+    }
+    sm.count = (uint32_t)cnt;
+    sm.add_totals = (totals && r0 == 0) ? 1 : 0;  // the caller's totals once, with the first chunk
+    for (int f = 0; f < dynk::SS_TOTALS; ++f) sm.totals_in[f] = sm.add_totals ? totals[f] : 0ull;
+    dynk::launch_site_merge(sm, a->s_get);
+    HIP_TRY(a, hipGetLastError());
+    HIP_TRY(a, hipStreamSynchronize(a->s_get));  // (the host vector is filled again for the next chunk)
   }
   if (t.sparse()) HIP_TRY(a, copy_out(a, &dropped, dropped_at, sizeof(uint64_t)));
   if (dropped > dropped_before)

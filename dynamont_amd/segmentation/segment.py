@@ -154,6 +154,15 @@ def parse(argv=None) -> Namespace:
                    help="with --site-summary FILE: also save the run's per-site table (and, with --site-histogram, its histograms) "
                         "as exact integers once the pipeline is dry: the covered sites as sparse columns in an .npz, for a later "
                         "run's --site-control")
+    p.add_argument("--site-merge-ranks", action="store_true",
+                   help="with --site-summary FILE under torch.distributed.run: every rank fills a per-site table of its own (with "
+                        "--site-capacity: a sparse one of that capacity each); once the pipeline is dry the ranks pack the covered "
+                        "positions on their GPUs, the records travel to rank 0, which adds them into its table by key (exact integers: "
+                        "the same bits for any number of ranks) and writes every per-site output. In one process it does nothing")
+    p.add_argument("--site-table-in", action="append", default=[], metavar="TABLE.npz",
+                   help="with --site-summary FILE: add a table an earlier run saved with --site-table-out (the same references, the "
+                        "same histogram bins and range) into this run's table before the first batch, totals included: several "
+                        "flow cells of one sample add up. Repeatable")
     p.add_argument("--site-control", default="", metavar="TABLE.npz",
                    help="with --site-summary FILE and --site-histogram: compare the run, per reference position, against the table a "
                         "control run saved with --site-table-out (the same references, the same histogram bins and range, bit for "
@@ -987,7 +996,8 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             guide_auto: int = 0, guide_rounds: int = 8, guide_rescue: int = 0, guide_rescue_margin: int = 1,
             posterior_samples: int = 0, sample_seed: int = 0, border_interval: float = 0.0,
             soft_levels: bool = False, site_summary: str = "", site_histogram: str = "", site_table_out: str = "",
-            site_control: str = "", site_mixture: int = 0, site_capacity: int = 0, site_model_out: str = "", site_model: str = "") -> None:
+            site_control: str = "", site_mixture: int = 0, site_capacity: int = 0, site_model_out: str = "", site_model: str = "",
+            site_merge_ranks: bool = False, site_table_in=()) -> None:
     """Counterpart of segment.py:261-371. Under ``torch.distributed.run`` every rank drives one GPU
     on the reads ``index % world == rank``, formats and compresses its rows into a part of the output
     frame, and the parts' bytes are gathered to rank 0, which owns the file (reads are independent;
@@ -1029,17 +1039,23 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
         raise ValueError("--site-model-out saves the fitted per-site mixtures: it needs --site-mixture")
     if site_model and not site_summary:
         raise ValueError("--site-model scores every row against its position's model beside the per-site table: it needs --site-summary FILE")
+    if site_merge_ranks and not site_summary:
+        raise ValueError("--site-merge-ranks adds the ranks' per-site tables: it needs --site-summary FILE")
+    if site_table_in and not site_summary:
+        raise ValueError("--site-table-in adds a saved per-site table into the run's: it needs --site-summary FILE")
     LAST_RUN.pop("site_rows_dropped", None)
     LAST_RUN.pop("site_model_dropped", None)
     site_refs = None
     control_table = None
     loaded_model = None
+    tables_in = []
     if site_summary:
         # refused before anything is started: what the per-site table cannot do yet, and a BAM that is not mapped
         from dynamont_amd.bam_io import bam_references
         from dynamont_amd.sites import DYN_SITE_NONE, contig_offsets
-        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
-            raise ValueError("--site-summary runs in one process: merging the per-site tables of several ranks is not built yet")
+        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1 and not site_merge_ranks:
+            raise ValueError("--site-summary runs in one process: merging the per-site tables of several ranks is not built yet "
+                             "without --site-merge-ranks, which has every rank fill a table of its own and rank 0 add them")
         if host_preprocess or ZSTD_PARALLEL_FRAMES or not _native_bam(basecalls):
             raise ValueError("--site-summary needs the basecalls as a mapped .bam read by the native reader (not with "
                              "--host-preprocess, --parallel-zstd-frames or DYN_PY_BAM=1)")
@@ -1053,6 +1069,11 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
             # refused before anything is started: a model fitted over other references
             from dynamont_amd.segmentation.utils import load_site_model
             loaded_model = load_site_model(site_model, names, lengths)
+        for path in site_table_in:
+            # refused before anything is started: a saved table of other references, or whose histograms are not the run's
+            from dynamont_amd.segmentation.utils import check_site_control, load_site_table
+            tables_in.append((path, load_site_table(path)))
+            check_site_control(tables_in[-1][1], path, names, lengths, site_hist, flag="--site-table-in")
         if site_control:
             # refused before anything is started: a control of other references, without histograms or of other bins
             from dynamont_amd.segmentation.utils import check_site_control, load_site_table
@@ -1131,12 +1152,90 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
 
     site_counts = [0, 0]  # --site-summary: reads handed to the aligner, reads of those left without ids
 
+    def merge_rank_tables(aligner, num_sites):
+        # --site-merge-ranks, with the pipeline dry. Every rank > 0 packs the covered sites of its run's half [0, N) on its GPU
+        # (Aligner.site_table_pack: only they cross to the host). The records travel to rank 0 rank by rank, as _gather_parts sends
+        # the parts of the frame: in every round ONE rank sends a piece of at most 64 MB, header included -- header [n, first,
+        # totals[5]] u64, cells [n][7] u64, site [n] u32, level [n][bins + 2] u32, dwell [n][16] u32 -- and rank 0 adds it by key
+        # (Aligner.site_summary_merge) before the next round: rank 0 never holds more than one piece. The totals ride on a rank's
+        # first piece (a rank without a covered site sends that piece with n = 0: the merge then adds the totals alone). Integers,
+        # so the table is the same bits whatever the number of ranks and the order. An exception on any rank ends the whole job
+        # (parallel.abort_on_error around segment()'s body). Returns (rows the ranks' own tables dropped, RECORDS the merge found
+        # no bucket for -- a record is one rank's sums for one position), the same on every rank.
+        t_start = _time.perf_counter()
+        B = (aligner._site_histogram[0] + 2) if aligner._site_histogram else 0
+        record = 56 + 4 + 4 * (B + 16 if B else 0)
+        per_chunk = max(1, ((64 << 20) - 56) // record)
+        mine = aligner.site_table_pack(0, num_sites) if rank != 0 else None
+        t_pack = _time.perf_counter() - t_start
+        n_mine = int(mine["site"].size) if mine is not None else 0
+        own_dropped = aligner.site_map()["rows_dropped"] if site_capacity else 0
+        edges = aligner.site_histogram(0, 0)["edges"] if B and rank == 0 else None
+        merge_dropped = n_records = 0
+        for src in range(1, world):
+            sent = 0
+            while True:
+                payload = b""
+                if rank == src:
+                    a, b = sent, min(sent + per_chunk, n_mine)
+                    head = np.array([b - a, 1 if a == 0 else 0] + [int(mine["totals"][k]) for k in mine["totals"]], dtype=np.uint64)
+                    parts = [head, np.stack([c[a:b] for c in mine["limbs"]], axis=1) if b > a else np.zeros((0, 7), dtype=np.uint64),
+                             mine["site"][a:b].astype(np.uint32)]
+                    if B:
+                        parts += [mine["level"][a:b], mine["dwell"][a:b]]
+                    payload = b"".join(np.ascontiguousarray(p).tobytes() for p in parts)
+                    sent = b
+                blobs = parallel.gather_bytes(comm, payload)
+                if rank == 0 and blobs[src]:
+                    blob = blobs[src]
+                    head = np.frombuffer(blob, dtype=np.uint64, count=7)
+                    n = int(head[0])
+                    at = 56
+                    cells = np.frombuffer(blob, dtype=np.uint64, count=7 * n, offset=at).reshape(n, 7)
+                    at += 56 * n
+                    packed = {"site": np.frombuffer(blob, dtype=np.uint32, count=n, offset=at), "limbs": [cells[:, f] for f in range(7)],
+                              "totals": [int(v) for v in head[2:7]] if int(head[1]) else None}
+                    at += 4 * n
+                    if B:
+                        packed["level"] = np.frombuffer(blob, dtype=np.uint32, count=B * n, offset=at).reshape(n, B)
+                        at += 4 * B * n
+                        packed["dwell"] = np.frombuffer(blob, dtype=np.uint32, count=16 * n, offset=at).reshape(n, 16)
+                        packed["edges"] = edges
+                    n_records += n
+                    before = aligner.site_map()["sites_dropped"] if site_capacity else 0
+                    try:
+                        aligner.site_summary_merge(packed)
+                    except MemoryError:  # (a full sparse table: the records without a bucket are counted, the others were added)
+                        merge_dropped += aligner.site_map()["sites_dropped"] - before
+                if not parallel.any_rank(comm, rank == src and sent < n_mine):
+                    break
+        counts = np.array(site_counts + [own_dropped], dtype=np.uint64)
+        blobs = parallel.gather_bytes(comm, counts.tobytes())
+        total = np.zeros(4, dtype=np.uint64)
+        if rank == 0:
+            for blob in blobs:
+                total[:3] += np.frombuffer(blob, dtype=np.uint64, count=3)
+            total[3] = merge_dropped
+            site_counts[0], site_counts[1] = int(total[0]), int(total[1])
+            print(f"site tables merged: {n_records} records of {world - 1} ranks ({n_records * record} bytes) in "
+                  f"{_time.perf_counter() - t_start - t_pack:.3f} s (exchange and merge; a rank's own pack before it: {t_pack:.3f} s on rank 0's clock)",
+                  file=sys.stderr, flush=True)
+        dropped = parallel.broadcast_str(comm, "%d %d" % (int(total[2]), int(total[3]))).split()
+        return int(dropped[0]), int(dropped[1])
+
     def write_sites(aligner):
         # --site-summary, with the pipeline dry: the sites with coverage, a window of the table at a time
         if not site_summary:
             return
         from dynamont_amd.segmentation.utils import SITE_QUANTILE_PROBS, write_site_summary
         num_sites = int(site_refs[1][-1])
+        ranks_dropped = merge_dropped = 0
+        if comm is not None:
+            # --site-merge-ranks: every rank's covered sites, packed on its GPU, into rank 0's table by key; rank 0 writes
+            ranks_dropped, merge_dropped = merge_rank_tables(aligner, num_sites)
+            LAST_RUN["site_rows_dropped"] = ranks_dropped + merge_dropped  # (every rank: the job ends with one exit status)
+            if rank != 0:
+                return
         # --site-histogram: the three quantile columns, reduced on the GPU window by window beside the table's window
         quantiles = (lambda lo, hi: aligner.site_quantiles(SITE_QUANTILE_PROBS, lo, hi)) if site_hist else None
         control = None
@@ -1184,6 +1283,9 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
         if site_capacity:
             m = aligner.site_map()
             sparse = f"; sparse table: {m['n_keys']} of {m['capacity']} rows taken, rows_dropped {m['rows_dropped']}"
+            if comm is not None:  # the ranks' dropped rows and the sites the merge found no bucket for, summed
+                m["rows_dropped"] = ranks_dropped + merge_dropped
+                sparse += f" (rows dropped on the ranks {ranks_dropped}, records dropped in the merge {merge_dropped})"
             LAST_RUN["site_rows_dropped"] = m["rows_dropped"]
         print(f"site summary written: {site_summary}: {written} sites with coverage; reads_ok {t['reads_ok']}, rows_added {t['rows_added']}, "
               f"samples_added {t['samples_added']}, rows_without_site {t['rows_without_site']}, rows_skipped {t['rows_skipped']}; "
@@ -1192,6 +1294,9 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
         if site_capacity and m["rows_dropped"]:
             print(f"site summary INCOMPLETE: {m['rows_dropped']} rows of positions that found no row in the full table of {m['capacity']} "
                   f"(rows_skipped counts them too) were dropped; every position in {site_summary} is complete, positions are missing. "
+                  + (f"(Of that count {ranks_dropped} are rows the ranks' own tables dropped and {merge_dropped} are RECORDS -- one rank's sums "
+                     f"for one position -- that found no row in rank 0's table in the merge.) " if comm is not None else "")
+                  + ("(A position that one rank dropped and another rank kept holds the other ranks' rows only.) " if ranks_dropped else "") +
                   f"Run again with a larger --site-capacity (exit status 3)", file=sys.stderr, flush=True)
 
     def write_band_report(lines):
@@ -1267,7 +1372,10 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                         raise MemoryError(f"--site-histogram: the counters of {int(site_refs[1][-1])} sites ({4 * (bins + 18)} bytes each) "
                                           f"do not fit: {error}") from None
                     print(f"site histogram: {bins} bins over [{h_lo!r}, {h_hi!r})", file=sys.stderr, flush=True)
-                    if control_table is not None:
+                    for path, table in tables_in:  # (a range left to the model table is known only now)
+                        from dynamont_amd.segmentation.utils import check_site_control
+                        check_site_control(table, path, site_refs[0], table["ref_lengths"], (bins, h_lo, h_hi), flag="--site-table-in")
+                    if control_table is not None and rank == 0:  # (--site-merge-ranks: rank 0 writes; a control is counted once)
                         # before the first batch: the control into [N, 2N). (A range left to the model table is known only now.)
                         from dynamont_amd.segmentation.utils import check_site_control, load_site_control
                         check_site_control(control_table, site_control, site_refs[0], control_table["ref_lengths"], (bins, h_lo, h_hi))
@@ -1281,6 +1389,17 @@ def segment(data_path: str, basecalls: str, processes: int, outfile: str, model_
                             raise MemoryError(f"--site-capacity {site_capacity}: the control {site_control} does not fit the sparse table "
                                               f"beside the run ({error}); run again with a larger --site-capacity") from None
                         print(f"site control: {site_control}: {added} sites with coverage loaded", file=sys.stderr, flush=True)
+            for path, table in tables_in if rank == 0 else []:
+                # --site-table-in: into the run's half before the first batch, by key, totals included; on rank 0 only -- a saved
+                # table is counted once
+                from dynamont_amd.segmentation.utils import merge_site_table
+                try:
+                    added = merge_site_table(aligner, table, 0, totals=True)
+                except MemoryError as error:
+                    # a table that is only partly in would be reported as if it were whole: the run ends here
+                    raise MemoryError(f"--site-capacity {site_capacity}: the table {path} does not fit the sparse table ({error}); "
+                                      f"run again with a larger --site-capacity") from None
+                print(f"site table in: {path}: {added} sites with coverage added", file=sys.stderr, flush=True)
             if loaded_model is not None:
                 # --site-model: onto the GPU before the first ticket, beside the table; every ticket from here on is scored
                 from dynamont_amd.segmentation.utils import upload_site_model
@@ -1458,7 +1577,7 @@ def main(argv=None) -> None:
             border_interval=args.border_interval, soft_levels=args.soft_levels, site_summary=args.site_summary, site_table_out=args.site_table_out,
             site_control=args.site_control, site_mixture=args.site_mixture,
             site_histogram=args.site_histogram, site_capacity=args.site_capacity, site_model_out=args.site_model_out,
-            site_model=args.site_model)
+            site_model=args.site_model, site_merge_ranks=args.site_merge_ranks, site_table_in=tuple(args.site_table_in))
     _stamp("segment() returned (aligner closed)")
     # --site-capacity: rows were dropped from a full table -- everything is written, the status says that sites are missing
     status = 3 if LAST_RUN.get("site_rows_dropped") else 0

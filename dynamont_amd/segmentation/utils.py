@@ -468,16 +468,21 @@ def ks_two_sample_p(d: float, n_a: int, n_b: int) -> float:
     return min(1.0, max(0.0, 2.0 * total))
 
 
-def save_site_table(path: str, aligner, ref_names, ref_lengths, lo: int = 0, hi=None, window: int = 1 << 20, windows=None) -> int:
+def save_site_table(path: str, aligner, ref_names, ref_lengths, lo: int = 0, hi=None, window: int = 1 << 20, windows=None,
+                    packed: bool = False) -> int:
     """The covered sites of the window [lo, hi) (default: one sample, the references' total length) of ``aligner``'s per-site table
     as an .npz (numpy only): ``site`` uint64 (relative to ``lo``), the seven limb columns, ``level`` / ``dwell`` counters when the
     handle has histograms, ``hist_spec`` = (bins, lo, hi) with the bounds as float64 BITS (uint64; bins 0 = no histograms),
     ``ref_names``, ``ref_lengths``, ``totals`` and ``version``. Fetched window by window: nothing genome-sized is on the host at
     once. ``windows`` (a sparse table: Aligner.site_map_windows at log2(window)): the indices w of the id windows [w * window,
-    (w + 1) * window) that hold a site, the only ones fetched then; the file is the same. Returns the sites saved."""
+    (w + 1) * window) that hold a site, the only ones fetched then; the file is the same. ``packed``: the covered sites come
+    through ``Aligner.site_table_pack`` -- compacted on the GPU, only they cross to the host -- instead of windows of the whole id
+    range; the file is the same. Returns the sites saved."""
     lengths = np.asarray(ref_lengths, dtype=np.uint64)
     hi = int(lo) + int(lengths.sum()) if hi is None else int(hi)
-    if windows is None:
+    if packed:
+        spans = []
+    elif windows is None:
         spans = [(w0, min(w0 + int(window), hi)) for w0 in range(int(lo), hi, int(window))]
     else:
         spans = [(max(int(lo), int(w) * int(window)), min(hi, (int(w) + 1) * int(window))) for w in sorted(windows)]
@@ -496,6 +501,16 @@ def save_site_table(path: str, aligner, ref_names, ref_lengths, lo: int = 0, hi=
             h = aligner.site_histogram(w0, w1)
             level.append(h["level"][idx])
             dwell.append(h["dwell"][idx])
+    if packed:
+        t = aligner.site_table_pack(int(lo), hi)
+        totals = t["totals"]
+        idx = np.flatnonzero(t["n_rows"])      # (a live row has a non-zero word; the file keeps the covered ones, as the windows do)
+        sites.append(t["site"][idx])
+        for f in range(7):
+            limbs[f].append(np.asarray(t["limbs"][f], dtype=np.uint64)[idx])
+        if spec:
+            level.append(t["level"][idx])
+            dwell.append(t["dwell"][idx])
     if totals is None:
         totals = aligner.site_summary(int(lo), int(lo))["totals"]
     from dynamont_amd._dynamont import SITE_SUMMARY_TOTALS
@@ -540,22 +555,26 @@ def load_site_table(path: str) -> dict:
                 "totals": dict(zip(SITE_SUMMARY_TOTALS, [int(v) for v in z["totals"].tolist()]))}
 
 
-def check_site_control(table: dict, path: str, ref_names, ref_lengths, hist_spec) -> None:
+def check_site_control(table: dict, path: str, ref_names, ref_lengths, hist_spec, flag: str = "--site-control") -> None:
     """--site-control: refuses, each with its own message, a saved table whose references differ from the BAM header's in name or
     length, one without histograms, and one whose hist_spec is not bit-equal to the run's ``hist_spec`` = (bins, lo, hi); a bound
-    of None (the range left to the model table) is compared once the run knows it."""
+    of None (the range left to the model table) is compared once the run knows it. ``flag`` names the option in the messages
+    (--site-table-in checks its files the same way); ``hist_spec`` None: the run has no histograms and takes the table alone
+    (--site-table-in only: a control always has them)."""
     names, lengths = [str(n) for n in ref_names], [int(v) for v in ref_lengths]
     if table["ref_names"] != names:
-        raise ValueError(f"--site-control {path}: its reference names differ from the BAM header's")
+        raise ValueError(f"{flag} {path}: its reference names differ from the BAM header's")
     if [int(v) for v in table["ref_lengths"].tolist()] != lengths:
-        raise ValueError(f"--site-control {path}: its reference lengths differ from the BAM header's")
+        raise ValueError(f"{flag} {path}: its reference lengths differ from the BAM header's")
+    if hist_spec is None:
+        return
     if table["hist_spec"] is None:
-        raise ValueError(f"--site-control {path}: the file holds no histograms (it was saved by a run without --site-histogram)")
+        raise ValueError(f"{flag} {path}: the file holds no histograms (it was saved by a run without --site-histogram)")
     bins, lo, hi = hist_spec
     mine = [int(bins)] + [None if v is None else int(np.array([v], dtype=np.float64).view(np.uint64)[0]) for v in (lo, hi)]
     theirs = [int(v) for v in table["hist_bits"].tolist()]
     if any(m is not None and m != t for m, t in zip(mine, theirs)):
-        raise ValueError(f"--site-control {path}: its histograms ({table['hist_spec'][0]} bins over [{table['hist_spec'][1]!r}, "
+        raise ValueError(f"{flag} {path}: its histograms ({table['hist_spec'][0]} bins over [{table['hist_spec'][1]!r}, "
                          f"{table['hist_spec'][2]!r})) are not the run's ({bins} bins over [{lo!r}, {hi!r})), bit for bit")
 
 
@@ -673,6 +692,21 @@ def load_site_control(aligner, table: dict, offset: int, window: int = 1 << 20) 
             hist["dwell"][rel] = table["dwell"][a:b]
         aligner.site_summary_add(int(offset) + w0, cols, hist)
     return int(site.size)
+
+
+def merge_site_table(aligner, table: dict, offset: int = 0, totals: bool = False) -> int:
+    """adds a loaded table (``load_site_table``) into ``aligner``'s table and histograms BY KEY (``Aligner.site_summary_merge``):
+    site s of the file into the site ``offset + s``, only the file's covered sites cross to the device, however they are
+    scattered over the id space. ``totals``: the file's five totals are added too (several flow cells of one sample add up); the
+    default leaves the handle's totals the run's own, as ``load_site_control`` does. Returns the covered sites added."""
+    spec = getattr(aligner, "_site_histogram", None)
+    packed = {"site": table["site"], "limbs": table["limbs"], "totals": table["totals"] if totals else None}
+    if table["hist_spec"] and spec:
+        packed["level"], packed["dwell"] = table["level"], table["dwell"]
+        b, h_lo, h_hi = table["hist_spec"]
+        packed["edges"] = h_lo + np.arange(b + 1, dtype=np.float64) * ((h_hi - h_lo) / b)
+    aligner.site_summary_merge(packed, int(offset))
+    return int(np.asarray(table["site"]).size)
 
 
 def site_control_columns(compare: dict, run: dict, control: dict) -> list:

@@ -684,6 +684,37 @@ int dyn_aligner_site_summary_add(dyn_aligner* a, uint64_t lo, uint64_t hi,
     const uint64_t* m1_lo, const uint64_t* m1_hi, const uint64_t* m2_lo, const uint64_t* m2_hi,
     const uint64_t totals[5],           /* may be NULL: adds none */
     const uint32_t* level, const uint32_t* dwell);   /* both NULL: the table alone; else [n][bins+2] and [n][16] */
+/* (added within ABI 10) THE TABLE BY CONTENT. dyn_aligner_site_pack returns the LIVE rows among the
+ * table rows [row_lo, row_hi) -- the ids of a dense table, the buckets [0, capacity) of a sparse one -- as records, compacted on
+ * the device so that only the records cross to the host:
+ *   site[i]      the row's id (dense: the row; sparse: the bucket's key)
+ *   cells[i][7]  n_rows, n_samples, dwell_sq, m1_lo, m1_hi, m2_lo, m2_hi
+ *   level[i][bins + 2], dwell[i][16]   the row's counters, when both are given (both or neither)
+ * A row is live iff its id lies in [site_lo, site_hi) and any of its 7 cell words or -- when the counters are asked for -- of its
+ * bins + 2 + 16 counters is non-zero; a key alone (dyn_aligner_set_site_model inserts such keys) makes no row live. The records
+ * stand in ascending row order (so ascending id for a dense table) and are the same bytes every time for a given table. *count
+ * gets the number of live rows whatever cap is; cap < *count copies NOTHING and is DYN_ERR_INVALID_ARGUMENT (call again with
+ * *count). The conditions of dyn_aligner_site_summary_fetch (completed jobs; dyn_aligner_site_histogram_fetch's when counters are
+ * asked for) -- and the tickets in flight when the call is made are waited for first: the records are the table behind every
+ * job submitted before the call. row_hi above the table's rows, or [site_lo, site_hi) no range of the table's ids:
+ * DYN_ERR_INVALID_ARGUMENT. An empty range of rows or of ids is DYN_OK with *count = 0 and touches nothing, the device
+ * included; row_lo > row_hi or site_lo > site_hi is refused before the device is looked at. The rows are walked 2^20 at a time.
+ * dyn_aligner_site_summary_merge adds `count` such records into the table BY KEY: record i into the row of the id
+ * site[i] + offset (dense: that row; sparse: found or inserted as dyn_aligner_site_summary_add does). It adds what
+ * dyn_aligner_site_summary_add adds, by the same device-scope atomics; the same id may appear any number of times in one call
+ * (the records of several ranks concatenated), an all-zero record adds nothing and inserts no key, `totals` (may be NULL) is added
+ * once. Every site[i] + offset must be below num_sites: otherwise DYN_ERR_INVALID_ARGUMENT, with the record's index in the text,
+ * before anything is added. Records whose id finds no bucket in a sparse table are dropped whole and counted in sites_dropped;
+ * the call then returns DYN_ERR_OUT_OF_MEMORY with their number in the text -- the other records were added. sites_dropped counts
+ * RECORDS here: an id without a bucket that three records name counts three times. count = 0 adds the totals alone (totals
+ * NULL: touches nothing). The sum of tables is the same bits whatever the order of the records or of the calls. */
+int dyn_aligner_site_pack(dyn_aligner* a, uint64_t row_lo, uint64_t row_hi, uint64_t site_lo, uint64_t site_hi, uint64_t cap,
+    uint32_t* site, uint64_t* cells,     /* [cap], [cap][7] */
+    uint32_t* level, uint32_t* dwell,    /* both NULL: the table alone; else [cap][bins+2] and [cap][16] */
+    uint64_t* count);
+int dyn_aligner_site_summary_merge(dyn_aligner* a, uint64_t count, const uint32_t* site, uint64_t offset, const uint64_t* cells,
+    const uint64_t totals[5],           /* may be NULL: adds none */
+    const uint32_t* level, const uint32_t* dwell);   /* both NULL: the table alone; else [count][bins+2] and [count][16] */
 /* Compares the sites [site_lo, site_hi) with the sites starting at other_lo, pair by pair, on the device: the histograms never
  * cross to the host. Pair i: A = site_lo + i, B = other_lo + i; a[e], b[e] their Bc = bins + 2 level counters, PA[e], PB[e] the
  * inclusive prefix sums (uint32: fewer than 2^32 rows per site is the defined domain), nA = PA[Bc - 1], nB = PB[Bc - 1]. Per counter

@@ -49,6 +49,9 @@ void launch_site_mixture(const SiteMixture&, hipStream_t) { no_device("launch_si
 void launch_site_gather(const SiteGather&, hipStream_t) { no_device("launch_site_gather"); }
 void launch_site_scatter_add(const SiteScatter&, hipStream_t) { no_device("launch_site_scatter_add"); }
 void launch_site_map_windows(const SiteWindows&, hipStream_t) { no_device("launch_site_map_windows"); }
+void launch_site_pack(const SitePack&, hipStream_t) { no_device("launch_site_pack"); }
+void launch_site_pack_write(const SitePack&, hipStream_t) { no_device("launch_site_pack_write"); }
+void launch_site_merge(const SiteMerge&, hipStream_t) { no_device("launch_site_merge"); }
 void launch_rescale_init(RescaleState*, uint64_t, hipStream_t) { no_device("launch_rescale_init"); }
 void launch_rescale_pass(const ReadDesc*, int, uint32_t, const ReadState*, const TraceBuffers&, const double*, double*, const Emis*, double*,
                          RescaleState*, hipStream_t) {
